@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the denoise-and-drag hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one complete drag edit of one shape (BASELINE.json config 3 / SURVEY.md 8(d) "C3"):
@@ -11,7 +11,8 @@ guided DDPM update, drag_utils.py:336-398) followed by the 256^3 occupancy decod
 The untimed set-up per rank (update_latent_params: 200 DDPM steps that also record the 40 guidance
 features) is reported as `unet_steps_per_s`.  Ranks edit independent shapes (weak scaling); the only
 collective is the final gather of the occupancy volumes to rank 0 (RCCL), inside the timed region.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR: rank 0 also writes what the last timed step computed as
+DIR/<name>.npy (float32; see dump_outputs), so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -30,6 +31,9 @@ GUIDED_STEPS = 40          # w_time of config 3
 NUM_STEPS = 200
 HANDLES = 3
 RES = 256
+DUMP_VOLUME_SAMPLES = 1 << 22     # voxels of a 256^3 volume kept by --dump-outputs (16 MB; the whole volume is 64 MiB)
+DUMP_SAMPLE_SEED = 0
+RNG_SEED = 20240      # + rank: torch's default generators (the step kernels' noise is keyed by the device's) and NumPy's global one
 UNET_FWD_GFLOP = 634.9
 GUIDED_GFLOP = 977.8
 PEAK_MFMA_F16_TFLOPS = 2500.0   # dense, MI355X_MICROARCH.md
@@ -51,6 +55,35 @@ def one_edit(ds, src, tgt):
     for _ in ds.training(src, tgt, scale=1200, cof=0.4):      # GUI defaults main.py:102,105
         pass
     return ds.volume
+
+
+def volume_sample_index(n):
+    """The --dump-outputs voxel sample: n distinct flat indices into a RES^3 volume, sorted, drawn from a fixed seed (the same
+    on every run and every build)."""
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(RES ** 3, size=n, replace=False))
+
+
+def dump_outputs(out_dir, ds, world, gathered=None):
+    """What the last timed edit handed its caller, as float32 DIR/<name>.npy (about 23 MB in all):
+      volume_sample    the 256^3 occupancy-logit volume one_edit returns, at the voxels volume_sample_index(DUMP_VOLUME_SAMPLES // N)
+      latent           the edited latent that volume was decoded from, 1x96x128x128 (DragStuff.tri_feat)
+      drag_losses      the drag loss of each of the 40 guided iterations, in the order they ran (DragStuff.last_losses)
+      gathered_volume_sample_rank<r>   N > 1: the same voxels of rank r's volume as the gather delivered it to rank 0 (r >= 1)"""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = torch.from_numpy(volume_sample_index(DUMP_VOLUME_SAMPLES // world))
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+    def sample(vol):
+        assert tuple(vol.shape) == (RES, RES, RES), vol.shape      # the indices were drawn for a RES^3 volume
+        return vol.reshape(-1)[idx.to(vol.device)]
+    save("volume_sample", sample(ds.volume))
+    save("latent", ds.tri_feat)
+    save("drag_losses", torch.cat(ds.last_losses))
+    for r, v in enumerate(gathered or []):
+        if r > 0:
+            save(f"gathered_volume_sample_rank{r}", sample(v))
 
 
 def _cpu_info():
@@ -413,7 +446,11 @@ def main():
                          "the multi-rank control flow (spawn, rendezvous, barriers, gather, per-rank report), NOT a measurement")
     ap.add_argument("--c4-shape-profile", default=None, help="write the per-shape conv/GEMM CSV of the reconstruction step here")
     ap.add_argument("--shape-profile", default=None, help="write the per-shape conv/GEMM timing CSV of one edit here")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (volume sample, latent, drag losses) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -423,6 +460,10 @@ def main():
     import torch.distributed as dist
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
+    # torch seeds its default CPU and device generators from OS entropy in every process; the step kernels draw their noise from
+    # Philox keyed by the device generator's seed (gaussian_diffusion._draw), so without this every run would edit other inputs
+    torch.manual_seed(RNG_SEED + rank)
+    np.random.seed(RNG_SEED + rank)
     comm_dev = device                                          # where collective operands live: the GPU under RCCL
     if world > 1:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -491,6 +532,8 @@ def main():
                 for r, v in enumerate(per_rank)]
     print(f"[bench] rank {rank}: edit {per_rank[rank]['edit_ms']} ms, gather call {per_rank[rank]['gather_ms']} ms per step "
           f"(stream time; rank 0's gather includes waiting for the slowest rank)", file=sys.stderr, flush=True)
+    if a.dump_outputs and rank == 0:             # before the roofline leg's extra edit replaces the last timed step's results
+        dump_outputs(a.dump_outputs, ds, world, recv)
 
     # ---- roofline leg: the same edit once more with HIP events around every implicit-GEMM launch ----
     roofline = small_maps = step_breakdown = None

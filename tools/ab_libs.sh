@@ -2,7 +2,7 @@
 # Same-box A/B of library builds: tools/ab_libs.sh build/lib_A.so build/lib_B.so ...  (two alternating rounds of the
 # un-profiled bench, then one kernel trace per build: kernel time per guided step and the per-symbol lines matching $AB_GREP).
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/ab
 mkdir -p $O
 cd $R

@@ -1,7 +1,7 @@
 #!/bin/bash
 # un-profiled s/shape for a list of environment settings, two alternating rounds on one box:  tools/env_ab.sh "A=1" "A=2 B=3" ...
 # (AB_ROUNDS sets the number of rounds; a failing run prints the tail of its stderr instead of a number)
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for round in $(seq 1 ${AB_ROUNDS:-2}); do
   for cfg in "$@"; do

@@ -2,7 +2,7 @@
 # per-symbol kernel time of one guided step for a list of environment settings, plain launch sequence, one box:
 #   AB_GREP="gn_" tools/env_trace_ab.sh "ISHAP_GN_XCD=0" "ISHAP_GN_XCD=1"    -> gpurun_out/env_trace/<setting>.txt
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/env_trace
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel trace of the generate path (C2, forward-only steps): per-kernel table of a 60-step sample at batch 1 and 8 -> gpurun_out/c2trace/
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/c2trace
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

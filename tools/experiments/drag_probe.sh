@@ -1,6 +1,6 @@
 #!/bin/bash
 # sweep the grid caps of the drag-loss launches (bench wall + per-kernel averages from a short trace)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for cfg in "1024 512" "1024 1024"; do
   set -- $cfg

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Fixed vs per-K-step cost of the tiled conv kernel on the large maps: same map, growing Cin, statistics epilogue on/off.
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 for H in 128 64 32; do
   for cin in 64 128 256 512 1024; do
     for st in 0 1; do

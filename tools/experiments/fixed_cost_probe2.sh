@@ -1,5 +1,5 @@
 #!/bin/bash
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 BI_EMPTY=0 ./build/bi2 128 64 256 1 1 2 3 0 4 | grep empty
 BI_EMPTY=131072 ./build/bi2 128 64 256 1 1 2 3 0 4 | grep empty
 for b in bi2 bi2DABL_NOLOAD bi2DABL_NOMFMA bi2DABL_NOEPI bi2DABL_NOLOADDABL_NOEPI; do

@@ -1,6 +1,6 @@
 #!/bin/bash
 # grid cap of the big-map GroupNorm apply kernel: per-kernel averages from a short trace
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for cap in 1024 512 256 2048; do
   export ISHAP_GN_APPLY_BLOCKS=$cap

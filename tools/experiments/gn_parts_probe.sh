@@ -1,6 +1,6 @@
 #!/bin/bash
 # group-local GroupNorm: workgroups ("parts") per (image, group) -- total kernel time of the local GN kernels per setting
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for cfg in "8 256 256" "16 256 512" "16 512 512" "16 128 512" "8 128 256"; do
   set -- $cfg

@@ -1,6 +1,6 @@
 #!/bin/bash
 # un-profiled s/shape for group-local GroupNorm partitioning settings (two alternating rounds, same box)
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 for round in 1 2; do
   for cfg in "8 128" "8 256" "8 512" "4 128" "2 128" "8 64"; do
     set -- $cfg

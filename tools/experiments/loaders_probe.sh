@@ -1,6 +1,6 @@
 #!/bin/bash
 # 4 vs 8 loader waves on the 64x64-tile kernel (single team: ISHAP_HALVES=1), harness
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 export ISHAP_HALVES=1
 for b in bi2 bi3DIG2_LOADERS8; do
   for shp in "64 256 256 0 3" "64 512 256 0 3" "32 512 512 0 3" "32 512 512 0 1" "32 1536 512 0 1" "16 768 768 0 1"; do

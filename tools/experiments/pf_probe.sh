@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 4: K-step ablation table + L2 weight-prefetch / ring-depth variants of the LDS-DMA conv kernel (harness builds from
 # tools/experiments/pf_probe_build.sh).  Output: gpurun_out/pf_probe.txt
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 O=gpurun_out/pf_probe.txt
 mkdir -p gpurun_out; : > $O
 run() { # variant, args...

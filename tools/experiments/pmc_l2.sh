@@ -1,7 +1,7 @@
 #!/bin/bash
 # L2 hit-rate counter pass (its own run: --pmc with --kernel-trace only), per kernel symbol: TCC_HIT_sum / TCC_MISS_sum.
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/final
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

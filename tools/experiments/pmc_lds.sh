@@ -1,7 +1,7 @@
 #!/bin/bash
 # LDS-utilisation counter pass (its own run: --pmc with --kernel-trace only), summarised per kernel symbol.
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/final
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 kernel trace of a short bench run -> gpurun_out/<tag>_stats.csv, <tag>_bygrid.txt, <tag>_step.txt
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 TAG=${1:-prof}
 O=$R/gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # small-map 3x3 kernel probes: K slices sweep (z), ablations, tiled kernel for comparison; HBM-cold weights (nbuf copies cycled)
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 for shp in "8 1024 1024 16" "8 2048 1024 8" "16 768 768 24" "16 1792 768 12" "32 512 512 40" "32 768 512 30"; do
   set -- $shp
   nb=$4

@@ -1,6 +1,6 @@
 #!/bin/bash
 # where a small-map 3x3 launch (conv3_small_kernel, 8x8 maps) spends its time: stamps + ablations; output gpurun_out/s3_probe2.txt
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 O=gpurun_out/s3_probe2.txt; : > $O
 for shape in "8 1024 1024 0 4" "8 2048 1024 0 6" "8 1024 2048 0 3" "8 1024 1024 0 2" "8 1024 1024 0 8"; do
   set -- $shape

@@ -1,5 +1,5 @@
 #!/bin/bash
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 for b in bi4 bi4DABL_STAT_COPIES8 bi4DABL_STAT_COPIES32; do
   for st in 0 1; do
     echo -n "$b "; ./build/$b 128 256 256 1 1 2 3 $st 4 | grep gen

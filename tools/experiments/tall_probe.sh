@@ -3,7 +3,7 @@
 # 8 KB of weights + 6.2 KB of activations for twice the FLOPs of the 64x64 tile's 8 + 3.1 KB; with half as many tiles the launch takes
 # twice the K slices to fill the chip (the consumer adds them up).  build/ig_tall = tools/bench_igemm.hip -DIG4_TALL_PROBE.
 # args: H Cin Cout big ksplit gen ksize stats nbuf ; HBM-cold weights (16 rotating copies)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd $R
 run() { echo -n "$1 ks=$3  "; timeout -k 5 60 build/ig_$1 $2 0 $3 6 3 0 16 | tail -1; }
 for shape in "32 512 512" "32 1024 512" "32 768 512" "32 256 512"; do

@@ -6,7 +6,7 @@
 #   hipcc $F tools/bench_igemm.hip -o build/ig_base; hipcc $F -DABL_XFORM tools/bench_igemm.hip -o build/ig_xform
 #   hipcc $F -DABL_XFORM -DABL_XFORM_FILM tools/bench_igemm.hip -o build/ig_xform_film; hipcc $F -DIG_STAMPS tools/bench_igemm.hip -o build/ig_stamps
 # args of the harness: H Cin Cout big ksplit gen ksize stats nbuf
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd $R
 for shape in "128 256 256 1" "128 512 256 1" "64 512 512 0" "64 256 256 0" "64 768 256 0" "32 512 512 0"; do
   for v in base xform xform_film; do

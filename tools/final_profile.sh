@@ -5,7 +5,7 @@
 # trace, counter passes -- runs the PLAIN launch sequence (ISHAP_OVERLAP_TAIL=0): per-kernel durations of two queues sharing the
 # chip are not per-kernel figures, and rocprofv3's queue interception distorts two-queue runs (profiles/round5_overlap_tail_ab.txt).
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/final
 rm -rf $O; mkdir -p $O
 cd $R

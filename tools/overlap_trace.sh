@@ -3,7 +3,7 @@
 #   tools/overlap_trace.sh "ISHAP_TAIL_DEFER_WGS=128" "ISHAP_TAIL_DEFER_WGS=192" ...     (ISHAP_OVERLAP_TAIL=1 is added to every setting)
 # Output: gpurun_out/overlap/{plain,<setting>}.txt
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/overlap
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

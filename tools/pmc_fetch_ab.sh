@@ -2,7 +2,7 @@
 # FETCH_SIZE per kernel symbol for a list of environment settings (one rocprofv3 --pmc pass each, plain launch sequence):
 #   tools/pmc_fetch_ab.sh "ISHAP_IG4_NOUTER=0" "ISHAP_IG4_NOUTER=2"   -> gpurun_out/pmc_ab/<setting>.txt
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/pmc_ab
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

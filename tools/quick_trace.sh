@@ -1,7 +1,7 @@
 #!/bin/bash
 # step timeline + per-grid kernel table + per-shape conv table of the current build (no full bench line): gpurun_out/quick/
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/quick
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
