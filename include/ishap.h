@@ -37,7 +37,8 @@ int ishap_device_status(void);
  * for the stand-alone operator calls) on `stream` would be allowed in-launch rendezvous right now. */
 int ishap_rendezvous_would_grant(const void* owner, void* stream);
 int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the size of its scratch buffer; 3 since ishap_step_coefs
-                            * ends with rng / rng_seed / rng_offset / noise_out */
+                            * ends with rng / rng_seed / rng_offset / noise_out; 4 since the batched drag calls (ishap_drag_batch_*,
+                            * ishap_ddpm_step_guided_scales) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -194,6 +195,13 @@ int ishap_ddpm_step(const float* x, const float* model_out, const float* noise, 
 int ishap_ddpm_step_guided(const float* x, const float* model_out, const float* noise, const float* variance_in,
                            const ishap_step_coefs* k, int N, int C, int HW, const float* grad, float scale,
                            const float* grad_mul_dev, float* guided, float* sample, float* variance, void* stream);
+/* The same with one guidance scale per image (batched drag edits): guided[n] = sample[n] + variance[n] * (scales[n] * grad[n]
+ * [* *grad_mul_dev]); scales = device float[N].  Image n is bitwise what ishap_ddpm_step_guided gives with scale = scales[n]
+ * and the same noise.  Drawn noise (k->rng, noise NULL) spans the whole batch: image n takes the Philox vectors of its own
+ * place in [N][C][HW], a stream of its own but NOT the one a single-image call with the same seed and offset draws. */
+int ishap_ddpm_step_guided_scales(const float* x, const float* model_out, const float* noise, const float* variance_in,
+                                  const ishap_step_coefs* k, int N, int C, int HW, const float* grad, const float* scales,
+                                  const float* grad_mul_dev, float* guided, float* sample, float* variance, void* stream);
 /* img = sample + variance * (scale * grad)   (drag_utils.py:384-392); grad_mul_dev: optional device scalar */
 int ishap_guided_update(const float* sample, const float* variance, const float* grad, float scale,
                         const float* grad_mul_dev, long long numel, float* out, void* stream);
@@ -230,6 +238,38 @@ int ishap_drag_loss_grad(const ishap_drag_args* a, const void* edit_nhwc_f16, co
  * guided step uses (drag_utils.py:355-383 up to loss.backward()) */
 int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
                               float* grad_nhwc, float* loss, void* cot_f16, unsigned* bits, float* scale2, void* stream);
+/* E drag edits in one call, in the launches of one (loss + gradient: terms, gather, finish; + cotangent: terms, gather, scale).
+ * Per edit: its handles (a CSR range of one packed sources / targets array), cof, rounded-texel bitmap, mask count, loss sums
+ * and fixed-point scatter buffer; its tap slice edit + e*W*W*ld and guidance slice orig + e*orig_stride.  Shared: W, ld, Cc,
+ * chmap, r, voxel, l1, and ONE power-of-two loss scale for the whole batch, picked from max|g| over all edits.
+ * Each edit's loss and fp32 gradient are BITWISE those of ishap_drag_loss_grad on that edit alone; its fp16 cotangent is the
+ * solo one times 2^(k_batch - k_solo) (bitwise where both are normal fp16 numbers).  The input-gradient backward is linear in
+ * the cotangent and removes scale2[1] at its end, so a batched backward needs nothing else. */
+typedef struct {
+  int E;                /* edits, 1..32 */
+  int W, ld, Cc;        /* as in ishap_drag_args */
+  const int* chmap;     /* device int[3*Cc] */
+  const float* sources; /* device [handle_offsets[E]][3]: the handles of all edits, edit by edit */
+  const float* targets; /* device, same layout */
+  const int* handle_offsets; /* HOST int[E+1], CSR: edit e owns handles [handle_offsets[e], handle_offsets[e+1]); [0] = 0, each range non-empty */
+  int r;
+  float voxel;
+  const float* cof;     /* HOST float[E] */
+  int l1;
+  long long orig_stride;  /* halfs between the guidance features of consecutive edits; 0 = every edit reads the same one */
+  void* scratch;          /* device, 16-byte aligned, ishap_drag_batch_scratch_bytes(E, W, ld) bytes; zeroed by the setup call,
+                           * left zero by every loss call */
+  long long scratch_bytes;
+} ishap_drag_batch_args;
+long long ishap_drag_batch_scratch_bytes(int E, int W, int ld);
+/* once per batch of edits (ishap_drag_setup for each edit) */
+int ishap_drag_batch_setup(const ishap_drag_batch_args* a, void* stream);
+/* edit_nhwc_f16 [E][W*W][ld] (the resident tap of a batch-E forward); loss device float[E]; grad_nhwc fp32 [E][W*W][ld] */
+int ishap_drag_batch_loss_grad(const ishap_drag_batch_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
+                               float* grad_nhwc, float* loss, void* stream);
+/* the same plus the fp16 cotangent [E][W*W][ld] with the batch's loss scale; bits: device uint32[1]; scale2: device float[2] */
+int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
+                                    float* grad_nhwc, float* loss, void* cot_f16, unsigned* bits, float* scale2, void* stream);
 /* fp32 gradient -> fp16 cotangent times a power-of-two loss scale picked from max|g| on the device;
  * bits: device scratch uint32[1]; scale2: device float[2] = {scale, 1/scale} */
 int ishap_grad_to_scaled_f16(const float* grad, void* out_f16, unsigned* bits, float* scale2, long long numel,

@@ -36,6 +36,13 @@ class DragArgsC(C.Structure):
                 ("l1", C.c_int), ("touched", c_void_p), ("nmask", c_void_p), ("acc", c_void_p), ("grad_fx", c_void_p), ("chan_weight", c_void_p)]
 
 
+class DragBatchArgsC(C.Structure):
+    _fields_ = [("E", C.c_int), ("W", C.c_int), ("ld", C.c_int), ("Cc", C.c_int), ("chmap", c_void_p), ("sources", c_void_p),
+                ("targets", c_void_p), ("handle_offsets", C.POINTER(C.c_int)), ("r", C.c_int), ("voxel", C.c_float),
+                ("cof", C.POINTER(C.c_float)), ("l1", C.c_int), ("orig_stride", C.c_longlong), ("scratch", c_void_p),
+                ("scratch_bytes", C.c_longlong)]
+
+
 class DecoderWeightsC(C.Structure):
     _fields_ = [("B", c_void_p), ("W1", c_void_p), ("b1", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
                 ("w3", c_void_p), ("b3", c_void_p)]
@@ -82,6 +89,8 @@ SYMBOLS = {
                                   C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ishap_ddpm_step_guided": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.POINTER(StepCoefs), C.c_int, C.c_int, C.c_int,
                                          c_void_p, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ishap_ddpm_step_guided_scales": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.POINTER(StepCoefs), C.c_int, C.c_int,
+                                                C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ishap_guided_update": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_float, c_void_p, C.c_longlong, c_void_p,
                                       c_void_p]),
     "ishap_axpby": (C.c_int, [c_void_p, c_void_p, C.c_float, C.c_float, C.c_longlong, c_void_p, c_void_p]),
@@ -89,6 +98,11 @@ SYMBOLS = {
     "ishap_drag_loss_grad": (C.c_int, [C.POINTER(DragArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ishap_drag_loss_cotangent": (C.c_int, [C.POINTER(DragArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
+    "ishap_drag_batch_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "ishap_drag_batch_setup": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p]),
+    "ishap_drag_batch_loss_grad": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ishap_drag_batch_loss_cotangent": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]),
     "ishap_grad_to_scaled_f16": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
     "ishap_planes_prepare": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, c_void_p, c_void_p]),
     "ishap_triplane_decode_points": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_longlong,
@@ -132,8 +146,8 @@ def lib():
             fn = getattr(l, name)     # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
-        if l.ishap_version() < 3:     # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 3): rebuild with `python -m ishapediting_amd.build`")
+        if l.ishap_version() < 4:     # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 4): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -170,6 +170,22 @@ int ishap_ddpm_step_guided(const float* x, const float* model_out, const float* 
   return ddpm_step_launch(a, (hipStream_t)stream);
 }
 
+int ishap_ddpm_step_guided_scales(const float* x, const float* model_out, const float* noise, const float* variance_in,
+                                  const ishap_step_coefs* k, int N, int C, int HW, const float* grad, const float* scales,
+                                  const float* grad_mul_dev, float* guided, float* sample, float* variance, void* stream) {
+  ISHAP_REQUIRE(x && model_out && k && grad && scales && guided, "null argument");
+  ISHAP_REQUIRE(k->mode == 0, "the guided step is p_sample_guidance's sqrt(variance) form (mode 0)");
+  DdpmStepArgs a;
+  a.x = x; a.model_out = model_out; a.noise = noise; a.variance_in = variance_in;
+  a.sample = sample; a.variance = variance;
+  a.N = N; a.C = C; a.HW = HW;
+  a.min_log = k->min_log; a.max_log = k->max_log; a.sqrt_recip = k->sqrt_recip; a.sqrt_recipm1 = k->sqrt_recipm1;
+  a.coef1 = k->coef1; a.coef2 = k->coef2; a.nonzero = k->nonzero; a.clip = k->clip_denoised; a.mode = k->mode;
+  a.guide_grad = grad; a.guide_scales = scales; a.guide_mul = grad_mul_dev; a.guided = guided;
+  a.rng = k->rng; a.rng_seed = k->rng_seed; a.rng_offset = k->rng_offset; a.noise_out = k->noise_out;
+  return ddpm_step_launch(a, (hipStream_t)stream);
+}
+
 int ishap_guided_update(const float* sample, const float* variance, const float* grad, float scale,
                         const float* grad_mul_dev, long long numel, float* out, void* stream) {
   ISHAP_REQUIRE(sample && variance && grad && out, "null argument");
@@ -214,6 +230,69 @@ int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit, const 
   ISHAP_REQUIRE(edit && orig && grad && loss && cot_f16 && bits && scale2, "null argument");
   d.edit = (const half_t*)edit; d.orig = (const half_t*)orig; d.grad = grad; d.loss = loss;
   return drag_loss_cotangent_launch(d, (half_t*)cot_f16, bits, scale2, (hipStream_t)stream);
+}
+
+// ---- E edits per call: one scratch buffer, carved as [grad_fx E*W*W*ld int64][acc E*2 int64][nmask E int32][touched E*3*W*W]
+// [chan_weight 3*ld], every part starting on a 256-byte boundary
+static long long drag_batch_carve(int E, int W, int ld, long long* o_acc, long long* o_nmask, long long* o_touched, long long* o_chw) {
+  auto up = [](long long v) { return (v + 255) & ~255ll; };
+  long long o = up((long long)E * W * W * ld * 8);
+  *o_acc = o; o = up(o + (long long)E * 16);
+  *o_nmask = o; o = up(o + (long long)E * 4);
+  *o_touched = o; o = up(o + (long long)E * 3 * W * W);
+  *o_chw = o; o = up(o + 3ll * ld);
+  return o;
+}
+
+long long ishap_drag_batch_scratch_bytes(int E, int W, int ld) {
+  if (E < 1 || W < 2 || ld < 1) return -1;
+  long long a, b, c, d;
+  return drag_batch_carve(E, W, ld, &a, &b, &c, &d);
+}
+
+static int fill_drag_batch(const ishap_drag_batch_args* a, DragBatchArgs& d) {
+  ISHAP_REQUIRE(a && a->chmap && a->sources && a->targets && a->handle_offsets && a->cof && a->scratch, "null argument");
+  ISHAP_REQUIRE(a->E >= 1 && a->E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");
+  ISHAP_REQUIRE(a->W > 1 && a->r >= 0 && a->Cc >= 1 && a->ld >= 1 && a->orig_stride >= 0, "drag dims");
+  long long o_acc, o_nmask, o_touched, o_chw;
+  const long long need = drag_batch_carve(a->E, a->W, a->ld, &o_acc, &o_nmask, &o_touched, &o_chw);
+  ISHAP_REQUIRE(a->scratch_bytes >= need, "drag batch: scratch smaller than ishap_drag_batch_scratch_bytes(E, W, ld)");
+  ISHAP_REQUIRE(((unsigned long long)a->scratch & 15ull) == 0, "drag batch: scratch must be 16-byte aligned");
+  char* sc = (char*)a->scratch;
+  DragArgs& b = d.base;
+  b.W = a->W; b.ld = a->ld; b.Cc = a->Cc; b.chmap = a->chmap; b.sources = a->sources; b.targets = a->targets;
+  b.r = a->r; b.voxel = a->voxel; b.l1 = a->l1;
+  b.gfx = (long long*)sc; b.acc = (long long*)(sc + o_acc); b.nmask = (int*)(sc + o_nmask);
+  b.touched = (unsigned char*)(sc + o_touched); b.chw = (unsigned char*)(sc + o_chw);
+  d.E = a->E;
+  d.orig_stride = a->orig_stride;
+  for (int e = 0; e <= a->E; ++e) d.hoff[e] = a->handle_offsets[e];
+  for (int e = 0; e < a->E; ++e) d.cof[e] = a->cof[e];
+  return 0;
+}
+
+int ishap_drag_batch_setup(const ishap_drag_batch_args* a, void* stream) {
+  DragBatchArgs d;
+  ISHAP_TRY(fill_drag_batch(a, d));
+  return drag_batch_setup_launch(d, (hipStream_t)stream);
+}
+
+int ishap_drag_batch_loss_grad(const ishap_drag_batch_args* a, const void* edit, const void* orig, float* grad, float* loss,
+                               void* stream) {
+  DragBatchArgs d;
+  ISHAP_TRY(fill_drag_batch(a, d));
+  ISHAP_REQUIRE(edit && orig && grad && loss, "null argument");
+  d.base.edit = (const half_t*)edit; d.base.orig = (const half_t*)orig; d.base.grad = grad; d.base.loss = loss;
+  return drag_batch_loss_grad_launch(d, (hipStream_t)stream);
+}
+
+int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* edit, const void* orig, float* grad,
+                                    float* loss, void* cot_f16, unsigned* bits, float* scale2, void* stream) {
+  DragBatchArgs d;
+  ISHAP_TRY(fill_drag_batch(a, d));
+  ISHAP_REQUIRE(edit && orig && grad && loss && cot_f16 && bits && scale2, "null argument");
+  d.base.edit = (const half_t*)edit; d.base.orig = (const half_t*)orig; d.base.grad = grad; d.base.loss = loss;
+  return drag_batch_loss_cotangent_launch(d, (half_t*)cot_f16, bits, scale2, (hipStream_t)stream);
 }
 
 int ishap_grad_to_scaled_f16(const float* grad, void* out_f16, unsigned* bits, float* scale2, long long numel,

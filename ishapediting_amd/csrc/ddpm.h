@@ -24,6 +24,7 @@ struct DdpmStepArgs {
   const float* guide_grad = nullptr;   // [N][C][HW] or null
   const float* guide_mul = nullptr;    // optional device scalar (1 / loss scale of the fp16 backward pass)
   float guide_scale = 0.f;
+  const float* guide_scales = nullptr; // optional device float[N]: image n uses guide_scales[n] instead of guide_scale
   float* guided = nullptr;
   // in-kernel noise (include/ishap.h, ishap_step_coefs::rng): used when rng != 0 and noise == nullptr
   int rng = 0;

@@ -36,6 +36,9 @@ __device__ __forceinline__ f32x4 step_noise4(unsigned long long vec, unsigned lo
   return n;
 }
 
+// PER_IMAGE: the guidance scale of image n is read from a.guide_scales[n] (batched drag edits, one scale per edit); the other
+// instantiation is the kernel of the single-scale call, unchanged
+template <bool PER_IMAGE>
 __global__ __launch_bounds__(256) void ddpm_step_kernel(DdpmStepArgs a) {
   const float gm = (a.guided && a.guide_mul) ? *a.guide_mul : 1.f;
   const long long per_img = (long long)a.C * a.HW;           // floats per image in x
@@ -62,6 +65,7 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(DdpmStepArgs a) {
     if (a.variance_in) var_in = var_l;
     f32x4 gr = {0.f, 0.f, 0.f, 0.f};
     if (a.guided) gr = gr_l;
+    const float gscale = PER_IMAGE ? a.guide_scales[n] : a.guide_scale;
     f32x4 o_sample, o_x0, o_var, o_mean, o_guided;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -81,7 +85,7 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(DdpmStepArgs a) {
       else s = mean + a.nonzero * sqrtf(a.variance_in ? var_in[k] : var) * nz[k];          // :503 / :508
       o_sample[k] = s; o_x0[k] = x0; o_var[k] = var; o_mean[k] = mean;
       // the dict's "variance" is the caller's override when one was given (gaussian_diffusion.py:510), else the learned one
-      o_guided[k] = s + (a.variance_in ? var_in[k] : var) * (a.guide_scale * (gr[k] * gm));
+      o_guided[k] = s + (a.variance_in ? var_in[k] : var) * (gscale * (gr[k] * gm));
     }
     if (a.guided) *reinterpret_cast<f32x4*>(a.guided + e) = o_guided;
     if (a.sample) *reinterpret_cast<f32x4*>(a.sample + e) = o_sample;
@@ -95,7 +99,8 @@ int ddpm_step_launch(const DdpmStepArgs& a, hipStream_t s) {
   ISHAP_REQUIRE(((long long)a.C * a.HW) % 4 == 0, "C*H*W must be a multiple of 4");
   long long nvec = (long long)a.N * a.C * a.HW / 4;
   int blocks = (int)std::min<long long>((nvec + 255) / 256, 2048);
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(blocks), dim3(256), 0, s, a);
+  if (a.guide_scales) hipLaunchKernelGGL(ddpm_step_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(ddpm_step_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }

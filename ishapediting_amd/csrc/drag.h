@@ -28,3 +28,20 @@ int drag_setup_launch(const DragArgs& a, hipStream_t s);        // touched bitma
 int drag_loss_grad_launch(const DragArgs& a, hipStream_t s);
 int drag_loss_cotangent_launch(const DragArgs& a, half_t* cot, unsigned* bits, float* scale2, hipStream_t s);
 int grad_to_scaled_f16_launch(const float* g, half_t* o, unsigned* bits, float* scale2, long long n, hipStream_t s);
+
+// ---- E edits in one call (include/ishap.h, ishap_drag_batch_*): the launches of one edit, grids that cover all of them ----
+constexpr int DRAG_MAX_EDITS = 32;
+struct DragBatchArgs {
+  // the shared fields (W, ld, Cc, chmap, chw, r, voxel, l1) and the BASE of every per-edit array: edit e reads edit + e*W*W*ld,
+  // orig + e*orig_stride, sources / targets + 3*hoff[e], and owns slice e of touched [E][3*W*W], nmask [E], acc [E][2],
+  // gfx / grad [E][W*W*ld] and loss [E]; base.B and base.cof are unused
+  DragArgs base;
+  int E = 0;
+  long long orig_stride = 0;         // halfs between the guidance slices of consecutive edits; 0: one guidance feature for all
+  int hoff[DRAG_MAX_EDITS + 1] = {};  // handle CSR offsets into sources / targets
+  int tblk[DRAG_MAX_EDITS + 1] = {};  // first workgroup of each edit in the terms pass (filled by the launcher)
+  float cof[DRAG_MAX_EDITS] = {};
+};
+int drag_batch_setup_launch(DragBatchArgs& a, hipStream_t s);
+int drag_batch_loss_grad_launch(DragBatchArgs& a, hipStream_t s);
+int drag_batch_loss_cotangent_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float* scale2, hipStream_t s);

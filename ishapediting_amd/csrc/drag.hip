@@ -90,8 +90,8 @@ __device__ __forceinline__ void drag_motion_body(const DragArgs& a, int blk, int
     // the segment's DSEG positions: all their texel loads are issued before the first is used.  Round 6: really -- written as
     // `if (in bounds) patch = fma(w, texel[...], patch)` every one of the 40 loads sat in a conditional block of its own, and the
     // compiler closes such a block with s_waitcnt vmcnt(0): 41 of the kernel's 46 waits stood right behind a load (26 us per step).
-    // Now every load is unconditional at a clamped coordinate and a sample outside the map (zeros padding, drag_utils.py:355)
-    // enters with weight 0: fma(0, texel, acc) = acc, the same sums (the sign of a zero apart, which the fixed-point scatter drops).
+    // Now every load is unconditional at a clamped coordinate and a tap outside the map (zeros padding, drag_utils.py:355)
+    // enters with value 0 and weight 0: fma(0, 0, acc) = acc, the same sums as skipping it, whatever the clamped texel holds.
     float dseg[DSEG];
     half_t tp[DSEG][4], te[DSEG][4];
     float wp[DSEG][4], we[DSEG][4];
@@ -108,10 +108,15 @@ __device__ __forceinline__ void drag_motion_body(const DragArgs& a, int blk, int
         const int xt = bt.x0 + (q & 1), yt = bt.y0 + (q >> 1);
         const int xsc = min(max(xs, 0), a.W - 1), ysc = min(max(ys, 0), a.W - 1);
         const int xtc = min(max(xt, 0), a.W - 1), ytc = min(max(yt, 0), a.W - 1);
-        tp[ii][q] = a.orig[((long long)ysc * a.W + xsc) * a.ld + ch];
-        te[ii][q] = a.edit[((long long)ytc * a.W + xtc) * a.ld + ch];
-        wp[ii][q] = (on && xs == xsc && ys == ysc) ? bs.w[q] : 0.f;
-        we[ii][q] = (on && xt == xtc && yt == ytc) ? bt.w[q] : 0.f;
+        const half_t vp = a.orig[((long long)ysc * a.W + xsc) * a.ld + ch];
+        const half_t ve = a.edit[((long long)ytc * a.W + xtc) * a.ld + ch];
+        // the VALUE is selected as well as the weight (one v_cndmask behind the load, no extra wait): a clamped tap that reads a
+        // non-finite border texel must not turn a sample outside the map into 0 * Inf = NaN; for finite texels the same bits
+        const bool ins = on && xs == xsc && ys == ysc, ine = on && xt == xtc && yt == ytc;
+        tp[ii][q] = ins ? vp : (half_t)0.f;
+        te[ii][q] = ine ? ve : (half_t)0.f;
+        wp[ii][q] = ins ? bs.w[q] : 0.f;
+        we[ii][q] = ine ? bt.w[q] : 0.f;
       }
     }
 #pragma unroll
@@ -152,16 +157,7 @@ __device__ __forceinline__ void drag_motion_body(const DragArgs& a, int blk, int
 }
 
 // touched[p][row][col] = 1 where a rounded lattice texel of any source/target point lands (drag_utils.py:322-334)
-__global__ void drag_touch_kernel(DragArgs a) {
-  const int side = 2 * a.r + 1;
-  const int total = 3 * a.B * 2 * side * side;
-  int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  int j = idx % side;
-  int i = (idx / side) % side;
-  int st = (idx / (side * side)) % 2;
-  int b = (idx / (side * side * 2)) % a.B;
-  int p = idx / (side * side * 2 * a.B);
+__device__ __forceinline__ void drag_touch_one(const DragArgs& a, int p, int b, int st, int i, int j) {
   int ac, ar;
   plane_axes(p, ac, ar);
   const float* pt = st ? a.targets : a.sources;
@@ -186,8 +182,20 @@ __global__ void drag_touch_kernel(DragArgs a) {
       for (int dx = -1; dx <= 2; ++dx) mark(bt.y0 + dy, bt.x0 + dx, 2u);
   }
 }
+__global__ void drag_touch_kernel(DragArgs a) {
+  const int side = 2 * a.r + 1;
+  const int total = 3 * a.B * 2 * side * side;
+  int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  int j = idx % side;
+  int i = (idx / side) % side;
+  int st = (idx / (side * side)) % 2;
+  int b = (idx / (side * side * 2)) % a.B;
+  int p = idx / (side * side * 2 * a.B);
+  drag_touch_one(a, p, b, st, i, j);
+}
 
-__global__ void drag_count_kernel(DragArgs a) {
+__device__ __forceinline__ void drag_count_body(const DragArgs& a) {
   __shared__ int red[256];
   int cnt = 0;
   for (int i = threadIdx.x; i < 3 * a.W * a.W; i += 256) cnt += (a.touched[i] & 1) ? 0 : 1;
@@ -196,6 +204,7 @@ __global__ void drag_count_kernel(DragArgs a) {
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
   if (threadIdx.x == 0) a.nmask[0] = red[0];
 }
+__global__ void drag_count_kernel(DragArgs a) { drag_count_body(a); }
 
 // chw[p][ch] = number of (plane p, c) pairs that resize_feat_align maps to tap channel ch (0 or 1; 2 where the nearest
 // resize repeats a channel): lets the gather pass below add the mask term per tap element without a scatter
@@ -229,7 +238,7 @@ __global__ void drag_finish_kernel(DragArgs a) { drag_finish(a); }
 // (drag_utils.py:376-381: cof * mean over the untouched texels of |edit - orig|^2 or |.|), which is elementwise in the tap's
 // own layout once the channel map is inverted (chw) -- it used to be a second 2-million-atomic scatter.  The buffer is
 // left zero for the next call (no memset launch); with `absmax_bits` the pass also finds max|g| for the loss scale.
-__global__ __launch_bounds__(256) void drag_gather_kernel(DragArgs a, unsigned* __restrict__ absmax_bits) {
+__device__ __forceinline__ void drag_gather_body(const DragArgs& a, int blk, int nblk, unsigned* __restrict__ absmax_bits) {
   typedef long long ll2 __attribute__((ext_vector_type(2)));
   typedef unsigned char uc8 __attribute__((ext_vector_type(8)));
   const long long n = (long long)a.W * a.W * a.ld;
@@ -238,7 +247,7 @@ __global__ __launch_bounds__(256) void drag_gather_kernel(DragArgs a, unsigned* 
   const float denom = (float)a.Cc * (float)a.nmask[0];
   float m = 0.f, lsum = 0.f;
   // a thread takes 8 consecutive channels of one texel (ld % 8 == 0): 16-byte accesses on every stream
-  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < n; i += (long long)gridDim.x * blockDim.x * 8) {
+  for (long long i = ((long long)blk * blockDim.x + threadIdx.x) * 8; i < n; i += (long long)nblk * blockDim.x * 8) {
     float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int tex = (int)(i / a.ld), ch = (int)(i - (long long)tex * a.ld);
     const unsigned char t0 = a.touched[tex], t1 = a.touched[WW + tex], t2 = a.touched[2 * WW + tex];
@@ -286,6 +295,9 @@ __global__ __launch_bounds__(256) void drag_gather_kernel(DragArgs a, unsigned* 
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(absmax_bits, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
   }
+}
+__global__ __launch_bounds__(256) void drag_gather_kernel(DragArgs a, unsigned* __restrict__ absmax_bits) {
+  drag_gather_body(a, blockIdx.x, gridDim.x, absmax_bits);
 }
 
 int drag_setup_launch(const DragArgs& a, hipStream_t s) {
@@ -388,6 +400,146 @@ int grad_to_scaled_f16_launch(const float* g, half_t* o, unsigned* bits, float* 
   hipLaunchKernelGGL(absmax_kernel, dim3(std::min(blocks, 512)), dim3(256), 0, s, g, n, bits);
   hipLaunchKernelGGL(pick_scale_kernel, dim3(1), dim3(1), 0, s, bits, scale2);
   hipLaunchKernelGGL(scale_to_f16_kernel, dim3(blocks), dim3(256), 0, s, g, o, scale2, n);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ==== E edits per call ====
+// Every pass of one edit above becomes one launch whose grid is the concatenation of the E solo grids: workgroup blk of edit e
+// runs exactly what workgroup blk of the solo launch for that edit runs (same bodies, same workgroup count, same grid stride).
+// So each edit's float partial sums are formed in the same groups and order as alone, its fixed-point totals are the same
+// integers, and its loss and fp32 gradient are BITWISE those of ishap_drag_loss_grad on that edit -- three launches per guided
+// step whatever E is.
+//
+// One loss scale for the batch.  The cotangent is g * 2^k in fp16 with k picked from max|g| over ALL edits (so k_batch <= k_solo
+// of every edit).  Multiplying by a power of two is exact in fp32, and the fp16 cast of g * 2^k_batch equals the solo cotangent
+// times 2^(k_batch - k_solo) bit for bit wherever it stays a normal fp16 number.  The UNet input-gradient backward is linear in
+// its cotangent and removes the scale at its end (scale2[1]); a power-of-two rescaling of all its fp16 intermediates is exact as
+// long as none leaves the fp16 range.  One scale per batch therefore needs no change to the backward: only an edit whose
+// gradient is 2^10+ times smaller than the largest one of the batch loses low bits to fp16 subnormals.
+__device__ __forceinline__ DragArgs drag_edit_args(const DragBatchArgs& b, int e) {
+  DragArgs a = b.base;
+  const long long n = (long long)a.W * a.W * a.ld;
+  const int h0 = b.hoff[e];
+  a.edit += e * n;
+  a.orig += e * b.orig_stride;
+  a.sources += 3 * h0;
+  a.targets += 3 * h0;
+  a.B = b.hoff[e + 1] - h0;
+  a.cof = b.cof[e];
+  a.touched += (long long)e * 3 * a.W * a.W;
+  a.nmask += e;
+  a.grad += e * n;
+  a.gfx += e * n;
+  a.acc += 2 * e;
+  a.loss += e;
+  return a;
+}
+
+// one thread per (handle, plane, source / target, lattice i, j) over the packed handles of all edits
+__global__ void drag_batch_touch_kernel(DragBatchArgs b) {
+  const int side = 2 * b.base.r + 1;
+  const int per = 3 * 2 * side * side;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= per * b.hoff[b.E]) return;
+  const int h = idx / per;
+  int e = 0;
+  while (e + 1 < b.E && h >= b.hoff[e + 1]) ++e;
+  int rem = idx - h * per;
+  const int j = rem % side; rem /= side;
+  const int i = rem % side; rem /= side;
+  const int st = rem % 2;
+  const int p = rem / 2;
+  drag_touch_one(drag_edit_args(b, e), p, h - b.hoff[e], st, i, j);
+}
+__global__ void drag_batch_count_kernel(DragBatchArgs b) { drag_count_body(drag_edit_args(b, blockIdx.x)); }
+
+__global__ __launch_bounds__(256) void drag_batch_terms_kernel(DragBatchArgs b, unsigned* absmax_bits) {
+  if (absmax_bits && blockIdx.x == 0 && threadIdx.x == 0) absmax_bits[0] = 0u;
+  int e = 0;
+  while (e + 1 < b.E && (int)blockIdx.x >= b.tblk[e + 1]) ++e;       // workgroup-uniform
+  drag_motion_body(drag_edit_args(b, e), blockIdx.x - b.tblk[e], b.tblk[e + 1] - b.tblk[e]);
+}
+__global__ __launch_bounds__(256) void drag_batch_gather_kernel(DragBatchArgs b, int blocks_per_edit, unsigned* __restrict__ absmax_bits) {
+  const int e = blockIdx.x / blocks_per_edit;
+  drag_gather_body(drag_edit_args(b, e), blockIdx.x - e * blocks_per_edit, blocks_per_edit, absmax_bits);
+}
+__global__ void drag_batch_finish_kernel(DragBatchArgs b) {
+  for (int e = 0; e < b.E; ++e) drag_finish(drag_edit_args(b, e));
+}
+__global__ void drag_batch_scale_kernel(const float* __restrict__ g, half_t* __restrict__ o, const unsigned* __restrict__ bits,
+                                        float* __restrict__ scale2, DragBatchArgs b, long long n) {
+  const float sc = pick_scale(__uint_as_float(bits[0]));
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    scale2[0] = sc;
+    scale2[1] = 1.f / sc;
+    for (int e = 0; e < b.E; ++e) drag_finish(drag_edit_args(b, e));
+  }
+  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)gridDim.x * blockDim.x * 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+    *reinterpret_cast<half4*>(o + i) = (half4){(half_t)(v[0] * sc), (half_t)(v[1] * sc), (half_t)(v[2] * sc), (half_t)(v[3] * sc)};
+  }
+}
+
+static int drag_batch_check(const DragBatchArgs& a) {
+  ISHAP_REQUIRE(a.E >= 1 && a.E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");
+  ISHAP_REQUIRE((3 * a.base.W * a.base.W) % 4 == 0 && a.base.ld % 8 == 0,
+                "drag: 3*W*W must be a multiple of 4 and the tap channels of 8");
+  ISHAP_REQUIRE(a.hoff[0] == 0, "drag batch: handle_offsets[0] must be 0");
+  for (int e = 0; e < a.E; ++e) ISHAP_REQUIRE(a.hoff[e + 1] > a.hoff[e], "drag batch: every edit needs at least one handle");
+  return 0;
+}
+
+int drag_batch_setup_launch(DragBatchArgs& a, hipStream_t s) {
+  ISHAP_TRY(drag_batch_check(a));
+  const DragArgs& d = a.base;
+  const int side = 2 * d.r + 1;
+  const long long n = (long long)d.W * d.W * d.ld;
+  ISHAP_CHECK_HIP(hipMemsetAsync(d.touched, 0, (size_t)a.E * 3 * d.W * d.W, s));
+  ISHAP_CHECK_HIP(hipMemsetAsync(d.gfx, 0, (size_t)a.E * n * sizeof(long long), s));
+  ISHAP_CHECK_HIP(hipMemsetAsync(d.acc, 0, (size_t)a.E * 2 * sizeof(long long), s));
+  const int total = 3 * 2 * side * side * a.hoff[a.E];
+  hipLaunchKernelGGL(drag_batch_touch_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(drag_batch_count_kernel, dim3(a.E), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(drag_chan_weight_kernel, dim3(ceil_div(3 * d.ld, 256)), dim3(256), 0, s, d);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// the solo terms grid of every edit, concatenated (drag_terms_launch)
+static int drag_batch_terms_launch(DragBatchArgs& a, unsigned* bits, hipStream_t s) {
+  constexpr int cap = 1024;
+  const int side = 2 * a.base.r + 1;
+  a.tblk[0] = 0;
+  for (int e = 0; e < a.E; ++e) {
+    const int nrows = 3 * (a.hoff[e + 1] - a.hoff[e]) * side * ((a.base.Cc + 63) / 64) * ((side + DSEG - 1) / DSEG);
+    a.tblk[e + 1] = a.tblk[e] + min(ceil_div(nrows * 64, 256), cap);
+  }
+  hipLaunchKernelGGL(drag_batch_terms_kernel, dim3(a.tblk[a.E]), dim3(256), 0, s, a, bits);
+  return 0;
+}
+
+// requires ishap_drag_batch_setup on this scratch first
+int drag_batch_loss_grad_launch(DragBatchArgs& a, hipStream_t s) {
+  ISHAP_TRY(drag_batch_check(a));
+  const long long n = (long long)a.base.W * a.base.W * a.base.ld;
+  const unsigned gb = gather_blocks(n);
+  ISHAP_TRY(drag_batch_terms_launch(a, nullptr, s));
+  hipLaunchKernelGGL(drag_batch_gather_kernel, dim3(gb * a.E), dim3(256), 0, s, a, (int)gb, (unsigned*)nullptr);
+  hipLaunchKernelGGL(drag_batch_finish_kernel, dim3(1), dim3(1), 0, s, a);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int drag_batch_loss_cotangent_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float* scale2, hipStream_t s) {
+  ISHAP_TRY(drag_batch_check(a));
+  const long long n = (long long)a.base.W * a.base.W * a.base.ld;
+  const unsigned gb = gather_blocks(n);
+  ISHAP_TRY(drag_batch_terms_launch(a, bits, s));
+  hipLaunchKernelGGL(drag_batch_gather_kernel, dim3(gb * a.E), dim3(256), 0, s, a, (int)gb, bits);
+  const long long nt = n * a.E;
+  hipLaunchKernelGGL(drag_batch_scale_kernel, dim3((unsigned)std::min<long long>((nt / 4 + 255) / 256, 1024)), dim3(256), 0, s,
+                     (const float*)a.base.grad, cot, (const unsigned*)bits, scale2, a, nt);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }

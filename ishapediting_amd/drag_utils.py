@@ -165,6 +165,100 @@ class DragKernels:
         return self.cot, self.scale2
 
 
+def pack_handles(sources, targets):
+    """K edits' handle arrays -> the packed form of ishap_drag_batch_args: (sources [H, 3], targets [H, 3] float32 tensors on the
+    CPU, CSR offsets list of K + 1 ints; edit e owns rows offsets[e]:offsets[e + 1])."""
+    if len(sources) != len(targets):
+        raise ValueError(f"{len(sources)} source sets but {len(targets)} target sets: one of each per edit")
+    if len(sources) == 0:
+        raise ValueError("no edits")
+    src, tgt, offs = [], [], [0]
+    for e, (s_, t_) in enumerate(zip(sources, targets)):
+        s_ = (s_.detach().cpu() if th.is_tensor(s_) else th.as_tensor(np.asarray(s_))).to(th.float32).reshape(-1, 3)
+        t_ = (t_.detach().cpu() if th.is_tensor(t_) else th.as_tensor(np.asarray(t_))).to(th.float32).reshape(-1, 3)
+        if s_.shape[0] != t_.shape[0] or s_.shape[0] == 0:
+            raise ValueError(f"edit {e}: {s_.shape[0]} sources and {t_.shape[0]} targets (need the same, non-zero count)")
+        src.append(s_)
+        tgt.append(t_)
+        offs.append(offs[-1] + s_.shape[0])
+    return th.cat(src).contiguous(), th.cat(tgt).contiguous(), offs
+
+
+def check_edit_count(K: int, max_edits: int):
+    if K > max_edits:
+        raise ValueError(f"{K} edits requested but this DragStuff was built for max_edits={max_edits}")
+    if K < 1:
+        raise ValueError("no edits")
+
+
+def per_edit(value, K: int, name: str) -> List[float]:
+    """A float (every edit) or a length-K sequence (one per edit) -> K floats."""
+    if th.is_tensor(value):
+        value = value.detach().cpu().reshape(-1).tolist() if value.dim() else float(value)
+    if isinstance(value, (int, float, np.floating, np.integer)):
+        return [float(value)] * K
+    vals = [float(v) for v in value]
+    if len(vals) != K:
+        raise ValueError(f"{name}: {len(vals)} values for {K} edits (give one float or one value per edit)")
+    return vals
+
+
+class BatchDragKernels:
+    """Device state + calls of the drag loss for E edits at once (ishap_drag_batch_*): one scratch buffer, one loss scale."""
+
+    def __init__(self, device, E: int, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str = "l2"):
+        self.device = th.device(device)
+        self.E, self.W, self.ld, self.r, self.voxel = int(E), W, ld, r, float(voxel)
+        self.l1 = 1 if loss_type == "l1" else 0
+        self.chmap = th.as_tensor(np.asarray(chmap), dtype=th.int32).reshape(3, -1).contiguous().to(self.device)
+        self.Cc = self.chmap.shape[1]
+        self._L = _lib.lib()
+        nbytes = int(self._L.ishap_drag_batch_scratch_bytes(self.E, W, ld))
+        if nbytes <= 0:
+            raise ValueError(f"drag batch: bad dimensions E={E}, W={W}, ld={ld}")
+        self.scratch = th.zeros(nbytes, dtype=th.uint8, device=self.device)
+        self.grad = th.empty((self.E, W * W, ld), dtype=th.float32, device=self.device)
+        self.loss = th.zeros(self.E, dtype=th.float32, device=self.device)
+        self.cot = th.empty((self.E, W * W, ld), dtype=th.float16, device=self.device)
+        self.bits = th.zeros(1, dtype=th.int32, device=self.device)
+        self.scale2 = th.ones(2, dtype=th.float32, device=self.device)
+        self.sources = self.targets = None
+
+    def setup(self, sources, targets, cof):
+        """sources / targets: lists of E handle arrays; cof: a float or E floats."""
+        src, tgt, offs = pack_handles(sources, targets)
+        if len(offs) - 1 != self.E:
+            raise ValueError(f"{len(offs) - 1} edits given to drag kernels set up for {self.E}")
+        self.sources, self.targets = src.to(self.device), tgt.to(self.device)
+        self.offsets = list(offs)
+        self._offs = (C.c_int * (self.E + 1))(*offs)
+        self.cof = per_edit(cof, self.E, "cof")
+        self._cof = (C.c_float * self.E)(*self.cof)
+        with th.cuda.device(self.device):
+            _lib.check(self._L.ishap_drag_batch_setup(C.byref(self._args(0)), _lib.stream_ptr(self.device)))
+
+    def _args(self, orig_stride: int) -> _lib.DragBatchArgsC:
+        return _lib.DragBatchArgsC(self.E, self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
+                                   self.targets.data_ptr(), self._offs, self.r, self.voxel, self._cof, self.l1, int(orig_stride),
+                                   self.scratch.data_ptr(), self.scratch.numel())
+
+    def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int):
+        """edit: [E][W*W][ld] fp16; orig: edit e's guidance at orig + e * orig_stride halfs (0: one guidance for all edits)."""
+        with th.cuda.device(self.device):
+            _lib.check(self._L.ishap_drag_batch_loss_grad(C.byref(self._args(orig_stride)), edit_ptr, orig_ptr, self.grad.data_ptr(),
+                                                          self.loss.data_ptr(), _lib.stream_ptr(self.device)))
+        return self.grad, self.loss
+
+    def loss_cotangent_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int, loss_out=None):
+        """losses + gradients + the batch's fp16 cotangent (one loss scale, scale2) in three launches; `loss_out`: device float[E]."""
+        loss = self.loss if loss_out is None else loss_out
+        with th.cuda.device(self.device):
+            _lib.check(self._L.ishap_drag_batch_loss_cotangent(
+                C.byref(self._args(orig_stride)), edit_ptr, orig_ptr, self.grad.data_ptr(), loss.data_ptr(), self.cot.data_ptr(),
+                self.bits.data_ptr(), self.scale2.data_ptr(), _lib.stream_ptr(self.device)))
+        return self.cot, self.scale2
+
+
 def synthesize_latent(model, diffusion, args=None, t1=None, t2=0, inter_latent_idx=None, inter_feat_idx=None, img=None,
                       calc_grad=False, **kwargs):
     """drag_utils.py:61-131 (no caller in the reference; kept for the call surface).  calc_grad=True keeps the autograd
@@ -212,12 +306,17 @@ class DragStuff:
     args = get_args()
     overlap_tail = None       # None: the module default (_OVERLAP_TAIL, i.e. ISHAP_OVERLAP_TAIL); True / False: this object only
 
-    def __init__(self, device=None, args=None):
+    def __init__(self, device=None, args=None, max_edits=1):
+        """`max_edits`: the most edits one training_batch call may run (the model context is built for that batch size; the
+        default 1 builds exactly the single-edit object)."""
         if args is not None:
             self.args = args
+        if int(max_edits) < 1:
+            raise ValueError(f"max_edits must be >= 1, not {max_edits}")
+        self.max_edits = int(max_edits)
         self.device = th.device("cuda", th.cuda.current_device()) if device is None else th.device(device)
         self.model, self.diffusion = create_model_and_diffusion(
-            **args_to_dict(self.args, model_and_diffusion_defaults().keys()), device=self.device)
+            **args_to_dict(self.args, model_and_diffusion_defaults().keys()), device=self.device, max_batch=self.max_edits)
         self.model.eval()
         self.decoder = MultiTriplane(1, input_dim=3, output_dim=1, device=self.device)
         self.decoder.eval()
@@ -242,6 +341,13 @@ class DragStuff:
         self.last_losses: List[float] = []
         self._dk: Optional[DragKernels] = None
         self.step_noise = None        # optional callable i -> noise tensor (parity runs); default randn like the reference
+        # batched edits (training_batch): set by update_latent_params_batch; None = edit variants of the single shape
+        self.w_batch = None
+        self.w0_batch = None
+        self.feature_guidance_batch: List[th.Tensor] = []     # fp16 NHWC taps [K, S*S, C], one per guided step
+        self.meshes0 = []
+        self.meshes = []
+        self.volumes = []
 
     def set_offset1(self, r1):
         self.r1 = int(r1)
@@ -298,6 +404,7 @@ class DragStuff:
         else:
             img = th.randn((1, 96, self.args.image_size, self.args.image_size), dtype=th.float32, device=self.device)
         self.latent_code = img.clone().detach()
+        self.w_batch, self.w0_batch, self.feature_guidance_batch = None, None, []     # training_batch: variants of this shape
         for i in range(self.args.num_steps - 1, -1, -1):
             keep = i < self.args.w_time
             outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
@@ -385,6 +492,121 @@ class DragStuff:
             self.last_losses.append(losses[i:i + 1])
             yield 1 - i / (self.args.w_time - 1.)
         self.mesh = self.get_mesh(img=img, t=stop_time)
+
+    # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
+    def _check_edits(self, K: int):
+        check_edit_count(K, self.max_edits)
+
+    def update_latent_params_batch(self, imgs, **kwargs):
+        """update_latent_params for K shapes at once: imgs [K, 96, S, S].  Records w_batch [K, ...], one [K, S*S, C] guidance tap
+        per guided step (feature_guidance_batch) and meshes0 (K meshes).  training_batch then edits shape k with edit k."""
+        if type(imgs) is np.ndarray:
+            imgs = th.tensor(imgs)
+        if not th.is_tensor(imgs) or imgs.dim() != 4:
+            raise ValueError("update_latent_params_batch: imgs must be a [K, C, S, S] tensor or array")
+        K = imgs.shape[0]
+        self._check_edits(K)
+        img = imgs.to(device=self.device, dtype=th.float32).contiguous()
+        self.latent_code = img.clone().detach()
+        self.feature_guidance_batch = []
+        for i in range(self.args.num_steps - 1, -1, -1):
+            outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
+                                                    clip_denoised=self.args.clip_denoised, want_inter_feat=False,
+                                                    noise=self._noise(i, img), want_noise=False, **kwargs)
+            img = outs["sample"]
+            if i == self.args.w_time:
+                self.w_batch = img.clone().detach()
+                self.w0_batch = self.w_batch.clone().detach()
+            if i < self.args.w_time:
+                self.feature_guidance_batch.append(self.model.copy_tap(self.args.feat_layer, K))
+        assert len(self.feature_guidance_batch) == self.args.w_time
+        self.meshes0 = [self.get_mesh(tri_feat=img[k:k + 1]) for k in range(K)]
+        self.meshes = copy.deepcopy(self.meshes0)
+        return img
+
+    def get_meshes(self, img, t=0):
+        """get_mesh for a batch of latents: the t remaining unguided steps at batch K, then one decode per shape (sets
+        tri_feat_batch, volumes, meshes)."""
+        for i in range(t - 1, -1, -1):
+            outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
+                                                    clip_denoised=self.args.clip_denoised, want_inter_feat=False,
+                                                    noise=self._noise(i, img), want_noise=False)
+            img = outs["sample"]
+        self.tri_feat_batch = img
+        self.meshes, self.volumes = [], []
+        for k in range(img.shape[0]):
+            self.meshes.append(self.get_mesh(tri_feat=img[k:k + 1]))
+            self.volumes.append(self.volume)
+        return self.meshes
+
+    def training_batch(self, sources, targets, scale=600, cof=0.2):
+        """K drag edits in one guided loop (the generator of training(), same progress values).  sources / targets: lists of K
+        handle arrays (their counts may differ); scale, cof: a float or K values.  After update_latent_params_batch edit k
+        drags shape k; otherwise the K edits are variants of the single shape of update_latent_params (its w and guidance
+        features, shared).  train_flag stops all edits at one stop_time; each then finishes its remaining steps unguided.
+        Afterwards: meshes / volumes (K of each) and last_losses (one [K] tensor per step).  Every edit's drag loss and gradient
+        are bitwise those of a solo call; the loss scale of the fp16 backward is one power of two for the batch (exact for the
+        linear backward).  Injected noise (step_noise -> [K, ...]) makes edit k repeat a solo run with noise k; drawn noise spans
+        the batch and differs from a solo run's."""
+        if len(sources) != len(targets):
+            raise ValueError(f"{len(sources)} source sets but {len(targets)} target sets: one of each per edit")
+        K = len(sources)
+        self._check_edits(K)
+        scales = per_edit(scale, K, "scale")
+        cofs = per_edit(cof, K, "cof")
+        ch, width = self.model.tap_shape(self.args.feat_layer)
+        if self.w_batch is not None:
+            if self.w_batch.shape[0] != K:
+                raise ValueError(f"{K} edits for the {self.w_batch.shape[0]} shapes of update_latent_params_batch")
+            img = self.w_batch.clone().detach()
+            guidance, stride = self.feature_guidance_batch, width * width * ch
+        else:
+            if self.w is None:
+                raise RuntimeError("training_batch needs update_latent_params (variants of one shape) or update_latent_params_batch first")
+            img = self.w.expand(K, *self.w.shape[1:]).contiguous()
+            guidance, stride = self.feature_guidance, 0
+        stop_time = 0
+        self.train_flag = True
+        dk = BatchDragKernels(self.device, K, W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size,
+                              loss_type=self.args.loss_type)
+        dk.setup(sources, targets, cofs)
+        self._dk_batch = dk
+        scales_dev = th.tensor(scales, dtype=th.float32, device=self.device)
+        losses = th.zeros((self.args.w_time, K), dtype=th.float32, device=self.device)
+        self.diffusion.prepare(self.model, range(self.args.w_time))
+        self.last_losses = []
+        L = _lib.lib()
+        for i in range(self.args.w_time - 1, -1, -1):
+            if not self.train_flag:
+                stop_time = i + 1
+                break
+            origin = guidance[self.args.w_time - 1 - i]
+            got = {}
+
+            def loss_and_backward():          # the structure of training(): loss + backward beside the forward tail
+                cot, scale2 = dk.loss_cotangent_ptr(self.model.tap_ptr(), origin.data_ptr(), stride, loss_out=losses[i])
+                got["grad"] = self.model.backward_input(cot, scale2)
+                return got["grad"]
+
+            outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
+                                                    keep_for_backward=True, want_inter_feat=False,
+                                                    noise=self._noise(i, img), between=loss_and_backward,
+                                                    overlap=_OVERLAP_TAIL if self.overlap_tail is None else self.overlap_tail,
+                                                    guided_scale=scales_dev if _FUSED_UPDATE else None, want_noise=False)
+            if _FUSED_UPDATE:
+                img = outs["guided"]
+            else:
+                new = th.empty_like(img)
+                n1 = img[0].numel()
+                with th.cuda.device(self.device):
+                    for k in range(K):
+                        _lib.check(L.ishap_guided_update(outs["sample"][k].data_ptr(), outs["variance"][k].data_ptr(),
+                                                         got["grad"][k].data_ptr(), scales[k], None, n1, new[k].data_ptr(),
+                                                         _lib.stream_ptr(self.device)))
+                img = new
+            self.last_losses.append(losses[i])
+            yield 1 - i / (self.args.w_time - 1.)
+        self.get_meshes(img=img, t=stop_time)
 
     # ------------------------------------------------------------------ real shapes (:401-471, :552-566)
     def train_triplane(self, mesh=None, mesh_path=None, center_mesh=True, tri_feat_path=None, path="./",

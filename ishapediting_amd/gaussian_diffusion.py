@@ -155,6 +155,14 @@ class SpacedDiffusion:
             grad, scale = guide
             assert grad.shape == x.shape and grad.dtype == torch.float32 and grad.is_contiguous()
             outs["guided"] = torch.empty_like(x)
+            if torch.is_tensor(scale):        # one scale per image (batched drag edits): device float[N]
+                assert scale.shape == (N,) and scale.dtype == torch.float32 and scale.device == x.device
+                with torch.cuda.device(x.device):
+                    _lib.check(_lib.lib().ishap_ddpm_step_guided_scales(
+                        x.data_ptr(), model_output.data_ptr(), _lib.ptr(noise), _lib.ptr(variance_in), C.byref(k), N, Cc, HW,
+                        grad.data_ptr(), scale.data_ptr(), None, outs["guided"].data_ptr(), _lib.ptr(outs.get("sample")),
+                        _lib.ptr(outs.get("variance")), _lib.stream_ptr(x.device)))
+                return outs
             with torch.cuda.device(x.device):
                 _lib.check(_lib.lib().ishap_ddpm_step_guided(
                     x.data_ptr(), model_output.data_ptr(), _lib.ptr(noise), _lib.ptr(variance_in), C.byref(k), N, Cc, HW,
@@ -206,7 +214,9 @@ class SpacedDiffusion:
         beside them, and the step arithmetic waits for it.  Results are identical with and without it.
         `guided_scale` (with a `between` that returns d loss / d x): the drag loop's update `sample + variance * scale * grad`
         (drag_utils.py:384-392) is formed by the step kernel itself and returned as "guided" -- one launch instead of two, the
-        intermediate sample / variance tensors are not written.
+        intermediate sample / variance tensors are not written.  A float32 device tensor of N values gives image n its own scale
+        (batched drag edits); a drawn noise (noise=None) then spans the batch, so image n's noise is not the one a single-image
+        call would draw.
         `want_noise=False`: the dict's "noise" may be None when the step drew the noise itself (`_draw`); the drag loop does
         not read it."""
         assert denoised_fn is None and cond_fn is None, "not used on the path"
@@ -239,7 +249,8 @@ class SpacedDiffusion:
                 noise, rng = self._draw(x, want_noise)
             noise = None if noise is None else self._prep(noise)
             vin = None if variance is None else self._prep(variance)
-            o = self._step(x, mo, ti, noise, vin, clip_denoised, 0, (), guide=(grad, float(guided_scale)), rng=rng)
+            gs = guided_scale if torch.is_tensor(guided_scale) else float(guided_scale)
+            o = self._step(x, mo, ti, noise, vin, clip_denoised, 0, (), guide=(grad, gs), rng=rng)
             return {"guided": o["guided"], "inter_feat": inter, "noise": noise if rng is None else rng[2]}
         if variance_noise is not None:
             o = self._step(x, mo, ti, self._prep(variance_noise), None, clip_denoised, 2, ("sample", "variance"))
