@@ -19,7 +19,8 @@
 // igemm2's chunk ^ ((row >> 1) & 7).
 // Tile shapes (igemm4_launch_main): 128x128 on maps 16 ... 128 wide (several image rows per tile below 128; fragment reads
 // interleaved into the MFMA blocks), 64x64 one- and two-team on maps 16 ... 64 wide, 128 pixels x 64 channels on the 64-wide
-// maps, and on the 8x8 maps 64x64 tiles (= one image) with K cut into ~16 slices whose fp32 partial tiles are left for the
+// maps, 128 pixels x 32 channels with one halo slab per chunk (igemm4_halo_kernel) where the 64x64 form has ~256 workgroups,
+// and on the 8x8 maps 64x64 tiles (= one image) with K cut into ~16 slices whose fp32 partial tiles are left for the
 // consuming GroupNorm kernel to add up (igemm4_small_map_slices; took the level over from a one-launch small-map kernel late in round 4, removed in round 6).
 // Reference arithmetic: conv2d 3x3, padding 1 (gd/unet.py ResBlock in_layers / out_layers, :236-256) and its input
 // gradient (flipped, transposed weights).  Same products as igemm2, another order of the K sum inside the fp32
@@ -27,6 +28,7 @@
 #include "common.h"
 #include "igemm_epilogue.h"
 #include <type_traits>
+#include <utility>
 
 __device__ __attribute__((aligned(128))) half_t g_zero_line4[64];   // zero-initialised: source of out-of-image rows
 typedef __attribute__((address_space(3))) void lds_void4;
@@ -59,6 +61,37 @@ __device__ __forceinline__ void ig4_wait_vm(int n) {
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;     // never more than 40 outstanding by construction; safe anyway
   }
 #undef IG4_W
+}
+
+// the tile (m, n, K slice) of this workgroup: the XCD remap and the tile order of launch4 (hbase bit 30)
+__device__ __forceinline__ void ig4_tile(const IgemmHot& h, int hbase, int& tile_m, int& tile_n, int& tile_z) {
+  const int nx = h.ny_shift() >= 0 ? (1 << h.nx_shift()) : (int)gridDim.x, ny = h.ny_shift() >= 0 ? (1 << h.ny_shift()) : (int)gridDim.y;
+  const int nwg = h.nwg;
+  // hbase (round 5): a launch may cover only tiles [hbase, hbase + grid) of the layer -- the overlapped forward tail runs a
+  // layer as several one-dimensional launches of at most ISHAP_TAIL_WGS tiles, so that it never holds the LDS of more compute
+  // units than that and the backward chain on the caller's stream keeps the rest (launch4)
+  // bit 30 of hbase: the tile order WITHIN an XCD's share.  0: n-tiles fastest (an XCD holds few m-tiles x all weight panels:
+  // right when the activations dominate, the 64^2 / 128^2 maps); 1: m-tiles fastest, then K slices, n-tiles slowest (an XCD
+  // holds ONE or two weight panels x every m-tile and slice: right on the 32^2 / 16^2 maps, where the weights are most of the
+  // bytes and every XCD used to pull all of them: 29.4 MB fetched per 32^2 launch for 5.7 MB of operands, round 4 PMC pass)
+  const bool n_outer = (hbase >> 30) & 1;
+  const int lin = (hbase & 0x3fffffff) + blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
+  const int q = nwg >> 3, r = nwg & 7, xcd = lin & 7, pos = lin >> 3;
+  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+  if (n_outer) {                                   // launcher: only with power-of-two nx
+    tile_m = swz & (nx - 1);
+    const int rest = swz >> h.nx_shift();
+    tile_n = rest / h.ksplit;
+    tile_z = rest - tile_n * h.ksplit;
+  } else if (h.ny_shift() >= 0) {
+    tile_n = swz & (ny - 1);
+    tile_m = (swz >> h.ny_shift()) & (nx - 1);
+    tile_z = swz >> (h.ny_shift() + h.nx_shift());
+  } else {
+    tile_n = swz % ny;
+    tile_m = (swz / ny) % nx;
+    tile_z = swz / (ny * nx);
+  }
 }
 
 // HALVES = 2: two 8-wave teams with their own rings split the K range and meet in the epilogue (igemm2's two-team form: a
@@ -103,35 +136,7 @@ __global__ __launch_bounds__(512 * HALVES) void igemm4_kernel(const void* hX, co
         (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   int tile_m, tile_n, tile_z;
-  {
-    const int nx = h.ny_shift() >= 0 ? (1 << h.nx_shift()) : (int)gridDim.x, ny = h.ny_shift() >= 0 ? (1 << h.ny_shift()) : (int)gridDim.y;
-    const int nwg = h.nwg;
-    // hbase (round 5): a launch may cover only tiles [hbase, hbase + grid) of the layer -- the overlapped forward tail runs a
-    // layer as several one-dimensional launches of at most ISHAP_TAIL_WGS tiles, so that it never holds the LDS of more compute
-    // units than that and the backward chain on the caller's stream keeps the rest (launch4)
-    // bit 30 of hbase: the tile order WITHIN an XCD's share.  0: n-tiles fastest (an XCD holds few m-tiles x all weight panels:
-    // right when the activations dominate, the 64^2 / 128^2 maps); 1: m-tiles fastest, then K slices, n-tiles slowest (an XCD
-    // holds ONE or two weight panels x every m-tile and slice: right on the 32^2 / 16^2 maps, where the weights are most of the
-    // bytes and every XCD used to pull all of them: 29.4 MB fetched per 32^2 launch for 5.7 MB of operands, round 4 PMC pass)
-    const bool n_outer = (hbase >> 30) & 1;
-    const int lin = (hbase & 0x3fffffff) + blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-    const int q = nwg >> 3, r = nwg & 7, xcd = lin & 7, pos = lin >> 3;
-    const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    if (n_outer) {                                   // launcher: only with power-of-two nx
-      tile_m = swz & (nx - 1);
-      const int rest = swz >> h.nx_shift();
-      tile_n = rest / h.ksplit;
-      tile_z = rest - tile_n * h.ksplit;
-    } else if (h.ny_shift() >= 0) {
-      tile_n = swz & (ny - 1);
-      tile_m = (swz >> h.ny_shift()) & (nx - 1);
-      tile_z = swz >> (h.ny_shift() + h.nx_shift());
-    } else {
-      tile_n = swz % ny;
-      tile_m = (swz / ny) % nx;
-      tile_z = swz / (ny * nx);
-    }
-  }
+  ig4_tile(h, hbase, tile_m, tile_n, tile_z);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int ks_id = tile_z;                        // nbatch == 1 (launcher)
   const int H = h.H, HW = H * WD;
@@ -531,13 +536,266 @@ __global__ __launch_bounds__(512 * HALVES) void igemm4_kernel(const void* hX, co
 #endif
 }
 
-template <int BM, int BN, int WD, int NSTW, int NSTX, int HALVES = 1>
+// ---- 128-pixel x 32-channel tiles with one halo slab per 64-channel chunk (igemm4_halo_kernel) ----
+// A tile is R = 128 / WD whole image rows.  Per chunk the slab of image rows y0 - 1 .. y0 + R (SR = (R + 2) WD pixels x 64
+// channels, rows outside the image from g_zero_line4) is staged ONCE and read at all nine (dy, dx) shifts: a 64x64 tile stages
+// its R rows three times per chunk (once per dy).  Staged bytes per K-step (64 channels of K): 4 KB of weights + SR x 128 B / 9,
+// against 8 + 2.7 KB for a 64x64 tile of the same area -- -29 / -37 / -42 % on the 64 / 32 / 16-wide maps.
+// K runs in the order of the one-team 64x64 kernel (chunk, dy, dx, K half): each output element sees the same MFMA sequence,
+// so for the same K partition the outputs are bitwise those of igemm4_kernel<64, 64, WD, *, *, 1>.
+// A vertical shift moves a slab row by WD (a multiple of 8): `row & 7`, and with it the swizzle, is unchanged, and the fragment
+// address of (dy, dx) is that of (0, dx) + dy WD 128 B -- except for a lane whose dx shift leaves its image row, which reads the
+// zero row at every dy; the nine addresses per fragment are precomputed, a K-step costs one v_add per ds_read as in igemm4_kernel.
+// Loader schedule: weights DIST = NSTW - 1 K-steps ahead as in igemm4_kernel; the slab of chunk k + 1 goes to the other of the two
+// slab slots (dead once the reads of chunk k - 1 are done, i.e. from barrier 9k on) in the first XP iterations of chunk k, two
+// DMA instructions per iteration.  Every vmcnt is a compile-time count from ig4h_wait (a model of that issue sequence).
+constexpr int ig4h_min(int a, int b) { return a < b ? a : b; }
+// weight K-steps issued once barrier S is passed (S = -1: the prologue) in a slice of NS K-steps
+constexpr int ig4h_wupto(int S, int NS, int DIST, int PRO) { return ig4h_min(NS, ig4h_min(S + 1 + DIST, PRO + 2 * (S + 1))); }
+// slab DMA instructions issued after barrier S (the next chunk's slab, two per iteration)
+constexpr int ig4h_xpart(int S, int NCH, int XI) {
+  const int p = S % 9, XP = (XI + 1) / 2;
+  return (S / 9 + 1 < NCH && p < XP) ? ig4h_min(2, XI - 2 * p) : 0;
+}
+// loads issued by a loader wave up to and including the prologue (S = -1) / iteration S
+constexpr int ig4h_issued(int S, int NCH, int XI, int WI, int DIST, int PRO) {
+  int n = XI + WI * ig4h_wupto(S, 9 * NCH, DIST, PRO);
+  for (int t = 0; t <= S; ++t) n += ig4h_xpart(t, NCH, XI);
+  return n;
+}
+// vmcnt at the wait of K-step S: everything issued before it minus the last load S needs (its weights; at a chunk start, its slab)
+constexpr int ig4h_wait(int S, int NCH, int XI, int WI, int DIST, int PRO) {
+  const int NS = 9 * NCH;
+  int J = -1;                                      // the iteration (-1: prologue) that issued the weights of step S
+  while (ig4h_wupto(J, NS, DIST, PRO) <= S) ++J;
+  int posx = 0;
+  for (int t = 0; t < J; ++t) posx += ig4h_xpart(t, NCH, XI);
+  int need = XI + WI * (S + 1) + posx;
+  if (S % 9 == 0 && S > 0) {                       // the slab of chunk S / 9: issued by iterations S - 9 .. S - 9 + XP - 1
+    const int last = S - 9 + (XI + 1) / 2 - 1;
+    const int px = ig4h_issued(last, NCH, XI, WI, DIST, PRO);
+    need = need > px ? need : px;
+  }
+  return ig4h_issued(S - 1, NCH, XI, WI, DIST, PRO) - need;
+}
+// the loader runs a slice of any length >= 2 chunks as model slices of 2 and 3 chunks: their waits must match a long slice's
+constexpr bool ig4h_classes(int XI, int WI, int DIST, int PRO) {
+  for (int p = 0; p < 9; ++p) {
+    const int first = ig4h_wait(p, 2, XI, WI, DIST, PRO), mid = ig4h_wait(9 + p, 3, XI, WI, DIST, PRO), last = ig4h_wait(9 + p, 2, XI, WI, DIST, PRO);
+    if (first != ig4h_wait(p, 6, XI, WI, DIST, PRO) || last != ig4h_wait(45 + p, 6, XI, WI, DIST, PRO) || last != ig4h_wait(18 + p, 3, XI, WI, DIST, PRO)) return false;
+    for (int k = 1; k < 5; ++k)
+      if (mid != ig4h_wait(9 * k + p, 6, XI, WI, DIST, PRO)) return false;
+  }
+  return true;
+}
+template <class F, int... P>
+__device__ __forceinline__ void ig4h_unroll(F&& f, std::integer_sequence<int, P...>) {
+  (f(std::integral_constant<int, P>{}), ...);
+}
+
+template <int WD, int NSTW>
+__global__ __launch_bounds__(512) void igemm4_halo_kernel(const void* hX, const void* hWt, int hK, int hCin, int hldx, int hldw, int hH, int hW,
+                                                          int hksplit, int hnwg, unsigned hpacked, int hbase, IgemmArgs a) {
+  const IgemmHot h{(const half_t*)hX, (const half_t*)hWt, hK, hCin, hldx, hldw, hH, hW, hksplit, hnwg, hpacked};
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int BM = 128, BN = 32, BK = 64;
+  constexpr int R = BM / WD;                       // image rows per tile
+  constexpr int SR = (R + 2) * WD;                 // slab rows: image rows y0 - 1 .. y0 + R
+  constexpr int XI = SR / 8 / 4;                   // slab DMA instructions per loader wave per chunk
+  constexpr int XP = (XI + 1) / 2;                 // iterations that issue them
+  constexpr int WI = 1;                            // weight DMA instructions per loader wave per K-step (32 rows)
+  constexpr int WSLOT = BN * BK;                   // halfs
+  constexpr int XSLOT = (SR + 8) * BK;             // SR rows + the zero row (row SR) + padding to a 1 KiB multiple
+  constexpr int TMW = 32, TNW = 32, MT = 2, NT = 2;   // four MFMA waves along the pixels
+  constexpr int DIST = NSTW - 1;
+  constexpr int PRO = DIST < IG4_PRO ? DIST : IG4_PRO;
+  static_assert(WD % 8 == 0 && BM % WD == 0 && SR % 32 == 0, "a tile is whole image rows; the swizzle survives a shift by WD");
+  static_assert(ig4h_classes(XI, WI, DIST, PRO), "a slice's first / middle / last chunks wait as the model slices the loader uses");
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+  half_t* const sW = reinterpret_cast<half_t*>(smem_raw);   // [NSTW][WSLOT]
+  half_t* const sX = sW + NSTW * WSLOT;                      // [2][XSLOT]
+  const bool loader = wave8 >= 4;
+  const int wave = wave8 & 3;
+  IG_STAMP(0, wave8 == 0);
+  if (tid < 2 * 8)                                 // the zero rows of both slab slots
+    *reinterpret_cast<f32x4*>(sX + (tid >> 3) * XSLOT + SR * BK + (tid & 7) * 8) = (f32x4){0.f, 0.f, 0.f, 0.f};
+  int tile_m, tile_n, tile_z;
+  ig4_tile(h, hbase, tile_m, tile_n, tile_z);
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const int ks_id = tile_z;
+  const int H = h.H, HW = H * WD;
+  const int NC = h.Cin / BK;
+  // this K slice: whole chunks [c0, c0 + nch)
+  const int per = (NC + h.ksplit - 1) / h.ksplit;
+  const int c0 = min(NC, ks_id * per), nch = min(NC, c0 + per) - c0;
+  const int ns = 9 * nch;
+  const int n_img = h.hw_shift() >= 0 ? (m0 >> h.hw_shift()) : m0 / HW;
+  const int y0 = (m0 - n_img * HW) / WD;
+  __syncthreads();                                 // the zero rows are in place
+
+  f32x4 acc[NT][MT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  IG_STAMP(1, wave8 == 0);
+  if (loader) {
+    using std::integral_constant;
+    const int lrow = lane >> 3, pch = lane & 7;
+    // slab row sr = pixel (y0 - 1 + sr / WD, sr % WD); a DMA instruction covers 8 rows of one image row, so `ok` is wave-uniform
+    const half_t* xp[XI];
+    int xinc[XI];                                  // to the next chunk: 64 channels on, or stay on the zero line
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      const int sr = (wave * XI + i) * 8 + lrow;
+      const int yy = y0 - 1 + sr / WD, xx = sr % WD;
+      const int sc = (pch ^ (sr & 7)) * 8;
+      const bool ok = (unsigned)yy < (unsigned)H;
+      const long long pix = h.ups() ? (long long)n_img * (HW >> 2) + (yy >> 1) * (WD >> 1) + (xx >> 1) : (long long)n_img * HW + yy * WD + xx;
+      xp[i] = ok ? h.X + pix * h.ldx + c0 * BK + sc : (const half_t*)g_zero_line4 + sc;
+      xinc[i] = ok ? BK : 0;
+    }
+    const int wrow = wave * 8 + lrow;
+    const half_t* wp = h.Wt + (long long)(n0 + wrow) * h.ldw + (pch ^ ((wrow >> 1) & 7)) * 8 + c0 * BK;
+    int hws = 0;                                   // weight ring slot of the issue head
+    unsigned hx = 0;                               // slab slot (0 / 1) the next slab goes to
+    auto issue_w = [&](auto U) __attribute__((always_inline)) {   // weights of K-step U (its tap: U % 9)
+      IG4_DMA(wp, sW + hws * WSLOT + wave * 8 * BK);
+      hws = hws + 1 == NSTW ? 0 : hws + 1;
+      wp += decltype(U)::value % 9 == 8 ? (long long)BK - 8LL * h.Cin : (long long)h.Cin;
+    };
+    auto issue_x = [&](auto I) __attribute__((always_inline)) {   // slab instruction I of the next chunk
+      constexpr int i = decltype(I)::value;
+      IG4_DMA(xp[i], sX + hx * XSLOT + (wave * XI + i) * 8 * BK);
+      xp[i] += xinc[i];
+      if constexpr (i == XI - 1) hx ^= 1u;
+    };
+    // prologue: the first chunk's slab, then PRO weight steps
+    if (nch > 0) {
+      ig4h_unroll(issue_x, std::make_integer_sequence<int, XI>{});
+      ig4h_unroll(issue_w, std::make_integer_sequence<int, PRO>{});
+    }
+    // iteration S of the model slice of NCH chunks: wait for K-step S, barrier, issue what the model issues after it
+    auto iter = [&](auto SC, auto NCHC) __attribute__((always_inline)) {
+      constexpr int S = decltype(SC)::value, NCH = decltype(NCHC)::value;
+      constexpr int cnt = ig4h_wait(S, NCH, XI, WI, DIST, PRO);
+      static_assert(cnt >= 0 && cnt <= 63, "vmcnt range");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cnt) : "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      constexpr int w0 = ig4h_wupto(S - 1, 9 * NCH, DIST, PRO), w1 = ig4h_wupto(S, 9 * NCH, DIST, PRO);
+      ig4h_unroll([&](auto U) __attribute__((always_inline)) { issue_w(integral_constant<int, w0 + decltype(U)::value>{}); },
+                  std::make_integer_sequence<int, w1 - w0>{});
+      constexpr int xn = ig4h_xpart(S, NCH, XI), xi0 = 2 * (S % 9);
+      ig4h_unroll([&](auto I) __attribute__((always_inline)) { issue_x(integral_constant<int, xi0 + decltype(I)::value>{}); },
+                  std::make_integer_sequence<int, xn>{});
+    };
+    // the first chunk, the middle ones and the last wait as chunk 0 of a 2-chunk slice, chunk 1 of 3 and chunk 1 of 2 (ig4h_classes)
+    auto chunk = [&](auto BASE, auto NCHC) __attribute__((always_inline)) {
+      ig4h_unroll([&](auto P) __attribute__((always_inline)) { iter(integral_constant<int, decltype(BASE)::value + decltype(P)::value>{}, NCHC); },
+                  std::make_integer_sequence<int, 9>{});
+    };
+    if (nch == 1) {
+      chunk(integral_constant<int, 0>{}, integral_constant<int, 1>{});
+    } else if (nch > 1) {
+      chunk(integral_constant<int, 0>{}, integral_constant<int, 2>{});
+      for (int k = 1; k + 1 < nch; ++k) chunk(integral_constant<int, 9>{}, integral_constant<int, 3>{});
+      chunk(integral_constant<int, 9>{}, integral_constant<int, 2>{});
+    }
+  } else {
+    // ---- MFMA waves: wave w owns pixels 32 w .. 32 w + 31 of the tile x all 32 channels ----
+    unsigned wo[2][NT], xo[3][3][2][MT];           // [dy][dx][K half][j]: byte addresses within slot 0 of each ring
+    const unsigned wbase = (unsigned)(unsigned long long)(lds_void4*)sW, xbase = (unsigned)(unsigned long long)(lds_void4*)sX;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const int ch = (lane >> 4) + 4 * kk;
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        const int row = i * 16 + (lane & 15);
+        wo[kk][i] = wbase + 2 * (row * BK + ((ch ^ ((row >> 1) & 7)) * 8));
+      }
+#pragma unroll
+      for (int j = 0; j < MT; ++j) {
+        const int pl = wave * TMW + j * 16 + (lane & 15);
+        const int x = pl % WD;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 3; ++dx) {
+            const int xs = x + dx - 1;
+            const int row = (xs >= 0 && xs < WD) ? pl + dy * WD + dx - 1 : SR;     // SR = the zero row
+            xo[dy][dx][kk][j] = xbase + 2 * (row * BK + (row == SR ? ch * 8 : ((ch ^ (row & 7)) * 8)));
+          }
+      }
+    }
+    half8 xa[MT], wa[NT], xb[MT], wb[NT];
+    unsigned sw_off = 0, sx_off = 0;               // byte offsets of the current weight / slab slots
+    auto read_half = [&](const unsigned (&xs)[2][MT], int kk, half8 (&xf)[MT], half8 (&wf)[NT]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int j = 0; j < MT; ++j) asm volatile("ds_read_b128 %0, %1" : "=v"(xf[j]) : "v"(xs[kk][j] + sx_off) : "memory");
+#pragma unroll
+      for (int i = 0; i < NT; ++i) asm volatile("ds_read_b128 %0, %1" : "=v"(wf[i]) : "v"(wo[kk][i] + sw_off) : "memory");
+    };
+    auto wait_frags = [&](auto pending, half8 (&xf)[MT], half8 (&wf)[NT]) __attribute__((always_inline)) {
+      asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(xf[0]), "+v"(xf[1]), "+v"(wf[0]), "+v"(wf[1]) : "n"(decltype(pending)::value) : "memory");
+    };
+    auto mfma_half = [&](half8 (&xf)[MT], half8 (&wf)[NT]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf[j], acc[i][j], 0, 0, 0);
+    };
+    using std::integral_constant;
+    // one K-step at tap T = 3 dy + dx (igemm4_kernel's burst form): second half read under the MFMAs of the first, first half of
+    // the next step read right after its barrier
+    auto step = [&](auto TC, int s) __attribute__((always_inline)) {
+      constexpr int T = decltype(TC)::value, TN = (T + 1) % 9;
+      read_half(xo[T / 3][T % 3], 1, xb, wb);
+      wait_frags(integral_constant<int, MT + NT>{}, xa, wa);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_half(xa, wa);
+      __builtin_amdgcn_sched_barrier(0);
+      wait_frags(integral_constant<int, 0>{}, xb, wb);
+      sw_off = sw_off + WSLOT * 2 == NSTW * WSLOT * 2 ? 0u : sw_off + WSLOT * 2;
+      if constexpr (T == 8) sx_off ^= XSLOT * 2;
+      if (s + 1 < ns) {
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        read_half(xo[TN / 3][TN % 3], 0, xa, wa);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      mfma_half(xb, wb);
+    };
+    if (ns > 0) __builtin_amdgcn_s_barrier();      // step 0 has landed (every wave passes ns barriers)
+    asm volatile("" ::: "memory");
+    IG_STAMP(2, wave8 == 0);
+    if (ns > 0) read_half(xo[0][0], 0, xa, wa);
+    for (int s = 0; s < ns; s += 9)
+      ig4h_unroll([&](auto TC) __attribute__((always_inline)) { step(TC, s + decltype(TC)::value); }, std::make_integer_sequence<int, 9>{});
+  }
+  IG_STAMP(3, wave8 == 0);
+  IG_STAMP(4, wave8 == 0);
+  igemm_epilogue<MT, NT, TMW, TNW, BN, 512, 4>(a, acc, m0, n0, wave, 0, lane, 0, ks_id, reinterpret_cast<float*>(smem_raw), !loader, -1);
+#endif
+}
+
+// HALO: igemm4_halo_kernel<WD, NSTW> (BM = 128, BN = 32, two slab slots of (BM / WD + 2) image rows)
+template <int BM, int BN, int WD, int NSTW, int NSTX, int HALVES = 1, bool HALO = false>
 static int launch4(const IgemmArgs& a, hipStream_t s) {
-  constexpr size_t ring = (size_t)HALVES * (NSTW * BN * 64 + NSTX * (BM + 8) * 64) * sizeof(half_t);
+  static_assert(!HALO || (BM == 128 && BN == 32 && NSTX == 2 && HALVES == 1), "the halo kernel's tile");
+  constexpr int XROWS = HALO ? (BM / WD + 2) * WD : BM;      // pixel rows of a slab slot
+  constexpr size_t ring = (size_t)HALVES * (NSTW * BN * 64 + NSTX * (XROWS + 8) * 64) * sizeof(half_t);
   constexpr size_t epi = (size_t)HALVES * BM * (BN + 4) * 4 + (size_t)BM * (BN + 8) * 2 + 16384;      // staged epilogue: fp32 tile(s) + fp16 tile + partial sums
   static_assert((ring > epi ? ring : epi) <= 163840, "LDS");
   const size_t smem = ring > epi ? ring : epi;
-  auto kern = igemm4_kernel<BM, BN, WD, NSTW, NSTX, HALVES>;
+  auto kern = [] {
+    if constexpr (HALO) return igemm4_halo_kernel<WD, NSTW>;
+    else return igemm4_kernel<BM, BN, WD, NSTW, NSTX, HALVES>;
+  }();
   ISHAP_TRY(ishap_set_max_lds((const void*)kern, (int)smem));
   const dim3 grid(a.M / BM, ceil_div(a.N, BN), a.ksplit);
   IgemmArgs b = a;
@@ -661,12 +919,31 @@ bool igemm4_tall_tiles(const IgemmArgs& a, bool big) {
   const long long tiles = (long long)(a.M / 128) * ((a.N + 63) / 64);
   return tiles >= 224 && tiles <= 512;
 }
+#ifndef IG4_HALO_W
+#define IG4_HALO_W 6
+#endif
+// 128-pixel x 32-channel halo tiles (igemm4_halo_kernel) where the 64x64 tiles of the same launch are 224 ... 256 workgroups (the
+// same count: same tile area) and the K slices are whole 64-channel chunks, at least two of them (a one-chunk slice pays a whole
+// slab fill before its first MFMA).  ISHAP_IG4_HALO=0: the 64x64 / 128x64 choices below everywhere.
+bool igemm4_halo_tiles(const IgemmArgs& a, bool big) {
+  static const int on = [] { const char* e = getenv("ISHAP_IG4_HALO"); return e ? atoi(e) : 1; }();
+  if (big || !on || a.K2 != 0 || (a.W != 64 && a.W != 32 && a.W != 16) || a.M % 128 != 0 || (a.H * a.W) % 128 != 0 || a.N % 32 != 0) return false;
+  const int nc = a.Cin / 64;
+  if (nc % a.ksplit != 0 || nc / a.ksplit < 2) return false;
+  const long long tiles = (long long)(a.M / 128) * (a.N / 32) * a.ksplit;
+  return tiles >= 224 && tiles <= 256;
+}
 int igemm4_launch_main(const IgemmArgs& a, bool big, hipStream_t s) {
   if (big) {
     if (a.W == 128) return launch4<128, 128, 128, IG4_BIG_W, IG4_BIG_X>(a, s);
     if (a.W == 64) return launch4<128, 128, 64, IG4_BIG_W, IG4_BIG_X>(a, s);
     if (a.W == 32) return launch4<128, 128, 32, IG4_BIG_W, IG4_BIG_X>(a, s);
     return launch4<128, 128, 16, IG4_BIG_W, IG4_BIG_X>(a, s);
+  }
+  if (igemm4_halo_tiles(a, big)) {
+    if (a.W == 64) return launch4<128, 32, 64, IG4_HALO_W, 2, 1, true>(a, s);
+    if (a.W == 32) return launch4<128, 32, 32, IG4_HALO_W, 2, 1, true>(a, s);
+    return launch4<128, 32, 16, IG4_HALO_W, 2, 1, true>(a, s);
   }
   if (igemm4_tall_tiles(a, big)) return launch4<128, 64, 64, IG4_SMALL_W, IG4_SMALL_X>(a, s);
 #ifdef IG4_TALL_PROBE      // harness only (tools/experiments/tall_probe.sh; profiles/round6_tall_tiles_sliced_launches.txt): 128 x 64 tiles on the 32^2 / 16^2 maps

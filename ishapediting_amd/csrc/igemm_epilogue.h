@@ -51,10 +51,10 @@ __device__ __forceinline__ bool igemm_epilogue_is_staged(const IgemmArgs& a, int
          (!a.gb_x || (a.N & 31) == 0);
 }
 
-template <int MT, int NT, int TMW, int TNW, int BN, int T>
+template <int MT, int NT, int TMW, int TNW, int BN, int T, int WM = 2>
 __device__ __forceinline__ void igemm_epilogue_staged(const IgemmArgs& a, f32x4 (&acc)[NT][MT], int m0, int n0, int wm, int wn,
                                                       int lane, int batch, float* lds_f, bool active, int team2) {
-  constexpr int BM_T = 2 * TMW;
+  constexpr int BM_T = WM * TMW;
   constexpr int LDF = BN + 4;                      // fp32 tile pitch: conflict-free ds_write_b128 of the fragments and row reads
   constexpr int LDH = BN + 8;                      // fp16 tile pitch (halfs)
   constexpr int CPRW = BN / 8;                     // 8-channel chunks per tile row
@@ -262,7 +262,8 @@ __device__ __forceinline__ void igemm_epilogue_staged(const IgemmArgs& a, f32x4 
 // `team2` >= 0 (two-team kernels on the staged path only): this wave belongs to team `team2`, and BOTH teams hold partial
 // accumulators that the staged epilogue adds up (team 0 + team 1) while it finishes the rows -- the separate merge pass
 // through LDS (two barriers, 1 100 cycles of a 64x64 launch) is gone.  -1: `acc` is complete in the waves flagged `active`.
-template <int MT, int NT, int TMW, int TNW, int BN, int STAGE_THREADS = 0>
+// WM: MFMA waves along the pixels (wm = 0 .. WM - 1), each TMW pixels x TNW channels; the tile is WM * TMW pixels.
+template <int MT, int NT, int TMW, int TNW, int BN, int STAGE_THREADS = 0, int WM = 2>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[NT][MT], int m0, int n0, int wm, int wn,
                                                int lane, int batch, int ks_id, float* lds_f, bool active = true, int team2 = -1) {
   // `active` = false: a loader wave of a producer/consumer kernel -- it owns no outputs but must take part in the
@@ -276,12 +277,12 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
   const float* const bias2 = a.bias2;
   const half_t* const resp = a.res;
   const int HW = a.H * a.W;
-  constexpr int BM_T = 2 * TMW;                  // rows of the workgroup tile
+  constexpr int BM_T = WM * TMW;                 // rows of the workgroup tile
   constexpr int LDT = BN + 8;                    // staged-tile row pitch in halfs (conflict-free 8-byte fragment writes)
   half_t* const out16 = (half_t*)a.out + (long long)batch * a.bso;
   if constexpr (STAGE_THREADS > 0) {
     if (igemm_epilogue_is_staged(a, batch)) {
-      igemm_epilogue_staged<MT, NT, TMW, TNW, BN, STAGE_THREADS>(a, acc, m0, n0, wm, wn, lane, batch, lds_f, active, team2);
+      igemm_epilogue_staged<MT, NT, TMW, TNW, BN, STAGE_THREADS, WM>(a, acc, m0, n0, wm, wn, lane, batch, lds_f, active, team2);
       return;
     }
   }
@@ -508,12 +509,12 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
     if (t < BN * 2) {
       const int nl = t >> 1;
       if (n0 + nl < a.N) {
-        // the two wm waves, each about its own pivot P over nW = 16 * MT pixels, brought to pivot 0 in double:
+        // the WM wm waves, each about its own pivot P over nW = 16 * MT pixels, brought to pivot 0 in double:
         //   sum x = s + nW P,   sum x^2 = q + 2 P s + nW P^2
         constexpr double nW = 16.0 * MT;
         double v = 0.0;
 #pragma unroll
-        for (int w = 0; w < 2; ++w) {
+        for (int w = 0; w < WM; ++w) {
           const double sw = (double)lds_f[(w * BN + nl) * 3 + 0], qw = (double)lds_f[(w * BN + nl) * 3 + 1];
           const double P = (double)lds_f[(w * BN + nl) * 3 + 2];
           v += (t & 1) ? qw + P * (2.0 * sw + nW * P) : sw + nW * P;
