@@ -356,12 +356,19 @@ int ishap_mesh_occupancy(const float* verts, const int* tris, long long ntris, c
  * Brackets every implicit-GEMM launch with HIP events on its own stream between begin and end.
  * out[v*3+{0,1,2}] = {launches, total ms, algorithmic FLOPs}; one v per kernel symbol: 0 conv3x3 128^2 tile,
  * 1 conv3x3 64^2 tile, 2 GEMM 128^2 tile, 3 GEMM 64^2 tile, 4 conv3x3 64^2 tile two-team, 5 small-map GEMM kernel,
- * 6 register-staged stem kernel, 7 the 3x3 kernel's 128x32 halo tiles (csrc/igemm.hip lists 8-12). */
+ * 6 register-staged stem kernel, 7 the 3x3 kernel's 128x32 halo tiles (csrc/igemm.hip lists 8-12; ishap_igemm_plan). */
 int ishap_profile_begin(void);
 int ishap_profile_end(double* out, int nvar);
 /* Per-shape CSV ("M,N,K,conv3,tile,ksplit,launches,main_ms,reduce_ms,gflop" lines) of the same records; call
  * before the next ishap_profile_begin.  Returns the number of lines, -2 when `cap` is too small. */
 int ishap_profile_shapes(char* buf, int cap);
+/* The kernel choice of one convolution / GEMM launch, on the host, no GPU needed: the K split conv_op picks and what
+ * igemm_launch then runs.  M = N*H*W output pixels (per batch entry), cin channels per tap, taps 9 (3x3) or 1, K2 channels of a
+ * folded 1x1 second source, H x W the output map, pending: the consumer adds the K slices up, epilogue_sums: GroupNorm
+ * statistics or GroupNorm-backward sums in the epilogue.  Writes the K split, the ishap_profile_end variant and the kernel
+ * instance as a kernel trace names it (e.g. "igemm4_kernel<64, 64, 32, 4, 3, 1>").  0, or -2 when `kernel_cap` is too small. */
+int ishap_igemm_plan(int M, int cin, int cout, int taps, int K2, int H, int W, int nbatch, int pending, int epilogue_sums,
+                     int* ksplit, int* prof_slot, char* kernel, int kernel_cap);
 
 #ifdef __cplusplus
 }

@@ -263,8 +263,75 @@ struct IgemmArgs {
 // set (non-null) by igemm.hip around a launch while ishap_profile_begin/end is active: the kernel launchers then attach
 // these events to the dispatch itself (hipExtLaunchKernelGGL), so their elapsed time is the kernel's own duration
 extern hipEvent_t g_igemm_prof_start, g_igemm_prof_stop;
+
+// The LDS-DMA kernels' launch (igemm2.hip, igemm4.hip): IgemmHot first, then the kernel's own scalars `extra`, then the
+// IgemmArgs copy carrying the shifts.  grid: the layer's tiles (shifts, IgemmHot::nwg); launch: the grid dispatched (igemm4's
+// chunked form: a 1-D share of them).  packed_hi: bits 25+ of IgemmHot::packed (igemm4: the second source's 64-channel chunks).
+template <typename Kern, typename... Extra>
+static int igemm_dma_launch(Kern kern, dim3 grid, dim3 launch, dim3 block, size_t smem, hipStream_t s, const IgemmArgs& a,
+                            unsigned packed_hi, Extra... extra) {
+  auto lg2 = [](int v) { int k = 0; while ((1 << k) < v) ++k; return (1 << k) == v ? k : -1; };   // -1: not a power of two (or 0)
+  IgemmArgs b = a;
+  b.w_shift = lg2(a.W);
+  b.hw_shift = lg2(a.H * a.W);
+  if (b.w_shift < 0 || b.hw_shift < 0) b.w_shift = b.hw_shift = -1;
+  b.nx_shift = lg2((int)grid.x);
+  b.ny_shift = lg2((int)grid.y);
+  if (b.nx_shift < 0 || b.ny_shift < 0) b.nx_shift = b.ny_shift = -1;
+  const int nwg = (int)(grid.x * grid.y * grid.z);
+  const unsigned packed = (unsigned)(b.w_shift & 0x3f) | (unsigned)(b.hw_shift & 0x3f) << 6 | (unsigned)(b.nx_shift & 0x3f) << 12 |
+                          (unsigned)(b.ny_shift & 0x3f) << 18 | (b.ups ? 1u << 24 : 0u) | packed_hi;
+  if (g_igemm_prof_start) hipExtLaunchKernelGGL(kern, launch, block, smem, s, g_igemm_prof_start, g_igemm_prof_stop, 0, (const void*)b.X,
+                                                (const void*)b.Wt, b.K, b.Cin, b.ldx, b.ldw, b.H, b.W, b.ksplit, nwg, packed, extra..., b);
+  else hipLaunchKernelGGL(kern, launch, block, smem, s, (const void*)b.X, (const void*)b.Wt, b.K, b.Cin, b.ldx, b.ldw, b.H, b.W, b.ksplit,
+                          nwg, packed, extra..., b);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- which kernel runs a convolution / GEMM launch (igemm.hip: igemm_plan_ksplit, igemm_plan) ----
+// Every instance family of the implicit GEMM; igemm_launch runs one per launch, igemm_prof_slot files it for the profiler.
+enum class IgemmForm {
+  skinny,          // igemm_skinny_kernel (igemm_skinny.hip): small maps, one launch, 16 waves split K
+  reg32,           // igemm_kernel: register-staged, BK = 32 (K not a multiple of 64; 64x64 tiles)
+  ig2_128,         // igemm2_kernel (igemm2.hip, LDS-DMA ring, BK = 64): 128x128 tiles
+  ig2_64,          //   64x64 tiles
+  ig2_teams,       //   64x64 two-team (3x3)
+  ig4_128,         // igemm4_kernel (igemm4.hip, 3x3, activation slab staged once per dy): 128x128 tiles
+  ig4_64,          //   64x64 tiles, 6-slot weight ring
+  ig4_64_ring4,    //   64x64 tiles, 4-slot weight ring (slices of 9-12 K-steps)
+  ig4_teams,       //   64x64 two-team
+  ig4_w8,          //   64x64 tiles on the 8x8 maps (one tile = one image, sliced launches)
+  ig4_tall,        //   128x64 tiles on the 64-wide maps
+  ig4_halo,        // igemm4_halo_kernel: 128x32 tiles, one slab per 64-channel chunk for all nine taps
+};
+struct IgemmPlan {
+  IgemmForm form;
+  bool big;        // 128-row tiles of the generic families (ig2_128, ig4_128): the shape profile's `tile` column
+};
+// the selection switches, read once from the environment (defaults in brackets; DESIGN.md lists them)
+struct IgemmSwitches {
+  int igemm4;      // ISHAP_IGEMM4 [2]: 0 = never igemm4, 1 = its 128x128 tiles only, 2 = every shape it takes
+  int ig4_teams;   // ISHAP_IG4_TEAMS [2]: 2 = two-team and 128x64 tiles, 1 = 128x64 tiles only, 0 = neither
+  int ig4_halo;    // ISHAP_IG4_HALO [1]: 0 = no halo tiles
+  int halves;      // ISHAP_HALVES [2]: 2 = igemm2's two-team form
+  int skinny;      // ISHAP_SKINNY [1]: 0 = the tiled kernel + reduce instead of the skinny kernel
+  int g1_slices;   // ISHAP_G1_SLICES [1]: 0 = no sliced 1x1 GEMMs on the 8x8 maps
+  int big_min;     // ISHAP_BIG_MIN [192]: 128x128 workgroups from which the 128-tile is taken
+};
+const IgemmSwitches& igemm_switches();
+// K slices of a launch (pending: the consumer adds the slices up, no reduce launch); a.ksplit is not read
+int igemm_plan_ksplit(const IgemmArgs& a, bool pending, const IgemmSwitches& sw = igemm_switches());
+// the form of a launch whose a.ksplit is set; no HIP runtime call
+IgemmPlan igemm_plan(const IgemmArgs& a, const IgemmSwitches& sw = igemm_switches());
+int igemm_prof_slot(const IgemmPlan& p, bool conv3);    // ishap_profile_end's variant index
+// the main kernel of a planned launch (no split-K reduce); with `name` set: only the kernel's name, no HIP call
+int igemm_launch_main(const IgemmArgs& a, const IgemmPlan& p, hipStream_t s, std::string* name = nullptr);
+int igemm2_launch(const IgemmArgs& a, IgemmForm f, hipStream_t s, std::string* name);   // igemm2.hip: ig2_* forms
+int igemm4_launch(const IgemmArgs& a, IgemmForm f, hipStream_t s, std::string* name);   // igemm4.hip: ig4_* forms
+int igemm_skinny_launch(const IgemmArgs& a, int mt, hipStream_t s, std::string* name = nullptr);   // mt: pixels / 16 per workgroup, 0 = pick
+bool igemm_skinny_applicable(const IgemmArgs& a);
+template <typename... T>
+std::string igemm_kernel_name(const char* fmt, T... v) { char b[96]; snprintf(b, sizeof b, fmt, v...); return b; }   // launchers' `name`
 int igemm_launch(const IgemmArgs& a, hipStream_t s);
 int igemm_reduce_launch(const IgemmArgs& a, hipStream_t s);
-int igemm4_small_map_slices(const IgemmArgs& a);  // igemm4.hip: K slices of its sliced launch on an 8x8 map (consumer adds them up), 0 = not taken
-// picks a split so the grid fills the chip; returns workspace floats needed
-int igemm_pick_ksplit(int M, int N, int K, int nbatch, bool pending = false);   // pending: the consumer adds the slices up (no reduce launch)

@@ -274,11 +274,11 @@ extern "C" int ishap_profile_begin(void) {
   g_prof_on = true;
   return 0;
 }
-// out[v*3 + {0,1,2}] = {launches, total milliseconds, algorithmic FLOPs} for variant v:
-//   0 conv3x3 128x128 tile, 1 conv3x3 64x64 tile, 2 GEMM 128x128 tile, 3 GEMM 64x64 tile, 4 conv3x3 64x64 two-team,
-//   5 small-map (skinny) GEMM kernel, 6 register-staged (BK = 32) kernel, 7 unused (was conv3_small, removed in round 6),
-//   8 / 9 / 10 the dx-reuse conv kernel (igemm4.hip): 128x128 tile / 64x64 tile / 64x64 two-team, 11 its sliced launches on
-//   the 8x8 maps, 12 its 128x64 tiles; 7 its 128x32 halo tiles (igemm4_halo_kernel; the slot of the removed conv3_small)
+// out[v*3 + {0,1,2}] = {launches, total milliseconds, algorithmic FLOPs} for variant v (igemm_prof_slot):
+//   0 / 1 igemm2 conv3x3 128x128 / 64x64 tile, 2 / 3 igemm2 GEMM 128x128 / 64x64 tile, 4 igemm2 conv3x3 64x64 two-team,
+//   5 small-map (skinny) kernel, 6 register-staged (BK = 32) kernel, 7 igemm4's 128x32 halo tiles (igemm4_halo_kernel),
+//   8 / 9 / 10 igemm4 128x128 tile / 64x64 tile (either ring) / 64x64 two-team, 11 igemm4's sliced launches on the 8x8 maps,
+//   12 igemm4's 128x64 tiles
 extern "C" int ishap_profile_end(double* out, int nvar) {
   g_prof_on = false;
   for (int i = 0; i < nvar * 3; ++i) out[i] = 0.0;
@@ -319,84 +319,29 @@ extern "C" int ishap_profile_shapes(char* buf, int cap) {
   return (int)agg.size();
 }
 
-int igemm2_launch_main(const IgemmArgs& a, bool big, hipStream_t s);   // igemm2.hip (LDS-DMA ring, BK = 64)
-bool igemm2_two_teams(const IgemmArgs& a, bool big);
-bool igemm4_applicable(const IgemmArgs& a, bool big);                  // igemm4.hip (3x3 with each activation slab staged once for dx = -1, 0, +1)
-bool igemm4_two_teams(const IgemmArgs& a, bool big);
-bool igemm4_tall_tiles(const IgemmArgs& a, bool big);
-bool igemm4_halo_tiles(const IgemmArgs& a, bool big);
-int igemm4_launch_main(const IgemmArgs& a, bool big, hipStream_t s);
-// ISHAP_IGEMM4: 0 = never, 1 = 128x128 tiles only, 2 (default) = every shape igemm4 takes
-static bool igemm4_wanted(const IgemmArgs& a, bool big) {
-  static const int use4 = [] { const char* e = getenv("ISHAP_IGEMM4"); return e ? atoi(e) : 2; }();
-  return use4 && (use4 > 1 || big) && igemm4_applicable(a, big);
-}
-
-template <int BM, int BN, int BK, int WM, int WN, bool CONV3>
-static int launch_cfg(const IgemmArgs& a, hipStream_t s) {
-  int prof_slot = -1;
-  auto fire = [&]() -> int {
-    if constexpr (BK == 64) {
-      if (CONV3 && igemm4_wanted(a, BM == 128)) return igemm4_launch_main(a, BM == 128, s);
-      return igemm2_launch_main(a, BM == 128, s);
-    } else {
-      // K not a multiple of 64 (tiny configurations; the full model's stem is padded to 128 channels): the register-staged kernel
-      constexpr size_t smem = 2 * (size_t)(BM + BN) * BK * sizeof(half_t);
-      auto kern = igemm_kernel<BM, BN, BK, WM, WN, CONV3>;
-      ISHAP_TRY(ishap_set_max_lds((const void*)kern, (int)smem));
-      const dim3 grid(a.M / BM, ceil_div(a.N, BN), a.nbatch * a.ksplit);
-      if (g_igemm_prof_start) hipExtLaunchKernelGGL(kern, grid, dim3(256), smem, s, g_igemm_prof_start, g_igemm_prof_stop, 0, a);
-      else hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
-      return 0;
-    }
-  };
-  if (g_prof_on) {
-    ProfRec r;
-    r.a = prof_event(); r.b = prof_event(); r.c = nullptr;
-    r.flops = 2.0 * a.M * a.N * a.K * a.nbatch * a.flops_scale;
-    // one variant per kernel symbol: 0/1 conv 128/64 tile, 2/3 GEMM 128/64 tile, 4 two-team 64-tile conv,
-    // 5 small-map kernel (set in igemm_launch), 6 register-staged BK=32 kernel (stem conv)
-    r.variant = BK == 64 ? ((CONV3 ? 0 : 2) + (BM == 128 ? 0 : 1)) : 6;
-    if (BK == 64 && igemm2_two_teams(a, BM == 128)) r.variant = 4;
-    if (BK == 64 && CONV3 && igemm4_wanted(a, BM == 128))
-      r.variant = BM == 128 ? 8 : (a.W == 8 ? 11 : igemm4_halo_tiles(a, false) ? 7 : (igemm4_tall_tiles(a, false) ? 12 : (igemm4_two_teams(a, false) ? 10 : 9)));
-    r.M = a.M * a.nbatch; r.N = a.N; r.K = a.K; r.conv3 = CONV3; r.big = BM == 128; r.ksplit = a.ksplit;
-    g_igemm_prof_start = r.a; g_igemm_prof_stop = r.b;      // attached to the dispatch: kernel begin / end timestamps
-    const int rc = fire();
-    g_igemm_prof_start = nullptr; g_igemm_prof_stop = nullptr;
-    if (rc) return rc;
-    prof_slot = (int)g_prof.size();
-    g_prof.push_back(r);
-  } else {
-    ISHAP_TRY(fire());
-  }
-  ISHAP_CHECK_HIP(hipGetLastError());
-  if (a.ksplit > 1 && !a.defer_reduce) {
-    const unsigned rblocks = (unsigned)((long long)a.nbatch * (a.M / 16) * ((a.N + 63) / 64));
-    hipLaunchKernelGGL(igemm_splitk_reduce, dim3(rblocks), dim3(256), 0, s, a);
-    ISHAP_CHECK_HIP(hipGetLastError());
-    if (prof_slot >= 0) {
-      g_prof[prof_slot].c = prof_event();
-      (void)hipEventRecord(g_prof[prof_slot].c, s);
-    }
-  }
-  return 0;
+// ---- the launch plan: K slices and kernel form of every implicit-GEMM launch (no HIP runtime call) ----
+const IgemmSwitches& igemm_switches() {
+  static const IgemmSwitches sw = [] {
+    auto env = [](const char* k, int dflt) { const char* e = getenv(k); return e ? atoi(e) : dflt; };
+    return IgemmSwitches{env("ISHAP_IGEMM4", 2), env("ISHAP_IG4_TEAMS", 2), env("ISHAP_IG4_HALO", 1), env("ISHAP_HALVES", 2),
+                         env("ISHAP_SKINNY", 1), env("ISHAP_G1_SLICES", 1), env("ISHAP_BIG_MIN", 192)};
+  }();
+  return sw;
 }
 
 // Tile and split-K policy.  256 CUs: prefer the 128x128 tile when it alone yields >= ~200 workgroups, otherwise the
 // 64x64 tile; split K while the grid stays below ~224 workgroups (the small-map, weight-streaming layers),
 // keeping >= 6 K-steps of 64 per slice so the fp32 partial traffic stays below the weight traffic.
-static bool igemm_use_big(int M, int N, int nbatch) {
-  if (M % 128 != 0 || N < 128) return false;
-  long long blocks = (long long)(M / 128) * ceil_div(N, 128) * nbatch;
-  static const int big_min = [] { const char* e = getenv("ISHAP_BIG_MIN"); return e ? atoi(e) : 192; }();
-  return blocks >= big_min;
+static bool use_big(const IgemmArgs& a, const IgemmSwitches& sw) {
+  if (a.M % 128 != 0 || a.N < 128) return false;
+  return (long long)(a.M / 128) * ceil_div(a.N, 128) * a.nbatch >= sw.big_min;
 }
-int igemm_pick_ksplit(int M, int N, int K, int nbatch, bool pending) {
-  const bool big = igemm_use_big(M, N, nbatch);
+
+int igemm_plan_ksplit(const IgemmArgs& a, bool pending, const IgemmSwitches& sw) {
+  const bool big = use_big(a, sw);
   const int bm = big ? 128 : 64, bn = big ? 128 : 64;
-  long long blocks = (long long)(M / bm) * ceil_div(N, bn) * nbatch;
-  int ks = K / 64;
+  const long long blocks = (long long)(a.M / bm) * ceil_div(a.N, bn) * a.nbatch;
+  const int ks = a.K / 64;
   // policy constants, each swept in situ (tools/experiments/sweep_split_policy.sh, profiles/round4_env_ab_pending_split.txt,
   // profiles/round5_ab_policy_resweep.txt: all flat within +-0.5 % around these values)
   constexpr int nosplit = 36;       // K-steps below which a launch followed by a reduce launch is not split (24 / 48: +0.5 %)
@@ -404,10 +349,129 @@ int igemm_pick_ksplit(int M, int N, int K, int nbatch, bool pending) {
   constexpr int minsteps = 6;       // K-steps left per slice at least
   // slices whose consumer adds them up cost no reduce launch: thresholds of their own (12 / 3 against 36 / 6: 0.1783 -> 0.1777 s/shape)
   constexpr int p_nosplit = 12, p_minsteps = 3;
-  if (ks < (pending ? p_nosplit : nosplit)) return 1;        // below ~36 K-steps the extra reduce launch (~5.5 us) costs more than the split saves (harness sweep: ~48; in situ: 36)
   int split = 1;
-  while (blocks * split < fill && ks / (split * 2) >= (pending ? p_minsteps : minsteps) && split < 32) split *= 2;
+  if (ks >= (pending ? p_nosplit : nosplit))        // below ~36 K-steps the extra reduce launch (~5.5 us) costs more than the split saves (harness sweep: ~48; in situ: 36)
+    while (blocks * split < fill && ks / (split * 2) >= (pending ? p_minsteps : minsteps) && split < 32) split *= 2;
+  if (!a.conv3 && a.M <= 64 && a.K % 64 == 0) {
+    // 1x1 GEMMs on the 8x8 maps: the one-launch small-map kernel (10.7 vs 16.2 us at K = 3072) -- unless the consumer adds K
+    // slices up and K is long: then the tiled kernel with 8-16 slices left pending (harness, K = 3072 -> 1024: 5.0 us against
+    // the skinny kernel's 8.1; at K = 1024 the two tie, profiles/round4_gemm1x1_slices_probe.txt).  ISHAP_G1_SLICES=0: off
+    split = (sw.g1_slices && pending && a.K >= 2048) ? (a.K >= 3072 ? 16 : 8) : 1;
+  }
+  if (sw.igemm4 > 1 && pending && a.conv3 && a.W == 8 && a.H == 8 && a.nbatch == 1 && a.Cin % 64 == 0 && a.M % 64 == 0 &&
+      a.K == 9 * a.Cin + a.K2 && (!a.K2 || (a.K2 % 64 == 0 && a.K2 / 64 <= 127 && a.X2))) {
+    // 3x3 on the 8x8 maps whose consumer adds K slices up: igemm4's 64x64 tiles (= one image) with enough slices for ~one
+    // workgroup per CU: the harness has 16 x 16 workgroups at 8.1 us against 9.1 for the one-launch small-map kernel this replaced
+    // (1024 -> 1024), 11.3 against 15.1 (2048 -> 1024), 11.1 against 16.4 (1024 -> 2048), 9.5 against 23.9 with the folded skip
+    // (profiles/round4_igemm4_w8_probe.txt, _w8_k2_probe.txt).  Fewer than 2 slices: the generic split above
+    constexpr int target = 256;        // workgroups (in-situ sweep 256 .. 640: flat)
+    const int tiles = (a.M / 64) * ((a.N + 63) / 64), G = 3 * (a.Cin / 64);
+    int s4 = (target + tiles / 2) / tiles;
+    if (s4 > 16) s4 = 16;
+    if (s4 > G) s4 = G;
+    if (s4 >= 2) {
+      const int per = (G + s4 - 1) / s4;
+      split = (G + per - 1) / per;                   // no slice without 3x3 groups (the second source's chunks are dealt out likewise)
+    }
+  }
   return split;
+}
+
+IgemmPlan igemm_plan(const IgemmArgs& a, const IgemmSwitches& sw) {
+  // 1x1 GEMMs on the 8x8 maps: the one-launch skinny kernel beats the tiled one there (measured in situ: 7.8 vs 11.4 us
+  // at 64 x 1024 x 1024); in situ it wins at M = 64 (-3..5 us per launch) and loses at M = 256; for 3x3 layers it re-reads
+  // the im2col fragments once per 16-channel tile and loses (L2-bound).  ISHAP_SKINNY=0: the tiled kernel + reduce instead
+  if (sw.skinny && !a.conv3 && a.M <= 64 && igemm_skinny_applicable(a)) return {IgemmForm::skinny, false};
+  // K not a multiple of 64 (tiny configurations; the full model's stem is padded to 128 channels): the register-staged kernel,
+  // built with 64x64 tiles only
+  if (a.conv3 ? a.Cin % 64 != 0 : a.K % 64 != 0) return {IgemmForm::reg32, false};
+  // the statistics epilogues file a whole tile under image m0 / HW: a tile must not straddle two images
+  const bool big = use_big(a, sw) && (!(a.stat_out || a.gb_x) || (a.H * a.W) % 128 == 0);
+  // igemm4 takes 3x3 launches (optionally with the folded 1x1 second source) with Cin % 64 == 0, one image per tile, a tile =
+  // whole image rows of a map 16 / 32 / 64 / 128 pixels wide.  ISHAP_IGEMM4: 0 = never, 1 = 128x128 tiles only, 2 = all of these
+  auto igemm4_takes = [&] {
+    const int BM = big ? 128 : 64;
+    if (!sw.igemm4 || (sw.igemm4 == 1 && !big)) return false;
+    if (!a.conv3 || a.nbatch != 1 || a.Cin % 64 != 0 || a.K != 9 * a.Cin + a.K2) return false;
+    if (a.K2 && (a.K2 % 64 != 0 || a.K2 / 64 > 127 || !a.X2)) return false;
+    // the folded second source runs with a short lookahead (one slab per step, NSTX - 1 ahead): worth it on the 128-tiles
+    // (-11 %), a loss on the 64-tiles (+4..18 %, profiles/round4_igemm4_probe_v4.txt) -- those stay with igemm2
+    // (the sliced launches on the 8x8 maps excepted: 9.5 us against 23.9 for the one-launch kernel they replaced, round 4)
+    const bool w8 = !big && a.W == 8 && a.H == 8 && a.ksplit > 1;
+    if (a.K2 && !big && !w8) return false;
+    // (128-pixel tiles on maps narrower than 128: several image rows per tile -- the batched generate path, where M = batch * H * W
+    // fills the chip with 128x128 tiles on the 64^2 ... 16^2 maps)
+    if (big ? (a.W != 128 && a.W != 64 && a.W != 32 && a.W != 16) : (a.W != 16 && a.W != 32 && a.W != 64 && !w8)) return false;
+    return BM % a.W == 0 && (a.H * a.W) % BM == 0 && a.M % BM == 0;
+  };
+  if (!igemm4_takes()) {
+    if (big) return {IgemmForm::ig2_128, true};
+    // one workgroup per CU at most and a K slice long enough to split: the two-team variant of the 64x64 conv kernel
+    // (measured: +4..16 % there, a loss on short slices and 1x1).  ISHAP_HALVES=1: one team
+    const long long tiles = (long long)(a.M / 64) * ((a.N + 63) / 64) * a.nbatch * a.ksplit;
+    const int steps = (a.K / 64 + a.ksplit - 1) / a.ksplit;
+    if (sw.halves == 2 && a.conv3 && tiles <= 256 && steps >= 16) return {IgemmForm::ig2_teams, false};
+    return {IgemmForm::ig2_64, false};
+  }
+  if (big) return {IgemmForm::ig4_128, true};
+  const int nc = a.Cin / 64;                                   // 64-channel chunks
+  const int groups = (3 * nc + a.ksplit - 1) / a.ksplit;       // (chunk, dy) groups of 3 K-steps per slice
+  // 128-pixel x 32-channel halo tiles where the 64x64 tiles of the same launch are 224 ... 256 workgroups (the same count: same
+  // tile area) and the K slices are whole 64-channel chunks, at least two of them (a one-chunk slice pays a whole slab fill before
+  // its first MFMA).  ISHAP_IG4_HALO=0: the 64x64 / 128x64 choices below everywhere
+  if (sw.ig4_halo && a.K2 == 0 && (a.W == 64 || a.W == 32 || a.W == 16) && a.M % 128 == 0 && (a.H * a.W) % 128 == 0 && a.N % 32 == 0 &&
+      nc % a.ksplit == 0 && nc / a.ksplit >= 2) {
+    const long long tiles = (long long)(a.M / 128) * (a.N / 32) * a.ksplit;
+    if (tiles >= 224 && tiles <= 256) return {IgemmForm::ig4_halo, false};
+  }
+  // 128-pixel x 64-channel tiles (two image rows of a 64-wide map): for the 64^2 layers with >= 512 output channels the grid still
+  // fills the chip (32 x 8 = 256 workgroups) and a K-step stages 13.3 KB for twice the FLOPs of a 64x64 tile's 10.7 KB; with only 128
+  // such tiles (the 64^2 256->256 layers) it loses (0.1804 -> 0.182 s/shape): at least 224 tiles.  ISHAP_IG4_TEAMS=0: off
+  if (sw.ig4_teams && a.W == 64 && a.K2 == 0 && a.ksplit == 1 && a.M % 128 == 0 && (a.H * a.W) % 128 == 0) {
+    const long long tiles = (long long)(a.M / 128) * ((a.N + 63) / 64);
+    if (tiles >= 224 && tiles <= 512) return {IgemmForm::ig4_tall, false};
+  }
+  // the 8x8 maps' sliced launches, whether or not the two-team test below would pass (no two-team instance for them)
+  if (a.W == 8) return {IgemmForm::ig4_w8, false};
+  // two teams: one workgroup per CU at most (<= 256 tiles) and a K slice long enough to halve (measured break-even: ~40 steps).
+  // ISHAP_IG4_TEAMS other than 2: one team
+  const long long tiles = (long long)(a.M / 64) * ((a.N + 63) / 64) * a.ksplit;
+  if (sw.ig4_teams == 2 && tiles <= 256 && 3 * groups + a.K2 / 64 >= 48) return {IgemmForm::ig4_teams, false};
+  // slices of 9-12 K-steps: too short for the 6-slot ring's compile-time loader path (13 steps), long enough for the 4-slot
+  // ring's (9) -- -13 % per launch there (16^2 512->512 in 8 slices 7.7 -> 6.7 us, 32^2 256->512 in 4 slices 9.9 -> 8.6;
+  // profiles/round4_igemm4_ring_by_slice_length_probe.txt); longer slices keep the deeper ring (+5 % at 36 steps with 4 slots)
+  if (a.K2 == 0 && 3 * groups >= 9 && 3 * groups <= 12) return {IgemmForm::ig4_64_ring4, false};
+  return {IgemmForm::ig4_64, false};
+}
+
+int igemm_prof_slot(const IgemmPlan& p, bool conv3) {
+  // [form][conv3], forms in IgemmForm's order: skinny, reg32, ig2_128, ig2_64, ig2_teams, ig4_128, ig4_64, ig4_64_ring4, ig4_teams,
+  // ig4_w8, ig4_tall, ig4_halo (the slot layout at ishap_profile_end)
+  static const int slot[][2] = {{5, 5}, {6, 6}, {2, 0}, {3, 1}, {4, 4}, {8, 8}, {9, 9}, {9, 9}, {10, 10}, {11, 11}, {12, 12}, {7, 7}};
+  static_assert(sizeof slot / sizeof slot[0] == (int)IgemmForm::ig4_halo + 1, "one row per form");
+  return slot[(int)p.form][conv3];
+}
+
+template <bool CONV3>
+static int launch_reg32(const IgemmArgs& a, hipStream_t s, std::string* name) {
+  constexpr int BM = 64, BN = 64, BK = 32;
+  if (name) { *name = igemm_kernel_name("igemm_kernel<%d, %d, %d, 2, 2, %s>", BM, BN, BK, CONV3 ? "true" : "false"); return 0; }
+  constexpr size_t smem = 2 * (size_t)(BM + BN) * BK * sizeof(half_t);
+  auto kern = igemm_kernel<BM, BN, BK, 2, 2, CONV3>;
+  ISHAP_TRY(ishap_set_max_lds((const void*)kern, (int)smem));
+  const dim3 grid(a.M / BM, ceil_div(a.N, BN), a.nbatch * a.ksplit);
+  if (g_igemm_prof_start) hipExtLaunchKernelGGL(kern, grid, dim3(256), smem, s, g_igemm_prof_start, g_igemm_prof_stop, 0, a);
+  else hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
+  return 0;
+}
+
+int igemm_launch_main(const IgemmArgs& a, const IgemmPlan& p, hipStream_t s, std::string* name) {
+  switch (p.form) {
+    case IgemmForm::skinny: return igemm_skinny_launch(a, 0, s, name);
+    case IgemmForm::reg32: return a.conv3 ? launch_reg32<true>(a, s, name) : launch_reg32<false>(a, s, name);
+    case IgemmForm::ig2_128: case IgemmForm::ig2_64: case IgemmForm::ig2_teams: return igemm2_launch(a, p.form, s, name);
+    default: return igemm4_launch(a, p.form, s, name);
+  }
 }
 
 // the stand-alone reduce of deferred split-K slices (a.ws, a.ksplit, bias / residual / output fields as in the main launch)
@@ -417,17 +481,6 @@ int igemm_reduce_launch(const IgemmArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(igemm_splitk_reduce, dim3(rblocks), dim3(256), 0, s, a);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
-}
-
-bool igemm_skinny_applicable(const IgemmArgs& a);                      // igemm_skinny.hip (small maps, one launch)
-int igemm_skinny_launch(const IgemmArgs& a, int mt, hipStream_t s);
-
-// 1x1 GEMMs on the 8x8 maps: the one-launch skinny kernel beats the tiled one there (measured in situ: 7.8 vs 11.4 us
-// at 64 x 1024 x 1024); for 3x3 layers it re-reads the im2col fragments once per 16-channel tile and loses.
-static bool use_skinny(const IgemmArgs& a) {
-  static const int on = [] { const char* e = getenv("ISHAP_SKINNY"); return e ? atoi(e) : 1; }();   // 0: the tiled kernel + reduce instead
-  // in situ it wins at M = 64 (-3..5 us per launch) and loses at M = 256; 3x3 layers never (L2-bound fragment re-reads)
-  return on && !a.conv3 && a.M <= 64 && igemm_skinny_applicable(a);
 }
 
 int igemm_launch(const IgemmArgs& a, hipStream_t s) {
@@ -442,41 +495,54 @@ int igemm_launch(const IgemmArgs& a, hipStream_t s) {
                             a.gb_stats && a.gb_gamma && a.gb_beta && (!a.gb_film || a.gb_emb)),
                 "fused GroupNorm-backward sums: fp16 dense output, N % 32 == 0, no forward statistics");
   ISHAP_REQUIRE(a.ldx % 8 == 0 && a.ldw % 8 == 0, "row strides must keep 16-byte alignment");
-  if (use_skinny(a)) {
-    if (!g_prof_on) return igemm_skinny_launch(a, 0, s);
+  const IgemmPlan p = igemm_plan(a);
+  ISHAP_REQUIRE(p.form == IgemmForm::skinny || !(a.stat_out || a.gb_x) || (a.H * a.W > 0 && (a.H * a.W) % 64 == 0),
+                "fused GroupNorm sums need H*W to be a multiple of the 64-row tile");
+  int prof_slot = -1;
+  if (g_prof_on) {
     ProfRec r;
     r.a = prof_event(); r.b = prof_event(); r.c = nullptr;
-    r.flops = 2.0 * a.M * a.N * a.K * a.flops_scale;
-    r.variant = 5;
-    r.M = a.M; r.N = a.N; r.K = a.K; r.conv3 = a.conv3; r.big = false; r.ksplit = 0;      // ksplit 0 marks the skinny kernel
-    g_igemm_prof_start = r.a; g_igemm_prof_stop = r.b;
-    const int rc = igemm_skinny_launch(a, 0, s);
+    r.flops = 2.0 * a.M * a.N * a.K * a.nbatch * a.flops_scale;
+    r.variant = igemm_prof_slot(p, a.conv3);
+    r.M = a.M * a.nbatch; r.N = a.N; r.K = a.K; r.conv3 = a.conv3 != 0; r.big = p.big;
+    r.ksplit = p.form == IgemmForm::skinny ? 0 : a.ksplit;    // ksplit 0 marks the skinny kernel
+    g_igemm_prof_start = r.a; g_igemm_prof_stop = r.b;      // attached to the dispatch: kernel begin / end timestamps
+    const int rc = igemm_launch_main(a, p, s);
     g_igemm_prof_start = nullptr; g_igemm_prof_stop = nullptr;
+    if (rc) return rc;
+    prof_slot = (int)g_prof.size();
     g_prof.push_back(r);
-    return rc;
+  } else {
+    ISHAP_TRY(igemm_launch_main(a, p, s));
   }
-  const bool k64 = a.conv3 ? (a.Cin % 64 == 0) : (a.K % 64 == 0);
-  bool big = igemm_use_big(a.M, a.N, a.nbatch) && k64;      // the register-staged BK = 32 kernel (tiny configurations only) is built with 64x64 tiles
-  if (a.stat_out || a.gb_x) {
-    // the statistics epilogues file a whole tile under image m0 / HW: a tile must not straddle two images
-    const int hw = a.H * a.W;
-    ISHAP_REQUIRE(hw > 0 && hw % 64 == 0, "fused GroupNorm sums need H*W to be a multiple of the 64-row tile");
-    if (hw % 128 != 0) big = false;
+  ISHAP_CHECK_HIP(hipGetLastError());
+  if (a.ksplit > 1 && !a.defer_reduce) {
+    ISHAP_TRY(igemm_reduce_launch(a, s));
+    if (prof_slot >= 0) {
+      g_prof[prof_slot].c = prof_event();
+      (void)hipEventRecord(g_prof[prof_slot].c, s);
+    }
   }
-#define IG_DISPATCH(BM, BN, WM_, WN_)                                                          \
-  do {                                                                                         \
-    if (a.conv3) {                                                                             \
-      if (k64) return launch_cfg<BM, BN, 64, WM_, WN_, true>(a, s);                            \
-      return launch_cfg<BM, BN, 32, WM_, WN_, true>(a, s);                                     \
-    } else {                                                                                   \
-      if (k64) return launch_cfg<BM, BN, 64, WM_, WN_, false>(a, s);                           \
-      return launch_cfg<BM, BN, 32, WM_, WN_, false>(a, s);                                    \
-    }                                                                                          \
-  } while (0)
-  if (big) {
-    if (a.conv3) return launch_cfg<128, 128, 64, 2, 2, true>(a, s);
-    return launch_cfg<128, 128, 64, 2, 2, false>(a, s);
+  return 0;
+}
+
+// CPU view of the plan (include/ishap.h): the K split conv_op picks and the kernel igemm_launch runs for one shape
+extern "C" int ishap_igemm_plan(int M, int cin, int cout, int taps, int K2, int H, int W, int nbatch, int pending, int epilogue_sums,
+                                int* ksplit, int* prof_slot, char* kernel, int kernel_cap) {
+  static const half_t second_source = 0;         // the planner only asks whether a folded source is there
+  static long long sums = 0;
+  IgemmArgs a;
+  a.M = M; a.N = cout; a.Cin = cin; a.K = taps * cin + K2; a.conv3 = taps == 9; a.K2 = K2; a.X2 = K2 ? &second_source : nullptr;
+  a.H = H; a.W = W; a.nbatch = nbatch; a.stat_out = epilogue_sums ? &sums : nullptr;
+  a.ksplit = igemm_plan_ksplit(a, pending != 0);
+  const IgemmPlan p = igemm_plan(a);
+  std::string name;
+  ISHAP_TRY(igemm_launch_main(a, p, nullptr, &name));
+  if (ksplit) *ksplit = a.ksplit;
+  if (prof_slot) *prof_slot = igemm_prof_slot(p, a.conv3);
+  if (kernel) {
+    if ((int)name.size() + 1 > kernel_cap) return -2;
+    memcpy(kernel, name.c_str(), name.size() + 1);
   }
-  IG_DISPATCH(64, 64, 2, 2);
-#undef IG_DISPATCH
+  return 0;
 }

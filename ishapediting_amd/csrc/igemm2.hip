@@ -385,52 +385,28 @@ __global__ __launch_bounds__((256 + 64 * IG2_LOADERS) * HALVES) void igemm2_kern
 }
 
 template <int BM, int BN, int NST, bool CONV3, int HALVES = 1>
-static int launch2(const IgemmArgs& a, hipStream_t s) {
+static int launch2(const IgemmArgs& a, hipStream_t s, std::string* name) {
+  if (name) { *name = igemm_kernel_name("igemm2_kernel<%d, %d, %d, %s, %d>", BM, BN, NST, CONV3 ? "true" : "false", HALVES); return 0; }
   constexpr size_t smem = (size_t)HALVES * NST * (BM + BN) * 64 * sizeof(half_t);
   static_assert(smem <= 163840, "LDS");
   auto kern = igemm2_kernel<BM, BN, NST, CONV3, HALVES>;
   ISHAP_TRY(ishap_set_max_lds((const void*)kern, (int)smem));
-  dim3 grid(a.M / BM, ceil_div(a.N, BN), a.nbatch * a.ksplit);
-  IgemmArgs b = a;
-  auto lg2 = [](int v) { int k = 0; while ((1 << k) < v) ++k; return (1 << k) == v ? k : -1; };
-  b.w_shift = a.W > 0 ? lg2(a.W) : -1;
-  b.hw_shift = (a.W > 0 && a.H > 0) ? lg2(a.H * a.W) : -1;
-  if (b.w_shift < 0 || b.hw_shift < 0) b.w_shift = b.hw_shift = -1;
-  b.nx_shift = lg2((int)grid.x);
-  b.ny_shift = lg2((int)grid.y);
-  if (b.nx_shift < 0 || b.ny_shift < 0) b.nx_shift = b.ny_shift = -1;
-  IgemmHot h;
-  h.X = b.X; h.Wt = b.Wt; h.K = b.K; h.Cin = b.Cin; h.ldx = b.ldx; h.ldw = b.ldw; h.H = b.H; h.W = b.W; h.ksplit = b.ksplit;
-  h.nwg = (int)(grid.x * grid.y * grid.z);
-  h.packed = (unsigned)(b.w_shift & 0x3f) | (unsigned)(b.hw_shift & 0x3f) << 6 | (unsigned)(b.nx_shift & 0x3f) << 12 |
-             (unsigned)(b.ny_shift & 0x3f) << 18 | (b.ups ? 1u << 24 : 0u);
-  if (g_igemm_prof_start) hipExtLaunchKernelGGL(kern, grid, dim3((256 + 64 * IG2_LOADERS) * HALVES), smem, s, g_igemm_prof_start, g_igemm_prof_stop, 0,
-                                                (const void*)h.X, (const void*)h.Wt, h.K, h.Cin, h.ldx, h.ldw, h.H, h.W, h.ksplit, h.nwg, h.packed, b);
-  else hipLaunchKernelGGL(kern, grid, dim3((256 + 64 * IG2_LOADERS) * HALVES), smem, s,
-                          (const void*)h.X, (const void*)h.Wt, h.K, h.Cin, h.ldx, h.ldw, h.H, h.W, h.ksplit, h.nwg, h.packed, b);
-  ISHAP_CHECK_HIP(hipGetLastError());
-  return 0;
+  const dim3 grid(a.M / BM, ceil_div(a.N, BN), a.nbatch * a.ksplit);
+  return igemm_dma_launch(kern, grid, grid, dim3((256 + 64 * IG2_LOADERS) * HALVES), smem, s, a, 0u);
 }
 
-// one workgroup per CU at most and a K slice long enough to split: the two-team variant of the 64x64 conv kernel
-// (measured: +4..16 % there, a loss on short slices and 1x1)
-bool igemm2_two_teams(const IgemmArgs& a, bool big) {
-  static const int halves = [] { const char* e = getenv("ISHAP_HALVES"); return e ? atoi(e) : 2; }();
-  if (big || halves != 2 || !a.conv3) return false;
-  const long long tiles = (long long)(a.M / 64) * ((a.N + 63) / 64) * a.nbatch * a.ksplit;
-  const int steps = (a.K / 64 + a.ksplit - 1) / a.ksplit;
-  return tiles <= 256 && steps >= 16;
-}
-
-// main kernel only (the caller adds the split-K reduce); big = 128x128 tile, else 64x64
-int igemm2_launch_main(const IgemmArgs& a, bool big, hipStream_t s) {
+// main kernel only (the caller adds the split-K reduce)
+int igemm2_launch(const IgemmArgs& a, IgemmForm f, hipStream_t s, std::string* name) {
 #ifndef IG2_BIG_NST
 #define IG2_BIG_NST 4
 #endif
-  if (big) return a.conv3 ? launch2<128, 128, IG2_BIG_NST, true>(a, s) : launch2<128, 128, IG2_BIG_NST, false>(a, s);
 #ifndef IG2_SMALL_NST
 #define IG2_SMALL_NST 4
 #endif
-  if (igemm2_two_teams(a, big)) return launch2<64, 64, 4, true, 2>(a, s);
-  return a.conv3 ? launch2<64, 64, IG2_SMALL_NST, true>(a, s) : launch2<64, 64, IG2_SMALL_NST, false>(a, s);
+  switch (f) {
+    case IgemmForm::ig2_128: return a.conv3 ? launch2<128, 128, IG2_BIG_NST, true>(a, s, name) : launch2<128, 128, IG2_BIG_NST, false>(a, s, name);
+    case IgemmForm::ig2_teams: return launch2<64, 64, 4, true, 2>(a, s, name);
+    case IgemmForm::ig2_64: return a.conv3 ? launch2<64, 64, IG2_SMALL_NST, true>(a, s, name) : launch2<64, 64, IG2_SMALL_NST, false>(a, s, name);
+    default: ISHAP_REQUIRE(false, "igemm2: not one of its forms");
+  }
 }

@@ -17,11 +17,11 @@
 // Swizzle of the activation slab: 16-byte chunk ^ (row & 7) -- conflict-free for ds_read_b128 fragments starting at ANY
 // row under the lane grouping of MI355X_MICROARCH.md (LDS table), which the shifted reads need; the weight slab keeps
 // igemm2's chunk ^ ((row >> 1) & 7).
-// Tile shapes (igemm4_launch_main): 128x128 on maps 16 ... 128 wide (several image rows per tile below 128; fragment reads
+// Tile shapes (igemm4_launch; which one a launch gets: igemm_plan in igemm.hip): 128x128 on maps 16 ... 128 wide (several image rows per tile below 128; fragment reads
 // interleaved into the MFMA blocks), 64x64 one- and two-team on maps 16 ... 64 wide, 128 pixels x 64 channels on the 64-wide
 // maps, 128 pixels x 32 channels with one halo slab per chunk (igemm4_halo_kernel) where the 64x64 form has ~256 workgroups,
 // and on the 8x8 maps 64x64 tiles (= one image) with K cut into ~16 slices whose fp32 partial tiles are left for the
-// consuming GroupNorm kernel to add up (igemm4_small_map_slices; took the level over from a one-launch small-map kernel late in round 4, removed in round 6).
+// consuming GroupNorm kernel to add up (igemm_plan_ksplit; took the level over from a one-launch small-map kernel late in round 4, removed in round 6).
 // Reference arithmetic: conv2d 3x3, padding 1 (gd/unet.py ResBlock in_layers / out_layers, :236-256) and its input
 // gradient (flipped, transposed weights).  Same products as igemm2, another order of the K sum inside the fp32
 // accumulators: the two kernels agree to summation order (tests/test_gpu_fullsize.py: <= 2e-3 relative over the full model).
@@ -785,8 +785,10 @@ __global__ __launch_bounds__(512) void igemm4_halo_kernel(const void* hX, const 
 
 // HALO: igemm4_halo_kernel<WD, NSTW> (BM = 128, BN = 32, two slab slots of (BM / WD + 2) image rows)
 template <int BM, int BN, int WD, int NSTW, int NSTX, int HALVES = 1, bool HALO = false>
-static int launch4(const IgemmArgs& a, hipStream_t s) {
+static int launch4(const IgemmArgs& a, hipStream_t s, std::string* name) {
   static_assert(!HALO || (BM == 128 && BN == 32 && NSTX == 2 && HALVES == 1), "the halo kernel's tile");
+  if (name) { *name = HALO ? igemm_kernel_name("igemm4_halo_kernel<%d, %d>", WD, NSTW)
+                           : igemm_kernel_name("igemm4_kernel<%d, %d, %d, %d, %d, %d>", BM, BN, WD, NSTW, NSTX, HALVES); return 0; }
   constexpr int XROWS = HALO ? (BM / WD + 2) * WD : BM;      // pixel rows of a slab slot
   constexpr size_t ring = (size_t)HALVES * (NSTW * BN * 64 + NSTX * (XROWS + 8) * 64) * sizeof(half_t);
   constexpr size_t epi = (size_t)HALVES * BM * (BN + 4) * 4 + (size_t)BM * (BN + 8) * 2 + 16384;      // staged epilogue: fp32 tile(s) + fp16 tile + partial sums
@@ -798,31 +800,21 @@ static int launch4(const IgemmArgs& a, hipStream_t s) {
   }();
   ISHAP_TRY(ishap_set_max_lds((const void*)kern, (int)smem));
   const dim3 grid(a.M / BM, ceil_div(a.N, BN), a.ksplit);
-  IgemmArgs b = a;
-  auto lg2 = [](int v) { int k = 0; while ((1 << k) < v) ++k; return (1 << k) == v ? k : -1; };
-  b.w_shift = lg2(a.W);
-  b.hw_shift = lg2(a.H * a.W);
-  if (b.w_shift < 0 || b.hw_shift < 0) b.w_shift = b.hw_shift = -1;
-  b.nx_shift = lg2((int)grid.x);
-  b.ny_shift = lg2((int)grid.y);
-  if (b.nx_shift < 0 || b.ny_shift < 0) b.nx_shift = b.ny_shift = -1;
-  IgemmHot h;
-  h.X = b.X; h.Wt = b.Wt; h.K = b.K; h.Cin = b.Cin; h.ldx = b.ldx; h.ldw = b.ldw; h.H = b.H; h.W = b.W; h.ksplit = b.ksplit;
-  h.nwg = (int)(grid.x * grid.y * grid.z);
-  h.packed = (unsigned)(b.w_shift & 0x3f) | (unsigned)(b.hw_shift & 0x3f) << 6 | (unsigned)(b.nx_shift & 0x3f) << 12 |
-             (unsigned)(b.ny_shift & 0x3f) << 18 | (b.ups ? 1u << 24 : 0u) | (unsigned)(b.K2 / 64) << 25;
+  const unsigned k2_chunks = (unsigned)(a.K2 / 64) << 25;
+  const bool remap = !(grid.x & (grid.x - 1)) && !(grid.y & (grid.y - 1));      // powers of two: the kernel's tile remap by shifts
+  const int nwg = (int)(grid.x * grid.y * grid.z);
   // chunked form (IgemmArgs::chunk_tiles > 0, a multiple of 8 so that a tile keeps the `lin & 7` = XCD of the remap): the layer as
   // ceil(tiles / chunk) launches of at most `chunk` tiles each, back to back on the stream
   // tile order within an XCD's share (kernel: bit 30 of hbase).  Bytes an XCD's L2 has to pull under each order, from the tiles it
   // is dealt (q = tiles / 8 consecutive ids): a weight panel per distinct (n-tile, K slice), an activation slab per distinct
   // (m-tile, K slice); neighbouring m-tiles share their halo rows inside one L2.  ISHAP_IG4_NOUTER=0 / 1 forces an order.
   int n_outer = 0;
-  if (b.nx_shift >= 0) {
+  if (remap) {
     static const int force = [] { const char* e = getenv("ISHAP_IG4_NOUTER"); return e ? atoi(e) : 2; }();
     const int nx = (int)grid.x, ny = (int)grid.y, nz = (int)grid.z;
-    const int q = (h.nwg + 7) / 8;
-    const double wp = (double)BN * (b.K / (double)nz) * 2.0;                 // one weight panel of one slice
-    const double xs = (double)BM * b.Cin * 2.0 / nz + (b.K2 ? (double)BM * b.K2 * 2.0 / nz : 0.0);   // one tile's pixels, one slice's channels
+    const int q = (nwg + 7) / 8;
+    const double wp = (double)BN * (a.K / (double)nz) * 2.0;                 // one weight panel of one slice
+    const double xs = (double)BM * a.Cin * 2.0 / nz + (a.K2 ? (double)BM * a.K2 * 2.0 / nz : 0.0);   // one tile's pixels, one slice's channels
     auto cdiv = [](int a, int d) { return (a + d - 1) / d; };
     // order 0: n fastest, then m, then z
     const int nA = ny < q ? ny : q, mzA = cdiv(q, ny), mA = nx < mzA ? nx : mzA, zA = cdiv(mzA, nx);
@@ -833,57 +825,14 @@ static int launch4(const IgemmArgs& a, hipStream_t s) {
     n_outer = force == 2 ? (costB < 0.8 * costA) : force;
   }
   const int order_bit = n_outer ? (1 << 30) : 0;
-  const int tiles = h.nwg;
   const int chunk = a.chunk_tiles;
-  const bool chunked = chunk > 0 && chunk % 8 == 0 && tiles > chunk && b.nx_shift >= 0 && !g_igemm_prof_start;
-  if (chunked) {
-    for (int base = 0; base < tiles; base += chunk) {
-      const int n = tiles - base < chunk ? tiles - base : chunk;
-      hipLaunchKernelGGL(kern, dim3(n), dim3(512 * HALVES), smem, s,
-                         (const void*)h.X, (const void*)h.Wt, h.K, h.Cin, h.ldx, h.ldw, h.H, h.W, h.ksplit, h.nwg, h.packed, base | order_bit, b);
-    }
-  } else if (g_igemm_prof_start) hipExtLaunchKernelGGL(kern, grid, dim3(512 * HALVES), smem, s, g_igemm_prof_start, g_igemm_prof_stop, 0,
-                                                (const void*)h.X, (const void*)h.Wt, h.K, h.Cin, h.ldx, h.ldw, h.H, h.W, h.ksplit, h.nwg, h.packed, order_bit, b);
-  else hipLaunchKernelGGL(kern, grid, dim3(512 * HALVES), smem, s,
-                          (const void*)h.X, (const void*)h.Wt, h.K, h.Cin, h.ldx, h.ldw, h.H, h.W, h.ksplit, h.nwg, h.packed, order_bit, b);
-  ISHAP_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// the shapes this kernel takes: 3x3 (optionally with the folded 1x1 second source), Cin % 64 == 0, one image per tile, a tile =
-// whole image rows of a map 16 / 32 / 64 / 128 pixels wide
-bool igemm4_applicable(const IgemmArgs& a, bool big) {
-  const int BM = big ? 128 : 64;
-  if (!a.conv3 || a.nbatch != 1 || a.Cin % 64 != 0 || a.K != 9 * a.Cin + a.K2) return false;
-  if (a.K2 && (a.K2 % 64 != 0 || a.K2 / 64 > 127 || !a.X2)) return false;
-  // the folded second source runs with a short lookahead (one slab per step, NSTX - 1 ahead): worth it on the 128-tiles
-  // (-11 %), a loss on the 64-tiles (+4..18 %, profiles/round4_igemm4_probe_v4.txt) -- those stay with igemm2
-  // (the sliced launches on the 8x8 maps excepted: 9.5 us against 23.9 for the one-launch kernel they replaced, round 4)
-  const bool w8 = !big && a.W == 8 && a.H == 8 && a.ksplit > 1;
-  if (a.K2 && !big && !w8) return false;
-  // (128-pixel tiles on maps narrower than 128: several image rows per tile -- the batched generate path, where M = batch * H * W
-  // fills the chip with 128x128 tiles on the 64^2 ... 16^2 maps)
-  if (big ? (a.W != 128 && a.W != 64 && a.W != 32 && a.W != 16) : (a.W != 16 && a.W != 32 && a.W != 64 && !w8)) return false;
-  if (BM % a.W != 0 || (a.H * a.W) % BM != 0 || a.M % BM != 0) return false;
-  return true;
-}
-
-// The 8x8 maps (one tile = one image): K slices for a sliced launch whose consumer adds the slices up, 0 = not taken (the shape
-// then goes through the generic tile + split policy).  Enough slices for ~one workgroup per CU: the harness has 16 x 16 workgroups at
-// 8.1 us against 9.1 for the one-launch small-map kernel this replaced (1024 -> 1024), 11.3 against 15.1 (2048 -> 1024), 11.1
-// against 16.4 (1024 -> 2048), 9.5 against 23.9 with the folded skip (profiles/round4_igemm4_w8_probe.txt, _w8_k2_probe.txt)
-int igemm4_small_map_slices(const IgemmArgs& a) {
-  static const int on = [] { const char* all = getenv("ISHAP_IGEMM4"); return (all ? atoi(all) : 2) > 1; }();      // igemm.hip: 2 (default) = every shape igemm4 takes
-  constexpr int target = 256;        // workgroups (in-situ sweep 256 .. 640: flat)
-  if (!on || !a.conv3 || a.W != 8 || a.H != 8 || a.nbatch != 1 || a.Cin % 64 != 0 || a.M % 64 != 0 || a.K != 9 * a.Cin + a.K2) return 0;
-  if (a.K2 && (a.K2 % 64 != 0 || a.K2 / 64 > 127 || !a.X2)) return 0;
-  const int tiles = (a.M / 64) * ((a.N + 63) / 64), G = 3 * (a.Cin / 64);
-  int ks = (target + tiles / 2) / tiles;
-  if (ks > 16) ks = 16;
-  if (ks > G) ks = G;
-  if (ks < 2) return 0;
-  const int per = (G + ks - 1) / ks;
-  return (G + per - 1) / per;                      // no slice without 3x3 groups (the second source's chunks are dealt out likewise)
+  if (chunk > 0 && chunk % 8 == 0 && nwg > chunk && remap && !g_igemm_prof_start) {
+    for (int base = 0; base < nwg; base += chunk)
+      ISHAP_TRY(igemm_dma_launch(kern, grid, dim3(nwg - base < chunk ? nwg - base : chunk), dim3(512 * HALVES), smem, s, a, k2_chunks,
+                                 base | order_bit));
+    return 0;
+  }
+  return igemm_dma_launch(kern, grid, grid, dim3(512 * HALVES), smem, s, a, k2_chunks, order_bit);
 }
 
 #ifndef IG4_BIG_W
@@ -896,80 +845,43 @@ int igemm4_small_map_slices(const IgemmArgs& a) {
 #endif
 #ifndef IG4_W8_W               // the 8x8 maps' sliced launches: 9-18 K-steps per workgroup -- a 4-slot weight ring (3 steps in flight) lets
 #define IG4_W8_W 4             // a 9-step slice take the loader's compile-time path and beats the 6-slot one by 4-6 % per launch
-#define IG4_W8_X 3             // (profiles/round4_igemm4_w8_ring_probe.txt)
+#define IG4_W8_X 3             // (profiles/round4_igemm4_w8_ring_probe.txt); the 4-slot ring of ig4_64_ring4 as well
 #endif
 #ifndef IG4_TEAM_W
 #define IG4_TEAM_W 6
 #define IG4_TEAM_X 3
 #endif
-// two teams: one workgroup per CU at most (<= 256 tiles) and a K slice long enough to halve (measured break-even: ~40 steps)
-bool igemm4_two_teams(const IgemmArgs& a, bool big) {
-  static const int on = [] { const char* e = getenv("ISHAP_IG4_TEAMS"); return e ? atoi(e) : 2; }();
-  if (big || on != 2) return false;
-  const long long tiles = (long long)(a.M / 64) * ((a.N + 63) / 64) * a.ksplit;
-  const int groups = (3 * (a.Cin / 64) + a.ksplit - 1) / a.ksplit;
-  return tiles <= 256 && 3 * groups + a.K2 / 64 >= 48;
-}
-// 128-pixel x 64-channel tiles (two image rows of a 64-wide map): for the 64^2 layers with >= 512 output channels the grid still
-// fills the chip (32 x 8 = 256 workgroups) and a K-step stages 13.3 KB for twice the FLOPs of a 64x64 tile's 10.7 KB; with only 128
-// such tiles (the 64^2 256->256 layers) it loses (0.1804 -> 0.182 s/shape): at least 224 tiles
-bool igemm4_tall_tiles(const IgemmArgs& a, bool big) {
-  static const int on = [] { const char* e = getenv("ISHAP_IG4_TEAMS"); return e ? atoi(e) : 2; }();      // 0: plain one-team 64x64 tiles everywhere
-  if (big || !on || a.W != 64 || a.K2 != 0 || a.ksplit != 1 || a.M % 128 != 0 || (a.H * a.W) % 128 != 0) return false;
-  const long long tiles = (long long)(a.M / 128) * ((a.N + 63) / 64);
-  return tiles >= 224 && tiles <= 512;
-}
 #ifndef IG4_HALO_W
 #define IG4_HALO_W 6
 #endif
-// 128-pixel x 32-channel halo tiles (igemm4_halo_kernel) where the 64x64 tiles of the same launch are 224 ... 256 workgroups (the
-// same count: same tile area) and the K slices are whole 64-channel chunks, at least two of them (a one-chunk slice pays a whole
-// slab fill before its first MFMA).  ISHAP_IG4_HALO=0: the 64x64 / 128x64 choices below everywhere.
-bool igemm4_halo_tiles(const IgemmArgs& a, bool big) {
-  static const int on = [] { const char* e = getenv("ISHAP_IG4_HALO"); return e ? atoi(e) : 1; }();
-  if (big || !on || a.K2 != 0 || (a.W != 64 && a.W != 32 && a.W != 16) || a.M % 128 != 0 || (a.H * a.W) % 128 != 0 || a.N % 32 != 0) return false;
-  const int nc = a.Cin / 64;
-  if (nc % a.ksplit != 0 || nc / a.ksplit < 2) return false;
-  const long long tiles = (long long)(a.M / 128) * (a.N / 32) * a.ksplit;
-  return tiles >= 224 && tiles <= 256;
-}
-int igemm4_launch_main(const IgemmArgs& a, bool big, hipStream_t s) {
-  if (big) {
-    if (a.W == 128) return launch4<128, 128, 128, IG4_BIG_W, IG4_BIG_X>(a, s);
-    if (a.W == 64) return launch4<128, 128, 64, IG4_BIG_W, IG4_BIG_X>(a, s);
-    if (a.W == 32) return launch4<128, 128, 32, IG4_BIG_W, IG4_BIG_X>(a, s);
-    return launch4<128, 128, 16, IG4_BIG_W, IG4_BIG_X>(a, s);
+// main kernel only (the caller adds the split-K reduce); the planner sends only the map widths a form takes.  The instances are
+// named in the order the code object lays their kernels out: a new order moves the PC-relative data offsets inside every kernel
+int igemm4_launch(const IgemmArgs& a, IgemmForm f, hipStream_t s, std::string* name) {
+  switch (f) {
+    case IgemmForm::ig4_128:
+      if (a.W == 128) return launch4<128, 128, 128, IG4_BIG_W, IG4_BIG_X>(a, s, name);
+      if (a.W == 64) return launch4<128, 128, 64, IG4_BIG_W, IG4_BIG_X>(a, s, name);
+      if (a.W == 32) return launch4<128, 128, 32, IG4_BIG_W, IG4_BIG_X>(a, s, name);
+      return launch4<128, 128, 16, IG4_BIG_W, IG4_BIG_X>(a, s, name);
+    case IgemmForm::ig4_halo:
+      if (a.W == 64) return launch4<128, 32, 64, IG4_HALO_W, 2, 1, true>(a, s, name);
+      if (a.W == 32) return launch4<128, 32, 32, IG4_HALO_W, 2, 1, true>(a, s, name);
+      return launch4<128, 32, 16, IG4_HALO_W, 2, 1, true>(a, s, name);
+    case IgemmForm::ig4_tall: return launch4<128, 64, 64, IG4_SMALL_W, IG4_SMALL_X>(a, s, name);
+    case IgemmForm::ig4_teams:
+    case IgemmForm::ig4_w8:       // (named between two team widths: the code object keeps its kernel order, see above)
+      if (f == IgemmForm::ig4_teams && a.W == 64) return launch4<64, 64, 64, IG4_TEAM_W, IG4_TEAM_X, 2>(a, s, name);
+      if (f == IgemmForm::ig4_teams && a.W == 32) return launch4<64, 64, 32, IG4_TEAM_W, IG4_TEAM_X, 2>(a, s, name);
+      if (f == IgemmForm::ig4_w8) return launch4<64, 64, 8, IG4_W8_W, IG4_W8_X>(a, s, name);
+      return launch4<64, 64, 16, IG4_TEAM_W, IG4_TEAM_X, 2>(a, s, name);
+    case IgemmForm::ig4_64_ring4:
+      if (a.W == 64) return launch4<64, 64, 64, IG4_W8_W, IG4_W8_X>(a, s, name);
+      if (a.W == 32) return launch4<64, 64, 32, IG4_W8_W, IG4_W8_X>(a, s, name);
+      return launch4<64, 64, 16, IG4_W8_W, IG4_W8_X>(a, s, name);
+    case IgemmForm::ig4_64:
+      if (a.W == 64) return launch4<64, 64, 64, IG4_SMALL_W, IG4_SMALL_X>(a, s, name);
+      if (a.W == 32) return launch4<64, 64, 32, IG4_SMALL_W, IG4_SMALL_X>(a, s, name);
+      return launch4<64, 64, 16, IG4_SMALL_W, IG4_SMALL_X>(a, s, name);
+    default: ISHAP_REQUIRE(false, "igemm4: not one of its forms");
   }
-  if (igemm4_halo_tiles(a, big)) {
-    if (a.W == 64) return launch4<128, 32, 64, IG4_HALO_W, 2, 1, true>(a, s);
-    if (a.W == 32) return launch4<128, 32, 32, IG4_HALO_W, 2, 1, true>(a, s);
-    return launch4<128, 32, 16, IG4_HALO_W, 2, 1, true>(a, s);
-  }
-  if (igemm4_tall_tiles(a, big)) return launch4<128, 64, 64, IG4_SMALL_W, IG4_SMALL_X>(a, s);
-#ifdef IG4_TALL_PROBE      // harness only (tools/experiments/tall_probe.sh; profiles/round6_tall_tiles_sliced_launches.txt): 128 x 64 tiles on the 32^2 / 16^2 maps
-  if ((a.W == 32 || a.W == 16) && a.K2 == 0 && a.M % 128 == 0 && (a.H * a.W) % 128 == 0) {
-    const int st = 3 * ((3 * (a.Cin / 64) + a.ksplit - 1) / a.ksplit);
-    if (st >= 9 && st <= 12) return a.W == 32 ? launch4<128, 64, 32, IG4_W8_W, IG4_W8_X>(a, s) : launch4<128, 64, 16, IG4_W8_W, IG4_W8_X>(a, s);
-    return a.W == 32 ? launch4<128, 64, 32, IG4_SMALL_W, IG4_SMALL_X>(a, s) : launch4<128, 64, 16, IG4_SMALL_W, IG4_SMALL_X>(a, s);
-  }
-#endif
-  if (igemm4_two_teams(a, big)) {
-    if (a.W == 64) return launch4<64, 64, 64, IG4_TEAM_W, IG4_TEAM_X, 2>(a, s);
-    if (a.W == 32) return launch4<64, 64, 32, IG4_TEAM_W, IG4_TEAM_X, 2>(a, s);
-    if (a.W == 8) return launch4<64, 64, 8, IG4_W8_W, IG4_W8_X>(a, s);
-    return launch4<64, 64, 16, IG4_TEAM_W, IG4_TEAM_X, 2>(a, s);
-  }
-  if (a.W == 8) return launch4<64, 64, 8, IG4_W8_W, IG4_W8_X>(a, s);
-  // slices of 9-12 K-steps: too short for the 6-slot ring's compile-time loader path (13 steps), long enough for the 4-slot
-  // ring's (9) -- -13 % per launch there (16^2 512->512 in 8 slices 7.7 -> 6.7 us, 32^2 256->512 in 4 slices 9.9 -> 8.6;
-  // profiles/round4_igemm4_ring_by_slice_length_probe.txt); longer slices keep the deeper ring (+5 % at 36 steps with 4 slots)
-  const int steps = 3 * ((3 * (a.Cin / 64) + a.ksplit - 1) / a.ksplit);
-  if (a.K2 == 0 && steps >= 9 && steps <= 12) {
-    if (a.W == 64) return launch4<64, 64, 64, IG4_W8_W, IG4_W8_X>(a, s);
-    if (a.W == 32) return launch4<64, 64, 32, IG4_W8_W, IG4_W8_X>(a, s);
-    return launch4<64, 64, 16, IG4_W8_W, IG4_W8_X>(a, s);
-  }
-  if (a.W == 64) return launch4<64, 64, 64, IG4_SMALL_W, IG4_SMALL_X>(a, s);
-  if (a.W == 32) return launch4<64, 64, 32, IG4_SMALL_W, IG4_SMALL_X>(a, s);
-  return launch4<64, 64, 16, IG4_SMALL_W, IG4_SMALL_X>(a, s);
 }

@@ -178,19 +178,13 @@ __global__ __launch_bounds__(SK_WAVES * 64) void igemm_skinny_kernel(const void*
 }
 
 template <int MT>
-int launch_skinny(const IgemmArgs& a, hipStream_t s) {
+int launch_skinny(const IgemmArgs& a, hipStream_t s, std::string* name) {
+  if (name) { *name = igemm_kernel_name("igemm_skinny_kernel<%d, %s>", MT, a.conv3 ? "true" : "false"); return 0; }
   dim3 grid(a.M / (16 * MT), (a.N + 15) / 16);
-  if (a.conv3) {
-    if (g_igemm_prof_start) hipExtLaunchKernelGGL((igemm_skinny_kernel<MT, true>), grid, dim3(SK_WAVES * 64), 0, s, g_igemm_prof_start, g_igemm_prof_stop, 0,
-                                                   (const void*)a.X, (const void*)a.Wt, a.K, a.Cin, a.ldx, a.ldw, a.H, a.W, a.N, a);
-    else hipLaunchKernelGGL((igemm_skinny_kernel<MT, true>), grid, dim3(SK_WAVES * 64), 0, s, (const void*)a.X, (const void*)a.Wt, a.K, a.Cin, a.ldx,
-                            a.ldw, a.H, a.W, a.N, a);
-  } else {
-    if (g_igemm_prof_start) hipExtLaunchKernelGGL((igemm_skinny_kernel<MT, false>), grid, dim3(SK_WAVES * 64), 0, s, g_igemm_prof_start, g_igemm_prof_stop, 0,
-                                                   (const void*)a.X, (const void*)a.Wt, a.K, a.Cin, a.ldx, a.ldw, a.H, a.W, a.N, a);
-    else hipLaunchKernelGGL((igemm_skinny_kernel<MT, false>), grid, dim3(SK_WAVES * 64), 0, s, (const void*)a.X, (const void*)a.Wt, a.K, a.Cin, a.ldx,
-                            a.ldw, a.H, a.W, a.N, a);
-  }
+  auto kern = a.conv3 ? igemm_skinny_kernel<MT, true> : igemm_skinny_kernel<MT, false>;
+  if (g_igemm_prof_start) hipExtLaunchKernelGGL(kern, grid, dim3(SK_WAVES * 64), 0, s, g_igemm_prof_start, g_igemm_prof_stop, 0,
+                                                (const void*)a.X, (const void*)a.Wt, a.K, a.Cin, a.ldx, a.ldw, a.H, a.W, a.N, a);
+  else hipLaunchKernelGGL(kern, grid, dim3(SK_WAVES * 64), 0, s, (const void*)a.X, (const void*)a.Wt, a.K, a.Cin, a.ldx, a.ldw, a.H, a.W, a.N, a);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -206,13 +200,13 @@ bool igemm_skinny_applicable(const IgemmArgs& a) {
 }
 
 // mt: pixels per workgroup / 16 (1, 2 or 4); 0 = pick
-int igemm_skinny_launch(const IgemmArgs& a, int mt, hipStream_t s) {
+int igemm_skinny_launch(const IgemmArgs& a, int mt, hipStream_t s, std::string* name) {
   ISHAP_REQUIRE(igemm_skinny_applicable(a), "skinny kernel: shape");
   if (mt == 0) mt = (a.M % 64 == 0 && a.M > 64) ? 4 : (a.M % 32 == 0 ? 2 : 1);
   ISHAP_REQUIRE(a.M % (16 * mt) == 0, "skinny kernel: tile");
   switch (mt) {
-    case 1: return launch_skinny<1>(a, s);
-    case 2: return launch_skinny<2>(a, s);
-    default: return launch_skinny<4>(a, s);
+    case 1: return launch_skinny<1>(a, s, name);
+    case 2: return launch_skinny<2>(a, s, name);
+    default: return launch_skinny<4>(a, s, name);
   }
 }

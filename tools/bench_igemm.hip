@@ -3,11 +3,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <climits>
 #include <vector>
+#include "../ishapediting_amd/csrc/igemm.hip"
 #include "../ishapediting_amd/csrc/igemm2.hip"
 #include "../ishapediting_amd/csrc/igemm4.hip"
 #include "../ishapediting_amd/csrc/igemm_skinny.hip"
-hipEvent_t g_igemm_prof_start = nullptr, g_igemm_prof_stop = nullptr;
 #ifdef IG_STAMPS
 __device__ unsigned long long* g_ig_stamps;
 #include <algorithm>
@@ -60,18 +61,28 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   const int mt = ksplit;                          // gen 4 (skinny kernel): argument 5 is MT (pixels per workgroup / 16)
   if (gen == 4) { a.ksplit = 1; }
+  // the library's plan for this launch with the tile size of argument 4 (128 when the shape allows it): igemm4 where it takes the
+  // shape (gen 6), igemm2 (otherwise); ISHAP_IG4_TEAMS / _HALO / _HALVES choose among their forms as in the library
+  auto plan_of = [](const IgemmArgs& x, bool ig4, bool tile128) {
+    IgemmSwitches sw = igemm_switches();
+    sw.igemm4 = ig4 ? 2 : 0; sw.skinny = 0; sw.big_min = tile128 ? 0 : INT_MAX;
+    return igemm_plan(x, sw);
+  };
+  const IgemmPlan plan = plan_of(a, gen == 6, big);
   int turn = 0;
   auto run = [&]() {
     a.Wt = W + (size_t)(turn++ % nbuf) * wel;
     if (gen == 4) igemm_skinny_launch(a, mt, 0);
-    else if (gen == 6 && igemm4_applicable(a, big)) igemm4_launch_main(a, big, 0);
-    else igemm2_launch_main(a, big, 0);
+    else igemm_launch_main(a, plan, 0);
   };
-  if (gen == 6 && !igemm4_applicable(a, big)) { printf("gen6: shape not applicable\n"); return 1; }
+  std::string kname;
+  igemm_launch_main(a, plan, 0, &kname);
+  if (gen != 4) printf("%s\n", kname.c_str());
+  if (gen == 6 && plan.form < IgemmForm::ig4_128) { printf("gen6: shape not applicable\n"); return 1; }
   if (gen == 4 || gen == 6) {         // check against the tiled kernel
     half_t* O1; hipMalloc(&O1, (size_t)M * Cout * 2);
     IgemmArgs b = a; b.out = O1; b.stat_out = nullptr; b.ksplit = 1;
-    igemm2_launch_main(b, 0, 0);
+    igemm_launch_main(b, plan_of(b, false, false), 0);
     run();
     std::vector<half_t> o((size_t)M * Cout), o1((size_t)M * Cout);
     hipMemcpy(o.data(), O, o.size() * 2, hipMemcpyDeviceToHost);
@@ -96,11 +107,12 @@ int main(int argc, char** argv) {
     half_t *Xb, *Ob; hipMalloc(&Xb, (size_t)Mb * Cin * 2); hipMalloc(&Ob, (size_t)Mb * Cout * 2);
     hipMemset(Xb, 0, (size_t)Mb * Cin * 2);
     b.X = Xb; b.out = Ob; b.M = Mb; b.H = Hb; b.W = Hb; b.stat_out = nullptr; b.ksplit = 1;
+    const IgemmPlan plan_b = plan_of(b, false, !big);
     auto time_it = [&](int mode) {
-      for (int i = 0; i < 5; ++i) { if (mode != 1) run(); if (mode != 0) igemm2_launch_main(b, !big, 0); }
+      for (int i = 0; i < 5; ++i) { if (mode != 1) run(); if (mode != 0) igemm_launch_main(b, plan_b, 0); }
       hipDeviceSynchronize();
       hipEventRecord(e0, 0);
-      for (int i = 0; i < it; ++i) { if (mode != 1) run(); if (mode != 0) igemm2_launch_main(b, !big, 0); }
+      for (int i = 0; i < it; ++i) { if (mode != 1) run(); if (mode != 0) igemm_launch_main(b, plan_b, 0); }
       hipEventRecord(e1, 0);
       hipEventSynchronize(e1);
       float t; hipEventElapsedTime(&t, e0, e1);
