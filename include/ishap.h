@@ -38,7 +38,7 @@ int ishap_device_status(void);
 int ishap_rendezvous_would_grant(const void* owner, void* stream);
 int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the size of its scratch buffer; 3 since ishap_step_coefs
                             * ends with rng / rng_seed / rng_offset / noise_out; 4 since the batched drag calls (ishap_drag_batch_*,
-                            * ishap_ddpm_step_guided_scales) */
+                            * ishap_ddpm_step_guided_scales); 5 since ishap_igemm_run / ishap_igemm_reduce */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -369,6 +369,44 @@ int ishap_profile_shapes(char* buf, int cap);
  * instance as a kernel trace names it (e.g. "igemm4_kernel<64, 64, 32, 4, 3, 1>").  0, or -2 when `kernel_cap` is too small. */
 int ishap_igemm_plan(int M, int cin, int cout, int taps, int K2, int H, int W, int nbatch, int pending, int epilogue_sums,
                      int* ksplit, int* prof_slot, char* kernel, int kernel_cap);
+
+/* One implicit-GEMM launch as a UNet layer makes it (conv_op, csrc/unet.hip), for testing a kernel form in isolation:
+ *   out[m][n] = sum_k X(m, k) * Wt[n][k] (+ bias[n]) (+ bias2[n]) (+ res[m or its half-resolution pixel][n]),
+ * k = tap * Cin + c over the 3x3 taps (zero padding per image; ups: the source map is (H/2, W/2), upsampled on the fly), then
+ * K2 columns of the folded second source X2 against Wt columns [9 Cin, 9 Cin + K2).  The kernel form and the K split follow
+ * from the shape exactly as in the product; the caller cannot choose them.  Every buffer comes with its size in bytes, and
+ * every extent the launch would touch is checked against it (and its alignment) before any HIP call: a failed check returns
+ * -2 with a message.  Row strides are in elements; X, X2, Wt, bias, bias2, ws and gb_x need 16-byte alignment, out and res
+ * 8 bytes, and ldx, ldx2, ldw are multiples of 8, ldo and ldr multiples of 4. */
+typedef struct {
+  void* ptr;
+  long long bytes;
+} ishap_buf;
+typedef struct {
+  int M, N, Cin, taps, K2, H, W;   /* M = images * H * W output pixels, H x W the output map */
+  int ldx, ldx2, ldw, ldo, ldr;
+  int ups, res_ups;                /* X / the residual is the (H/2, W/2) map */
+  int out_mode;                    /* 0: fp16 out[M][ldo]; 2: fp32 NCHW out[images][N][H][W] */
+  int pending;                     /* the consumer adds the K slices up: with a K split they stay in ws (ishap_igemm_reduce) */
+  int chunk_tiles;                 /* 0, or a multiple of 8: igemm4 forms run as launches of at most that many tiles */
+  ishap_buf X;                     /* fp16 [pixels][ldx] */
+  ishap_buf X2;                    /* fp16 [M][ldx2], K2 > 0 only */
+  ishap_buf Wt;                    /* fp16 [round_up(N, 128)][ldw], rows >= N zero */
+  ishap_buf out, bias, bias2;      /* bias, bias2: fp32 [N] or NULL */
+  ishap_buf res;                   /* fp16 [M or M / 4][ldr] or NULL; may alias out */
+  ishap_buf ws;                    /* fp32 [ksplit][M][N] when the launch splits K */
+  ishap_buf stat_out;              /* int64 [images][N][2] or NULL: += (sum, sum of squares) of the stored values, fixed point */
+  /* GroupNorm-backward sums (exclusive with stat_out): gb_csums [images][N][2] += (sum dyh, sum dyh * xhat), fixed point */
+  ishap_buf gb_x, gb_stats, gb_gamma, gb_beta, gb_emb, gb_csums;
+  int gb_emb_ld, gb_film, gb_act;
+} ishap_igemm_desc;
+/* Checks `d` and plans the launch; writes the K split and the kernel name (as ishap_igemm_plan does); with launch != 0 then
+ * enqueues it on `stream` (the split-K reduce too, unless the slices are left pending).  launch = 0: no HIP call at all. */
+int ishap_igemm_run(const ishap_igemm_desc* d, int launch, void* stream, int* ksplit, char* kernel, int kernel_cap);
+/* The stand-alone reduce of a pending launch's `nslab` slices in d->ws into d->out (+ bias, bias2, res, res_ups): what a
+ * consumer that cannot add slices up runs first (slab_materialize, csrc/unet.hip).  Reads M, N, H, W, ldo, ldr and those
+ * buffers, checked as above; launch = 0: the checks only. */
+int ishap_igemm_reduce(const ishap_igemm_desc* d, int nslab, int launch, void* stream);
 
 #ifdef __cplusplus
 }

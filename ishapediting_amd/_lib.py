@@ -43,6 +43,18 @@ class DragBatchArgsC(C.Structure):
                 ("scratch_bytes", C.c_longlong)]
 
 
+class IgemmBufC(C.Structure):
+    _fields_ = [("ptr", c_void_p), ("bytes", C.c_longlong)]
+
+
+class IgemmDescC(C.Structure):
+    _fields_ = ([(f, C.c_int) for f in ("M", "N", "Cin", "taps", "K2", "H", "W", "ldx", "ldx2", "ldw", "ldo", "ldr", "ups",
+                                        "res_ups", "out_mode", "pending", "chunk_tiles")] +
+                [(f, IgemmBufC) for f in ("X", "X2", "Wt", "out", "bias", "bias2", "res", "ws", "stat_out", "gb_x", "gb_stats",
+                                          "gb_gamma", "gb_beta", "gb_emb", "gb_csums")] +
+                [("gb_emb_ld", C.c_int), ("gb_film", C.c_int), ("gb_act", C.c_int)])
+
+
 class DecoderWeightsC(C.Structure):
     _fields_ = [("B", c_void_p), ("W1", c_void_p), ("b1", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
                 ("w3", c_void_p), ("b3", c_void_p)]
@@ -120,6 +132,8 @@ SYMBOLS = {
     "ishap_profile_end": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
     "ishap_profile_shapes": (C.c_int, [C.c_char_p, C.c_int]),
     "ishap_igemm_plan": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
+    "ishap_igemm_run": (C.c_int, [C.POINTER(IgemmDescC), C.c_int, c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_int]),
+    "ishap_igemm_reduce": (C.c_int, [C.POINTER(IgemmDescC), C.c_int, C.c_int, c_void_p]),
     "ishap_triplane_decode_grid": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_int,
                                              c_void_p, c_void_p]),
 }
@@ -147,8 +161,9 @@ def lib():
             fn = getattr(l, name)     # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
-        if l.ishap_version() < 4:     # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 4): rebuild with `python -m ishapediting_amd.build`")
+        # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run
+        if l.ishap_version() < 5:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 5): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "igemm_epilogue.h"
 #include "gn_bwd_terms.h"
+#include "../../include/ishap.h"
 
 template <int BM, int BN, int BK, int WM, int WN, bool CONV3>
 __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs a) {
@@ -483,7 +484,8 @@ int igemm_reduce_launch(const IgemmArgs& a, hipStream_t s) {
   return 0;
 }
 
-int igemm_launch(const IgemmArgs& a, hipStream_t s) {
+// what every launch must satisfy before it reaches a kernel (no HIP runtime call)
+static int igemm_check(const IgemmArgs& a, const IgemmPlan& p) {
   ISHAP_REQUIRE(a.M % 64 == 0, "M must be a multiple of 64");
   ISHAP_REQUIRE(a.N % 4 == 0, "N must be a multiple of 4");
   ISHAP_REQUIRE(a.K % 32 == 0, "K must be a multiple of 32");
@@ -495,9 +497,14 @@ int igemm_launch(const IgemmArgs& a, hipStream_t s) {
                             a.gb_stats && a.gb_gamma && a.gb_beta && (!a.gb_film || a.gb_emb)),
                 "fused GroupNorm-backward sums: fp16 dense output, N % 32 == 0, no forward statistics");
   ISHAP_REQUIRE(a.ldx % 8 == 0 && a.ldw % 8 == 0, "row strides must keep 16-byte alignment");
-  const IgemmPlan p = igemm_plan(a);
   ISHAP_REQUIRE(p.form == IgemmForm::skinny || !(a.stat_out || a.gb_x) || (a.H * a.W > 0 && (a.H * a.W) % 64 == 0),
                 "fused GroupNorm sums need H*W to be a multiple of the 64-row tile");
+  return 0;
+}
+
+int igemm_launch(const IgemmArgs& a, hipStream_t s) {
+  const IgemmPlan p = igemm_plan(a);
+  ISHAP_TRY(igemm_check(a, p));
   int prof_slot = -1;
   if (g_prof_on) {
     ProfRec r;
@@ -545,4 +552,127 @@ extern "C" int ishap_igemm_plan(int M, int cin, int cout, int taps, int K2, int 
     memcpy(kernel, name.c_str(), name.size() + 1);
   }
   return 0;
+}
+
+// ---- one launch through the C ABI (include/ishap.h, ishap_igemm_run): the IgemmArgs conv_op fills, checked against the
+// caller's buffer sizes first, then the product's own plan and launch ----
+
+static bool desc_fits(const ishap_buf& b, long long bytes, int align) {
+  return bytes <= 0 || (b.ptr && b.bytes >= bytes && ((unsigned long long)b.ptr % (unsigned)align) == 0);
+}
+#define DESC_BUF(buf, need, align, what)                                                                             \
+  ISHAP_REQUIRE(desc_fits(d->buf, (need), (align)), std::string(what) + ": needs " + std::to_string((long long)(need)) + \
+                " bytes at " #align "-byte alignment, has " + std::to_string(d->buf.bytes))
+
+// The fields conv_op sets (nbatch = 1, alpha = 1, fp16 or NCHW fp32 output), every extent the launch touches checked against
+// the caller's byte sizes, and the K split planned as conv_op plans it.  No HIP runtime call.
+static int igemm_desc_args(const ishap_igemm_desc* d, IgemmArgs& a) {
+  ISHAP_REQUIRE(d != nullptr, "descriptor");
+  constexpr long long LIM = 1ll << 31;           // the kernels index each operand with 32-bit element offsets
+  ISHAP_REQUIRE(d->taps == 1 || d->taps == 9, "taps: 1 (1x1) or 9 (3x3)");
+  ISHAP_REQUIRE(d->M > 0 && d->N > 0 && d->Cin > 0 && d->H > 0 && d->W > 0 && d->K2 >= 0 && d->M < LIM / 8 && d->N < 65536 &&
+                    d->H < 65536 && d->W < 65536,
+                "extents");
+  const long long HW = (long long)d->H * d->W;
+  ISHAP_REQUIRE(d->M % HW == 0, "M = images * H * W");
+  const long long nimg = d->M / HW;
+  ISHAP_REQUIRE(d->out_mode == IG_OUT_F16 || d->out_mode == IG_OUT_NCHW_F32, "out_mode: fp16 rows or NCHW fp32");
+  ISHAP_REQUIRE(!d->ups || (d->taps == 9 && d->H % 2 == 0 && d->W % 2 == 0), "ups: a 3x3 launch on an even map");
+  ISHAP_REQUIRE(!d->res_ups || (d->res.ptr && d->H % 2 == 0 && d->W % 2 == 0), "res_ups: a residual on an even map");
+  ISHAP_REQUIRE(d->K2 == 0 || d->taps == 9, "a folded second source rides on a 3x3 launch");
+  ISHAP_REQUIRE(d->ldx >= d->Cin && d->ldx % 8 == 0, "ldx: >= Cin, a multiple of 8");
+  ISHAP_REQUIRE(d->K2 == 0 || (d->ldx2 >= d->K2 && d->ldx2 % 8 == 0), "ldx2: >= K2, a multiple of 8");
+  const long long K = (long long)d->taps * d->Cin + d->K2;
+  ISHAP_REQUIRE(d->ldw >= K && d->ldw % 8 == 0, "ldw: >= taps * Cin + K2, a multiple of 8");
+  ISHAP_REQUIRE(d->out_mode != IG_OUT_F16 || (d->ldo >= d->N && d->ldo % 4 == 0), "ldo: >= N, a multiple of 4");
+  ISHAP_REQUIRE(!d->res.ptr || (d->ldr >= d->N && d->ldr % 4 == 0), "ldr: >= N, a multiple of 4");
+  ISHAP_REQUIRE(d->chunk_tiles >= 0 && d->chunk_tiles % 8 == 0, "chunk_tiles: 0 or a multiple of 8");
+  ISHAP_REQUIRE(!(d->stat_out.ptr && d->gb_x.ptr), "forward statistics and GroupNorm-backward sums are exclusive");
+  ISHAP_REQUIRE(d->out_mode == IG_OUT_F16 || !(d->stat_out.ptr || d->gb_x.ptr), "epilogue sums need fp16 output");
+
+  a = IgemmArgs{};
+  a.X = (const half_t*)d->X.ptr; a.X2 = (const half_t*)d->X2.ptr; a.Wt = (const half_t*)d->Wt.ptr; a.out = d->out.ptr;
+  a.bias = (const float*)d->bias.ptr; a.bias2 = (const float*)d->bias2.ptr; a.res = (const half_t*)d->res.ptr;
+  a.ws = (float*)d->ws.ptr; a.stat_out = (long long*)d->stat_out.ptr;
+  if (d->gb_x.ptr) {
+    a.gb_x = (const half_t*)d->gb_x.ptr; a.gb_stats = (const float*)d->gb_stats.ptr; a.gb_gamma = (const float*)d->gb_gamma.ptr;
+    a.gb_beta = (const float*)d->gb_beta.ptr; a.gb_emb = (const float*)d->gb_emb.ptr; a.gb_emb_ld = d->gb_emb_ld;
+    a.gb_film = d->gb_film != 0; a.gb_act = d->gb_act != 0; a.gb_csums = (long long*)d->gb_csums.ptr;
+  }
+  a.M = d->M; a.N = d->N; a.K = (int)K; a.K2 = d->K2; a.Cin = d->Cin; a.conv3 = d->taps == 9;
+  a.ldx = d->ldx; a.ldx2 = d->ldx2; a.ldw = d->ldw; a.ldo = d->ldo; a.ldr = d->ldr;
+  a.H = d->H; a.W = d->W; a.ups = d->ups != 0; a.res_ups = d->res_ups != 0;
+  a.out_mode = d->out_mode; a.chunk_tiles = d->chunk_tiles;
+  a.ksplit = igemm_plan_ksplit(a, d->pending != 0);
+  if (d->pending && a.ksplit > 1) {
+    ISHAP_REQUIRE(d->out_mode == IG_OUT_F16 && d->ldo == d->N && !d->stat_out.ptr && !d->gb_x.ptr,
+                  "deferred reduce: dense fp16 output, no epilogue sums");
+    a.defer_reduce = 1;
+  }
+
+  // every extent the launch touches, in bytes
+  const long long xrows = d->ups ? d->M / 4 : d->M, rrows = d->res_ups ? d->M / 4 : d->M;
+  const long long npad = (d->N + 127) / 128 * 128;
+  const long long xe = (xrows - 1) * d->ldx + d->Cin, x2e = (long long)(d->M - 1) * d->ldx2 + d->K2, we = npad * d->ldw;
+  const long long oe = d->out_mode == IG_OUT_F16 ? (long long)(d->M - 1) * d->ldo + d->N : (long long)d->M * d->N;
+  const long long re = (rrows - 1) * d->ldr + d->N, wse = a.ksplit > 1 ? (long long)a.ksplit * d->M * d->N : 0;
+  ISHAP_REQUIRE(xe < LIM && x2e < LIM && we < LIM && oe < LIM && re < LIM && wse < LIM, "an operand beyond 2^31 elements");
+  DESC_BUF(X, xe * 2, 16, "X");
+  if (d->K2) DESC_BUF(X2, x2e * 2, 16, "X2");
+  DESC_BUF(Wt, we * 2, 16, "Wt ([round_up(N, 128)][ldw])");
+  DESC_BUF(out, oe * (d->out_mode == IG_OUT_F16 ? 2 : 4), 8, "out");
+  if (d->res.ptr) DESC_BUF(res, re * 2, 8, "res");
+  if (d->bias.ptr) DESC_BUF(bias, (long long)d->N * 4, 16, "bias");
+  if (d->bias2.ptr) DESC_BUF(bias2, (long long)d->N * 4, 16, "bias2");
+  DESC_BUF(ws, wse * 4, 16, "ws (K slices x M x N floats)");
+  if (d->stat_out.ptr) DESC_BUF(stat_out, nimg * d->N * 16, 8, "stat_out ([images][N][2] int64)");
+  if (d->gb_x.ptr) {
+    ISHAP_REQUIRE(!d->gb_film || d->gb_emb_ld >= 2 * d->N, "gb_emb_ld: >= 2 N (scale, shift)");
+    DESC_BUF(gb_x, (long long)d->M * d->N * 2, 16, "gb_x ([M][N] fp16)");
+    DESC_BUF(gb_stats, nimg * 32 * 2 * 4, 4, "gb_stats ([images][32][2] float)");
+    DESC_BUF(gb_gamma, (long long)d->N * 4, 4, "gb_gamma");
+    DESC_BUF(gb_beta, (long long)d->N * 4, 4, "gb_beta");
+    if (d->gb_film) DESC_BUF(gb_emb, ((nimg - 1) * d->gb_emb_ld + 2 * d->N) * 4, 4, "gb_emb");
+    DESC_BUF(gb_csums, nimg * d->N * 16, 8, "gb_csums ([images][N][2] int64)");
+  }
+  return igemm_check(a, igemm_plan(a));
+}
+
+extern "C" int ishap_igemm_run(const ishap_igemm_desc* d, int launch, void* stream, int* ksplit, char* kernel, int kernel_cap) {
+  IgemmArgs a;
+  ISHAP_TRY(igemm_desc_args(d, a));
+  std::string name;
+  ISHAP_TRY(igemm_launch_main(a, igemm_plan(a), nullptr, &name));
+  if (ksplit) *ksplit = a.ksplit;
+  if (kernel) {
+    if ((int)name.size() + 1 > kernel_cap) return -2;
+    memcpy(kernel, name.c_str(), name.size() + 1);
+  }
+  return launch ? igemm_launch(a, (hipStream_t)stream) : 0;
+}
+
+extern "C" int ishap_igemm_reduce(const ishap_igemm_desc* d, int nslab, int launch, void* stream) {
+  ISHAP_REQUIRE(d != nullptr, "descriptor");
+  ISHAP_REQUIRE(nslab >= 2 && nslab <= 64, "nslab: the K slices of a deferred launch (2 .. 64)");
+  ISHAP_REQUIRE(d->M > 0 && d->N > 0 && d->H > 0 && d->W > 0 && d->M % 16 == 0 && d->N % 4 == 0 && d->M < (1 << 28) && d->N < 65536 &&
+                    d->H < 65536 && d->W < 65536 && d->M % ((long long)d->H * d->W) == 0,
+                "M = images * H * W, a multiple of 16; N a multiple of 4");
+  ISHAP_REQUIRE(d->out_mode == IG_OUT_F16 && d->ldo >= d->N && d->ldo % 4 == 0, "fp16 output, ldo >= N, a multiple of 4");
+  ISHAP_REQUIRE(!d->res.ptr || (d->ldr >= d->N && d->ldr % 4 == 0), "ldr: >= N, a multiple of 4");
+  ISHAP_REQUIRE(!d->res_ups || (d->res.ptr && d->H % 2 == 0 && d->W % 2 == 0), "res_ups: a residual on an even map");
+  ISHAP_REQUIRE(!d->stat_out.ptr && !d->gb_x.ptr, "the stand-alone reduce adds no epilogue sums");
+  const long long rrows = d->res_ups ? d->M / 4 : d->M;
+  const long long oe = (long long)(d->M - 1) * d->ldo + d->N, re = (rrows - 1) * d->ldr + d->N, wse = (long long)nslab * d->M * d->N;
+  ISHAP_REQUIRE(oe < (1ll << 31) && re < (1ll << 31) && wse < (1ll << 31), "an operand beyond 2^31 elements");
+  DESC_BUF(out, oe * 2, 8, "out");
+  if (d->res.ptr) DESC_BUF(res, re * 2, 8, "res");
+  if (d->bias.ptr) DESC_BUF(bias, (long long)d->N * 4, 16, "bias");
+  if (d->bias2.ptr) DESC_BUF(bias2, (long long)d->N * 4, 16, "bias2");
+  DESC_BUF(ws, wse * 4, 16, "ws (K slices x M x N floats)");
+  // slab_materialize's arguments (unet.hip)
+  IgemmArgs a;
+  a.ws = (float*)d->ws.ptr; a.ksplit = nslab; a.M = d->M; a.N = d->N; a.K = 64;
+  a.bias = (const float*)d->bias.ptr; a.bias2 = (const float*)d->bias2.ptr; a.res = (const half_t*)d->res.ptr; a.ldr = d->ldr;
+  a.res_ups = d->res_ups != 0; a.H = d->H; a.W = d->W; a.out = d->out.ptr; a.ldo = d->ldo; a.out_mode = IG_OUT_F16;
+  return launch ? igemm_reduce_launch(a, (hipStream_t)stream) : 0;
 }
