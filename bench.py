@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the denoise-and-drag hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one complete drag edit of one shape (BASELINE.json config 3 / SURVEY.md 8(d) "C3"):
@@ -13,6 +13,10 @@ features) is reported as `unet_steps_per_s`.  Ranks edit independent shapes (wea
 collective is the final gather of the occupancy volumes to rank 0 (RCCL), inside the timed region.
 Prints ONE JSON line on rank 0.  --dump-outputs DIR: rank 0 also writes what the last timed step computed as
 DIR/<name>.npy (float32; see dump_outputs), so that two builds can be compared output for output.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump, the line.  --full adds, after the
+timed steps, every leg that only reports next to the headline: the roofline / per-kernel leg (one more edit with HIP events on
+every implicit-GEMM launch), the surface-extraction timings, the CPU baseline, concurrent edits, C2 at batch 1 and 8, and C4
+(each still switched off by its --no-* option).
 """
 import argparse
 import ctypes as C
@@ -196,6 +200,32 @@ def visible_gpu_count():
             k = len([t for t in v.split(",") if t.strip() != ""])
             n = k if n is None else min(n, k)
     return n
+
+
+def surface_leg(device, vol):
+    """Surface of the last decoded volume on the device (reported separately from the headline, as BASELINE's metric
+    does for marching cubes): marching cubes (256-case table) + 10 smoothing sweeps, csrc/surface.hip."""
+    from ishapediting_amd.mesh import extract_surface, smooth_mesh
+    extract_surface(vol)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    sv, st = extract_surface(vol)
+    smooth_mesh(sv, st, 10)
+    torch.cuda.synchronize()
+    surface_ms = (time.time() - t0) * 1e3
+    # the random-weight volume is noise (surface through almost every cell); a shape-like volume for scale:
+    ax = torch.arange(RES, dtype=torch.float32, device=device) - 120.3
+    sph = 90.4 - torch.sqrt(ax[:, None, None] ** 2 + ax[None, :, None] ** 2 + ax[None, None, :] ** 2)
+    extract_surface(sph)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    sv2, st2 = extract_surface(sph)
+    smooth_mesh(sv2, st2, 10)
+    torch.cuda.synchronize()
+    surface_ms_sphere = (time.time() - t0) * 1e3
+    return {"surface_vertices": int(sv.shape[0]), "surface_triangles": int(st.shape[0]),
+            "surface_extract_ms": round(surface_ms, 2),
+            "surface_extract_ms_sphere256": round(surface_ms_sphere, 2), "sphere256_vertices": int(sv2.shape[0])}
 
 
 def c2_generate_leg(device, steps=1000, batch=1):
@@ -430,11 +460,14 @@ def spawn_workers(a):
     sys.exit(rc)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the legs reported next to it: roofline / per-kernel profile, surface "
+                         "extraction, CPU baseline, concurrent edits, C2, C4 (a plain run times the headline steps only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c2", action="store_true", help="skip the generate-path leg (BASELINE configs[1]) after the headline")
     ap.add_argument("--c2-steps", type=int, default=1000)
@@ -448,9 +481,16 @@ def main():
     ap.add_argument("--shape-profile", default=None, help="write the per-shape conv/GEMM timing CSV of one edit here")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (volume sample, latent, drag losses) as DIR/<name>.npy")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full and (a.shape_profile or a.c4_shape_profile):
+        ap.error("--shape-profile and --c4-shape-profile come from legs that only --full runs")
+    return a
+
+
+def main():
+    a = parse_args()
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -535,9 +575,9 @@ def main():
     if a.dump_outputs and rank == 0:             # before the roofline leg's extra edit replaces the last timed step's results
         dump_outputs(a.dump_outputs, ds, world, recv)
 
-    # ---- roofline leg: the same edit once more with HIP events around every implicit-GEMM launch ----
+    # ---- roofline leg (--full): the same edit once more with HIP events around every implicit-GEMM launch ----
     roofline = small_maps = step_breakdown = None
-    if rank == 0:
+    if rank == 0 and a.full:
         L = _lib.lib()
         # per-launch durations are measured in the PLAIN launch sequence: in the timed (default) configuration the forward tail
         # shares the chip with loss + backward, and a launch's duration inside that window is not the kernel's own
@@ -657,30 +697,10 @@ def main():
                                                 "tflops": round(out[i * 3 + 2] / max(out[i * 3 + 1], 1e-9) / 1e9, 1)}
                                      for i in range(NV) if out[i * 3] > 0}}
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(1234)
 
     if rank == 0:
-        # surface of the last decoded volume on the device (reported separately from the headline, as BASELINE's metric
-        # does for marching cubes): marching cubes (256-case table) + 10 smoothing sweeps, csrc/surface.hip
-        from ishapediting_amd.mesh import extract_surface, smooth_mesh
-        extract_surface(vol)
-        torch.cuda.synchronize()
-        t0 = time.time()
-        sv, st = extract_surface(vol)
-        smooth_mesh(sv, st, 10)
-        torch.cuda.synchronize()
-        surface_ms = (time.time() - t0) * 1e3
-        # the random-weight volume is noise (surface through almost every cell); a shape-like volume for scale:
-        ax = torch.arange(RES, dtype=torch.float32, device=device) - 120.3
-        sph = 90.4 - torch.sqrt(ax[:, None, None] ** 2 + ax[None, :, None] ** 2 + ax[None, None, :] ** 2)
-        extract_surface(sph)
-        torch.cuda.synchronize()
-        t0 = time.time()
-        sv2, st2 = extract_surface(sph)
-        smooth_mesh(sv2, st2, 10)
-        torch.cuda.synchronize()
-        surface_ms_sphere = (time.time() - t0) * 1e3
         line = {
             "metric": "end-to-end drag-edit wall-clock (s) per shape", "value": round(sec_per_shape, 4), "unit": "s/shape",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
@@ -693,28 +713,28 @@ def main():
             "algorithmic_tflops_per_gpu": round((GUIDED_STEPS * GUIDED_GFLOP + 1185.0) / 1e3 / (dt / a.steps), 1),
             "unet_steps_per_s": round(NUM_STEPS / t_setup, 2),
             "setup_s": round(t_setup, 3),
-            "surface_vertices": int(sv.shape[0]), "surface_triangles": int(st.shape[0]),
-            "surface_extract_ms": round(surface_ms, 2),
-            "surface_extract_ms_sphere256": round(surface_ms_sphere, 2), "sphere256_vertices": int(sv2.shape[0]),
-            "roofline": roofline, "roofline_small_maps": small_maps, "step_breakdown": step_breakdown, "cpu_baseline": cpu,
-            "per_rank": per_rank,
         }
+        if a.full:
+            line.update(surface_leg(device, vol))
+        line.update({"roofline": roofline, "roofline_small_maps": small_maps, "step_breakdown": step_breakdown, "cpu_baseline": cpu,
+                     "per_rank": per_rank})
         if a.rehearse:
             line["data"] = "synthetic; REHEARSAL (all ranks on one GPU, gloo on host copies): not a measurement"
         if cpu:
             line["speedup_vs_cpu_baseline"] = round(cpu["value"] / sec_per_shape, 1)
-        if world == 1 and not a.no_concurrent:
+        legs = world == 1 and a.full                                 # the one-GPU legs reported next to the headline
+        if legs and not a.no_concurrent:
             line.update(concurrent_edits_leg(device, ds, src, tgt, 1235))
-        if world == 1 and not (a.no_c2 and a.no_c4):
+        if legs and not (a.no_c2 and a.no_c4):
             del ds                                                   # the edit context's arena + guidance cache
             torch.cuda.empty_cache()
-        if world == 1 and not a.no_c2:
+        if legs and not a.no_c2:
             line.update(c2_generate_leg(device, a.c2_steps))
             torch.cuda.empty_cache()
             if not a.no_c2_batch8:
                 line.update(c2_generate_leg(device, a.c2_steps, batch=8))
                 torch.cuda.empty_cache()
-        if world == 1 and not a.no_c4:
+        if legs and not a.no_c4:
             line.update(c4_real_shape_leg(device, a.c4_shape_profile))
         print(json.dumps(line), flush=True)
     if world > 1:

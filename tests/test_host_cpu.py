@@ -231,6 +231,17 @@ def test_bench_counts_gpus_without_loading_hip(monkeypatch):
     assert bench.visible_gpu_count() == 0
 
 
+def test_bench_plain_run_leaves_the_side_legs_to_full():
+    """A plain bench run times the headline only; the legs reported next to it, and the profile files they write, need --full."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert not a.full
+    assert bench.parse_args(["--full", "--no-c2", "--shape-profile", "s.csv"]).full
+    for opt in ("--shape-profile", "--c4-shape-profile"):
+        with pytest.raises(SystemExit):
+            bench.parse_args([opt, "s.csv"])
+
+
 def test_philox_restatement_known_answers():
     """Random123's known-answer vectors for philox4x32-10 pin the test-side generator (tests/helpers.py) that the step kernel's
     in-launch noise is compared with on the GPU (test_gpu_parity.py::test_step_draws_its_own_noise)."""

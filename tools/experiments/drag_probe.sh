@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 for cfg in "1024 512" "1024 1024"; do
   set -- $cfg
   export ISHAP_DRAG_BLOCKS=$1 ISHAP_DRAG_OUT_BLOCKS=$2
-  rm -rf /tmp/dp; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/dp -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > /tmp/dp.json 2>/dev/null || exit 1
+  rm -rf $TMPDIR/dp; rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/dp -- python3 $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > $TMPDIR/dp.json 2>/dev/null || exit 1
   python3 - "$1 $2" $(find /tmp/dp -name "*kernel_stats.csv") <<'PY'
 import csv, json, sys
 print("cap", sys.argv[1], "bench", json.load(open("/tmp/dp.json"))["value"], end="  ")

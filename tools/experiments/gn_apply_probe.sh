@@ -4,7 +4,7 @@ R=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for cap in 1024 512 256 2048; do
   export ISHAP_GN_APPLY_BLOCKS=$cap
-  rm -rf /tmp/gp; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/gp -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > /tmp/gp.json 2>/dev/null || exit 1
+  rm -rf $TMPDIR/gp; rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/gp -- python3 $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > $TMPDIR/gp.json 2>/dev/null || exit 1
   python3 - "$cap" $(find /tmp/gp -name "*kernel_stats.csv") <<'PY'
 import csv, sys
 tot = 0

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 for cfg in "8 256 256" "16 256 512" "16 512 512" "16 128 512" "8 128 256"; do
   set -- $cfg
   export ISHAP_GN_PARTS=$1 ISHAP_GN_PART_ELEMS=$2 ISHAP_GN_MAX_WGS=$3
-  rm -rf /tmp/gp; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/gp -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > /tmp/gp.json 2>/dev/null || exit 1
+  rm -rf $TMPDIR/gp; rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/gp -- python3 $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > $TMPDIR/gp.json 2>/dev/null || exit 1
   python3 - "$1 $2 $3" $(find /tmp/gp -name "*kernel_stats.csv") <<'PY'
 import csv, sys
 f = b = nf = nb = 0

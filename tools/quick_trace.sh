@@ -5,7 +5,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/quick
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-concurrent --no-c2 --no-c4 --shape-profile $O/shapes.csv > $O/shapes_bench.json 2> $O/shapes.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-concurrent --no-c2 --no-c4 --shape-profile $O/shapes.csv > $O/shapes_bench.json 2> $O/shapes.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-concurrent --no-c2 --no-c4 > $O/trace_bench.json 2> $O/trace.err || exit 1
 f=$(find $O/trace -name "*kernel_trace.csv")
 python3 $R/tools/trace_by_grid.py $f > $O/kernel_by_grid.txt
