@@ -303,6 +303,25 @@ int ishap_triplane_decode_grid(const float* planes, int S, const ishap_decoder_w
 int ishap_triplane_points_loss_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* W1T,
                                     const float* W2T, const float* coords, const float* gt, long long npts,
                                     float* dplanes, float* loss, float* logits, void* stream);
+/* direct triplane fitting (drag_utils.py:473-550, train_triplane_opt), one Adam step = these two calls:
+ * (1) dplanes [3][S][S][32] += d(BCE + pair_w * mse)/d planes and loss_parts[2] += {BCEWithLogits mean, mse} for the batch
+ *     coords[idx[i]] / gt[idx[i]] (i < nbatch; coords [P][3], gt [P], idx int32) and the random pairs r = rand_coords[j],
+ *     r + 0.01 * rand_noise[j] (j < nrand; [nrand][3] each; points outside [-1,1] sample zeros).  Float atomics: the
+ *     low bits of dplanes vary from run to run. */
+int ishap_triplane_fit_loss_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* coords,
+                                 const float* gt, const int* idx, long long nbatch, const float* rand_coords,
+                                 const float* rand_noise, long long nrand, float pair_w, float* dplanes, float* loss_parts,
+                                 void* stream);
+/* (2) reg_parts[2] = {l2reg, tvreg} of `planes` (axisnetworks.py:564-575, one object), then torch's Adam step (no weight
+ *     decay) on grad = dplanes + l2_w * d l2reg + tv_w * d tvreg into planes_out (must not alias planes); m, v: Adam state
+ *     [3][S][S][32]; step: device int32 step count, incremented by the call; dplanes is left zeroed.  reg_parts may be NULL.
+ *     ws: device double[ISHAP_TRIPLANE_REG_WS].  Bitwise repeatable. */
+#define ISHAP_TRIPLANE_REG_WS 576
+int ishap_triplane_reg_adam_step(const float* planes, float* planes_out, float* m, float* v, float* dplanes, int S, int* step,
+                                 double lr, double beta1, double beta2, double eps, float l2_w, float tv_w, double* ws,
+                                 float* reg_parts, void* stream);
+/* reg_parts[2] = {l2reg, tvreg} of planes alone (MultiTriplane.l2reg / tvreg); ws as above */
+int ishap_triplane_reg_values(const float* planes, int S, double* ws, float* reg_parts, void* stream);
 /* chain rule from planes = clamp(sqrt_recip*x - sqrt_recipm1*eps, -1, 1)*range + middle back to the step's inputs
  * (drag_utils.py:448-450, gd/gaussian_diffusion.py:333-338,299-301): g_direct [96][S][S] = explicit d/dx term,
  * cot_out [192][S][S] = cotangent of the model output (eps half; variance half zero) for the UNet backward */

@@ -117,6 +117,13 @@ SYMBOLS = {
                                                   c_void_p, c_void_p, c_void_p]),
     "ishap_grad_to_scaled_f16": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
     "ishap_planes_prepare": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, c_void_p, c_void_p]),
+    "ishap_triplane_fit_loss_grad": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, c_void_p, c_void_p,
+                                               C.c_longlong, c_void_p, c_void_p, C.c_longlong, C.c_float, c_void_p, c_void_p,
+                                               c_void_p]),
+    "ishap_triplane_reg_adam_step": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int, c_void_p, C.c_double,
+                                               C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, c_void_p, c_void_p,
+                                               c_void_p]),
+    "ishap_triplane_reg_values": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, c_void_p]),
     "ishap_triplane_decode_points": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_longlong,
                                                c_void_p, c_void_p]),
     "ishap_surface_scratch_bytes": (C.c_longlong, [C.c_int]),
@@ -161,9 +168,10 @@ def lib():
             fn = getattr(l, name)     # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
-        # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run
-        if l.ishap_version() < 5:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 5): rebuild with `python -m ishapediting_amd.build`")
+        # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run;
+        # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*
+        if l.ishap_version() < 6:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 6): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -334,6 +334,40 @@ int ishap_triplane_points_loss_grad(const float* planes, int S, const ishap_deco
   return decode_points_bwd_launch(b, (hipStream_t)stream);
 }
 
+int ishap_triplane_fit_loss_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* coords,
+                                 const float* gt, const int* idx, long long nbatch, const float* rand_coords,
+                                 const float* rand_noise, long long nrand, float pair_w, float* dplanes, float* loss_parts,
+                                 void* stream) {
+  DecodeArgs d;
+  ISHAP_TRY(fill_dec(w, d));
+  ISHAP_REQUIRE(planes && dplanes && loss_parts, "null argument");
+  ISHAP_REQUIRE(nbatch == 0 || (coords && gt && idx), "null batch");
+  ISHAP_REQUIRE(nrand == 0 || (rand_coords && rand_noise), "null random pairs");
+  FitArgs f;
+  f.planes = planes; f.S = S; f.B = d.B; f.W1 = d.W1; f.b1 = d.b1; f.W2 = d.W2; f.b2 = d.b2; f.w3 = d.w3; f.b3 = d.b3;
+  f.coords = coords; f.gt = gt; f.idx = idx; f.nbatch = nbatch; f.rcoords = rand_coords; f.rnoise = rand_noise;
+  f.nrand = nrand; f.pair_w = pair_w; f.dplanes = dplanes; f.loss_parts = loss_parts;
+  return triplane_fit_loss_grad_launch(f, (hipStream_t)stream);
+}
+
+int ishap_triplane_reg_adam_step(const float* planes, float* planes_out, float* m, float* v, float* dplanes, int S, int* step,
+                                 double lr, double beta1, double beta2, double eps, float l2_w, float tv_w, double* ws,
+                                 float* reg_parts, void* stream) {
+  static_assert(ISHAP_TRIPLANE_REG_WS == 3 * TRIPLANE_REG_BLOCKS * 3, "workspace size");
+  ISHAP_REQUIRE(planes_out && m && v && dplanes && step, "null argument");
+  RegAdamArgs r;
+  r.planes = planes; r.S = S; r.ws = ws; r.reg_parts = reg_parts; r.planes_out = planes_out; r.m = m; r.v = v;
+  r.dplanes = dplanes; r.step = step; r.lr = lr; r.beta1 = beta1; r.beta2 = beta2; r.eps = eps; r.l2_w = l2_w; r.tv_w = tv_w;
+  return triplane_reg_adam_launch(r, (hipStream_t)stream);
+}
+
+int ishap_triplane_reg_values(const float* planes, int S, double* ws, float* reg_parts, void* stream) {
+  ISHAP_REQUIRE(reg_parts, "null argument");
+  RegAdamArgs r;
+  r.planes = planes; r.S = S; r.ws = ws; r.reg_parts = reg_parts;
+  return triplane_reg_adam_launch(r, (hipStream_t)stream);
+}
+
 int ishap_x0_grad_to_cotangent(const float* dplanes, const float* range, const float* x, const float* model_out,
                                float sqrt_recip, float sqrt_recipm1, int clip_denoised, int S, float* g_direct,
                                float* cot_out, void* stream) {

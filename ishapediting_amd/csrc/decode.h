@@ -2,6 +2,28 @@
 #include "common.h"
 #include <algorithm>
 
+// accumulator register s of lane-half h of a 32x32 MFMA tile holds row kmap(s, h) (cdna_hip_programming.md, C/D layout)
+__device__ __forceinline__ int kmap(int s, int h) { return (s & 3) + 8 * (s >> 2) + 4 * h; }
+
+// sin/cos of an fp32 angle: 3-term Cody-Waite reduction by pi/2 (exact for |x| < ~1e4, far above the Fourier
+// phases seen here) + the classic single-precision minimax polynomials on [-pi/4, pi/4]; ~1e-7 absolute.
+// (ocml's sincosf inlines its huge-argument path 64 times per tile and blows the register budget.)
+__device__ __forceinline__ void sincos_cw(float x, float& s, float& c) {
+  const float k = rintf(x * 0.63661977236758134f);
+  float r = fmaf(-k, 1.5703125f, x);
+  r = fmaf(-k, 4.837512969970703125e-4f, r);
+  r = fmaf(-k, 7.54978995489188e-8f, r);
+  const float z = r * r;
+  const float sp = fmaf(r * z, fmaf(z, fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f), -1.6666654611e-1f), r);
+  const float cp = fmaf(z * z, fmaf(z, fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f), 4.166664568298827e-2f),
+                        fmaf(z, -0.5f, 1.f));
+  const int q = (int)k & 3;
+  const float s1 = (q & 1) ? cp : sp;
+  const float c1 = (q & 1) ? sp : cp;
+  s = (q & 2) ? -s1 : s1;
+  c = ((q + 1) & 2) ? -c1 : c1;
+}
+
 struct DecodeArgs {
   const float* planes = nullptr;   // [3][S][S][32] un-normalised, channels-last
   int S = 0;
@@ -36,3 +58,37 @@ int decode_points_bwd_launch(const DecBwdArgs& a, hipStream_t s);
 int x0_grad_launch(const float* dplanes, const float* rng, const float* x, const float* model_out, float sr, float srm1,
                    int clip, int S, float* g_direct, float* cot_out, hipStream_t s);
 int planes_prepare_launch(const float* latent, const float* rng, const float* mid, float* planes, int S, hipStream_t s);
+
+// Direct triplane fitting (reference: drag_utils.py:473-550, train_triplane_opt), csrc/decode_fit.hip.
+struct FitArgs {
+  const float* planes = nullptr;   // [3][S][S][32] un-normalised, channels-last
+  int S = 0;
+  const float *B = nullptr, *W1 = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
+  const float* coords = nullptr;   // [P][3] occupancy samples
+  const float* gt = nullptr;       // [P]
+  const int* idx = nullptr;        // [nbatch] this step's batch: coords[idx[i]], gt[idx[i]]
+  long long nbatch = 0;
+  const float* rcoords = nullptr;  // [nrand][3] r = rand*2-1
+  const float* rnoise = nullptr;   // [nrand][3] randn; the pair partner is r + 0.01 * noise
+  long long nrand = 0;
+  float pair_w = 0.f;              // weight of the pair mse (0.3)
+  float* dplanes = nullptr;        // [3][S][S][32] += d(BCE + pair_w * mse)/d planes
+  float* loss_parts = nullptr;     // [2] += {BCE mean, mse}
+};
+int triplane_fit_loss_grad_launch(const FitArgs& a, hipStream_t s);
+
+#define TRIPLANE_REG_BLOCKS 64     // partial-sum blocks per plane of the regulariser reduction
+struct RegAdamArgs {
+  const float* planes = nullptr;   // [3][S][S][32] this step's planes
+  int S = 0;
+  double* ws = nullptr;            // [3][TRIPLANE_REG_BLOCKS][3] partial sums
+  float* reg_parts = nullptr;      // [2] = {l2reg, tvreg} of `planes` (may be null when stepping)
+  // Adam (all null: the regulariser values alone)
+  float* planes_out = nullptr;     // the stepped planes (must not alias `planes`)
+  float *m = nullptr, *v = nullptr;
+  float* dplanes = nullptr;        // read, then zeroed
+  int* step = nullptr;             // device step counter, incremented by the launch
+  double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0;   // double as torch's Python scalars (1 - 0.999f is not 0.001f)
+  float l2_w = 0.f, tv_w = 0.f;
+};
+int triplane_reg_adam_launch(const RegAdamArgs& a, hipStream_t s);

@@ -21,27 +21,6 @@
 #define LDH 136   // padded row stride (halfs) of the split weight images: 272 B = 16 B mod 256 -> conflict-free ds_read_b128
 #define LDB 36    // padded row stride (floats) of the Fourier matrix
 
-__device__ __forceinline__ int kmap(int s, int h) { return (s & 3) + 8 * (s >> 2) + 4 * h; }
-
-// sin/cos of an fp32 angle: 3-term Cody-Waite reduction by pi/2 (exact for |x| < ~1e4, far above the Fourier
-// phases seen here) + the classic single-precision minimax polynomials on [-pi/4, pi/4]; ~1e-7 absolute.
-// (ocml's sincosf inlines its huge-argument path 64 times per tile and blows the register budget.)
-__device__ __forceinline__ void sincos_cw(float x, float& s, float& c) {
-  const float k = rintf(x * 0.63661977236758134f);
-  float r = fmaf(-k, 1.5703125f, x);
-  r = fmaf(-k, 4.837512969970703125e-4f, r);
-  r = fmaf(-k, 7.54978995489188e-8f, r);
-  const float z = r * r;
-  const float sp = fmaf(r * z, fmaf(z, fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f), -1.6666654611e-1f), r);
-  const float cp = fmaf(z * z, fmaf(z, fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f), 4.166664568298827e-2f),
-                        fmaf(z, -0.5f, 1.f));
-  const int q = (int)k & 3;
-  const float s1 = (q & 1) ? cp : sp;
-  const float c1 = (q & 1) ? sp : cp;
-  s = (q & 2) ? -s1 : s1;
-  c = ((q + 1) & 2) ? -c1 : c1;
-}
-
 // latent [96][S][S] (NCHW, one shape) * range + middle  ->  planes [3][S][S][32]   (drag_utils.py:295)
 __global__ void planes_prepare_kernel(const float* __restrict__ latent, const float* __restrict__ rng,
                                       const float* __restrict__ mid, float* __restrict__ planes, int S) {

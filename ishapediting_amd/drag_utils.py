@@ -300,6 +300,24 @@ def synthesize_latent(model, diffusion, args=None, t1=None, t2=0, inter_latent_i
             "pred_xstart": predict_x0, "model_output": model_output, "variance": variance, "noise": noise}
 
 
+def load_triplane_stats(stats=None, stats_dir=None):
+    """(means, stds) of the triplane statistics (96 values each) for train_triplane_opt's init: `stats` when given, else
+    {stats_dir}/means.npy and stds.npy (the reference reads them from the chairs statistics directory)."""
+    if stats is not None:
+        means, stds = stats
+    else:
+        files = [os.path.join(stats_dir, f) for f in ("means.npy", "stds.npy")] if stats_dir else []
+        if not files or not all(os.path.exists(f) for f in files):
+            raise FileNotFoundError(
+                "train_triplane_opt needs the triplane statistics: pass stats=(means, stds) or set args.stats_dir to a "
+                f"directory holding means.npy and stds.npy (stats_dir={stats_dir!r})")
+        means, stds = (np.load(f) for f in files)
+    means, stds = (np.asarray(v, dtype=np.float32).reshape(-1) for v in (means, stds))
+    if means.size != 96 or stds.size != 96:
+        raise ValueError(f"triplane statistics must hold 96 values each, not {means.size} and {stds.size}")
+    return means, stds
+
+
 class DragStuff:
     """drag_utils.py:174-583."""
 
@@ -684,6 +702,44 @@ class DragStuff:
             img = new
             self.last_losses.append(loss)
         return img
+
+    def train_triplane_opt(self, mesh=None, mesh_path=None, center_mesh=True, path="./", points=None, occupancies=None,
+                           stats=None, epochs=20, batch_size=40000, lr=1e-3, seed=None, batch_fn=None):
+        """drag_utils.py:473-550: fit the three planes to the mesh's occupancy directly (Adam on BCE + 0.3 pair mse +
+        0.001 l2reg + 0.01 tvreg, the MLP frozen; no diffusion model).  `points`/`occupancies` replace the mesh sampling;
+        `stats=(means, stds)` replaces {args.stats_dir}/means.npy, stds.npy (the init is randn * stds + means); `seed`
+        seeds the one device generator behind the init, the per-epoch permutations and the random pairs;
+        `batch_fn(step) -> (idx, r, noise)` injects a step's batch.  Saves tri_feat_opt.npy and mesh_opt.obj under `path`,
+        leaves the fitted planes in decoder.embeddings and the per-step (bce, mse, l2reg, tvreg) in last_losses [steps, 4],
+        and returns the normalised latent (planes - middle) / range [1,96,S,S].  The drag state is not touched."""
+        from .triplane_decoder import fit_triplanes, planes_to_latent
+        means, stds = load_triplane_stats(stats, self.args.stats_dir)
+        if points is None:      # a seeded call samples from torch.Generator().manual_seed(seed)
+            points, occupancies = mesh_backend.sample_occupancy(
+                mesh, mesh_path, center_mesh, self.args.points_size, self.args.points_uniform_ratio, device=self.device,
+                generator=None if seed is None else th.Generator().manual_seed(int(seed)))
+            if points is None:
+                return None
+        points = th.as_tensor(np.asarray(points) if not th.is_tensor(points) else points, dtype=th.float32).to(self.device)
+        occupancies = th.as_tensor(np.asarray(occupancies) if not th.is_tensor(occupancies) else occupancies,
+                                   dtype=th.float32).reshape(-1).to(self.device)
+        S = self.args.image_size
+        gen = th.Generator(device=self.device)
+        if seed is not None:
+            gen.manual_seed(int(seed))
+        else:
+            gen.seed()
+        mean = th.as_tensor(np.asarray(means), dtype=th.float32).reshape(1, 96, 1, 1).to(self.device)
+        std = th.as_tensor(np.asarray(stds), dtype=th.float32).reshape(1, 96, 1, 1).to(self.device)
+        init = th.randn((1, 96, S, S), generator=gen, device=self.device) * std + mean
+        planes, self.last_losses = fit_triplanes(self.decoder, points, occupancies, init, epochs=epochs,
+                                                 batch_size=batch_size, lr=lr, generator=gen, batch_fn=batch_fn)
+        fitted = planes_to_latent(planes)
+        self.decoder.embeddings = [fitted[:, 32 * i:32 * (i + 1)].clone() for i in range(3)]
+        latent = (fitted - self.middle) / self.range
+        np.save(os.path.join(path, "tri_feat_opt.npy"), latent.cpu().numpy())
+        mesh_backend.write_mesh(os.path.join(path, "mesh_opt.obj"), self.get_mesh(latent))
+        return latent
 
     def latent_inversion(self, tri_feat, fwd_noise=None):
         outs = self.diffusion.ddpm_inversion(self.model, tri_feat, self.args.w_time, fwd_noise=fwd_noise,

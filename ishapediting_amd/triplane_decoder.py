@@ -16,6 +16,10 @@ import torch
 from . import _lib
 from .unet_spec import DECODER_SHAPES
 
+# train_triplane_opt's loss weights and optimiser (drag_utils.py:516-539)
+PAIR_WEIGHT, L2_WEIGHT, TV_WEIGHT = 0.3, 0.001, 0.01
+REG_WS = 576          # doubles of regulariser workspace (ISHAP_TRIPLANE_REG_WS, include/ishap.h)
+
 
 class _Net:
     """Stands in for the nn.Sequential `net` (axisnetworks.py:526-535): holds the seven tensors on the device."""
@@ -120,6 +124,50 @@ class MultiTriplane:
         return loss, dplanes, logits
 
 
+    def fit_loss_grad(self, planes: torch.Tensor, coords: torch.Tensor, gt: torch.Tensor, idx: torch.Tensor,
+                      rand_coords: torch.Tensor, rand_noise: torch.Tensor, dplanes: Optional[torch.Tensor] = None,
+                      loss_parts: Optional[torch.Tensor] = None, pair_weight: float = PAIR_WEIGHT):
+        """The decoder terms of one train_triplane_opt step (drag_utils.py:526-535) on explicit channels-last planes
+        [3,S,S,32]: BCEWithLogits(decoder(coords[idx]), gt[idx]) + pair_weight * mse(decoder(r), decoder(r + 0.01 * noise)).
+        Adds d loss / d planes into `dplanes` and {BCE, mse} into `loss_parts` (both zero-allocated when None, both device
+        tensors) and returns (loss_parts, dplanes).  One kernel launch, no host synchronisation."""
+        dev = self.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        coords = coords.detach().to(**f32).reshape(-1, 3).contiguous()
+        gt = gt.detach().to(**f32).reshape(-1).contiguous()
+        idx = idx.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        rc = rand_coords.detach().to(**f32).reshape(-1, 3).contiguous()
+        rn = rand_noise.detach().to(**f32).reshape(-1, 3).contiguous()
+        assert coords.shape[0] == gt.shape[0] and rc.shape == rn.shape
+        assert planes.dtype == torch.float32 and planes.is_contiguous() and planes.shape[0] == 3 and planes.shape[3] == 32
+        if dplanes is None:
+            dplanes = torch.zeros_like(planes)
+        if loss_parts is None:
+            loss_parts = torch.zeros(2, **f32)
+        w = self.net.weights_c()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ishap_triplane_fit_loss_grad(
+                planes.data_ptr(), planes.shape[1], C.byref(w), coords.data_ptr(), gt.data_ptr(), idx.data_ptr(), idx.numel(),
+                rc.data_ptr(), rn.data_ptr(), rc.shape[0], float(pair_weight), dplanes.data_ptr(), loss_parts.data_ptr(),
+                _lib.stream_ptr(dev)))
+        return loss_parts, dplanes
+
+    def _reg_values(self) -> torch.Tensor:
+        """{l2reg, tvreg} summed over the objects' planes, divided by num_objs (axisnetworks.py:564-575)."""
+        out = torch.zeros(2, dtype=torch.float32, device=self.device)
+        for o in range(self.num_objs):
+            out += reg_values(self._planes(o))
+        return out / self.num_objs
+
+    def l2reg(self) -> torch.Tensor:
+        """axisnetworks.py:571-575: sum of the planes' L2 norms / num_objs, as a device scalar."""
+        return self._reg_values()[0]
+
+    def tvreg(self) -> torch.Tensor:
+        """axisnetworks.py:564-569: sum of the planes' H and W total-variation norms / num_objs, as a device scalar."""
+        return self._reg_values()[1]
+
+
 def prepare_planes(latent: torch.Tensor, rng: Optional[torch.Tensor], mid: Optional[torch.Tensor]) -> torch.Tensor:
     """(tri_feat * range + middle).reshape(3,32,S,S) (drag_utils.py:295) as channels-last planes, one kernel."""
     assert latent.shape[0] == 1 and latent.shape[1] == 96
@@ -157,3 +205,98 @@ def decode_planes_grid(decoder: MultiTriplane, planes: torch.Tensor, res: int) -
 def decode_volume(decoder: MultiTriplane, latent: torch.Tensor, rng, mid, res: int) -> torch.Tensor:
     """get_mesh's decode half (drag_utils.py:295-298 + visualize.py:79-97) without leaving the device."""
     return decode_planes_grid(decoder, prepare_planes(latent, rng, mid), res)
+
+
+def reg_values(planes: torch.Tensor) -> torch.Tensor:
+    """{l2reg, tvreg} (axisnetworks.py:564-575, one object) of channels-last planes [3,S,S,32] as a device float[2]."""
+    dev = planes.device
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(REG_WS, dtype=torch.float64, device=dev)
+    planes = planes.detach().to(dtype=torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ishap_triplane_reg_values(planes.data_ptr(), planes.shape[1], ws.data_ptr(), out.data_ptr(),
+                                                        _lib.stream_ptr(dev)))
+    return out
+
+
+class TriplaneAdam:
+    """torch.optim.Adam(planes, lr, betas, eps) for channels-last planes [3,S,S,32], with train_triplane_opt's two
+    regularisers folded into the step (drag_utils.py:536-539).  m, v and the step count live on the device; `step()` reads
+    the accumulated `dplanes`, adds the regulariser gradients, steps and leaves `dplanes` zeroed.  The planes alternate
+    between two buffers: `planes` is the current one."""
+
+    def __init__(self, planes: torch.Tensor, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 l2_weight: float = L2_WEIGHT, tv_weight: float = TV_WEIGHT):
+        assert planes.dtype == torch.float32 and planes.dim() == 4 and planes.shape[0] == 3 and planes.shape[3] == 32
+        self.planes = planes.detach().clone().contiguous()
+        self._spare = torch.empty_like(self.planes)
+        self.m = torch.zeros_like(self.planes)
+        self.v = torch.zeros_like(self.planes)
+        self.dplanes = torch.zeros_like(self.planes)
+        self.step_count = torch.zeros(1, dtype=torch.int32, device=planes.device)
+        self.ws = torch.empty(REG_WS, dtype=torch.float64, device=planes.device)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.l2_weight, self.tv_weight = float(l2_weight), float(tv_weight)
+
+    def step(self, reg_parts: Optional[torch.Tensor] = None):
+        """One Adam step; `reg_parts` (device float[2] or None) receives {l2reg, tvreg} of the planes before the step."""
+        dev = self.planes.device
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ishap_triplane_reg_adam_step(
+                self.planes.data_ptr(), self._spare.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.dplanes.data_ptr(),
+                self.planes.shape[1], self.step_count.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
+                self.l2_weight, self.tv_weight, self.ws.data_ptr(), _lib.ptr(reg_parts), _lib.stream_ptr(dev)))
+        self.planes, self._spare = self._spare, self.planes
+        return self.planes
+
+
+def batch_schedule(n: int, batch_size: int):
+    """DataLoader(batch_size, shuffle=True)'s batches over n samples: (start, count) into the epoch's permutation,
+    the last one partial when batch_size does not divide n."""
+    if n <= 0 or batch_size <= 0:
+        raise ValueError(f"need points and a positive batch size (n={n}, batch_size={batch_size})")
+    return [(s, min(batch_size, n - s)) for s in range(0, n, batch_size)]
+
+
+def planes_to_latent(planes: torch.Tensor) -> torch.Tensor:
+    """channels-last planes [3,S,S,32] -> [1,96,S,S] (the reference's tri_feat layout)."""
+    S = planes.shape[1]
+    return planes.permute(0, 3, 1, 2).reshape(1, 96, S, S).contiguous()
+
+
+def fit_triplanes(decoder: MultiTriplane, points: torch.Tensor, occupancies: torch.Tensor, init: torch.Tensor,
+                  epochs: int = 20, batch_size: int = 40000, lr: float = 1e-3, generator: Optional[torch.Generator] = None,
+                  batch_fn=None):
+    """The optimisation loop of train_triplane_opt (drag_utils.py:521-539) from `init` ([1,96,S,S], un-normalised) with
+    the decoder's MLP frozen.  Per epoch one randperm of the points; per batch r = rand*2-1 and the offset noise, all
+    from `generator` (a device torch.Generator).  `batch_fn(step) -> (idx, r, noise)` replaces them (parity runs).
+    Returns (planes [3,S,S,32], losses [steps, 4] = (bce, mse, l2reg, tvreg) per step, on the device).  The host never
+    waits on the device inside the loop."""
+    dev = decoder.device
+    points = torch.as_tensor(points).detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    occupancies = torch.as_tensor(occupancies).detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    n = points.shape[0]
+    assert occupancies.shape[0] == n
+    sched = batch_schedule(n, batch_size)
+    steps = epochs * len(sched)
+    opt = TriplaneAdam(prepare_planes(init.to(dev), None, None), lr=lr)
+    losses = torch.zeros((steps, 4), dtype=torch.float32, device=dev)
+    k = 0
+    for _ in range(epochs):
+        perm = None if batch_fn is not None else torch.randperm(n, generator=generator, device=dev).to(torch.int32)
+        for start, cnt in sched:
+            if batch_fn is not None:
+                idx, r, noise = batch_fn(k)
+            else:
+                idx = perm[start:start + cnt]
+                r = torch.rand((cnt, 3), generator=generator, device=dev) * 2 - 1
+                noise = torch.randn((cnt, 3), generator=generator, device=dev)
+            decoder.fit_loss_grad(opt.planes, points, occupancies, idx, r, noise, dplanes=opt.dplanes, loss_parts=losses[k, 0:2])
+            opt.step(losses[k, 2:4])
+            k += 1
+    return opt.planes, losses
+
+
+def total_loss(losses: torch.Tensor) -> torch.Tensor:
+    """(bce, mse, l2reg, tvreg) rows -> the reference's summed loss per step."""
+    return losses[..., 0] + PAIR_WEIGHT * losses[..., 1] + L2_WEIGHT * losses[..., 2] + TV_WEIGHT * losses[..., 3]
