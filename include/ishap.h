@@ -38,7 +38,9 @@ int ishap_device_status(void);
 int ishap_rendezvous_would_grant(const void* owner, void* stream);
 int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the size of its scratch buffer; 3 since ishap_step_coefs
                             * ends with rng / rng_seed / rng_offset / noise_out; 4 since the batched drag calls (ishap_drag_batch_*,
-                            * ishap_ddpm_step_guided_scales); 5 since ishap_igemm_run / ishap_igemm_reduce */
+                            * ishap_ddpm_step_guided_scales); 5 since ishap_igemm_run / ishap_igemm_reduce; 6 since
+                            * ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7 since
+                            * the mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -370,6 +372,26 @@ int ishap_mesh_points_on_tris(const float* verts, const int* tris, const int* tr
 /* occ[i] = 1 inside / 0 outside */
 int ishap_mesh_occupancy(const float* verts, const int* tris, long long ntris, const float* pts, long long npts,
                          float* occ, void* stream);
+
+/* ------------------------------------------------------------------ mesh metrics (meshProcess.py:7-118)
+ * Replaces the reference's Open3D RaycastingScene / cKDTree queries behind calc_implicit_field, calc_hausdorff, calc_iou,
+ * calc_local_distance and calc_mesh_points_normals.
+ * dist[i] = distance from pts[i] to the nearest triangle (exact fp32 closest point: vertex, edge and face regions), signed
+ * when sdf != 0: negative inside, inside by the +x ray parity of ishap_mesh_occupancy; tri[i] = the nearest triangle, the
+ * lowest index on exact ties (may be null).  Deterministic.  scratch: ishap_mesh_distance_scratch_bytes(ntris) device
+ * bytes (one box per tile of 256 triangles, 32 bytes each); ntris < 2^31. */
+long long ishap_mesh_distance_scratch_bytes(long long ntris);
+int ishap_mesh_distance(const float* verts, const int* tris, long long ntris, const float* pts, long long npts, int sdf,
+                        float* dist, int* tri, void* scratch, long long scratch_bytes, void* stream);
+/* out2[0] = max over a of min_b |a-b|^2, out2[1] = max over b of min_a |a-b|^2 (squared Hausdorff distances, device floats);
+ * nearest: device float[na + nb], left holding the per-point minima (a's first) */
+int ishap_hausdorff(const float* a, long long na, const float* b, long long nb, float* nearest, float* out2, void* stream);
+/* fa, fb: device float[groups * per_group], two fields on the same samples, group-major.  out: device float[2*groups + 2]:
+ * out[g] = |A and B| / |A or B| of group g (inside: value < 0, or value != 0 when `occupancy`; NaN for an empty union),
+ * out[groups + g] = mean of (fb - fa)^2, out[2*groups] / out[2*groups + 1] = their means over the groups.  Fixed summation
+ * order, double accumulators: bitwise repeatable. */
+int ishap_group_field_stats(const float* fa, const float* fb, int groups, long long per_group, int occupancy, float* out,
+                            void* stream);
 
 /* ------------------------------------------------------------------ measurement aid (bench.py roofline leg)
  * Brackets every implicit-GEMM launch with HIP events on its own stream between begin and end.

@@ -472,6 +472,211 @@ __global__ __launch_bounds__(256) void occupancy_kernel(const float* __restrict_
   if (i < np) occ[i] = (crossings & 1u) ? 1.f : 0.f;
 }
 
+// ---- distance from a point to a triangle mesh (meshProcess.py:7-14, 108-118: RaycastingScene.compute_signed_distance /
+//      compute_closest_points in the reference) ------------------------------------------------------------------------
+// Triangles go through LDS in tiles of MD_TILE, one thread owns a point (as occupancy_kernel).  Every tile has an
+// axis-aligned box (mesh_tile_box_kernel).  Before the tile loop a lane bounds its answer from above by the distance to the
+// farthest corner of the nearest box; a workgroup then skips every tile whose box no lane could find a closer triangle in
+// (block-wide vote).  Marching cubes emits triangles in voxel order, so a tile is a compact strip of the surface.
+constexpr int MD_TILE = 256;
+// The box test is a lower bound only up to rounding: a tile is skipped when its fp32 box distance exceeds the fp32 bound
+// by a relative MD_REL plus MD_ABS times the coordinate magnitude (the error of the fp32 closest point is a few ulp of
+// that magnitude).  Any triangle whose computed distance could reach the final minimum is therefore visited, and the
+// outputs are bit for bit those of visiting every tile.
+constexpr float MD_REL = 1e-4f, MD_ABS = 2e-5f;
+
+// box of tile b: {lo.xyz, max |coordinate|}, {hi.xyz, 0}
+__global__ __launch_bounds__(MD_TILE) void mesh_tile_box_kernel(const float* __restrict__ v, const int* __restrict__ t,
+                                                                long long nt, float4* __restrict__ box) {
+  __shared__ float red[6][MD_TILE];
+  const long long f = (long long)blockIdx.x * MD_TILE + threadIdx.x;
+  float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+  if (f < nt) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float* P = v + 3LL * t[3 * f + c];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], P[k]); hi[k] = fmaxf(hi[k], P[k]); }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { red[k][threadIdx.x] = lo[k]; red[3 + k][threadIdx.x] = hi[k]; }
+  __syncthreads();
+  for (int o = MD_TILE / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        red[k][threadIdx.x] = fminf(red[k][threadIdx.x], red[k][threadIdx.x + o]);
+        red[3 + k][threadIdx.x] = fmaxf(red[3 + k][threadIdx.x], red[3 + k][threadIdx.x + o]);
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    float mag = 0.f;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) mag = fmaxf(mag, fabsf(red[k][0]));
+    box[2 * blockIdx.x] = make_float4(red[0][0], red[1][0], red[2][0], mag);
+    box[2 * blockIdx.x + 1] = make_float4(red[3][0], red[4][0], red[5][0], 0.f);
+  }
+}
+
+__device__ __forceinline__ float seg_dist2(float apx, float apy, float apz, float abx, float aby, float abz) {
+  const float l2 = abx * abx + aby * aby + abz * abz;
+  const float s = l2 > 0.f ? fminf(fmaxf((apx * abx + apy * aby + apz * abz) / l2, 0.f), 1.f) : 0.f;
+  const float dx = apx - s * abx, dy = apy - s * aby, dz = apz - s * abz;
+  return dx * dx + dy * dy + dz * dz;
+}
+
+// Squared distance from p to triangle (a, b, c): the closest point by Voronoi region (vertex, edge, face) as in Ericson,
+// Real-Time Collision Detection 5.1.5, written as selections so a wave runs one straight path.  Each region gives the
+// closest point as a + (nv ab + nw ac) / den; the last assignment that holds is Ericson's first matching region.
+__device__ __forceinline__ float tri_dist2(float px, float py, float pz, float4 r0, float4 r1, float4 r2) {
+  const float ax = r0.x, ay = r0.y, az = r0.z, bx = r0.w, by = r1.x, bz = r1.y, cx = r1.z, cy = r1.w, cz = r2.x;
+  const float abx = bx - ax, aby = by - ay, abz = bz - az;
+  const float acx = cx - ax, acy = cy - ay, acz = cz - az;
+  const float apx = px - ax, apy = py - ay, apz = pz - az;
+  const float bpx = px - bx, bpy = py - by, bpz = pz - bz;
+  const float cpx = px - cx, cpy = py - cy, cpz = pz - cz;
+  const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
+  const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
+  const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
+  const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+  float nv = vb, nw = vc, den = va + vb + vc;                                              // face
+  if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) { nv = d5 - d6; nw = d4 - d3; den = nv + nw; }   // edge bc
+  if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { nv = 0.f; nw = d2; den = d2 - d6; }           // edge ac
+  if (d6 >= 0.f && d5 <= d6) { nv = 0.f; nw = 1.f; den = 1.f; }                           // vertex c
+  if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { nv = d1; nw = 0.f; den = d1 - d3; }           // edge ab
+  if (d3 >= 0.f && d4 <= d3) { nv = 1.f; nw = 0.f; den = 1.f; }                           // vertex b
+  if (d1 <= 0.f && d2 <= 0.f) { nv = 0.f; nw = 0.f; den = 1.f; }                          // vertex a
+  const float r = 1.f / den, sv = nv * r, sw = nw * r;
+  const float dx = apx - sv * abx - sw * acx, dy = apy - sv * aby - sw * acy, dz = apz - sv * abz - sw * acz;
+  float dd = dx * dx + dy * dy + dz * dz;
+  if (!(dd <= 3.0e38f)) {    // degenerate triangle (no area: den = 0 in the face region): nearest of its three edges
+    dd = fminf(seg_dist2(apx, apy, apz, abx, aby, abz), seg_dist2(apx, apy, apz, acx, acy, acz));
+    dd = fminf(dd, seg_dist2(bpx, bpy, bpz, cx - bx, cy - by, cz - bz));
+  }
+  return dd;
+}
+
+// d2[i] = min over triangles of the squared distance, tri[i] = its lowest index (tiles and triangles are visited in index
+// order and only a strictly smaller distance replaces the best).  occ (may be null): sign source, dist[i] = -sqrt(d2) where
+// occ[i] != 0; out[i] may alias occ[i] (read before written by the same lane).
+__global__ __launch_bounds__(MD_TILE) void mesh_distance_kernel(const float* __restrict__ v, const int* __restrict__ t,
+                                                                long long nt, const float4* __restrict__ box,
+                                                                const float* __restrict__ pts, long long np, const float* occ,
+                                                                float* out, int* __restrict__ tri_out) {
+  __shared__ float4 tri[MD_TILE][3];
+  const long long i = (long long)blockIdx.x * MD_TILE + threadIdx.x;
+  const bool live = i < np;
+  float px = 0.f, py = 0.f, pz = 0.f;
+  if (live) { px = pts[3 * i]; py = pts[3 * i + 1]; pz = pts[3 * i + 2]; }
+  const float pmag = fmaxf(fabsf(px), fmaxf(fabsf(py), fabsf(pz)));
+  const int ntiles = (int)((nt + MD_TILE - 1) / MD_TILE);
+  // upper bound: every triangle of a tile lies in its box, so none is farther than the box's farthest corner
+  float bound = 3.0e38f;
+  for (int b = 0; b < ntiles; ++b) {
+    const float4 lo = box[2 * b], hi = box[2 * b + 1];
+    const float fx = fmaxf(fabsf(px - lo.x), fabsf(hi.x - px)), fy = fmaxf(fabsf(py - lo.y), fabsf(hi.y - py));
+    const float fz = fmaxf(fabsf(pz - lo.z), fabsf(hi.z - pz));
+    bound = fminf(bound, fx * fx + fy * fy + fz * fz);
+  }
+  float best = 3.4e38f;
+  int best_f = -1;
+  for (int b = 0; b < ntiles; ++b) {
+    const float4 lo = box[2 * b], hi = box[2 * b + 1];
+    const float gx = fmaxf(fmaxf(lo.x - px, px - hi.x), 0.f), gy = fmaxf(fmaxf(lo.y - py, py - hi.y), 0.f);
+    const float gz = fmaxf(fmaxf(lo.z - pz, pz - hi.z), 0.f);
+    const float lim = sqrtf(fminf(bound, best)) * (1.f + MD_REL) + MD_ABS * (pmag + lo.w);
+    const bool need = live && gx * gx + gy * gy + gz * gz <= lim * lim;
+    if (!__syncthreads_or(need)) continue;          // also the barrier before the tile is restaged
+    const long long f0 = (long long)b * MD_TILE;
+    const int m = (int)min((long long)MD_TILE, nt - f0);
+    if ((int)threadIdx.x < m) {
+      const long long f = f0 + threadIdx.x;
+      const float* A = v + 3LL * t[3 * f];
+      const float* B = v + 3LL * t[3 * f + 1];
+      const float* Cv = v + 3LL * t[3 * f + 2];
+      tri[threadIdx.x][0] = make_float4(A[0], A[1], A[2], B[0]);
+      tri[threadIdx.x][1] = make_float4(B[1], B[2], Cv[0], Cv[1]);
+      tri[threadIdx.x][2] = make_float4(Cv[2], 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    if (need) {
+      for (int k = 0; k < m; ++k) {
+        const float dd = tri_dist2(px, py, pz, tri[k][0], tri[k][1], tri[k][2]);
+        if (dd < best) { best = dd; best_f = (int)(f0 + k); }
+      }
+    }
+  }
+  if (!live) return;
+  const float d = sqrtf(best);
+  float s = d;
+  if (occ) s = occ[i] != 0.f ? -d : d;
+  out[i] = s;
+  if (tri_out) tri_out[i] = best_f;
+}
+
+// out[0] = max of x[0, na), out[1] = max of x[na, na + nb) (one workgroup; the maximum does not depend on the order)
+__global__ __launch_bounds__(1024) void max2_kernel(const float* __restrict__ x, long long na, long long nb, float* __restrict__ out) {
+  __shared__ float red[1024];
+  for (int h = 0; h < 2; ++h) {
+    const float* y = h ? x + na : x;
+    const long long n = h ? nb : na;
+    float m = -3.4e38f;
+    for (long long k = threadIdx.x; k < n; k += 1024) m = fmaxf(m, y[k]);
+    __syncthreads();
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+      if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) out[h] = red[0];
+  }
+}
+
+// Per group g of P values of two fields on the same sample positions: out[g] = |A and B| / |A or B| (inside: field < 0, or
+// field != 0 when `occupancy`), out[G + g] = mean of (b - a)^2.  One workgroup per group, fixed summation order, double
+// accumulators; the counts are exact.  An empty union gives 0/0 = NaN (the reference's division).
+__global__ __launch_bounds__(256) void group_stats_kernel(const float* __restrict__ fa, const float* __restrict__ fb, long long P,
+                                                          int G, int occupancy, float* __restrict__ out) {
+  __shared__ double red[3][256];
+  const long long g = blockIdx.x;
+  const float* a = fa + g * P;
+  const float* b = fb + g * P;
+  const long long per = (P + 255) / 256;
+  const long long k0 = threadIdx.x * per, k1 = min(P, k0 + per);
+  double inter = 0.0, uni = 0.0, sq = 0.0;
+  for (long long k = k0; k < k1; ++k) {
+    const float x = a[k], y = b[k];
+    const bool ia = occupancy ? x != 0.f : x < 0.f, ib = occupancy ? y != 0.f : y < 0.f;
+    inter += (ia && ib) ? 1.0 : 0.0;
+    uni += (ia || ib) ? 1.0 : 0.0;
+    const double e = (double)y - (double)x;
+    sq += e * e;
+  }
+  red[0][threadIdx.x] = inter; red[1][threadIdx.x] = uni; red[2][threadIdx.x] = sq;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o)
+      for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[g] = (float)(red[0][0] / red[1][0]);
+    out[G + g] = (float)(red[2][0] / (double)P);
+  }
+}
+// out[2G] = mean over groups of out[0, G), out[2G + 1] = mean of out[G, 2G) (in group order)
+__global__ void group_mean_kernel(int G, float* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  double s0 = 0.0, s1 = 0.0;
+  for (int g = 0; g < G; ++g) { s0 += (double)out[g]; s1 += (double)out[G + g]; }
+  out[2 * G] = (float)(s0 / G);
+  out[2 * G + 1] = (float)(s1 / G);
+}
+
 int fill(SurfArgs& a, const float* volume, int res, float level, void* scratch, unsigned* counts) {
   ISHAP_REQUIRE(volume && scratch && res >= 2 && res <= 1024, "surface: volume, scratch and 2 <= res <= 1024");
   a.vol = volume; a.res = res; a.level = level; a.n = (long long)res * res * res;
@@ -607,6 +812,49 @@ extern "C" int ishap_mesh_occupancy(const float* verts, const int* tris, long lo
   ISHAP_REQUIRE(verts && tris && pts && occ && ntris > 0 && npts > 0, "mesh_occupancy arguments");
   hipLaunchKernelGGL(occupancy_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, (hipStream_t)stream, verts, tris, ntris, pts,
                      npts, occ);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" long long ishap_mesh_distance_scratch_bytes(long long ntris) {
+  if (ntris < 0) return -1;
+  return (ntris + MD_TILE - 1) / MD_TILE * 2 * (long long)sizeof(float4);
+}
+
+extern "C" int ishap_mesh_distance(const float* verts, const int* tris, long long ntris, const float* pts, long long npts, int sdf,
+                                   float* dist, int* tri, void* scratch, long long scratch_bytes, void* stream) {
+  ISHAP_REQUIRE(verts && tris && pts && dist && scratch && ntris > 0 && npts > 0, "mesh_distance arguments");
+  ISHAP_REQUIRE(scratch_bytes >= ishap_mesh_distance_scratch_bytes(ntris),
+                "mesh_distance: scratch smaller than ishap_mesh_distance_scratch_bytes(ntris)");
+  ISHAP_REQUIRE(ntris < (1ll << 31), "mesh_distance: triangle indices must fit 31 bits");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned tiles = (unsigned)((ntris + MD_TILE - 1) / MD_TILE), blocks = (unsigned)((npts + MD_TILE - 1) / MD_TILE);
+  float4* box = (float4*)scratch;
+  // the sign is ishap_mesh_occupancy's: its 0/1 result lands in dist and the distance kernel reads it back per point
+  if (sdf) hipLaunchKernelGGL(occupancy_kernel, dim3(blocks), dim3(256), 0, s, verts, tris, ntris, pts, npts, dist);
+  hipLaunchKernelGGL(mesh_tile_box_kernel, dim3(tiles), dim3(MD_TILE), 0, s, verts, tris, ntris, box);
+  hipLaunchKernelGGL(mesh_distance_kernel, dim3(blocks), dim3(MD_TILE), 0, s, verts, tris, ntris, (const float4*)box, pts, npts,
+                     sdf ? (const float*)dist : nullptr, dist, tri);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int ishap_hausdorff(const float* a, long long na, const float* b, long long nb, float* nearest, float* out2, void* stream) {
+  ISHAP_REQUIRE(a && b && nearest && out2 && na > 0 && nb > 0, "hausdorff arguments");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(nearest_sq_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, a, na, b, nb, nearest);
+  hipLaunchKernelGGL(nearest_sq_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, b, nb, a, na, nearest + na);
+  hipLaunchKernelGGL(max2_kernel, dim3(1), dim3(1024), 0, s, nearest, na, nb, out2);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int ishap_group_field_stats(const float* fa, const float* fb, int groups, long long per_group, int occupancy, float* out,
+                                       void* stream) {
+  ISHAP_REQUIRE(fa && fb && out && groups > 0 && per_group > 0, "group_field_stats arguments");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(group_stats_kernel, dim3((unsigned)groups), dim3(256), 0, s, fa, fb, per_group, groups, occupancy ? 1 : 0, out);
+  hipLaunchKernelGGL(group_mean_kernel, dim3(1), dim3(64), 0, s, groups, out);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }
