@@ -40,7 +40,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * ends with rng / rng_seed / rng_offset / noise_out; 4 since the batched drag calls (ishap_drag_batch_*,
                             * ishap_ddpm_step_guided_scales); 5 since ishap_igemm_run / ishap_igemm_reduce; 6 since
                             * ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7 since
-                            * the mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats) */
+                            * the mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats); 8 since
+                            * ishap_arap / ishap_arap_scratch_bytes / ishap_nearest_vertices */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -392,6 +393,25 @@ int ishap_hausdorff(const float* a, long long na, const float* b, long long nb, 
  * order, double accumulators: bitwise repeatable. */
 int ishap_group_field_stats(const float* fa, const float* fb, int groups, long long per_group, int occupancy, float* out,
                             void* stream);
+
+/* ------------------------------------------------------------------ ARAP deformation (meshProcess.py:222-236)
+ * Replaces the reference's Open3D deform_as_rigid_as_possible: Sorkine & Alexa 2007, spokes energy, cotangent weights
+ * w_ij = max(0, 1/2 sum cot) (triangles in ascending index), all arithmetic in fp64.  Device pointers throughout.
+ * rest: float[nverts*3]; tris: int[ntris*3]; cons_ids: int[ncons], distinct, in [0, nverts); cons_pos: float[ncons*3].
+ * out: float[nverts*3] (not aliasing rest): constrained vertices at their targets, vertices whose component of the w > 0
+ * graph holds no constraint at rest (bit for bit), the free rest after max_iter alternations of the local rotation fit
+ * and the global solve L_ff x_f = b_f - L_fc x_c (Jacobi-preconditioned CG on three columns, warm-started; a column stops
+ * when |r| <= tol max(|rhs|, 1e-300) or after max_cg iterations, max_cg <= 0: 4 free vertices + 100).
+ * energy: double[max_iter], E_k = sum_i sum_j w_ij |e'_ij - R_i e_ij|^2 at the rotations of step k and p'^(k-1);
+ * cg_iters: int[max_iter], the CG iterations of step k, negated when max_cg ended the solve before every column met tol.
+ * Triangle and constraint ids are checked on the device before use (an error names the fault).  Synchronises the stream
+ * during setup and once per 32 CG iterations.  Bitwise repeatable.  scratch: ishap_arap_scratch_bytes device bytes. */
+long long ishap_arap_scratch_bytes(long long nverts, long long ntris, long long ncons);
+int ishap_arap(const float* rest, long long nverts, const int* tris, long long ntris, const int* cons_ids, const float* cons_pos,
+               long long ncons, int max_iter, double tol, long long max_cg, float* out, double* energy, int* cg_iters,
+               void* scratch, long long scratch_bytes, void* stream);
+/* idx[i] = the vertex nearest to pts[i] (squared distance in fp64), the lowest index on ties (main.py:525-527's pick) */
+int ishap_nearest_vertices(const float* verts, long long nverts, const float* pts, long long npts, int* idx, void* stream);
 
 /* ------------------------------------------------------------------ measurement aid (bench.py roofline leg)
  * Brackets every implicit-GEMM launch with HIP events on its own stream between begin and end.

@@ -140,6 +140,10 @@ SYMBOLS = {
                                       c_void_p, C.c_longlong, c_void_p]),
     "ishap_hausdorff": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, c_void_p]),
     "ishap_group_field_stats": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_longlong, C.c_int, c_void_p, c_void_p]),
+    "ishap_arap_scratch_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_longlong]),
+    "ishap_arap": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_double,
+                             C.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
+    "ishap_nearest_vertices": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p]),
     "ishap_profile_begin": (C.c_int, []),
     "ishap_profile_end": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
     "ishap_profile_shapes": (C.c_int, [C.c_char_p, C.c_int]),
@@ -174,9 +178,10 @@ def lib():
             fn.restype = res
             fn.argtypes = args
         # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run;
-        # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats
-        if l.ishap_version() < 7:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 7): rebuild with `python -m ishapediting_amd.build`")
+        # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats;
+        # 8: ishap_arap / ishap_nearest_vertices
+        if l.ishap_version() < 8:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 8): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 
