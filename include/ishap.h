@@ -41,7 +41,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * ishap_ddpm_step_guided_scales); 5 since ishap_igemm_run / ishap_igemm_reduce; 6 since
                             * ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7 since
                             * the mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats); 8 since
-                            * ishap_arap / ishap_arap_scratch_bytes / ishap_nearest_vertices */
+                            * ishap_arap / ishap_arap_scratch_bytes / ishap_nearest_vertices; 9 since ishap_attention_run /
+                            * ishap_attention8_run */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -468,6 +469,48 @@ int ishap_igemm_run(const ishap_igemm_desc* d, int launch, void* stream, int* ks
  * consumer that cannot add slices up runs first (slab_materialize, csrc/unet.hip).  Reads M, N, H, W, ldo, ldr and those
  * buffers, checked as above; launch = 0: the checks only. */
 int ishap_igemm_reduce(const ishap_igemm_desc* d, int nslab, int launch, void* stream);
+
+/* One attention launch as a UNet AttentionBlock makes it (csrc/attention.hip), for testing a kernel form in isolation.
+ * QKVAttentionLegacy per (image, head): a = softmax(q k^T / sqrt(d)) v, head h at qkv channels [h*3d, (h+1)*3d) as q | k | v.
+ *   pass 0 (forward):  qkv -> out (a) and lse (log-sum-exp of each query's scores);
+ *   pass 1 (backward): qkv, out, lse and dout (the gradient of a) -> dqkv.
+ * T a multiple of 64, d = 32 or 64, C = heads * d.  The kernel form follows from the shape as in the product.  Every buffer is
+ * checked against its size in bytes and its alignment (qkv, and in the backward out and dout, 16 bytes; out in the forward
+ * and dqkv 8; lse 4) before any HIP call: a failed check returns -2 with a message. */
+typedef struct {
+  int pass;                        /* 0: forward, 1: backward */
+  int N, T, C, heads, d;
+  int xcd_map;                     /* -1: the product's setting (ISHAP_ATTN_XCD), 0: plain grid, 1: XCD-aware grid */
+  ishap_buf qkv;                   /* fp16 [N][T][3C] */
+  ishap_buf out;                   /* fp16 [N][T][C]: written by the forward, read by the backward */
+  ishap_buf lse;                   /* fp32 [N * heads][T]: written by the forward, read by the backward */
+  ishap_buf dout;                  /* fp16 [N][T][C], backward only */
+  ishap_buf dqkv;                  /* fp16 [N][T][3C], backward only */
+} ishap_attention_desc;
+/* Checks `d` and writes the kernel instance (e.g. "attn_fwd_kernel<64,4>", "attn_bwd_kernel<32,2>/512" with its thread
+ * count); with launch != 0 then enqueues it on `stream`.  launch = 0: no HIP call at all. */
+int ishap_attention_run(const ishap_attention_desc* d, int launch, void* stream, char* kernel, int kernel_cap);
+
+/* The 8x8-map AttentionBlock body (attn8_fused_kernel): qkv = xn Wqkv^T + bqkv, the attention of every head (d = 64, T = 64
+ * tokens), and proj_out's K slice of each head, slices[h] = a_h Wproj[:, h*64 .. h*64+63]^T in fp32.  C = 64 * heads <= 1152,
+ * and N * heads * 12 workgroups must fit on the device's compute units at once. */
+typedef struct {
+  int N, C, heads;
+  ishap_buf xn;                    /* fp16 [N][64][C] */
+  ishap_buf wqkv;                  /* fp16 [3C][C] */
+  ishap_buf bqkv;                  /* fp32 [3C] */
+  ishap_buf wproj;                 /* fp16 [C][C] */
+  ishap_buf qkv;                   /* fp16 [N][64][3C], out */
+  ishap_buf aout;                  /* fp16 [N][64][C], out */
+  ishap_buf lse;                   /* fp32 [N][heads][64], out */
+  ishap_buf slices;                /* fp32 [heads][N * 64][C], out */
+  ishap_buf flags;                 /* uint32 [N][heads][16]: scratch, zeroed by the call */
+} ishap_attention8_desc;
+/* Checks `d` (launch = 0 stops there).  Otherwise fails on a pending device-side failure, zeroes the flags and enqueues the
+ * block on `stream`: with one_launch != 0 as ONE launch whose workgroups wait for each other, if the device's rendezvous
+ * tenancy is granted (*granted_out = 1), else as two launches of the same kernel (bitwise the same values).  A wait that gave
+ * up is reported by the status check at the end of the call, or by the next call. */
+int ishap_attention8_run(const ishap_attention8_desc* d, int one_launch, int launch, void* stream, int* granted_out);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,16 @@ class IgemmDescC(C.Structure):
                 [("gb_emb_ld", C.c_int), ("gb_film", C.c_int), ("gb_act", C.c_int)])
 
 
+class AttnDescC(C.Structure):
+    _fields_ = ([(f, C.c_int) for f in ("pass_", "N", "T", "C", "heads", "d", "xcd_map")] +
+                [(f, IgemmBufC) for f in ("qkv", "out", "lse", "dout", "dqkv")])
+
+
+class Attn8DescC(C.Structure):
+    _fields_ = ([(f, C.c_int) for f in ("N", "C", "heads")] +
+                [(f, IgemmBufC) for f in ("xn", "wqkv", "bqkv", "wproj", "qkv", "aout", "lse", "slices", "flags")])
+
+
 class DecoderWeightsC(C.Structure):
     _fields_ = [("B", c_void_p), ("W1", c_void_p), ("b1", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
                 ("w3", c_void_p), ("b3", c_void_p)]
@@ -150,6 +160,8 @@ SYMBOLS = {
     "ishap_igemm_plan": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "ishap_igemm_run": (C.c_int, [C.POINTER(IgemmDescC), C.c_int, c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "ishap_igemm_reduce": (C.c_int, [C.POINTER(IgemmDescC), C.c_int, C.c_int, c_void_p]),
+    "ishap_attention_run": (C.c_int, [C.POINTER(AttnDescC), C.c_int, c_void_p, C.c_char_p, C.c_int]),
+    "ishap_attention8_run": (C.c_int, [C.POINTER(Attn8DescC), C.c_int, C.c_int, c_void_p, C.POINTER(C.c_int)]),
     "ishap_triplane_decode_grid": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_int,
                                              c_void_p, c_void_p]),
 }
@@ -179,9 +191,9 @@ def lib():
             fn.argtypes = args
         # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run;
         # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats;
-        # 8: ishap_arap / ishap_nearest_vertices
-        if l.ishap_version() < 8:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 8): rebuild with `python -m ishapediting_amd.build`")
+        # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run
+        if l.ishap_version() < 9:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 9): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

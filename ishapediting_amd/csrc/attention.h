@@ -10,8 +10,14 @@ struct AttnArgs {
   float* Dbuf = nullptr;         // backward scratch [N*heads][T]
   int N = 1, T = 0, C = 0, heads = 0, d = 0;
   float alpha = 1.f;             // 1/sqrt(d)  (= s*s with s = d^-1/4, unet.py:348-351)
-  int xcd_map = 1;               // XCD-aware workgroup -> (tile, head) mapping (attention.hip: attn_xcd_item); set by the launchers
+  int xcd_map = 1;               // XCD-aware workgroup -> (tile, head) mapping (attention.hip: attn_xcd_item), 0 or 1; the product
+                                 // passes attn_xcd_setting()
 };
+int attn_xcd_setting();          // ISHAP_ATTN_XCD (default 1), read once per process
+int attn_check(const AttnArgs& a);   // the shape contract both launchers require (no HIP call)
+// the kernel instance a launch of `a` runs, e.g. "attn_fwd_kernel<64,4>" / "attn_bwd_kernel<32,2>/512" (threads); no HIP call
+std::string attn_forward_form(const AttnArgs& a);
+std::string attn_backward_form(const AttnArgs& a);
 int attn_forward_launch(const AttnArgs& a, hipStream_t s);
 int attn_backward_launch(const AttnArgs& a, hipStream_t s);
 

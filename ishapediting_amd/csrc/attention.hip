@@ -1,5 +1,6 @@
 // Fused attention for the UNet's AttentionBlocks (reference: guided_diffusion/unet.py:337-354, QKVAttentionLegacy:
-// per head  w = softmax_fp32((q*s)^T (k*s)), s = d^-1/4;  a = w v;  tokens T <= 1024, head width d = 64).
+// per head  w = softmax_fp32((q*s)^T (k*s)), s = d^-1/4;  a = w v;  tokens T any multiple of 64 (the product's largest map
+// has 1024; tests/test_gpu_attention_oracle.py runs up to 2048), head width d = 64 or 32).
 // Forward and backward are flash-style: the T x T score matrix never leaves the CU.
 //   forward : one workgroup = 64 queries of one (image, head); online softmax over 64-key tiles; writes a and
 //             lse = m + log(sum) per query.
@@ -14,6 +15,8 @@
 // index (V, K, Q, dA as "transposed" A operands) are read from the row-major LDS tiles with ds_read_b64_tr_b16.
 // qkv layout (legacy order): token row of 3C halfs, head h at [h*3d, (h+1)*3d): q | k | v.
 #include "attention.h"
+#include <cstring>
+#include "../../include/ishap.h"
 
 __device__ __forceinline__ half8 ld_frag(const half_t* tile, int stride, int i0, int k0, int lane) {
   return *reinterpret_cast<const half8*>(tile + (i0 + (lane & 15)) * stride + k0 + 8 * (lane >> 4));
@@ -458,24 +461,35 @@ __global__ __launch_bounds__(256 * TEAMS) void attn_bwd_kernel(const void* h_qkv
   else attn_bwd_dkv_body<D, TEAMS>(a, n, tile, h, team, s0 + team * 64 * RS, s1 + team * 64 * RS, sD + team * 128, mrg);
 }
 
-static int check_attn(const AttnArgs& a) {
+int attn_check(const AttnArgs& a) {
   ISHAP_REQUIRE(a.T % 64 == 0 && a.T >= 64, "attention: tokens must be a multiple of 64");
-  ISHAP_REQUIRE(a.C == a.heads * a.d && (a.d == 64 || a.d == 32), "attention: head width 64 or 32");
+  ISHAP_REQUIRE(a.d == 64 || a.d == 32, "attention: head width 64 or 32");
+  ISHAP_REQUIRE(a.heads >= 1 && a.heads < 65536 && a.C == a.heads * a.d, "attention: channels C = heads * head width");
+  ISHAP_REQUIRE(a.N >= 1 && a.N < 32768, "attention: images");
+  ISHAP_REQUIRE((long long)(a.T / 64) * a.heads * a.N * 2 < (1ll << 31), "attention: work items (tiles * heads * images * 2) < 2^31");
+  ISHAP_REQUIRE(a.xcd_map == 0 || a.xcd_map == 1, "attention: xcd_map 0 or 1");
   return 0;
 }
 
 // teams of the forward launch: four once a team of two would walk >= 4 key tiles (T = 1024: 13.5 -> 12.5 us, round 3)
 static int attn_fwd_teams(int ntile) { return ntile >= 8 ? 4 : 2; }
+// threads of the backward launch: two teams, but one tile is launched with one team (a second would have nothing to do)
+static int attn_bwd_threads(int T) { return T > 64 ? 512 : 256; }
 
-static int attn_xcd_on() {
-  static const int on = [] { const char* e = getenv("ISHAP_ATTN_XCD"); return e ? atoi(e) : 1; }();
+int attn_xcd_setting() {
+  static const int on = [] { const char* e = getenv("ISHAP_ATTN_XCD"); return e ? (atoi(e) != 0 ? 1 : 0) : 1; }();
   return on;
 }
 
-int attn_forward_launch(const AttnArgs& a_in, hipStream_t s) {
-  AttnArgs a = a_in;
-  a.xcd_map = attn_xcd_on();
-  ISHAP_TRY(check_attn(a));
+std::string attn_forward_form(const AttnArgs& a) {
+  return "attn_fwd_kernel<" + std::to_string(a.d) + "," + std::to_string(attn_fwd_teams(a.T / 64)) + ">";
+}
+std::string attn_backward_form(const AttnArgs& a) {
+  return "attn_bwd_kernel<" + std::to_string(a.d) + ",2>/" + std::to_string(attn_bwd_threads(a.T));
+}
+
+int attn_forward_launch(const AttnArgs& a, hipStream_t s) {
+  ISHAP_TRY(attn_check(a));
   dim3 g(a.T / 64, a.heads, a.N);
   const int ntile = a.T / 64;
   const bool four = attn_fwd_teams(ntile) == 4;
@@ -493,12 +507,9 @@ int attn_forward_launch(const AttnArgs& a_in, hipStream_t s) {
   return 0;
 }
 
-int attn_backward_launch(const AttnArgs& a_in, hipStream_t s) {
-  AttnArgs a = a_in;
-  a.xcd_map = attn_xcd_on();
-  ISHAP_TRY(check_attn(a));
+int attn_backward_launch(const AttnArgs& a, hipStream_t s) {
+  ISHAP_TRY(attn_check(a));
   dim3 g(a.T / 64, a.heads, a.N * 2);
-  // one tile: a second team would have nothing to do
 #define ATTN_BWD(Dv, TM, THREADS)                                                                                              \
   do {                                                                                                                         \
     auto kern = attn_bwd_kernel<Dv, TM>;                                                                                       \
@@ -507,8 +518,8 @@ int attn_backward_launch(const AttnArgs& a_in, hipStream_t s) {
     hipLaunchKernelGGL(kern, g, dim3(THREADS), smem, s, (const void*)a.qkv, (const void*)a.out, (const void*)a.dout,           \
                        (void*)a.dqkv, a.lse, a.Dbuf, a.T, a.C, a);                                                             \
   } while (0)
-  if (a.d == 64) ATTN_BWD(64, 2, a.T > 64 ? 512 : 256);
-  else ATTN_BWD(32, 2, a.T > 64 ? 512 : 256);
+  if (a.d == 64) ATTN_BWD(64, 2, attn_bwd_threads(a.T));
+  else ATTN_BWD(32, 2, attn_bwd_threads(a.T));
 #undef ATTN_BWD
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
@@ -524,7 +535,10 @@ int attn_backward_launch(const AttnArgs& a_in, hipStream_t s) {
 //   2. waits for the 12 flags of its head (bounded spin: a give-up raises the status word and poisons the outputs), reads the
 //      head's q | k | v (24 KB) with agent-scope loads -- MI355X_MICROARCH.md hand-off table, first row: every store and every
 //      load of the handed-off bytes is sc1, the flag follows the storing waves' vmcnt(0) -- and computes the head's attention
-//      exactly as attn_fwd_kernel does (S^T = K Q^T, per-lane softmax state, O^T = V^T P^T through the transposed LDS read);
+//      with attn_fwd_kernel's arithmetic (S^T = K Q^T, per-lane softmax state, O^T = V^T P^T through the transposed LDS read):
+//      lse is bitwise attn_fwd_kernel's; a may differ by one fp16 ulp in rare elements, because the compiler fuses a's
+//      fp16(o * (1/sum)) into one multiply-and-convert here and rounds twice (fp32, then fp16) there
+//      (tests/test_gpu_attention_oracle.py);
 //      every part does this redundantly (2 x 0.5 MFLOP): it is cheaper than a second exchange;
 //   3. its share of proj_out's K slice of this head: out_h[64][n] = a_h[64][64] Wproj[n][h*64 ..]^T for its 16-channel tiles
 //      (64 tiles of C = 1024 dealt over the 12 parts), fp32, into slices[h]: the consumer adds the 16 slices up.
@@ -778,5 +792,88 @@ int attn8_fused_launch(const Attn8Args& a, hipStream_t s, bool one_launch) {
   }
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+// ---- one launch through the C ABI (include/ishap.h, ishap_attention_run / ishap_attention8_run): the arguments the product
+// builds (attn_forward / attn_backward in unet.hip / backward.hip), every buffer checked against the caller's byte size first ----
+
+static bool attn_buf_fits(const ishap_buf& b, long long bytes, int align) {
+  return b.ptr && b.bytes >= bytes && ((unsigned long long)b.ptr % (unsigned)align) == 0;
+}
+#define ATTN_BUF(buf, need, align)                                                                                        \
+  ISHAP_REQUIRE(attn_buf_fits(d->buf, (need), (align)), std::string("buffer " #buf ": needs ") + std::to_string((long long)(need)) + \
+                " bytes at " #align "-byte alignment, has " + std::to_string(d->buf.bytes))
+
+extern "C" int ishap_attention_run(const ishap_attention_desc* d, int launch, void* stream, char* kernel, int kernel_cap) {
+  ISHAP_REQUIRE(d != nullptr, "descriptor");
+  ISHAP_REQUIRE(d->pass == 0 || d->pass == 1, "pass: 0 forward, 1 backward");
+  ISHAP_REQUIRE(d->xcd_map >= -1 && d->xcd_map <= 1, "xcd_map: -1 (the product's setting), 0 or 1");
+  AttnArgs a;
+  a.N = d->N; a.T = d->T; a.C = d->C; a.heads = d->heads; a.d = d->d;
+  a.alpha = d->d > 0 ? 1.f / sqrtf((float)d->d) : 0.f;
+  a.xcd_map = d->xcd_map < 0 ? attn_xcd_setting() : d->xcd_map;
+  ISHAP_TRY(attn_check(a));
+  const long long rows = (long long)a.N * a.T;
+  ATTN_BUF(qkv, rows * 3 * a.C * 2, 16);
+  ATTN_BUF(lse, (long long)a.N * a.heads * a.T * 4, 4);
+  if (d->pass == 0) {
+    ATTN_BUF(out, rows * a.C * 2, 8);
+  } else {
+    ATTN_BUF(out, rows * a.C * 2, 16);
+    ATTN_BUF(dout, rows * a.C * 2, 16);
+    ATTN_BUF(dqkv, rows * 3 * a.C * 2, 8);
+  }
+  a.qkv = (const half_t*)d->qkv.ptr; a.out = (half_t*)d->out.ptr; a.lse = (float*)d->lse.ptr;
+  if (d->pass == 1) { a.dout = (const half_t*)d->dout.ptr; a.dqkv = (half_t*)d->dqkv.ptr; }
+  const std::string name = d->pass == 0 ? attn_forward_form(a) : attn_backward_form(a);
+  if (kernel) {
+    ISHAP_REQUIRE((int)name.size() < kernel_cap, "kernel: name buffer too small");
+    memcpy(kernel, name.c_str(), name.size() + 1);
+  }
+  if (!launch) return 0;
+  return d->pass == 0 ? attn_forward_launch(a, (hipStream_t)stream) : attn_backward_launch(a, (hipStream_t)stream);
+}
+
+// attn8_fused_launch's shape and co-residency contract, with a message per condition
+static int attn8_check(const Attn8Args& a) {
+  ISHAP_REQUIRE(a.N >= 1 && a.N < 65536, "attn8: images");
+  ISHAP_REQUIRE(a.heads >= 1 && a.heads * 64 == a.C, "attn8: head width 64 (C = 64 * heads)");
+  ISHAP_REQUIRE(a.C / 16 <= 6 * A8_PARTS, "attn8: C <= 1152 (at most 6 proj_out tiles a part)");
+  ISHAP_REQUIRE(a.N * a.heads * A8_PARTS <= ishap_cu_count(), "attn8: co-resident workgroups (N * heads * 12 <= compute units)");
+  return 0;
+}
+
+extern "C" int ishap_attention8_run(const ishap_attention8_desc* d, int one_launch, int launch, void* stream, int* granted_out) {
+  ISHAP_REQUIRE(d != nullptr, "descriptor");
+  if (granted_out) *granted_out = 0;
+  Attn8Args a;
+  a.N = d->N; a.C = d->C; a.heads = d->heads; a.alpha = 1.f / sqrtf(64.f);
+  ISHAP_TRY(attn8_check(a));
+  const long long rows = (long long)a.N * 64, C = a.C;
+  ATTN_BUF(xn, rows * C * 2, 16);
+  ATTN_BUF(wqkv, 3 * C * C * 2, 16);
+  ATTN_BUF(bqkv, 3 * C * 4, 16);
+  ATTN_BUF(wproj, C * C * 2, 16);
+  ATTN_BUF(qkv, rows * 3 * C * 2, 8);
+  ATTN_BUF(aout, rows * C * 2, 8);
+  ATTN_BUF(lse, (long long)a.N * a.heads * 64 * 4, 4);
+  ATTN_BUF(slices, (long long)a.heads * rows * C * 4, 16);
+  ATTN_BUF(flags, (long long)a.N * a.heads * 16 * 4, 4);
+  if (!launch) return 0;
+  ISHAP_TRY(ishap_check_status());          // an earlier launch's device-side failure surfaces here
+  hipStream_t s = (hipStream_t)stream;
+  a.xn = (const half_t*)d->xn.ptr; a.wqkv = (const half_t*)d->wqkv.ptr; a.bqkv = (const float*)d->bqkv.ptr;
+  a.wproj = (const half_t*)d->wproj.ptr; a.qkv = (half_t*)d->qkv.ptr; a.aout = (half_t*)d->aout.ptr; a.lse = (float*)d->lse.ptr;
+  a.slices = (float*)d->slices.ptr; a.flags = (unsigned*)d->flags.ptr;
+  a.status = ishap_status_word();
+  ISHAP_REQUIRE(a.status != nullptr, "device status word");
+  ISHAP_CHECK_HIP(hipMemsetAsync(a.flags, 0, (size_t)a.N * a.heads * 16 * 4, s));
+  // the one-launch form needs the device's rendezvous tenancy, as ishap_group_norm32's route 3 does
+  const bool granted = one_launch && ishap_rendezvous_begin(nullptr, s);
+  const int r = attn8_fused_launch(a, s, granted);
+  ishap_rendezvous_end(nullptr, s, granted);
+  if (granted_out) *granted_out = granted ? 1 : 0;
+  ISHAP_TRY(r);
+  return ishap_check_status();
 }
 

@@ -126,7 +126,7 @@ static int attn_backward(Exec& e, AttnL& L, const Tensor& dy, Tensor& dx) {
   } else {
     AttnArgs g;
     g.qkv = sv.qkv.p; g.out = sv.a.p; g.dout = dA.p; g.dqkv = dqkv.p; g.lse = sv.lse; g.Dbuf = u->attn_D;
-    g.N = N; g.T = T; g.C = C; g.heads = heads; g.d = d; g.alpha = alpha;
+    g.N = N; g.T = T; g.C = C; g.heads = heads; g.d = d; g.alpha = alpha; g.xcd_map = attn_xcd_setting();
     ISHAP_TRY(attn_backward_launch(g, e.s));
   }
   Tensor dn;

@@ -507,6 +507,7 @@ static int attn_forward(Exec& e, AttnL& L, Tensor x, Tensor& y) {
     AttnArgs g;
     g.qkv = qkv.p; g.out = a.p; g.lse = lse; g.N = N; g.T = T; g.C = C; g.heads = heads; g.d = d;
     g.alpha = 1.f / sqrtf((float)d);
+    g.xcd_map = attn_xcd_setting();
     ISHAP_TRY(attn_forward_launch(g, e.s));
   }
   y = x;
@@ -784,12 +785,13 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 8; }   // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 9; }   // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
                                         // 7: mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats)
                                         // 8: ARAP deformation (ishap_arap, ishap_arap_scratch_bytes, ishap_nearest_vertices)
+                                        // 9: one attention launch through the ABI (ishap_attention_run, ishap_attention8_run)
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");
