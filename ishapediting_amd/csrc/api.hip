@@ -9,6 +9,8 @@ static thread_local std::string g_err;
 void ishap_set_error(const std::string& msg) { g_err = msg; }
 
 #include <atomic>
+#include <cstdio>
+#include <cstring>
 #include <mutex>
 static std::atomic<unsigned*> g_status{nullptr};
 static std::mutex g_status_mu;
@@ -68,11 +70,41 @@ struct Tenant {
 Tenant g_tenant[64];
 }  // namespace
 
+// ---- the runtime switches: every environment variable the library reads (the Python package reads three more of its own:
+//      ISHAP_FUSED_UPDATE, ISHAP_OVERLAP_TAIL, ISHAP_STEP_RNG) ----
+static const struct { const char* name; int dflt; const char* meaning; } kSwitches[] = {
+    {"ISHAP_IGEMM4", 2, "3x3 convolutions on igemm4: 0 = never, 1 = its 128x128 tiles only, 2 = every shape it takes"},
+    {"ISHAP_IG4_TEAMS", 2, "igemm4 forms: 2 = two-team and 128x64 tiles, 1 = 128x64 tiles only, 0 = neither"},
+    {"ISHAP_IG4_HALO", 1, "0 = no igemm4 halo tiles"},
+    {"ISHAP_HALVES", 2, "2 = igemm2's two-team form"},
+    {"ISHAP_SKINNY", 1, "0 = the tiled kernel + reduce instead of the skinny kernel"},
+    {"ISHAP_G1_SLICES", 1, "0 = no sliced 1x1 GEMMs on the 8x8 maps"},
+    {"ISHAP_BIG_MIN", 192, "128x128 workgroups from which the 128-tile is taken"},
+    {"ISHAP_IG4_NOUTER", 2, "igemm4 tile order within an XCD: 0 = n-tiles fastest, 1 = m-tiles fastest, 2 = by estimated L2 traffic"},
+    {"ISHAP_GN_PARTS", 8, "most workgroups per (image, group) of the group-local GroupNorm kernels"},
+    {"ISHAP_GN_SPIN_LIMIT", 0, "polls before a rendezvous (group-local GroupNorm, fused 8x8 attention) gives up; <= 0 = the built-in limit"},
+    {"ISHAP_GN_XCD", 1, "group-local GroupNorm: 0 = no XCD-local dealing, 1 = dealing + local record copy, 2 = also pre-touch the copy"},
+    {"ISHAP_TAIL_MID", -1, "backward blocks before a deferred forward tail starts: k > 0 = after k, 0 = at the fork, < 0 = first map <= 16x16"},
+    {"ISHAP_LOCAL_GN", 1, "0 = the two-pass GroupNorm route on the small maps too"},
+    {"ISHAP_TAIL_DEFER_WGS", 128, "most tiles per launch of the overlapped forward tail's 3x3 convolutions"},
+    {"ISHAP_BWD_MARKS", 0, "non-zero = a context records the backward pass's per-block events (read when the context is created)"},
+    {"ISHAP_ATTN_XCD", 1, "0 = no XCD-local placement of an attention head's workgroups (any non-zero value = 1)"},
+    {"ISHAP_ATTN8", 1, "0 = no fused attention kernel on the 8x8 maps"},
+    {"ISHAP_EVENT_FENCE", 0, "non-zero = the library's ordering events keep the default system-scope fence"},
+};
+int ishap_switch(const char* name, int fallback) {
+  for (const auto& s : kSwitches)
+    if (!strcmp(s.name, name) && s.dflt == fallback) {
+      const char* e = getenv(name);
+      return e ? atoi(e) : fallback;
+    }
+  fprintf(stderr, "ishap_switch: %s (default %d) is not a row of kSwitches\n", name, fallback);
+  abort();
+}
+
 unsigned ishap_event_flags() {
-  static const unsigned f = [] {
-    const char* e = getenv("ISHAP_EVENT_FENCE");
-    return (e && atoi(e)) ? (unsigned)hipEventDisableTiming : (unsigned)(hipEventDisableTiming | hipEventDisableSystemFence);
-  }();
+  static const unsigned f = ishap_switch("ISHAP_EVENT_FENCE", 0) ? (unsigned)hipEventDisableTiming
+                                                                 : (unsigned)(hipEventDisableTiming | hipEventDisableSystemFence);
   return f;
 }
 

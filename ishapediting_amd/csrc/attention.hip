@@ -477,7 +477,7 @@ static int attn_fwd_teams(int ntile) { return ntile >= 8 ? 4 : 2; }
 static int attn_bwd_threads(int T) { return T > 64 ? 512 : 256; }
 
 int attn_xcd_setting() {
-  static const int on = [] { const char* e = getenv("ISHAP_ATTN_XCD"); return e ? (atoi(e) != 0 ? 1 : 0) : 1; }();
+  static const int on = ishap_switch("ISHAP_ATTN_XCD", 1) != 0 ? 1 : 0;
   return on;
 }
 
@@ -556,10 +556,7 @@ __device__ __forceinline__ void st8_agent(half_t* p, half4 v) {
   __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-#ifndef A8_NW
-#define A8_NW 4          // waves per workgroup: 4 / 8 / 16 -> 14.2 / 15.4 / 27 us per launch (C = 1024)
-#endif
-constexpr int A8_WAVES = A8_NW;
+constexpr int A8_WAVES = 4;      // waves per workgroup: 4 / 8 / 16 -> 14.2 / 15.4 / 27 us per launch (C = 1024)
 constexpr int A8_SMEM = (A8_WAVES * 4 * 64 * 16 > 64 * (72 + 80 + 72) * 2 ? A8_WAVES * 4 * 64 * 16 : 64 * (72 + 80 + 72) * 2) + 16;
 constexpr int A8_WAVES_UNUSED = 0;     // phase 1: one 64-deep K-step per wave at C = 1024, every fragment load of the workgroup in flight at once
 __global__ __launch_bounds__(A8_WAVES * 64) void attn8_fused_kernel(Attn8Args a) {
@@ -767,7 +764,7 @@ __global__ __launch_bounds__(A8_WAVES * 64) void attn8_fused_kernel(Attn8Args a)
 }
 
 bool attn8_applicable(int N, int T, int C, int d) {
-  static const int on = [] { const char* e = getenv("ISHAP_ATTN8"); return e ? atoi(e) : 1; }();      // -1.0 % per edit (profiles/round5_ab_attn8_fused.txt)
+  static const int on = ishap_switch("ISHAP_ATTN8", 1);      // -1.0 % per edit (profiles/round5_ab_attn8_fused.txt)
   return on && T == 64 && d == 64 && C % 64 == 0 && C / 16 <= 6 * A8_PARTS && N * (C / 64) * A8_PARTS <= ishap_cu_count();
 }
 
@@ -777,7 +774,7 @@ int attn8_fused_launch(const Attn8Args& a, hipStream_t s, bool one_launch) {
   ISHAP_TRY(ishap_set_max_lds((const void*)attn8_fused_kernel, A8_SMEM));
   Attn8Args b = a;
   // polls before the wait for the head's other parts gives up (ISHAP_GN_SPIN_LIMIT: the test hook of the GroupNorm rendezvous)
-  static const int spin = [] { const char* e = getenv("ISHAP_GN_SPIN_LIMIT"); const int n = e ? atoi(e) : 0; return n > 0 ? n : (1 << 22); }();
+  static const int spin = [] { const int n = ishap_switch("ISHAP_GN_SPIN_LIMIT", 0); return n > 0 ? n : (1 << 22); }();
   b.spin_limit = spin;
   if (one_launch) {
     b.phases = 3;

@@ -46,6 +46,10 @@ enum { ISHAP_DEV_OK = 0, ISHAP_DEV_GN_RENDEZVOUS = 1, ISHAP_DEV_CHAIN_TIMEOUT = 
 // nothing on the host reads memory behind these events, and the default fence is a cache write-back + invalidate in front of
 // whatever the stream runs next (hip_runtime_api.h, hipEventDisableSystemFence).  ISHAP_EVENT_FENCE=1 restores the default.
 unsigned ishap_event_flags();
+// A runtime switch of the library: atoi of the environment variable `name`, `fallback` where it is not set.  Every name the
+// library listens to is a row of ONE table (api.hip, kSwitches: name, default, meaning); a name that is not in it, or a
+// fallback that is not the table's default, aborts.  Reads the environment at every call: callers keep the value in a static.
+int ishap_switch(const char* name, int fallback);
 unsigned* ishap_status_word();        // null only if the pinned allocation failed
 int ishap_check_status();             // 0, or -3 with the error string set (the word is cleared once reported)
 int ishap_cu_count();                 // compute units of the current device (cached per device)
@@ -86,20 +90,12 @@ static inline int ishap_set_max_lds(const void* kern, int bytes) {
   return 0;
 }
 
-// 16-byte output store of a streaming kernel's result.  ISHAP_WT_STORES=1 (compile time): write-through (`sc1`), so that the bytes
-// leave for memory while the kernel runs instead of sitting dirty in the XCD's L2 until the end-of-kernel write-back (a
-// dependent boundary costs + B / 6 TB/s behind B dirty bytes, MI355X_MICROARCH.md price list, row `boundary`; the next kernel
-// reads them from the memory side either way: its L2 starts invalidated).
-#ifndef ISHAP_WT_STORES
-#define ISHAP_WT_STORES 0
-#endif
+// 16-byte output store of a streaming kernel's result.  A plain store: the write-through (`sc1`) form, which lets the bytes
+// leave for memory while the kernel runs instead of sitting dirty in the XCD's L2 until the end-of-kernel write-back, was
+// measured and not kept (profiles/round5_ab_write_through_stores.txt).
 #if defined(__HIPCC__)
 __device__ __forceinline__ void store_out16(half_t* p, const half8& v) {
-#if ISHAP_WT_STORES
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#else
   *reinterpret_cast<half8*>(p) = v;
-#endif
 }
 #endif
 
@@ -309,7 +305,7 @@ struct IgemmPlan {
   IgemmForm form;
   bool big;        // 128-row tiles of the generic families (ig2_128, ig4_128): the shape profile's `tile` column
 };
-// the selection switches, read once from the environment (defaults in brackets; DESIGN.md lists them)
+// the selection switches, read once from the environment (defaults in brackets; the table of all switches: api.hip, kSwitches)
 struct IgemmSwitches {
   int igemm4;      // ISHAP_IGEMM4 [2]: 0 = never igemm4, 1 = its 128x128 tiles only, 2 = every shape it takes
   int ig4_teams;   // ISHAP_IG4_TEAMS [2]: 2 = two-team and 128x64 tiles, 1 = 128x64 tiles only, 0 = neither

@@ -80,9 +80,6 @@ __device__ __forceinline__ void drag_motion_body(const DragArgs& a, int blk, int
     int xcur = 0, ycur = 0;
     bool open = false;
     auto flush_col = [&](int x, float v0, float v1) {
-#ifdef DRAG_ABL_NOATOM      // timing ablation (tools/build_variant.sh): the scatter's atomics left out -- wrong gradients
-      if (v0 != 12345.f) return;
-#endif
       if (!live || x < 0 || x >= a.W) return;
       if (ycur >= 0 && ycur < a.W) fx_add(a.gfx + ((long long)ycur * a.W + x) * a.ld + ch, v0, DRAG_FX_SCALE);
       if (ycur + 1 >= 0 && ycur + 1 < a.W) fx_add(a.gfx + ((long long)(ycur + 1) * a.W + x) * a.ld + ch, v1, DRAG_FX_SCALE);
@@ -316,9 +313,9 @@ int drag_setup_launch(const DragArgs& a, hipStream_t s) {
 }
 
 // every workgroup of these passes ends with same-address atomics (loss sum, max|g|) that serialise at ~10 ns each:
-// few, fat workgroups (the loops are grid-stride).  Measured: tools/experiments/drag_probe.sh.
+// few, fat workgroups (the loops are grid-stride).
 static int drag_terms_launch(const DragArgs& a, unsigned* bits, hipStream_t s) {
-  constexpr int cap = 1024;          // swept in round 2 (tools/experiments/drag_probe.sh)
+  constexpr int cap = 1024;          // swept in round 2; no result file was kept, and the library no longer reads the cap from the environment: not repeatable as is
   const int side = 2 * a.r + 1;
   const int nrows = 3 * a.B * side * ((a.Cc + 63) / 64) * ((side + DSEG - 1) / DSEG);
   hipLaunchKernelGGL(drag_terms_kernel, dim3(min(ceil_div(nrows * 64, 256), cap)), dim3(256), 0, s, a, bits);

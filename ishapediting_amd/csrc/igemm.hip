@@ -323,9 +323,9 @@ extern "C" int ishap_profile_shapes(char* buf, int cap) {
 // ---- the launch plan: K slices and kernel form of every implicit-GEMM launch (no HIP runtime call) ----
 const IgemmSwitches& igemm_switches() {
   static const IgemmSwitches sw = [] {
-    auto env = [](const char* k, int dflt) { const char* e = getenv(k); return e ? atoi(e) : dflt; };
-    return IgemmSwitches{env("ISHAP_IGEMM4", 2), env("ISHAP_IG4_TEAMS", 2), env("ISHAP_IG4_HALO", 1), env("ISHAP_HALVES", 2),
-                         env("ISHAP_SKINNY", 1), env("ISHAP_G1_SLICES", 1), env("ISHAP_BIG_MIN", 192)};
+    return IgemmSwitches{ishap_switch("ISHAP_IGEMM4", 2), ishap_switch("ISHAP_IG4_TEAMS", 2), ishap_switch("ISHAP_IG4_HALO", 1),
+                         ishap_switch("ISHAP_HALVES", 2), ishap_switch("ISHAP_SKINNY", 1), ishap_switch("ISHAP_G1_SLICES", 1),
+                         ishap_switch("ISHAP_BIG_MIN", 192)};
   }();
   return sw;
 }
@@ -343,7 +343,7 @@ int igemm_plan_ksplit(const IgemmArgs& a, bool pending, const IgemmSwitches& sw)
   const int bm = big ? 128 : 64, bn = big ? 128 : 64;
   const long long blocks = (long long)(a.M / bm) * ceil_div(a.N, bn) * a.nbatch;
   const int ks = a.K / 64;
-  // policy constants, each swept in situ (tools/experiments/sweep_split_policy.sh, profiles/round4_env_ab_pending_split.txt,
+  // policy constants, each swept in situ (profiles/round4_env_ab_pending_split.txt,
   // profiles/round5_ab_policy_resweep.txt: all flat within +-0.5 % around these values)
   constexpr int nosplit = 36;       // K-steps below which a launch followed by a reduce launch is not split (24 / 48: +0.5 %)
   constexpr int fill = 224;         // split while the grid stays below this many workgroups (plateau 208 .. 256)

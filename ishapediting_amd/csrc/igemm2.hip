@@ -13,21 +13,7 @@ __device__ __attribute__((aligned(128))) half_t g_zero_line[64];   // zero-initi
 
 typedef __attribute__((address_space(3))) void lds_void;
 
-#ifndef IG2_LOADERS
-#define IG2_LOADERS 4          // loader waves per workgroup (4 measured faster than 8)
-#endif
-// L2 prefetch of the weight panel (round 4).  The CUs of an XCD walk K in step, so every ring stage holds lines no CU of
-// the XCD has touched before (this K-step's slab of the weight panel): each stage lands at the latency of an L2 MISS and
-// the K-step takes miss latency / (NST - 1).  MFMA wave 0 (1: the second 64 rows of a 128-row panel) therefore touches one
-// dword of every 128-byte weight line IG2_PF_DIST K-steps ahead of the step being multiplied, by LDS-DMA into a 256-byte
-// scratch (no register to keep alive, no effect on the loader waves' vmcnt counting): by the time the loaders stage that
-// step its lines are L2 hits.  IG2_PF_SHARE: the m-tiles of an XCD that share a panel take turns (step % sharers).
-#ifndef IG2_PF_DIST
-#define IG2_PF_DIST 0
-#endif
-#ifndef IG2_PF_SHARE
-#define IG2_PF_SHARE 0
-#endif
+constexpr int IG2_LOADERS = 4; // loader waves per workgroup (4 measured faster than 8)
 
 // HALVES = 2: the workgroup is two such 8-wave teams, each with its own ring, working on the two halves of the K range
 // and meeting once in LDS at the end -- split-K by two without partial tiles in HBM or a reduce launch.  It gives a CU
@@ -67,7 +53,6 @@ __global__ __launch_bounds__((256 + 64 * IG2_LOADERS) * HALVES) void igemm2_kern
   // linear id so that one XCD gets a contiguous run of tiles (n fastest, then m): neighbouring image rows, whose 3x3
   // halos overlap, and both n-tiles of the same rows then share an L2.  Pure speed: any placement is correct.
   int tile_m, tile_n, tile_z;
-  int pf_turn = 0, pf_mask = 0;          // weight-prefetch duty among the m-tiles of this XCD that share a panel
   {
     // grid extents: from the preloaded arguments when they are powers of two (gridDim.* is a load from the hidden arguments)
     const int nx = h.ny_shift() >= 0 ? (1 << h.nx_shift()) : (int)gridDim.x, ny = h.ny_shift() >= 0 ? (1 << h.ny_shift()) : (int)gridDim.y;
@@ -79,22 +64,13 @@ __global__ __launch_bounds__((256 + 64 * IG2_LOADERS) * HALVES) void igemm2_kern
       tile_n = swz & (ny - 1);
       tile_m = (swz >> h.ny_shift()) & (nx - 1);
       tile_z = swz >> (h.ny_shift() + h.nx_shift());
-      if (IG2_PF_SHARE && r == 0 && (q >> h.ny_shift()) >= 2 && ((q >> h.ny_shift()) & ((q >> h.ny_shift()) - 1)) == 0 &&
-          (q & (ny - 1)) == 0 && (q >> h.ny_shift()) <= nx) {
-        pf_mask = (q >> h.ny_shift()) - 1;       // q tiles per XCD, n fastest: q / ny m-tiles of one z share a weight panel
-        pf_turn = (pos >> h.ny_shift()) & pf_mask;
-      }
     } else {
       tile_n = swz % ny;
       tile_m = (swz / ny) % nx;
       tile_z = swz / (ny * nx);
     }
   }
-#ifdef ABL_SAMEX
-  const int m0 = (tile_m & 1) * BM;      // every block reads the same two pixel tiles (L2-hot probe; wrong results)
-#else
   const int m0 = tile_m * BM;
-#endif
   const int n0 = tile_n * BN;
   const int batch = h.ksplit == 1 ? tile_z : tile_z / h.ksplit;
   const int ks_id = h.ksplit == 1 ? 0 : tile_z % h.ksplit;
@@ -199,24 +175,18 @@ __global__ __launch_bounds__((256 + 64 * IG2_LOADERS) * HALVES) void igemm2_kern
     ++next_ks;
     half_t* sx = lds + slot * STAGE;
     half_t* sw = sx + BM * BK;
-#ifndef ABL_NOLOAD
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
-#ifndef ABL_NOX
       if (i % LSPLIT == lpart)
         __builtin_amdgcn_global_load_lds(xp[i], (lds_void*)(sx + (wave * XI + i) * RPI * BK), 16, 0, 0);
-#endif
       xp[i] += xstep[i];
     }
 #pragma unroll
     for (int i = 0; i < WI; ++i) {
-#ifndef ABL_NOW
       if (i % LSPLIT == lpart)
         __builtin_amdgcn_global_load_lds(wp[i], (lds_void*)(sw + (wave * WI + i) * RPI * BK), 16, 0, 0);
-#endif
       wp[i] += BK;
     }
-#endif
   };
 
   f32x4 acc[NT][MT];
@@ -238,13 +208,7 @@ __global__ __launch_bounds__((256 + 64 * IG2_LOADERS) * HALVES) void igemm2_kern
       if (k < nk) {
         // stage k must have landed: stages up to min(nk, k+NST-1)-1 are issued, (XI+WI) instructions each
         if (k + NST - 1 <= nk) {
-#if defined(ABL_NOX)
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * (WI)) : "memory");
-#elif defined(ABL_NOW)
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * (XI)) : "memory");
-#else
           asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * (XI + WI) / LSPLIT) : "memory");
-#endif
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -257,7 +221,7 @@ __global__ __launch_bounds__((256 + 64 * IG2_LOADERS) * HALVES) void igemm2_kern
     // MFMA waves.  A K-step is two 32-deep halves; the fragments of the second half are read while the MFMAs of the
     // first run, and the first half of step k+1 is read (right after that step's barrier) under the MFMAs of the second
     // half of step k: the matrix pipe never waits for an LDS round trip (the straightforward loop -- read, wait, 16
-    // MFMAs, read, wait ... -- spent 1170 cycles per step on 512 cycles of MFMA work, tools/experiments/fixed_cost_probe2.sh).
+    // MFMAs, read, wait ... -- spent 1170 cycles per step on 512 cycles of MFMA work, round-2 ablation builds of tools/bench_igemm.hip).
     // All fragment reads of step k have returned (lgkmcnt(0)) before this wave enters barrier k+1, after which the
     // loaders may overwrite that ring slot.
     // The reads are inline asm with hand-counted s_waitcnt lgkmcnt: hipcc's own counting falls back to lgkmcnt(0) for
@@ -297,43 +261,22 @@ __global__ __launch_bounds__((256 + 64 * IG2_LOADERS) * HALVES) void igemm2_kern
         asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(xf[0]), "+v"(xf[1]), "+v"(wf[0]), "+v"(wf[1]) : "n"(decltype(pending)::value) : "memory");
     };
     auto mfma_half = [&](half8 (&xf)[MT], half8 (&wf)[NT]) {
-#ifndef ABL_NOMFMA
 #pragma unroll
       for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf[j], acc[i][j], 0, 0, 0);
-#else
-#pragma unroll
-      for (int i = 0; i < NT; ++i) acc[i][0][0] += (float)wf[i][0];
-#pragma unroll
-      for (int j = 0; j < MT; ++j) acc[0][j][1] += (float)xf[j][0];
-#endif
     };
-    // Measured (tools/experiments/fixed_cost_probe2.sh, loads ablated): 0.44 us per 128x128x64 step = 1.23 PFLOP/s chip-wide, the
+    // Measured (round 2, harness build with the loads ablated; profiles/round4_kstep_ablation.txt has the later table): 0.44 us per 128x128x64 step = 1.23 PFLOP/s chip-wide, the
     // rate an MFMA-dense loop on random data sustains at the clock the chip holds under that load (MI355X_MICROARCH.md,
     // DVFS); spreading the reads one per MFMA gap instead of in a burst changed nothing.
     using std::integral_constant;
-#if IG2_PF_DIST > 0
-    __shared__ int pf_scratch[64];
-    const bool pf_wave = wave8 < BN / 64;
-    const half_t* pfp = Wt + (long long)(n0 + wave8 * 64 + lane) * h.ldw + (long long)ks0 * BK;
-    auto pf_issue = [&](int step) {
-      if (((ks0 + step) & pf_mask) == pf_turn)
-        __builtin_amdgcn_global_load_lds(pfp + step * BK, (lds_void*)pf_scratch, 4, 0, 0);
-    };
-    if (pf_wave)
-      for (int s2 = NST - 1; s2 < min(nk, IG2_PF_DIST); ++s2) pf_issue(s2);
-#endif
     __builtin_amdgcn_s_barrier();                // step 0 has landed
     asm volatile("" ::: "memory");
     IG_STAMP(2, wave_all == 0);
     if (nk > 0) read_half(0, 0, xa, wa);
     for (int k = 0; k < nk_loop; ++k) {
       const bool act = k < nk;                   // the shorter half (odd step count) idles through the last barrier
-#if IG2_PF_DIST > 0
-      if (pf_wave && k + IG2_PF_DIST < nk) pf_issue(k + IG2_PF_DIST);
-#endif
       if (act) {
         read_half(k, 1, xb, wb);
         wait_frags(integral_constant<int, MT + NT>{}, xa, wa);
@@ -374,9 +317,6 @@ __global__ __launch_bounds__((256 + 64 * IG2_LOADERS) * HALVES) void igemm2_kern
     }
   }
   IG_STAMP(4, wave_all == 0);
-#ifdef ABL_NOEPI
-  if (a.alpha == 12345.f)                        // harness probe: the launch without its epilogue (never true)
-#endif
   igemm_epilogue<MT, NT, TMW, TNW, BN, (256 + 64 * IG2_LOADERS) * HALVES>(a, acc, m0, n0, wm, wn, lane, batch, ks_id,
                                                                         reinterpret_cast<float*>(smem_raw),
                                                                         !loader && (team == 0 || merge_in_epilogue),
@@ -397,12 +337,7 @@ static int launch2(const IgemmArgs& a, hipStream_t s, std::string* name) {
 
 // main kernel only (the caller adds the split-K reduce)
 int igemm2_launch(const IgemmArgs& a, IgemmForm f, hipStream_t s, std::string* name) {
-#ifndef IG2_BIG_NST
-#define IG2_BIG_NST 4
-#endif
-#ifndef IG2_SMALL_NST
-#define IG2_SMALL_NST 4
-#endif
+  constexpr int IG2_BIG_NST = 4, IG2_SMALL_NST = 4;     // ring depth of the 128- and the 64-tile forms
   switch (f) {
     case IgemmForm::ig2_128: return a.conv3 ? launch2<128, 128, IG2_BIG_NST, true>(a, s, name) : launch2<128, 128, IG2_BIG_NST, false>(a, s, name);
     case IgemmForm::ig2_teams: return launch2<64, 64, 4, true, 2>(a, s, name);

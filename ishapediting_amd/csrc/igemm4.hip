@@ -2,7 +2,7 @@
 // the three horizontal taps of a kernel row.
 //
 // Why: the K loop of the LDS-DMA kernels runs at the rate the CU's load path delivers bytes into LDS, ~36 B/clk per CU
-// whatever the hit rates (tools/experiments/pf_probe.sh, profiles/round4_kstep_ablation.txt: without the activation loads a 64x64-tile
+// whatever the hit rates (profiles/round4_kstep_ablation.txt: without the activation loads a 64x64-tile
 // launch loses 25-37 % of its time, without the weight loads 14-33 %; an L2 prefetch of the weight panel changes nothing) --
 // so the lever is staged bytes per FLOP.  igemm2 stages a BM x 64 activation slab per K-step, i.e. nine times per
 // (pixel, channel); here K runs (chunk, dy, dx) with dx innermost and the slab of (chunk, dy) is staged once and read at
@@ -40,15 +40,9 @@ constexpr int ig4_loads(int a, int b, int wi, int xi) {
   return c;
 }
 
-#ifndef IG4_PRO
-#define IG4_PRO 2              // K-steps issued before the first wait; the ring then fills two steps per iteration
-#endif
+constexpr int IG4_PRO = 2;     // K-steps issued before the first wait; the ring then fills two steps per iteration
 
-#ifdef ABL_NOLOAD             // harness probe: the K loop without its DMA (addresses still computed; wrong results)
-#define IG4_DMA(src, dst) asm volatile("" ::"v"(src), "v"((unsigned)(unsigned long long)(lds_void4*)(dst)))
-#else
 #define IG4_DMA(src, dst) __builtin_amdgcn_global_load_lds((src), (lds_void4*)(dst), 16, 0, 0)
-#endif
 
 // s_waitcnt vmcnt takes an immediate; the loader waves know the count only at run time (block-uniform), hence the switch
 __device__ __forceinline__ void ig4_wait_vm(int n) {
@@ -306,37 +300,6 @@ __global__ __launch_bounds__(512 * HALVES) void igemm4_kernel(const void* hX, co
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         issue3();
-#ifdef ABL_XFORM
-        // HARNESS TIMING PROBE (tools/bench_igemm.hip -DABL_XFORM; wrong results): what a GroupNorm apply + SiLU
-        // of the NEXT activation slab, done in LDS by the loader waves, costs the K loop.  The slab of steps 3(j+1) .. 3(j+1)+2 is
-        // rewritten in two halves, in the iterations of steps 3j+1 and 3j+2 (it has landed once at most the weights of the three
-        // steps issued after it are outstanding); the arithmetic is gn_act.h's sequence with per-lane stand-in parameters
-        if (ph != 0) {
-          if (ph == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * WI) : "memory");
-          const int nslot = (s / 3 + 1) % NSTX;
-          half_t* xs = sX + nslot * XSLOT;
-          const float x_mu = 0.01f * (float)(lane & 7), x_rs = 1.05f, x_g = 0.9f + 1e-3f * (float)lane, x_b = 0.02f;
-#pragma unroll
-          for (int i2 = 0; i2 < (XI + 1) / 2; ++i2) {
-            const int i = (ph - 1) * ((XI + 1) / 2) + i2;
-            if (i < XI) {
-              half8* p = reinterpret_cast<half8*>(xs + (wave * XI + i) * 8 * BK + lane * 8);
-              half8 v = *p;
-#pragma unroll
-              for (int c = 0; c < 8; ++c) {
-                const half_t yh = gn_affine((float)v[c], x_mu, x_rs, x_g, x_b);
-#ifdef ABL_XFORM_FILM
-                const half_t yf = gn_film(yh, (half_t)1.01f, (half_t)0.01f);
-                v[c] = (half_t)gn_silu((float)yf);
-#else
-                v[c] = (half_t)gn_silu((float)yh);
-#endif
-              }
-              *p = v;
-            }
-          }
-        }
-#endif
         ph = ph == 2 ? 0 : ph + 1;
       }
     } else {
@@ -404,18 +367,11 @@ __global__ __launch_bounds__(512 * HALVES) void igemm4_kernel(const void* hX, co
         asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(xf[0]), "+v"(xf[1]), "+v"(wf[0]), "+v"(wf[1]) : "n"(decltype(pending)::value) : "memory");
     };
     auto mfma_half = [&](half8 (&xf)[MT], half8 (&wf)[NT]) {
-#ifndef ABL_NOMFMA
 #pragma unroll
       for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf[j], acc[i][j], 0, 0, 0);
-#else
-#pragma unroll
-      for (int i = 0; i < NT; ++i) acc[i][0][0] += (float)wf[i][0];
-#pragma unroll
-      for (int j = 0; j < MT; ++j) acc[0][j][1] += (float)xf[j][0];
-#endif
     };
     // MFMAs of one 32-deep half with the fragment reads of the NEXT half in their gaps (one read behind each of the first MT + NT
     // MFMAs, pinned by scheduling barriers): issued in a burst the eight reads and their address adds kept the MFMA pipe idle for
@@ -810,7 +766,7 @@ static int launch4(const IgemmArgs& a, hipStream_t s, std::string* name) {
   // (m-tile, K slice); neighbouring m-tiles share their halo rows inside one L2.  ISHAP_IG4_NOUTER=0 / 1 forces an order.
   int n_outer = 0;
   if (remap) {
-    static const int force = [] { const char* e = getenv("ISHAP_IG4_NOUTER"); return e ? atoi(e) : 2; }();
+    static const int force = ishap_switch("ISHAP_IG4_NOUTER", 2);
     const int nx = (int)grid.x, ny = (int)grid.y, nz = (int)grid.z;
     const int q = (nwg + 7) / 8;
     const double wp = (double)BN * (a.K / (double)nz) * 2.0;                 // one weight panel of one slice
@@ -835,25 +791,15 @@ static int launch4(const IgemmArgs& a, hipStream_t s, std::string* name) {
   return igemm_dma_launch(kern, grid, grid, dim3(512 * HALVES), smem, s, a, k2_chunks, order_bit);
 }
 
-#ifndef IG4_BIG_W
-#define IG4_BIG_W 5
-#define IG4_BIG_X 3
-#endif
-#ifndef IG4_SMALL_W
-#define IG4_SMALL_W 6
-#define IG4_SMALL_X 3
-#endif
-#ifndef IG4_W8_W               // the 8x8 maps' sliced launches: 9-18 K-steps per workgroup -- a 4-slot weight ring (3 steps in flight) lets
-#define IG4_W8_W 4             // a 9-step slice take the loader's compile-time path and beats the 6-slot one by 4-6 % per launch
-#define IG4_W8_X 3             // (profiles/round4_igemm4_w8_ring_probe.txt); the 4-slot ring of ig4_64_ring4 as well
-#endif
-#ifndef IG4_TEAM_W
-#define IG4_TEAM_W 6
-#define IG4_TEAM_X 3
-#endif
-#ifndef IG4_HALO_W
-#define IG4_HALO_W 6
-#endif
+// ring depths (weight slots, activation slab slots) of the forms
+constexpr int IG4_BIG_W = 5, IG4_BIG_X = 3;
+constexpr int IG4_SMALL_W = 6, IG4_SMALL_X = 3;
+// the 8x8 maps' sliced launches: 9-18 K-steps per workgroup -- a 4-slot weight ring (3 steps in flight) lets
+// a 9-step slice take the loader's compile-time path and beats the 6-slot one by 4-6 % per launch
+// (profiles/round4_igemm4_w8_ring_probe.txt); the 4-slot ring of ig4_64_ring4 as well
+constexpr int IG4_W8_W = 4, IG4_W8_X = 3;
+constexpr int IG4_TEAM_W = 6, IG4_TEAM_X = 3;
+constexpr int IG4_HALO_W = 6;
 // main kernel only (the caller adds the split-K reduce); the planner sends only the map widths a form takes.  The instances are
 // named in the order the code object lays their kernels out: a new order moves the PC-relative data offsets inside every kernel
 int igemm4_launch(const IgemmArgs& a, IgemmForm f, hipStream_t s, std::string* name) {

@@ -7,32 +7,14 @@
 #include "common.h"
 #include "gn_bwd_terms.h"
 #include "gn_act.h"
+#include "stamps.h"
 #include <type_traits>
-
-// Diagnostic build only (tools/bench_igemm.hip -DIG_STAMPS): s_memtime stamps of one wave per workgroup into a buffer of
-// their own (cdna_hip_programming.md 7, In-kernel stamps).  In the library the macro expands to nothing.
-#ifdef IG_STAMPS
-extern __device__ unsigned long long* g_ig_stamps;      // [workgroup][16]
-#define IG_STAMP(slot, cond)                                                                                   \
-  do {                                                                                                         \
-    if (cond) {                                                                                                \
-      unsigned long long t_;                                                                                   \
-      __builtin_amdgcn_sched_barrier(0);                                                                       \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                              \
-      __builtin_amdgcn_sched_barrier(0);                                                                       \
-      if ((threadIdx.x & 63) == 0)                                                                             \
-        g_ig_stamps[(size_t)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 16 + (slot)] = t_; \
-    }                                                                                                          \
-  } while (0)
-#else
-#define IG_STAMP(slot, cond) do {} while (0)
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // Staged epilogue of the LDS-DMA kernels (round 3).  The round-2 form did everything on the four MFMA waves in the
 // fragment layout: scale / bias / residual / convert / statistics for MT x NT tiles of 4 values each, ~60 instructions
 // per tile behind run-time selects, then row sums by DPP chains -- 10 300 cycles of a 128x128-tile launch and 4 400 of a
-// 64x64 one (s_memtime stamps, tools/bench_igemm.hip -DIG_STAMPS), on one wave per SIMD while the loader waves idled.
+// 64x64 one (s_memtime stamps, tools/bench_igemm.hip -DISHAP_STAMPS), on one wave per SIMD while the loader waves idled.
 // Now the MFMA waves only park their raw fp32 accumulators in LDS (the ring is dead by then), and EVERY wave of the
 // workgroup -- loaders and the second team included -- finishes the tile row-wise: a thread owns one 8-channel chunk of a
 // few rows, so bias / FiLM-free epilogue operands are loaded once per thread, the residual and the output are whole
@@ -160,9 +142,6 @@ __device__ __forceinline__ void igemm_epilogue_staged(const IgemmArgs& a, f32x4 
       half8 o;
 #pragma unroll
       for (int c = 0; c < 4; ++c) { o[c] = (half_t)v0[c]; o[4 + c] = (half_t)v1[c]; }
-#ifdef ABL_EPI_NOSTORE
-      if (alpha == 12345.f)
-#endif
       store_out16(out16 + (long long)(m0 + row) * a.ldo + n, o);
       if (want_fwd) {
         *reinterpret_cast<half8*>(tileH + row * LDH + chunk * 8) = o;    // the statistics pass reads the stored values by column
@@ -217,12 +196,7 @@ __device__ __forceinline__ void igemm_epilogue_staged(const IgemmArgs& a, f32x4 
         }
         const double P = (double)(float)tileH[nl], nn = (double)BM_T;
         const double v = k ? Q + P * (2.0 * S + nn * P) : S + nn * P;
-#ifdef ABL_STAT_COPIES      // harness probe (tools/experiments/stat_probe2.sh): spread the same-address atomics over copies of the table
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.stat_out + (long long)((m0 / BM_T) % ABL_STAT_COPIES) * a.N * 2 +
-                                                        ((long long)n_img * a.N + n0 + nl) * 2 + k),
-#else
         atomicAdd(reinterpret_cast<unsigned long long*>(a.stat_out + ((long long)n_img * a.N + n0 + nl) * 2 + k),
-#endif
                   (unsigned long long)__double2ll_rn(v * (double)(k ? STAT_SCALE_SQ : STAT_SCALE_SUM)));
       }
     }
@@ -257,7 +231,7 @@ __device__ __forceinline__ void igemm_epilogue_staged(const IgemmArgs& a, f32x4 
 // STAGE_THREADS > 0 (the LDS-DMA kernels; = threads of the workgroup, all of which call this function): fp16 outputs
 // of an unsplit launch are collected in LDS and leave as full 16-byte-per-lane row segments written by every wave,
 // loader waves included.  The fragment layout's own stores are 8 bytes per lane over 16 rows: issue-bound, ~9 us of
-// a 128^2-map launch against ~2 us this way (tools/experiments/fixed_cost_probe2.sh).  Values and their order of evaluation are
+// a 128^2-map launch against ~2 us this way (round-2 ablation builds of tools/bench_igemm.hip).  Values and their order of evaluation are
 // unchanged, so results are bit-identical to the direct path.
 // `team2` >= 0 (two-team kernels on the staged path only): this wave belongs to team `team2`, and BOTH teams hold partial
 // accumulators that the staged epilogue adds up (team 0 + team 1) while it finishes the rows -- the separate merge pass
@@ -305,7 +279,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
     for (int c = 0; c < 4; ++c) { ssum[i][c] = 0.f; ssq[i][c] = 0.f; piv[i][c] = 0.f; }
   // One loop over the wave's MT x NT fragment tiles per output mode, the mode tested OUTSIDE the loop: with the tests
   // inside, every tile jumped over the other modes' code and the launch paid an instruction-cache miss per jump
-  // (~4 us of a 128x128-tile launch, tools/experiments/fixed_cost_probe3.sh).
+  // (~4 us of a 128x128-tile launch, round-2 ablation builds of tools/bench_igemm.hip).
   auto col = [&](int i) { return n0 + wn * TNW + i * 16 + (lane >> 4) * 4; };
   auto row = [&](int j) { return m0 + wm * TMW + j * 16 + (lane & 15); };
   if (!active) {
@@ -424,11 +398,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
     for (int c = threadIdx.x; c < BM_T * CPRW; c += STAGE_THREADS) {
       const int row = c / CPRW, ch = c - row * CPRW;
       const int n = n0 + ch * 8;
-#ifdef ABL_EPI_NOSTORE
-      if (n < a.N && alpha == 12345.f)
-#else
       if (n < a.N)
-#endif
         *reinterpret_cast<half8*>(out16 + (long long)(m0 + row) * a.ldo + n) = *reinterpret_cast<const half8*>(tile + row * LDT + ch * 8);
     }
   }
@@ -521,12 +491,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
         }
         const int n_img = m0 / HW;                                        // a tile never straddles images (HW % BM == 0)
         const long long fx = __double2ll_rn(v * (double)((t & 1) ? scale_q : STAT_SCALE_SUM));
-#ifdef ABL_STAT_COPIES      // harness probe: spread the same-address atomics over ABL_STAT_COPIES copies of the table
-        atomicAdd(reinterpret_cast<unsigned long long*>(sdst + (long long)((m0 / BM_T) % ABL_STAT_COPIES) * a.N * 2 +
-                                                        ((long long)n_img * a.N + n0 + nl) * 2 + (t & 1)),
-#else
         atomicAdd(reinterpret_cast<unsigned long long*>(sdst + ((long long)n_img * a.N + n0 + nl) * 2 + (t & 1)),
-#endif
                   (unsigned long long)fx);
       }
     }

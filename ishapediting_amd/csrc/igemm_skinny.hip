@@ -13,9 +13,7 @@
 namespace {
 
 constexpr int SK_WAVES = 16;
-#ifndef SK_DEPTH
-#define SK_DEPTH 3                       // K-steps of fragment loads in flight per wave
-#endif
+constexpr int SK_DEPTH = 3;              // K-steps of fragment loads in flight per wave
 __device__ __attribute__((aligned(128))) half_t g_zero_line_sk[64];   // zero-initialised: what padded taps read
 
 template <int MT, bool CONV3>

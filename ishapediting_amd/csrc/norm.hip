@@ -234,9 +234,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(int h_main_blocks, int h_
     // the old loop).  Measured (profiles/round5_ab_gn_inflight.txt): 8.99 -> 8.64 us (plain + SiLU, 128^2 x 256) and 7.32 -> 6.62
     // (FiLM variant) -- a few per cent, not the 2x a bytes-in-flight limit would have given: the launch is a chain of ~2 us phases
     // (sums -> finalise -> barrier -> loads -> stores), not a stream.
-#ifndef GN_APPLY_U
-#define GN_APPLY_U 4
-#endif
+    constexpr int GN_APPLY_U = 4;
     constexpr int U = SPLIT ? 1 : GN_APPLY_U;      // the head's variant writes three vectors per pixel: batching it doubled its time (8.8 -> 15.8 us)
     for (int pix0 = tg / CV; pix0 < npix; pix0 += U * pstep) {
       half8 v[U];
@@ -285,7 +283,7 @@ int gn_apply_launch(const GnApplyArgs& a, hipStream_t s) {
   const int HWo = a.pool ? (a.H / 2) * (a.W / 2) : a.H * a.W;
   long long total = (long long)a.N * HWo * (a.C / 8);
   int blocks = (int)((total + 255) / 256);
-  constexpr int cap_sums = 1024;          // in-situ sweep (tools/experiments/gn_apply_probe.sh): flat 512 .. 2048
+  constexpr int cap_sums = 1024;          // in-situ sweep, flat 512 .. 2048 (no result file kept; the cap is no longer read from the environment: not repeatable as is)
   if (blocks > (a.sums ? cap_sums : 4096)) blocks = a.sums ? cap_sums : 4096;   // fewer, fatter blocks amortise the finalise prologue
   // thread count = multiple of CV (a thread owns one 8-channel vector): blocks = multiple of CV / gcd(CV, 256)
   const int CV = a.C / 8;

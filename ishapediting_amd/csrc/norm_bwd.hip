@@ -123,10 +123,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const long long* h_cs
   int cur_n = -1;
   // (round 5: the loop can fetch the operands of U pixels before it processes the first -- see gn_apply_kernel, norm.hip; here a
   // pixel already has 2-4 loads in flight and U = 2 was slower)
-#ifndef GN_BWD_U
-#define GN_BWD_U 1      // measured: 2 pixels per batch 8.93 -> 9.47 us (170-188 registers), not kept (profiles/round5_ab_gn_inflight.txt)
-#endif
-  constexpr int U = GN_BWD_U;
+  constexpr int U = 1;    // measured: 2 pixels per batch 8.93 -> 9.47 us (170-188 registers), not kept (profiles/round5_ab_gn_inflight.txt)
   for (int pix0 = tg / CV; pix0 < npix; pix0 += U * pstep) {
     float up[U][8], ad[U][8];
     half8 xv[U], a2[U];

@@ -13,20 +13,7 @@
 #include "norm.h"
 #include "gn_bwd_terms.h"
 #include "gn_act.h"
-
-#ifdef GN_STAMPS          // diagnostic build (tools/experiments/persist_chain.hip -DGN_STAMPS): s_memtime of thread 0 at the phase boundaries
-extern __device__ unsigned long long* g_gn_stamps;      // [workgroup][8]
-#define GN_STAMP(k)                                                                                    \
-  do {                                                                                                 \
-    if (threadIdx.x == 0) {                                                                            \
-      unsigned long long t_;                                                                           \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                      \
-      g_gn_stamps[(size_t)(blockIdx.x + gridDim.x * blockIdx.y) * 8 + (k)] = t_;                       \
-    }                                                                                                  \
-  } while (0)
-#else
-#define GN_STAMP(k) do {} while (0)
-#endif
+#include "stamps.h"
 
 namespace {
 
@@ -188,12 +175,8 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* scratch
 // (~550-900) -- and with the agent-scope store as before.  A poller checks the local copy `GN_LOCAL_POLLS` times per look at the
 // agent-scope copy, so a placement that is NOT co-located (or an L2 that does not show the plain store) costs time, never
 // correctness: the agent-scope path is complete by itself.
-#ifndef GN_XCD_LOCAL
-#define GN_XCD_LOCAL 1
-#endif
-#ifndef GN_LOCAL_POLLS
-#define GN_LOCAL_POLLS 4
-#endif
+constexpr int GN_XCD_LOCAL = 1;
+constexpr int GN_LOCAL_POLLS = 4;
 __device__ __forceinline__ void group_rendezvous(double& a, double& b, unsigned long long* rec, int part, int parts,
                                                  double* scratch, unsigned* status, int spin_limit, bool xcd_local) {
   if (parts <= 1) return;
@@ -319,7 +302,7 @@ __global__ __launch_bounds__(1024) void gn_local_kernel(int h_parts, int h_C, in
     if (c < a.Ca) {
       if (pend) {
         // bias / residual are fetched BEFORE the slices are waited for: one memory round trip instead of three in a row
-        // (the kernel is latency-bound, tools/experiments/persist_chain.hip -DGN_STAMPS)
+        // (the kernel is latency-bound, tools/experiments/persist_chain.hip -DISHAP_STAMPS)
         const bool pre = PF && u == (int)threadIdx.x;                    // requested above
         float bv[VEC], b2v[VEC], r[VEC];
 #pragma unroll
@@ -676,12 +659,12 @@ int pick_threads(int nunits) { return nunits >= 1024 ? 1024 : (nunits <= 256 ? 2
 // workgroups per (image, group): as many as keep the whole grid resident at once (the rendezvous spins) and leave a part
 // at least `min_pixels` pixels made of whole units of `unit` pixels (a row pair when the kernel pools)
 int pick_parts(int N, int HW, int cpg, int unit, bool have_rec) {
-  static const int maxp = [] { const char* e = getenv("ISHAP_GN_PARTS"); return e ? atoi(e) : 8; }();
+  static const int maxp = ishap_switch("ISHAP_GN_PARTS", 8);
   constexpr int min_el = 128;       // elements per part at least (in-situ sweeps below)
   if (!have_rec) return 1;
   // the rendezvous costs ~3 atomic round trips (3-4 us), yet more, smaller parts still win down to a few hundred elements
   // per workgroup (in-situ sweep: 0.2445 / 0.2464 / 0.2500 / 0.2574 s per edit at >= 256 / 1024 / 2048 / 4096 elements;
-  // with the tagged-granule rendezvous, tools/experiments/gn_parts_probe.sh: local-GN kernel time 193 / 198 / 216 / 243 at >= 128 / 256 /
+  // with the tagged-granule rendezvous (round-5 sweep; of its switches only ISHAP_GN_PARTS is still read): local-GN kernel time 193 / 198 / 216 / 243 at >= 128 / 256 /
   // 1024 / 2048 elements, 226 / 271 with at most 4 / 2 parts, 203-214 with up to 16 parts)
   int p = 1;
   // co-residency: a workgroup of these kernels (<= 1024 threads, <= 160 KB of LDS) always fits a compute unit by itself, so
@@ -696,13 +679,13 @@ int pick_parts(int N, int HW, int cpg, int unit, bool have_rec) {
 constexpr size_t LOCAL_LDS_CAP = 160 * 1024 - GN_SCRATCH_BYTES;
 // polls before a rendezvous gives up; ISHAP_GN_SPIN_LIMIT exists so that a test can force the give-up path (1 poll)
 int spin_limit() {
-  static const int v = [] { const char* e = getenv("ISHAP_GN_SPIN_LIMIT"); const int n = e ? atoi(e) : 0; return n > 0 ? n : GN_SPIN_LIMIT; }();
+  static const int v = [] { const int n = ishap_switch("ISHAP_GN_SPIN_LIMIT", 0); return n > 0 ? n : GN_SPIN_LIMIT; }();
   return v;
 }
 
 // the parts of a group on one XCD (group_of_block) and the XCD-local copy of the record: ISHAP_GN_XCD=0 switches both off
 int xcd_deal(int parts) {          // 0: off; 1: XCD-local dealing + local copy; 2: also touch the local copy's lines at kernel start
-  static const int on = [] { const char* e = getenv("ISHAP_GN_XCD"); return e ? atoi(e) : 1; }();      // in situ: 1 and 2 both -0.4 % against 0, no difference between them (profiles/round5_ab_gn_xcd_local.txt)
+  static const int on = ishap_switch("ISHAP_GN_XCD", 1);      // in situ: 1 and 2 both -0.4 % against 0, no difference between them (profiles/round5_ab_gn_xcd_local.txt)
   return parts > 1 ? on : 0;
 }
 

@@ -269,7 +269,7 @@ bool exec_is_solo(const Exec& e) {
 
 bool small_map(int HW) {
   // ISHAP_LOCAL_GN=0: the two-pass GroupNorm route everywhere (A/B); the 64x64 maps group-local as well measured slower (round 5)
-  static const int on = [] { const char* v = getenv("ISHAP_LOCAL_GN"); return v ? atoi(v) : 1; }();
+  static const int on = ishap_switch("ISHAP_LOCAL_GN", 1);
   return on && HW <= 1024;
 }
 bool local_gn(int HW, int C) { return small_map(HW) && gn_local_fits(HW, C); }
@@ -563,7 +563,7 @@ static void tail_exec(Exec& e, ishap_unet* u) {
   // the tail's 3x3 convolutions as launches of at most P tiles: it then holds the LDS of at most P compute units at a time and
   // the backward chain on the caller's stream keeps the rest.  In-situ sweep with the start point (profiles/round5_overlap_tail_ab.txt):
   // 96 / 112 / 128 / 144 / 160 / 192 / 256 tiles -> 0.1706 / 0.1707 / 0.1682 / 0.1707 / 0.1714 / 0.1727 / 0.1785 s per edit
-  static const int wgs = [] { const char* v = getenv("ISHAP_TAIL_DEFER_WGS"); return v ? atoi(v) : 128; }();
+  static const int wgs = ishap_switch("ISHAP_TAIL_DEFER_WGS", 128);
   e.chunk_tiles = wgs;
 }
 
@@ -806,7 +806,7 @@ int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out
   ISHAP_CHECK_HIP(hipSetDevice(device));
   ishap_unet* u = new ishap_unet();
   u->cfg = *cfg;
-  { const char* v = getenv("ISHAP_BWD_MARKS"); u->marks_on = v && atoi(v) != 0; }
+  u->marks_on = ishap_switch("ISHAP_BWD_MARKS", 0) != 0;
   u->device = device;
   int r = unet_build(u);
   if (r) { delete u; return r; }

@@ -252,3 +252,56 @@ def test_philox_restatement_known_answers():
     for ctr, key, want in kat:
         got = philox4x32_10([np.array([v]) for v in ctr], key)
         assert tuple(int(g[0]) for g in got) == want
+
+
+def test_product_sources_hold_no_probe_code_and_tools_set_only_live_switches():
+    """The library's sources are the product only.  (1) Every preprocessor conditional in csrc/ and include/ is an include guard, a
+    test of __HIP_DEVICE_COMPILE__ / __HIPCC__ / __cplusplus, or the one ISHAP_STAMPS switch of csrc/stamps.h: ablations and frozen
+    knobs do not live there (a probe is a patch under tools/experiments/probes/, applied to a copy by tools/build_variant.sh).
+    (2) One file of csrc/ reads the environment: the switch table.  (3) Every ISHAP_* variable a file under tools/ assigns is a
+    row of that table, a switch of the Python package or the bench's own -- a sweep of a variable nobody reads reports "flat"
+    for any value.  Patches the experiments README lists as historical (they apply to older commits) are exempt, by name."""
+    csrc = os.path.join(ROOT, "ishapediting_amd", "csrc")
+    files = [os.path.join(d, f) for d in (csrc, os.path.join(ROOT, "include")) for f in sorted(os.listdir(d))
+             if os.path.isfile(os.path.join(d, f))]
+    assert len(files) > 30
+    bad, stamp_tests, env_readers = [], [], []
+    for path in files:
+        lines = open(path).read().split("\n")
+        if "getenv" in "\n".join(lines) and path.startswith(csrc):
+            env_readers.append(os.path.basename(path))
+        for i, line in enumerate(lines):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            names = set(re.findall(r"[A-Za-z_]\w*", m.group(2).split("//")[0])) - {"defined"}
+            guard = m.group(1) == "ifndef" and len(names) == 1 and re.match(r"\s*#\s*define\s+%s\s*$" % next(iter(names)), lines[i + 1])
+            if names == {"ISHAP_STAMPS"} and os.path.basename(path) == "stamps.h":
+                stamp_tests.append(i)
+            elif not guard and not (len(names) == 1 and names <= {"__HIP_DEVICE_COMPILE__", "__HIPCC__", "__cplusplus"}):
+                bad.append(f"{os.path.relpath(path, ROOT)}:{i + 1}: {line.strip()}")
+    assert not bad, "\n".join(bad)
+    assert len(stamp_tests) == 1
+    assert len(env_readers) == 1, env_readers
+    table_src = open(os.path.join(csrc, env_readers[0])).read()
+    table = set(re.findall(r'^\s*\{"(ISHAP_[A-Z0-9_]+)",\s*-?\d+,\s*"[^"]+"\},?$', table_src, re.M))
+    assert len(table) == 18 and "ISHAP_GN_SPIN_LIMIT" in table, sorted(table)
+    # every name the sources pass to the helper is a row (the helper aborts otherwise; this finds it without running the path)
+    asked = set()
+    for path in files:
+        asked |= set(re.findall(r'ishap_switch\("(\w+)"', open(path).read()))
+    assert asked == table, asked ^ table
+    allowed = table | {"ISHAP_FUSED_UPDATE", "ISHAP_OVERLAP_TAIL", "ISHAP_STEP_RNG", "ISHAP_BENCH_CPU_THREADS"}
+    historical = {"fixup8_conv_splitk_groupnorm.patch", "tiled_weights.patch"}
+    readme = open(os.path.join(ROOT, "tools", "experiments", "README.md")).read()
+    for h in historical:
+        assert re.search(r"%s.*historical" % re.escape(h), readme), f"{h} is not listed as historical in tools/experiments/README.md"
+    dead = []
+    for d, _, fs in os.walk(os.path.join(ROOT, "tools")):
+        for f in fs:
+            if f in historical or f.endswith((".pyc", ".so")):
+                continue
+            for name in re.findall(r"(ISHAP_[A-Z0-9_]+)=", open(os.path.join(d, f), errors="replace").read()):
+                if name not in allowed:
+                    dead.append(f"{os.path.relpath(os.path.join(d, f), ROOT)}: {name}")
+    assert not dead, "\n".join(sorted(set(dead)))

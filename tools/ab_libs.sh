@@ -19,7 +19,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do
   n=$(basename $lib .so)
   cp $R/$lib $R/ishapediting_amd/libishap_hip.so
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$n -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-c2 --no-c4 --no-concurrent > $O/trace_$n.json 2> $O/trace_$n.err || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$n -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-c2 --no-c4 --no-concurrent > $O/trace_$n.json 2> $O/trace_$n.err || exit 1
   f=$(find $O/trace_$n -name "*kernel_trace.csv")
   python3 $R/tools/step_timeline.py $f > $O/step_$n.txt
   rm -rf $O/trace_$n

@@ -1,5 +1,5 @@
 // Standalone timing harness for the LDS-DMA implicit-GEMM kernel (development aid, not part of the library).
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DABL_NOLOAD|-DABL_NOMFMA] tools/bench_igemm.hip -o /tmp/bench_igemm
+// Build: tools/build_variant.sh NAME --harness [--patch tools/experiments/probes/X.patch] [-DISHAP_STAMPS]  -> build/NAME
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -9,11 +9,12 @@
 #include "../ishapediting_amd/csrc/igemm2.hip"
 #include "../ishapediting_amd/csrc/igemm4.hip"
 #include "../ishapediting_amd/csrc/igemm_skinny.hip"
-#ifdef IG_STAMPS
+#ifdef ISHAP_STAMPS
 __device__ unsigned long long* g_ig_stamps;
 #include <algorithm>
 #endif
 void ishap_set_error(const std::string& m) { fprintf(stderr, "ERR %s\n", m.c_str()); }
+int ishap_switch(const char* name, int fallback) { const char* e = getenv(name); return e ? atoi(e) : fallback; }   // the library's: api.hip
 
 __global__ void empty_kernel(int* p) { if (p) *p = 0; }
 // floor of an epilogue: every workgroup writes `per_wg` bytes as 16-byte stores, nothing else
@@ -31,7 +32,7 @@ int main(int argc, char** argv) {
   int nbuf = argc > 9 ? atoi(argv[9]) : 1;       // weight copies cycled through (> 256 MB in total = HBM-cold weights, as in the network)
   int k2 = argc > 10 ? atoi(argv[10]) : 0;       // channels of a folded 1x1 second source (3x3 launches): K = 9 Cin + k2
   int M = H * H, K = ksize * ksize * Cin + k2;
-#ifdef IG_STAMPS
+#ifdef ISHAP_STAMPS
   const int nwg_st = 8192;                         // before ANY launch: the stamped kernels write through this pointer
   unsigned long long* sb; hipMalloc(&sb, (size_t)nwg_st * 16 * 8); hipMemset(sb, 0, (size_t)nwg_st * 16 * 8);
   hipMemcpyToSymbol(HIP_SYMBOL(g_ig_stamps), &sb, sizeof(sb));
@@ -142,7 +143,7 @@ int main(int argc, char** argv) {
       hipFree(buf);
     }
   }
-#ifdef IG_STAMPS
+#ifdef ISHAP_STAMPS
   {
     // in-kernel timeline: per workgroup, s_memtime at fixed points of one wave; median over workgroups of the differences
     const int nwg = nwg_st;

@@ -1,7 +1,7 @@
 // Persistent-kernel prototype for the 8x8 level ("measure, not cite").
 // HISTORICAL (rounds 3-5): form (A) launches csrc/igemm_small3.hip, which round 6 removed from the library together with the other
 // measured-loser kernel families -- this file builds against the round-5 tree (git show 3dbab91:ishapediting_amd/csrc/igemm_small3.hip);
-// its results are in profiles/round3_persistent_chain.txt and the GN_STAMPS table in DESIGN.md.
+// its results are in profiles/round3_persistent_chain.txt and the GN_STAMP table in DESIGN.md.
 //
 // Chain of L layers on a 64-pixel x 1024-channel map at batch 1, each layer = what half a ResBlock of the middle block
 // does (guided_diffusion/unet.py:236-256):   x_l = x_{l-1} + conv3x3( SiLU( GroupNorm32(x_{l-1}) ) ) + bias
@@ -31,7 +31,7 @@ hipEvent_t g_igemm_prof_start = nullptr, g_igemm_prof_stop = nullptr;
 #ifdef C8_STAMPS
 __device__ unsigned long long* g_c8_stamps;
 #endif
-#ifdef GN_STAMPS
+#ifdef ISHAP_STAMPS
 __device__ unsigned long long* g_gn_stamps;
 #endif
 void ishap_set_error(const std::string& m) { fprintf(stderr, "ERR %s\n", m.c_str()); }
@@ -352,13 +352,13 @@ int main(int argc, char** argv) {
     g.gamma = dg; g.beta = db; g.N = 1; g.H = 8; g.W = 8; g.C = C; g.act = 1;
     if (gn_local_launch(g, s)) exit(1);
   };
-#ifdef GN_STAMPS
+#ifdef ISHAP_STAMPS
   unsigned long long* dstg; CK(hipMalloc(&dstg, 512 * 8 * 8)); CK(hipMemset(dstg, 0, 512 * 8 * 8));
   CK(hipMemcpyToSymbol(HIP_SYMBOL(g_gn_stamps), &dstg, sizeof(dstg)));
 #endif
   for (int i = 0; i < 3; ++i) run_launches();
   CK(hipStreamSynchronize(s));
-#ifdef GN_STAMPS
+#ifdef ISHAP_STAMPS
   {
     // the last GroupNorm launch of run_launches is the final materialise (parts = 1); re-run ONE mid-chain GroupNorm for the stamps
     CK(hipMemset(dstg, 0, 512 * 8 * 8));

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 6: row-major [Cout][9 Cin] weight operand vs the tile-packed one (IgemmArgs::w_tiled; csrc/igemm4.hip) in the conv harness,
-# HBM-cold weights (16 rotating copies).  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-result -mllvm
-# -amdgpu-kernarg-preload-count=14 tools/bench_igemm.hip -o build/ig_base.   Harness args: H Cin Cout big ksplit gen ksize stats nbuf k2 tiled
+# HBM-cold weights (16 rotating copies).  HISTORICAL: needs probes/tiled_weights.patch, which applies to the sources of commit dad48f7
+# (in a checkout of that commit: apply the patch, build tools/bench_igemm.hip as build/ig_base).  Harness args: H Cin Cout big ksplit gen ksize stats nbuf k2 tiled
 R=$(cd "$(dirname "$0")/../.." && pwd)
 cd $R
 run() { for t in 0 1; do echo -n "tiled=$t  "; timeout -k 5 60 build/ig_base $@ $t | tail -1; done; }

@@ -19,7 +19,10 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-amdgpu-kernarg-preload-count=14", "--cuda-device-only", "-S"]
+sys.path.insert(0, ROOT)
+from ishapediting_amd.build import FLAGS as BUILD_FLAGS  # noqa: E402  (the product build's flags: the audit reads what ships)
+
+FLAGS = [f for f in BUILD_FLAGS if f != "-fPIC"] + ["--cuda-device-only", "-S"]
 NEAR = 6          # instructions between a load and a vmcnt(0) for the wait to count as "behind the load"
 
 

@@ -9,6 +9,7 @@ LDS-DMA convolution launch got 0.5-1.1 us slower (+3 % per edit, profiles/round6
 anywhere.  tests/test_host_cpu.py holds the hot kernels to zero scratch with this module.
 
     python tools/kernel_meta.py [path/to/libishap_hip.so] [name substring]
+    python tools/kernel_meta.py --diff A.so B.so      # one line per kernel whose code or metadata differs; exit status 1 if any
 """
 import os
 import struct
@@ -73,6 +74,69 @@ def kernels(lib_path: str):
     return out
 
 
+def _functions(elf: bytes):
+    """{symbol: bytes of the function in its section} for every FUNC symbol of the ELF64 image"""
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
+    sec = [struct.unpack_from("<IIQQQQII", elf, shoff + i * shentsize) for i in range(shnum)]   # name, type, flags, addr, off, size, link, info
+    out = {}
+    for _, sh_type, _, _, off, size, link, _ in sec:
+        if sh_type != 2:                 # SHT_SYMTAB
+            continue
+        stroff = sec[link][4]
+        for p in range(off, off + size, 24):
+            st_name, st_info, _, st_shndx, st_value, st_size = struct.unpack_from("<IBBHQQ", elf, p)
+            if st_info & 15 == 2 and 0 < st_shndx < shnum:      # STT_FUNC, defined here
+                name = elf[stroff + st_name:elf.index(b"\0", stroff + st_name)].decode()
+                start = sec[st_shndx][4] + st_value - sec[st_shndx][3]
+                out[name] = elf[start:start + st_size]
+    return out
+
+
+META_KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size",
+             ".kernarg_segment_size", ".max_flat_workgroup_size", ".wavefront_size")
+
+
+def kernel_code(lib_path: str):
+    """{kernel symbol: [(metadata tuple, machine code bytes), ...]}: a list, since two translation units may both hold a
+    kernel of one (internal-linkage) name"""
+    import msgpack
+    out = {}
+    for triple, elf in _code_objects(open(lib_path, "rb").read()):
+        if "gfx950" not in triple:
+            continue
+        fn = _functions(elf)
+        for name, ntype, desc in _notes(elf):
+            if name == "AMDGPU" and ntype == 32:
+                for k in msgpack.unpackb(desc, raw=False, strict_map_key=False).get("amdhsa.kernels", []):
+                    out.setdefault(k[".name"], []).append((tuple(k.get(m, 0) for m in META_KEYS), fn[k[".name"]]))
+    return out
+
+
+def diff(lib_a: str, lib_b: str) -> int:
+    a, b = kernel_code(lib_a), kernel_code(lib_b)
+    dm = demangle(sorted(set(a) | set(b)))
+    bad = 0
+    for n in sorted(set(a) | set(b), key=lambda n: dm[n]):
+        short = dm[n].split("(")[0].replace("void ", "")
+        if n not in a or n not in b:
+            what = f"only in {lib_b if n in b else lib_a}"
+        elif len(a[n]) != len(b[n]):
+            what = f"{len(a[n])} / {len(b[n])} copies"
+        else:
+            what = ", ".join(w for w, i in (("metadata", 0), ("code", 1)) if [x[i] for x in a[n]] != [x[i] for x in b[n]])
+            if "code" in what:
+                what += " (" + " / ".join(f"{len(x[1])} -> {len(y[1])} bytes" for x, y in zip(a[n], b[n]) if x[1] != y[1]) + ")"
+        if what:
+            bad += 1
+            print(f"DIFF {short}: {what}")
+    na, nb = sum(map(len, a.values())), sum(map(len, b.values()))
+    print(f"{na} kernels, {sum(len(c) for v in a.values() for _, c in v)} bytes of kernel code in {lib_a}")
+    print(f"{nb} kernels, {sum(len(c) for v in b.values() for _, c in v)} bytes of kernel code in {lib_b}")
+    print(f"{bad} kernels differ (compared: the bytes of each kernel's function in .text and its metadata entry: {', '.join(m[1:] for m in META_KEYS)})")
+    return 1 if bad else 0
+
+
 def demangle(names):
     import subprocess
     try:
@@ -83,6 +147,8 @@ def demangle(names):
 
 
 def main():
+    if len(sys.argv) == 4 and sys.argv[1] == "--diff":
+        sys.exit(diff(sys.argv[2], sys.argv[3]))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = sys.argv[1] if len(sys.argv) > 1 and os.path.exists(sys.argv[1]) else os.path.join(root, "ishapediting_amd", "libishap_hip.so")
     pat = sys.argv[-1] if len(sys.argv) > 1 and not os.path.exists(sys.argv[-1]) else ""
