@@ -424,15 +424,16 @@ int ishap_profile_end(double* out, int nvar);
 /* Per-shape CSV ("M,N,K,conv3,tile,ksplit,launches,main_ms,reduce_ms,gflop" lines) of the same records; call
  * before the next ishap_profile_begin.  Returns the number of lines, -2 when `cap` is too small. */
 int ishap_profile_shapes(char* buf, int cap);
-/* The kernel choice of one convolution / GEMM launch, on the host, no GPU needed: the K split conv_op picks and what
- * igemm_launch then runs.  M = N*H*W output pixels (per batch entry), cin channels per tap, taps 9 (3x3) or 1, K2 channels of a
+/* The kernel choice of one convolution / GEMM launch, on the host, no GPU needed: the K split every layer launch gets (igemm_fill,
+ * csrc/igemm.hip) and what igemm_launch then runs.  M = N*H*W output pixels (per batch entry), cin channels per tap, taps 9 (3x3) or 1, K2 channels of a
  * folded 1x1 second source, H x W the output map, pending: the consumer adds the K slices up, epilogue_sums: GroupNorm
  * statistics or GroupNorm-backward sums in the epilogue.  Writes the K split, the ishap_profile_end variant and the kernel
  * instance as a kernel trace names it (e.g. "igemm4_kernel<64, 64, 32, 4, 3, 1>").  0, or -2 when `kernel_cap` is too small. */
 int ishap_igemm_plan(int M, int cin, int cout, int taps, int K2, int H, int W, int nbatch, int pending, int epilogue_sums,
                      int* ksplit, int* prof_slot, char* kernel, int kernel_cap);
 
-/* One implicit-GEMM launch as a UNet layer makes it (conv_op, csrc/unet.hip), for testing a kernel form in isolation:
+/* One implicit-GEMM launch as a UNet layer makes it, for testing a kernel form in isolation (the call and the executor's
+ * conv_op, csrc/unet.hip, describe the launch with the same record and fill their kernel arguments with the same function):
  *   out[m][n] = sum_k X(m, k) * Wt[n][k] (+ bias[n]) (+ bias2[n]) (+ res[m or its half-resolution pixel][n]),
  * k = tap * Cin + c over the 3x3 taps (zero padding per image; ups: the source map is (H/2, W/2), upsampled on the fly), then
  * K2 columns of the folded second source X2 against Wt columns [9 Cin, 9 Cin + K2).  The kernel form and the K split follow
@@ -466,7 +467,7 @@ typedef struct {
  * enqueues it on `stream` (the split-K reduce too, unless the slices are left pending).  launch = 0: no HIP call at all. */
 int ishap_igemm_run(const ishap_igemm_desc* d, int launch, void* stream, int* ksplit, char* kernel, int kernel_cap);
 /* The stand-alone reduce of a pending launch's `nslab` slices in d->ws into d->out (+ bias, bias2, res, res_ups): what a
- * consumer that cannot add slices up runs first (slab_materialize, csrc/unet.hip).  Reads M, N, H, W, ldo, ldr and those
+ * consumer that cannot add slices up runs first (slab_materialize, csrc/unet.hip, through the same argument fill).  Reads M, N, H, W, ldo, ldr and those
  * buffers, checked as above; launch = 0: the checks only. */
 int ishap_igemm_reduce(const ishap_igemm_desc* d, int nslab, int launch, void* stream);
 

@@ -33,8 +33,10 @@ static int dgrad_op(Exec& e, const ConvW& c, const Tensor& dy, Tensor& dx_out, i
     gb->sums_ready = 1;
     ISHAP_REQUIRE(gb->C == n_out && gb->gmode == GB_SAME, "fused GroupNorm-backward sums need the gradient at the GN resolution");
   }
-  return conv_op(e, dy.p, dy.N, dy.H, dy.W, dy.C, c.wT, c.cout_pad, c.taps, n_out, nullptr, nullptr, 0, dx_out.p, n_out,
-                 IG_OUT_F16, 0, 0, nullptr, gb, nullptr, 0, 0, nullptr, 0, may_pend ? &dx_out.pend : nullptr);
+  ConvLaunch k = conv_launch(dy, c, dx_out);
+  k.Wt = c.wT; k.kpad = c.cout_pad; k.cout = n_out; k.bias = nullptr;      // the transposed operand: dy's channels are its K
+  k.gb = gb; k.pend_out = may_pend ? &dx_out.pend : nullptr;
+  return conv_op(e, k);
 }
 
 // group-local input gradient of act(film(GN(x))) on a small map; `up` may still be pending (norm_local.hip)
@@ -50,7 +52,29 @@ static int gn_bwd_local_op(Exec& e, const GnBwdArgs& g, Tensor& up) {
   if (e.dry) return 0;
   return gn_bwd_local_launch(a, e.s);
 }
-static bool local_gn_bwd(int HW, int C, int gmode) { return small_map(HW) && gn_bwd_local_fits(HW, C, gmode); }
+static bool local_gn_bwd(const GnBwdArgs& g) { return small_map(g.H * g.W) && gn_bwd_local_fits(g.H * g.W, g.C, g.gmode); }
+
+// The input gradient of a convolution `c` that reads act(film(GN(x))), in two parts; `g` describes the GroupNorm (x, stats,
+// weights, FiLM row, shape, gmode).  The route is a function of g's shape alone, so both parts (and a dry run) take the same one.
+// Dgrad part: dy -> dact, the gradient arriving at the activation.  Group-local route: dact may stay pending (the norm part adds
+// the slices up); else, with the gradient at the GroupNorm's own resolution, the launch gathers the backward sums in its epilogue.
+static int conv_gn_dgrad(Exec& e, const ConvW& c, const Tensor& dy, GnBwdArgs& g, Tensor& dact) {
+  const bool loc = local_gn_bwd(g);
+  return dgrad_op(e, c, dy, dact, g.C, (!loc && g.gmode == GB_SAME) ? &g : nullptr, loc);
+}
+// Norm part: dact -> g.dx (allocated by the caller between the two parts, with g.add / add2 / dx2 / csplit as it needs them)
+static int conv_gn_norm(Exec& e, GnBwdArgs& g, Tensor& dact) {
+  g.g = dact.p;
+  return local_gn_bwd(g) ? gn_bwd_local_op(e, g, dact) : gn_bwd_op(e, g);
+}
+// both parts with the plain result between them: dx (its shape set by the caller) is allocated here
+static int conv_gn_backward(Exec& e, const ConvW& c, const Tensor& dy, GnBwdArgs g, Tensor& dx) {
+  Tensor dact;
+  ISHAP_TRY(conv_gn_dgrad(e, c, dy, g, dact));
+  ISHAP_ALLOC(dx.p, e, dx.numel());
+  g.dx = dx.p;
+  return conv_gn_norm(e, g, dact);
+}
 
 // `split` > 0: the block input was a skip concatenation [h | skip]; its gradient is written as two dense tensors
 // (dx = first `split` channels, *dx2 = the rest) so no slicing pass is needed afterwards.
@@ -63,28 +87,19 @@ static int res_backward(Exec& e, ResL& L, const Tensor& dy, Tensor& dx, int spli
   const Tensor& h1 = sv.h1;
   ISHAP_REQUIRE(dy.C == L.cout && dy.H == h1.H && dy.N == x.N, "ResBlock gradient shape");
   // out_layers: conv2 <- SiLU <- FiLM <- GN2
-  Tensor dc;
   Tensor dh1 = h1;
-  {
-    GnBwdArgs g;
-    g.x = h1.p; g.stats = sv.stats2; g.gamma = L.n2.gamma; g.beta = L.n2.beta;
-    g.emb = u->film_cur + L.emb_off; g.emb_ld = u->film_cur_ld;
-    g.N = h1.N; g.H = h1.H; g.W = h1.W; g.C = L.cout; g.film = 1; g.act = 1; g.gmode = GB_SAME;
-    const bool loc = local_gn_bwd(h1.H * h1.W, L.cout, GB_SAME);
-    ISHAP_TRY(dgrad_op(e, L.c2, dy, dc, L.cout, loc ? nullptr : &g, loc));
-    ISHAP_ALLOC(dh1.p, e, h1.numel());
-    g.g = dc.p; g.dx = dh1.p;
-    if (loc) ISHAP_TRY(gn_bwd_local_op(e, g, dc));
-    else ISHAP_TRY(gn_bwd_op(e, g));
-  }
+  GnBwdArgs g2;
+  g2.x = h1.p; g2.stats = sv.stats2; g2.gamma = L.n2.gamma; g2.beta = L.n2.beta;
+  g2.emb = u->film_cur + L.emb_off; g2.emb_ld = u->film_cur_ld;
+  g2.N = h1.N; g2.H = h1.H; g2.W = h1.W; g2.C = L.cout; g2.film = 1; g2.act = 1; g2.gmode = GB_SAME;
+  ISHAP_TRY(conv_gn_backward(e, L.c2, dy, g2, dh1));
   // in_layers: conv1 <- (up/down sample) <- SiLU <- GN1
   GnBwdArgs g1;
   g1.x = x.p; g1.stats = sv.stats1; g1.gamma = L.n1.gamma; g1.beta = L.n1.beta;
   g1.N = x.N; g1.H = x.H; g1.W = x.W; g1.C = L.cin; g1.film = 0; g1.act = 1;
   g1.gmode = L.down ? GB_UNPOOL : (L.up ? GB_SUM4 : GB_SAME);
-  const bool loc1 = local_gn_bwd(x.H * x.W, L.cin, g1.gmode);
   Tensor da;
-  ISHAP_TRY(dgrad_op(e, L.c1, dh1, da, L.cin, (!loc1 && g1.gmode == GB_SAME) ? &g1 : nullptr, loc1));
+  ISHAP_TRY(conv_gn_dgrad(e, L.c1, dh1, g1, da));
   const half_t* add = dy.p;     // identity skip: gradient of `x_upd(x)` (unet.py:241,256)
   if (L.has_skip) {
     Tensor dxs;
@@ -104,10 +119,8 @@ static int res_backward(Exec& e, ResL& L, const Tensor& dy, Tensor& dx, int spli
     ISHAP_ALLOC(dx.p, e, x.numel());
   }
   dx.sums = nullptr;
-  g1.g = da.p; g1.add = add; g1.dx = dx.p; g1.add2 = add2;
-  if (loc1) ISHAP_TRY(gn_bwd_local_op(e, g1, da));
-  else ISHAP_TRY(gn_bwd_op(e, g1));
-  return 0;
+  g1.add = add; g1.dx = dx.p; g1.add2 = add2;
+  return conv_gn_norm(e, g1, da);
 }
 
 static int attn_backward(Exec& e, AttnL& L, const Tensor& dy, Tensor& dx) {
@@ -129,20 +142,12 @@ static int attn_backward(Exec& e, AttnL& L, const Tensor& dy, Tensor& dx) {
     g.N = N; g.T = T; g.C = C; g.heads = heads; g.d = d; g.alpha = alpha; g.xcd_map = attn_xcd_setting();
     ISHAP_TRY(attn_backward_launch(g, e.s));
   }
-  Tensor dn;
   dx = x;
-  {
-    GnBwdArgs g;
-    g.x = x.p; g.stats = sv.stats; g.gamma = L.n.gamma; g.beta = L.n.beta;
-    g.N = N; g.H = x.H; g.W = x.W; g.C = C; g.film = 0; g.act = 0; g.gmode = GB_SAME;
-    const bool loc = local_gn_bwd(T, C, GB_SAME);
-    ISHAP_TRY(dgrad_op(e, L.qkv, dqkv, dn, C, loc ? nullptr : &g, loc));
-    ISHAP_ALLOC(dx.p, e, x.numel());
-    g.g = dn.p; g.add = dy.p; g.dx = dx.p;
-    if (loc) ISHAP_TRY(gn_bwd_local_op(e, g, dn));
-    else ISHAP_TRY(gn_bwd_op(e, g));
-  }
-  return 0;
+  GnBwdArgs g;
+  g.x = x.p; g.stats = sv.stats; g.gamma = L.n.gamma; g.beta = L.n.beta;
+  g.N = N; g.H = x.H; g.W = x.W; g.C = C; g.film = 0; g.act = 0; g.gmode = GB_SAME;
+  g.add = dy.p;
+  return conv_gn_backward(e, L.qkv, dqkv, g, dx);
 }
 
 static int block_backward(Exec& e, BlockL& b, Tensor g, Tensor& out, int split = 0, Tensor* out2 = nullptr,
@@ -208,20 +213,12 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
     Tensor dout{nullptr, N, S, S, opad};
     ISHAP_ALLOC(dout.p, e, dout.numel());
     if (!dry) ISHAP_TRY(nchw_to_nhwc_f16_scaled(cot_out, cot_out_f16 ? 0 : 1, dout.p, N, cfg.out_channels, S * S, opad, 1.f, s));
-    Tensor dact;
     GnBwdArgs a;
     a.x = u->h_final.p; a.stats = u->head_stats; a.gamma = u->head_norm.gamma;
     a.beta = u->head_norm.beta; a.N = N; a.H = S; a.W = S; a.C = u->final_ch; a.act = 1;
-    const bool loc = local_gn_bwd(S * S, u->final_ch, GB_SAME);
-    ISHAP_TRY(dgrad_op(e, u->head, dout, dact, u->final_ch, loc ? nullptr : &a, loc));
     g = u->h_final;
     if (dry) g = Tensor{nullptr, N, S, S, u->final_ch};
-    Tensor gh = g;
-    ISHAP_ALLOC(gh.p, e, g.numel());
-    a.g = dact.p; a.dx = gh.p;
-    if (loc) ISHAP_TRY(gn_bwd_local_op(e, a, dact));
-    else ISHAP_TRY(gn_bwd_op(e, a));
-    g = gh;
+    ISHAP_TRY(conv_gn_backward(e, u->head, dout, a, g));
   } else {
     F = dry ? n_out - 1 : u->last_feat;
     ISHAP_REQUIRE(F >= 0, "the last forward had no tap (feat_layer < 0)");

@@ -331,3 +331,28 @@ template <typename... T>
 std::string igemm_kernel_name(const char* fmt, T... v) { char b[96]; snprintf(b, sizeof b, fmt, v...); return b; }   // launchers' `name`
 int igemm_launch(const IgemmArgs& a, hipStream_t s);
 int igemm_reduce_launch(const IgemmArgs& a, hipStream_t s);
+
+// One convolution launch as a UNet layer asks for it.  The executor (unet.hip conv_op) and the single-launch ABI
+// (igemm.hip ishap_igemm_run) both describe their launch with this record and turn it into IgemmArgs with igemm_fill.
+struct ConvLaunch {
+  const half_t* X = nullptr;     // source [N][H][W][ldx]; H, W: the OUTPUT map (the source is (H/2, W/2) with ups)
+  int N = 0, H = 0, W = 0, ldx = 0, ups = 0;
+  const half_t* Wt = nullptr;    // packed operand [rows_pad(cout)][ldw], taps * kpad (+ K2) columns used; ldw 0: taps * kpad
+  int kpad = 0, taps = 9, ldw = 0, cout = 0;
+  const float* bias = nullptr;
+  const half_t* res = nullptr;   // residual [N*H*W][ldr] (at (H/2, W/2) with res_ups)
+  int ldr = 0, res_ups = 0;
+  void* out = nullptr;
+  int ldo = 0, out_mode = IG_OUT_F16;
+  long long* stat_out = nullptr;           // forward GroupNorm sums of the output, gathered in the epilogue
+  const struct GnBwdArgs* gb = nullptr;    // norm.h: the output is the gradient arriving at act(film(GN(x))), its backward sums gathered
+  const half_t* X2 = nullptr;    // folded 1x1 second source (IgemmArgs::X2) and its bias
+  int ldx2 = 0, K2 = 0;
+  const float* bias2 = nullptr;
+  SlabSrc* pend_out = nullptr;   // non-null: the consumer adds split-K slices up itself, so a split launch runs no reduce
+};
+// IgemmArgs of the launch `c` describes, its K split planned (defer_reduce set when c.pend_out allows it and K splits).
+// Left to the caller: a.ws, sized by the a.ksplit planned here, and the profiling weight a.flops_scale.
+int igemm_fill(const ConvLaunch& c, int chunk_tiles, IgemmArgs& a);
+// IgemmArgs of the stand-alone reduce (igemm_reduce_launch) of the pending slices `p` of an [M][N] result into fp16 rows of stride ldo
+IgemmArgs igemm_reduce_fill(const SlabSrc& p, int M, int N, int H, int W, void* out, int ldo);

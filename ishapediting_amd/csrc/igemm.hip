@@ -16,6 +16,7 @@
 #include "common.h"
 #include "igemm_epilogue.h"
 #include "gn_bwd_terms.h"
+#include "norm.h"
 #include "../../include/ishap.h"
 
 template <int BM, int BN, int BK, int WM, int WN, bool CONV3>
@@ -554,8 +555,40 @@ extern "C" int ishap_igemm_plan(int M, int cin, int cout, int taps, int K2, int 
   return 0;
 }
 
-// ---- one launch through the C ABI (include/ishap.h, ishap_igemm_run): the IgemmArgs conv_op fills, checked against the
-// caller's buffer sizes first, then the product's own plan and launch ----
+// ---- a layer's launch as IgemmArgs: the one place the fields are filled, for the executor (unet.hip conv_op) and for the
+// single-launch ABI below alike ----
+int igemm_fill(const ConvLaunch& c, int chunk_tiles, IgemmArgs& a) {
+  a = IgemmArgs{};
+  a.stat_out = c.stat_out;
+  if (const GnBwdArgs* gb = c.gb) {       // accumulate the GroupNorm-backward sums in this launch's epilogue
+    a.gb_x = gb->x; a.gb_stats = gb->stats; a.gb_gamma = gb->gamma; a.gb_beta = gb->beta; a.gb_emb = gb->emb;
+    a.gb_emb_ld = gb->emb_ld; a.gb_film = gb->film; a.gb_act = gb->act; a.gb_csums = gb->csums;
+  }
+  a.X = c.X; a.Wt = c.Wt; a.out = c.out; a.bias = c.bias; a.res = c.res;
+  a.M = c.N * c.H * c.W; a.N = c.cout; a.K = c.taps * c.kpad + c.K2;
+  a.X2 = c.X2; a.ldx2 = c.ldx2; a.K2 = c.K2; a.bias2 = c.bias2;
+  a.conv3 = c.taps == 9; a.Cin = c.kpad;
+  a.ldx = c.ldx; a.ldw = c.ldw ? c.ldw : c.taps * c.kpad; a.ldo = c.ldo; a.ldr = c.ldr;
+  a.H = c.H; a.W = c.W; a.ups = c.ups; a.res_ups = c.res_ups;
+  a.out_mode = c.out_mode; a.chunk_tiles = chunk_tiles;
+  a.ksplit = igemm_plan_ksplit(a, c.pend_out != nullptr);
+  if (c.pend_out && a.ksplit > 1) {
+    ISHAP_REQUIRE(c.out_mode == IG_OUT_F16 && c.ldo == c.cout && !c.stat_out && !c.gb, "deferred reduce: dense fp16 output, no epilogue sums");
+    a.defer_reduce = 1;
+  }
+  return 0;
+}
+
+IgemmArgs igemm_reduce_fill(const SlabSrc& p, int M, int N, int H, int W, void* out, int ldo) {
+  IgemmArgs a;
+  a.ws = const_cast<float*>(p.ws); a.ksplit = p.nslab; a.M = M; a.N = N; a.K = 64;
+  a.bias = p.bias; a.bias2 = p.bias2; a.res = p.res; a.ldr = p.ldr; a.res_ups = p.res_ups;
+  a.H = H; a.W = W; a.out = out; a.ldo = ldo; a.out_mode = IG_OUT_F16;
+  return a;
+}
+
+// ---- one launch through the C ABI (include/ishap.h, ishap_igemm_run): the descriptor checked against the caller's buffer
+// sizes, then the same fill, plan and launch a layer goes through ----
 
 static bool desc_fits(const ishap_buf& b, long long bytes, int align) {
   return bytes <= 0 || (b.ptr && b.bytes >= bytes && ((unsigned long long)b.ptr % (unsigned)align) == 0);
@@ -564,8 +597,8 @@ static bool desc_fits(const ishap_buf& b, long long bytes, int align) {
   ISHAP_REQUIRE(desc_fits(d->buf, (need), (align)), std::string(what) + ": needs " + std::to_string((long long)(need)) + \
                 " bytes at " #align "-byte alignment, has " + std::to_string(d->buf.bytes))
 
-// The fields conv_op sets (nbatch = 1, alpha = 1, fp16 or NCHW fp32 output), every extent the launch touches checked against
-// the caller's byte sizes, and the K split planned as conv_op plans it.  No HIP runtime call.
+// Every extent the launch touches checked against the caller's byte sizes; the fields and the K split are igemm_fill's
+// (nbatch = 1, alpha = 1, fp16 or NCHW fp32 output).  No HIP runtime call.
 static int igemm_desc_args(const ishap_igemm_desc* d, IgemmArgs& a) {
   ISHAP_REQUIRE(d != nullptr, "descriptor");
   constexpr long long LIM = 1ll << 31;           // the kernels index each operand with 32-bit element offsets
@@ -590,25 +623,23 @@ static int igemm_desc_args(const ishap_igemm_desc* d, IgemmArgs& a) {
   ISHAP_REQUIRE(!(d->stat_out.ptr && d->gb_x.ptr), "forward statistics and GroupNorm-backward sums are exclusive");
   ISHAP_REQUIRE(d->out_mode == IG_OUT_F16 || !(d->stat_out.ptr || d->gb_x.ptr), "epilogue sums need fp16 output");
 
-  a = IgemmArgs{};
-  a.X = (const half_t*)d->X.ptr; a.X2 = (const half_t*)d->X2.ptr; a.Wt = (const half_t*)d->Wt.ptr; a.out = d->out.ptr;
-  a.bias = (const float*)d->bias.ptr; a.bias2 = (const float*)d->bias2.ptr; a.res = (const half_t*)d->res.ptr;
-  a.ws = (float*)d->ws.ptr; a.stat_out = (long long*)d->stat_out.ptr;
+  ConvLaunch c; GnBwdArgs gb; SlabSrc pend;      // what c.gb / c.pend_out point to
+  c.X = (const half_t*)d->X.ptr; c.N = (int)nimg; c.H = d->H; c.W = d->W; c.ldx = d->ldx;
+  c.Wt = (const half_t*)d->Wt.ptr; c.kpad = d->Cin; c.taps = d->taps; c.ldw = d->ldw;
+  c.cout = d->N; c.bias = (const float*)d->bias.ptr;
+  c.res = (const half_t*)d->res.ptr; c.ldr = d->ldr; c.res_ups = d->res_ups != 0;
+  c.out = d->out.ptr; c.ldo = d->ldo; c.out_mode = d->out_mode;
+  c.ups = d->ups != 0; c.stat_out = (long long*)d->stat_out.ptr;
   if (d->gb_x.ptr) {
-    a.gb_x = (const half_t*)d->gb_x.ptr; a.gb_stats = (const float*)d->gb_stats.ptr; a.gb_gamma = (const float*)d->gb_gamma.ptr;
-    a.gb_beta = (const float*)d->gb_beta.ptr; a.gb_emb = (const float*)d->gb_emb.ptr; a.gb_emb_ld = d->gb_emb_ld;
-    a.gb_film = d->gb_film != 0; a.gb_act = d->gb_act != 0; a.gb_csums = (long long*)d->gb_csums.ptr;
+    gb.x = (const half_t*)d->gb_x.ptr; gb.stats = (const float*)d->gb_stats.ptr; gb.gamma = (const float*)d->gb_gamma.ptr;
+    gb.beta = (const float*)d->gb_beta.ptr; gb.emb = (const float*)d->gb_emb.ptr; gb.emb_ld = d->gb_emb_ld;
+    gb.film = d->gb_film != 0; gb.act = d->gb_act != 0; gb.csums = (long long*)d->gb_csums.ptr;
+    c.gb = &gb;
   }
-  a.M = d->M; a.N = d->N; a.K = (int)K; a.K2 = d->K2; a.Cin = d->Cin; a.conv3 = d->taps == 9;
-  a.ldx = d->ldx; a.ldx2 = d->ldx2; a.ldw = d->ldw; a.ldo = d->ldo; a.ldr = d->ldr;
-  a.H = d->H; a.W = d->W; a.ups = d->ups != 0; a.res_ups = d->res_ups != 0;
-  a.out_mode = d->out_mode; a.chunk_tiles = d->chunk_tiles;
-  a.ksplit = igemm_plan_ksplit(a, d->pending != 0);
-  if (d->pending && a.ksplit > 1) {
-    ISHAP_REQUIRE(d->out_mode == IG_OUT_F16 && d->ldo == d->N && !d->stat_out.ptr && !d->gb_x.ptr,
-                  "deferred reduce: dense fp16 output, no epilogue sums");
-    a.defer_reduce = 1;
-  }
+  c.X2 = (const half_t*)d->X2.ptr; c.ldx2 = d->ldx2; c.K2 = d->K2; c.bias2 = (const float*)d->bias2.ptr;
+  c.pend_out = d->pending ? &pend : nullptr;
+  ISHAP_TRY(igemm_fill(c, d->chunk_tiles, a));
+  a.ws = (float*)d->ws.ptr;
 
   // every extent the launch touches, in bytes
   const long long xrows = d->ups ? d->M / 4 : d->M, rrows = d->res_ups ? d->M / 4 : d->M;
@@ -669,10 +700,9 @@ extern "C" int ishap_igemm_reduce(const ishap_igemm_desc* d, int nslab, int laun
   if (d->bias.ptr) DESC_BUF(bias, (long long)d->N * 4, 16, "bias");
   if (d->bias2.ptr) DESC_BUF(bias2, (long long)d->N * 4, 16, "bias2");
   DESC_BUF(ws, wse * 4, 16, "ws (K slices x M x N floats)");
-  // slab_materialize's arguments (unet.hip)
-  IgemmArgs a;
-  a.ws = (float*)d->ws.ptr; a.ksplit = nslab; a.M = d->M; a.N = d->N; a.K = 64;
-  a.bias = (const float*)d->bias.ptr; a.bias2 = (const float*)d->bias2.ptr; a.res = (const half_t*)d->res.ptr; a.ldr = d->ldr;
-  a.res_ups = d->res_ups != 0; a.H = d->H; a.W = d->W; a.out = d->out.ptr; a.ldo = d->ldo; a.out_mode = IG_OUT_F16;
+  SlabSrc p;
+  p.ws = (const float*)d->ws.ptr; p.nslab = nslab; p.bias = (const float*)d->bias.ptr; p.bias2 = (const float*)d->bias2.ptr;
+  p.res = (const half_t*)d->res.ptr; p.ldr = d->ldr; p.res_ups = d->res_ups != 0;
+  const IgemmArgs a = igemm_reduce_fill(p, d->M, d->N, d->H, d->W, d->out.ptr, d->ldo);
   return launch ? igemm_reduce_launch(a, (hipStream_t)stream) : 0;
 }

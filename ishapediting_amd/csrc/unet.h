@@ -66,7 +66,6 @@ struct AttnSaved {
   Tensor x, qkv, a;
   float* stats = nullptr;
   float* lse = nullptr;
-  half_t* P = nullptr;    // softmax probabilities [N*heads][T][T] kept for the backward (null: recompute)
 };
 
 struct ResL {
@@ -99,7 +98,7 @@ struct ParamSlot {
   std::string name;
   int ndim = 0;
   long long shape[4] = {0, 0, 0, 0};
-  int kind = 0;     // 0 conv weight, 1 conv bias, 2 plain fp32 vector/matrix copy, 3 emb weight, 4 emb bias
+  int kind = 0;     // 0 conv weight, 1 conv bias, 2 plain fp32 vector / matrix copied to dst + dst_off
   ConvW* conv = nullptr;
   float* dst = nullptr;
   long long dst_off = 0;
@@ -215,13 +214,11 @@ static inline int aalloc_checked(Exec& e, size_t count, T** out) {
     (ptr) = salloc((e), (size_t)(count));                                                             \
     ISHAP_REQUIRE((ptr) != nullptr, "GroupNorm statistics arena exhausted");                          \
   } while (0)
-// X [N,H,W,ldx] (*) Wt -> out; taps 9 (3x3, pad 1) or 1; picks split-K and uses the context workspace
-// pend_out: the caller's consumer can read split-K slices (a group-local GroupNorm pass): when the launch splits K, the
-// slices stay in an arena buffer described by *pend_out and no reduce kernel runs (fp16 dense outputs only)
-int conv_op(Exec& e, const half_t* X, int N, int H, int W, int ldx, const half_t* Wt, int kpad, int taps, int cout,
-            const float* bias, const half_t* res, int ldr, void* out, int ldo, int out_mode, int ups, int res_ups,
-            long long* stat_out = nullptr, const struct GnBwdArgs* gb = nullptr, const half_t* X2 = nullptr, int ldx2 = 0,
-            int K2 = 0, const float* bias2 = nullptr, int ldw = 0, SlabSrc* pend_out = nullptr);
+// One convolution launch (ConvLaunch, common.h): picks split-K and uses the context workspace.  With c.pend_out (the consumer is a
+// group-local GroupNorm pass) a split launch leaves its slices in an arena buffer described by *c.pend_out: no reduce kernel
+int conv_op(Exec& e, const ConvLaunch& c);
+// the launch y = w (*) x with w's bias, gathering the sums y carries; call sites add what else they use
+ConvLaunch conv_launch(const Tensor& x, const ConvW& w, const Tensor& y);
 // small maps (<= 32 x 32): GroupNorm passes run group-local (norm_local.hip), producers gather no statistics
 int unet_join_tail(ishap_unet* u, hipStream_t s);
 bool small_map(int HW);

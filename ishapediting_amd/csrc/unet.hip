@@ -154,9 +154,11 @@ int unet_build(ishap_unet* u) {
     ISHAP_TRY(dalloc(&c.bias, round_up(c.cout, 4)));
     return 0;
   };
-  auto reg_conv = [&](ConvW& c) -> int {
+  // conv2d: a 1x1 Conv2d weight [O,I,1,1] (the skip connections); the attention blocks' 1x1 convs are Conv1d [O,I,1]
+  auto reg_conv = [&](ConvW& c, bool conv2d = false) -> int {
     ISHAP_TRY(conv_alloc(c));
     if (c.taps == 9) reg(c.path + ".weight", {c.cout, c.cin, 3, 3}, 0, &c, nullptr, 0);
+    else if (conv2d) reg(c.path + ".weight", {c.cout, c.cin, 1, 1}, 0, &c, nullptr, 0);
     else reg(c.path + ".weight", {c.cout, c.cin, 1}, 0, &c, nullptr, 0);
     reg(c.path + ".bias", {c.cout}, 1, &c, nullptr, 0);
     return 0;
@@ -179,10 +181,7 @@ int unet_build(ishap_unet* u) {
   reg("time_embed.0.bias", {ted}, 2, nullptr, &u->te_b0, 0);
   reg("time_embed.2.weight", {ted, ted}, 2, nullptr, &u->te_w2, 0);
   reg("time_embed.2.bias", {ted}, 2, nullptr, &u->te_b2, 0);
-  // stem is the only stem conv in the skip-less plain form; the skip 1x1 convs are Conv2d [O,I,1,1]
-  ISHAP_TRY(conv_alloc(u->stem));
-  reg("input_blocks.0.0.weight", {u->stem.cout, u->stem.cin, 3, 3}, 0, &u->stem, nullptr, 0);
-  reg("input_blocks.0.0.bias", {u->stem.cout}, 1, &u->stem, nullptr, 0);
+  ISHAP_TRY(reg_conv(u->stem));
   for (auto& r : u->res) {
     ISHAP_TRY(reg_norm(r.n1, r.path + ".in_layers.0"));
     ISHAP_TRY(reg_conv(r.c1));
@@ -191,7 +190,7 @@ int unet_build(ishap_unet* u) {
     ISHAP_TRY(reg_norm(r.n2, r.path + ".out_layers.0"));
     ISHAP_TRY(reg_conv(r.c2));
     if (r.has_skip) {
-      ISHAP_TRY(conv_alloc(r.skip));
+      ISHAP_TRY(reg_conv(r.skip, true));
       if (!r.down && !r.up && r.c2.kpad % 64 == 0 && r.skip.kpad % 64 == 0) {
         // forward operand [c2 (9 taps) | skip (1x1)] concatenated along K: both convolutions in one launch
         const int ld = 9 * r.c2.kpad + r.skip.kpad;
@@ -201,8 +200,6 @@ int unet_build(ishap_unet* u) {
         r.c2.cat_ld = ld; r.c2.cat_off = 0;
         r.skip.cat = r.c2.cat; r.skip.cat_ld = ld; r.skip.cat_off = 9 * r.c2.kpad;
       }
-      reg(r.skip.path + ".weight", {r.cout, r.cin, 1, 1}, 0, &r.skip, nullptr, 0);
-      reg(r.skip.path + ".bias", {r.cout}, 1, &r.skip, nullptr, 0);
     }
   }
   for (auto& a : u->attn) {
@@ -211,9 +208,7 @@ int unet_build(ishap_unet* u) {
     ISHAP_TRY(reg_conv(a.proj));
   }
   ISHAP_TRY(reg_norm(u->head_norm, "out.0"));
-  ISHAP_TRY(conv_alloc(u->head));
-  reg("out.2.weight", {u->head.cout, u->head.cin, 3, 3}, 0, &u->head, nullptr, 0);
-  reg("out.2.bias", {u->head.cout}, 1, &u->head, nullptr, 0);
+  ISHAP_TRY(reg_conv(u->head));
 
   const int NB = cfg.max_batch;
   ISHAP_TRY(dalloc(&u->d_temb, (size_t)NB * mc));
@@ -274,40 +269,28 @@ bool small_map(int HW) {
 }
 bool local_gn(int HW, int C) { return small_map(HW) && gn_local_fits(HW, C); }
 
-int conv_op(Exec& e, const half_t* X, int N, int H, int W, int ldx, const half_t* Wt, int kpad, int taps,
-                   int cout, const float* bias, const half_t* res, int ldr, void* out, int ldo, int out_mode, int ups,
-                   int res_ups, long long* stat_out, const GnBwdArgs* gb, const half_t* X2, int ldx2, int K2,
-                   const float* bias2, int ldw, SlabSrc* pend_out) {
+ConvLaunch conv_launch(const Tensor& x, const ConvW& w, const Tensor& y) {
+  ConvLaunch c;
+  c.X = x.p; c.N = y.N; c.H = y.H; c.W = y.W; c.ldx = x.C;
+  c.Wt = w.w; c.kpad = w.kpad; c.taps = w.taps; c.cout = w.cout; c.bias = w.bias;
+  c.out = y.p; c.ldo = y.C; c.stat_out = y.sums;
+  return c;
+}
+
+int conv_op(Exec& e, const ConvLaunch& c) {
+  if (c.pend_out) *c.pend_out = SlabSrc{};
   IgemmArgs a;
-  a.stat_out = stat_out;
-  if (gb) {       // this launch produces the gradient arriving at act(film(GN(x))): accumulate the GN-backward sums in its epilogue
-    a.gb_x = gb->x; a.gb_stats = gb->stats; a.gb_gamma = gb->gamma; a.gb_beta = gb->beta; a.gb_emb = gb->emb;
-    a.gb_emb_ld = gb->emb_ld; a.gb_film = gb->film; a.gb_act = gb->act; a.gb_csums = gb->csums;
-  }
-  a.X = X; a.Wt = Wt; a.out = out; a.bias = bias; a.res = res;
-  a.M = N * H * W; a.N = cout; a.K = taps * kpad + K2;
-  a.X2 = X2; a.ldx2 = ldx2; a.K2 = K2; a.bias2 = bias2;
-  a.conv3 = taps == 9; a.Cin = kpad;
-  a.ldx = ldx; a.ldw = ldw ? ldw : taps * kpad; a.ldo = ldo; a.ldr = ldr;
-  a.H = H; a.W = W; a.ups = ups; a.res_ups = res_ups;
-  a.out_mode = out_mode;
-  a.chunk_tiles = e.chunk_tiles;
-  a.flops_scale = (Wt == e.u->head.w) ? 1.f / 3.f : 1.f;
-  a.ksplit = igemm_plan_ksplit(a, pend_out != nullptr);
-  if (pend_out) *pend_out = SlabSrc{};
-  if (pend_out && a.ksplit > 1) {
+  ISHAP_TRY(igemm_fill(c, e.chunk_tiles, a));
+  a.flops_scale = (c.Wt == e.u->head.w) ? 1.f / 3.f : 1.f;    // profiling weight of the hi/lo-split head; the executor's own, not part of the shared fill
+  const size_t need = a.ksplit > 1 ? (size_t)a.ksplit * a.M * a.N : 0;
+  if (a.defer_reduce) {
     // the consumer adds the slices up itself: they live in the arena until it has run
-    ISHAP_REQUIRE(out_mode == IG_OUT_F16 && ldo == cout && !stat_out && !gb, "deferred reduce: dense fp16 output, no epilogue sums");
-    float* slab = nullptr;
-    ISHAP_ALLOC(slab, e, (size_t)a.ksplit * a.M * a.N);
-    pend_out->ws = slab; pend_out->nslab = a.ksplit; pend_out->zstride = (long long)a.M * a.N;
-    pend_out->bias = bias; pend_out->bias2 = bias2; pend_out->res = res; pend_out->ldr = ldr; pend_out->res_ups = res_ups;
-    if (e.dry) return 0;
-    a.ws = slab;
-    a.defer_reduce = 1;
-    return igemm_launch(a, e.s);
+    ISHAP_ALLOC(a.ws, e, need);
+    SlabSrc& p = *c.pend_out;
+    p.ws = a.ws; p.nslab = a.ksplit; p.zstride = (long long)a.M * a.N;
+    p.bias = c.bias; p.bias2 = c.bias2; p.res = c.res; p.ldr = c.ldr; p.res_ups = c.res_ups;
+    return e.dry ? 0 : igemm_launch(a, e.s);
   }
-  size_t need = a.ksplit > 1 ? (size_t)a.ksplit * a.M * a.N : 0;
   if (e.dry) {
     if (need > e.u->ws_floats) e.u->ws_floats = need;
     return 0;
@@ -323,11 +306,7 @@ int slab_materialize(Exec& e, Tensor& t) {
   const SlabSrc p = t.pend;
   t.pend = SlabSrc{};
   if (e.dry) return 0;
-  IgemmArgs a;
-  a.ws = const_cast<float*>(p.ws); a.ksplit = p.nslab; a.M = (int)t.rows(); a.N = t.C; a.K = 64;
-  a.bias = p.bias; a.bias2 = p.bias2; a.res = p.res; a.ldr = p.ldr; a.res_ups = p.res_ups;
-  a.H = t.H; a.W = t.W; a.out = t.p; a.ldo = t.C; a.out_mode = IG_OUT_F16;
-  return igemm_reduce_launch(a, e.s);
+  return igemm_reduce_launch(igemm_reduce_fill(p, (int)t.rows(), t.C, t.H, t.W, t.p, t.C), e.s);
 }
 
 int gn_stats_op(Exec& e, const Tensor& x, float* stats) {
@@ -364,6 +343,33 @@ static int gn_local_op(Exec& e, Tensor& x, const NormW& nw, half_t* out, half_t*
   return gn_local_launch(g, e.s);
 }
 
+// out = act(film(GN(x))) (+ 2x2 pool with the pooled raw input in xpool | the head's hi/lo split); `stats` receives (mean, rstd)
+// for the backward pass; emb: the FiLM row (null without film).  x may be pending or a lazy skip concatenation.  Route: a small
+// map takes ONE group-local launch; else pending slices are added up by the stand-alone reduce, the statistics pass runs unless
+// the producer (or the two producers of a lazy concatenation) gathered the sums, and the apply kernel finalises those sums into
+// `stats` itself.  The split form has no group-local kernel (the head's map is full-size in the real model anyway).
+// Plan equals replay: the deferred forward tail is walked twice, dry by the forward and for real by unet_run_tail, and both walks
+// must make the same allocations.  The route here reads only the shape (local_gn) and fields of x that the plan walk sets as the
+// replay does (pend, sums, cat_*); the outputs are the caller's, allocated before the call; gn_local_op's record and
+// gn_stats_op's scratch bound are taken in dry runs too.  The tenancy (exec_is_solo) only picks launch forms inside gn_local_op.
+static int gn_forward_op(Exec& e, Tensor& x, const NormW& nw, half_t* out, half_t* xpool, float* stats, const float* emb,
+                         int film, int act, int pool, int split = 0) {
+  const int emb_ld = emb ? e.u->film_cur_ld : 0;
+  if (!split && local_gn(x.H * x.W, x.C)) return gn_local_op(e, x, nw, out, xpool, stats, emb, emb_ld, film, act, pool);
+  const bool lazy_cat = x.cat_a != nullptr;
+  ISHAP_REQUIRE(!lazy_cat || (x.cat_sa && x.cat_sb), "a lazy concatenation on a large map carries the producers' sums");
+  ISHAP_TRY(slab_materialize(e, x));
+  const bool summed = x.sums || lazy_cat;
+  if (!summed) ISHAP_TRY(gn_stats_op(e, x, stats));
+  if (e.dry) return 0;
+  GnApplyArgs g;
+  g.x = x.p; g.out = out; g.xpool = xpool; g.stats = stats; g.sums = x.sums; g.stats_out = summed ? stats : nullptr;
+  g.gamma = nw.gamma; g.beta = nw.beta; g.emb = emb; g.emb_ld = emb_ld;
+  g.N = x.N; g.H = x.H; g.W = x.W; g.C = x.C; g.film = film; g.act = act; g.pool = pool; g.split = split;
+  if (lazy_cat) { g.x = x.cat_a; g.x2 = x.cat_b; g.sums = x.cat_sa; g.sums2 = x.cat_sb; g.csplit = x.cat_ca; g.xcopy = x.p; }
+  return gn_apply_launch(g, e.s);
+}
+
 static int res_forward(Exec& e, ResL& L, Tensor x, Tensor& y) {
   ishap_unet* u = e.u;
   const int N = x.N, H = x.H, W = x.W;
@@ -373,51 +379,24 @@ static int res_forward(Exec& e, ResL& L, Tensor x, Tensor& y) {
   float* st2 = nullptr; ISHAP_ALLOC(st2, e, (size_t)N * 64);
   const bool lazy_cat = x.cat_a != nullptr;
   ISHAP_REQUIRE(!lazy_cat || (!L.down && !L.up), "a skip concatenation feeds a plain ResBlock");
-  const bool loc_in = local_gn(H * W, L.cin), loc_out = local_gn(Ho * Wo, L.cout);
+  const bool loc_out = local_gn(Ho * Wo, L.cout);     // conv1 may then leave its split-K slices to the second GroupNorm
   const bool nosum_out = small_map(Ho * Wo);      // the consumers of an activation on a small map gather their own statistics
   Tensor a{nullptr, N, L.down ? Ho : H, L.down ? Wo : W, L.cin};
   ISHAP_ALLOC(a.p, e, a.numel());
   Tensor xs = x;
   xs.pend = SlabSrc{}; xs.cat_pend = SlabSrc{};
   if (L.down) { xs = a; ISHAP_ALLOC(xs.p, e, a.numel()); }
-  if (loc_in) {
-    ISHAP_TRY(gn_local_op(e, x, L.n1, a.p, L.down ? xs.p : nullptr, st1, nullptr, 0, 0, 1, L.down));
-  } else {
-    ISHAP_REQUIRE(!lazy_cat || (x.cat_sa && x.cat_sb), "a lazy concatenation on a large map carries the producers' sums");
-    ISHAP_TRY(slab_materialize(e, x));
-    if (!x.sums && !lazy_cat) ISHAP_TRY(gn_stats_op(e, x, st1));
-    if (!e.dry) {
-      GnApplyArgs g;
-      g.x = x.p; g.out = a.p; g.xpool = L.down ? xs.p : nullptr;
-      g.stats = st1; g.sums = x.sums; g.stats_out = x.sums ? st1 : nullptr; g.gamma = L.n1.gamma; g.beta = L.n1.beta;
-      g.N = N; g.H = H; g.W = W; g.C = L.cin; g.act = 1; g.pool = L.down;
-      if (lazy_cat) {
-        g.x = x.cat_a; g.x2 = x.cat_b; g.sums = x.cat_sa; g.sums2 = x.cat_sb; g.csplit = x.cat_ca; g.xcopy = x.p;
-        g.stats_out = st1;
-      }
-      ISHAP_TRY(gn_apply_launch(g, e.s));
-    }
-  }
+  ISHAP_TRY(gn_forward_op(e, x, L.n1, a.p, L.down ? xs.p : nullptr, st1, nullptr, 0, 1, L.down));
   Tensor h1{nullptr, N, Ho, Wo, L.cout};
   ISHAP_ALLOC(h1.p, e, h1.numel());
   if (!nosum_out) ISHAP_SALLOC(h1.sums, e, (size_t)N * L.cout * 2);
   Tensor c = h1;
   c.pend = SlabSrc{};
   ISHAP_ALLOC(c.p, e, h1.numel());
-  ISHAP_TRY(conv_op(e, a.p, N, Ho, Wo, L.cin, L.c1.w, L.c1.kpad, 9, L.cout, L.c1.bias, nullptr, 0, h1.p, L.cout, IG_OUT_F16,
-                    L.up, 0, h1.sums, nullptr, nullptr, 0, 0, nullptr, 0, loc_out ? &h1.pend : nullptr));
-  if (loc_out) {
-    ISHAP_TRY(gn_local_op(e, h1, L.n2, c.p, nullptr, st2, u->film_cur + L.emb_off, u->film_cur_ld, 1, 1, 0));
-  } else {
-    if (!h1.sums) ISHAP_TRY(gn_stats_op(e, h1, st2));
-    if (!e.dry) {
-      GnApplyArgs g;
-      g.x = h1.p; g.out = c.p; g.stats = st2; g.sums = h1.sums; g.stats_out = h1.sums ? st2 : nullptr; g.gamma = L.n2.gamma; g.beta = L.n2.beta;
-      g.emb = u->film_cur + L.emb_off; g.emb_ld = u->film_cur_ld;
-      g.N = N; g.H = Ho; g.W = Wo; g.C = L.cout; g.film = 1; g.act = 1;
-      ISHAP_TRY(gn_apply_launch(g, e.s));
-    }
-  }
+  ConvLaunch k1 = conv_launch(a, L.c1, h1);
+  k1.ups = L.up; k1.pend_out = loc_out ? &h1.pend : nullptr;
+  ISHAP_TRY(conv_op(e, k1));
+  ISHAP_TRY(gn_forward_op(e, h1, L.n2, c.p, nullptr, st2, u->film_cur + L.emb_off, 1, 1, 0));
   y = h1;
   y.pend = SlabSrc{};
   ISHAP_ALLOC(y.p, e, h1.numel());
@@ -426,19 +405,20 @@ static int res_forward(Exec& e, ResL& L, Tensor x, Tensor& y) {
   // the block output's next reader is always a GroupNorm pass (the next ResBlock's, an attention block's, the head's):
   // on a small map it may stay pending
   SlabSrc* ypend = small_map(Ho * Wo) ? &y.pend : nullptr;
+  ConvLaunch k2 = conv_launch(c, L.c2, y);
   if (L.has_skip && L.c2.cat) {
     // y = conv2(c) + skip(x) as ONE launch: the 1x1 skip convolution is L.cin more K columns read from x
-    ISHAP_TRY(conv_op(e, c.p, N, Ho, Wo, L.cout, L.c2.cat, L.c2.kpad, 9, L.cout, L.c2.bias, nullptr, 0, y.p, L.cout,
-                      IG_OUT_F16, 0, 0, y.sums, nullptr, xs.p, L.cin, L.skip.kpad, L.skip.bias, L.c2.cat_ld, ypend));
+    k2.Wt = L.c2.cat; k2.ldw = L.c2.cat_ld; k2.X2 = xs.p; k2.ldx2 = L.cin; k2.K2 = L.skip.kpad; k2.bias2 = L.skip.bias;
+    k2.pend_out = ypend;
   } else if (L.has_skip) {
-    ISHAP_TRY(conv_op(e, xs.p, N, Ho, Wo, L.cin, L.skip.w, L.skip.kpad, 1, L.cout, L.skip.bias, nullptr, 0, y.p, L.cout,
-                      IG_OUT_F16, 0, 0));
-    ISHAP_TRY(conv_op(e, c.p, N, Ho, Wo, L.cout, L.c2.w, L.c2.kpad, 9, L.cout, L.c2.bias, y.p, L.cout, y.p, L.cout,
-                      IG_OUT_F16, 0, 0, y.sums));
+    ConvLaunch ks = conv_launch(xs, L.skip, y);
+    ks.stat_out = nullptr;              // y is complete, and its sums gathered, only after conv2 below
+    ISHAP_TRY(conv_op(e, ks));
+    k2.res = y.p; k2.ldr = L.cout;
   } else {
-    ISHAP_TRY(conv_op(e, c.p, N, Ho, Wo, L.cout, L.c2.w, L.c2.kpad, 9, L.cout, L.c2.bias, xs.p, L.cin, y.p, L.cout,
-                      IG_OUT_F16, 0, L.up, y.sums, nullptr, nullptr, 0, 0, nullptr, 0, ypend));
+    k2.res = xs.p; k2.ldr = L.cin; k2.res_ups = L.up; k2.pend_out = ypend;
   }
+  ISHAP_TRY(conv_op(e, k2));
   h1.pend = SlabSrc{};
   x.pend = SlabSrc{}; x.cat_pend = SlabSrc{};
   L.sv.x = x; L.sv.h1 = h1; L.sv.xs = xs; L.sv.stats1 = st1; L.sv.stats2 = st2;
@@ -446,8 +426,6 @@ static int res_forward(Exec& e, ResL& L, Tensor x, Tensor& y) {
 }
 
 static int attn_forward(Exec& e, AttnL& L, Tensor x, Tensor& y) {
-  ishap_unet* u = e.u;
-  (void)u;
   const int N = x.N, T = x.H * x.W, C = L.C, heads = L.heads, d = C / heads;
   ISHAP_REQUIRE(x.C == C, "attention channels");
   ISHAP_REQUIRE(d % 32 == 0, "head width must be a multiple of 32");
@@ -456,18 +434,7 @@ static int attn_forward(Exec& e, AttnL& L, Tensor x, Tensor& y) {
   Tensor nrm = x;
   nrm.pend = SlabSrc{};
   ISHAP_ALLOC(nrm.p, e, x.numel());
-  if (local_gn(T, C)) {
-    ISHAP_TRY(gn_local_op(e, x, L.n, nrm.p, nullptr, st, nullptr, 0, 0, 0, 0));
-  } else {
-    ISHAP_TRY(slab_materialize(e, x));
-    if (!x.sums) ISHAP_TRY(gn_stats_op(e, x, st));
-    if (!e.dry) {
-      GnApplyArgs g;
-      g.x = x.p; g.out = nrm.p; g.stats = st; g.sums = x.sums; g.stats_out = x.sums ? st : nullptr; g.gamma = L.n.gamma; g.beta = L.n.beta;
-      g.N = N; g.H = x.H; g.W = x.W; g.C = C; g.act = 0;
-      ISHAP_TRY(gn_apply_launch(g, e.s));
-    }
-  }
+  ISHAP_TRY(gn_forward_op(e, x, L.n, nrm.p, nullptr, st, nullptr, 0, 0, 0));
   Tensor qkv{nullptr, N, x.H, x.W, 3 * C};
   ISHAP_ALLOC(qkv.p, e, qkv.numel());
   if (attn8_applicable(N, T, C, d) && L.qkv.kpad == C && L.proj.kpad == C && small_map(T)) {
@@ -495,11 +462,10 @@ static int attn_forward(Exec& e, AttnL& L, Tensor x, Tensor& y) {
       g.N = N; g.C = C; g.heads = heads; g.alpha = 1.f / sqrtf((float)d);
       ISHAP_TRY(attn8_fused_launch(g, e.s, exec_is_solo(e)));
     }
-    L.sv.x = x; L.sv.qkv = qkv; L.sv.a = a; L.sv.stats = st; L.sv.lse = lse; L.sv.P = nullptr;
+    L.sv.x = x; L.sv.qkv = qkv; L.sv.a = a; L.sv.stats = st; L.sv.lse = lse;
     return 0;
   }
-  ISHAP_TRY(conv_op(e, nrm.p, N, x.H, x.W, C, L.qkv.w, L.qkv.kpad, 1, 3 * C, L.qkv.bias, nullptr, 0, qkv.p, 3 * C,
-                    IG_OUT_F16, 0, 0));
+  ISHAP_TRY(conv_op(e, conv_launch(nrm, L.qkv, qkv)));
   Tensor a = x;
   ISHAP_ALLOC(a.p, e, x.numel());
   if (!e.dry) {
@@ -516,9 +482,10 @@ static int attn_forward(Exec& e, AttnL& L, Tensor x, Tensor& y) {
   y.sums = nullptr;
   const bool nosum = small_map(T);
   if (!nosum) ISHAP_SALLOC(y.sums, e, (size_t)N * C * 2);
-  ISHAP_TRY(conv_op(e, a.p, N, x.H, x.W, C, L.proj.w, L.proj.kpad, 1, C, L.proj.bias, x.p, C, y.p, C, IG_OUT_F16, 0, 0,
-                    y.sums, nullptr, nullptr, 0, 0, nullptr, 0, nosum ? &y.pend : nullptr));
-  L.sv.x = x; L.sv.qkv = qkv; L.sv.a = a; L.sv.stats = st; L.sv.lse = lse; L.sv.P = nullptr;
+  ConvLaunch kp = conv_launch(a, L.proj, y);
+  kp.res = x.p; kp.ldr = C; kp.pend_out = nosum ? &y.pend : nullptr;
+  ISHAP_TRY(conv_op(e, kp));
+  L.sv.x = x; L.sv.qkv = qkv; L.sv.a = a; L.sv.stats = st; L.sv.lse = lse;
   return 0;
 }
 
@@ -530,8 +497,7 @@ static int block_forward(Exec& e, BlockL& b, Tensor h, Tensor& out) {
       y = Tensor{nullptr, h.N, h.H, h.W, u->stem.cout};
       ISHAP_ALLOC(y.p, e, y.numel());
       if (!small_map(h.H * h.W)) ISHAP_SALLOC(y.sums, e, (size_t)h.N * u->stem.cout * 2);
-      ISHAP_TRY(conv_op(e, h.p, h.N, h.H, h.W, h.C, u->stem.w, u->stem.kpad, 9, u->stem.cout, u->stem.bias, nullptr, 0, y.p,
-                        u->stem.cout, IG_OUT_F16, 0, 0, y.sums));
+      ISHAP_TRY(conv_op(e, conv_launch(h, u->stem, y)));
     } else if (l.kind == 1) {
       ISHAP_TRY(res_forward(e, u->res[l.idx], h, y));
     } else {
@@ -604,23 +570,14 @@ static int out_blocks_range(Exec& e, ishap_unet* u, size_t i0, size_t i1, Tensor
 // ---- head in fp32 (unet.py:667-669): GroupNorm, SiLU, 3x3 conv with fp32 weights.  The fp32 products are
 //      formed on the fp16 MFMA from hi/lo splits of both operands (3 partial products, fp32 accumulate). ----
 static int forward_head(Exec& e, ishap_unet* u, Tensor h, int N, float* out) {
-  const ishap_unet_config& cfg = u->cfg;
-  const int S = cfg.image_size;
-  ISHAP_TRY(slab_materialize(e, h));      // the head's GroupNorm runs on the full-size map (never group-local in the real model)
-  u->h_final = h;
+  const int S = u->cfg.image_size;
   ISHAP_ALLOC(u->head_stats, e, (size_t)N * 64);
-  if (!h.sums) ISHAP_TRY(gn_stats_op(e, h, u->head_stats));
   half_t* hsplit = nullptr; ISHAP_ALLOC(hsplit, e, (size_t)h.numel() * 3);
-  if (!e.dry) {
-    GnApplyArgs g;
-    g.x = h.p; g.out = hsplit; g.stats = u->head_stats; g.sums = h.sums; g.stats_out = h.sums ? u->head_stats : nullptr;
-    g.gamma = u->head_norm.gamma; g.beta = u->head_norm.beta;
-    g.N = N; g.H = S; g.W = S; g.C = h.C; g.act = 1; g.split = 1;
-    ISHAP_TRY(gn_apply_launch(g, e.s));
-  }
-  ISHAP_TRY(conv_op(e, hsplit, N, S, S, 3 * h.C, u->head.w, u->head.kpad, 9, cfg.out_channels, u->head.bias, nullptr, 0, out,
-                    0, IG_OUT_NCHW_F32, 0, 0));
-  return 0;
+  ISHAP_TRY(gn_forward_op(e, h, u->head_norm, hsplit, nullptr, u->head_stats, nullptr, 0, 1, 0, 1));
+  u->h_final = h;
+  ConvLaunch c = conv_launch(Tensor{hsplit, N, S, S, 3 * h.C}, u->head, Tensor{nullptr, N, S, S, 0});
+  c.out = out; c.out_mode = IG_OUT_NCHW_F32;      // NCHW fp32: no row stride
+  return conv_op(e, c);
 }
 
 // the deferred forward tail (ISHAP_TAIL_DEFER): the launches unet_forward_impl only planned, on the side stream, behind the event
@@ -755,8 +712,8 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
     // rest -- allocate what it will allocate, launch nothing -- so that the caller's backward gets its scratch above the whole
     // forward; ishap_unet_run_tail enqueues the launches later, behind an event the backward records after its first blocks
     // (the tail then runs beside the backward's latency-bound middle, not beside its chip-filling first and last launches).
-    // The plan and the replay make the same allocations by construction: no route below depends on the tenancy, only launch
-    // forms do (gn_local_op's parts, attn8_fused_launch's one- or two-launch form)
+    // The plan and the replay make the same allocations: no route depends on the tenancy, only launch forms do (gn_forward_op;
+    // attn8_fused_launch's one- or two-launch form)
     u->tail = ishap_unet::TailState{split, h, hs, N, out, u->arena.off, u->stat_off, (keep & 1) != 0};
     Exec plan = e;
     plan.dry = true;

@@ -1,7 +1,8 @@
 """Every implicit-GEMM kernel form, one launch at a time, against a float64 convolution on the CPU.
 
-Each case in CASES is one launch through ishap_igemm_run (include/ishap.h). That call fills the IgemmArgs that conv_op
-(csrc/unet.hip) fills, plans the K split and form as the product does, and launches. The result is compared with torch conv2d /
+Each case in CASES is one launch through ishap_igemm_run (include/ishap.h). That call describes the launch with the
+ConvLaunch record the executor's conv_op (csrc/unet.hip) uses and fills IgemmArgs with the same function (igemm_fill,
+csrc/igemm.hip: fields, K split, deferred reduce), so the oracle launch and the layer launch go through one fill; then it launches. The result is compared with torch conv2d /
 matmul in float64 of the same fp16 values, zero-padded per image. A case asserts four things:
   1. form: the kernel name the call reports is the case's expected name;
   2. values: |gpu - ref| <= 2^-11 |ref| + 2^-16 A for every element, where A = sum |x w| (+ |bias| + |bias2| + |res|) is the same

@@ -1,6 +1,6 @@
 """Which kernel every implicit-GEMM launch gets: the K split and kernel form that csrc/igemm.hip plans (igemm_plan_ksplit,
 igemm_plan), read on the CPU through ishap_igemm_plan.  The expected values are what the dispatch chose before it was gathered
-into the planner (conv_op's split overrides, igemm_launch's tile pick, the igemm2 / igemm4 ladders and the profiling slot
+into the planner (the executor's split overrides, igemm_launch's tile pick, the igemm2 / igemm4 ladders and the profiling slot
 conditional), evaluated for these shapes -- not values read back from the planner."""
 import ctypes as C
 import json

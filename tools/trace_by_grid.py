@@ -1,5 +1,7 @@
 """Aggregate a rocprofv3 kernel_trace.csv by (kernel name with template arguments, grid, workgroup, LDS bytes):
-launches, total ms, average us.  Usage: trace_by_grid.py kernel_trace.csv [name substring]"""
+launches, total ms, average us.  Usage: trace_by_grid.py kernel_trace.csv [name substring]
+trace_by_grid.py --ordered kernel_trace.csv: no times, one line per launch in dispatch order within each queue (queues numbered by
+first appearance) -- two builds that enqueue the same launches print the same text (diff it)."""
 import collections
 import csv
 import re
@@ -12,6 +14,16 @@ def short(name):
     m = re.match(r"([A-Za-z_0-9:]+(<[^()]*>)?)", name)
     return (m.group(1) if m else name)[:64]
 
+
+if sys.argv[1] == "--ordered":
+    queues = collections.OrderedDict()
+    for r in sorted(csv.DictReader(open(sys.argv[2])), key=lambda r: int(r["Dispatch_Id"])):
+        queues.setdefault(r["Queue_Id"], []).append(r)
+    for q, rows in enumerate(queues.values()):
+        for r in rows:
+            grid, wg = (",".join(r.get(f"{k}_Size_{d}", "?") for d in "XYZ") for k in ("Grid", "Workgroup"))
+            print(f"q{q} grid={grid} wg={wg} lds={r.get('LDS_Block_Size', '?')} {re.sub(r'^void ', '', r['Kernel_Name'])}")
+    sys.exit(0)
 
 agg = collections.defaultdict(lambda: [0, 0.0])
 for r in csv.DictReader(open(sys.argv[1])):
