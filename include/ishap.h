@@ -42,7 +42,7 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7 since
                             * the mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats); 8 since
                             * ishap_arap / ishap_arap_scratch_bytes / ishap_nearest_vertices; 9 since ishap_attention_run /
-                            * ishap_attention8_run */
+                            * ishap_attention8_run; 10 since ishap_group_norm32_plan replaced ishap_group_norm32_parts */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -161,8 +161,18 @@ int ishap_group_norm32(const void* x_nhwc_f16, const float* gamma, const float* 
 int ishap_group_norm32_backward(const void* g_nhwc_f16, const void* x_nhwc_f16, const float* stats, const float* gamma,
                                 const float* beta, int N, int H, int W, int C, int silu, int route, void* dx_nhwc_f16,
                                 void* scratch, void* stream);
-/* workgroups per (image, group) route 3 uses for this shape on the current device (> 1: the rendezvous is exercised) */
-int ishap_group_norm32_parts(int N, int HW, int C);
+/* Which launch one GroupNorm pass gets, without running anything and without a GPU (the compute-unit count that bounds `parts` is
+ * the current device's, 256 where there is none): a pass over [N][H*W][C] -- forward, or backward != 0 for the input gradient with
+ * gmode 0 / 1 / 2 = the upstream gradient at the same / half (the forward pooled) / twice (the forward upsampled) the resolution;
+ * pending != 0: the input (backward: the upstream gradient) is still the split-K slices of its producer; film / act / pool: the
+ * fused FiLM, SiLU and 2x2 average pool.  route as above, and *route_out = the route taken (route 0 resolved as the executor does,
+ * ISHAP_LOCAL_GN included; a backward pass off the small maps takes 1).  Group-local routes (2, 3): parts = workgroups per (image,
+ * group) (> 1: the in-launch rendezvous is exercised), vec = channels per lane, the grid is (grid_x, grid_y) workgroups of
+ * `threads`, lds_bytes of dynamic LDS, xcd = how the parts are dealt to workgroups (ISHAP_GN_XCD; 0 with one part).  Full-map routes (1, 4): the apply kernel's launch, parts = 0.  kernel: the kernel's name
+ * with its template arguments; -2 when kernel_cap is too small.  Outputs may be NULL. */
+int ishap_group_norm32_plan(int N, int H, int W, int C, int backward, int pending, int film, int act, int pool, int gmode, int route,
+                            int* route_out, int* parts, int* vec, int* threads, int* grid_x, int* grid_y, int* lds_bytes,
+                            int* xcd, char* kernel, int kernel_cap);
 
 /* ------------------------------------------- diffusion step (gd/gaussian_diffusion.py:232-331, 400-510) */
 typedef struct {

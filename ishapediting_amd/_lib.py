@@ -81,7 +81,7 @@ SYMBOLS = {
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "ishap_group_norm32_backward": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, c_void_p, c_void_p, c_void_p]),
-    "ishap_group_norm32_parts": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "ishap_group_norm32_plan": (C.c_int, [C.c_int] * 11 + [C.POINTER(C.c_int)] * 8 + [C.c_char_p, C.c_int]),
     "ishap_unet_create": (C.c_int, [C.POINTER(UNetConfigC), C.c_int, C.POINTER(c_void_p)]),
     "ishap_unet_destroy": (None, [c_void_p]),
     "ishap_unet_num_params": (C.c_int, [c_void_p]),
@@ -191,9 +191,9 @@ def lib():
             fn.argtypes = args
         # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run;
         # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats;
-        # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run
-        if l.ishap_version() < 9:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 9): rebuild with `python -m ishapediting_amd.build`")
+        # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run; 10: ishap_group_norm32_plan
+        if l.ishap_version() < 10:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 10): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -39,20 +39,16 @@ static int dgrad_op(Exec& e, const ConvW& c, const Tensor& dy, Tensor& dx_out, i
   return conv_op(e, k);
 }
 
-// group-local input gradient of act(film(GN(x))) on a small map; `up` may still be pending (norm_local.hip)
+// group-local input gradient of act(film(GN(x))) on a small map; the upstream gradient `up` (g.g) may still be pending (norm_local.hip)
 static int gn_bwd_local_op(Exec& e, const GnBwdArgs& g, Tensor& up) {
-  GnBwdLocalArgs a;
-  a.g = up.p; a.slab = up.pend; a.x = g.x; a.add = g.add; a.add2 = g.add2; a.dx = g.dx; a.dx2 = g.dx2; a.csplit = g.csplit;
-  a.stats = g.stats; a.gamma = g.gamma; a.beta = g.beta; a.emb = g.emb; a.emb_ld = g.emb_ld;
-  a.N = g.N; a.H = g.H; a.W = g.W; a.C = g.C; a.film = g.film; a.act = g.act; a.gmode = g.gmode;
+  const SlabSrc slab = up.pend;
+  up.pend = SlabSrc{};
   long long* rec = nullptr;
   ISHAP_SALLOC(rec, e, (size_t)g.N * 32 * GN_REC_STRIDE);       // zeroed with the rest of the statistics arena
-  a.rec = exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr;     // see gn_local_op
-  up.pend = SlabSrc{};
   if (e.dry) return 0;
-  return gn_bwd_local_launch(a, e.s);
+  return gn_bwd_local_launch(gn_bwd_local_fill(g, slab, exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr), e.s);   // see gn_local_op
 }
-static bool local_gn_bwd(const GnBwdArgs& g) { return small_map(g.H * g.W) && gn_bwd_local_fits(g.H * g.W, g.C, g.gmode); }
+static bool local_gn_bwd(const GnBwdArgs& g) { return gn_route(g.H * g.W, g.C, g.gmode, true) == GnRoute::local; }
 
 // The input gradient of a convolution `c` that reads act(film(GN(x))), in two parts; `g` describes the GroupNorm (x, stats,
 // weights, FiLM row, shape, gmode).  The route is a function of g's shape alone, so both parts (and a dry run) take the same one.

@@ -67,6 +67,18 @@ int ishap_cu_count();                 // compute units of the current device (ca
 bool ishap_rendezvous_begin(const void* owner, hipStream_t s);   // true: this sequence may use in-launch rendezvous
 void ishap_rendezvous_end(const void* owner, hipStream_t s, bool granted);
 bool ishap_rendezvous_contended(const void* owner, hipStream_t s);   // reads and clears "someone else asked while I held the device"   // closes the sequence (records its event on s)
+// RAII around a launch sequence: asks for the tenancy at construction (a dry run, which launches nothing, is "granted" without
+// asking; a sequence with want = false launches no rendezvous grid and does not ask), closes it (event on the stream) at scope exit
+struct TenancyScope {
+  const void* owner; hipStream_t s; bool granted;
+  TenancyScope(const void* o, hipStream_t st, bool dry, bool want = true)
+      : owner(o), s(st), granted(dry ? true : want && ishap_rendezvous_begin(o, st)), dry_(dry) {}
+  ~TenancyScope() { if (!dry_) ishap_rendezvous_end(owner, s, granted); }
+  TenancyScope(const TenancyScope&) = delete;
+  TenancyScope& operator=(const TenancyScope&) = delete;
+ private:
+  bool dry_;
+};
 
 #define ISHAP_TRY(expr)        \
   do {                         \

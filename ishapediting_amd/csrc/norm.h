@@ -35,7 +35,24 @@ struct GnApplyArgs {
   int csplit = 0;
   int main_blocks = 0;           // set by the launcher: the grid size (a preloaded scalar in the kernel)
 };
-int gn_apply_launch(const GnApplyArgs& a, hipStream_t s);
+// What a full-map launcher would enqueue (its apply kernel): filled INSTEAD of launching when passed to one -- the CPU view of the
+// plan, ishap_group_norm32_plan
+struct GnLaunchInfo {
+  int grid_x = 0, threads = 256;
+  std::string kernel;              // name with template arguments
+};
+// Grid of the full-map apply kernels (forward and backward): one thread per 8-channel vector, at most `cap` blocks (fewer, fatter
+// blocks amortise the finalise prologue), and a thread count that is a multiple of CV (a thread owns one 8-channel vector for all
+// its pixels): blocks = a multiple of CV / gcd(CV, 256)
+static inline int gn_apply_blocks(long long total, int CV, int cap) {
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > cap) blocks = cap;
+  int gcd = CV, r256 = 256;
+  while (r256) { const int t = gcd % r256; gcd = r256; r256 = t; }
+  const int unit = CV / gcd;
+  return blocks < unit ? unit : blocks / unit * unit;
+}
+int gn_apply_launch(const GnApplyArgs& a, hipStream_t s, GnLaunchInfo* info = nullptr);
 
 // ---- backward of  y = act(film(gn(x)))  w.r.t. x (no parameter gradients: the path never needs them) ----
 // g is the gradient arriving at y (possibly at another resolution, see gmode); result
@@ -60,7 +77,15 @@ struct GnBwdArgs {
   int sums_ready = 0;             // csums were already accumulated by the producing implicit-GEMM epilogue: apply pass only
   int main_blocks = 0;
 };
-int gn_backward_launch(const GnBwdArgs& a, hipStream_t s);
+int gn_backward_launch(const GnBwdArgs& a, hipStream_t s, GnLaunchInfo* info = nullptr);
+
+// ---- which route a GroupNorm pass takes (norm.hip): the executor's forward and backward ops and route 0 of the stand-alone calls ----
+// small maps (<= 32 x 32): GroupNorm passes run group-local (norm_local.hip), producers gather no statistics.
+// ISHAP_LOCAL_GN=0: no map is small -- the two-pass route everywhere (A/B); the 64x64 maps group-local as well measured slower (round 5)
+bool small_map(int HW);
+enum class GnRoute { full_map, local };
+// local: a small map whose group fits the LDS staging of the pass (the backward stages fp32 when gmode != GB_SAME)
+GnRoute gn_route(int HW, int C, int gmode, bool backward);
 
 // ---------------------------------------------------------------------------------------------------------------
 // Group-local GroupNorm kernels (norm_local.hip) for maps of at most 32 x 32 pixels: one workgroup owns one
@@ -98,7 +123,9 @@ struct GnLocalArgs {
   int spin_limit = GN_SPIN_LIMIT;
 };
 bool gn_local_fits(int HW, int C);              // LDS budget of the forward / backward staging
-int gn_local_parts(int N, int HW, int C);       // workgroups per (image, group) the launcher picks when a rendezvous record is given
+// the kernel arguments of the pass `g` describes (x / x2 / csplit / xcopy: a lazy skip concatenation, as for the full-map kernel) with
+// source A possibly still pending in `slab`; rec: zeroed rendezvous record or null
+GnLocalArgs gn_local_fill(const GnApplyArgs& g, const SlabSrc& slab, unsigned long long* rec);
 int gn_local_launch(const GnLocalArgs& a, hipStream_t s);
 
 struct GnBwdLocalArgs {
@@ -123,4 +150,31 @@ struct GnBwdLocalArgs {
   int spin_limit = GN_SPIN_LIMIT;
 };
 bool gn_bwd_local_fits(int HW, int C, int gmode);
+// the kernel arguments of the pass `g` describes, its upstream gradient g.g possibly still pending in `slab`; rec as above
+GnBwdLocalArgs gn_bwd_local_fill(const GnBwdArgs& g, const SlabSrc& slab, unsigned long long* rec);
 int gn_bwd_local_launch(const GnBwdLocalArgs& a, hipStream_t s);
+
+// ---- what one group-local launch looks like, forward or backward: planned in ONE place (norm_local.hip gn_local_plan; no HIP
+// runtime call -- ishap_cu_count() answers 256 without a device), read by the two launchers and by ishap_group_norm32_plan ----
+struct GnLocalShape {
+  int N = 1, H = 0, W = 0, C = 0;
+  bool backward = false;
+  bool pending = false;            // the input (forward) / the upstream gradient (backward) is split-K slices
+  bool have_rec = false;           // a rendezvous record is given: several workgroups per (image, group) allowed
+  int film = 0, act = 1;
+  int pool = 0;                    // forward only
+  int gmode = GB_SAME;             // backward only
+};
+struct GnLocalPlan {
+  int parts = 1;                   // workgroups per (image, group): grid = (32 * parts, N)
+  int vec = 1;                     // channels per lane and access: template argument VEC
+  int threads = 256;
+  int lds_bytes = 0;               // dynamic LDS: the scratch doubles + this part's staged values
+  int xcd = 0;                     // 0: parts dealt consecutively; 1: XCD-local dealing + local record copy; 2: also pre-touch the copy
+  bool backward = false;
+  bool film = false, act = false;  // template arguments FILM, ACT
+  bool pool = false;               // forward: POOL
+  bool stage32 = false;            // backward: STAGE32
+};
+GnLocalPlan gn_local_plan(const GnLocalShape& q);
+std::string gn_local_kernel_name(const GnLocalPlan& p);

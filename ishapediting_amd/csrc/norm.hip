@@ -277,28 +277,37 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(int h_main_blocks, int h_
   }
 }
 
-int gn_apply_launch(const GnApplyArgs& a, hipStream_t s) {
+bool small_map(int HW) {
+  static const int on = ishap_switch("ISHAP_LOCAL_GN", 1);
+  return on && HW <= 1024;
+}
+GnRoute gn_route(int HW, int C, int gmode, bool backward) {
+  const bool fits = backward ? gn_bwd_local_fits(HW, C, gmode) : gn_local_fits(HW, C);
+  return small_map(HW) && fits ? GnRoute::local : GnRoute::full_map;
+}
+
+int gn_apply_launch(const GnApplyArgs& a, hipStream_t s, GnLaunchInfo* info) {
   ISHAP_REQUIRE(!a.x2 || (a.sums && a.sums2 && a.xcopy && !a.pool && !a.split && a.csplit % 8 == 0 && a.csplit > 0 && a.csplit < a.C),
                 "two-source GroupNorm: sums of both halves, a copy target, plain variant");
   const int HWo = a.pool ? (a.H / 2) * (a.W / 2) : a.H * a.W;
-  long long total = (long long)a.N * HWo * (a.C / 8);
-  int blocks = (int)((total + 255) / 256);
   constexpr int cap_sums = 1024;          // in-situ sweep, flat 512 .. 2048 (no result file kept; the cap is no longer read from the environment: not repeatable as is)
-  if (blocks > (a.sums ? cap_sums : 4096)) blocks = a.sums ? cap_sums : 4096;   // fewer, fatter blocks amortise the finalise prologue
-  // thread count = multiple of CV (a thread owns one 8-channel vector): blocks = multiple of CV / gcd(CV, 256)
-  const int CV = a.C / 8;
-  int gcd = CV, r256 = 256;
-  while (r256) { const int t = gcd % r256; gcd = r256; r256 = t; }
-  const int unit = CV / gcd;
-  blocks = blocks < unit ? unit : blocks / unit * unit;
   GnApplyArgs a2 = a;
-  a2.main_blocks = blocks;
-  dim3 g(blocks), b(256);
-  if (a.split) hipLaunchKernelGGL((gn_apply_kernel<false, true, false, true>), g, b, 0, s, a2.main_blocks, a2.C, a2.H, a2.W, a2.N, a2);
-  else if (a.pool) hipLaunchKernelGGL((gn_apply_kernel<false, true, true, false>), g, b, 0, s, a2.main_blocks, a2.C, a2.H, a2.W, a2.N, a2);
-  else if (a.film) hipLaunchKernelGGL((gn_apply_kernel<true, true, false, false>), g, b, 0, s, a2.main_blocks, a2.C, a2.H, a2.W, a2.N, a2);
-  else if (a.act) hipLaunchKernelGGL((gn_apply_kernel<false, true, false, false>), g, b, 0, s, a2.main_blocks, a2.C, a2.H, a2.W, a2.N, a2);
-  else hipLaunchKernelGGL((gn_apply_kernel<false, false, false, false>), g, b, 0, s, a2.main_blocks, a2.C, a2.H, a2.W, a2.N, a2);
+  a2.main_blocks = gn_apply_blocks((long long)a.N * HWo * (a.C / 8), a.C / 8, a.sums ? cap_sums : 4096);
+  // the instances that exist, <FILM, ACT, POOL, SPLIT>: the head's hi/lo split, SiLU + pool, FiLM + SiLU, SiLU, plain
+  typedef void (*Kernel)(int, int, int, int, int, GnApplyArgs);
+  static constexpr struct { Kernel kern; const char* name; } form[5] = {
+      {gn_apply_kernel<false, true, false, true>, "gn_apply_kernel<false, true, false, true>"},
+      {gn_apply_kernel<false, true, true, false>, "gn_apply_kernel<false, true, true, false>"},
+      {gn_apply_kernel<true, true, false, false>, "gn_apply_kernel<true, true, false, false>"},
+      {gn_apply_kernel<false, true, false, false>, "gn_apply_kernel<false, true, false, false>"},
+      {gn_apply_kernel<false, false, false, false>, "gn_apply_kernel<false, false, false, false>"}};
+  const auto& f = form[a.split ? 0 : a.pool ? 1 : a.film ? 2 : a.act ? 3 : 4];
+  if (info) {
+    info->grid_x = a2.main_blocks;
+    info->kernel = f.name;
+    return 0;
+  }
+  hipLaunchKernelGGL(f.kern, dim3(a2.main_blocks), dim3(256), 0, s, a2.main_blocks, a2.C, a2.H, a2.W, a2.N, a2);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -11,6 +11,7 @@
 //   0  what the executor would pick for this map
 #include "../../include/ishap.h"
 #include "norm.h"
+#include <cstring>
 
 namespace {
 
@@ -52,10 +53,10 @@ __global__ void identity_fill_kernel(half_t* w, int C, int rows) {
   if (i < rows * C) w[i] = (i / C == i % C) ? (half_t)1.f : (half_t)0.f;
 }
 
+// route 0: what the executor picks for this map (gn_route; ISHAP_LOCAL_GN=0 included)
 int resolve_route(int route, int HW, int C, bool backward) {
   if (route != 0) return route;
-  const bool loc = HW <= 1024 && (backward ? gn_bwd_local_fits(HW, C, GB_SAME) : gn_local_fits(HW, C));
-  return loc ? 3 : 4;
+  return gn_route(HW, C, GB_SAME, backward) == GnRoute::local ? 3 : (backward ? 1 : 4);
 }
 
 }  // namespace
@@ -77,25 +78,19 @@ int ishap_group_norm32(const void* x_nhwc_f16, const float* gamma, const float* 
   const int HW = H * W;
   const Scratch sc = carve(scratch, N, HW, C);
   ISHAP_CHECK_HIP(hipMemsetAsync(scratch, 0, sc.zero_bytes, s));
-  const half_t* x = (const half_t*)x_nhwc_f16;
   route = resolve_route(route, HW, C, false);
+  GnApplyArgs g;
+  g.x = (const half_t*)x_nhwc_f16; g.out = (half_t*)y_nhwc_f16; g.gamma = gamma; g.beta = beta;
+  g.N = N; g.H = H; g.W = W; g.C = C; g.act = silu;
   if (route == 2 || route == 3) {
-    GnLocalArgs g;
-    g.xa = x; g.Ca = C; g.out = (half_t*)y_nhwc_f16; g.stats_out = stats; g.gamma = gamma; g.beta = beta;
-    g.N = N; g.H = H; g.W = W; g.C = C; g.film = 0; g.act = silu; g.pool = 0;
     // route 3 (several workgroups per group meeting inside the launch) needs the device's rendezvous tenancy (common.h);
     // while another context / stream of the process holds it the call degrades to one workgroup per group (route 2)
-    const bool granted = route == 3 && ishap_rendezvous_begin(nullptr, s);
-    g.rec = granted ? sc.rec : nullptr;
-    const int r = gn_local_launch(g, s);
-    ishap_rendezvous_end(nullptr, s, granted);
-    return r;
+    TenancyScope tenancy(nullptr, s, false, route == 3);
+    g.stats_out = stats;
+    return gn_local_launch(gn_local_fill(g, SlabSrc{}, tenancy.granted ? sc.rec : nullptr), s);
   }
-  GnApplyArgs g;
-  g.x = x; g.out = (half_t*)y_nhwc_f16; g.gamma = gamma; g.beta = beta;
-  g.N = N; g.H = H; g.W = W; g.C = C; g.act = silu;
   if (route == 1) {
-    ISHAP_TRY(gn_stats_launch(x, sc.partial, stats, N, HW, C, s));
+    ISHAP_TRY(gn_stats_launch(g.x, sc.partial, stats, N, HW, C, s));
     g.stats = stats;
   } else {
     // producer stand-in: copy = x * I through the implicit-GEMM kernel, whose epilogue gathers the per-channel sums
@@ -106,7 +101,7 @@ int ishap_group_norm32(const void* x_nhwc_f16, const float* gamma, const float* 
     hipLaunchKernelGGL(identity_fill_kernel, dim3((rows * C + 255) / 256), dim3(256), 0, s, sc.ident, C, rows);
     ISHAP_CHECK_HIP(hipGetLastError());
     IgemmArgs a;
-    a.X = x; a.Wt = sc.ident; a.out = sc.copy; a.M = N * HW; a.N = C; a.K = C; a.conv3 = 0; a.Cin = C;
+    a.X = g.x; a.Wt = sc.ident; a.out = sc.copy; a.M = N * HW; a.N = C; a.K = C; a.conv3 = 0; a.Cin = C;
     a.ldx = C; a.ldw = C; a.ldo = C; a.H = H; a.W = W; a.out_mode = IG_OUT_F16; a.ksplit = 1;
     a.stat_out = sc.csums;
     ISHAP_TRY(igemm_launch(a, s));
@@ -127,27 +122,62 @@ int ishap_group_norm32_backward(const void* g_nhwc_f16, const void* x_nhwc_f16, 
   const Scratch sc = carve(scratch, N, HW, C);
   ISHAP_CHECK_HIP(hipMemsetAsync(scratch, 0, sc.zero_bytes, s));
   route = resolve_route(route, HW, C, true);
-  if (route == 4) route = 1;
-  if (route == 2 || route == 3) {
-    GnBwdLocalArgs a;
-    a.g = (const half_t*)g_nhwc_f16; a.x = (const half_t*)x_nhwc_f16; a.dx = (half_t*)dx_nhwc_f16;
-    a.stats = stats; a.gamma = gamma; a.beta = beta; a.N = N; a.H = H; a.W = W; a.C = C; a.film = 0; a.act = silu;
-    a.gmode = GB_SAME;
-    const bool granted = route == 3 && ishap_rendezvous_begin(nullptr, s);
-    a.rec = granted ? sc.rec : nullptr;
-    const int r = gn_bwd_local_launch(a, s);
-    ishap_rendezvous_end(nullptr, s, granted);
-    return r;
-  }
   GnBwdArgs a;
   a.g = (const half_t*)g_nhwc_f16; a.x = (const half_t*)x_nhwc_f16; a.dx = (half_t*)dx_nhwc_f16;
   a.stats = stats; a.gamma = gamma; a.beta = beta; a.N = N; a.H = H; a.W = W; a.C = C; a.film = 0; a.act = silu;
-  a.gmode = GB_SAME; a.csums = sc.csums;
+  a.gmode = GB_SAME;
+  if (route == 2 || route == 3) {
+    TenancyScope tenancy(nullptr, s, false, route == 3);
+    return gn_bwd_local_launch(gn_bwd_local_fill(a, SlabSrc{}, tenancy.granted ? sc.rec : nullptr), s);
+  }
+  a.csums = sc.csums;
   return gn_backward_launch(a, s);
 }
 
-/* workgroups per (image, group) the group-local kernels use for this shape on the current device (tests assert that a
- * case really exercises the in-launch rendezvous) */
-int ishap_group_norm32_parts(int N, int HW, int C) { return gn_local_parts(N, HW, C); }
+/* CPU view of the plan (include/ishap.h): the route, kernel and launch geometry one GroupNorm pass of this shape gets */
+int ishap_group_norm32_plan(int N, int H, int W, int C, int backward, int pending, int film, int act, int pool, int gmode, int route,
+                            int* route_out, int* parts, int* vec, int* threads, int* grid_x, int* grid_y, int* lds_bytes,
+                            int* xcd, char* kernel, int kernel_cap) {
+  ISHAP_REQUIRE(N >= 1 && H >= 1 && W >= 1 && C >= 32 && C % 32 == 0, "GroupNorm32 dims");
+  ISHAP_REQUIRE(route >= 0 && route <= (backward ? 3 : 4), "route 0..4 (backward: 0..3)");
+  ISHAP_REQUIRE(gmode == GB_SAME || (backward && (gmode == GB_UNPOOL || gmode == GB_SUM4)), "gmode: a backward pass's GB_*");
+  ISHAP_REQUIRE(!pool || (!backward && !film && act && H % 2 == 0 && W % 2 == 0), "pool variant: forward, SiLU, no FiLM");
+  ISHAP_REQUIRE(!film || act, "FiLM is followed by SiLU");
+  const int HW = H * W;
+  if (route == 0) route = gn_route(HW, C, gmode, backward != 0) == GnRoute::local ? 3 : (backward ? 1 : 4);
+  GnLocalPlan p;
+  GnLaunchInfo full;
+  const bool local = route == 2 || route == 3;
+  if (local) {
+    ISHAP_REQUIRE(backward ? gn_bwd_local_fits(HW, C, gmode) : gn_local_fits(HW, C), "group does not fit in LDS");
+    GnLocalShape q;
+    q.N = N; q.H = H; q.W = W; q.C = C; q.backward = backward != 0; q.pending = pending != 0; q.have_rec = route == 3;
+    q.film = film; q.act = act; q.pool = pool; q.gmode = gmode;
+    p = gn_local_plan(q);
+  } else if (backward) {
+    GnBwdArgs a;
+    a.N = N; a.H = H; a.W = W; a.C = C; a.film = film; a.act = act; a.gmode = gmode;
+    ISHAP_TRY(gn_backward_launch(a, nullptr, &full));
+  } else {
+    static const long long sums = 0;               // the launcher only asks whether the producer gathered the sums (route 4)
+    GnApplyArgs a;
+    a.N = N; a.H = H; a.W = W; a.C = C; a.film = film; a.act = act; a.pool = pool; a.sums = route == 4 ? &sums : nullptr;
+    ISHAP_TRY(gn_apply_launch(a, nullptr, &full));
+  }
+  const std::string name = local ? gn_local_kernel_name(p) : full.kernel;
+  if (route_out) *route_out = route;
+  if (parts) *parts = local ? p.parts : 0;         // 0: not a group-local launch
+  if (vec) *vec = local ? p.vec : 8;
+  if (threads) *threads = local ? p.threads : full.threads;
+  if (grid_x) *grid_x = local ? 32 * p.parts : full.grid_x;
+  if (grid_y) *grid_y = local ? N : 1;
+  if (lds_bytes) *lds_bytes = local ? p.lds_bytes : 0;
+  if (xcd) *xcd = local ? p.xcd : 0;
+  if (kernel) {
+    if ((int)name.size() + 1 > kernel_cap) return -2;
+    memcpy(kernel, name.c_str(), name.size() + 1);
+  }
+  return 0;
+}
 
 }  // extern "C"

@@ -187,34 +187,31 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const long long* h_cs
   }
 }
 
-int gn_backward_launch(const GnBwdArgs& a, hipStream_t s) {
+int gn_backward_launch(const GnBwdArgs& a, hipStream_t s, GnLaunchInfo* info) {
   ISHAP_REQUIRE(a.C % 32 == 0 && a.C / 8 <= 256, "GroupNorm channels");
   ISHAP_REQUIRE(a.csplit == 0 || (a.dx2 && a.csplit % 8 == 0 && a.csplit < a.C), "split output");
   const int HW = a.H * a.W;
   const int rpb = gn_rows_per_block(HW), nblk = HW / rpb, CV = a.C / 8;
   const int rpi = 256 / CV > 0 ? 256 / CV : 1;
   const size_t smem = (size_t)rpi * a.C * 2 * sizeof(float);
-  long long total = (long long)a.N * HW * CV;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  int gcd = CV, r256 = 256;                      // apply kernel: thread count = multiple of CV
-  while (r256) { const int t = gcd % r256; gcd = r256; r256 = t; }
-  const int unit = CV / gcd;
-  blocks = blocks < unit ? unit : blocks / unit * unit;
   GnBwdArgs a2 = a;
-  a2.main_blocks = blocks;
-  const int grid_apply = blocks;
-#define GB_LAUNCH(F, A)                                                                                             \
-  do {                                                                                                              \
-    if (!a.sums_ready)                                                                                              \
-      hipLaunchKernelGGL((gn_bwd_partial_kernel<F, A>), dim3(nblk, a.N), dim3(256), smem, s, a, rpb);               \
-    hipLaunchKernelGGL((gn_bwd_apply_kernel<F, A>), dim3(grid_apply), dim3(256), 0, s, (const long long*)a2.csums,   \
-                       a2.main_blocks, a2.C, a2.H, a2.W, a2.N, a2);                                               \
-  } while (0)
-  if (a.film) GB_LAUNCH(true, true);
-  else if (a.act) GB_LAUNCH(false, true);
-  else GB_LAUNCH(false, false);
-#undef GB_LAUNCH
+  a2.main_blocks = gn_apply_blocks((long long)a.N * HW * CV, CV, 1024);
+  // the instances that exist, <FILM, ACT>: FiLM + SiLU, SiLU, plain
+  typedef void (*Partial)(GnBwdArgs, int);
+  typedef void (*Apply)(const long long*, int, int, int, int, int, GnBwdArgs);
+  static constexpr struct { Partial partial; Apply apply; const char* name; } form[3] = {
+      {gn_bwd_partial_kernel<true, true>, gn_bwd_apply_kernel<true, true>, "gn_bwd_apply_kernel<true, true>"},
+      {gn_bwd_partial_kernel<false, true>, gn_bwd_apply_kernel<false, true>, "gn_bwd_apply_kernel<false, true>"},
+      {gn_bwd_partial_kernel<false, false>, gn_bwd_apply_kernel<false, false>, "gn_bwd_apply_kernel<false, false>"}};
+  const auto& f = form[a.film ? 0 : a.act ? 1 : 2];
+  if (info) {
+    info->grid_x = a2.main_blocks;
+    info->kernel = f.name;
+    return 0;
+  }
+  if (!a.sums_ready) hipLaunchKernelGGL(f.partial, dim3(nblk, a.N), dim3(256), smem, s, a, rpb);
+  hipLaunchKernelGGL(f.apply, dim3(a2.main_blocks), dim3(256), 0, s, (const long long*)a2.csums, a2.main_blocks, a2.C, a2.H,
+                     a2.W, a2.N, a2);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }

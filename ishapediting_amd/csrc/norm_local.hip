@@ -688,11 +688,33 @@ int xcd_deal(int parts) {          // 0: off; 1: XCD-local dealing + local copy;
   static const int on = ishap_switch("ISHAP_GN_XCD", 1);      // in situ: 1 and 2 both -0.4 % against 0, no difference between them (profiles/round5_ab_gn_xcd_local.txt)
   return parts > 1 ? on : 0;
 }
+// (parts, xcd) as the kernels' leading scalar h_parts: parts itself, or -(parts [+ 64]) for the XCD-local dealing [+ the pre-touch of
+// the local copy]; the kernels' prologue takes it apart again
+int h_parts_of(const GnLocalPlan& p) { return p.xcd ? -(p.parts + (p.xcd == 2 ? 64 : 0)) : p.parts; }
 
 template <typename K>
-int set_lds(K kern, size_t smem) {
-  (void)smem;
+int set_lds(K kern) {
   return ishap_set_max_lds((const void*)kern, (int)LOCAL_LDS_CAP + GN_SCRATCH_BYTES);
+}
+
+// The instances that exist, by (VEC, variant).  Forward variants: SiLU + pool, FiLM + SiLU, SiLU, plain; backward: the last three,
+// with fp32 staging, then with fp16 staging.
+typedef void (*GnLocalKernel)(int, int, int, int, GnLocalArgs);
+typedef void (*GnBwdLocalKernel)(int, int, int, GnBwdLocalArgs);
+template <int V>
+constexpr GnLocalKernel kFwd[4] = {gn_local_kernel<V, false, true, true>, gn_local_kernel<V, true, true, false>,
+                                   gn_local_kernel<V, false, true, false>, gn_local_kernel<V, false, false, false>};
+template <int V>
+constexpr GnBwdLocalKernel kBwd[6] = {gn_bwd_local_kernel<V, true, true, true>,   gn_bwd_local_kernel<V, false, true, true>,
+                                      gn_bwd_local_kernel<V, false, false, true>, gn_bwd_local_kernel<V, true, true, false>,
+                                      gn_bwd_local_kernel<V, false, true, false>, gn_bwd_local_kernel<V, false, false, false>};
+GnLocalKernel fwd_kernel(const GnLocalPlan& p) {
+  const GnLocalKernel* row = p.vec == 8 ? kFwd<8> : p.vec == 4 ? kFwd<4> : p.vec == 2 ? kFwd<2> : kFwd<1>;
+  return row[p.pool ? 0 : p.film ? 1 : p.act ? 2 : 3];
+}
+GnBwdLocalKernel bwd_kernel(const GnLocalPlan& p) {
+  const GnBwdLocalKernel* row = p.vec == 8 ? kBwd<8> : p.vec == 4 ? kBwd<4> : p.vec == 2 ? kBwd<2> : kBwd<1>;
+  return row[(p.stage32 ? 0 : 3) + (p.film ? 0 : p.act ? 1 : 2)];
 }
 
 }  // namespace
@@ -700,9 +722,51 @@ int set_lds(K kern, size_t smem) {
 bool gn_local_fits(int HW, int C) {
   return C % 32 == 0 && (size_t)HW * (C / 32) * sizeof(half_t) <= LOCAL_LDS_CAP;
 }
-int gn_local_parts(int N, int HW, int C) { return C % 32 ? 1 : pick_parts(N, HW, C / 32, 1, true); }
 bool gn_bwd_local_fits(int HW, int C, int gmode) {
   return C % 32 == 0 && (size_t)HW * (C / 32) * (gmode != GB_SAME ? sizeof(float) : sizeof(half_t)) <= LOCAL_LDS_CAP;
+}
+
+GnLocalPlan gn_local_plan(const GnLocalShape& q) {
+  GnLocalPlan p;
+  const int HW = q.H * q.W, cpg = q.C / 32;
+  p.backward = q.backward;
+  // the variants that exist: the pooled form and FiLM carry SiLU (the launchers require it of their callers)
+  p.pool = !q.backward && q.pool;
+  p.film = q.film && !p.pool;
+  p.act = q.act || p.film || p.pool;
+  p.stage32 = q.backward && q.gmode != GB_SAME;      // 0.25 * fp16 and sums of four fp16 values are kept in fp32 between the passes
+  p.parts = pick_parts(q.N, HW, cpg, p.pool ? 2 * q.W : 1, q.have_rec);
+  p.xcd = xcd_deal(p.parts);
+  const int PP = HW / p.parts;
+  p.vec = pick_vec(cpg, PP, q.pending);
+  p.threads = pick_threads(PP * (cpg / p.vec));
+  p.lds_bytes = GN_SCRATCH_BYTES + (int)((size_t)PP * cpg * (p.stage32 ? sizeof(float) : sizeof(half_t)));
+  return p;
+}
+
+std::string gn_local_kernel_name(const GnLocalPlan& p) {
+  auto tf = [](bool b) { return b ? "true" : "false"; };
+  return igemm_kernel_name(p.backward ? "gn_bwd_local_kernel<%d, %s, %s, %s>" : "gn_local_kernel<%d, %s, %s, %s>", p.vec, tf(p.film),
+                           tf(p.act), tf(p.backward ? p.stage32 : p.pool));
+}
+
+GnLocalArgs gn_local_fill(const GnApplyArgs& g, const SlabSrc& slab, unsigned long long* rec) {
+  GnLocalArgs a;
+  a.xa = g.x; a.slab = slab; a.ya = slab.pending() ? const_cast<half_t*>(g.x) : nullptr;
+  a.Ca = g.csplit ? g.csplit : g.C; a.xb = g.x2; a.xcopy = g.xcopy;
+  a.out = g.out; a.xpool = g.xpool; a.stats_out = g.stats_out; a.gamma = g.gamma; a.beta = g.beta; a.emb = g.emb; a.emb_ld = g.emb_ld;
+  a.N = g.N; a.H = g.H; a.W = g.W; a.C = g.C; a.film = g.film; a.act = g.act; a.pool = g.pool;
+  a.rec = rec;
+  return a;
+}
+
+GnBwdLocalArgs gn_bwd_local_fill(const GnBwdArgs& g, const SlabSrc& slab, unsigned long long* rec) {
+  GnBwdLocalArgs a;
+  a.g = g.g; a.slab = slab; a.x = g.x; a.add = g.add; a.add2 = g.add2; a.dx = g.dx; a.dx2 = g.dx2; a.csplit = g.csplit;
+  a.stats = g.stats; a.gamma = g.gamma; a.beta = g.beta; a.emb = g.emb; a.emb_ld = g.emb_ld;
+  a.N = g.N; a.H = g.H; a.W = g.W; a.C = g.C; a.film = g.film; a.act = g.act; a.gmode = g.gmode;
+  a.rec = rec;
+  return a;
 }
 
 int gn_local_launch(const GnLocalArgs& a, hipStream_t s) {
@@ -710,41 +774,21 @@ int gn_local_launch(const GnLocalArgs& a, hipStream_t s) {
   ISHAP_REQUIRE((a.Ca == a.C) == (a.xb == nullptr), "second source exactly when the input is a concatenation");
   ISHAP_REQUIRE(a.slab.pending() || a.xa, "source A: a tensor or pending slices");
   ISHAP_REQUIRE(!a.pool || (a.H % 2 == 0 && a.W % 2 == 0 && !a.film), "pool variant");
-  const int HW = a.H * a.W, cpg = a.C / 32;
-  ISHAP_REQUIRE(gn_local_fits(HW, a.C), "group does not fit in LDS");
+  ISHAP_REQUIRE(gn_local_fits(a.H * a.W, a.C), "group does not fit in LDS");
   GnLocalArgs b = a;
   b.spin_limit = spin_limit();
   b.status = ishap_status_word();
   ISHAP_REQUIRE(b.status != nullptr, "device status word");
-  b.parts = pick_parts(a.N, HW, cpg, a.pool ? 2 * a.W : 1, a.rec != nullptr);
-  const int PP = HW / b.parts;
-  const int VEC = pick_vec(cpg, PP, a.slab.pending());
-  const int T = pick_threads(PP * (cpg / VEC));
-  const size_t smem = GN_SCRATCH_BYTES + (size_t)PP * cpg * sizeof(half_t);
-  dim3 grid(32 * b.parts, a.N), blk(T);
-#define GL_LAUNCH(V, F, A, P)                                                            \
-  do {                                                                                   \
-    auto kern = gn_local_kernel<V, F, A, P>;                                             \
-    ISHAP_TRY(set_lds(kern, smem));                                                      \
-    hipLaunchKernelGGL(kern, grid, blk, smem, s, xcd_deal(b.parts) ? -(b.parts + (xcd_deal(b.parts) == 2 ? 64 : 0)) : b.parts, b.C, b.H * b.W, b.Ca, b);      \
-  } while (0)
-#define GL_VARIANT(V)                                                                    \
-  do {                                                                                   \
-    if (a.pool) GL_LAUNCH(V, false, true, true);                                         \
-    else if (a.film) GL_LAUNCH(V, true, true, false);                                    \
-    else if (a.act) GL_LAUNCH(V, false, true, false);                                    \
-    else GL_LAUNCH(V, false, false, false);                                              \
-  } while (0)
   ISHAP_REQUIRE(!a.pool || a.act, "the pooled variant carries SiLU (ResBlock in_layers)");
   ISHAP_REQUIRE(!a.film || a.act, "FiLM is followed by SiLU (ResBlock out_layers)");
-  switch (VEC) {
-    case 8: GL_VARIANT(8); break;
-    case 4: GL_VARIANT(4); break;
-    case 2: GL_VARIANT(2); break;
-    default: GL_VARIANT(1); break;
-  }
-#undef GL_VARIANT
-#undef GL_LAUNCH
+  GnLocalShape q;
+  q.N = a.N; q.H = a.H; q.W = a.W; q.C = a.C; q.pending = a.slab.pending(); q.have_rec = a.rec != nullptr;
+  q.film = a.film; q.act = a.act; q.pool = a.pool;
+  const GnLocalPlan p = gn_local_plan(q);
+  b.parts = p.parts;
+  const GnLocalKernel kern = fwd_kernel(p);
+  ISHAP_TRY(set_lds(kern));
+  hipLaunchKernelGGL(kern, dim3(32 * p.parts, a.N), dim3(p.threads), (size_t)p.lds_bytes, s, h_parts_of(p), b.C, b.H * b.W, b.Ca, b);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -754,45 +798,20 @@ int gn_bwd_local_launch(const GnBwdLocalArgs& a, hipStream_t s) {
   ISHAP_REQUIRE(a.csplit == 0 || (a.dx2 && a.csplit % 32 == 0 && a.csplit < a.C), "split output");
   ISHAP_REQUIRE(a.slab.pending() || a.g, "upstream gradient: a tensor or pending slices");
   ISHAP_REQUIRE(!a.film || a.act, "FiLM is followed by SiLU");
-  const int HW = a.H * a.W, cpg = a.C / 32;
-  const bool s32 = a.gmode != GB_SAME;      // 0.25 * fp16 and sums of four fp16 values are kept in fp32 between the passes
   GnBwdLocalArgs b = a;
   b.spin_limit = spin_limit();
   b.status = ishap_status_word();
   ISHAP_REQUIRE(b.status != nullptr, "device status word");
-  b.parts = pick_parts(a.N, HW, cpg, 1, a.rec != nullptr);
-  const int PP = HW / b.parts;
-  const size_t smem = GN_SCRATCH_BYTES + (size_t)PP * cpg * (s32 ? sizeof(float) : sizeof(half_t));
+  GnLocalShape q;
+  q.N = a.N; q.H = a.H; q.W = a.W; q.C = a.C; q.backward = true; q.pending = a.slab.pending(); q.have_rec = a.rec != nullptr;
+  q.film = a.film; q.act = a.act; q.gmode = a.gmode;
+  const GnLocalPlan p = gn_local_plan(q);
+  b.parts = p.parts;
+  const size_t smem = (size_t)p.lds_bytes;
   ISHAP_REQUIRE(smem <= LOCAL_LDS_CAP + GN_SCRATCH_BYTES, "group does not fit in LDS");
-  const int VEC = pick_vec(cpg, PP, a.slab.pending());
-  const int T = pick_threads(PP * (cpg / VEC));
-  dim3 grid(32 * b.parts, a.N), blk(T);
-#define GB_LAUNCH(V, F, A, S32)                                                          \
-  do {                                                                                   \
-    auto kern = gn_bwd_local_kernel<V, F, A, S32>;                                       \
-    ISHAP_TRY(set_lds(kern, smem));                                                      \
-    hipLaunchKernelGGL(kern, grid, blk, smem, s, xcd_deal(b.parts) ? -(b.parts + (xcd_deal(b.parts) == 2 ? 64 : 0)) : b.parts, b.C, b.H * b.W, b);            \
-  } while (0)
-#define GB_VARIANT(V)                                                                    \
-  do {                                                                                   \
-    if (s32) {                                                                           \
-      if (a.film) GB_LAUNCH(V, true, true, true);                                        \
-      else if (a.act) GB_LAUNCH(V, false, true, true);                                   \
-      else GB_LAUNCH(V, false, false, true);                                             \
-    } else {                                                                             \
-      if (a.film) GB_LAUNCH(V, true, true, false);                                       \
-      else if (a.act) GB_LAUNCH(V, false, true, false);                                  \
-      else GB_LAUNCH(V, false, false, false);                                            \
-    }                                                                                    \
-  } while (0)
-  switch (VEC) {
-    case 8: GB_VARIANT(8); break;
-    case 4: GB_VARIANT(4); break;
-    case 2: GB_VARIANT(2); break;
-    default: GB_VARIANT(1); break;
-  }
-#undef GB_VARIANT
-#undef GB_LAUNCH
+  const GnBwdLocalKernel kern = bwd_kernel(p);
+  ISHAP_TRY(set_lds(kern));
+  hipLaunchKernelGGL(kern, dim3(32 * p.parts, a.N), dim3(p.threads), smem, s, h_parts_of(p), b.C, b.H * b.W, b);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -190,16 +190,6 @@ struct Exec {
   int chunk_tiles = 0;          // > 0: the dx-reuse convolutions of this sequence run as launches of at most that many tiles (the overlapped forward tail)
   bool tenant = true;           // this sequence holds the device's rendezvous tenancy (common.h ishap_rendezvous_begin)
 };
-// RAII around a launch sequence: asks for the tenancy at construction, closes it (event on the stream) at scope exit
-struct TenancyScope {
-  const void* owner; hipStream_t s; bool granted;
-  TenancyScope(const void* o, hipStream_t st, bool dry) : owner(o), s(st), granted(dry ? true : ishap_rendezvous_begin(o, st)), dry_(dry) {}
-  ~TenancyScope() { if (!dry_) ishap_rendezvous_end(owner, s, granted); }
-  TenancyScope(const TenancyScope&) = delete;
-  TenancyScope& operator=(const TenancyScope&) = delete;
- private:
-  bool dry_;
-};
 // Arena allocation that FAILS THE CALL when the arena sized by the create-time dry runs is exceeded (a null pointer
 // must never reach a kernel): ISHAP_ALLOC(ptr, e, count) inside any function returning an int status.
 template <typename T>
@@ -219,11 +209,8 @@ static inline int aalloc_checked(Exec& e, size_t count, T** out) {
 int conv_op(Exec& e, const ConvLaunch& c);
 // the launch y = w (*) x with w's bias, gathering the sums y carries; call sites add what else they use
 ConvLaunch conv_launch(const Tensor& x, const ConvW& w, const Tensor& y);
-// small maps (<= 32 x 32): GroupNorm passes run group-local (norm_local.hip), producers gather no statistics
 int unet_join_tail(ishap_unet* u, hipStream_t s);
-bool small_map(int HW);
 bool exec_is_solo(const Exec& e);   // no other stream of this context has work in flight (in-launch rendezvous allowed)
-bool local_gn(int HW, int C);
 int slab_materialize(Exec& e, Tensor& t);    // add up a pending tensor with the stand-alone reduce kernel (consumers that cannot)
 long long* salloc(Exec& e, size_t count);   // from the stats arena
 int gn_stats_op(Exec& e, const Tensor& x, float* stats);

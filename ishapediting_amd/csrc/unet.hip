@@ -262,12 +262,7 @@ bool exec_is_solo(const Exec& e) {
   return e.dry || (e.tenant && (e.u->side == nullptr || e.s != e.u->side));
 }
 
-bool small_map(int HW) {
-  // ISHAP_LOCAL_GN=0: the two-pass GroupNorm route everywhere (A/B); the 64x64 maps group-local as well measured slower (round 5)
-  static const int on = ishap_switch("ISHAP_LOCAL_GN", 1);
-  return on && HW <= 1024;
-}
-bool local_gn(int HW, int C) { return small_map(HW) && gn_local_fits(HW, C); }
+static bool local_gn(int HW, int C) { return gn_route(HW, C, GB_SAME, false) == GnRoute::local; }
 
 ConvLaunch conv_launch(const Tensor& x, const ConvW& w, const Tensor& y) {
   ConvLaunch c;
@@ -319,28 +314,18 @@ int gn_stats_op(Exec& e, const Tensor& x, float* stats) {
   return gn_stats_launch(x.p, e.gn_partial ? e.gn_partial : e.u->gn_partial, stats, x.N, x.H * x.W, x.C, e.s);
 }
 
-// GroupNorm (+FiLM) (+SiLU) (+2x2 pool) of `x` into `out` on a small map: one group-local launch that also adds up `x`
-// when it is still pending (and its first half when x is a lazy skip concatenation), see norm_local.hip
-static int gn_local_op(Exec& e, Tensor& x, const NormW& nw, half_t* out, half_t* xpool, float* stats_out, const float* emb,
-                       int emb_ld, int film, int act, int pool) {
-  GnLocalArgs g;
-  if (x.cat_a) {
-    g.xa = x.cat_a; g.slab = x.cat_pend; g.ya = x.cat_pend.pending() ? const_cast<half_t*>(x.cat_a) : nullptr;
-    g.Ca = x.cat_ca; g.xb = x.cat_b; g.xcopy = x.p;
-  } else {
-    g.xa = x.p; g.slab = x.pend; g.ya = x.pend.pending() ? x.p : nullptr; g.Ca = x.C;
-  }
+// The GroupNorm pass `g` on a small map: one group-local launch that also adds up `x` when it is still pending (and its first
+// half when x is a lazy skip concatenation), see norm_local.hip
+static int gn_local_op(Exec& e, Tensor& x, const GnApplyArgs& g) {
+  const SlabSrc slab = x.cat_a ? x.cat_pend : x.pend;
   x.pend = SlabSrc{};
   x.cat_pend = SlabSrc{};
-  g.out = out; g.xpool = xpool; g.stats_out = stats_out; g.gamma = nw.gamma; g.beta = nw.beta; g.emb = emb; g.emb_ld = emb_ld;
-  g.N = x.N; g.H = x.H; g.W = x.W; g.C = x.C; g.film = film; g.act = act; g.pool = pool;
   long long* rec = nullptr;
   ISHAP_SALLOC(rec, e, (size_t)x.N * 32 * GN_REC_STRIDE);       // zeroed with the statistics arena at the start of the forward
+  if (e.dry) return 0;
   // several workgroups per group rendezvous inside the launch: only while this launch sequence is the context's only one
   // (beside an overlapped forward tail two half-resident rendezvous grids could wait on each other's compute units)
-  g.rec = exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr;
-  if (e.dry) return 0;
-  return gn_local_launch(g, e.s);
+  return gn_local_launch(gn_local_fill(g, slab, exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr), e.s);
 }
 
 // out = act(film(GN(x))) (+ 2x2 pool with the pooled raw input in xpool | the head's hi/lo split); `stats` receives (mean, rstd)
@@ -354,19 +339,21 @@ static int gn_local_op(Exec& e, Tensor& x, const NormW& nw, half_t* out, half_t*
 // gn_stats_op's scratch bound are taken in dry runs too.  The tenancy (exec_is_solo) only picks launch forms inside gn_local_op.
 static int gn_forward_op(Exec& e, Tensor& x, const NormW& nw, half_t* out, half_t* xpool, float* stats, const float* emb,
                          int film, int act, int pool, int split = 0) {
-  const int emb_ld = emb ? e.u->film_cur_ld : 0;
-  if (!split && local_gn(x.H * x.W, x.C)) return gn_local_op(e, x, nw, out, xpool, stats, emb, emb_ld, film, act, pool);
   const bool lazy_cat = x.cat_a != nullptr;
+  GnApplyArgs g;
+  g.x = x.p; g.out = out; g.xpool = xpool; g.stats_out = stats;
+  g.gamma = nw.gamma; g.beta = nw.beta; g.emb = emb; g.emb_ld = emb ? e.u->film_cur_ld : 0;
+  g.N = x.N; g.H = x.H; g.W = x.W; g.C = x.C; g.film = film; g.act = act; g.pool = pool; g.split = split;
+  if (lazy_cat) { g.x = x.cat_a; g.x2 = x.cat_b; g.csplit = x.cat_ca; g.xcopy = x.p; }
+  if (!split && local_gn(x.H * x.W, x.C)) return gn_local_op(e, x, g);
   ISHAP_REQUIRE(!lazy_cat || (x.cat_sa && x.cat_sb), "a lazy concatenation on a large map carries the producers' sums");
   ISHAP_TRY(slab_materialize(e, x));
   const bool summed = x.sums || lazy_cat;
   if (!summed) ISHAP_TRY(gn_stats_op(e, x, stats));
   if (e.dry) return 0;
-  GnApplyArgs g;
-  g.x = x.p; g.out = out; g.xpool = xpool; g.stats = stats; g.sums = x.sums; g.stats_out = summed ? stats : nullptr;
-  g.gamma = nw.gamma; g.beta = nw.beta; g.emb = emb; g.emb_ld = emb_ld;
-  g.N = x.N; g.H = x.H; g.W = x.W; g.C = x.C; g.film = film; g.act = act; g.pool = pool; g.split = split;
-  if (lazy_cat) { g.x = x.cat_a; g.x2 = x.cat_b; g.sums = x.cat_sa; g.sums2 = x.cat_sb; g.csplit = x.cat_ca; g.xcopy = x.p; }
+  g.stats = stats; g.sums = x.sums;
+  if (lazy_cat) { g.sums = x.cat_sa; g.sums2 = x.cat_sb; }
+  if (!summed) g.stats_out = nullptr;
   return gn_apply_launch(g, e.s);
 }
 
@@ -742,13 +729,14 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 9; }   // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 10; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
                                         // 7: mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats)
                                         // 8: ARAP deformation (ishap_arap, ishap_arap_scratch_bytes, ishap_nearest_vertices)
                                         // 9: one attention launch through the ABI (ishap_attention_run, ishap_attention8_run)
+                                        // 10: ishap_group_norm32_plan replaces ishap_group_norm32_parts
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");

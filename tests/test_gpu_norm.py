@@ -83,7 +83,10 @@ def test_group_norm32_with_group_mean_1000x_its_spread(gold, route, silu):
     x, w, b = T(g["gn_x"]).float(), T(g["gn_w"]), T(g["gn_b"])
     want = g["gn_y_silu"] if silu else g["gn_y_plain"]
     if route == 3:
-        parts = _lib.lib().ishap_group_norm32_parts(1, 32 * 32, 64)
+        parts = C.c_int()
+        _lib.check(_lib.lib().ishap_group_norm32_plan(1, 32, 32, 64, 0, 0, 0, silu, 0, 0, 3, None, C.byref(parts), None, None, None,
+                                                      None, None, None, None, 0))
+        parts = parts.value
         assert parts > 1, "this shape must exercise the rendezvous"
     y, stats, xd = group_norm(x, w, b, silu, route)
     r, mx = rel(y, want), float((y - T(want)).abs().max())
