@@ -256,8 +256,10 @@ int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit_nhwc_f1
  * Per edit: its handles (a CSR range of one packed sources / targets array), cof, rounded-texel bitmap, mask count, loss sums
  * and fixed-point scatter buffer; its tap slice edit + e*W*W*ld and guidance slice orig + e*orig_stride.  Shared: W, ld, Cc,
  * chmap, r, voxel, l1, and ONE power-of-two loss scale for the whole batch, picked from max|g| over all edits.
- * Each edit's loss and fp32 gradient are BITWISE those of ishap_drag_loss_grad on that edit alone; its fp16 cotangent is the
- * solo one times 2^(k_batch - k_solo) (bitwise where both are normal fp16 numbers).  The input-gradient backward is linear in
+ * Each edit's loss and fp32 gradient are BITWISE those of ishap_drag_loss_grad on that edit alone, by construction: the
+ * single-edit calls above are the E = 1 case of these, the same kernels on the caller's own buffers, and an edit's workgroups do
+ * the same work whatever stands beside them.  Its fp16 cotangent is the solo one times 2^(k_batch - k_solo) (bitwise where both
+ * are normal fp16 numbers).  The input-gradient backward is linear in
  * the cotangent and removes scale2[1] at its end, so a batched backward needs nothing else. */
 typedef struct {
   int E;                /* edits, 1..32 */
@@ -276,7 +278,7 @@ typedef struct {
   long long scratch_bytes;
 } ishap_drag_batch_args;
 long long ishap_drag_batch_scratch_bytes(int E, int W, int ld);
-/* once per batch of edits (ishap_drag_setup for each edit) */
+/* once per batch of edits (what ishap_drag_setup does, for each edit) */
 int ishap_drag_batch_setup(const ishap_drag_batch_args* a, void* stream);
 /* edit_nhwc_f16 [E][W*W][ld] (the resident tap of a batch-E forward); loss device float[E]; grad_nhwc fp32 [E][W*W][ld] */
 int ishap_drag_batch_loss_grad(const ishap_drag_batch_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,

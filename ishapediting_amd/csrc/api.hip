@@ -229,39 +229,55 @@ int ishap_axpby(const float* x, const float* y, float a, float b, long long nume
   return axpby_launch(x, y, out, a, b, numel, (hipStream_t)stream);
 }
 
-static int fill_drag(const ishap_drag_args* a, DragArgs& d) {
+// ---- drag loss: one set of launches (csrc/drag.hip) that takes E edits; the shape requirements are checked there
+static const auto fill_drag_shared = [](const auto* a, DragArgs& b) {     // what the solo and the batched struct both hold
+  b.W = a->W; b.ld = a->ld; b.Cc = a->Cc; b.chmap = a->chmap; b.sources = a->sources; b.targets = a->targets;
+  b.r = a->r; b.voxel = a->voxel; b.l1 = a->l1;
+};
+
+// the per-call pointers of a loss call (nullptr for a setup call, which reads none of them)
+static void fill_drag_call(DragBatchArgs& d, const void* edit, const void* orig, float* grad, float* loss) {
+  d.base.edit = (const half_t*)edit; d.base.orig = (const half_t*)orig; d.base.grad = grad; d.base.loss = loss;
+}
+
+// the solo ABI: E = 1 on the caller's own buffers (a batch of one owns slice 0 of every per-edit array, i.e. the array)
+static int fill_drag(const ishap_drag_args* a, DragBatchArgs& d) {
   ISHAP_REQUIRE(a && a->chmap && a->sources && a->targets && a->touched && a->nmask && a->acc && a->grad_fx && a->chan_weight,
                 "null argument");
   ISHAP_REQUIRE(a->W > 1 && a->B >= 1 && a->r >= 0 && a->Cc >= 1 && a->ld >= 1, "drag dims");
-  d.W = a->W; d.ld = a->ld; d.Cc = a->Cc; d.chmap = a->chmap; d.sources = a->sources; d.targets = a->targets;
-  d.B = a->B; d.r = a->r; d.voxel = a->voxel; d.cof = a->cof; d.l1 = a->l1;
-  d.touched = a->touched; d.nmask = a->nmask; d.acc = (long long*)a->acc; d.gfx = (long long*)a->grad_fx;
-  d.chw = a->chan_weight;
+  DragArgs& b = d.base;
+  fill_drag_shared(a, b);
+  b.touched = a->touched; b.nmask = a->nmask; b.acc = (long long*)a->acc; b.gfx = (long long*)a->grad_fx;
+  b.chw = a->chan_weight;
+  d.E = 1;
+  d.orig_stride = 0;
+  d.hoff[0] = 0; d.hoff[1] = a->B;
+  d.cof[0] = a->cof;
   return 0;
 }
 
 int ishap_drag_setup(const ishap_drag_args* a, void* stream) {
-  DragArgs d;
+  DragBatchArgs d;
   ISHAP_TRY(fill_drag(a, d));
-  return drag_setup_launch(d, (hipStream_t)stream);
+  return drag_batch_setup_launch(d, (hipStream_t)stream);
 }
 
 int ishap_drag_loss_grad(const ishap_drag_args* a, const void* edit, const void* orig, float* grad, float* loss,
                          void* stream) {
-  DragArgs d;
+  DragBatchArgs d;
   ISHAP_TRY(fill_drag(a, d));
   ISHAP_REQUIRE(edit && orig && grad && loss, "null argument");
-  d.edit = (const half_t*)edit; d.orig = (const half_t*)orig; d.grad = grad; d.loss = loss;
-  return drag_loss_grad_launch(d, (hipStream_t)stream);
+  fill_drag_call(d, edit, orig, grad, loss);
+  return drag_batch_loss_launch(d, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit, const void* orig, float* grad, float* loss,
                               void* cot_f16, unsigned* bits, float* scale2, void* stream) {
-  DragArgs d;
+  DragBatchArgs d;
   ISHAP_TRY(fill_drag(a, d));
   ISHAP_REQUIRE(edit && orig && grad && loss && cot_f16 && bits && scale2, "null argument");
-  d.edit = (const half_t*)edit; d.orig = (const half_t*)orig; d.grad = grad; d.loss = loss;
-  return drag_loss_cotangent_launch(d, (half_t*)cot_f16, bits, scale2, (hipStream_t)stream);
+  fill_drag_call(d, edit, orig, grad, loss);
+  return drag_batch_loss_launch(d, (half_t*)cot_f16, bits, scale2, (hipStream_t)stream);
 }
 
 // ---- E edits per call: one scratch buffer, carved as [grad_fx E*W*W*ld int64][acc E*2 int64][nmask E int32][touched E*3*W*W]
@@ -284,7 +300,7 @@ long long ishap_drag_batch_scratch_bytes(int E, int W, int ld) {
 
 static int fill_drag_batch(const ishap_drag_batch_args* a, DragBatchArgs& d) {
   ISHAP_REQUIRE(a && a->chmap && a->sources && a->targets && a->handle_offsets && a->cof && a->scratch, "null argument");
-  ISHAP_REQUIRE(a->E >= 1 && a->E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");
+  ISHAP_REQUIRE(a->E >= 1 && a->E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");      // hoff / cof below hold that many
   ISHAP_REQUIRE(a->W > 1 && a->r >= 0 && a->Cc >= 1 && a->ld >= 1 && a->orig_stride >= 0, "drag dims");
   long long o_acc, o_nmask, o_touched, o_chw;
   const long long need = drag_batch_carve(a->E, a->W, a->ld, &o_acc, &o_nmask, &o_touched, &o_chw);
@@ -292,8 +308,7 @@ static int fill_drag_batch(const ishap_drag_batch_args* a, DragBatchArgs& d) {
   ISHAP_REQUIRE(((unsigned long long)a->scratch & 15ull) == 0, "drag batch: scratch must be 16-byte aligned");
   char* sc = (char*)a->scratch;
   DragArgs& b = d.base;
-  b.W = a->W; b.ld = a->ld; b.Cc = a->Cc; b.chmap = a->chmap; b.sources = a->sources; b.targets = a->targets;
-  b.r = a->r; b.voxel = a->voxel; b.l1 = a->l1;
+  fill_drag_shared(a, b);
   b.gfx = (long long*)sc; b.acc = (long long*)(sc + o_acc); b.nmask = (int*)(sc + o_nmask);
   b.touched = (unsigned char*)(sc + o_touched); b.chw = (unsigned char*)(sc + o_chw);
   d.E = a->E;
@@ -314,8 +329,8 @@ int ishap_drag_batch_loss_grad(const ishap_drag_batch_args* a, const void* edit,
   DragBatchArgs d;
   ISHAP_TRY(fill_drag_batch(a, d));
   ISHAP_REQUIRE(edit && orig && grad && loss, "null argument");
-  d.base.edit = (const half_t*)edit; d.base.orig = (const half_t*)orig; d.base.grad = grad; d.base.loss = loss;
-  return drag_batch_loss_grad_launch(d, (hipStream_t)stream);
+  fill_drag_call(d, edit, orig, grad, loss);
+  return drag_batch_loss_launch(d, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* edit, const void* orig, float* grad,
@@ -323,8 +338,8 @@ int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* 
   DragBatchArgs d;
   ISHAP_TRY(fill_drag_batch(a, d));
   ISHAP_REQUIRE(edit && orig && grad && loss && cot_f16 && bits && scale2, "null argument");
-  d.base.edit = (const half_t*)edit; d.base.orig = (const half_t*)orig; d.base.grad = grad; d.base.loss = loss;
-  return drag_batch_loss_cotangent_launch(d, (half_t*)cot_f16, bits, scale2, (hipStream_t)stream);
+  fill_drag_call(d, edit, orig, grad, loss);
+  return drag_batch_loss_launch(d, (half_t*)cot_f16, bits, scale2, (hipStream_t)stream);
 }
 
 int ishap_grad_to_scaled_f16(const float* grad, void* out_f16, unsigned* bits, float* scale2, long long numel,

@@ -10,6 +10,9 @@
 // (2r+1) lattice points that differ in z are identical terms of the mean.  Each plane therefore has
 // B*(2r+1)^2 distinct sample positions with multiplicity (2r+1).  A wave owns one position; lanes run
 // over channels, which are contiguous in NHWC (coalesced 2-byte reads, fp32 atomics for the scatter).
+//
+// One set of kernels: the per-edit device bodies first, then the kernels and launches, which take E edits per call
+// (DragBatchArgs).  The single-edit ABI is the E = 1 call of the same kernels on the caller's own buffers.
 #include "drag.h"
 #include <cstdlib>
 
@@ -179,18 +182,6 @@ __device__ __forceinline__ void drag_touch_one(const DragArgs& a, int p, int b, 
       for (int dx = -1; dx <= 2; ++dx) mark(bt.y0 + dy, bt.x0 + dx, 2u);
   }
 }
-__global__ void drag_touch_kernel(DragArgs a) {
-  const int side = 2 * a.r + 1;
-  const int total = 3 * a.B * 2 * side * side;
-  int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  int j = idx % side;
-  int i = (idx / side) % side;
-  int st = (idx / (side * side)) % 2;
-  int b = (idx / (side * side * 2)) % a.B;
-  int p = idx / (side * side * 2 * a.B);
-  drag_touch_one(a, p, b, st, i, j);
-}
 
 __device__ __forceinline__ void drag_count_body(const DragArgs& a) {
   __shared__ int red[256];
@@ -201,7 +192,6 @@ __device__ __forceinline__ void drag_count_body(const DragArgs& a) {
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
   if (threadIdx.x == 0) a.nmask[0] = red[0];
 }
-__global__ void drag_count_kernel(DragArgs a) { drag_count_body(a); }
 
 // chw[p][ch] = number of (plane p, c) pairs that resize_feat_align maps to tap channel ch (0 or 1; 2 where the nearest
 // resize repeats a channel): lets the gather pass below add the mask term per tap element without a scatter
@@ -214,11 +204,6 @@ __global__ void drag_chan_weight_kernel(DragArgs a) {
   a.chw[idx] = (unsigned char)min(cnt, 255);
 }
 
-__global__ __launch_bounds__(256) void drag_terms_kernel(DragArgs a, unsigned* absmax_bits) {
-  if (absmax_bits && blockIdx.x == 0 && threadIdx.x == 0) absmax_bits[0] = 0u;   // for the atomicMax of the pass that follows
-  drag_motion_body(a, blockIdx.x, gridDim.x);
-}
-
 // loss from the two fixed-point sums; leaves them zero for the next call
 __device__ __forceinline__ void drag_finish(const DragArgs& a) {
   const int side = 2 * a.r + 1;
@@ -229,7 +214,6 @@ __device__ __forceinline__ void drag_finish(const DragArgs& a) {
   a.acc[0] = 0;
   a.acc[1] = 0;
 }
-__global__ void drag_finish_kernel(DragArgs a) { drag_finish(a); }
 
 // Gather pass: fixed-point scatter buffer (motion term) -> the fp32 gradient the ABI returns, plus the MASK term
 // (drag_utils.py:376-381: cof * mean over the untouched texels of |edit - orig|^2 or |.|), which is elementwise in the tap's
@@ -293,49 +277,6 @@ __device__ __forceinline__ void drag_gather_body(const DragArgs& a, int blk, int
     if (threadIdx.x == 0) atomicMax(absmax_bits, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
   }
 }
-__global__ __launch_bounds__(256) void drag_gather_kernel(DragArgs a, unsigned* __restrict__ absmax_bits) {
-  drag_gather_body(a, blockIdx.x, gridDim.x, absmax_bits);
-}
-
-int drag_setup_launch(const DragArgs& a, hipStream_t s) {
-  const int side = 2 * a.r + 1;
-  ISHAP_REQUIRE((3 * a.W * a.W) % 4 == 0 && a.ld % 8 == 0, "drag: 3*W*W must be a multiple of 4 and the tap channels of 8");
-  ISHAP_CHECK_HIP(hipMemsetAsync(a.touched, 0, (size_t)3 * a.W * a.W, s));
-  // the scatter buffer and the loss sums start at zero here; every loss call leaves them zero again
-  ISHAP_CHECK_HIP(hipMemsetAsync(a.gfx, 0, (size_t)a.W * a.W * a.ld * sizeof(long long), s));
-  ISHAP_CHECK_HIP(hipMemsetAsync(a.acc, 0, 2 * sizeof(long long), s));
-  int total = 3 * a.B * 2 * side * side;
-  hipLaunchKernelGGL(drag_touch_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(drag_count_kernel, dim3(1), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(drag_chan_weight_kernel, dim3(ceil_div(3 * a.ld, 256)), dim3(256), 0, s, a);
-  ISHAP_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// every workgroup of these passes ends with same-address atomics (loss sum, max|g|) that serialise at ~10 ns each:
-// few, fat workgroups (the loops are grid-stride).
-static int drag_terms_launch(const DragArgs& a, unsigned* bits, hipStream_t s) {
-  constexpr int cap = 1024;          // swept in round 2; no result file was kept, and the library no longer reads the cap from the environment: not repeatable as is
-  const int side = 2 * a.r + 1;
-  const int nrows = 3 * a.B * side * ((a.Cc + 63) / 64) * ((side + DSEG - 1) / DSEG);
-  hipLaunchKernelGGL(drag_terms_kernel, dim3(min(ceil_div(nrows * 64, 256), cap)), dim3(256), 0, s, a, bits);
-  return 0;
-}
-static unsigned gather_blocks(long long n) {
-  constexpr int cap = 512;
-  return (unsigned)std::min<long long>((n / 8 + 255) / 256, cap);
-}
-
-// requires ishap_drag_setup on these buffers first (it zeroes the scratch this call leaves zero again)
-int drag_loss_grad_launch(const DragArgs& a, hipStream_t s) {
-  const long long n = (long long)a.W * a.W * a.ld;
-  ISHAP_REQUIRE(a.ld % 8 == 0, "drag: tap channels must be a multiple of 8");
-  ISHAP_TRY(drag_terms_launch(a, nullptr, s));
-  hipLaunchKernelGGL(drag_gather_kernel, dim3(gather_blocks(n)), dim3(256), 0, s, a, (unsigned*)nullptr);
-  hipLaunchKernelGGL(drag_finish_kernel, dim3(1), dim3(1), 0, s, a);
-  ISHAP_CHECK_HIP(hipGetLastError());
-  return 0;
-}
 
 // ---- fp32 gradient -> scaled fp16 cotangent (power-of-two loss scale chosen from max|g|) ----
 __global__ void absmax_kernel(const float* __restrict__ g, long long n, unsigned* __restrict__ out_bits) {
@@ -365,32 +306,6 @@ __global__ void scale_to_f16_kernel(const float* __restrict__ g, half_t* __restr
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     o[i] = (half_t)(g[i] * sc);
 }
-// the same with the scale picked by every thread from max|g| (published by thread 0) and the drag loss finished here:
-// three launches fewer per guided step
-__global__ void drag_scale_kernel(const float* __restrict__ g, half_t* __restrict__ o, const unsigned* __restrict__ bits,
-                                  float* __restrict__ scale2, DragArgs a, long long n) {
-  const float sc = pick_scale(__uint_as_float(bits[0]));
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    scale2[0] = sc;
-    scale2[1] = 1.f / sc;
-    drag_finish(a);
-  }
-  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)gridDim.x * blockDim.x * 4) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
-    *reinterpret_cast<half4*>(o + i) = (half4){(half_t)(v[0] * sc), (half_t)(v[1] * sc), (half_t)(v[2] * sc), (half_t)(v[3] * sc)};
-  }
-}
-// loss + gradient + scaled fp16 cotangent of one guided step in three launches (motion scatter, gather + mask, scale)
-int drag_loss_cotangent_launch(const DragArgs& a, half_t* cot, unsigned* bits, float* scale2, hipStream_t s) {
-  const long long n = (long long)a.W * a.W * a.ld;
-  ISHAP_REQUIRE(a.ld % 8 == 0, "drag: tap channels must be a multiple of 8");
-  ISHAP_TRY(drag_terms_launch(a, bits, s));
-  hipLaunchKernelGGL(drag_gather_kernel, dim3(gather_blocks(n)), dim3(256), 0, s, a, bits);
-  hipLaunchKernelGGL(drag_scale_kernel, dim3((unsigned)std::min<long long>((n / 4 + 255) / 256, 1024)), dim3(256), 0, s,
-                     (const float*)a.grad, cot, (const unsigned*)bits, scale2, a, n);
-  ISHAP_CHECK_HIP(hipGetLastError());
-  return 0;
-}
 int grad_to_scaled_f16_launch(const float* g, half_t* o, unsigned* bits, float* scale2, long long n, hipStream_t s) {
   ISHAP_CHECK_HIP(hipMemsetAsync(bits, 0, sizeof(unsigned), s));
   int blocks = (int)std::min<long long>((n + 255) / 256, 1024);
@@ -401,12 +316,12 @@ int grad_to_scaled_f16_launch(const float* g, half_t* o, unsigned* bits, float* 
   return 0;
 }
 
-// ==== E edits per call ====
-// Every pass of one edit above becomes one launch whose grid is the concatenation of the E solo grids: workgroup blk of edit e
-// runs exactly what workgroup blk of the solo launch for that edit runs (same bodies, same workgroup count, same grid stride).
-// So each edit's float partial sums are formed in the same groups and order as alone, its fixed-point totals are the same
-// integers, and its loss and fp32 gradient are BITWISE those of ishap_drag_loss_grad on that edit -- three launches per guided
-// step whatever E is.
+// ==== the launches: E edits per call; the solo ABI (ishap_drag_setup / _loss_grad / _loss_cotangent) is E = 1 ====
+// Every pass is one launch whose grid is the concatenation of one grid per edit: workgroup blk of edit e runs the body above on
+// edit e's slice (drag_edit_args) with that edit's own workgroup count as its grid stride, whatever E is and whichever edits
+// stand beside it.  So each edit's float partial sums are formed in the same groups and order as alone, its fixed-point totals
+// are the same integers, and its loss and fp32 gradient are BITWISE those of a call with that edit alone -- by construction:
+// the call with one edit runs these same kernels -- three launches per guided step whatever E is.
 //
 // One loss scale for the batch.  The cotangent is g * 2^k in fp16 with k picked from max|g| over ALL edits (so k_batch <= k_solo
 // of every edit).  Multiplying by a power of two is exact in fp32, and the fp16 cast of g * 2^k_batch equals the solo cotangent
@@ -433,7 +348,9 @@ __device__ __forceinline__ DragArgs drag_edit_args(const DragBatchArgs& b, int e
   return a;
 }
 
-// one thread per (handle, plane, source / target, lattice i, j) over the packed handles of all edits
+// one thread per (handle, plane, source / target, lattice i, j) over the packed handles of all edits.  Which thread takes which
+// tuple is free: drag_touch_one reads the handles and does nothing but atomicOr marks into `touched`, and OR commutes, so the
+// bitmap is the same for every assignment of tuples to threads (the single-edit kernel this one replaced ordered them plane-major)
 __global__ void drag_batch_touch_kernel(DragBatchArgs b) {
   const int side = 2 * b.base.r + 1;
   const int per = 3 * 2 * side * side;
@@ -452,7 +369,7 @@ __global__ void drag_batch_touch_kernel(DragBatchArgs b) {
 __global__ void drag_batch_count_kernel(DragBatchArgs b) { drag_count_body(drag_edit_args(b, blockIdx.x)); }
 
 __global__ __launch_bounds__(256) void drag_batch_terms_kernel(DragBatchArgs b, unsigned* absmax_bits) {
-  if (absmax_bits && blockIdx.x == 0 && threadIdx.x == 0) absmax_bits[0] = 0u;
+  if (absmax_bits && blockIdx.x == 0 && threadIdx.x == 0) absmax_bits[0] = 0u;   // for the atomicMax of the pass that follows
   int e = 0;
   while (e + 1 < b.E && (int)blockIdx.x >= b.tblk[e + 1]) ++e;       // workgroup-uniform
   drag_motion_body(drag_edit_args(b, e), blockIdx.x - b.tblk[e], b.tblk[e + 1] - b.tblk[e]);
@@ -464,6 +381,8 @@ __global__ __launch_bounds__(256) void drag_batch_gather_kernel(DragBatchArgs b,
 __global__ void drag_batch_finish_kernel(DragBatchArgs b) {
   for (int e = 0; e < b.E; ++e) drag_finish(drag_edit_args(b, e));
 }
+// fp32 gradient -> fp16 cotangent as scale_to_f16_kernel, with the scale picked by every thread from max|g| (published by thread
+// 0) and the drag losses finished here: three launches fewer per guided step
 __global__ void drag_batch_scale_kernel(const float* __restrict__ g, half_t* __restrict__ o, const unsigned* __restrict__ bits,
                                         float* __restrict__ scale2, DragBatchArgs b, long long n) {
   const float sc = pick_scale(__uint_as_float(bits[0]));
@@ -478,6 +397,7 @@ __global__ void drag_batch_scale_kernel(const float* __restrict__ g, half_t* __r
   }
 }
 
+// the shape requirements of every drag call, solo or batched (api.hip checks only the pointers and dimensions of its structs)
 static int drag_batch_check(const DragBatchArgs& a) {
   ISHAP_REQUIRE(a.E >= 1 && a.E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");
   ISHAP_REQUIRE((3 * a.base.W * a.base.W) % 4 == 0 && a.base.ld % 8 == 0,
@@ -487,6 +407,7 @@ static int drag_batch_check(const DragBatchArgs& a) {
   return 0;
 }
 
+// buffers as ishap.h describes them; zeroes the scratch that every loss call leaves zero again
 int drag_batch_setup_launch(DragBatchArgs& a, hipStream_t s) {
   ISHAP_TRY(drag_batch_check(a));
   const DragArgs& d = a.base;
@@ -503,8 +424,21 @@ int drag_batch_setup_launch(DragBatchArgs& a, hipStream_t s) {
   return 0;
 }
 
-// the solo terms grid of every edit, concatenated (drag_terms_launch)
-static int drag_batch_terms_launch(DragBatchArgs& a, unsigned* bits, hipStream_t s) {
+static unsigned gather_blocks(long long n) {
+  constexpr int cap = 512;
+  return (unsigned)std::min<long long>((n / 8 + 255) / 256, cap);
+}
+
+// Losses + fp32 gradients of the E edits in three launches (motion scatter, gather + mask, finish); with `cot` the third launch
+// also writes the scaled fp16 cotangent (drag_batch_scale_kernel) and `bits` / `scale2` must be given.  Requires
+// drag_batch_setup_launch on these buffers first.
+int drag_batch_loss_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float* scale2, hipStream_t s) {
+  ISHAP_TRY(drag_batch_check(a));
+  if (!cot) bits = nullptr;
+  // every workgroup of the terms and gather passes ends with same-address atomics (loss sum, max|g|) that serialise at ~10 ns
+  // each: few, fat workgroups (the loops are grid-stride).  Terms: a wave per DSEG positions of a lattice row, at most `cap`
+  // workgroups per edit (swept in round 2; no result file was kept, and the library no longer reads the cap from the environment:
+  // not repeatable as is)
   constexpr int cap = 1024;
   const int side = 2 * a.base.r + 1;
   a.tblk[0] = 0;
@@ -513,30 +447,16 @@ static int drag_batch_terms_launch(DragBatchArgs& a, unsigned* bits, hipStream_t
     a.tblk[e + 1] = a.tblk[e] + min(ceil_div(nrows * 64, 256), cap);
   }
   hipLaunchKernelGGL(drag_batch_terms_kernel, dim3(a.tblk[a.E]), dim3(256), 0, s, a, bits);
-  return 0;
-}
-
-// requires ishap_drag_batch_setup on this scratch first
-int drag_batch_loss_grad_launch(DragBatchArgs& a, hipStream_t s) {
-  ISHAP_TRY(drag_batch_check(a));
   const long long n = (long long)a.base.W * a.base.W * a.base.ld;
   const unsigned gb = gather_blocks(n);
-  ISHAP_TRY(drag_batch_terms_launch(a, nullptr, s));
-  hipLaunchKernelGGL(drag_batch_gather_kernel, dim3(gb * a.E), dim3(256), 0, s, a, (int)gb, (unsigned*)nullptr);
-  hipLaunchKernelGGL(drag_batch_finish_kernel, dim3(1), dim3(1), 0, s, a);
-  ISHAP_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-int drag_batch_loss_cotangent_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float* scale2, hipStream_t s) {
-  ISHAP_TRY(drag_batch_check(a));
-  const long long n = (long long)a.base.W * a.base.W * a.base.ld;
-  const unsigned gb = gather_blocks(n);
-  ISHAP_TRY(drag_batch_terms_launch(a, bits, s));
   hipLaunchKernelGGL(drag_batch_gather_kernel, dim3(gb * a.E), dim3(256), 0, s, a, (int)gb, bits);
-  const long long nt = n * a.E;
-  hipLaunchKernelGGL(drag_batch_scale_kernel, dim3((unsigned)std::min<long long>((nt / 4 + 255) / 256, 1024)), dim3(256), 0, s,
-                     (const float*)a.base.grad, cot, (const unsigned*)bits, scale2, a, nt);
+  if (cot) {
+    const long long nt = n * a.E;
+    hipLaunchKernelGGL(drag_batch_scale_kernel, dim3((unsigned)std::min<long long>((nt / 4 + 255) / 256, 1024)), dim3(256), 0, s,
+                       (const float*)a.base.grad, cot, (const unsigned*)bits, scale2, a, nt);
+  } else {
+    hipLaunchKernelGGL(drag_batch_finish_kernel, dim3(1), dim3(1), 0, s, a);
+  }
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }

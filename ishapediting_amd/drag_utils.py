@@ -95,15 +95,30 @@ _FUSED_UPDATE = os.environ.get("ISHAP_FUSED_UPDATE", "1") == "1"     # guided up
 _OVERLAP_TAIL = os.environ.get("ISHAP_OVERLAP_TAIL", "1") == "1"      # round 5: on by default (see training())
 
 
-class DragKernels:
-    """Device state + calls for the drag loss (drag_utils.py:309-334 setup, :355-383 per step)."""
+class _DragKernelsBase:
+    """What the solo and the batched kernels object share: the dimensions of the tap, the channel map and the loss scale."""
 
-    def __init__(self, device, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str = "l2"):
+    def __init__(self, device, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str):
         self.device = th.device(device)
         self.W, self.ld, self.r, self.voxel = W, ld, r, float(voxel)
         self.l1 = 1 if loss_type == "l1" else 0
         self.chmap = th.as_tensor(np.asarray(chmap), dtype=th.int32).reshape(3, -1).contiguous().to(self.device)
         self.Cc = self.chmap.shape[1]
+        self.bits = th.zeros(1, dtype=th.int32, device=self.device)
+        self.scale2 = th.ones(2, dtype=th.float32, device=self.device)
+        self.sources = self.targets = None
+        self._L = _lib.lib()
+
+    def _call(self, fn, *args):
+        with th.cuda.device(self.device):
+            _lib.check(fn(*args, _lib.stream_ptr(self.device)))
+
+
+class DragKernels(_DragKernelsBase):
+    """Device state + calls for the drag loss (drag_utils.py:309-334 setup, :355-383 per step)."""
+
+    def __init__(self, device, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str = "l2"):
+        super().__init__(device, W, ld, chmap, r, voxel, loss_type)
         self.touched = th.zeros(3 * W * W, dtype=th.uint8, device=self.device)
         self.nmask = th.zeros(1, dtype=th.int32, device=self.device)
         self.chan_weight = th.zeros(3 * ld, dtype=th.uint8, device=self.device)
@@ -112,11 +127,7 @@ class DragKernels:
         self.grad = th.empty((W * W, ld), dtype=th.float32, device=self.device)
         self.loss = th.zeros(1, dtype=th.float32, device=self.device)
         self.cot = th.empty((W * W, ld), dtype=th.float16, device=self.device)
-        self.bits = th.zeros(1, dtype=th.int32, device=self.device)
-        self.scale2 = th.ones(2, dtype=th.float32, device=self.device)
-        self.sources = self.targets = None
         self.cof = 0.0
-        self._L = _lib.lib()
 
     def _args(self) -> _lib.DragArgsC:
         return _lib.DragArgsC(self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
@@ -131,37 +142,30 @@ class DragKernels:
         self.sources, self.targets = pts(sources), pts(targets)
         assert self.sources.shape[0] == self.targets.shape[0]
         self.cof = float(cof)
-        a = self._args()
-        with th.cuda.device(self.device):
-            _lib.check(self._L.ishap_drag_setup(C.byref(a), _lib.stream_ptr(self.device)))
+        self._call(self._L.ishap_drag_setup, C.byref(self._args()))
 
     def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int):
-        a = self._args()
-        with th.cuda.device(self.device):
-            _lib.check(self._L.ishap_drag_loss_grad(C.byref(a), edit_ptr, orig_ptr, self.grad.data_ptr(),
-                                                    self.loss.data_ptr(), _lib.stream_ptr(self.device)))
+        self._call(self._L.ishap_drag_loss_grad, C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
+                   self.loss.data_ptr())
         return self.grad, self.loss
 
     def loss_grad(self, edit: th.Tensor, orig: th.Tensor):
         assert edit.dtype == th.float16 and orig.dtype == th.float16 and edit.is_contiguous() and orig.is_contiguous()
         return self.loss_grad_ptr(edit.data_ptr(), orig.data_ptr())
 
-    def loss_cotangent_ptr(self, edit_ptr: int, orig_ptr: int, loss_out=None):
-        """loss + gradient + scaled fp16 cotangent in one call (three launches); `loss_out`: a device float to write the loss to."""
-        a = self._args()
+    def loss_cotangent_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int = 0, loss_out=None):
+        """loss + gradient + scaled fp16 cotangent in one call (three launches); `loss_out`: a device float to write the loss to;
+        `orig_stride`: the batched object's argument, 0 here (one edit reads one guidance tap)."""
+        assert orig_stride == 0
         loss = self.loss if loss_out is None else loss_out
-        with th.cuda.device(self.device):
-            _lib.check(self._L.ishap_drag_loss_cotangent(C.byref(a), edit_ptr, orig_ptr, self.grad.data_ptr(), loss.data_ptr(),
-                                                         self.cot.data_ptr(), self.bits.data_ptr(), self.scale2.data_ptr(),
-                                                         _lib.stream_ptr(self.device)))
+        self._call(self._L.ishap_drag_loss_cotangent, C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
+                   loss.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(), self.scale2.data_ptr())
         return self.cot, self.scale2
 
     def scaled_cotangent(self):
         """fp32 gradient -> fp16 cotangent * 2^k (k from max|g|) so the fp16 backward neither under- nor overflows."""
-        with th.cuda.device(self.device):
-            _lib.check(self._L.ishap_grad_to_scaled_f16(self.grad.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(),
-                                                        self.scale2.data_ptr(), self.grad.numel(),
-                                                        _lib.stream_ptr(self.device)))
+        self._call(self._L.ishap_grad_to_scaled_f16, self.grad.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(),
+                   self.scale2.data_ptr(), self.grad.numel())
         return self.cot, self.scale2
 
 
@@ -203,16 +207,12 @@ def per_edit(value, K: int, name: str) -> List[float]:
     return vals
 
 
-class BatchDragKernels:
+class BatchDragKernels(_DragKernelsBase):
     """Device state + calls of the drag loss for E edits at once (ishap_drag_batch_*): one scratch buffer, one loss scale."""
 
     def __init__(self, device, E: int, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str = "l2"):
-        self.device = th.device(device)
-        self.E, self.W, self.ld, self.r, self.voxel = int(E), W, ld, r, float(voxel)
-        self.l1 = 1 if loss_type == "l1" else 0
-        self.chmap = th.as_tensor(np.asarray(chmap), dtype=th.int32).reshape(3, -1).contiguous().to(self.device)
-        self.Cc = self.chmap.shape[1]
-        self._L = _lib.lib()
+        super().__init__(device, W, ld, chmap, r, voxel, loss_type)
+        self.E = int(E)
         nbytes = int(self._L.ishap_drag_batch_scratch_bytes(self.E, W, ld))
         if nbytes <= 0:
             raise ValueError(f"drag batch: bad dimensions E={E}, W={W}, ld={ld}")
@@ -220,9 +220,6 @@ class BatchDragKernels:
         self.grad = th.empty((self.E, W * W, ld), dtype=th.float32, device=self.device)
         self.loss = th.zeros(self.E, dtype=th.float32, device=self.device)
         self.cot = th.empty((self.E, W * W, ld), dtype=th.float16, device=self.device)
-        self.bits = th.zeros(1, dtype=th.int32, device=self.device)
-        self.scale2 = th.ones(2, dtype=th.float32, device=self.device)
-        self.sources = self.targets = None
 
     def setup(self, sources, targets, cof):
         """sources / targets: lists of E handle arrays; cof: a float or E floats."""
@@ -234,8 +231,7 @@ class BatchDragKernels:
         self._offs = (C.c_int * (self.E + 1))(*offs)
         self.cof = per_edit(cof, self.E, "cof")
         self._cof = (C.c_float * self.E)(*self.cof)
-        with th.cuda.device(self.device):
-            _lib.check(self._L.ishap_drag_batch_setup(C.byref(self._args(0)), _lib.stream_ptr(self.device)))
+        self._call(self._L.ishap_drag_batch_setup, C.byref(self._args(0)))
 
     def _args(self, orig_stride: int) -> _lib.DragBatchArgsC:
         return _lib.DragBatchArgsC(self.E, self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
@@ -244,18 +240,15 @@ class BatchDragKernels:
 
     def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int):
         """edit: [E][W*W][ld] fp16; orig: edit e's guidance at orig + e * orig_stride halfs (0: one guidance for all edits)."""
-        with th.cuda.device(self.device):
-            _lib.check(self._L.ishap_drag_batch_loss_grad(C.byref(self._args(orig_stride)), edit_ptr, orig_ptr, self.grad.data_ptr(),
-                                                          self.loss.data_ptr(), _lib.stream_ptr(self.device)))
+        self._call(self._L.ishap_drag_batch_loss_grad, C.byref(self._args(orig_stride)), edit_ptr, orig_ptr, self.grad.data_ptr(),
+                   self.loss.data_ptr())
         return self.grad, self.loss
 
     def loss_cotangent_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int, loss_out=None):
         """losses + gradients + the batch's fp16 cotangent (one loss scale, scale2) in three launches; `loss_out`: device float[E]."""
         loss = self.loss if loss_out is None else loss_out
-        with th.cuda.device(self.device):
-            _lib.check(self._L.ishap_drag_batch_loss_cotangent(
-                C.byref(self._args(orig_stride)), edit_ptr, orig_ptr, self.grad.data_ptr(), loss.data_ptr(), self.cot.data_ptr(),
-                self.bits.data_ptr(), self.scale2.data_ptr(), _lib.stream_ptr(self.device)))
+        self._call(self._L.ishap_drag_batch_loss_cotangent, C.byref(self._args(orig_stride)), edit_ptr, orig_ptr,
+                   self.grad.data_ptr(), loss.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(), self.scale2.data_ptr())
         return self.cot, self.scale2
 
 
@@ -411,6 +404,16 @@ class DragStuff:
     def _noise(self, i, like):
         return None if self.step_noise is None else self.step_noise(i).to(like.device)
 
+    def _denoise(self, img, t, each=None, **kwargs):
+        """The unguided steps i = t - 1 .. 0 from `img`; `each(i, sample)` runs after step i.  Returns the last sample."""
+        for i in range(t - 1, -1, -1):
+            img = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
+                                                   clip_denoised=self.args.clip_denoised, want_inter_feat=False,
+                                                   noise=self._noise(i, img), want_noise=False, **kwargs)["sample"]
+            if each is not None:
+                each(i, img)
+        return img
+
     def update_latent_params(self, img=None, **kwargs):
         if img is not None:
             if th.is_tensor(img):
@@ -423,17 +426,15 @@ class DragStuff:
             img = th.randn((1, 96, self.args.image_size, self.args.image_size), dtype=th.float32, device=self.device)
         self.latent_code = img.clone().detach()
         self.w_batch, self.w0_batch, self.feature_guidance_batch = None, None, []     # training_batch: variants of this shape
-        for i in range(self.args.num_steps - 1, -1, -1):
-            keep = i < self.args.w_time
-            outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
-                                                    clip_denoised=self.args.clip_denoised, want_inter_feat=False,
-                                                    noise=self._noise(i, img), want_noise=False, **kwargs)
-            img = outs["sample"]
+
+        def record(i, img):
             if i == self.args.w_time:
                 self.w = img.clone().detach()
                 self.w0 = self.w.clone().detach()
-            if keep:
+            if i < self.args.w_time:
                 self.feature_guidance.append(self.model.copy_tap(self.args.feat_layer)[0])
+
+        img = self._denoise(img, self.args.num_steps, each=record, **kwargs)
         assert len(self.feature_guidance) == self.args.w_time
         self.mesh0 = self.get_mesh(tri_feat=img)
         self.mesh = copy.deepcopy(self.mesh0)
@@ -443,45 +444,36 @@ class DragStuff:
     def get_mesh(self, tri_feat=None, img=None, t=0):
         if tri_feat is None:
             img = img if img is not None else th.randn((1, 96, self.args.image_size, self.args.image_size)).to(self.device)
-            for i in range(t - 1, -1, -1):
-                outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
-                                                        clip_denoised=self.args.clip_denoised, want_inter_feat=False,
-                                                        noise=self._noise(i, img), want_noise=False)
-                img = outs["sample"]
-            tri_feat = img
+            tri_feat = self._denoise(img, t)
         self.tri_feat = tri_feat
         self.volume = decode_volume(self.decoder, tri_feat.to(self.device), self.range, self.middle,
                                     self.args.shape_resolution)
         return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10)
 
     # ------------------------------------------------------------------ drag loop (:302-399)
-    def training(self, sources=None, targets=None, scale=600, cof=0.2):
-        if self.args.num_samples > 1:
-            raise NotImplementedError("We can handle only one shape at each time!")
-        self.sources = th.tensor(np.asarray(sources), device=self.device, dtype=th.float32)
-        self.targets = th.tensor(np.asarray(targets), device=self.device, dtype=th.float32)
-        assert self.sources.shape[0] == self.targets.shape[0]
-        img = self.w.clone().detach()
+    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale):
+        """The guided loop of training() and training_batch(): a generator that yields the progress value after each step and
+        returns (img, stop_time) -- the latent and the number of unguided steps left when train_flag stopped it (0: ran to
+        the end).  `dk`: a DragKernels or BatchDragKernels after setup; `guidance[n]`: the guidance tap of the n-th step, edit e's
+        at + e * stride halfs; `scales`: the guidance scale of every image as floats; `guided_scale`: the same as
+        p_sample_guidance takes it (a float, or a device tensor with one value per image).  last_losses gets one [images]
+        tensor per step."""
+        w_time = self.args.w_time
         stop_time = 0
         self.train_flag = True
-        ch, width = self.model.tap_shape(self.args.feat_layer)
-        dk = DragKernels(self.device, W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size,
-                         loss_type=self.args.loss_type)
-        dk.setup(self.sources, self.targets, cof)
-        self._dk = dk
-        losses = th.zeros(self.args.w_time, dtype=th.float32, device=self.device)   # one slot per iteration, no per-step copy
-        self.diffusion.prepare(self.model, range(self.args.w_time))                 # timestep embeddings of the whole loop, once
+        losses = th.zeros((w_time, len(scales)), dtype=th.float32, device=self.device)   # one slot per iteration, no per-step copy
+        self.diffusion.prepare(self.model, range(w_time))                               # timestep embeddings of the whole loop, once
         self.last_losses = []
-        L = _lib.lib()
-        for i in range(self.args.w_time - 1, -1, -1):
+        for i in range(w_time - 1, -1, -1):
             if not self.train_flag:
                 stop_time = i + 1
                 break
-            origin = self.feature_guidance[self.args.w_time - 1 - i]
+            origin = guidance[w_time - 1 - i]
+            slot = losses[i]
             got = {}
 
             def loss_and_backward():          # needs the tap only
-                cot, scale2 = dk.loss_cotangent_ptr(self.model.tap_ptr(), origin.data_ptr(), loss_out=losses[i:i + 1])
+                cot, scale2 = dk.loss_cotangent_ptr(self.model.tap_ptr(), origin.data_ptr(), orig_stride=stride, loss_out=slot)
                 got["grad"] = self.model.backward_input(cot, scale2)           # = img.grad of the reference (:384)
                 return got["grad"]
 
@@ -498,17 +490,35 @@ class DragStuff:
                                                     keep_for_backward=True, want_inter_feat=False,
                                                     noise=self._noise(i, img), between=loss_and_backward,
                                                     overlap=_OVERLAP_TAIL if self.overlap_tail is None else self.overlap_tail,
-                                                    guided_scale=float(scale) if _FUSED_UPDATE else None, want_noise=False)
+                                                    guided_scale=guided_scale if _FUSED_UPDATE else None, want_noise=False)
             if _FUSED_UPDATE:
                 img = outs["guided"]
             else:
                 new = th.empty_like(img)
+                n1 = img[0].numel()
                 with th.cuda.device(self.device):
-                    _lib.check(L.ishap_guided_update(outs["sample"].data_ptr(), outs["variance"].data_ptr(), got["grad"].data_ptr(),
-                                                     float(scale), None, img.numel(), new.data_ptr(), _lib.stream_ptr(self.device)))
+                    for k, sc in enumerate(scales):
+                        _lib.check(_lib.lib().ishap_guided_update(
+                            outs["sample"][k].data_ptr(), outs["variance"][k].data_ptr(), got["grad"][k].data_ptr(), sc, None, n1,
+                            new[k].data_ptr(), _lib.stream_ptr(self.device)))
                 img = new
-            self.last_losses.append(losses[i:i + 1])
-            yield 1 - i / (self.args.w_time - 1.)
+            self.last_losses.append(slot)
+            yield 1 - i / (w_time - 1.)
+        return img, stop_time
+
+    def training(self, sources=None, targets=None, scale=600, cof=0.2):
+        if self.args.num_samples > 1:
+            raise NotImplementedError("We can handle only one shape at each time!")
+        self.sources = th.tensor(np.asarray(sources), device=self.device, dtype=th.float32)
+        self.targets = th.tensor(np.asarray(targets), device=self.device, dtype=th.float32)
+        assert self.sources.shape[0] == self.targets.shape[0]
+        img = self.w.clone().detach()
+        ch, width = self.model.tap_shape(self.args.feat_layer)
+        dk = DragKernels(self.device, W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size,
+                         loss_type=self.args.loss_type)
+        dk.setup(self.sources, self.targets, cof)
+        self._dk = dk
+        img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale))
         self.mesh = self.get_mesh(img=img, t=stop_time)
 
     # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
@@ -527,16 +537,15 @@ class DragStuff:
         img = imgs.to(device=self.device, dtype=th.float32).contiguous()
         self.latent_code = img.clone().detach()
         self.feature_guidance_batch = []
-        for i in range(self.args.num_steps - 1, -1, -1):
-            outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
-                                                    clip_denoised=self.args.clip_denoised, want_inter_feat=False,
-                                                    noise=self._noise(i, img), want_noise=False, **kwargs)
-            img = outs["sample"]
+
+        def record(i, img):
             if i == self.args.w_time:
                 self.w_batch = img.clone().detach()
                 self.w0_batch = self.w_batch.clone().detach()
             if i < self.args.w_time:
                 self.feature_guidance_batch.append(self.model.copy_tap(self.args.feat_layer, K))
+
+        img = self._denoise(img, self.args.num_steps, each=record, **kwargs)
         assert len(self.feature_guidance_batch) == self.args.w_time
         self.meshes0 = [self.get_mesh(tri_feat=img[k:k + 1]) for k in range(K)]
         self.meshes = copy.deepcopy(self.meshes0)
@@ -545,11 +554,7 @@ class DragStuff:
     def get_meshes(self, img, t=0):
         """get_mesh for a batch of latents: the t remaining unguided steps at batch K, then one decode per shape (sets
         tri_feat_batch, volumes, meshes)."""
-        for i in range(t - 1, -1, -1):
-            outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
-                                                    clip_denoised=self.args.clip_denoised, want_inter_feat=False,
-                                                    noise=self._noise(i, img), want_noise=False)
-            img = outs["sample"]
+        img = self._denoise(img, t)
         self.tri_feat_batch = img
         self.meshes, self.volumes = [], []
         for k in range(img.shape[0]):
@@ -583,47 +588,12 @@ class DragStuff:
                 raise RuntimeError("training_batch needs update_latent_params (variants of one shape) or update_latent_params_batch first")
             img = self.w.expand(K, *self.w.shape[1:]).contiguous()
             guidance, stride = self.feature_guidance, 0
-        stop_time = 0
-        self.train_flag = True
         dk = BatchDragKernels(self.device, K, W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size,
                               loss_type=self.args.loss_type)
         dk.setup(sources, targets, cofs)
         self._dk_batch = dk
         scales_dev = th.tensor(scales, dtype=th.float32, device=self.device)
-        losses = th.zeros((self.args.w_time, K), dtype=th.float32, device=self.device)
-        self.diffusion.prepare(self.model, range(self.args.w_time))
-        self.last_losses = []
-        L = _lib.lib()
-        for i in range(self.args.w_time - 1, -1, -1):
-            if not self.train_flag:
-                stop_time = i + 1
-                break
-            origin = guidance[self.args.w_time - 1 - i]
-            got = {}
-
-            def loss_and_backward():          # the structure of training(): loss + backward beside the forward tail
-                cot, scale2 = dk.loss_cotangent_ptr(self.model.tap_ptr(), origin.data_ptr(), stride, loss_out=losses[i])
-                got["grad"] = self.model.backward_input(cot, scale2)
-                return got["grad"]
-
-            outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
-                                                    keep_for_backward=True, want_inter_feat=False,
-                                                    noise=self._noise(i, img), between=loss_and_backward,
-                                                    overlap=_OVERLAP_TAIL if self.overlap_tail is None else self.overlap_tail,
-                                                    guided_scale=scales_dev if _FUSED_UPDATE else None, want_noise=False)
-            if _FUSED_UPDATE:
-                img = outs["guided"]
-            else:
-                new = th.empty_like(img)
-                n1 = img[0].numel()
-                with th.cuda.device(self.device):
-                    for k in range(K):
-                        _lib.check(L.ishap_guided_update(outs["sample"][k].data_ptr(), outs["variance"][k].data_ptr(),
-                                                         got["grad"][k].data_ptr(), scales[k], None, n1, new[k].data_ptr(),
-                                                         _lib.stream_ptr(self.device)))
-                img = new
-            self.last_losses.append(losses[i])
-            yield 1 - i / (self.args.w_time - 1.)
+        img, stop_time = yield from self._guided_loop(img, dk, guidance, stride, scales, scales_dev)
         self.get_meshes(img=img, t=stop_time)
 
     # ------------------------------------------------------------------ real shapes (:401-471, :552-566)

@@ -236,13 +236,15 @@ class SpacedDiffusion:
         if between is not None:
             try:
                 grad = between()
-            finally:
-                # also when `between` raises: the planned tail writes `model_output` through the pointer the forward was given --
-                # it must be enqueued and joined while that tensor is still alive (include/ishap.h, ishap_unet_forward)
-                if kw.get("overlap_tail"):
-                    if hasattr(model, "run_tail"):
-                        model.run_tail()      # the tail the forward only planned
-                    model.join_tail()
+            except BaseException as first:
+                # the tail is closed also when `between` raises; what `between` raised is what the caller sees, with a failure
+                # of the tail calls (likely a consequence: a device error fails them too) chained to it as its cause
+                try:
+                    self._close_tail(model, kw)
+                except Exception as second:
+                    raise first from second
+                raise
+            self._close_tail(model, kw)
         if guided_scale is not None and grad is not None and variance_noise is None:
             rng = None
             if noise is None:
@@ -264,6 +266,18 @@ class SpacedDiffusion:
         return {"sample": o["sample"], "pred_xstart": o["pred_xstart"], "inter_feat": inter,
                 "model_output": mo[:, :x.shape[1]], "noise": noise if rng is None else rng[2],
                 "variance": o["variance"] if variance is None else variance, "mean": o["mean"]}
+
+    @staticmethod
+    def _close_tail(model, kw):
+        """The planned tail writes `model_output` through the pointer the forward was given -- it must be enqueued and joined
+        while that tensor is still alive (include/ishap.h, ishap_unet_forward).  join_tail is called whatever run_tail did (alone it enqueues a plan that was never run)."""
+        if not kw.get("overlap_tail"):
+            return
+        try:
+            if hasattr(model, "run_tail"):
+                model.run_tail()      # the tail the forward only planned
+        finally:
+            model.join_tail()
 
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, noise=None):
         """gaussian_diffusion.py:400-444 (`noise` injectable for parity runs; default randn_like as there)."""

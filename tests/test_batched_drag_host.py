@@ -93,3 +93,145 @@ def test_batched_drag_kernels_use_no_scratch():
         found = [n for n in ks if want in n]
         assert len(found) == 1, (want, found)
         assert ks[found[0]].get(".private_segment_fixed_size", 0) == 0, (want, ks[found[0]])
+
+
+# ------------------------------------------------------------------------------------------------ the shared guided loop
+class _TailModel:
+    """What p_sample_guidance needs of a model up to `between`: a forward with a tap, and the planned tail's two calls."""
+
+    def __init__(self, run_tail_error=None):
+        self.calls, self.run_tail_error = [], run_tail_error
+
+    def tap_ptr(self):
+        return 0
+
+    def __call__(self, x, ts, feat_layer=-1, **kw):
+        self.calls.append(("forward", kw.get("overlap_tail", False)))
+        return torch.zeros(x.shape[0], 2 * x.shape[1], *x.shape[2:]), None
+
+    def run_tail(self):
+        self.calls.append("run_tail")
+        if self.run_tail_error is not None:
+            raise self.run_tail_error
+
+    def join_tail(self):
+        self.calls.append("join_tail")
+
+
+def test_failing_run_tail_neither_skips_join_tail_nor_hides_what_between_raised():
+    from ishapediting_amd.gaussian_diffusion import create_gaussian_diffusion
+    d = create_gaussian_diffusion(timestep_respacing="10")
+    x = torch.zeros(1, 6, 4, 4)
+
+    def between():
+        raise ValueError("the loss failed")
+
+    second = RuntimeError("ishap error -3")
+    m = _TailModel(run_tail_error=second)
+    with pytest.raises(ValueError, match="the loss failed") as ei:
+        d.p_sample_guidance(m, x, 3, feat_layer=1, keep_for_backward=True, between=between, overlap=True)
+    assert m.calls == [("forward", True), "run_tail", "join_tail"]
+    assert ei.value.__cause__ is second                  # the second failure is chained, not lost
+    # a tail that closes cleanly: the same exception, nothing chained
+    m = _TailModel()
+    with pytest.raises(ValueError, match="the loss failed") as ei:
+        d.p_sample_guidance(m, x, 3, feat_layer=1, keep_for_backward=True, between=between, overlap=True)
+    assert m.calls == [("forward", True), "run_tail", "join_tail"] and ei.value.__cause__ is None
+    # the plain sequence plans no tail and closes none
+    m = _TailModel()
+    with pytest.raises(ValueError, match="the loss failed"):
+        d.p_sample_guidance(m, x, 3, feat_layer=1, keep_for_backward=True, between=between, overlap=False)
+    assert m.calls == [("forward", False)]
+
+
+class _LoopModel:
+    def tap_shape(self, feat_layer):
+        return 16, 4                   # channels, width
+
+    def tap_ptr(self):
+        return 1000
+
+    def backward_input(self, cot, scale2):
+        return "grad"
+
+
+class _LoopDiffusion:
+    def __init__(self, log):
+        self.log = log
+
+    def prepare(self, model, indices):
+        self.log.append(("prepare", list(indices)))
+
+    def p_sample_guidance(self, model, x, t, **kw):
+        self.log.append(("step", t, kw))
+        if kw.get("between") is not None:
+            assert kw["between"]() == "grad"
+        return {"guided": x + 1, "sample": x + 1}
+
+
+def _loop_dragstuff(monkeypatch, log):
+    """A DragStuff without its model context; the two kernels classes replaced by recorders of the calls the loop makes."""
+    from argparse import Namespace
+    from ishapediting_amd import drag_utils as du
+
+    def recorder(batched):
+        class Kernels:
+            def __init__(self, device, *a, **kw):
+                log.append(("kernels", batched, a[0] if batched else None, kw["W"], kw["ld"], kw["r"], kw["loss_type"]))
+
+            def setup(self, sources, targets, cof):
+                log.append(("setup", batched, cof))
+
+            def loss_cotangent_ptr(self, edit_ptr, orig_ptr, orig_stride=0, loss_out=None):
+                log.append(("loss", batched, edit_ptr, orig_stride, tuple(loss_out.shape)))
+                return "cot", "scale2"
+        return Kernels
+    monkeypatch.setattr(du, "DragKernels", recorder(False))
+    monkeypatch.setattr(du, "BatchDragKernels", recorder(True))
+    ds = du.DragStuff.__new__(du.DragStuff)
+    ds.args = Namespace(num_samples=1, w_time=3, feat_layer=2, loss_type="l2", clip_denoised=True)
+    ds.device, ds.max_edits = torch.device("cpu"), 2
+    ds.model, ds.diffusion = _LoopModel(), _LoopDiffusion(log)
+    ds.r1, ds.voxel_size, ds.step_noise = 2, 0.25, None
+    ds.overlap_tail = True                           # whatever ISHAP_OVERLAP_TAIL / ISHAP_FUSED_UPDATE say in this environment
+    monkeypatch.setattr(du, "_FUSED_UPDATE", True)
+    ds.w, ds.w_batch = torch.zeros(1, 6, 4, 4), None
+    ds.feature_guidance = [torch.zeros(16, 16, dtype=torch.float16) for _ in range(3)]
+    ds.get_mesh = lambda tri_feat=None, img=None, t=0: log.append(("get_mesh", float(img.mean()), t))
+    ds.get_meshes = lambda img, t=0: log.append(("get_meshes", float(img.mean()), t))
+    loops = []
+    inner = du.DragStuff._guided_loop
+    monkeypatch.setattr(du.DragStuff, "_guided_loop", lambda self, *a: (loops.append(1), inner(self, *a))[1])
+    return ds, loops
+
+
+def test_training_and_training_batch_drive_one_guided_loop(monkeypatch):
+    """Both entry points run DragStuff._guided_loop; for K = 1 the steps they issue differ in the guidance scale (a float
+    against a device tensor) and in nothing else -- same keyword set, same loss slot, same progress values."""
+    h = np.array([[0.1, 0.2, 0.3]], np.float32)
+    runs = {}
+    for name in ("training", "training_batch"):
+        log = []
+        ds, loops = _loop_dragstuff(monkeypatch, log)
+        args = (h, h + 0.1) if name == "training" else ([h], [h + 0.1])
+        prog = list(getattr(ds, name)(*args, scale=50, cof=0.4))
+        assert loops == [1], name
+        assert prog == [0.0, 0.5, 1.0] and len(ds.last_losses) == 3 and all(l.shape == (1,) for l in ds.last_losses)
+        runs[name] = log
+    solo, batch = runs["training"], runs["training_batch"]
+    assert [e[0] for e in solo] == ["kernels", "setup", "prepare"] + ["step", "loss"] * 3 + ["get_mesh"]
+    assert [e[0] for e in batch] == ["kernels", "setup", "prepare"] + ["step", "loss"] * 3 + ["get_meshes"]
+    assert solo[0] == ("kernels", False, None, 4, 16, 2, "l2") and batch[0] == ("kernels", True, 1, 4, 16, 2, "l2")
+    assert solo[1] == ("setup", False, 0.4) and batch[1] == ("setup", True, [0.4])
+    assert solo[2] == batch[2] == ("prepare", [0, 1, 2])
+    for a, b in zip(solo[3:-1], batch[3:-1]):
+        if a[0] == "loss":                 # tap pointer, orig_stride 0 (one shape: shared guidance), a one-float loss slot
+            assert a[2:] == b[2:] == (1000, 0, (1,))
+            continue
+        assert a[1] == b[1] and set(a[2]) == set(b[2])
+        ka, kb = dict(a[2]), dict(b[2])
+        assert isinstance(ka.pop("guided_scale"), float) and torch.equal(kb.pop("guided_scale"), torch.tensor([50.0]))
+        assert callable(ka.pop("between")) and callable(kb.pop("between"))
+        assert ka == kb == dict(feat_layer=2, keep_for_backward=True, want_inter_feat=False, noise=None, overlap=True,
+                                want_noise=False)
+    assert solo[-1] == ("get_mesh", 3.0, 0) and batch[-1] == ("get_meshes", 3.0, 0)

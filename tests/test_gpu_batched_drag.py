@@ -101,6 +101,81 @@ def test_batched_drag_loss_is_bitwise_the_solo_loss(gold, loss_type, shared):
     assert int(bk.scratch[:gfx_bytes].abs().max()) == 0 and int(bk.scratch[acc_off:acc_off + 16 * E].abs().max()) == 0
 
 
+def _touched_of(bk, E, W, ld):
+    """The [E][3*W*W] touched bitmaps inside the batch scratch (the carve rule of ishap_drag_batch_scratch_bytes: grad_fx, acc,
+    nmask, touched, chan_weight, every part on a 256-byte boundary)."""
+    up = lambda v: (v + 255) // 256 * 256      # noqa: E731
+    off = up(up(up(E * W * W * ld * 8) + 16 * E) + 4 * E)
+    return bk.scratch[off:off + E * 3 * W * W].reshape(E, 3 * W * W)
+
+
+@pytest.mark.parametrize("loss_type", ["l2", "l1"])
+@pytest.mark.parametrize("cof", [0.0, 0.4])
+def test_one_edit_through_the_solo_and_the_batch_abi_gives_the_same_bits(gold, loss_type, cof):
+    """E = 1: ishap_drag_* (its own touched / nmask / acc / grad_fx / chan_weight buffers) against ishap_drag_batch_* (one carved
+    scratch) on the G7 edit -- the same kernels, so gradient, loss, cotangent, loss scale and both bits of the touched bitmap
+    are equal bit for bit."""
+    from ishapediting_amd.drag_utils import BatchDragKernels, DragKernels
+    g = gold("g7_drag")
+    edit, chmap, ld = _tap_from_planes(T(g["edit"]))
+    orig, _, _ = _tap_from_planes(T(g["orig"]))
+    W, r, voxel = 16, int(g["r1"]), float(g["voxel_size"])
+    e_d, o_d = edit.to(dev()).contiguous(), orig.to(dev()).contiguous()
+    dk = DragKernels(dev(), W=W, ld=ld, chmap=chmap, r=r, voxel=voxel, loss_type=loss_type)
+    dk.setup(g["sources"], g["targets"], cof)
+    cot_s, sc_s = dk.loss_cotangent_ptr(e_d.data_ptr(), o_d.data_ptr())
+    bk = BatchDragKernels(dev(), 1, W=W, ld=ld, chmap=chmap, r=r, voxel=voxel, loss_type=loss_type)
+    bk.setup([g["sources"]], [g["targets"]], cof)
+    cot_b, sc_b = bk.loss_cotangent_ptr(e_d.data_ptr(), o_d.data_ptr(), 0)
+    torch.cuda.synchronize()
+    assert float(dk.grad.abs().max()) > 0
+    assert torch.equal(bk.grad[0], dk.grad) and torch.equal(bk.loss, dk.loss)
+    assert torch.equal(cot_b[0], cot_s) and torch.equal(sc_b, sc_s)
+    tb, ts = _touched_of(bk, 1, W, ld)[0], dk.touched
+    assert int((ts & 1).sum()) > 0 and int((ts & 2).sum()) > 0
+    assert torch.equal(tb & 1, ts & 1) and torch.equal(tb & 2, ts & 2)
+    # the separate calls of the solo ABI (loss_grad, then the generic scaling) give the fused call's bits too
+    g2, l2_ = dk.loss_grad(e_d, o_d)
+    g2, l2_ = g2.clone(), l2_.clone()
+    cot2, sc2 = dk.scaled_cotangent()
+    torch.cuda.synchronize()
+    assert torch.equal(g2, bk.grad[0]) and torch.equal(l2_, bk.loss) and torch.equal(cot2, cot_b[0]) and torch.equal(sc2, sc_b)
+
+
+@pytest.mark.parametrize("loss_type", ["l2", "l1"])
+def test_terms_grid_clipped_by_its_cap_is_bitwise_the_solo_run(gold, loss_type):
+    """The terms pass gives edit e min(ceil(rows_e * 64 / 256), 1024) workgroups, rows_e = 3 * handles_e * side * ceil(Cc / 64) *
+    ceil(side / 5).  G7's r1 = 2 and Cc = 20: side 5, 15 rows per handle.  Edit 0 has one handle: 15 rows, 4 workgroups (not
+    clipped).  Edit 1 has H = 4096 // 15 + 1 = 274 handles: 4110 rows, 1028 workgroups wanted, clipped to 1024 -- its waves stride
+    over the rows.  Each edit is bitwise its solo run, next to a neighbour whose grid is of the other kind."""
+    from ishapediting_amd.drag_utils import BatchDragKernels
+    g = gold("g7_drag")
+    edit, chmap, ld = _tap_from_planes(T(g["edit"]))
+    orig, _, _ = _tap_from_planes(T(g["orig"]))
+    W, r, voxel, Cc = 16, int(g["r1"]), float(g["voxel_size"]), chmap.shape[1]
+    side = 2 * r + 1
+    rows_per_handle = 3 * side * ((Cc + 63) // 64) * ((side + 4) // 5)
+    H = 4096 // rows_per_handle + 1
+    blocks = [min((rows_per_handle * n * 64 + 255) // 256, 1024) for n in (1, H)]
+    wanted = [(rows_per_handle * n * 64 + 255) // 256 for n in (1, H)]
+    assert (rows_per_handle, H, wanted, blocks) == (15, 274, [4, 1028], [4, 1024])
+    gen = torch.Generator().manual_seed(11)
+    srcs = [(torch.rand(n, 3, generator=gen) * 1.6 - 0.8) for n in (1, H)]
+    tgts = [(s + (torch.rand(s.shape, generator=gen) - 0.5) * 0.4).clamp(-0.8, 0.8) for s in srcs]
+    cofs = [0.2, 0.4]
+    edits = torch.stack([edit, (edit.float() * 0.7).half()])
+    solo = [_solo(W, ld, chmap, r, voxel, loss_type, srcs[e], tgts[e], cofs[e], edits[e], orig) for e in range(2)]
+    bk = BatchDragKernels(dev(), 2, W=W, ld=ld, chmap=chmap, r=r, voxel=voxel, loss_type=loss_type)
+    bk.setup(srcs, tgts, cofs)
+    e_d, o_d = edits.to(dev()).contiguous(), orig.to(dev()).contiguous()
+    grad, loss = bk.loss_grad_ptr(e_d.data_ptr(), o_d.data_ptr(), 0)
+    torch.cuda.synchronize()
+    for e in range(2):
+        assert float(solo[e][0].abs().max()) > 0 and bool(torch.isfinite(solo[e][1]).all())
+        assert torch.equal(grad[e], solo[e][0]), e
+        assert torch.equal(loss[e:e + 1], solo[e][1]), (e, float(loss[e]), float(solo[e][1]))
+
+
 @pytest.mark.parametrize("loss_type", ["l2", "l1"])
 @pytest.mark.parametrize("cof", [0.0, 0.4])
 def test_batched_drag_loss_edit_set_up_as_g7_matches_the_reference(gold, loss_type, cof):

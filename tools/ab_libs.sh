@@ -1,5 +1,5 @@
 #!/bin/bash
-# Same-box A/B of library builds: tools/ab_libs.sh build/lib_A.so build/lib_B.so ...  (two alternating rounds of the
+# Same-box A/B of library builds: tools/ab_libs.sh build/lib_A.so build/lib_B.so ...  ($AB_ROUNDS alternating rounds, default two, of the
 # un-profiled bench, then one kernel trace per build: kernel time per guided step and the per-symbol lines matching $AB_GREP).
 set -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -8,7 +8,7 @@ mkdir -p $O
 cd $R
 cp ishapediting_amd/libishap_hip.so $O/lib_installed.so            # restored at the end: a variant must not stay installed
 trap 'cp $O/lib_installed.so $R/ishapediting_amd/libishap_hip.so' EXIT
-for round in 1 2; do
+for round in $(seq ${AB_ROUNDS:-2}); do
   for lib in "$@"; do
     cp $lib ishapediting_amd/libishap_hip.so
     v=$(timeout -k 10 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-c2 --no-c4 --no-concurrent 2> $O/bench.err | python -c "import json,sys;print(json.loads(sys.stdin.read())['value'])") || exit 1
