@@ -42,7 +42,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7 since
                             * the mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats); 8 since
                             * ishap_arap / ishap_arap_scratch_bytes / ishap_nearest_vertices; 9 since ishap_attention_run /
-                            * ishap_attention8_run; 10 since ishap_group_norm32_plan replaced ishap_group_norm32_parts */
+                            * ishap_attention8_run; 10 since ishap_group_norm32_plan replaced ishap_group_norm32_parts; 11 since
+                            * the headless renderer (ishap_camera, ishap_render_mesh, ishap_render_scratch_bytes, ishap_unproject) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -425,6 +426,43 @@ int ishap_arap(const float* rest, long long nverts, const int* tris, long long n
                void* scratch, long long scratch_bytes, void* stream);
 /* idx[i] = the vertex nearest to pts[i] (squared distance in fp64), the lowest index on ties (main.py:525-527's pick) */
 int ishap_nearest_vertices(const float* verts, long long nverts, const float* pts, long long npts, int* idx, void* stream);
+
+/* ------------------------------------------------------------------ headless rendering (main.py:345-360, 492-507, 611-612)
+ * Replaces what the reference asks of Open3D's scene widget: render_to_image, render_to_depth_image and camera.unproject.
+ * The projection, coverage, depth and shading below are this library's OWN statement (csrc/render.hip; the fp64 form is
+ * tests/render_ref.py); parity with Open3D's / Filament's pictures is unpinned.
+ * Camera: looks from `eye` at `centre`; z_view > 0 in front of the eye; square pixels, f = (height/2) / tan(fov_y/2);
+ * x_win = width/2 + f x_view / z_view, y_win = height/2 - f y_view / z_view (row 0 is the top of the picture). */
+typedef struct {
+  float eye[3], centre[3], up[3];
+  float fov_y_deg, near, far;
+} ishap_camera;
+/* Device bytes ishap_render_mesh needs: 8 per pixel of visibility buffer + 16 per vertex + 16 per triangle + 16.
+ * -1 for invalid sizes (negative or >= 2^31 counts, a picture side outside [1, 16384]). */
+long long ishap_render_scratch_bytes(long long nverts, long long ntris, int width, int height);
+/* Renders the triangle mesh (verts float[3*nverts], tris int[3*ntris], both windings drawn) into any of
+ *   rgb    uint8 [height][width][3]  colour of the nearest triangle's part, background (0, 0, 0)
+ *   depth  float [height][width]     d = far/(far-near) (1 - near/z_view) in [0, 1), background exactly 1.0f
+ *   tri_id int   [height][width]     index of the nearest triangle, the lowest index on exact depth ties, background -1
+ * (each may be null).  Coverage is sampled at pixel centres (x + 0.5, y + 0.5) with the top-left fill rule on window positions
+ * rounded to 2^-14 pixel, in exact integer arithmetic: a closed mesh has no holes and no double hits along shared edges.
+ * 1/z_view is interpolated perspective-correctly.  The result does not depend on the order of the triangles beyond their ids,
+ * and two calls give the same bits.
+ * NEAR PLANE: there is no clipping.  A triangle with ANY vertex nearer than `near` (z_view < near) is skipped whole, as is one
+ * with a vertex more than 65536 pixels from the window origin, one of zero screen area, one whose bounding box holds no pixel
+ * centre, and one with a vertex index outside [0, nverts).  Pixels at or beyond `far` are dropped.
+ * normals: float[3*nverts] or null (flat face normals).  tri_part: int[ntris] or null (every triangle is part 0); parts:
+ * float[4*nparts] rows (r, g, b, lit), colours in [0, 1].  Shading: rgb = colour * (0.25 + 0.75 |n . v|) when lit != 0, n the
+ * normalised perspective-correctly interpolated normal and v the unit vector from the surface point to the eye (two-sided);
+ * rgb = colour when lit == 0; then round(255 rgb).  parts is needed only with rgb.
+ * scratch: 16-byte aligned device buffer of ishap_render_scratch_bytes(...) bytes; a smaller scratch_bytes fails the call. */
+int ishap_render_mesh(const float* verts, long long nverts, const int* tris, long long ntris, const float* normals,
+                      const int* tri_part, const float* parts, int nparts, const ishap_camera* camera, int width, int height,
+                      void* scratch, long long scratch_bytes, unsigned char* rgb, float* depth, int* tri_id, void* stream);
+/* camera.unproject(x, y, depth, width, height) (main.py:501-505): inverts the projection above for n rows (x, y, depth) of
+ * xyd; x, y in pixels NAME THE PIXEL (its centre x + 0.5, y + 0.5 is unprojected), as the GUI's integer event.x / event.y do.
+ * world: float[3*n].  Computed in fp64. */
+int ishap_unproject(const ishap_camera* camera, int width, int height, const float* xyd, long long n, float* world, void* stream);
 
 /* ------------------------------------------------------------------ measurement aid (bench.py roofline leg)
  * Brackets every implicit-GEMM launch with HIP events on its own stream between begin and end.

@@ -70,6 +70,11 @@ class DecoderWeightsC(C.Structure):
                 ("w3", c_void_p), ("b3", c_void_p)]
 
 
+class CameraC(C.Structure):
+    _fields_ = [("eye", C.c_float * 3), ("centre", C.c_float * 3), ("up", C.c_float * 3), ("fov_y_deg", C.c_float),
+                ("near", C.c_float), ("far", C.c_float)]
+
+
 # every symbol include/ishap.h declares: (restype, argtypes)
 SYMBOLS = {
     "ishap_last_error": (C.c_char_p, []),
@@ -154,6 +159,11 @@ SYMBOLS = {
     "ishap_arap": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_double,
                              C.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
     "ishap_nearest_vertices": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p]),
+    "ishap_render_scratch_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    "ishap_render_mesh": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, c_void_p, C.c_int,
+                                    C.POINTER(CameraC), C.c_int, C.c_int, c_void_p, C.c_longlong, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    "ishap_unproject": (C.c_int, [C.POINTER(CameraC), C.c_int, C.c_int, c_void_p, C.c_longlong, c_void_p, c_void_p]),
     "ishap_profile_begin": (C.c_int, []),
     "ishap_profile_end": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
     "ishap_profile_shapes": (C.c_int, [C.c_char_p, C.c_int]),
@@ -191,9 +201,10 @@ def lib():
             fn.argtypes = args
         # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run;
         # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats;
-        # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run; 10: ishap_group_norm32_plan
-        if l.ishap_version() < 10:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 10): rebuild with `python -m ishapediting_amd.build`")
+        # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run; 10: ishap_group_norm32_plan;
+        # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject
+        if l.ishap_version() < 11:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 11): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

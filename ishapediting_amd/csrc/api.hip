@@ -4,6 +4,7 @@
 #include "ddpm.h"
 #include "decode.h"
 #include "drag.h"
+#include "render.h"
 
 static thread_local std::string g_err;
 void ishap_set_error(const std::string& msg) { g_err = msg; }
@@ -430,6 +431,37 @@ int ishap_triplane_decode_grid(const float* planes, int S, const ishap_decoder_w
   ISHAP_REQUIRE(planes && axis && volume && res > 0, "null argument");
   d.planes = planes; d.S = S; d.lin = axis; d.res = res; d.npts = (long long)res * res * res; d.out = volume;
   return triplane_decode_launch(d, (hipStream_t)stream);
+}
+
+// ---- headless rendering (csrc/render.hip) ----
+long long ishap_render_scratch_bytes(long long nverts, long long ntris, int width, int height) {
+  return render_scratch_bytes(nverts, ntris, width, height);
+}
+
+int ishap_render_mesh(const float* verts, long long nverts, const int* tris, long long ntris, const float* normals,
+                      const int* tri_part, const float* parts, int nparts, const ishap_camera* camera, int width, int height,
+                      void* scratch, long long scratch_bytes, unsigned char* rgb, float* depth, int* tri_id, void* stream) {
+  ISHAP_REQUIRE(camera, "render_mesh: null camera");
+  RenderArgs a;
+  ISHAP_TRY(render_camera(camera->eye, camera->centre, camera->up, camera->fov_y_deg, camera->near, camera->far, width, height, a.cam));
+  const long long need = render_scratch_bytes(nverts, ntris, width, height);
+  ISHAP_REQUIRE(need > 0, "render_mesh: 0 <= nverts, ntris < 2^31");
+  ISHAP_REQUIRE(scratch && scratch_bytes >= need, "render_mesh: scratch smaller than ishap_render_scratch_bytes(nverts, ntris, width, height)");
+  ISHAP_REQUIRE(((uintptr_t)scratch & 15) == 0, "render_mesh: scratch must be 16-byte aligned");
+  ISHAP_REQUIRE(ntris == 0 || nverts == 0 || (verts && tris), "render_mesh: null verts / tris");
+  ISHAP_REQUIRE(!rgb || (parts && nparts > 0), "render_mesh: rgb needs at least one part");
+  a.verts = verts; a.tris = tris; a.normals = normals; a.tri_part = tri_part; a.parts = parts;
+  a.nverts = nverts; a.ntris = ntris; a.nparts = nparts; a.width = width; a.height = height;
+  a.scratch = scratch; a.rgb = rgb; a.depth = depth; a.tri_id = tri_id;
+  return render_mesh_launch(a, (hipStream_t)stream);
+}
+
+int ishap_unproject(const ishap_camera* camera, int width, int height, const float* xyd, long long n, float* world, void* stream) {
+  ISHAP_REQUIRE(camera && n >= 0 && (n == 0 || (xyd && world)), "unproject arguments");
+  RenderCam cam;
+  ISHAP_TRY(render_camera(camera->eye, camera->centre, camera->up, camera->fov_y_deg, camera->near, camera->far, width, height, cam));
+  if (n == 0) return 0;
+  return render_unproject_launch(cam, xyd, n, world, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -729,7 +729,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 10; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 11; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
@@ -737,6 +737,7 @@ int ishap_version(void) { return 10; }  // 2: ishap_mesh_smooth takes the scratc
                                         // 8: ARAP deformation (ishap_arap, ishap_arap_scratch_bytes, ishap_nearest_vertices)
                                         // 9: one attention launch through the ABI (ishap_attention_run, ishap_attention8_run)
                                         // 10: ishap_group_norm32_plan replaces ishap_group_norm32_parts
+                                        // 11: headless rendering (ishap_render_mesh, ishap_render_scratch_bytes, ishap_unproject)
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");

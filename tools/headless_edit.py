@@ -1,0 +1,148 @@
+"""A drag edit without a window: generate a shape, pick handles by pixel, edit, save before / after pictures.
+
+What the reference's GUI does with Open3D's scene widget (main.py:345-360, 492-517, 539-590, 611-612), with every stage on the
+device: a synthetic-weight DragStuff denoises a latent (update_latent_params), the camera is fitted to the mesh, K handle
+sources are picked by pixel from the depth picture (render.pick: unproject + nearest vertex), the targets are the sources
+moved by --offset, training() runs the guided loop, and before.png / after.png show the mesh with the red / blue handle
+spheres and green arrows.  With synthetic weights the decoded shape is noise; the path is the point.
+
+  python tools/headless_edit.py --out /tmp/edit [--handles 3] [--num_steps 6] [--w_time 3] [--res 64] [--size 512]
+
+--time instead measures the renderer alone (device events around `--repeat` calls after a warm-up, medians):
+  the 256^3 sphere mesh (~300 k triangles of a few pixels each) at 1024 x 1024, and 2 picture-filling triangles at 1024 x 1024
+  (the second shows that large triangles do not serialise on one lane), next to the bytes each call has to move
+  (vertices + triangles + 8 B per pixel of visibility + the three outputs).  Written to profiles/render_times.json.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def pick_sources(mesh, camera, depth, k, seed):
+    """k distinct surface pixels (seeded) -> [(vertex position, vertex index, depth, (x, y))]"""
+    from ishapediting_amd.render import pick
+    ys, xs = np.nonzero(depth.cpu().numpy() < 1.0)
+    if len(ys) < k:
+        raise RuntimeError(f"only {len(ys)} surface pixels for {k} handles")
+    out, seen = [], set()
+    for j in np.random.default_rng(seed).permutation(len(ys)):
+        pos, idx, d = pick(mesh, camera, depth, int(xs[j]), int(ys[j]))
+        if idx not in seen:
+            seen.add(idx)
+            out.append((pos, idx, d, (int(xs[j]), int(ys[j]))))
+        if len(out) == k:
+            break
+    return out
+
+
+def edit(a):
+    from ishapediting_amd import synthetic
+    from ishapediting_amd.drag_utils import DragStuff, get_args
+    from ishapediting_amd.render import Camera, edit_parts, render_mesh, save_picture
+    from ishapediting_amd.unet_spec import full_config
+    dev = torch.device("cuda", 0)
+    os.makedirs(a.out, exist_ok=True)
+    args = get_args(["--w_time", str(a.w_time), "--num_steps", str(a.num_steps), "--shape_resolution", str(a.res)])
+    ds = DragStuff(dev, args=args)
+    ds.load_weights(synthetic.round_torso_to_fp16(synthetic.unet_state_dict(full_config(), 1234)), synthetic.decoder_state_dict(4321),
+                    -0.05 * np.ones(96, np.float32), 0.05 * np.ones(96, np.float32))
+    ds.update_latent_params(img=synthetic.latent(0))
+    before = ds.mesh0
+    v = before.vertices
+    if v.shape[0] == 0:
+        raise RuntimeError("the decoded volume has no surface")
+    cam = Camera.fit(v.min(dim=0).values.cpu().numpy(), v.max(dim=0).values.cpu().numpy(), fov=60, aspect=1.0)   # main.py:611-612
+    first = render_mesh(before, cam, a.size, a.size)
+    picked = pick_sources(before, cam, first.depth, a.handles, a.seed)
+    sources = np.stack([p[0] for p in picked])
+    targets = sources + np.asarray(a.offset, np.float32)
+    for pos, idx, d, px in picked:
+        print(f"pick pixel {px}: vertex {idx} at {pos.tolist()}, depth {d:.6f}")
+    save_picture(os.path.join(a.out, "before.png"), render_mesh(edit_parts(before, sources, targets), cam, a.size, a.size))
+    for _ in ds.training(sources, targets, scale=a.scale, cof=a.cof):
+        pass
+    save_picture(os.path.join(a.out, "after.png"), render_mesh(edit_parts(ds.mesh, sources, targets), cam, a.size, a.size))
+    torch.cuda.synchronize()
+    print(json.dumps({"out": a.out, "handles": a.handles, "before_triangles": int(before.triangles.shape[0]),
+                      "after_triangles": int(ds.mesh.triangles.shape[0]), "camera": {"eye": list(cam.eye), "near": cam.near, "far": cam.far}}))
+
+
+def timed(fn, warmup, repeat):
+    """median and spread, in ms, of `repeat` calls after `warmup`, each between two device events"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeat):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    ms = np.sort(np.asarray(ms))
+    return {"median_ms": float(np.median(ms)), "min_ms": float(ms[0]), "p90_ms": float(ms[int(0.9 * (len(ms) - 1))]), "calls": repeat}
+
+
+def time_renderer(a):
+    from ishapediting_amd.mesh import extract_surface
+    from ishapediting_amd.render import Camera, render_arrays
+    dev = torch.device("cuda", 0)
+    side, res, r = 1024, 256, 90.4
+    ax = torch.arange(res, dtype=torch.float32) - (res - 1) / 2
+    x, y, z = torch.meshgrid(ax, ax, ax, indexing="ij")
+    v, f = extract_surface((r - torch.sqrt(x * x + y * y + z * z)).to(dev))
+    v = (v / (res - 1) * 2 - 1).contiguous()
+    cam = Camera(eye=(0.4, 0.3, 2.5), centre=(0, 0, 0), fov=60, near=0.1, far=10)
+    quad_v = torch.tensor([[-3, -3, 0], [3, -3, 0], [3, 3, 0], [-3, 3, 0]], dtype=torch.float32, device=dev)
+    quad_f = torch.tensor([[0, 1, 2], [0, 2, 3]], dtype=torch.int32, device=dev)
+
+    def floor_bytes(nv, nt):        # vertices + triangles + visibility + rgb, depth, tri_id
+        return 12 * nv + 12 * nt + side * side * (8 + 3 + 4 + 4)
+    out = {"picture": [side, side], "method": "device events around one render_arrays call (scratch and output allocation included), "
+           f"median of {a.repeat} after {a.warmup} warm-up calls", "device": torch.cuda.get_device_name(0)}
+    covered = render_arrays(v, f, cam, side, side)
+    out["mesh"] = {"triangles": int(f.shape[0]), "vertices": int(v.shape[0]), "coverage": float((covered.tri_id >= 0).float().mean()),
+                   "floor_bytes": floor_bytes(v.shape[0], f.shape[0]), **timed(lambda: render_arrays(v, f, cam, side, side), a.warmup, a.repeat)}
+    covered = render_arrays(quad_v, quad_f, cam, side, side)
+    out["full_screen_quad"] = {"triangles": 2, "coverage": float((covered.tri_id >= 0).float().mean()), "floor_bytes": floor_bytes(4, 2),
+                               **timed(lambda: render_arrays(quad_v, quad_f, cam, side, side), a.warmup, a.repeat)}
+    path = a.time_out or os.path.join(ROOT, "profiles", "render_times.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(out))
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--out", default="headless_edit_out")
+    p.add_argument("--handles", type=int, default=3)
+    p.add_argument("--offset", type=float, nargs=3, default=(0.0, 0.15, 0.0))
+    p.add_argument("--num_steps", type=int, default=6)
+    p.add_argument("--w_time", type=int, default=3)
+    p.add_argument("--res", type=int, default=64)
+    p.add_argument("--size", type=int, default=512)
+    p.add_argument("--scale", type=float, default=1200.0)
+    p.add_argument("--cof", type=float, default=0.4)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--time", action="store_true", help="measure the renderer instead of running an edit")
+    p.add_argument("--time_out", default=None, help="where --time writes its JSON (default profiles/render_times.json)")
+    p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--repeat", type=int, default=200)
+    a = p.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("headless_edit needs the GPU: rendering has no CPU fallback")
+    (time_renderer if a.time else edit)(a)
+
+
+if __name__ == "__main__":
+    main()
