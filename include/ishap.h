@@ -43,7 +43,10 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * the mesh metrics (ishap_mesh_distance, ishap_hausdorff, ishap_group_field_stats); 8 since
                             * ishap_arap / ishap_arap_scratch_bytes / ishap_nearest_vertices; 9 since ishap_attention_run /
                             * ishap_attention8_run; 10 since ishap_group_norm32_plan replaced ishap_group_norm32_parts; 11 since
-                            * the headless renderer (ishap_camera, ishap_render_mesh, ishap_render_scratch_bytes, ishap_unproject) */
+                            * the headless renderer (ishap_camera, ishap_render_mesh, ishap_render_scratch_bytes, ishap_unproject);
+                            * 12 since the winding numbers (ishap_mesh_winding, ishap_cloud_winding, ishap_cloud_areas,
+                            * ishap_winding_scratch_bytes) and sdf == 2 / sdf == -2 of ishap_mesh_distance (sign by winding
+                            * number for a counter-clockwise / a clockwise mesh; before 12 both values meant parity) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -392,10 +395,15 @@ int ishap_mesh_occupancy(const float* verts, const int* tris, long long ntris, c
  * Replaces the reference's Open3D RaycastingScene / cKDTree queries behind calc_implicit_field, calc_hausdorff, calc_iou,
  * calc_local_distance and calc_mesh_points_normals.
  * dist[i] = distance from pts[i] to the nearest triangle (exact fp32 closest point: vertex, edge and face regions), signed
- * when sdf != 0: negative inside, inside by the +x ray parity of ishap_mesh_occupancy; tri[i] = the nearest triangle, the
+ * when sdf != 0: negative inside, inside by the +x ray parity of ishap_mesh_occupancy (sdf == 2, ABI 12: inside where the
+ * winding number of ishap_mesh_winding exceeds 0.5 -- the sign survives holes, doubled faces and interior sheets; the
+ * mesh is counter-clockwise seen from outside, sdf == -2 is the same for a clockwise mesh: inside where w < -0.5); tri[i] = the nearest triangle, the
  * lowest index on exact ties (may be null).  Deterministic.  scratch: ishap_mesh_distance_scratch_bytes(ntris) device
- * bytes (one box per tile of 256 triangles, 32 bytes each); ntris < 2^31. */
+ * bytes (one box per tile of 256 triangles, 32 bytes each); ntris < 2^31.  sdf == 2 / -2 needs the larger
+ * ishap_mesh_distance_scratch_bytes_sdf(ntris, npts, 2) (the boxes, then the winding number's part sums); for every other sdf
+ * (0: unsigned; any other value: parity, as 1) that function returns ishap_mesh_distance_scratch_bytes(ntris).  Both return -1 on invalid sizes. */
 long long ishap_mesh_distance_scratch_bytes(long long ntris);
+long long ishap_mesh_distance_scratch_bytes_sdf(long long ntris, long long npts, int sdf);
 int ishap_mesh_distance(const float* verts, const int* tris, long long ntris, const float* pts, long long npts, int sdf,
                         float* dist, int* tri, void* scratch, long long scratch_bytes, void* stream);
 /* out2[0] = max over a of min_b |a-b|^2, out2[1] = max over b of min_a |a-b|^2 (squared Hausdorff distances, device floats);
@@ -407,6 +415,30 @@ int ishap_hausdorff(const float* a, long long na, const float* b, long long nb, 
  * order, double accumulators: bitwise repeatable. */
 int ishap_group_field_stats(const float* fa, const float* fb, int groups, long long per_group, int occupancy, float* out,
                             void* stream);
+
+/* ------------------------------------------------------------------ generalized winding number (ABI 12)
+ * Inside / outside that does not need a closed surface: the reference's data preparation assumes watertight meshes
+ * (drag_utils.py:437-440) or starts from oriented point clouds (meshProcess.py cloud2mesh: pointcloud.npz with `points` and
+ * `normals`).  Brute force over (query, primitive) pairs, fp32, compensated sums.
+ * ishap_mesh_winding: w[q] = 1/(4 pi) sum_f Omega_f(q), Omega by van Oosterom-Strackee (Jacobson et al. 2013): exactly 1
+ *   inside / 0 outside a closed mesh whose triangles are counter-clockwise seen from outside (-1 inside when they are
+ *   clockwise), k inside k nested copies, and a smooth value in between where the surface is open.  A triangle without
+ *   area contributes 0.
+ * ishap_cloud_winding: w[q] = 1/(4 pi) sum_i areas[i] (points[i] - q) . normals[i] / r^3 with
+ *   r^2 = max(|points[i] - q|^2, areas[i] / (2 pi)) (Barill et al. 2018; the clamp bounds one sample's share by 1/2).
+ *   normals: unit, outward.  areas: the surface area each sample stands for (ishap_cloud_areas, or the caller's own).
+ * ishap_cloud_areas: areas[i] = max(pi d_k(i)^2 / k, 1e-12), d_k = distance to the k-th nearest OTHER point (points equal
+ *   to point i count, at distance 0); 1 <= k <= 16, k < npoints.
+ * With few queries the primitive range is split over workgroups; the part sums go to `scratch`
+ * (ishap_winding_scratch_bytes(nprims, npts) device bytes, -1 on negative counts; a smaller scratch_bytes fails the call)
+ * and are added in part order.  The split depends on (nprims, npts) only and there are no float atomics: a call repeats
+ * bit for bit, and a query's value does not depend on where it stands in `pts`. */
+long long ishap_winding_scratch_bytes(long long nprims, long long npts);
+int ishap_mesh_winding(const float* verts, const int* tris, long long ntris, const float* pts, long long npts, float* w,
+                       void* scratch, long long scratch_bytes, void* stream);
+int ishap_cloud_winding(const float* points, const float* normals, const float* areas, long long npoints, const float* pts,
+                        long long npts, float* w, void* scratch, long long scratch_bytes, void* stream);
+int ishap_cloud_areas(const float* points, long long npoints, int k, float* areas, void* stream);
 
 /* ------------------------------------------------------------------ ARAP deformation (meshProcess.py:222-236)
  * Replaces the reference's Open3D deform_as_rigid_as_possible: Sorkine & Alexa 2007, spokes energy, cotangent weights

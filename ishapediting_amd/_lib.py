@@ -153,7 +153,14 @@ SYMBOLS = {
     "ishap_mesh_distance_scratch_bytes": (C.c_longlong, [C.c_longlong]),
     "ishap_mesh_distance": (C.c_int, [c_void_p, c_void_p, C.c_longlong, c_void_p, C.c_longlong, C.c_int, c_void_p, c_void_p,
                                       c_void_p, C.c_longlong, c_void_p]),
+    "ishap_mesh_distance_scratch_bytes_sdf": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int]),
     "ishap_hausdorff": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, c_void_p]),
+    "ishap_winding_scratch_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong]),
+    "ishap_mesh_winding": (C.c_int, [c_void_p, c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, C.c_longlong,
+                                     c_void_p]),
+    "ishap_cloud_winding": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p,
+                                      C.c_longlong, c_void_p]),
+    "ishap_cloud_areas": (C.c_int, [c_void_p, C.c_longlong, C.c_int, c_void_p, c_void_p]),
     "ishap_group_field_stats": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_longlong, C.c_int, c_void_p, c_void_p]),
     "ishap_arap_scratch_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_longlong]),
     "ishap_arap": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_double,
@@ -202,9 +209,10 @@ def lib():
         # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run;
         # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats;
         # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run; 10: ishap_group_norm32_plan;
-        # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject
-        if l.ishap_version() < 11:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 11): rebuild with `python -m ishapediting_amd.build`")
+        # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject; 12: ishap_mesh_winding / ishap_cloud_winding /
+        # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance
+        if l.ishap_version() < 12:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 12): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

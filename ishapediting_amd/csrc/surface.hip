@@ -13,6 +13,7 @@
 //           (owner voxel, edge type) -> vertex index lookup.
 #include "common.h"
 #include "mc_table.h"
+#include "winding.h"
 
 namespace {
 
@@ -821,17 +822,36 @@ extern "C" long long ishap_mesh_distance_scratch_bytes(long long ntris) {
   return (ntris + MD_TILE - 1) / MD_TILE * 2 * (long long)sizeof(float4);
 }
 
+// sdf == 2 / -2 adds the winding number's part sums behind the tile boxes (256-byte aligned); every other value is what
+// ishap_mesh_distance makes of it: unsigned (0) or signed by parity
+extern "C" long long ishap_mesh_distance_scratch_bytes_sdf(long long ntris, long long npts, int sdf) {
+  if (ntris < 0 || npts < 0) return -1;
+  const long long boxes = ishap_mesh_distance_scratch_bytes(ntris);
+  if (sdf != 2 && sdf != -2) return boxes;
+  return (boxes + 255) / 256 * 256 + ishap_winding_bytes(ntris, npts);
+}
+
 extern "C" int ishap_mesh_distance(const float* verts, const int* tris, long long ntris, const float* pts, long long npts, int sdf,
                                    float* dist, int* tri, void* scratch, long long scratch_bytes, void* stream) {
   ISHAP_REQUIRE(verts && tris && pts && dist && scratch && ntris > 0 && npts > 0, "mesh_distance arguments");
   ISHAP_REQUIRE(scratch_bytes >= ishap_mesh_distance_scratch_bytes(ntris),
                 "mesh_distance: scratch smaller than ishap_mesh_distance_scratch_bytes(ntris)");
   ISHAP_REQUIRE(ntris < (1ll << 31), "mesh_distance: triangle indices must fit 31 bits");
+  const bool winding = sdf == 2 || sdf == -2;
+  ISHAP_REQUIRE(!winding || scratch_bytes >= ishap_mesh_distance_scratch_bytes_sdf(ntris, npts, 2),
+                "mesh_distance: sdf == 2 / -2 needs ishap_mesh_distance_scratch_bytes_sdf(ntris, npts, 2) bytes of scratch");
   hipStream_t s = (hipStream_t)stream;
   const unsigned tiles = (unsigned)((ntris + MD_TILE - 1) / MD_TILE), blocks = (unsigned)((npts + MD_TILE - 1) / MD_TILE);
   float4* box = (float4*)scratch;
-  // the sign is ishap_mesh_occupancy's: its 0/1 result lands in dist and the distance kernel reads it back per point
-  if (sdf) hipLaunchKernelGGL(occupancy_kernel, dim3(blocks), dim3(256), 0, s, verts, tris, ntris, pts, npts, dist);
+  // the sign is an inside flag per point: its 0/1 value lands in dist and the distance kernel reads it back per point.
+  // sdf == 2: inside where the winding number exceeds 0.5 (-2: is below -0.5, a clockwise mesh); any other non-zero sdf:
+  // ishap_mesh_occupancy's ray parity
+  if (winding) {
+    char* wn = (char*)scratch + (ishap_mesh_distance_scratch_bytes(ntris) + 255) / 256 * 256;
+    ishap_winding_launch_mesh(verts, tris, ntris, pts, npts, dist, sdf > 0 ? 1 : -1, wn, s);
+  } else if (sdf) {
+    hipLaunchKernelGGL(occupancy_kernel, dim3(blocks), dim3(256), 0, s, verts, tris, ntris, pts, npts, dist);
+  }
   hipLaunchKernelGGL(mesh_tile_box_kernel, dim3(tiles), dim3(MD_TILE), 0, s, verts, tris, ntris, box);
   hipLaunchKernelGGL(mesh_distance_kernel, dim3(blocks), dim3(MD_TILE), 0, s, verts, tris, ntris, (const float4*)box, pts, npts,
                      sdf ? (const float*)dist : nullptr, dist, tri);

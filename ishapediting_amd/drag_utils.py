@@ -597,10 +597,20 @@ class DragStuff:
         self.get_meshes(img=img, t=stop_time)
 
     # ------------------------------------------------------------------ real shapes (:401-471, :552-566)
+    def _cloud_samples(self, cloud, center, generator=None):
+        """occupancy samples of an oriented point cloud ((points, normals) or an .npz path) by winding number"""
+        pts, nrm = mesh_backend.load_cloud(cloud)
+        return mesh_backend.sample_cloud_occupancy(pts, nrm, self.args.points_size, self.args.points_uniform_ratio, center=center,
+                                                   generator=generator, device=self.device)
+
     def train_triplane(self, mesh=None, mesh_path=None, center_mesh=True, tri_feat_path=None, path="./",
-                       points=None, occupancies=None):
+                       points=None, occupancies=None, occupancy="parity", cloud=None):
         """drag_utils.py:401-471.  `points`/`occupancies` (float32 [P,3] / [P,1]) replace the Open3D raycast
-        sampling (:418-440) when given; the mesh-file route needs Open3D like the reference."""
+        sampling (:418-440) when given; the mesh-file route needs Open3D like the reference.  occupancy: how the mesh's
+        samples are labelled, "parity" or "winding" (mesh.sample_occupancy; "winding" for meshes that are not watertight).
+        cloud: an oriented point cloud, a (points, normals) pair or the path of an .npz with those arrays, labelled by its
+        winding number instead of a mesh (mesh.sample_cloud_occupancy; `center_mesh` applies to its points)."""
+        mesh_backend._check_choice("occupancy", occupancy, mesh_backend.OCCUPANCY_METHODS)
         if tri_feat_path is not None:
             img = th.tensor(np.load(tri_feat_path), device=self.device)
             if img.dim() == 3:        # a CHW file (generate.py's triplanes/{i}.npy layout): the model wants a batch axis
@@ -609,9 +619,12 @@ class DragStuff:
             self.mesh0 = copy.deepcopy(self.mesh)
             self.latent_inversion(tri_feat=img)
             return
+        if points is None and cloud is not None:
+            points, occupancies = self._cloud_samples(cloud, center_mesh)
         if points is None:
             points, occupancies = mesh_backend.sample_occupancy(mesh, mesh_path, center_mesh, self.args.points_size,
-                                                                self.args.points_uniform_ratio, device=self.device)
+                                                                self.args.points_uniform_ratio, device=self.device,
+                                                                occupancy=occupancy)
             if points is None:
                 return
         points = th.as_tensor(np.asarray(points), dtype=th.float32).to(self.device)
@@ -674,20 +687,27 @@ class DragStuff:
         return img
 
     def train_triplane_opt(self, mesh=None, mesh_path=None, center_mesh=True, path="./", points=None, occupancies=None,
-                           stats=None, epochs=20, batch_size=40000, lr=1e-3, seed=None, batch_fn=None):
+                           stats=None, epochs=20, batch_size=40000, lr=1e-3, seed=None, batch_fn=None, occupancy="parity",
+                           cloud=None):
         """drag_utils.py:473-550: fit the three planes to the mesh's occupancy directly (Adam on BCE + 0.3 pair mse +
         0.001 l2reg + 0.01 tvreg, the MLP frozen; no diffusion model).  `points`/`occupancies` replace the mesh sampling;
         `stats=(means, stds)` replaces {args.stats_dir}/means.npy, stds.npy (the init is randn * stds + means); `seed`
         seeds the one device generator behind the init, the per-epoch permutations and the random pairs;
         `batch_fn(step) -> (idx, r, noise)` injects a step's batch.  Saves tri_feat_opt.npy and mesh_opt.obj under `path`,
         leaves the fitted planes in decoder.embeddings and the per-step (bce, mse, l2reg, tvreg) in last_losses [steps, 4],
-        and returns the normalised latent (planes - middle) / range [1,96,S,S].  The drag state is not touched."""
+        and returns the normalised latent (planes - middle) / range [1,96,S,S].  The drag state is not touched.
+        `occupancy` ("parity" | "winding") and `cloud` as train_triplane: how a mesh's samples are labelled, or an
+        oriented point cloud to label instead of a mesh."""
         from .triplane_decoder import fit_triplanes, planes_to_latent
+        mesh_backend._check_choice("occupancy", occupancy, mesh_backend.OCCUPANCY_METHODS)
         means, stds = load_triplane_stats(stats, self.args.stats_dir)
-        if points is None:      # a seeded call samples from torch.Generator().manual_seed(seed)
+        sample_gen = None if seed is None else th.Generator().manual_seed(int(seed))   # a seeded call samples from it
+        if points is None and cloud is not None:
+            points, occupancies = self._cloud_samples(cloud, center_mesh, sample_gen)
+        if points is None:
             points, occupancies = mesh_backend.sample_occupancy(
                 mesh, mesh_path, center_mesh, self.args.points_size, self.args.points_uniform_ratio, device=self.device,
-                generator=None if seed is None else th.Generator().manual_seed(int(seed)))
+                generator=sample_gen, occupancy=occupancy)
             if points is None:
                 return None
         points = th.as_tensor(np.asarray(points) if not th.is_tensor(points) else points, dtype=th.float32).to(self.device)

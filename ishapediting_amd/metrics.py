@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .mesh import OccupancyMesh, mesh_arrays, mesh_chamfer, mesh_occupancy, read_obj, sample_surface_points
+from .mesh import (OCCUPANCY_METHODS, OccupancyMesh, _check_choice, mesh_arrays, mesh_chamfer, mesh_occupancy, orientation_sign,
+                   read_obj, sample_surface_points)
 
 METRICS = ("IoU", "L2", "CD")
 
@@ -50,10 +51,12 @@ def _points(points, dev) -> torch.Tensor:
     return p.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
 
 
-def mesh_distance(verts: torch.Tensor, tris: torch.Tensor, points: torch.Tensor, sdf: bool = True):
+def mesh_distance(verts: torch.Tensor, tris: torch.Tensor, points: torch.Tensor, sdf=True, orientation: str = "auto"):
     """(distance [P] float32, closest triangle [P] int32) of device points to a device mesh: signed (negative inside,
-    inside by the ray parity of mesh_occupancy) when `sdf`, else unsigned.  The closest triangle is the lowest index on
-    exact ties."""
+    inside by the ray parity of mesh_occupancy) when `sdf`, else unsigned.  sdf=2: the sign comes from the winding number
+    instead (inside where mesh_winding_number > 0.5, negated first when mesh.orientation_sign(..., orientation) is -1), for
+    meshes that are not watertight.  The closest triangle is the lowest index on exact ties."""
+    winding = sdf is not True and sdf is not False and int(sdf) == 2
     dev = verts.device
     v = verts.detach().to(torch.float32).contiguous()
     t = tris.detach().to(device=dev, dtype=torch.int32).contiguous()
@@ -65,10 +68,11 @@ def mesh_distance(verts: torch.Tensor, tris: torch.Tensor, points: torch.Tensor,
     if t.shape[0] == 0:
         raise ValueError("mesh_distance: the mesh has no triangles")
     L = _lib.lib()
-    nbytes = int(L.ishap_mesh_distance_scratch_bytes(t.shape[0]))
+    mode = 2 * orientation_sign(v, t, orientation) if winding else int(bool(sdf))
+    nbytes = int(L.ishap_mesh_distance_scratch_bytes_sdf(t.shape[0], p.shape[0], mode))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(L.ishap_mesh_distance(v.data_ptr(), t.data_ptr(), t.shape[0], p.data_ptr(), p.shape[0], int(bool(sdf)),
+        _lib.check(L.ishap_mesh_distance(v.data_ptr(), t.data_ptr(), t.shape[0], p.data_ptr(), p.shape[0], mode,
                                          dist.data_ptr(), tri.data_ptr(), scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
     return dist, tri
 
@@ -102,14 +106,16 @@ def hausdorff_sq(pa: torch.Tensor, pb: torch.Tensor):
 # ---------------------------------------------------------------- meshProcess.py's call surface
 
 
-def calc_implicit_field(mesh, points, sdf: bool = True, device=None) -> torch.Tensor:
+def calc_implicit_field(mesh, points, sdf: bool = True, device=None, sign: str = "parity") -> torch.Tensor:
     """meshProcess.py:7-14: the signed distance of every point (negative inside), or with sdf=False the 0/1 occupancy.
+    sign: where inside comes from -- "parity" (ray crossings, closed meshes) or "winding" (winding number > 0.5, any mesh).
     Returns a [P] float32 device tensor."""
+    _check_choice("sign", sign, OCCUPANCY_METHODS)
     v, t = device_mesh(mesh, device)
     p = _points(points, v.device)
     if sdf:
-        return mesh_distance(v, t, p, sdf=True)[0]
-    return mesh_occupancy(v, t, p)
+        return mesh_distance(v, t, p, sdf=2 if sign == "winding" else True)[0]
+    return mesh_occupancy(v, t, p, method=sign)
 
 
 def calc_chamfer(mesh_a, mesh_b, point_num: int, seed: int = 0, device=None) -> float:
@@ -145,23 +151,26 @@ def iou_points(mesh_a, mesh_b, point_num: int, seed: int = 0, device=None) -> to
     return torch.cat([uniform, pa, pb], dim=0).contiguous()
 
 
-def calc_iou(mesh_a, mesh_b, point_num: int, seed: int = 0, device=None) -> float:
-    """meshProcess.py:59-77: |A and B| / |A or B| over iou_points(mesh_a, mesh_b, point_num, seed), inside by occupancy."""
+def calc_iou(mesh_a, mesh_b, point_num: int, seed: int = 0, device=None, sign: str = "parity") -> float:
+    """meshProcess.py:59-77: |A and B| / |A or B| over iou_points(mesh_a, mesh_b, point_num, seed), inside by occupancy
+    (sign: "parity" or "winding", as calc_implicit_field)."""
+    _check_choice("sign", sign, OCCUPANCY_METHODS)
     va, ta = device_mesh(mesh_a, device)
     vb, tb = device_mesh(mesh_b, va.device)
     pts = iou_points((va, ta), (vb, tb), point_num, seed)
-    oa, ob = mesh_occupancy(va, ta, pts), mesh_occupancy(vb, tb, pts)
+    oa, ob = mesh_occupancy(va, ta, pts, method=sign), mesh_occupancy(vb, tb, pts, method=sign)
     return float(field_stats(oa, ob, 1, occupancy=True)[0])
 
 
 def calc_local_distance(mesh_a, mesh_b, points_a, points_b, r: float, point_num: int, metric: str = "IoU", seed: int = 0,
-                        device=None) -> float:
+                        device=None, sign: str = "parity") -> float:
     """meshProcess.py:80-105: for every handle i, the signed distance of mesh_a at points_a[i] + offsets against that of
     mesh_b at points_b[i] + offsets (one set of `point_num` offsets uniform in [-r, r]^3, shared by all handles); the mean
     over the handles of
       'IoU'  |A and B| / |A or B| with inside = signed distance < 0 (NaN when neither mesh has a sample inside),
       'L2'   the mean of (d_b - d_a)^2,
       'CD'   0: the reference's branch is `pass`, so every handle contributes nothing.
+    sign: "parity" or "winding", where the signed distances take their sign from (calc_implicit_field).
     All handles go to the device in one distance launch per mesh and one statistics launch."""
     pa = points_a if torch.is_tensor(points_a) else np.asarray(points_a)
     pb = points_b if torch.is_tensor(points_b) else np.asarray(points_b)
@@ -169,6 +178,7 @@ def calc_local_distance(mesh_a, mesh_b, points_a, points_b, r: float, point_num:
         raise ArithmeticError("The 'points_a' and 'points_b' should have the same shape!")
     if metric not in METRICS:
         raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
+    _check_choice("sign", sign, OCCUPANCY_METHODS)
     if metric == "CD":
         return 0.0
     va, ta = device_mesh(mesh_a, device)
@@ -180,8 +190,9 @@ def calc_local_distance(mesh_a, mesh_b, points_a, points_b, r: float, point_num:
     offs = ((torch.rand((point_num, 3), generator=g) * 2 - 1) * r).to(dev)
     qa = (ha[:, None, :] + offs[None]).reshape(-1, 3).contiguous()
     qb = (hb[:, None, :] + offs[None]).reshape(-1, 3).contiguous()
-    da = mesh_distance(va, ta, qa, sdf=True)[0]
-    db = mesh_distance(vb, tb, qb, sdf=True)[0]
+    sdf = 2 if sign == "winding" else True
+    da = mesh_distance(va, ta, qa, sdf=sdf)[0]
+    db = mesh_distance(vb, tb, qb, sdf=sdf)[0]
     out = field_stats(da, db, G)
     return float(out[2 * G] if metric == "IoU" else out[2 * G + 1])
 
