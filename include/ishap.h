@@ -46,7 +46,7 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * the headless renderer (ishap_camera, ishap_render_mesh, ishap_render_scratch_bytes, ishap_unproject);
                             * 12 since the winding numbers (ishap_mesh_winding, ishap_cloud_winding, ishap_cloud_areas,
                             * ishap_winding_scratch_bytes) and sdf == 2 / sdf == -2 of ishap_mesh_distance (sign by winding
-                            * number for a counter-clockwise / a clockwise mesh; before 12 both values meant parity) */
+                            * number for a counter-clockwise / a clockwise mesh; before 12 both values meant parity); 13 since ishap_group_norm32_run */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -177,6 +177,62 @@ int ishap_group_norm32_backward(const void* g_nhwc_f16, const void* x_nhwc_f16, 
 int ishap_group_norm32_plan(int N, int H, int W, int C, int backward, int pending, int film, int act, int pool, int gmode, int route,
                             int* route_out, int* parts, int* vec, int* threads, int* grid_x, int* grid_y, int* lds_bytes,
                             int* xcd, char* kernel, int kernel_cap);
+
+/* ONE GroupNorm launch as the executor builds it (ABI 13): every option of the forward pass y = act(film(GN(x))) and of its input
+ * gradient, on any route, through the functions the UNet executor itself goes through (gn_route, gn_local_fill / gn_local_launch,
+ * gn_bwd_local_fill / gn_bwd_local_launch, gn_stats_launch, gn_apply_launch, gn_backward_launch: csrc/norm.h).  Tensors are NHWC
+ * fp16 [N][H*W][C] unless said otherwise; pointers that an option does not use stay NULL.
+ *   backward      0: forward; 1: input gradient
+ *   route         0 = the executor's choice; 1 = full map, two-pass statistics (backward: two-pass sums); 2 / 3 = group-local with
+ *                 one / several workgroups per (image, group); 4 (forward) = full map, statistics finalised in the apply kernel from
+ *                 per-channel fixed-point sums: the caller's `sums` (`sums2`), or, with sums NULL, those an identity 1x1 convolution
+ *                 gathers in its epilogue (C % 64 == 0, N*H*W % 64 == 0, H*W % 64 == 0 at N > 1)
+ *   film, act     FiLM `h * (1 + scale) + shift` (needs act) with emb = per image (scale[C] | shift[C]) fp32, emb_ld floats apart; SiLU
+ *   scratch       ishap_group_norm32_scratch_bytes(N, H*W, C) bytes
+ * forward:
+ *   x             the input; with x2: channels [0, csplit) [N][H*W][csplit], x2 the rest [N][H*W][C - csplit], and xcopy receives the
+ *                 concatenation [N][H*W][C] (csplit % 8 == 0, % 32 on the group-local routes; on the full map only with sums, sums2)
+ *   pool          2x2 mean of the activated map (even H, W; SiLU, no FiLM): out is [N][H/2*W/2][C], xpool (optional) the pooled input
+ *   split         the head's form (full map only; SiLU, no FiLM, no pool): out is [N][H*W][3C] = hi | lo | hi
+ *   out           the result;  stats_out [N][32][2] (mean, rstd): required on route 1, optional elsewhere
+ *   sums, sums2   route 4: [N][channels][2] 64-bit fixed point (sum * 2^24, sum of squares * 2^20) of x (and x2)
+ * backward:
+ *   g             the gradient arriving at y: same resolution (gmode 0), [N][H/2*W/2][C] each cell's share /4 (gmode 1, even H, W),
+ *                 [N][2H*2W][C] the four copies added (gmode 2);  add: optional addend indexed like g;  add2: optional addend
+ *                 [N][H*W][C];  x, stats: the forward's input and (mean, rstd)
+ *   dx            the result; with csplit != 0 channels [0, csplit) go to dx and the rest to dx2, each dense
+ *   sums_ready    route 1: csums [N][C][2] (sum dyh, sum dyh * xhat, both * 2^24) are the caller's; else they are gathered here
+ * pending source (group-local routes only): nslab >= 1 fp32 slices [nslab][rows][channels] at ws, zstride floats apart, stand for
+ *   the forward's x (channels = csplit with x2, else C; + bias + bias2 + res, res [rows][ldr] fp16, at (H/2, W/2) with res_ups;
+ *   x stays NULL and ya receives the fp16 tensor) or for the backward's g (no bias, no residual).
+ * launch == 0: check the descriptor and report; no HIP call, works without a GPU.  *route_out = the route taken, *parts_out = the
+ * workgroups per (image, group) that ran (0 on a full-map route; 1 on route 3 when the rendezvous tenancy was not granted),
+ * kernel = the kernel's name with its template arguments.  A descriptor outside the contract is refused (-2) before any HIP call. */
+typedef struct {
+  int backward, N, H, W, C, route, film, act;
+  int pool, split;                 /* forward */
+  int gmode, sums_ready;           /* backward */
+  int csplit, emb_ld;
+  const float *gamma, *beta, *emb;
+  void* scratch;
+  const void *x, *x2;
+  void *xcopy, *out, *xpool;
+  float* stats_out;
+  const long long *sums, *sums2;
+  const void* g;
+  const float* stats;
+  const void *add, *add2;
+  void *dx, *dx2;
+  long long* csums;
+  const float* ws;                 /* pending source */
+  int nslab, ldr, res_ups, reserved_;
+  long long zstride;
+  const float *bias, *bias2;
+  const void* res;
+  void* ya;
+} ishap_group_norm_desc;
+int ishap_group_norm32_run(const ishap_group_norm_desc* d, int launch, void* stream, int* route_out, int* parts_out, char* kernel,
+                           int kernel_cap);
 
 /* ------------------------------------------- diffusion step (gd/gaussian_diffusion.py:232-331, 400-510) */
 typedef struct {

@@ -65,6 +65,15 @@ class Attn8DescC(C.Structure):
                 [(f, IgemmBufC) for f in ("xn", "wqkv", "bqkv", "wproj", "qkv", "aout", "lse", "slices", "flags")])
 
 
+class GroupNormDescC(C.Structure):
+    _fields_ = ([(f, C.c_int) for f in ("backward", "N", "H", "W", "C", "route", "film", "act", "pool", "split", "gmode",
+                                        "sums_ready", "csplit", "emb_ld")] +
+                [(f, c_void_p) for f in ("gamma", "beta", "emb", "scratch", "x", "x2", "xcopy", "out", "xpool", "stats_out", "sums",
+                                         "sums2", "g", "stats", "add", "add2", "dx", "dx2", "csums", "ws")] +
+                [(f, C.c_int) for f in ("nslab", "ldr", "res_ups", "reserved_")] + [("zstride", C.c_longlong)] +
+                [(f, c_void_p) for f in ("bias", "bias2", "res", "ya")])
+
+
 class DecoderWeightsC(C.Structure):
     _fields_ = [("B", c_void_p), ("W1", c_void_p), ("b1", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
                 ("w3", c_void_p), ("b3", c_void_p)]
@@ -87,6 +96,8 @@ SYMBOLS = {
     "ishap_group_norm32_backward": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, c_void_p, c_void_p, c_void_p]),
     "ishap_group_norm32_plan": (C.c_int, [C.c_int] * 11 + [C.POINTER(C.c_int)] * 8 + [C.c_char_p, C.c_int]),
+    "ishap_group_norm32_run": (C.c_int, [C.POINTER(GroupNormDescC), C.c_int, c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                         C.c_char_p, C.c_int]),
     "ishap_unet_create": (C.c_int, [C.POINTER(UNetConfigC), C.c_int, C.POINTER(c_void_p)]),
     "ishap_unet_destroy": (None, [c_void_p]),
     "ishap_unet_num_params": (C.c_int, [c_void_p]),
@@ -210,9 +221,9 @@ def lib():
         # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats;
         # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run; 10: ishap_group_norm32_plan;
         # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject; 12: ishap_mesh_winding / ishap_cloud_winding /
-        # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance
-        if l.ishap_version() < 12:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 12): rebuild with `python -m ishapediting_amd.build`")
+        # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance; 13: ishap_group_norm32_run
+        if l.ishap_version() < 13:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 13): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -7,8 +7,14 @@ static inline int gn_rows_per_block(int HW) {
   if (r > HW) r = HW;
   return r;
 }
+// blocks of the two-pass reductions (forward statistics, backward sums): the last one takes the rows that are left when H*W is no
+// multiple of the block's rows (any map that is not a power of two, e.g. 6x6)
+static inline int gn_stat_blocks(int HW) {
+  const int r = gn_rows_per_block(HW);
+  return (HW + r - 1) / r;
+}
 static inline size_t gn_partial_floats(int N, int HW, int C) {
-  return (size_t)N * (HW / gn_rows_per_block(HW)) * C * 2 * 2;    // (sum, sum of squares) as doubles = 2 floats each
+  return (size_t)N * gn_stat_blocks(HW) * C * 2 * 2;    // (sum, sum of squares) as doubles = 2 floats each
 }
 // stats[n][32][2] = (mean, rstd); partial is scratch of gn_partial_floats()
 int gn_stats_launch(const half_t* x, float* partial, float* stats, int N, int HW, int C, hipStream_t s);
@@ -126,6 +132,8 @@ bool gn_local_fits(int HW, int C);              // LDS budget of the forward / b
 // the kernel arguments of the pass `g` describes (x / x2 / csplit / xcopy: a lazy skip concatenation, as for the full-map kernel) with
 // source A possibly still pending in `slab`; rec: zeroed rendezvous record or null
 GnLocalArgs gn_local_fill(const GnApplyArgs& g, const SlabSrc& slab, unsigned long long* rec);
+struct GnLocalShape;
+GnLocalShape gn_local_shape(const GnLocalArgs& a);      // what the launcher plans from (also read by ishap_group_norm32_run)
 int gn_local_launch(const GnLocalArgs& a, hipStream_t s);
 
 struct GnBwdLocalArgs {
@@ -152,6 +160,7 @@ struct GnBwdLocalArgs {
 bool gn_bwd_local_fits(int HW, int C, int gmode);
 // the kernel arguments of the pass `g` describes, its upstream gradient g.g possibly still pending in `slab`; rec as above
 GnBwdLocalArgs gn_bwd_local_fill(const GnBwdArgs& g, const SlabSrc& slab, unsigned long long* rec);
+GnLocalShape gn_bwd_local_shape(const GnBwdLocalArgs& a);
 int gn_bwd_local_launch(const GnBwdLocalArgs& a, hipStream_t s);
 
 // ---- what one group-local launch looks like, forward or backward: planned in ONE place (norm_local.hip gn_local_plan; no HIP

@@ -29,6 +29,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const half_t* __restric
   const int n = blockIdx.y;
   const int blk = blockIdx.x;
   const int row0 = blk * rows_per_block;
+  const int rows = HW - row0 < rows_per_block ? HW - row0 : rows_per_block;   // the last block of a map that is no multiple of the block
   const bool active = tid < rpi * CV;
   const int cv = tid % CV, r0 = tid / CV;
   double s[8], q[8];
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const half_t* __restric
   for (int i = 0; i < 8; ++i) { s[i] = 0.0; q[i] = 0.0; }
   if (active) {
     const half_t* base = x + ((long long)n * HW + row0) * C + cv * 8;
-    for (int r = r0; r < rows_per_block; r += rpi) {
+    for (int r = r0; r < rows; r += rpi) {
       half8 v = *reinterpret_cast<const half8*>(base + (long long)r * C);
 #pragma unroll
       for (int i = 0; i < 8; ++i) { const double f = (double)(float)v[i]; s[i] += f; q[i] += f * f; }
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 int gn_stats_launch(const half_t* x, float* partial, float* stats, int N, int HW, int C, hipStream_t s) {
   ISHAP_REQUIRE(C % 32 == 0 && C / 8 <= 256, "GroupNorm channels: multiple of 32, at most 2048");
   int rpb = gn_rows_per_block(HW);
-  int nblk = HW / rpb;
+  int nblk = gn_stat_blocks(HW);
   int CV = C / 8;
   int rpi = 256 / CV > 0 ? 256 / CV : 1;
   size_t smem = (size_t)rpi * C * 2 * sizeof(double);

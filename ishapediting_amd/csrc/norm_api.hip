@@ -53,12 +53,6 @@ __global__ void identity_fill_kernel(half_t* w, int C, int rows) {
   if (i < rows * C) w[i] = (i / C == i % C) ? (half_t)1.f : (half_t)0.f;
 }
 
-// route 0: what the executor picks for this map (gn_route; ISHAP_LOCAL_GN=0 included)
-int resolve_route(int route, int HW, int C, bool backward) {
-  if (route != 0) return route;
-  return gn_route(HW, C, GB_SAME, backward) == GnRoute::local ? 3 : (backward ? 1 : 4);
-}
-
 }  // namespace
 
 extern "C" {
@@ -68,70 +62,182 @@ long long ishap_group_norm32_scratch_bytes(int N, int HW, int C) {
   return (long long)carve(nullptr, N, HW, C).total;
 }
 
+// One GroupNorm launch, described by the caller field by field (include/ishap.h): the descriptor is checked against the contract of
+// the kernels it would reach before any HIP call, turned into the GnApplyArgs / GnBwdArgs (+ SlabSrc) the executor builds
+// (gn_forward_op in unet.hip, conv_gn_norm in backward.hip) and handed to the launchers the executor calls.  launch == 0 stops
+// after the plan: route, parts and kernel name, no HIP call.
+int ishap_group_norm32_run(const ishap_group_norm_desc* d, int launch, void* stream, int* route_out, int* parts_out, char* kernel,
+                           int kernel_cap) {
+  ISHAP_REQUIRE(d != nullptr, "descriptor");
+  ISHAP_REQUIRE(d->backward == 0 || d->backward == 1, "backward: 0 forward, 1 input gradient");
+  const bool bwd = d->backward != 0;
+  const int N = d->N, H = d->H, W = d->W, C = d->C;
+  ISHAP_REQUIRE(N >= 1 && N <= 16 && H >= 1 && W >= 1 && C % 32 == 0, "GroupNorm32 dims");
+  ISHAP_REQUIRE(C >= 32 && H <= 4096 && W <= 4096 && (long long)N * H * W * (C / 8) < (1ll << 31), "GroupNorm32 dims: 32-bit vector index");
+  ISHAP_REQUIRE(d->route >= 0 && d->route <= (bwd ? 3 : 4), bwd ? "backward route 0..3" : "route 0..4");
+  ISHAP_REQUIRE(!bwd || (d->gmode >= GB_SAME && d->gmode <= GB_SUM4), "gmode: 0 same, 1 unpool, 2 sum of four");
+  ISHAP_REQUIRE(d->gamma && d->beta && d->scratch, "null argument");
+  ISHAP_REQUIRE(!d->film || d->act, "FiLM is followed by SiLU");
+  ISHAP_REQUIRE(!d->film || (d->emb && d->emb_ld >= 2 * C), "FiLM rows: emb with emb_ld >= 2 C");
+  const int HW = H * W, gmode = bwd ? d->gmode : GB_SAME;
+  int route = d->route;
+  if (route == 0) route = (!d->split && gn_route(HW, C, gmode, bwd) == GnRoute::local) ? 3 : (bwd ? 1 : 4);
+  const bool local = route == 2 || route == 3;
+  ISHAP_REQUIRE(local || route == 4 || C <= 2048, "two-pass routes: at most 2048 channels");
+  const bool pending = d->nslab != 0 || d->ws != nullptr;
+  SlabSrc slab;
+  if (pending) {
+    ISHAP_REQUIRE(local, "a pending source is added up by the group-local kernels only (routes 2, 3)");
+    const int ld = bwd ? C : (d->x2 ? d->csplit : C);
+    const long long rows = (long long)N * (gmode == GB_UNPOOL ? HW / 4 : gmode == GB_SUM4 ? HW * 4 : HW);
+    ISHAP_REQUIRE(d->ws && d->nslab >= 1 && d->nslab <= 64 && d->zstride >= rows * ld, "pending source: ws, 1..64 slices, zstride >= rows * channels");
+    ISHAP_REQUIRE(!bwd || (!d->bias && !d->bias2 && !d->res), "a pending gradient has neither bias nor residual");
+    ISHAP_REQUIRE(!d->res || d->ldr >= ld, "pending residual: ldr >= channels");
+    ISHAP_REQUIRE(d->res ? (!d->res_ups || (H % 2 == 0 && W % 2 == 0)) : !d->res_ups, "res_ups: a residual at (H/2, W/2), even H and W");
+    slab.ws = d->ws; slab.nslab = d->nslab; slab.zstride = d->zstride; slab.bias = d->bias; slab.bias2 = d->bias2;
+    slab.res = (const half_t*)d->res; slab.ldr = d->ldr; slab.res_ups = d->res_ups;
+  } else {
+    ISHAP_REQUIRE(!d->bias && !d->bias2 && !d->res && !d->ya, "bias, bias2, res and ya belong to a pending source");
+  }
+  ISHAP_REQUIRE(d->csplit >= 0 && d->csplit < C && d->csplit % 8 == 0, "csplit: a multiple of 8 below C");
+  ISHAP_REQUIRE(!local || d->csplit % 32 == 0, "csplit on a group-local route: a multiple of 32");
+  const Scratch sc = carve(d->scratch, N, HW, C);
+  hipStream_t s = (hipStream_t)stream;
+  std::string name;
+  int parts = 0;
+  auto report = [&]() -> int {
+    if (route_out) *route_out = route;
+    if (parts_out) *parts_out = parts;
+    if (kernel) {
+      ISHAP_REQUIRE((int)name.size() < kernel_cap, "kernel: name buffer too small");
+      memcpy(kernel, name.c_str(), name.size() + 1);
+    }
+    return 0;
+  };
+  auto begin = [&]() -> int {          // every launching path: an earlier launch's device-side failure surfaces, the scratch is zeroed
+    ISHAP_TRY(ishap_check_status());
+    ISHAP_CHECK_HIP(hipMemsetAsync(d->scratch, 0, sc.zero_bytes, s));
+    return 0;
+  };
+
+  if (!bwd) {
+    ISHAP_REQUIRE(d->out != nullptr, "null argument: out");
+    ISHAP_REQUIRE(pending ? (!d->x && d->ya) : d->x != nullptr, "input: x, or pending slices with ya and no x");
+    ISHAP_REQUIRE((d->x2 != nullptr) == (d->csplit != 0) && (d->x2 != nullptr) == (d->xcopy != nullptr),
+                  "lazy concatenation: x2, csplit and xcopy go together");
+    ISHAP_REQUIRE(!d->pool || (H % 2 == 0 && W % 2 == 0), "pool: even H and W");
+    ISHAP_REQUIRE(!d->pool || (d->act && !d->film), "pool variant: SiLU, no FiLM");
+    ISHAP_REQUIRE(d->pool || !d->xpool, "xpool belongs to the pool variant");
+    ISHAP_REQUIRE(!d->split || !local, "the split form has no group-local kernel");
+    ISHAP_REQUIRE(!d->split || (d->act && !d->film && !d->pool), "split variant: SiLU, no FiLM, no pool");
+    ISHAP_REQUIRE(!d->x2 || (!d->pool && !d->split), "lazy concatenation: plain variant only");
+    ISHAP_REQUIRE(!d->x2 || local || (route == 4 && d->sums && d->sums2), "lazy concatenation on the full map: route 4 with sums and sums2");
+    ISHAP_REQUIRE((!d->sums && !d->sums2) || route == 4, "sums: route 4 only");
+    ISHAP_REQUIRE(!d->sums2 || (d->sums && d->x2), "sums2: the second source's, beside sums");
+    ISHAP_REQUIRE(route != 1 || d->stats_out, "route 1: stats_out receives the two-pass statistics");
+    ISHAP_REQUIRE(!local || gn_local_fits(HW, C), "group does not fit in LDS");
+    const bool stand_in = route == 4 && !d->sums;
+    // the stand-in producer's epilogue credits a tile's sums to ONE image (n_img = m0 / HW): a tile must not straddle images.  The
+    // launcher only takes 128-row tiles when H*W % 128 == 0 (igemm.hip), so 64-row tiles are what has to divide an image here
+    ISHAP_REQUIRE(!stand_in || (C % 64 == 0 && ((long long)N * HW) % 64 == 0 && (N == 1 || HW % 64 == 0)),
+                  "route 4: C % 64 == 0, N*H*W % 64 == 0, and H*W % 64 == 0 at batch > 1");
+    GnApplyArgs g;
+    g.x = (const half_t*)(pending ? d->ya : d->x); g.out = (half_t*)d->out; g.xpool = (half_t*)d->xpool; g.stats_out = d->stats_out;
+    g.gamma = d->gamma; g.beta = d->beta; g.emb = d->film ? d->emb : nullptr; g.emb_ld = d->film ? d->emb_ld : 0;
+    g.N = N; g.H = H; g.W = W; g.C = C; g.film = d->film; g.act = d->act; g.pool = d->pool; g.split = d->split;
+    g.x2 = (const half_t*)d->x2; g.csplit = d->csplit; g.xcopy = (half_t*)d->xcopy;
+    if (local) {
+      // route 3 (several workgroups per group meeting inside the launch) needs the device's rendezvous tenancy (common.h);
+      // while another context / stream of the process holds it the call degrades to one workgroup per group (route 2)
+      if (launch) ISHAP_TRY(begin());
+      TenancyScope tenancy(nullptr, s, !launch, route == 3);
+      const bool rec = launch ? tenancy.granted : route == 3;
+      const GnLocalArgs la = gn_local_fill(g, slab, rec ? sc.rec : nullptr);
+      const GnLocalPlan p = gn_local_plan(gn_local_shape(la));
+      name = gn_local_kernel_name(p);
+      parts = p.parts;
+      ISHAP_TRY(report());
+      return launch ? gn_local_launch(la, s) : 0;
+    }
+    g.sums = route == 4 ? (d->sums ? d->sums : sc.csums) : nullptr;
+    g.sums2 = d->sums2;
+    GnLaunchInfo info;
+    ISHAP_TRY(gn_apply_launch(g, nullptr, &info));
+    name = info.kernel;
+    ISHAP_TRY(report());
+    if (!launch) return 0;
+    ISHAP_TRY(begin());
+    if (route == 1) {
+      ISHAP_TRY(gn_stats_launch(g.x, sc.partial, d->stats_out, N, HW, C, s));
+      g.stats = d->stats_out;
+      g.stats_out = nullptr;
+    } else if (stand_in) {
+      // producer stand-in: copy = x * I through the implicit-GEMM kernel, whose epilogue gathers the per-channel sums
+      const int rows = (int)align_up((size_t)C, 128);
+      hipLaunchKernelGGL(identity_fill_kernel, dim3((rows * C + 255) / 256), dim3(256), 0, s, sc.ident, C, rows);
+      ISHAP_CHECK_HIP(hipGetLastError());
+      IgemmArgs a;
+      a.X = g.x; a.Wt = sc.ident; a.out = sc.copy; a.M = N * HW; a.N = C; a.K = C; a.conv3 = 0; a.Cin = C;
+      a.ldx = C; a.ldw = C; a.ldo = C; a.H = H; a.W = W; a.out_mode = IG_OUT_F16; a.ksplit = 1;
+      a.stat_out = sc.csums;
+      ISHAP_TRY(igemm_launch(a, s));
+      g.x = sc.copy;
+    }
+    return gn_apply_launch(g, s);
+  }
+
+  ISHAP_REQUIRE(d->x && d->stats && d->dx, "null argument: x, stats, dx");
+  ISHAP_REQUIRE(pending ? !d->g : d->g != nullptr, "upstream gradient: g, or pending slices and no g");
+  ISHAP_REQUIRE(!d->pool && !d->split, "pool and split are forward options");
+  ISHAP_REQUIRE(gmode != GB_UNPOOL || (H % 2 == 0 && W % 2 == 0), "GB_UNPOOL: even H and W");
+  ISHAP_REQUIRE((d->csplit != 0) == (d->dx2 != nullptr), "split output: dx2 and csplit go together");
+  ISHAP_REQUIRE(d->sums_ready ? (!local && d->csums) : !d->csums, "sums_ready: the caller's csums, full-map route only");
+  ISHAP_REQUIRE(!local || gn_bwd_local_fits(HW, C, gmode), "group does not fit in LDS");
+  GnBwdArgs a;
+  a.g = (const half_t*)d->g; a.x = (const half_t*)d->x; a.add = (const half_t*)d->add; a.add2 = (const half_t*)d->add2;
+  a.dx = (half_t*)d->dx; a.dx2 = (half_t*)d->dx2; a.csplit = d->csplit;
+  a.stats = d->stats; a.gamma = d->gamma; a.beta = d->beta; a.emb = d->film ? d->emb : nullptr; a.emb_ld = d->film ? d->emb_ld : 0;
+  a.N = N; a.H = H; a.W = W; a.C = C; a.film = d->film; a.act = d->act; a.gmode = gmode;
+  if (local) {
+    if (launch) ISHAP_TRY(begin());
+    TenancyScope tenancy(nullptr, s, !launch, route == 3);
+    const bool rec = launch ? tenancy.granted : route == 3;
+    const GnBwdLocalArgs la = gn_bwd_local_fill(a, slab, rec ? sc.rec : nullptr);
+    const GnLocalPlan p = gn_local_plan(gn_bwd_local_shape(la));
+    name = gn_local_kernel_name(p);
+    parts = p.parts;
+    ISHAP_TRY(report());
+    return launch ? gn_bwd_local_launch(la, s) : 0;
+  }
+  a.sums_ready = d->sums_ready;
+  a.csums = d->sums_ready ? d->csums : sc.csums;
+  GnLaunchInfo info;
+  ISHAP_TRY(gn_backward_launch(a, nullptr, &info));
+  name = info.kernel;
+  ISHAP_TRY(report());
+  if (!launch) return 0;
+  ISHAP_TRY(begin());
+  return gn_backward_launch(a, s);
+}
+
+// y = act(GN(x)) and its input gradient on a chosen route: the plain forms of the call above
 int ishap_group_norm32(const void* x_nhwc_f16, const float* gamma, const float* beta, int N, int H, int W, int C, int silu,
                        int route, void* y_nhwc_f16, float* stats, void* scratch, void* stream) {
   ISHAP_REQUIRE(x_nhwc_f16 && gamma && beta && y_nhwc_f16 && stats && scratch, "null argument");
-  ISHAP_REQUIRE(N >= 1 && N <= 16 && H >= 1 && W >= 1 && C % 32 == 0, "GroupNorm32 dims");
-  ISHAP_REQUIRE(route >= 0 && route <= 4, "route 0..4");
-  ISHAP_TRY(ishap_check_status());
-  hipStream_t s = (hipStream_t)stream;
-  const int HW = H * W;
-  const Scratch sc = carve(scratch, N, HW, C);
-  ISHAP_CHECK_HIP(hipMemsetAsync(scratch, 0, sc.zero_bytes, s));
-  route = resolve_route(route, HW, C, false);
-  GnApplyArgs g;
-  g.x = (const half_t*)x_nhwc_f16; g.out = (half_t*)y_nhwc_f16; g.gamma = gamma; g.beta = beta;
-  g.N = N; g.H = H; g.W = W; g.C = C; g.act = silu;
-  if (route == 2 || route == 3) {
-    // route 3 (several workgroups per group meeting inside the launch) needs the device's rendezvous tenancy (common.h);
-    // while another context / stream of the process holds it the call degrades to one workgroup per group (route 2)
-    TenancyScope tenancy(nullptr, s, false, route == 3);
-    g.stats_out = stats;
-    return gn_local_launch(gn_local_fill(g, SlabSrc{}, tenancy.granted ? sc.rec : nullptr), s);
-  }
-  if (route == 1) {
-    ISHAP_TRY(gn_stats_launch(g.x, sc.partial, stats, N, HW, C, s));
-    g.stats = stats;
-  } else {
-    // producer stand-in: copy = x * I through the implicit-GEMM kernel, whose epilogue gathers the per-channel sums
-    // the epilogue credits a tile's sums to ONE image (n_img = m0 / HW): a tile must not straddle images.  The launcher only
-    // takes 128-row tiles when H*W % 128 == 0 (igemm.hip), so 64-row tiles are what has to divide an image here
-    ISHAP_REQUIRE(C % 64 == 0 && ((long long)N * HW) % 64 == 0 && (N == 1 || HW % 64 == 0), "route 4: C % 64 == 0, N*H*W % 64 == 0, and H*W % 64 == 0 at batch > 1");
-    const int rows = (int)align_up((size_t)C, 128);
-    hipLaunchKernelGGL(identity_fill_kernel, dim3((rows * C + 255) / 256), dim3(256), 0, s, sc.ident, C, rows);
-    ISHAP_CHECK_HIP(hipGetLastError());
-    IgemmArgs a;
-    a.X = g.x; a.Wt = sc.ident; a.out = sc.copy; a.M = N * HW; a.N = C; a.K = C; a.conv3 = 0; a.Cin = C;
-    a.ldx = C; a.ldw = C; a.ldo = C; a.H = H; a.W = W; a.out_mode = IG_OUT_F16; a.ksplit = 1;
-    a.stat_out = sc.csums;
-    ISHAP_TRY(igemm_launch(a, s));
-    g.x = sc.copy; g.sums = sc.csums; g.stats_out = stats;
-  }
-  return gn_apply_launch(g, s);
+  ishap_group_norm_desc d = {};
+  d.N = N; d.H = H; d.W = W; d.C = C; d.route = route; d.act = silu;
+  d.gamma = gamma; d.beta = beta; d.scratch = scratch; d.x = x_nhwc_f16; d.out = y_nhwc_f16; d.stats_out = stats;
+  return ishap_group_norm32_run(&d, 1, stream, nullptr, nullptr, nullptr, 0);
 }
 
 int ishap_group_norm32_backward(const void* g_nhwc_f16, const void* x_nhwc_f16, const float* stats, const float* gamma,
                                 const float* beta, int N, int H, int W, int C, int silu, int route, void* dx_nhwc_f16,
                                 void* scratch, void* stream) {
   ISHAP_REQUIRE(g_nhwc_f16 && x_nhwc_f16 && stats && gamma && beta && dx_nhwc_f16 && scratch, "null argument");
-  ISHAP_REQUIRE(N >= 1 && N <= 16 && H >= 1 && W >= 1 && C % 32 == 0, "GroupNorm32 dims");
-  ISHAP_REQUIRE(route >= 0 && route <= 3, "backward route 0..3");
-  ISHAP_TRY(ishap_check_status());
-  hipStream_t s = (hipStream_t)stream;
-  const int HW = H * W;
-  const Scratch sc = carve(scratch, N, HW, C);
-  ISHAP_CHECK_HIP(hipMemsetAsync(scratch, 0, sc.zero_bytes, s));
-  route = resolve_route(route, HW, C, true);
-  GnBwdArgs a;
-  a.g = (const half_t*)g_nhwc_f16; a.x = (const half_t*)x_nhwc_f16; a.dx = (half_t*)dx_nhwc_f16;
-  a.stats = stats; a.gamma = gamma; a.beta = beta; a.N = N; a.H = H; a.W = W; a.C = C; a.film = 0; a.act = silu;
-  a.gmode = GB_SAME;
-  if (route == 2 || route == 3) {
-    TenancyScope tenancy(nullptr, s, false, route == 3);
-    return gn_bwd_local_launch(gn_bwd_local_fill(a, SlabSrc{}, tenancy.granted ? sc.rec : nullptr), s);
-  }
-  a.csums = sc.csums;
-  return gn_backward_launch(a, s);
+  ishap_group_norm_desc d = {};
+  d.backward = 1; d.N = N; d.H = H; d.W = W; d.C = C; d.route = route; d.act = silu; d.gmode = GB_SAME;
+  d.gamma = gamma; d.beta = beta; d.scratch = scratch; d.g = g_nhwc_f16; d.x = x_nhwc_f16; d.stats = stats; d.dx = dx_nhwc_f16;
+  return ishap_group_norm32_run(&d, 1, stream, nullptr, nullptr, nullptr, 0);
 }
 
 /* CPU view of the plan (include/ishap.h): the route, kernel and launch geometry one GroupNorm pass of this shape gets */

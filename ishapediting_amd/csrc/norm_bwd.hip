@@ -57,13 +57,14 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(GnBwdArgs a, int ro
   const int rpi = 256 / CV > 0 ? 256 / CV : 1;
   const int tid = threadIdx.x, n = blockIdx.y, blk = blockIdx.x;
   const int row0 = blk * rows_per_block;
+  const int rows = a.H * a.W - row0 < rows_per_block ? a.H * a.W - row0 : rows_per_block;   // the last block of a map that is no multiple of the block
   const bool active = tid < rpi * CV;
   const int cv = tid % CV, r0 = tid / CV;
   float s[8], q[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) { s[i] = 0.f; q[i] = 0.f; }
   if (active) {
-    for (int r = r0; r < rows_per_block; r += rpi) {
+    for (int r = r0; r < rows; r += rpi) {
       const int p = row0 + r;
       float dyh[8], xh[8];
       bwd_terms<FILM, ACT>(a, n, p / a.W, p % a.W, cv * 8, dyh, xh);
@@ -191,7 +192,7 @@ int gn_backward_launch(const GnBwdArgs& a, hipStream_t s, GnLaunchInfo* info) {
   ISHAP_REQUIRE(a.C % 32 == 0 && a.C / 8 <= 256, "GroupNorm channels");
   ISHAP_REQUIRE(a.csplit == 0 || (a.dx2 && a.csplit % 8 == 0 && a.csplit < a.C), "split output");
   const int HW = a.H * a.W;
-  const int rpb = gn_rows_per_block(HW), nblk = HW / rpb, CV = a.C / 8;
+  const int rpb = gn_rows_per_block(HW), nblk = gn_stat_blocks(HW), CV = a.C / 8;
   const int rpi = 256 / CV > 0 ? 256 / CV : 1;
   const size_t smem = (size_t)rpi * a.C * 2 * sizeof(float);
   GnBwdArgs a2 = a;

@@ -769,6 +769,19 @@ GnBwdLocalArgs gn_bwd_local_fill(const GnBwdArgs& g, const SlabSrc& slab, unsign
   return a;
 }
 
+GnLocalShape gn_local_shape(const GnLocalArgs& a) {
+  GnLocalShape q;
+  q.N = a.N; q.H = a.H; q.W = a.W; q.C = a.C; q.pending = a.slab.pending(); q.have_rec = a.rec != nullptr;
+  q.film = a.film; q.act = a.act; q.pool = a.pool;
+  return q;
+}
+GnLocalShape gn_bwd_local_shape(const GnBwdLocalArgs& a) {
+  GnLocalShape q;
+  q.N = a.N; q.H = a.H; q.W = a.W; q.C = a.C; q.backward = true; q.pending = a.slab.pending(); q.have_rec = a.rec != nullptr;
+  q.film = a.film; q.act = a.act; q.gmode = a.gmode;
+  return q;
+}
+
 int gn_local_launch(const GnLocalArgs& a, hipStream_t s) {
   ISHAP_REQUIRE(a.C % 32 == 0 && a.Ca > 0 && a.Ca <= a.C && a.Ca % 32 == 0, "GroupNorm channels: multiples of 32");
   ISHAP_REQUIRE((a.Ca == a.C) == (a.xb == nullptr), "second source exactly when the input is a concatenation");
@@ -781,10 +794,7 @@ int gn_local_launch(const GnLocalArgs& a, hipStream_t s) {
   ISHAP_REQUIRE(b.status != nullptr, "device status word");
   ISHAP_REQUIRE(!a.pool || a.act, "the pooled variant carries SiLU (ResBlock in_layers)");
   ISHAP_REQUIRE(!a.film || a.act, "FiLM is followed by SiLU (ResBlock out_layers)");
-  GnLocalShape q;
-  q.N = a.N; q.H = a.H; q.W = a.W; q.C = a.C; q.pending = a.slab.pending(); q.have_rec = a.rec != nullptr;
-  q.film = a.film; q.act = a.act; q.pool = a.pool;
-  const GnLocalPlan p = gn_local_plan(q);
+  const GnLocalPlan p = gn_local_plan(gn_local_shape(a));
   b.parts = p.parts;
   const GnLocalKernel kern = fwd_kernel(p);
   ISHAP_TRY(set_lds(kern));
@@ -802,10 +812,7 @@ int gn_bwd_local_launch(const GnBwdLocalArgs& a, hipStream_t s) {
   b.spin_limit = spin_limit();
   b.status = ishap_status_word();
   ISHAP_REQUIRE(b.status != nullptr, "device status word");
-  GnLocalShape q;
-  q.N = a.N; q.H = a.H; q.W = a.W; q.C = a.C; q.backward = true; q.pending = a.slab.pending(); q.have_rec = a.rec != nullptr;
-  q.film = a.film; q.act = a.act; q.gmode = a.gmode;
-  const GnLocalPlan p = gn_local_plan(q);
+  const GnLocalPlan p = gn_local_plan(gn_bwd_local_shape(a));
   b.parts = p.parts;
   const size_t smem = (size_t)p.lds_bytes;
   ISHAP_REQUIRE(smem <= LOCAL_LDS_CAP + GN_SCRATCH_BYTES, "group does not fit in LDS");

@@ -26,6 +26,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.groupnorm_ref import gn_bwd_ref      # gn_bwd_term (csrc/gn_bwd_terms.h) in float64 with its fp16 rounding points
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMON_H = os.path.join(ROOT, "ishapediting_amd", "csrc", "common.h")
 
@@ -242,23 +244,6 @@ def stat_ref(y, imgs):
 
 def f16r(t):
     return t.to(torch.float16).double()
-
-
-def gn_bwd_ref(up, x, mu, rs, gam, bet, esc, esh, film, act):
-    """gn_bwd_term (csrc/gn_bwd_terms.h) in float64 with its fp16 rounding points: gn_affine rounds the pre-activation, FiLM's
-    scale is fp16(1 + fp16(scale)), its product and sum each round to fp16 (gn_film).  Returns dyh, xhat."""
-    xhat = (x - mu) * rs
-    u, mult = up, gam
-    if film or act:
-        pre = f16r(xhat * gam + bet)
-        if film:
-            sc = f16r(1.0 + f16r(esc))
-            pre = f16r(f16r(pre * sc) + f16r(esh))
-            mult = mult * sc
-        if act:
-            sg = torch.sigmoid(pre)
-            u = u * (sg * (1.0 + pre * (1.0 - sg)))
-    return u * mult, xhat
 
 
 def gb_operands(c: Case):
