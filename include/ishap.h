@@ -46,7 +46,9 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * the headless renderer (ishap_camera, ishap_render_mesh, ishap_render_scratch_bytes, ishap_unproject);
                             * 12 since the winding numbers (ishap_mesh_winding, ishap_cloud_winding, ishap_cloud_areas,
                             * ishap_winding_scratch_bytes) and sdf == 2 / sdf == -2 of ishap_mesh_distance (sign by winding
-                            * number for a counter-clockwise / a clockwise mesh; before 12 both values meant parity); 13 since ishap_group_norm32_run */
+                            * number for a counter-clockwise / a clockwise mesh; before 12 both values meant parity); 13 since ishap_group_norm32_run;
+                            * 14 since the front end for clouds without normals (ishap_cloud_knn, ishap_cloud_normals,
+                            * ishap_cloud_orient, ishap_cloud_orient_scratch_bytes) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -495,6 +497,40 @@ int ishap_mesh_winding(const float* verts, const int* tris, long long ntris, con
 int ishap_cloud_winding(const float* points, const float* normals, const float* areas, long long npoints, const float* pts,
                         long long npts, float* w, void* scratch, long long scratch_bytes, void* stream);
 int ishap_cloud_areas(const float* points, long long npoints, int k, float* areas, void* stream);
+
+/* ------------------------------------------------------------------ clouds without normals (ABI 14)
+ * What a scanner delivers is points only; the reference assumes its pointcloud.npz carries normals (a user of it would
+ * call Open3D's estimate_normals and orient_normals_consistent_tangent_plane first).  Device pointers unless said otherwise;
+ * 1 <= k <= 16 and k < npoints in all three calls; coordinates must be finite.
+ * ishap_cloud_knn: idx[i*k + c], d2[i*k + c] = index and squared distance of the c-th nearest OTHER point of point i,
+ *   ascending by (d2, index): equal distances go to the smaller index, points equal to point i are neighbours at distance 0.
+ *   Brute force, fp32, npoints < 2^31.  A lane owns a query and the whole candidate range: the range is not split over
+ *   workgroups, npoints / 256 workgroups are enough at the cloud sizes cloud_to_mesh is documented for (1e5 and up).
+ *   Candidates are visited in a scattered tile order, so a cloud stored along a sweep costs no more than a shuffled one;
+ *   the result does not depend on that order.
+ * ishap_cloud_normals: normals[i] = the unit eigenvector of the smallest eigenvalue of the covariance of {point i} + its k
+ *   neighbours idx[i*k ..] about their mean (coordinates relative to point i; covariance and cyclic Jacobi in fp64, rounded once to fp32), signed so that its
+ *   component of largest magnitude is positive (ties: the lowest axis): a function of the input alone, NOT an orientation.
+ *   variation (may be NULL): l0 / (l0 + l1 + l2), 0 on a plane.  All points equal: (1, 0, 0) and 0; collinear points: some
+ *   unit vector across the line.  An index outside [0, npoints) is read as the point itself.
+ * ishap_cloud_orient: flips normals (in place; each comes out as it went in or negated, bit for bit) so that they agree
+ *   along the directed kNN graph.  Round r: every point that has no level yet takes, among its OWN neighbours with a level
+ *   in [1, r), the one with the largest |n_i . n_j| (ties: the first in neighbour order), is negated where that dot product
+ *   is negative (zero counts as positive) and gets level r.  A round that orients nothing while points remain makes the
+ *   remaining point with the largest z (ties: the smallest index) a seed of level r, negated where n_z < 0; round 1 always
+ *   seeds.  The topmost point of a closed surface that is not nested inside another has an outward normal with n_z > 0, so
+ *   such components come out pointing OUTWARD; a cavity's surface nested inside another component comes out pointing away
+ *   from its own interior, that is into the solid.  Independent of thread order, bitwise repeatable.
+ *   info (HOST int[2]): the number of rounds in which propagation oriented at least one point, and the number of seeds.
+ *   scratch: ishap_cloud_orient_scratch_bytes(npoints) device bytes (-1 on a negative count), 4-byte aligned; a smaller
+ *   scratch_bytes fails the call.  npoints < 2^30 - 16.  Rounds are enqueued 16 at a time; the call synchronises the stream
+ *   once per 16 rounds to read the number of points that remain, and has completed when it returns. */
+int ishap_cloud_knn(const float* points, long long npoints, int k, int* idx, float* d2, void* stream);
+int ishap_cloud_normals(const float* points, long long npoints, const int* idx, int k, float* normals, float* variation,
+                        void* stream);
+long long ishap_cloud_orient_scratch_bytes(long long npoints);
+int ishap_cloud_orient(const float* points, float* normals, const int* idx, long long npoints, int k, void* scratch,
+                       long long scratch_bytes, int* info, void* stream);
 
 /* ------------------------------------------------------------------ ARAP deformation (meshProcess.py:222-236)
  * Replaces the reference's Open3D deform_as_rigid_as_possible: Sorkine & Alexa 2007, spokes energy, cotangent weights

@@ -172,6 +172,11 @@ SYMBOLS = {
     "ishap_cloud_winding": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p,
                                       C.c_longlong, c_void_p]),
     "ishap_cloud_areas": (C.c_int, [c_void_p, C.c_longlong, C.c_int, c_void_p, c_void_p]),
+    "ishap_cloud_knn": (C.c_int, [c_void_p, C.c_longlong, C.c_int, c_void_p, c_void_p, c_void_p]),
+    "ishap_cloud_normals": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_int, c_void_p, c_void_p, c_void_p]),
+    "ishap_cloud_orient_scratch_bytes": (C.c_longlong, [C.c_longlong]),
+    "ishap_cloud_orient": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_longlong, C.c_int, c_void_p, C.c_longlong,
+                                     C.POINTER(C.c_int), c_void_p]),
     "ishap_group_field_stats": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_longlong, C.c_int, c_void_p, c_void_p]),
     "ishap_arap_scratch_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_longlong]),
     "ishap_arap": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_double,
@@ -221,9 +226,10 @@ def lib():
         # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats;
         # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run; 10: ishap_group_norm32_plan;
         # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject; 12: ishap_mesh_winding / ishap_cloud_winding /
-        # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance; 13: ishap_group_norm32_run
-        if l.ishap_version() < 13:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 13): rebuild with `python -m ishapediting_amd.build`")
+        # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance; 13: ishap_group_norm32_run;
+        # 14: ishap_cloud_knn / ishap_cloud_normals / ishap_cloud_orient / ishap_cloud_orient_scratch_bytes
+        if l.ishap_version() < 14:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 14): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

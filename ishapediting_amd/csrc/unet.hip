@@ -729,7 +729,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 13; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 14; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
@@ -742,6 +742,8 @@ int ishap_version(void) { return 13; }  // 2: ishap_mesh_smooth takes the scratc
                                         //     ishap_winding_scratch_bytes) and ishap_mesh_distance's sdf == 2 / sdf == -2 (sign by winding number,
                                         //     counter-clockwise / clockwise mesh; before 12 both meant parity, as any other non-zero value still does)
                                         // 13: one GroupNorm launch through the ABI (ishap_group_norm32_run)
+                                        // 14: clouds without normals (ishap_cloud_knn, ishap_cloud_normals, ishap_cloud_orient,
+                                        //     ishap_cloud_orient_scratch_bytes)
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");

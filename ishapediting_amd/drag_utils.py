@@ -598,7 +598,8 @@ class DragStuff:
 
     # ------------------------------------------------------------------ real shapes (:401-471, :552-566)
     def _cloud_samples(self, cloud, center, generator=None):
-        """occupancy samples of an oriented point cloud ((points, normals) or an .npz path) by winding number"""
+        """occupancy samples of a point cloud ((points, normals), bare points or an .npz path) by winding number; a cloud
+        without normals gets them from mesh.estimate_normals inside sample_cloud_occupancy"""
         pts, nrm = mesh_backend.load_cloud(cloud)
         return mesh_backend.sample_cloud_occupancy(pts, nrm, self.args.points_size, self.args.points_uniform_ratio, center=center,
                                                    generator=generator, device=self.device)
@@ -608,8 +609,10 @@ class DragStuff:
         """drag_utils.py:401-471.  `points`/`occupancies` (float32 [P,3] / [P,1]) replace the Open3D raycast
         sampling (:418-440) when given; the mesh-file route needs Open3D like the reference.  occupancy: how the mesh's
         samples are labelled, "parity" or "winding" (mesh.sample_occupancy; "winding" for meshes that are not watertight).
-        cloud: an oriented point cloud, a (points, normals) pair or the path of an .npz with those arrays, labelled by its
-        winding number instead of a mesh (mesh.sample_cloud_occupancy; `center_mesh` applies to its points)."""
+        cloud: a point cloud, labelled by its winding number instead of a mesh (mesh.sample_cloud_occupancy; `center_mesh`
+        applies to its points): a (points, normals) pair with unit outward normals, or the path of an .npz with those arrays;
+        or points alone -- a [N,3] array or tensor, (points, None), or an .npz without `normals` -- whose normals are then
+        estimated and oriented on the device (mesh.estimate_normals, 12 neighbours)."""
         mesh_backend._check_choice("occupancy", occupancy, mesh_backend.OCCUPANCY_METHODS)
         if tri_feat_path is not None:
             img = th.tensor(np.load(tri_feat_path), device=self.device)
@@ -696,8 +699,8 @@ class DragStuff:
         `batch_fn(step) -> (idx, r, noise)` injects a step's batch.  Saves tri_feat_opt.npy and mesh_opt.obj under `path`,
         leaves the fitted planes in decoder.embeddings and the per-step (bce, mse, l2reg, tvreg) in last_losses [steps, 4],
         and returns the normalised latent (planes - middle) / range [1,96,S,S].  The drag state is not touched.
-        `occupancy` ("parity" | "winding") and `cloud` as train_triplane: how a mesh's samples are labelled, or an
-        oriented point cloud to label instead of a mesh."""
+        `occupancy` ("parity" | "winding") and `cloud` as train_triplane: how a mesh's samples are labelled, or a
+        point cloud, with normals or without, to label instead of a mesh."""
         from .triplane_decoder import fit_triplanes, planes_to_latent
         mesh_backend._check_choice("occupancy", occupancy, mesh_backend.OCCUPANCY_METHODS)
         means, stds = load_triplane_stats(stats, self.args.stats_dir)

@@ -385,6 +385,87 @@ def cloud_areas(points: torch.Tensor, k: int = 8) -> torch.Tensor:
     return a
 
 
+def _check_cloud_k(what: str, points, k):
+    """host-side checks shared by the kNN / normal calls: (k, N); raises before any device work"""
+    if not (1 <= int(k) <= 16):
+        raise ValueError(f"{what}: k must be in 1..16, got {k!r}")
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{what}: points must be a [N,3] tensor, got {tuple(points.shape) if torch.is_tensor(points) else type(points).__name__}")
+    if points.shape[0] <= int(k):
+        raise ValueError(f"{what}: k = {k} needs more than {k} points, got {points.shape[0]}")
+    return int(k), points.shape[0]
+
+
+def _knn_launch(p: torch.Tensor, k: int):
+    idx = torch.empty((p.shape[0], k), dtype=torch.int32, device=p.device)
+    d2 = torch.empty((p.shape[0], k), dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().ishap_cloud_knn(p.data_ptr(), p.shape[0], k, idx.data_ptr(), d2.data_ptr(), _lib.stream_ptr(p.device)))
+    return idx, d2
+
+
+def _orient_launch(p: torch.Tensor, n: torch.Tensor, idx: torch.Tensor, k: int):
+    """orients n in place; (rounds, seeds)"""
+    L = _lib.lib()
+    nbytes = int(L.ishap_cloud_orient_scratch_bytes(p.shape[0]))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    info = (C.c_int * 2)()
+    with torch.cuda.device(p.device):
+        _lib.check(L.ishap_cloud_orient(p.data_ptr(), n.data_ptr(), idx.data_ptr(), p.shape[0], k, scratch.data_ptr(), nbytes, info,
+                                        _lib.stream_ptr(p.device)))
+    return int(info[0]), int(info[1])
+
+
+def cloud_knn(points: torch.Tensor, k: int = 8):
+    """The k nearest OTHER points of every point of a cloud (ishap_cloud_knn; brute force on the device), ascending by
+    (squared distance, index): equal distances go to the smaller index, equal points are neighbours at distance 0.
+    points [N,3] -> (idx [N,k] int32, d2 [N,k] float32); 1 <= k <= 16, k < N."""
+    k, _ = _check_cloud_k("cloud_knn", points, k)
+    _need_gpu(points, "cloud_knn")
+    return _knn_launch(points.detach().to(torch.float32).contiguous(), k)
+
+
+def estimate_normals(points: torch.Tensor, k: int = 12, orient: bool = True, return_info: bool = False):
+    """Unit normals [N,3] float32 of a cloud that has none (the device counterpart of Open3D's estimate_normals +
+    orient_normals_consistent_tangent_plane): the direction of least spread of every point's k nearest neighbours
+    (ishap_cloud_knn, ishap_cloud_normals), then, with `orient`, made consistent along the kNN graph from the topmost point
+    of every component (ishap_cloud_orient): OUTWARD for a closed surface that is not nested inside another; a cavity's
+    surface comes out pointing away from the cavity.  orient=False: the sign is a rule on the components (the largest in
+    magnitude is positive), not an orientation.  return_info: also a dict with `variation` [N] (l0 / (l0 + l1 + l2), 0 on a
+    plane), `rounds` and `seeds` (None without `orient`).  1 <= k <= 16, k < N."""
+    k, _ = _check_cloud_k("estimate_normals", points, k)
+    _need_gpu(points, "estimate_normals")
+    p = points.detach().to(torch.float32).contiguous()
+    idx, _ = _knn_launch(p, k)
+    n = torch.empty_like(p)
+    var = torch.empty(p.shape[0], dtype=torch.float32, device=p.device) if return_info else None
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().ishap_cloud_normals(p.data_ptr(), p.shape[0], idx.data_ptr(), k, n.data_ptr(), _lib.ptr(var),
+                                                 _lib.stream_ptr(p.device)))
+    rounds, seeds = _orient_launch(p, n, idx, k) if orient else (None, None)
+    return (n, {"variation": var, "rounds": rounds, "seeds": seeds}) if return_info else n
+
+
+def orient_normals(points: torch.Tensor, normals: torch.Tensor, k: int = 12, return_info: bool = False):
+    """`normals` [N,3] of any length and sign, normalised and oriented as estimate_normals orients its own
+    (ishap_cloud_orient over the k nearest neighbours): each comes back as its unit vector or the negation of it.
+    A zero normal raises.  return_info: also {"rounds", "seeds"}."""
+    k, N = _check_cloud_k("orient_normals", points, k)
+    if not torch.is_tensor(normals) or tuple(normals.shape) != (N, 3):
+        raise ValueError(f"orient_normals: {N} points but normals of shape "
+                         f"{tuple(normals.shape) if torch.is_tensor(normals) else type(normals).__name__}")
+    n = normals.detach().to(torch.float32)
+    length = torch.linalg.norm(n, dim=1, keepdim=True)
+    if not bool((length > 0).all()):                       # also false for NaN
+        raise ValueError(f"orient_normals: {int((~(length > 0)).sum())} normals are zero or not a number")
+    _need_gpu(points, "orient_normals")
+    p = points.detach().to(torch.float32).contiguous()
+    n = (n / length).to(p.device).contiguous()
+    idx, _ = _knn_launch(p, k)
+    rounds, seeds = _orient_launch(p, n, idx, k)
+    return (n, {"rounds": rounds, "seeds": seeds}) if return_info else n
+
+
 def cloud_winding_number(points: torch.Tensor, normals: torch.Tensor, query: torch.Tensor, areas=None) -> torch.Tensor:
     """Winding number of `query` about an oriented point cloud (ishap_cloud_winding; Barill et al. 2018): about 1 inside,
     0 outside when `normals` are unit and point outward.  areas [N]: the area each point stands for, cloud_areas(points)
@@ -540,35 +621,50 @@ def sample_occupancy(mesh, mesh_path, center_mesh, points_size, uniform_ratio, d
 
 def load_cloud(cloud):
     """(points [N,3], normals [N,3]) float32 numpy from a (points, normals) pair or the path of an .npz with those two
-    arrays (the reference's pointcloud.npz, meshProcess.py cloud2mesh)."""
-    if isinstance(cloud, (str, bytes)) or hasattr(cloud, "__fspath__"):
-        with np.load(cloud) as z:
-            pts, nrm = z["points"], z["normals"]
-    else:
-        pts, nrm = cloud
+    arrays (the reference's pointcloud.npz, meshProcess.py cloud2mesh).  A cloud without normals -- a bare [N,3] array or
+    tensor, a (points, None) pair or an .npz with `points` only -- gives (points, None): sample_cloud_occupancy and
+    cloud_to_mesh then estimate them (estimate_normals).  (An array of shape [2,3] is still read as one point and its
+    normal, as before.)"""
     def host(x):
         return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    pts, nrm = host(pts).astype(np.float32).reshape(-1, 3), host(nrm).astype(np.float32).reshape(-1, 3)
+    if isinstance(cloud, (str, bytes)) or hasattr(cloud, "__fspath__"):
+        with np.load(cloud) as z:
+            pts, nrm = z["points"], (z["normals"] if "normals" in z.files else None)
+    elif (torch.is_tensor(cloud) or isinstance(cloud, np.ndarray)) and cloud.ndim == 2 and tuple(cloud.shape) != (2, 3):
+        pts, nrm = cloud, None
+    else:
+        pts, nrm = cloud
+    pts = host(pts).astype(np.float32).reshape(-1, 3)
+    if nrm is None:
+        return pts, None
+    nrm = host(nrm).astype(np.float32).reshape(-1, 3)
     if pts.shape != nrm.shape:
         raise ValueError(f"cloud: {pts.shape[0]} points but {nrm.shape[0]} normals")
     return pts, nrm
 
 
-def sample_cloud_occupancy(points, normals, points_size, uniform_ratio, center=True, areas=None, generator=None, device=None):
+def sample_cloud_occupancy(points, normals=None, points_size=None, uniform_ratio=None, center=True, areas=None, generator=None,
+                           device=None, normals_k: int = 12):
     """sample_occupancy for an oriented point cloud, without meshing it: `points_size` samples -- a `uniform_ratio` share
     uniform in [-1,1]^3, the rest cloud points drawn with probability proportional to their area plus N(0, 0.01) noise --
     labelled by cloud_winding_number > 0.5.  center: the mesh route's rule (_center_rule) on the cloud's points; a
     translation leaves given `areas` as they are, a rescale by s multiplies them by s^2 (areas=None: cloud_areas of the
-    centred points).
+    centred points).  normals=None: a cloud without normals; they are estimated and oriented on the device from
+    `normals_k` neighbours (estimate_normals), on the points after the centring rule -- a translation and a uniform scale
+    leave normals as they are.
     Returns (points [P,3], occupancies [P,1]) float32 numpy, as sample_occupancy."""
+    if points_size is None or uniform_ratio is None:
+        raise ValueError("sample_cloud_occupancy: points_size and uniform_ratio are required")
+    if normals is None and not (1 <= int(normals_k) <= 16):
+        raise ValueError(f"sample_cloud_occupancy: normals_k must be in 1..16, got {normals_k!r}")
     p_np, n_np = load_cloud((points, normals))
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     p = torch.from_numpy(p_np).to(dev)
-    n = torch.from_numpy(n_np).to(dev)
     scale = 1.0
     if center:
         p, scale = _center_rule_scaled(p)
         p = p.contiguous()
+    n = estimate_normals(p, k=int(normals_k)) if n_np is None else torch.from_numpy(n_np).to(dev)
     if areas is None:
         a = cloud_areas(p)
     else:
@@ -589,17 +685,19 @@ def sample_cloud_occupancy(points, normals, points_size, uniform_ratio, center=T
     return pts.cpu().numpy(), occ.reshape(-1, 1).cpu().numpy()
 
 
-def cloud_to_mesh(points, normals, res: int = 256, smooth_iterations: int = 10, chunk: int = 1 << 21):
+def cloud_to_mesh(points, normals=None, res: int = 256, smooth_iterations: int = 10, chunk: int = 1 << 21, normals_k: int = 12):
     """Mesh of an oriented point cloud (the reference's meshProcess.cloud2mesh, here by winding number): cloud_winding_number
     on the linspace(-1, 1, res)^3 grid in chunks of `chunk` queries, extract_surface at level 0.5, vertices rescaled to
     [-1, 1], smooth_mesh.  Returns (vertices [V,3] float32, triangles [F,3] int32) on the device, counter-clockwise seen
     from outside.  Glue over existing calls, and brute force: res^3 x N pairs.  Measured on one MI355X with a 100 000-point
     cloud: 0.24 s at 128^3 and 1.6 s at 256^3 (1.7e12 pairs), linear in both counts -- a million-point
-    cloud at 256^3 takes about 16 s.  Fitting from sample_cloud_occupancy labels needs no mesh and is the main route."""
+    cloud at 256^3 takes about 16 s.  Fitting from sample_cloud_occupancy labels needs no mesh and is the main route.
+    normals=None: a cloud without normals; estimate_normals(points, k=normals_k) supplies them."""
     _need_gpu(points, "cloud_to_mesh")
     dev = points.device
     p = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
-    n = normals.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    n = (estimate_normals(p, k=normals_k) if normals is None
+         else normals.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous())
     a = cloud_areas(p)
     ax = torch.linspace(-1, 1, res, device=dev)
     vol = torch.empty(res ** 3, dtype=torch.float32, device=dev)
