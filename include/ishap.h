@@ -48,7 +48,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * ishap_winding_scratch_bytes) and sdf == 2 / sdf == -2 of ishap_mesh_distance (sign by winding
                             * number for a counter-clockwise / a clockwise mesh; before 12 both values meant parity); 13 since ishap_group_norm32_run;
                             * 14 since the front end for clouds without normals (ishap_cloud_knn, ishap_cloud_normals,
-                            * ishap_cloud_orient, ishap_cloud_orient_scratch_bytes) */
+                            * ishap_cloud_orient, ishap_cloud_orient_scratch_bytes); 15 since the snapshot of a kept forward
+                            * (ishap_unet_snapshot_save / _restore / _drop / _bytes) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -132,8 +133,33 @@ int ishap_unet_block_output(const ishap_unet* u, int group, int index, int* chan
 int ishap_unet_prepare_timesteps(ishap_unet* u, const float* timesteps, int n, void* stream);
 /* Device bytes the context holds besides the packed weights: activation arena + split-K partials + GroupNorm scratch
  * (SURVEY 8b's ishap_workspace_bytes; the context allocates them itself at create time, sized by dry runs of
- * forward + backward at every batch size 1..max_batch). */
+ * forward + backward at every batch size 1..max_batch), plus the snapshot buffers below once one has been saved. */
 long long ishap_unet_workspace_bytes(const ishap_unet* u);
+
+/* Snapshot of a kept forward (ABI 15).  A drag edit's first guided step runs the model on the same latent, at the same
+ * timestep, through the same weights in every edit of a loaded shape (drag_utils.py:309: img = self.w.clone()), so its
+ * forward -- not its loss or backward, which depend on the handles -- can be run once and put back for the later edits.
+ * ishap_unet_snapshot_save: valid after ishap_unet_forward with keep_for_backward bit 0; orders `stream` behind a planned
+ *   tail (as ishap_unet_join_tail) and copies, on `stream`, what a later ishap_unet_backward_input reads: the activation arena
+ *   and the GroupNorm-statistics arena below the forward's marks -- below the planned tail's when the forward planned one, the
+ *   backward from the tap reads nothing of the blocks after it -- and the FiLM rows of the forward's timesteps (the snapshot
+ *   owns its copy: a later ishap_unet_prepare_timesteps does not touch it), together with the host records that point into
+ *   them (saved tensors of every layer, block outputs, the tap).  Buffers are allocated on first use and kept; a second save
+ *   replaces the first.
+ * ishap_unet_snapshot_restore: orders `stream` behind any pending tail, copies the bytes back to the same offsets and puts the
+ *   host records back.  Afterwards ishap_unet_tap_ptr, ishap_unet_copy_tap and ishap_unet_backward_input (any number of
+ *   times) behave as after the forward the snapshot was taken of; the model output is the caller's to keep.  When that
+ *   forward had planned a tail, the blocks after the tap are not part of the snapshot: ishap_unet_backward_from_output and
+ *   ishap_unet_block_output past the tap fail on the restored state.
+ * Both return 0, a negative error, or 1 = unavailable while the per-launch profile records (between ishap_profile_begin and
+ * ishap_profile_end: a recorded edit runs, and counts, every forward) -- the caller then runs the ordinary forward.  A restore
+ * without a valid snapshot is an error and enqueues nothing.  A snapshot stops being valid when a parameter is loaded
+ * (ishap_unet_load_param) and when a forward runs with another batch size or another feat_layer than the snapshot's.
+ * ishap_unet_snapshot_drop frees the buffers; ishap_unet_snapshot_bytes is their size (0 when there are none). */
+int ishap_unet_snapshot_save(ishap_unet* u, void* stream);
+int ishap_unet_snapshot_restore(ishap_unet* u, void* stream);
+int ishap_unet_snapshot_drop(ishap_unet* u);
+long long ishap_unet_snapshot_bytes(const ishap_unet* u);
 
 /* d(sum(tap * cot)) / dx through output block feat_layer ... input block 0: what loss.backward()
  * computes for img.grad at drag_utils.py:383, without the weight gradients the reference discards.

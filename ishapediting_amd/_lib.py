@@ -115,6 +115,10 @@ SYMBOLS = {
     "ishap_unet_workspace_bytes": (C.c_longlong, [c_void_p]),
     "ishap_unet_join_tail": (C.c_int, [c_void_p, c_void_p]),
     "ishap_unet_run_tail": (C.c_int, [c_void_p]),
+    "ishap_unet_snapshot_save": (C.c_int, [c_void_p, c_void_p]),
+    "ishap_unet_snapshot_restore": (C.c_int, [c_void_p, c_void_p]),
+    "ishap_unet_snapshot_drop": (C.c_int, [c_void_p]),
+    "ishap_unet_snapshot_bytes": (C.c_longlong, [c_void_p]),
     "ishap_unet_marks": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, c_void_p, c_void_p]),
     "ishap_unet_prepare_timesteps": (C.c_int, [c_void_p, c_void_p, C.c_int, c_void_p]),
     "ishap_unet_backward_input": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -228,8 +232,8 @@ def lib():
         # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject; 12: ishap_mesh_winding / ishap_cloud_winding /
         # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance; 13: ishap_group_norm32_run;
         # 14: ishap_cloud_knn / ishap_cloud_normals / ishap_cloud_orient / ishap_cloud_orient_scratch_bytes
-        if l.ishap_version() < 14:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 14): rebuild with `python -m ishapediting_amd.build`")
+        if l.ishap_version() < 15:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 15): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -202,6 +202,7 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
   int F;
   Tensor g;
   if (cot_out) {
+    ISHAP_REQUIRE(dry || !u->restored_partial, "the restored snapshot holds the network up to the tap only: no full-depth backward on it");
     if (!dry) ISHAP_TRY(unet_join_tail(u, s));    // full depth: needs the blocks an overlapped forward put on the side stream
     // head backward: out = conv3x3(silu(gn(h)))  (unet.py:612-616,667-669)
     F = n_out - 1;

@@ -270,6 +270,7 @@ static hipEvent_t prof_event() {
   (void)hipEventCreate(&e);
   return e;
 }
+bool ishap_profile_recording() { return g_prof_on; }
 extern "C" int ishap_profile_begin(void) {
   for (auto& r : g_prof) { g_prof_pool.push_back(r.a); g_prof_pool.push_back(r.b); if (r.c) g_prof_pool.push_back(r.c); }
   g_prof.clear();

@@ -110,6 +110,27 @@ struct ParamSlot {
   }
 };
 
+// A copy of what ishap_unet_backward_input reads of one kept forward (ishap_unet_snapshot_save): the bytes of the activation and
+// statistics arenas below the forward's marks (below the planned tail's when one was planned: the backward from the tap reads
+// nothing of the tail's blocks), the FiLM rows, and the host records that point into them.  Restoring copies the bytes back to
+// the same offsets, so the recorded pointers hold again.
+struct UnetSnapshot {
+  bool valid = false;
+  bool partial = false;         // taken of a forward with a planned tail: the blocks after the tap and the head are not in it
+  char* arena = nullptr;      size_t arena_cap = 0, arena_bytes = 0;
+  long long* stat = nullptr;  size_t stat_cap = 0, stat_count = 0;
+  float* film = nullptr;      size_t film_cap = 0, film_floats = 0;
+  int film_ld = 0;
+  size_t fwd_mark = 0, stat_fwd_mark = 0;
+  int last_N = 0, last_feat = -1;
+  Tensor tap, x0, h_final;
+  float* head_stats = nullptr;
+  std::vector<ResSaved> res;
+  std::vector<AttnSaved> attn;
+  std::vector<Tensor> outs, cats;     // BlockL::out / ::cat of the input blocks, the middle block, the output blocks
+  size_t bytes() const { return arena_cap + stat_cap * sizeof(long long) + film_cap * sizeof(float); }
+};
+
 struct ishap_unet {
   ishap_unet_config cfg;
   int device = 0;
@@ -178,6 +199,9 @@ struct ishap_unet {
   float* gn_partial_side = nullptr;
   float* attn_D = nullptr;      // backward attention row sums
   size_t attn_D_floats = 0;
+  bool last_overlap = false;    // the last forward planned a tail (tail.arena_off / tail.stat_off are its)
+  UnetSnapshot snap;
+  bool restored_partial = false;   // the kept state came from a snapshot without the tail's blocks: no full-depth backward on it
 };
 
 struct Exec {
@@ -210,6 +234,7 @@ int conv_op(Exec& e, const ConvLaunch& c);
 // the launch y = w (*) x with w's bias, gathering the sums y carries; call sites add what else they use
 ConvLaunch conv_launch(const Tensor& x, const ConvW& w, const Tensor& y);
 int unet_join_tail(ishap_unet* u, hipStream_t s);
+bool ishap_profile_recording();     // between ishap_profile_begin and ishap_profile_end (igemm.hip)
 bool exec_is_solo(const Exec& e);   // no other stream of this context has work in flight (in-launch rendezvous allowed)
 int slab_materialize(Exec& e, Tensor& t);    // add up a pending tensor with the stand-alone reduce kernel (consumers that cannot)
 long long* salloc(Exec& e, size_t count);   // from the stats arena

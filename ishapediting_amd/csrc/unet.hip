@@ -624,6 +624,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
   const bool overlap = (keep & 2) != 0 && !dry && feat_layer >= 0 && feat_layer + 1 < (int)u->out_blocks.size() && tenancy.granted &&
                        !ishap_rendezvous_contended(u, s);
   if (!dry) ISHAP_TRY(unet_join_tail(u, s));       // the previous forward's tail still owns the arena it is about to reuse
+  if (!dry && u->snap.valid && (u->snap.last_N != N || u->snap.last_feat != feat_layer)) u->snap.valid = false;   // another shape of call
   if (overlap && !u->side) {
     // lowest priority: the tail is throughput work that should fill what the latency-bound chain on the caller's stream
     // leaves idle, not compete with it for compute units
@@ -642,6 +643,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
   const bool zero_in_convert = (u->stat_cap % 2 == 0) && (reinterpret_cast<uintptr_t>(u->stat_base) & 15) == 0;
   if (!dry && u->stat_cap && !zero_in_convert) ISHAP_CHECK_HIP(hipMemsetAsync(u->stat_base, 0, u->stat_cap * sizeof(long long), s));
   u->have_saved = false;
+  u->restored_partial = false;
   const int S = cfg.image_size, HW = S * S;
   // ---- timestep embedding -> emb -> every ResBlock's (scale | shift)   (unet.py:651, :245-250) ----
   u->film_cur = u->d_film;
@@ -717,10 +719,28 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
     ISHAP_TRY(nhwc_f16_to_nchw(u->tap.p, inter_feat, 0, N, u->tap.C, u->tap.H * u->tap.W, u->tap.C, s));
   u->last_N = N;
   u->last_feat = feat_layer;
+  u->last_overlap = overlap;
   u->have_saved = (keep & 1) != 0 && !dry;
   u->fwd_mark = u->arena.off;
   u->stat_fwd_mark = u->stat_off;
   u->bwd_since_fwd = 0;
+  return 0;
+}
+
+// ---- helpers of the snapshot calls below ----
+static void snap_blocks(ishap_unet* u, std::vector<BlockL*>& v) {
+  for (auto& b : u->in_blocks) v.push_back(&b);
+  v.push_back(&u->mid);
+  for (auto& b : u->out_blocks) v.push_back(&b);
+}
+template <typename T>
+static int snap_reserve(T** buf, size_t* cap, size_t need) {
+  if (need <= *cap) return 0;
+  if (*buf) ISHAP_CHECK_HIP(hipFree(*buf));         // hipFree waits for work that may still read it
+  *buf = nullptr;
+  *cap = 0;
+  ISHAP_CHECK_HIP(hipMalloc((void**)buf, need * sizeof(T)));
+  *cap = need;
   return 0;
 }
 
@@ -729,7 +749,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 14; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 15; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
@@ -744,6 +764,7 @@ int ishap_version(void) { return 14; }  // 2: ishap_mesh_smooth takes the scratc
                                         // 13: one GroupNorm launch through the ABI (ishap_group_norm32_run)
                                         // 14: clouds without normals (ishap_cloud_knn, ishap_cloud_normals, ishap_cloud_orient,
                                         //     ishap_cloud_orient_scratch_bytes)
+                                        // 15: snapshot of a kept forward (ishap_unet_snapshot_save / _restore / _drop / _bytes)
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");
@@ -799,6 +820,7 @@ void ishap_unet_destroy(ishap_unet* u) {
   fr(u->d_temb); fr(u->d_e1); fr(u->d_emb); fr(u->d_film);
   fr(u->film_cache); fr(u->pc_temb); fr(u->pc_e1); fr(u->pc_emb);
   fr(u->ws_side); fr(u->gn_partial_side);
+  fr(u->snap.arena); fr(u->snap.stat); fr(u->snap.film);
   if (u->side) (void)hipStreamDestroy(u->side);
   if (u->ev_fork) (void)hipEventDestroy(u->ev_fork);
   if (u->ev_tail) (void)hipEventDestroy(u->ev_tail);
@@ -834,6 +856,7 @@ int ishap_unet_load_param(ishap_unet* u, const char* name, const float* data, lo
   ISHAP_TRY(load_param(u, p, data, (hipStream_t)stream));
   if (!p.loaded) { p.loaded = true; u->n_loaded++; }
   u->film_cache_ts.clear();            // rows prepared from the previous weights are stale
+  u->snap.valid = false;               // and so is a snapshot of a forward through them
   return 0;
 }
 
@@ -911,7 +934,7 @@ const void* ishap_unet_tap_ptr(const ishap_unet* u) { return u ? u->tap.p : null
 long long ishap_unet_workspace_bytes(const ishap_unet* u) {
   if (!u) return 0;
   return (long long)(u->arena.cap + u->ws_floats * sizeof(float) + u->gn_partial_floats * sizeof(float) +
-                     u->stat_cap * sizeof(long long) + u->attn_D_floats * sizeof(float));
+                     u->stat_cap * sizeof(long long) + u->attn_D_floats * sizeof(float) + u->snap.bytes());
 }
 
 int ishap_unet_block_output(const ishap_unet* u, int group, int index, int* channels, int* size, void* dst_nchw_f16,
@@ -925,6 +948,7 @@ int ishap_unet_block_output(const ishap_unet* u, int group, int index, int* chan
   if (size) *size = b->res_out;
   if (!dst_nchw_f16) return 0;
   ISHAP_REQUIRE(u->have_saved && b->out.p, "block outputs stay resident only after a forward with keep_for_backward=1");
+  ISHAP_REQUIRE(!(u->restored_partial && group == 2 && index > u->last_feat), "the restored snapshot holds the network up to the tap only");
   ISHAP_TRY(ishap_check_status());
   ISHAP_CHECK_HIP(hipSetDevice(u->device));
   ISHAP_TRY(unet_join_tail(const_cast<ishap_unet*>(u), (hipStream_t)stream));
@@ -937,5 +961,97 @@ int ishap_unet_copy_tap(const ishap_unet* u, void* dst, void* stream) {
                                  (hipStream_t)stream));
   return 0;
 }
+
+// ---- snapshot of a kept forward: the drag loop's first guided step has the same input, timestep and weights in every edit of
+//      a loaded shape, so its forward is run once and put back for the later edits (two device copies instead of the launches
+//      up to the tap and the tail) ----
+int ishap_unet_snapshot_save(ishap_unet* u, void* stream) {
+  ISHAP_REQUIRE(u, "null argument");
+  ISHAP_REQUIRE(u->have_saved, "a snapshot needs a preceding forward with keep_for_backward=1");
+  if (ishap_profile_recording()) return 1;         // unavailable: the recorded edit runs (and counts) every forward
+  if (u->snap.film && u->film_cur == u->snap.film) {       // the kept state IS the restored snapshot
+    ISHAP_REQUIRE(u->snap.valid, "the kept state came from a snapshot that is no longer valid");
+    return 0;
+  }
+  ISHAP_TRY(ishap_check_status());
+  ISHAP_CHECK_HIP(hipSetDevice(u->device));
+  hipStream_t s = (hipStream_t)stream;
+  ISHAP_TRY(unet_join_tail(u, s));
+  UnetSnapshot& sn = u->snap;
+  sn.valid = false;
+  sn.partial = u->last_overlap;
+  sn.arena_bytes = sn.partial ? u->tail.arena_off : u->fwd_mark;
+  sn.stat_count = sn.partial ? u->tail.stat_off : u->stat_fwd_mark;
+  sn.film_ld = u->film_cur_ld;
+  sn.film_floats = (size_t)u->film_rows * (sn.film_ld ? (size_t)u->last_N : 1);
+  ISHAP_REQUIRE(sn.arena_bytes <= u->arena.cap && sn.stat_count <= u->stat_cap, "forward marks beyond the arenas");
+  ISHAP_TRY(snap_reserve(&sn.arena, &sn.arena_cap, sn.arena_bytes));
+  ISHAP_TRY(snap_reserve(&sn.stat, &sn.stat_cap, sn.stat_count));
+  ISHAP_TRY(snap_reserve(&sn.film, &sn.film_cap, sn.film_floats));
+  if (sn.arena_bytes) ISHAP_CHECK_HIP(hipMemcpyAsync(sn.arena, u->arena.base, sn.arena_bytes, hipMemcpyDeviceToDevice, s));
+  if (sn.stat_count) ISHAP_CHECK_HIP(hipMemcpyAsync(sn.stat, u->stat_base, sn.stat_count * sizeof(long long), hipMemcpyDeviceToDevice, s));
+  ISHAP_CHECK_HIP(hipMemcpyAsync(sn.film, u->film_cur, sn.film_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+  sn.fwd_mark = u->fwd_mark; sn.stat_fwd_mark = u->stat_fwd_mark;
+  sn.last_N = u->last_N; sn.last_feat = u->last_feat;
+  sn.tap = u->tap; sn.x0 = u->x0; sn.h_final = u->h_final; sn.head_stats = u->head_stats;
+  sn.res.clear(); sn.attn.clear(); sn.outs.clear(); sn.cats.clear();
+  for (auto& r : u->res) sn.res.push_back(r.sv);
+  for (auto& a : u->attn) sn.attn.push_back(a.sv);
+  std::vector<BlockL*> blocks;
+  snap_blocks(u, blocks);
+  for (BlockL* b : blocks) { sn.outs.push_back(b->out); sn.cats.push_back(b->cat); }
+  sn.valid = true;
+  return 0;
+}
+
+int ishap_unet_snapshot_restore(ishap_unet* u, void* stream) {
+  ISHAP_REQUIRE(u, "null argument");
+  UnetSnapshot& sn = u->snap;
+  ISHAP_REQUIRE(sn.valid, "no valid snapshot (none saved, or the weights / the batch size / the tapped block changed since)");
+  if (ishap_profile_recording()) return 1;         // unavailable: the caller runs the ordinary forward
+  ISHAP_TRY(ishap_check_status());
+  ISHAP_CHECK_HIP(hipSetDevice(u->device));
+  hipStream_t s = (hipStream_t)stream;
+  ISHAP_TRY(unet_join_tail(u, s));                 // a tail still in flight reads (and owns) the arena about to be overwritten
+  u->have_saved = false;
+  if (sn.arena_bytes) ISHAP_CHECK_HIP(hipMemcpyAsync(u->arena.base, sn.arena, sn.arena_bytes, hipMemcpyDeviceToDevice, s));
+  if (sn.stat_count) ISHAP_CHECK_HIP(hipMemcpyAsync(u->stat_base, sn.stat, sn.stat_count * sizeof(long long), hipMemcpyDeviceToDevice, s));
+  u->film_cur = sn.film;                           // the snapshot's own rows: a later prepare_timesteps may rewrite the cache
+  u->film_cur_ld = sn.film_ld;
+  u->fwd_mark = sn.fwd_mark; u->stat_fwd_mark = sn.stat_fwd_mark;
+  u->arena.off = sn.fwd_mark; u->stat_off = sn.stat_fwd_mark;
+  u->last_N = sn.last_N; u->last_feat = sn.last_feat;
+  u->tap = sn.tap; u->x0 = sn.x0; u->h_final = sn.h_final; u->head_stats = sn.head_stats;
+  for (size_t i = 0; i < u->res.size(); ++i) u->res[i].sv = sn.res[i];
+  for (size_t i = 0; i < u->attn.size(); ++i) u->attn[i].sv = sn.attn[i];
+  std::vector<BlockL*> blocks;
+  snap_blocks(u, blocks);
+  for (size_t i = 0; i < blocks.size(); ++i) { blocks[i]->out = sn.outs[i]; blocks[i]->cat = sn.cats[i]; }
+  u->last_overlap = false;
+  u->tail_deferred = false;
+  u->mid_recorded = false;
+  u->restored_partial = sn.partial;
+  u->bwd_since_fwd = 1;                            // the statistics scratch above the mark is whatever the last backward left:
+  u->have_saved = true;                            // the next backward zeroes it, as a second backward on one forward does
+  return 0;
+}
+
+int ishap_unet_snapshot_drop(ishap_unet* u) {
+  ISHAP_REQUIRE(u, "null argument");
+  ISHAP_CHECK_HIP(hipSetDevice(u->device));
+  UnetSnapshot& sn = u->snap;
+  sn.valid = false;
+  if (u->restored_partial || u->film_cur == sn.film) u->have_saved = false;    // the kept state reads the rows about to be freed
+  if (u->film_cur == sn.film) { u->film_cur = u->d_film; u->film_cur_ld = u->film_rows; }
+  if (sn.arena) ISHAP_CHECK_HIP(hipFree(sn.arena));
+  sn.arena = nullptr; sn.arena_cap = 0;
+  if (sn.stat) ISHAP_CHECK_HIP(hipFree(sn.stat));
+  sn.stat = nullptr; sn.stat_cap = 0;
+  if (sn.film) ISHAP_CHECK_HIP(hipFree(sn.film));
+  sn.film = nullptr; sn.film_cap = 0;
+  return 0;
+}
+
+long long ishap_unet_snapshot_bytes(const ishap_unet* u) { return u ? (long long)u->snap.bytes() : 0; }
 
 }  // extern "C"

@@ -93,6 +93,9 @@ def resize_feat_align(feature, cat_var=True):
 
 _FUSED_UPDATE = os.environ.get("ISHAP_FUSED_UPDATE", "1") == "1"     # guided update inside the DDPM step kernel (0: two launches, for A/B)
 _OVERLAP_TAIL = os.environ.get("ISHAP_OVERLAP_TAIL", "1") == "1"      # round 5: on by default (see training())
+# training() runs the forward of its first guided step once per loaded shape and puts its kept state back in later edits (0: every
+# edit runs all its forwards)
+_FIRST_STEP_REUSE = os.environ.get("ISHAP_FIRST_STEP_REUSE", "1") == "1"
 
 
 class _DragKernelsBase:
@@ -316,6 +319,33 @@ class DragStuff:
 
     args = get_args()
     overlap_tail = None       # None: the module default (_OVERLAP_TAIL, i.e. ISHAP_OVERLAP_TAIL); True / False: this object only
+    # First-step reuse (training()): every edit of a loaded shape starts from the same latent `w` at the same timestep through the
+    # same weights, so the forward of its first guided step -- model output, tap, everything the backward re-reads -- is the same,
+    # bit for bit, in every edit.  The first edit takes a snapshot of it (UNetModel.snapshot_save) and keeps the model output;
+    # later edits restore it instead of running the model.  `_shape_gen` counts the changes of what that forward depends on.
+    _w = None
+    _shape_gen = 0
+    _first_step = None        # {"key": ..., "out": model output} of the snapshot the model holds
+
+    @property
+    def w(self):
+        """The latent every edit starts from (timestep w_time).  Assigning it invalidates the first-step snapshot; so does an
+        in-place change (the snapshot records the tensor's version counter)."""
+        return self._w
+
+    @w.setter
+    def w(self, value):
+        self._w = value
+        self._shape_changed()
+
+    def _shape_changed(self):
+        self._shape_gen = self._shape_gen + 1
+        self._first_step = None
+
+    def _first_step_key(self, overlap):
+        w = self._w
+        return (self._shape_gen, id(self.model), id(w), getattr(w, "_version", None), tuple(w.shape), self.args.feat_layer,
+                self.args.w_time, tuple(getattr(self.diffusion, "timestep_map", ())), bool(overlap))
 
     def __init__(self, device=None, args=None, max_edits=1):
         """`max_edits`: the most edits one training_batch call may run (the model context is built for that batch size; the
@@ -386,6 +416,7 @@ class DragStuff:
 
     def load_weights(self, unet_sd, decoder_sd, lower_bound=None, upper_bound=None):
         """The in-memory half of update_model_params (:229-249)."""
+        self._shape_changed()
         self.model.load_state_dict(unet_sd, strict=True)
         if self.args.use_fp16:
             self.model.convert_to_fp16()
@@ -425,6 +456,7 @@ class DragStuff:
         else:
             img = th.randn((1, 96, self.args.image_size, self.args.image_size), dtype=th.float32, device=self.device)
         self.latent_code = img.clone().detach()
+        self._shape_changed()
         self.w_batch, self.w0_batch, self.feature_guidance_batch = None, None, []     # training_batch: variants of this shape
 
         def record(i, img):
@@ -451,14 +483,18 @@ class DragStuff:
         return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10)
 
     # ------------------------------------------------------------------ drag loop (:302-399)
-    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale):
+    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False):
         """The guided loop of training() and training_batch(): a generator that yields the progress value after each step and
         returns (img, stop_time) -- the latent and the number of unguided steps left when train_flag stopped it (0: ran to
         the end).  `dk`: a DragKernels or BatchDragKernels after setup; `guidance[n]`: the guidance tap of the n-th step, edit e's
         at + e * stride halfs; `scales`: the guidance scale of every image as floats; `guided_scale`: the same as
         p_sample_guidance takes it (a float, or a device tensor with one value per image).  last_losses gets one [images]
-        tensor per step."""
+        tensor per step.
+        `reuse_first` (training() only: `img` is a copy of self.w): the first step's forward comes from the snapshot of an earlier
+        edit of this shape when there is a valid one, and is saved as one otherwise."""
         w_time = self.args.w_time
+        overlap = _OVERLAP_TAIL if self.overlap_tail is None else self.overlap_tail
+        reuse_first = reuse_first and _FIRST_STEP_REUSE and hasattr(self.model, "snapshot_restore")
         stop_time = 0
         self.train_flag = True
         losses = th.zeros((w_time, len(scales)), dtype=th.float32, device=self.device)   # one slot per iteration, no per-step copy
@@ -486,11 +522,23 @@ class DragStuff:
             # (profiles/round5_overlap_tail_ab.txt); bit-identical results, tested.
             # the update img = sample + variance * scale * grad (:384-392) is formed by the step kernel (guided_scale): the loss +
             # backward run between the model call and the step arithmetic either way, beside the forward tail when overlapping
+            first = {}
+            if reuse_first and i == w_time - 1:
+                key, kept = self._first_step_key(overlap), self._first_step
+                # restore() is False while the per-launch profile records: that edit runs (and counts) all its forwards
+                if kept is not None and kept["key"] == key and self.model.has_snapshot() and self.model.snapshot_restore():
+                    first["model_output"] = kept["out"]
+                else:
+                    def keep_first(mo, key=key):       # after the tail: the model output is complete
+                        if self.model.snapshot_save():
+                            self._first_step = {"key": key, "out": mo.clone()}
+                    first["after_tail"] = keep_first
             outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
                                                     keep_for_backward=True, want_inter_feat=False,
                                                     noise=self._noise(i, img), between=loss_and_backward,
-                                                    overlap=_OVERLAP_TAIL if self.overlap_tail is None else self.overlap_tail,
-                                                    guided_scale=guided_scale if _FUSED_UPDATE else None, want_noise=False)
+                                                    overlap=overlap,
+                                                    guided_scale=guided_scale if _FUSED_UPDATE else None, want_noise=False,
+                                                    **first)
             if _FUSED_UPDATE:
                 img = outs["guided"]
             else:
@@ -507,6 +555,9 @@ class DragStuff:
         return img, stop_time
 
     def training(self, sources=None, targets=None, scale=600, cof=0.2):
+        """One drag edit of the loaded shape (drag_utils.py:302-399).  Every edit starts from self.w: from the second edit of a
+        shape on, the first guided step's forward is restored from a snapshot instead of run (ISHAP_FIRST_STEP_REUSE=0: always
+        run); results are bit-identical either way."""
         if self.args.num_samples > 1:
             raise NotImplementedError("We can handle only one shape at each time!")
         self.sources = th.tensor(np.asarray(sources), device=self.device, dtype=th.float32)
@@ -518,7 +569,7 @@ class DragStuff:
                          loss_type=self.args.loss_type)
         dk.setup(self.sources, self.targets, cof)
         self._dk = dk
-        img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale))
+        img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), True)
         self.mesh = self.get_mesh(img=img, t=stop_time)
 
     # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
@@ -536,6 +587,7 @@ class DragStuff:
         self._check_edits(K)
         img = imgs.to(device=self.device, dtype=th.float32).contiguous()
         self.latent_code = img.clone().detach()
+        self._shape_changed()
         self.feature_guidance_batch = []
 
         def record(i, img):
@@ -570,7 +622,8 @@ class DragStuff:
         Afterwards: meshes / volumes (K of each) and last_losses (one [K] tensor per step).  Every edit's drag loss and gradient
         are bitwise those of a solo call; the loss scale of the fp16 backward is one power of two for the batch (exact for the
         linear backward).  Injected noise (step_noise -> [K, ...]) makes edit k repeat a solo run with noise k; drawn noise spans
-        the batch and differs from a solo run's."""
+        the batch and differs from a solo run's.
+        Every step runs its forward: the first-step snapshot of training() is neither used nor taken here."""
         if len(sources) != len(targets):
             raise ValueError(f"{len(sources)} source sets but {len(targets)} target sets: one of each per edit")
         K = len(sources)
@@ -644,7 +697,8 @@ class DragStuff:
         """The guided-sampling loop of train_triplane (drag_utils.py:442-463): every step decodes `pred_xstart` on a
         random batch of occupancy samples and pushes the latent along d(-BCE)/d img (full-depth UNet backward).
         `batch_fn(i) -> (coord, gt)`, `img` and `steps` (step indices to run) replace the random batch / initial noise /
-        full schedule for parity runs."""
+        full schedule for parity runs.  Every step runs its forward (no first-step snapshot: the input differs from call to
+        call); the snapshot training() keeps of the loaded shape stays valid."""
         L = _lib.lib()
         d = self.diffusion
         if img is None:
@@ -735,6 +789,9 @@ class DragStuff:
         return latent
 
     def latent_inversion(self, tri_feat, fwd_noise=None):
+        """DDPM inversion of `tri_feat` to the edit's start latent (self.w) and guidance taps.  Every step runs its forward; the
+        new self.w invalidates the first-step snapshot of training()."""
+        self._shape_changed()
         outs = self.diffusion.ddpm_inversion(self.model, tri_feat, self.args.w_time, fwd_noise=fwd_noise,
                                              clip_denoised=self.args.clip_denoised, feat_layer=self.args.feat_layer,
                                              want_inter_feat=False, tap_sink=self._tap_sink_reset())
@@ -751,6 +808,7 @@ class DragStuff:
         return lambda: self._sink.append(self.model.copy_tap(self.args.feat_layer)[0])
 
     def clear_params(self):
+        self._shape_changed()
         self.mesh0 = None
         self.mesh = None
         self.latent_code = None

@@ -207,7 +207,8 @@ class SpacedDiffusion:
     # ------------------------------------------------------------------ reference surface
     def p_sample_guidance(self, model, x, t, noise=None, variance=None, variance_noise=None, clip_denoised=True,
                           denoised_fn=None, cond_fn=None, model_kwargs=None, feat_layer=-1, keep_for_backward=False,
-                          want_inter_feat=True, between=None, overlap=True, guided_scale=None, want_noise=True):
+                          want_inter_feat=True, between=None, overlap=True, guided_scale=None, want_noise=True,
+                          model_output=None, after_tail=None):
         """gaussian_diffusion.py:446-510.  Returns the same dict keys.
         `between`: a callable run after the model call and before the step arithmetic -- the drag loop passes its loss +
         backward here; with `overlap` the model then runs the part of the network those do not need (everything after the tap)
@@ -218,7 +219,11 @@ class SpacedDiffusion:
         (batched drag edits); a drawn noise (noise=None) then spans the batch, so image n's noise is not the one a single-image
         call would draw.
         `want_noise=False`: the dict's "noise" may be None when the step drew the noise itself (`_draw`); the drag loop does
-        not read it."""
+        not read it.
+        `model_output`: the model's output for (x, t) kept from an earlier call whose kept state the caller has put back
+        (UNetModel.snapshot_restore): the model is not called and no tail is planned; `between` and the step run as always
+        ("inter_feat" is None).  `after_tail(model_output)`: called once `between` has returned and a planned tail has been
+        joined -- the point at which the model output is complete and a snapshot of the forward can be taken."""
         assert denoised_fn is None and cond_fn is None, "not used on the path"
         ti = self._t_index(t)
         if torch.is_tensor(x) and x.requires_grad and torch.is_grad_enabled() and hasattr(model, "backward_from_output"):
@@ -231,7 +236,12 @@ class SpacedDiffusion:
             kw.update(keep_for_backward=keep_for_backward, want_inter_feat=want_inter_feat)
             if between is not None and overlap and feat_layer >= 0 and hasattr(model, "join_tail"):
                 kw.update(overlap_tail=True)
-        mo, inter = self._model(model, x, ti, feat_layer, **kw)
+        if model_output is not None:
+            assert tuple(model_output.shape) == (x.shape[0], 2 * x.shape[1], *x.shape[2:]) and model_output.dtype == torch.float32
+            kw.pop("overlap_tail", None)          # nothing is planned: nothing to close
+            mo, inter = model_output, None
+        else:
+            mo, inter = self._model(model, x, ti, feat_layer, **kw)
         grad = None
         if between is not None:
             try:
@@ -245,6 +255,8 @@ class SpacedDiffusion:
                     raise first from second
                 raise
             self._close_tail(model, kw)
+        if after_tail is not None:
+            after_tail(mo)
         if guided_scale is not None and grad is not None and variance_noise is None:
             rng = None
             if noise is None:

@@ -56,7 +56,8 @@ class UNetModel:
         self._L = L
         self._param_probe = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._fp16 = False
-        self._last_shape = None
+        self._last_shape, self._last_feat = None, -1
+        self._snap_key = None          # (N, feat_layer, input shape) of the forward a valid snapshot holds
 
     # ------------------------------------------------------------------ module-like surface
     def __del__(self):
@@ -82,6 +83,7 @@ class UNetModel:
     def convert_to_fp16(self):
         """unet.py:618-624 -- the packed weights already follow that contract (done at load)."""
         self._fp16 = True
+        self.snapshot_drop()
 
     def param_table(self) -> Dict[str, tuple]:
         L, out = self._L, {}
@@ -101,6 +103,7 @@ class UNetModel:
             raise RuntimeError(f"Error(s) in loading state_dict: missing keys {missing[:5]}..., "
                                f"unexpected keys {unexpected[:5]}...")
         s = _lib.stream_ptr(self.device)
+        self._snap_key = None          # the library drops the snapshot's validity with the first tensor it loads
         with torch.cuda.device(self.device):
             for k, shape in table.items():
                 if k not in sd:
@@ -137,7 +140,9 @@ class UNetModel:
             _lib.check(self._L.ishap_unet_forward(self._h, x.data_ptr(), ts, N, int(feat_layer), out.data_ptr(),
                                                   _lib.ptr(inter), int(bool(keep_for_backward)) | (2 if overlap_tail else 0),
                                                   _lib.stream_ptr(self.device)))
-        self._last_shape = tuple(x.shape)
+        self._last_shape, self._last_feat = tuple(x.shape), int(feat_layer)
+        if self._snap_key is not None and self._snap_key[:2] != (N, int(feat_layer)):
+            self._snap_key = None      # the library invalidates a snapshot when a forward has another batch size or tap
         self._tail_out = out if overlap_tail else None       # alive until the tail that writes it has been joined
         if feat_layer < 0:
             return out
@@ -155,6 +160,48 @@ class UNetModel:
         with torch.cuda.device(self.device):
             _lib.check(self._L.ishap_unet_join_tail(self._h, _lib.stream_ptr(self.device)))
         self._tail_out = None
+
+    # ------------------------------------------------------------------ snapshot of a kept forward
+    def snapshot_save(self) -> bool:
+        """Copy what `backward_input` reads of the last forward(keep_for_backward=True) -- saved activations up to the tap,
+        statistics, FiLM rows, the tap -- into buffers the context keeps; joins a pending tail first.  False: unavailable
+        (the per-launch profile is recording), nothing was saved."""
+        with torch.cuda.device(self.device):
+            rc = self._L.ishap_unet_snapshot_save(self._h, _lib.stream_ptr(self.device))
+        if rc == 1:
+            return False
+        _lib.check(rc)
+        self._tail_out = None
+        self._snap_key = (self._last_shape[0], self._last_feat, self._last_shape)
+        return True
+
+    def snapshot_restore(self) -> bool:
+        """Put the snapshot back: afterwards `tap_ptr`, `copy_tap` and `backward_input` behave as after the forward it was taken
+        of (a full-depth backward does not, when that forward planned a tail).  False: unavailable (the per-launch profile is
+        recording) -- run the forward instead.  Raises when there is no valid snapshot."""
+        with torch.cuda.device(self.device):
+            rc = self._L.ishap_unet_snapshot_restore(self._h, _lib.stream_ptr(self.device))
+        if rc == 1:
+            return False
+        _lib.check(rc)
+        self._tail_out = None
+        if self._snap_key is not None:
+            self._last_shape, self._last_feat = self._snap_key[2], self._snap_key[1]
+        return True
+
+    def has_snapshot(self) -> bool:
+        """A snapshot was saved and nothing has invalidated it since (weight load, convert_to_fp16, a forward of another batch
+        size or tap)."""
+        return self._snap_key is not None
+
+    def snapshot_drop(self):
+        self._snap_key = None
+        if getattr(self, "_h", None):
+            with torch.cuda.device(self.device):
+                _lib.check(self._L.ishap_unet_snapshot_drop(self._h))
+
+    def snapshot_bytes(self) -> int:
+        return int(self._L.ishap_unet_snapshot_bytes(self._h))
 
     def prepare_timesteps(self, timesteps):
         """Compute the timestep-dependent FiLM rows of a sampling loop once (they do not depend on x): forwards at these
