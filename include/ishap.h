@@ -49,7 +49,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * number for a counter-clockwise / a clockwise mesh; before 12 both values meant parity); 13 since ishap_group_norm32_run;
                             * 14 since the front end for clouds without normals (ishap_cloud_knn, ishap_cloud_normals,
                             * ishap_cloud_orient, ishap_cloud_orient_scratch_bytes); 15 since the snapshot of a kept forward
-                            * (ishap_unet_snapshot_save / _restore / _drop / _bytes) */
+                            * (ishap_unet_snapshot_save / _restore / _drop / _bytes); 16 since the connected components of a
+                            * volume (ishap_volume_label, ishap_volume_components_*, ishap_volume_flip) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -576,6 +577,34 @@ int ishap_arap(const float* rest, long long nverts, const int* tris, long long n
                void* scratch, long long scratch_bytes, void* stream);
 /* idx[i] = the vertex nearest to pts[i] (squared distance in fp64), the lowest index on ties (main.py:525-527's pick) */
 int ishap_nearest_vertices(const float* verts, long long nverts, const float* pts, long long npts, int* idx, void* stream);
+
+/* ------------------------------------------------------------------ connected components of a volume (ABI 16)
+ * csrc/components.hip.  vol: float[nx*ny*nz], p = (x*ny + y)*nz + z (z fastest: the decoder's and ishap_surface_*'s layout),
+ * the three extents independent.  A voxel is INSIDE where vol[p] - level > 0.f (the surface's own expression: a NaN is
+ * outside), OUTSIDE otherwise.  nx*ny*nz must be below 2^31; a larger size, a non-positive extent, a connectivity other than
+ * 6 or 26, a phase other than 0 or 1 or a null pointer returns -2 before anything is launched.  Device pointers throughout.
+ *
+ * ishap_volume_label: labels int[n].  phase 1 labels the inside voxels, phase 0 the outside voxels; voxels of the other phase
+ * get -1.  Every labelled voxel gets THE LOWEST LINEAR INDEX OF ITS COMPONENT under connectivity 6 (face neighbours) or 26
+ * (face, edge and corner neighbours): a function of the input alone, bitwise repeatable.  Three launches (union-find in LDS per
+ * 4 x 8 x 32 tile, unions across tile seams, flatten); no kernel waits for another workgroup and the host reads nothing. */
+int ishap_volume_label(const float* vol, int nx, int ny, int nz, float level, int phase, int connectivity, int* labels,
+                       void* stream);
+/* Device bytes of `scratch` for the three calls below on a volume of n voxels (-1 unless 0 < n < 2^31). */
+long long ishap_volume_components_scratch_bytes(long long n);
+/* The table of the components of `labels` (as ishap_volume_label wrote them), by the count / emit pattern of
+ * ishap_surface_count / _emit: count writes the number of components C to count[0] (device int; the caller's one host
+ * read-back) and leaves the root scan in `scratch`; emit, with the same labels and scratch, writes table int[C][9], one row per
+ * component IN ASCENDING ROOT ORDER: root, voxels, xmin, xmax, ymin, ymax, zmin, zmax, border (1 when the component has a voxel
+ * on any of the six faces of the box).  Integer sums and min / max: exact and repeatable.  Do not call emit when C == 0. */
+int ishap_volume_components_count(const int* labels, int nx, int ny, int nz, void* scratch, int* count, void* stream);
+int ishap_volume_components_emit(const int* labels, int nx, int ny, int nz, void* scratch, int* table, void* stream);
+/* Every voxel whose label is in roots (device int[nroots]; entries outside [0, n) are ignored) is reflected across the level:
+ * out = level - (in - level); a voxel moved to the inside whose mirror image would not be inside (in == level) gets the next
+ * float above level.  Every other voxel, and every NaN voxel, is copied bit for bit.  vol_out may alias vol_in.  After the call
+ * (out - level > 0) differs from the input's mask exactly on the non-NaN voxels of the listed components. */
+int ishap_volume_flip(const float* vol_in, float* vol_out, const int* labels, int nx, int ny, int nz, float level,
+                      const int* roots, long long nroots, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------ headless rendering (main.py:345-360, 492-507, 611-612)
  * Replaces what the reference asks of Open3D's scene widget: render_to_image, render_to_depth_image and camera.unproject.

@@ -181,6 +181,12 @@ SYMBOLS = {
     "ishap_cloud_orient_scratch_bytes": (C.c_longlong, [C.c_longlong]),
     "ishap_cloud_orient": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_longlong, C.c_int, c_void_p, C.c_longlong,
                                      C.POINTER(C.c_int), c_void_p]),
+    "ishap_volume_label": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, c_void_p, c_void_p]),
+    "ishap_volume_components_scratch_bytes": (C.c_longlong, [C.c_longlong]),
+    "ishap_volume_components_count": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, c_void_p, c_void_p, c_void_p]),
+    "ishap_volume_components_emit": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, c_void_p, c_void_p, c_void_p]),
+    "ishap_volume_flip": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, c_void_p, C.c_longlong,
+                                    c_void_p, c_void_p]),
     "ishap_group_field_stats": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_longlong, C.c_int, c_void_p, c_void_p]),
     "ishap_arap_scratch_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_longlong]),
     "ishap_arap": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_double,
@@ -231,9 +237,10 @@ def lib():
         # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run; 10: ishap_group_norm32_plan;
         # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject; 12: ishap_mesh_winding / ishap_cloud_winding /
         # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance; 13: ishap_group_norm32_run;
-        # 14: ishap_cloud_knn / ishap_cloud_normals / ishap_cloud_orient / ishap_cloud_orient_scratch_bytes
-        if l.ishap_version() < 15:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 15): rebuild with `python -m ishapediting_amd.build`")
+        # 14: ishap_cloud_knn / ishap_cloud_normals / ishap_cloud_orient / ishap_cloud_orient_scratch_bytes;
+        # 15: ishap_unet_snapshot_*; 16: ishap_volume_label / ishap_volume_components_* / ishap_volume_flip
+        if l.ishap_version() < 16:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 16): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -26,6 +26,7 @@ from . import _lib
 from .script_util import args_to_dict, create_model_and_diffusion, model_and_diffusion_defaults
 from .triplane_decoder import MultiTriplane, decode_volume
 from . import mesh as mesh_backend
+from .volume import clean_volume
 
 
 def get_args(argv=None):
@@ -375,6 +376,7 @@ class DragStuff:
         self.mesh = None
         self.mesh0 = None
         self.volume = None            # last decoded occupancy-logit volume [res]^3 on the device
+        self.clean = None             # None, or volume.clean_volume keywords (e.g. {"keep": "largest"}): get_mesh cleans the volume
         self.noise = []
         self.variance = []
         self.variance_noise = []
@@ -480,6 +482,8 @@ class DragStuff:
         self.tri_feat = tri_feat
         self.volume = decode_volume(self.decoder, tri_feat.to(self.device), self.range, self.middle,
                                     self.args.shape_resolution)
+        if self.clean is not None:    # floaters / cavities out before the surface; self.volume is then the cleaned volume
+            self.volume = clean_volume(self.volume, **self.clean)
         return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10)
 
     # ------------------------------------------------------------------ drag loop (:302-399)

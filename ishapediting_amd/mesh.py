@@ -155,10 +155,11 @@ class OccupancyMesh:
     `np.asarray(mesh.vertex_normals)`, `copy.deepcopy` -- and `to_open3d()`, which builds the real TriangleMesh for
     `update_mesh` (Open3D is imported only there, when called).  `.vertices` / `.triangles` stay device tensors (the
     product's own consumers: Chamfer, sampling, OBJ export); `np.asarray` of them works through torch's __array__ only for
-    host tensors, so GUI code goes through `to_open3d()` or `vertices_numpy()`."""
+    host tensors, so GUI code goes through `to_open3d()` or `vertices_numpy()`.
+    clean: None (the volume as given), or a dict of volume.clean_volume keywords: `.volume` is then the cleaned volume."""
 
-    def __init__(self, volume: torch.Tensor, res: int, smooth_iterations: int = 10):
-        self.volume = volume
+    def __init__(self, volume: torch.Tensor, res: int, smooth_iterations: int = 10, clean=None):
+        self.volume = volume if clean is None else _cleaned(volume, clean)
         self.res = res
         self.smooth_iterations = smooth_iterations
         self._mesh = None
@@ -256,14 +257,23 @@ def mesh_arrays(mesh):
     return np.asarray(v, dtype=np.float32).reshape(-1, 3), np.asarray(t, dtype=np.int32).reshape(-1, 3)
 
 
-def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, backend: str = None):
-    """get_mesh's mesh (drag_utils.py:298-300).  backend None -> the module-level BACKEND:
+def _cleaned(volume: torch.Tensor, clean: dict) -> torch.Tensor:
+    from . import volume as volume_ops              # volume.py imports this module
+    return volume_ops.clean_volume(volume, **clean)
+
+
+def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, backend: str = None, clean=None):
+    """get_mesh's mesh (drag_utils.py:298-300).  clean: None, or a dict of volume.clean_volume keywords (e.g.
+    {"keep": "largest"}): floaters / cavities are taken out of the volume before the surface is made, for every backend.
+    backend None -> the module-level BACKEND:
       "device"      OccupancyMesh (surface, smoothing on the device; vertices / triangles stay device tensors)
       "open3d"      the same device surface handed over as an open3d.geometry.TriangleMesh -- what the reference's GUI
                     expects from drag_stuff.mesh (main.py:288,314,373,478,507); only the final vertex / triangle arrays
                     cross PCIe (a few MB, not the 67 MB volume)
       "third_party" the reference's own PyMCubes + Open3D calls on the host."""
     backend = BACKEND if backend is None else backend
+    if clean is not None:
+        volume = _cleaned(volume, clean)
     if backend == "device":
         return OccupancyMesh(volume, res, smooth_iterations)
     if backend == "open3d":

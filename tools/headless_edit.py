@@ -6,7 +6,9 @@ sources are picked by pixel from the depth picture (render.pick: unproject + nea
 moved by --offset, training() runs the guided loop, and before.png / after.png show the mesh with the red / blue handle
 spheres and green arrows.  With synthetic weights the decoded shape is noise; the path is the point.
 
-  python tools/headless_edit.py --out /tmp/edit [--handles 3] [--num_steps 6] [--w_time 3] [--res 64] [--size 512]
+  python tools/headless_edit.py --out /tmp/edit [--handles 3] [--num_steps 6] [--w_time 3] [--res 64] [--size 512] [--clean largest]
+
+--clean largest keeps only the largest connected component of every decoded volume (DragStuff.clean, volume.clean_volume).
 
 --time instead measures the renderer alone (device events around `--repeat` calls after a warm-up, medians):
   the 256^3 sphere mesh (~300 k triangles of a few pixels each) at 1024 x 1024, and 2 picture-filling triangles at 1024 x 1024
@@ -51,6 +53,8 @@ def edit(a):
     os.makedirs(a.out, exist_ok=True)
     args = get_args(["--w_time", str(a.w_time), "--num_steps", str(a.num_steps), "--shape_resolution", str(a.res)])
     ds = DragStuff(dev, args=args)
+    if a.clean is not None:
+        ds.clean = {"keep": "largest" if a.clean == "largest" else int(a.clean)}
     ds.load_weights(synthetic.round_torso_to_fp16(synthetic.unet_state_dict(full_config(), 1234)), synthetic.decoder_state_dict(4321),
                     -0.05 * np.ones(96, np.float32), 0.05 * np.ones(96, np.float32))
     ds.update_latent_params(img=synthetic.latent(0))
@@ -134,6 +138,8 @@ def main():
     p.add_argument("--scale", type=float, default=1200.0)
     p.add_argument("--cof", type=float, default=0.4)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--clean", default=None, metavar="largest|K",
+                   help="keep only the largest (or the K largest) connected components of each decoded volume")
     p.add_argument("--time", action="store_true", help="measure the renderer instead of running an edit")
     p.add_argument("--time_out", default=None, help="where --time writes its JSON (default profiles/render_times.json)")
     p.add_argument("--warmup", type=int, default=10)
