@@ -22,16 +22,28 @@ __device__ __forceinline__ void plane_axes(int p, int& a_col, int& a_row) {
   a_row = (p == 0) ? 1 : 2;
 }
 
+// Lattice coordinate s + voxel * k as the reference forms it (drag_utils.py:314-316: the product rounded, then the sum).  Not
+// contracted into a fused multiply-add: every call site, and the reference's float32 lattice, get the same bits.
+__device__ __forceinline__ float lattice(float s, float voxel, int k) {
+#pragma clang fp contract(off)
+  const float o = voxel * (float)k;
+  return s + o;
+}
+
 struct Bilin { int x0, y0; float w[4]; };
 __device__ __forceinline__ Bilin bilin_setup(float u, float v, int W) {
 #pragma clang fp contract(off)      // the same (u, v) must give the same weights at every call site (zero loss at zero displacement)
+  // Texel coordinates and weights in double, rounded to float once.  In float, ix = (u + 1) / 2 * (W - 1) carries up to 2^-21 of
+  // a texel of rounding that is the SAME for every channel of a position (and, at a pitch of one texel, for every position of a
+  // lattice row): it does not average out, and moved the loss by 1e-7 to 2e-7 against the float64 statement of the same lattice
+  // (two units in the last place of the float it is returned as).  A dozen wave-uniform operations per position.
   Bilin b;
-  float ix = ((u + 1.f) / 2.f) * (float)(W - 1);
-  float iy = ((v + 1.f) / 2.f) * (float)(W - 1);
-  float fx = floorf(ix), fy = floorf(iy);
+  const double ix = (((double)u + 1.0) / 2.0) * (double)(W - 1);
+  const double iy = (((double)v + 1.0) / 2.0) * (double)(W - 1);
+  const double fx = floor(ix), fy = floor(iy);
   b.x0 = (int)fx; b.y0 = (int)fy;
-  float wx1 = ix - fx, wx0 = (fx + 1.f) - ix, wy1 = iy - fy, wy0 = (fy + 1.f) - iy;
-  b.w[0] = wx0 * wy0; b.w[1] = wx1 * wy0; b.w[2] = wx0 * wy1; b.w[3] = wx1 * wy1;
+  const double wx1 = ix - fx, wx0 = 1.0 - wx1, wy1 = iy - fy, wy0 = 1.0 - wy1;
+  b.w[0] = (float)(wx0 * wy0); b.w[1] = (float)(wx1 * wy0); b.w[2] = (float)(wx0 * wy1); b.w[3] = (float)(wx1 * wy1);
   return b;
 }
 
@@ -40,12 +52,17 @@ __device__ __forceinline__ Bilin bilin_setup(float u, float v, int W) {
 __device__ __forceinline__ void fx_add(long long* dst, float v, float scale) {
   atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)__float2ll_rn(v * scale));
 }
+// The 256 lane sums are added in double (fixed order: repeatable bits) and the workgroup's total is rounded ONCE, to the
+// accumulator's 2^-24: the loss carries no rounding of this tree.
 __device__ __forceinline__ void block_loss_add(float lsum, long long* dst) {
-  __shared__ float red[4];
-  for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
+  __shared__ double red[4];
+  double v = (double)lsum;
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
-  if (threadIdx.x == 0) fx_add(dst, red[0] + red[1] + red[2] + red[3], DRAG_ACC_SCALE);
+  if (threadIdx.x == 0)
+    atomicAdd(reinterpret_cast<unsigned long long*>(dst),
+              (unsigned long long)__double2ll_rn(((red[0] + red[1]) + (red[2] + red[3])) * (double)DRAG_ACC_SCALE));
 }
 
 constexpr int DSEG = 5;     // consecutive lattice positions a wave walks
@@ -76,9 +93,8 @@ __device__ __forceinline__ void drag_motion_body(const DragArgs& a, int blk, int
     const int c = cchunk * 64 + lane;
     const bool live = c < a.Cc;
     const int ch = live ? a.chmap[p * a.Cc + c] : 0;
-    const float oj = a.voxel * (float)(j - a.r);
-    const float su = a.sources[b * 3 + ac], sv = a.sources[b * 3 + ar] + oj;
-    const float tu = a.targets[b * 3 + ac], tv = a.targets[b * 3 + ar] + oj;
+    const float su = a.sources[b * 3 + ac], sv = lattice(a.sources[b * 3 + ar], a.voxel, j - a.r);
+    const float tu = a.targets[b * 3 + ac], tv = lattice(a.targets[b * 3 + ar], a.voxel, j - a.r);
     float a00 = 0.f, a01 = 0.f, a10 = 0.f, a11 = 0.f;     // [row y0 / y0+1][column xcur / xcur+1]
     int xcur = 0, ycur = 0;
     bool open = false;
@@ -98,9 +114,8 @@ __device__ __forceinline__ void drag_motion_body(const DragArgs& a, int blk, int
 #pragma unroll
     for (int ii = 0; ii < DSEG; ++ii) {
       const int i = seg * DSEG + ii;
-      const float oi = a.voxel * (float)(i - a.r);
-      const Bilin bs = bilin_setup(su + oi, sv, a.W);
-      const Bilin bt = bilin_setup(tu + oi, tv, a.W);
+      const Bilin bs = bilin_setup(lattice(su, a.voxel, i - a.r), sv, a.W);
+      const Bilin bt = bilin_setup(lattice(tu, a.voxel, i - a.r), tv, a.W);
       const bool on = live && i < side;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -134,8 +149,7 @@ __device__ __forceinline__ void drag_motion_body(const DragArgs& a, int blk, int
     for (int ii = 0; ii < DSEG; ++ii) {
       const int i = seg * DSEG + ii;
       if (i >= side) break;
-      const float oi = a.voxel * (float)(i - a.r);
-      const Bilin bt = bilin_setup(tu + oi, tv, a.W);
+      const Bilin bt = bilin_setup(lattice(tu, a.voxel, i - a.r), tv, a.W);
       const float d = dseg[ii];
       float g;
       if (a.l1) { if (live) lsum += mult * fabsf(d); g = -((d > 0.f) - (d < 0.f)) * mult / ntot; }
@@ -161,8 +175,8 @@ __device__ __forceinline__ void drag_touch_one(const DragArgs& a, int p, int b, 
   int ac, ar;
   plane_axes(p, ac, ar);
   const float* pt = st ? a.targets : a.sources;
-  float u = pt[b * 3 + ac] + a.voxel * (float)(i - a.r);
-  float v = pt[b * 3 + ar] + a.voxel * (float)(j - a.r);
+  float u = lattice(pt[b * 3 + ac], a.voxel, i - a.r);
+  float v = lattice(pt[b * 3 + ar], a.voxel, j - a.r);
   // th.round((p + 1) * (W - 1) / 2).type(int16): round-half-even, then wrap to int16
   int col = (int)(short)rintf((u + 1.f) * (float)(a.W - 1) / 2.f);
   int row = (int)(short)rintf((v + 1.f) * (float)(a.W - 1) / 2.f);
@@ -207,10 +221,13 @@ __global__ void drag_chan_weight_kernel(DragArgs a) {
 // loss from the two fixed-point sums; leaves them zero for the next call
 __device__ __forceinline__ void drag_finish(const DragArgs& a) {
   const int side = 2 * a.r + 1;
-  const float ntot = 3.f * (float)a.Cc * (float)a.B * (float)side * (float)side * (float)side;
-  float loss = -((float)a.acc[0] * (1.f / DRAG_ACC_SCALE)) / ntot;
-  if (a.cof > 0.f) loss -= a.cof * ((float)a.acc[1] * (1.f / DRAG_ACC_SCALE)) / ((float)a.Cc * (float)a.nmask[0]);
-  a.loss[0] = loss;
+  // one thread, once per edit: formed in double from the two integers and rounded to float once (a chain of six float
+  // operations here cost about a unit in the last place: measured 1.75e-7 -> 1.17e-7 on a loss of 0.76)
+  const double ntot = 3.0 * (double)a.Cc * (double)a.B * (double)side * (double)side * (double)side;
+  double loss = -((double)a.acc[0] * (1.0 / (double)DRAG_ACC_SCALE)) / ntot;
+  if (a.cof > 0.f)
+    loss -= (double)a.cof * ((double)a.acc[1] * (1.0 / (double)DRAG_ACC_SCALE)) / ((double)a.Cc * (double)a.nmask[0]);
+  a.loss[0] = (float)loss;
   a.acc[0] = 0;
   a.acc[1] = 0;
 }
@@ -298,7 +315,7 @@ __global__ void pick_scale_kernel(const unsigned* __restrict__ bits, float* __re
 __device__ __forceinline__ float pick_scale(float m) {
   float sc = 1.f;
   if (m > 0.f && isfinite(m)) sc = exp2f(floorf(log2f(256.f / m)));
-  return fminf(fmaxf(sc, 1.f / 1048576.f), 1.0e30f);
+  return fminf(fmaxf(sc, 0x1p-20f), 0x1p+99f);      // both clamps are powers of two, so the scale is one for every m
 }
 __global__ void scale_to_f16_kernel(const float* __restrict__ g, half_t* __restrict__ o, const float* __restrict__ scale2,
                                     long long n) {
