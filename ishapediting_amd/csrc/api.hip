@@ -419,7 +419,7 @@ int ishap_triplane_reg_values(const float* planes, int S, double* ws, float* reg
 int ishap_x0_grad_to_cotangent(const float* dplanes, const float* range, const float* x, const float* model_out,
                                float sqrt_recip, float sqrt_recipm1, int clip_denoised, int S, float* g_direct,
                                float* cot_out, void* stream) {
-  ISHAP_REQUIRE(dplanes && x && model_out && g_direct && cot_out && (S * S) % 32 == 0, "null argument");
+  ISHAP_REQUIRE(dplanes && x && model_out && g_direct && cot_out, "null argument");
   return x0_grad_launch(dplanes, range, x, model_out, sqrt_recip, sqrt_recipm1, clip_denoised, S, g_direct, cot_out,
                         (hipStream_t)stream);
 }

@@ -10,6 +10,16 @@
 // w_hi x_hi + w_lo x_hi + w_hi x_lo with fp32 accumulation (the dropped w_lo x_lo term is 2^-22 relative), i.e. three
 // v_mfma_f32_32x32x16_f16 (32 cycles each, K = 16) where the fp32 pipe needs sixteen 64-cycle MFMAs: 5.3x fewer matrix
 // cycles for fp32-grade results (parity tests: 1e-4 abs + 1e-4 rel against the fp32 reference, unchanged).
+// RANGE of the split: it is fp32-grade while the lo parts are representable in fp16.  At |W| ~ 1/sqrt(128) the weights' lo parts
+// are already fp16 SUBNORMALS (kept by the conversion and by the MFMA: nothing here may flush them -- flushed, the logit error is
+// 4e-4 instead of 3e-7), and a lo part's absolute rounding error is then 2^-25 whatever its size.  The network is positively
+// homogeneous (s W1, s b1, W2 / s is the same function), so the balance between the two layers is the checkpoint's choice:
+// supported is a balance within 2^+-4 of the synthetic weights', where tests/test_gpu_decoder_oracle.py holds every logit to the
+// float64 bound (measured on an MI355X, 2053 points: max |logit error| 2.7e-6 .. 3.9e-6 for s = 2^-4 .. 2^4, the numpy model of
+// the split alone gives 3e-7 .. 5e-6).  Beyond it the error grows 4x per octave -- measured 5.6e-5 / 6.6e-5 at 2^+-8 and
+// 1.1e-3 / 9.2e-4 at 2^+-12, model 6e-5 and 1e-3 -- and a hidden activation above 65504 overflows the hi part: non-finite
+// logits (model only: not run on a device).  tests/test_decoder_ref_host.py::test_split_range_model is
+// the arithmetic).  A checkpoint outside the range is rebalanced by a power of two before loading, which is exact in fp32.
 // One wave owns 32 query points (lane&31 = point, lane>>5 = which half of the K slots it feeds).
 // Weights are the MFMA A operand (rows = output neuron) read from LDS; activations are the B operand
 // (column = point).  D[neuron][point] keeps the point on the lane, so a layer's accumulator registers
@@ -39,7 +49,7 @@ __global__ void planes_prepare_kernel(const float* __restrict__ latent, const fl
     planes[((long long)p * SS + pix0 + j) * 32 + tx] = tile[tx][j];
 }
 int planes_prepare_launch(const float* latent, const float* rng, const float* mid, float* planes, int S, hipStream_t s) {
-  ISHAP_REQUIRE((S * S) % 32 == 0, "plane size");
+  ISHAP_REQUIRE(S >= 1 && ((long long)S * S) % 32 == 0, "planes_prepare: S * S must be a positive multiple of 32");
   hipLaunchKernelGGL(planes_prepare_kernel, dim3(S * S / 32, 1, 3), dim3(256), 0, s, latent, rng, mid, planes, S);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
@@ -216,7 +226,8 @@ __global__ __launch_bounds__(512) void triplane_decode_kernel(DecodeArgs a) {
 }
 
 int triplane_decode_launch(const DecodeArgs& a, hipStream_t s) {
-  ISHAP_REQUIRE(a.npts > 0, "no points");
+  ISHAP_REQUIRE(a.npts > 0, "triplane decode: no points");
+  ISHAP_REQUIRE(a.S >= 1, "triplane decode: plane size");
   ISHAP_REQUIRE(a.coords != nullptr || (a.lin != nullptr && a.res > 0), "either coords or a grid axis");
   const size_t smem = (size_t)4 * 128 * LDH * sizeof(half_t) + (size_t)(64 * LDB + 3 * 128) * sizeof(float);
   ISHAP_TRY(ishap_set_max_lds((const void*)triplane_decode_kernel, (int)smem));

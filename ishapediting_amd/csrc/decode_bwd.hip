@@ -51,7 +51,7 @@ __global__ __launch_bounds__(128) void decode_points_bwd_kernel(DecBwdArgs a) {
     }
     __syncthreads();
     {
-      float acc = a.b1[t];
+      float acc = a.b1[t];      // bias first, k ascending: the order tests/decoder_ref.py:_chain_error assumes for this kernel
       for (int k = 0; k < 128; ++k) acc += a.W1T[k * 128 + t] * ff[k];
       h1[t] = fmaxf(acc, 0.f);
     }
@@ -113,7 +113,8 @@ __global__ __launch_bounds__(128) void decode_points_bwd_kernel(DecBwdArgs a) {
 }
 
 int decode_points_bwd_launch(const DecBwdArgs& a, hipStream_t s) {
-  ISHAP_REQUIRE(a.npts > 0, "no points");
+  ISHAP_REQUIRE(a.npts > 0, "triplane points_loss_grad: no points");
+  ISHAP_REQUIRE(a.S >= 1, "triplane points_loss_grad: plane size");
   ISHAP_CHECK_HIP(hipMemsetAsync(a.dplanes, 0, (size_t)3 * a.S * a.S * 32 * sizeof(float), s));
   ISHAP_CHECK_HIP(hipMemsetAsync(a.loss, 0, sizeof(float), s));
   int blocks = (int)std::min<long long>(a.npts, 8192);
@@ -149,6 +150,8 @@ __global__ void x0_grad_kernel(const float* __restrict__ dplanes, const float* _
 }
 int x0_grad_launch(const float* dplanes, const float* rng, const float* x, const float* model_out, float sr, float srm1,
                    int clip, int S, float* g_direct, float* cot_out, hipStream_t s) {
+  // the kernel moves 32-pixel tiles: any other size would leave S * S % 32 pixels of every channel unwritten
+  ISHAP_REQUIRE(S >= 1 && ((long long)S * S) % 32 == 0, "x0_grad_to_cotangent: S * S must be a positive multiple of 32");
   hipLaunchKernelGGL(x0_grad_kernel, dim3(S * S / 32, 1, 3), dim3(256), 0, s, dplanes, rng, x, model_out, sr, srm1, clip, S,
                      g_direct, cot_out);
   ISHAP_CHECK_HIP(hipGetLastError());

@@ -104,6 +104,8 @@ __device__ __forceinline__ void fit_phases(const FitArgs& a, const FitLds& L, fl
     for (int g = 0; g < 4; ++g) f[g] += acc[g];
   }
   // ---- phases y = f @ _B: A = _B^T rows (32q + i), K = channels ----
+  // (the K order of this product and of the two layers below -- 32-blocks, within a block the pairs (8g + e, 8g + 4 + e) of one
+  // K = 2 instruction -- is restated in tests/decoder_ref.py:_fit_order for the kink filter's error bound: change both together)
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
 #pragma unroll
@@ -353,7 +355,7 @@ __global__ __launch_bounds__(64 * FIT_WAVES) void triplane_fit_kernel(FitArgs a)
 
 int triplane_fit_loss_grad_launch(const FitArgs& a, hipStream_t s) {
   ISHAP_REQUIRE(a.nbatch >= 0 && a.nrand >= 0 && a.nbatch + a.nrand > 0, "no points");
-  ISHAP_REQUIRE(a.S >= 2, "plane size");
+  ISHAP_REQUIRE(a.S >= 2, "triplane fit_loss_grad: plane size");
   const size_t smem = (size_t)(2 * 128 * FLD + 32 * BLD + 3 * 128) * sizeof(float);
   ISHAP_TRY(ishap_set_max_lds((const void*)triplane_fit_kernel, (int)smem));
   const long long items = (a.nrand + 31) / 32 + (a.nbatch + 31) / 32;
