@@ -33,6 +33,7 @@
 #include <climits>
 
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -40,7 +41,6 @@ constexpr int CC_TX = 4, CC_TY = 8, CC_TZ = 32;            // the tile: 1024 vox
 constexpr int CC_TV = CC_TX * CC_TY * CC_TZ;
 constexpr int CC_THREADS = 256, CC_PER = CC_TV / CC_THREADS;
 constexpr int CC_SLOTS = 2 * CC_TV;                        // LDS hash table of the accumulate pass (load factor <= 1/2)
-constexpr int CS_THREADS = 256, CS_ITEMS = 8, CS_BLOCK = CS_THREADS * CS_ITEMS;   // root scan
 constexpr int CC_ROW = 9;                                  // root, voxels, xmin, xmax, ymin, ymax, zmin, zmax, border
 
 struct Box {
@@ -197,65 +197,31 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int* labels, int
 }
 
 // ---- table ----
-__device__ __forceinline__ unsigned cc_block_scan(unsigned v, unsigned* lds, unsigned& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  unsigned inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  unsigned base = 0, tot = 0;
-  for (int w = 0; w < nw; ++w) {
-    const unsigned t = lds[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  __syncthreads();
-  total = tot;
-  return base + inc - v;
-}
 // bit i: voxel i0 + i is a root
 __device__ __forceinline__ unsigned root_bits(const int* __restrict__ labels, long long i0, long long n) {
   unsigned m = 0;
 #pragma unroll
-  for (int k = 0; k < CS_ITEMS; ++k)
+  for (int k = 0; k < SCAN_ITEMS; ++k)
     if (i0 + k < n && labels[i0 + k] == (int)(i0 + k)) m |= 1u << k;
   return m;
 }
-__global__ __launch_bounds__(CS_THREADS) void cc_count_kernel(const int* __restrict__ labels, long long n, unsigned* __restrict__ bsum) {
+__global__ __launch_bounds__(SCAN_THREADS) void cc_count_kernel(const int* __restrict__ labels, long long n, unsigned* __restrict__ bsum) {
   __shared__ unsigned lds[16];
-  const long long i0 = (long long)blockIdx.x * CS_BLOCK + (long long)threadIdx.x * CS_ITEMS;
+  const long long i0 = (long long)blockIdx.x * SCAN_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
   unsigned total;
-  cc_block_scan(__popc(root_bits(labels, i0, n)), lds, total);
+  block_exclusive_scan(__popc(root_bits(labels, i0, n)), lds, total);
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
-// one workgroup: exclusive scan of the block sums in place, the total -> *count
-__global__ __launch_bounds__(1024) void cc_scan_kernel(unsigned* __restrict__ bsum, long long nb, int* __restrict__ count) {
-  __shared__ unsigned lds[16];
-  unsigned carry = 0;
-  for (long long b0 = 0; b0 < nb; b0 += 1024) {
-    const long long i = b0 + threadIdx.x;
-    const unsigned v = i < nb ? bsum[i] : 0u;
-    unsigned total;
-    const unsigned ex = cc_block_scan(v, lds, total);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *count = (int)carry;
-}
 // a row per root in index order, ready for the accumulation; rank[root] = its row
-__global__ __launch_bounds__(CS_THREADS) void cc_rows_kernel(const int* __restrict__ labels, long long n, const unsigned* __restrict__ bsum,
+__global__ __launch_bounds__(SCAN_THREADS) void cc_rows_kernel(const int* __restrict__ labels, long long n, const unsigned* __restrict__ bsum,
                                                              int* __restrict__ rank, int* __restrict__ table) {
   __shared__ unsigned lds[16];
-  const long long i0 = (long long)blockIdx.x * CS_BLOCK + (long long)threadIdx.x * CS_ITEMS;
+  const long long i0 = (long long)blockIdx.x * SCAN_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
   const unsigned m = root_bits(labels, i0, n);
   unsigned total;
-  unsigned row = bsum[blockIdx.x] + cc_block_scan(__popc(m), lds, total);
+  unsigned row = bsum[blockIdx.x] + block_exclusive_scan(__popc(m), lds, total);
 #pragma unroll
-  for (int k = 0; k < CS_ITEMS; ++k) {
+  for (int k = 0; k < SCAN_ITEMS; ++k) {
     if (!((m >> k) & 1u)) continue;
     rank[i0 + k] = (int)row;
     int* r = table + (long long)row * CC_ROW;
@@ -343,15 +309,14 @@ int fill_box(Box& b, int nx, int ny, int nz) {
   return 0;
 }
 unsigned tiles(const Box& b) { return (unsigned)((b.nx + CC_TX - 1) / CC_TX) * (unsigned)b.tby * (unsigned)b.tbz; }
-long long scan_blocks(long long n) { return (n + CS_BLOCK - 1) / CS_BLOCK; }
 // scratch: rank int[n] (flip: mark bytes[n]) | block sums, 256-byte aligned
-long long sums_offset(long long n) { return (4 * n + 255) / 256 * 256; }
+long long sums_offset(long long n) { return align_up(4 * n, 256); }
 
 }  // namespace
 
 extern "C" long long ishap_volume_components_scratch_bytes(long long n) {
   if (n <= 0 || n >= (1ll << 31)) return -1;
-  return sums_offset(n) + (4 * scan_blocks(n) + 255) / 256 * 256;
+  return sums_offset(n) + align_up(4 * scan_u32_blocks(n), 256);
 }
 
 extern "C" int ishap_volume_label(const float* vol, int nx, int ny, int nz, float level, int phase, int connectivity, int* labels,
@@ -375,11 +340,11 @@ extern "C" int ishap_volume_components_count(const int* labels, int nx, int ny, 
   Box b;
   ISHAP_TRY(fill_box(b, nx, ny, nz));
   ISHAP_REQUIRE(labels && scratch && count, "volume_components_count: null argument");
-  const long long n = (long long)nx * ny * nz, nb = scan_blocks(n);
+  const long long n = (long long)nx * ny * nz, nb = scan_u32_blocks(n);
   unsigned* bsum = (unsigned*)((char*)scratch + sums_offset(n));
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(cc_count_kernel, dim3((unsigned)nb), dim3(CS_THREADS), 0, s, labels, n, bsum);
-  hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(1024), 0, s, bsum, nb, count);
+  hipLaunchKernelGGL(cc_count_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, labels, n, bsum);
+  scan_block_totals(bsum, nb, (unsigned*)count, s);              // the count is below 2^31: fill_box bounds n
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -388,11 +353,11 @@ extern "C" int ishap_volume_components_emit(const int* labels, int nx, int ny, i
   Box b;
   ISHAP_TRY(fill_box(b, nx, ny, nz));
   ISHAP_REQUIRE(labels && scratch && table, "volume_components_emit: null argument");
-  const long long n = (long long)nx * ny * nz, nb = scan_blocks(n);
+  const long long n = (long long)nx * ny * nz, nb = scan_u32_blocks(n);
   int* rank = (int*)scratch;
   const unsigned* bsum = (const unsigned*)((char*)scratch + sums_offset(n));
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(cc_rows_kernel, dim3((unsigned)nb), dim3(CS_THREADS), 0, s, labels, n, bsum, rank, table);
+  hipLaunchKernelGGL(cc_rows_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, labels, n, bsum, rank, table);
   hipLaunchKernelGGL(cc_accum_kernel, dim3(tiles(b)), dim3(CC_THREADS), 0, s, labels, b, (const int*)rank, table);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;

@@ -11,12 +11,12 @@
 // are integer ones whose results do not depend on their order (list lengths, sorted afterwards; min labels), so a call is
 // bitwise repeatable.  CG runs in chunks of ARAP_CHUNK iterations; the host reads the device's done flag once per chunk.
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
 constexpr int AB = 256;                 // threads of every per-vertex / per-triangle workgroup
 constexpr int ARAP_CHUNK = 32;          // CG iterations enqueued between two reads of the done flag
-constexpr int AS_THREADS = 256, AS_ITEMS = 8, AS_BLOCK = AS_THREADS * AS_ITEMS;   // exclusive scan
 constexpr int NPART = 9;                // doubles per workgroup partial
 
 // device-resident state of one call; the host reads it at the end of setup steps and once per CG chunk
@@ -47,69 +47,7 @@ __global__ __launch_bounds__(AB) void arap_check_cons_kernel(const int* __restri
   if (atomicAdd(ccount + c, 1) != 0) atomicOr(&st->bad, 4);
 }
 
-// ---------------------------------------------------------------- exclusive scan of unsigned counts (x[n] = grand total)
-__device__ __forceinline__ unsigned arap_block_scan(unsigned v, unsigned* lds, unsigned& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  unsigned inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  unsigned base = 0, tot = 0;
-  for (int w = 0; w < nw; ++w) {
-    const unsigned t = lds[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  __syncthreads();
-  total = tot;
-  return base + inc - v;
-}
-__global__ __launch_bounds__(AS_THREADS) void arap_scan_blocks_kernel(unsigned* __restrict__ x, long long n, unsigned* __restrict__ totals) {
-  __shared__ unsigned lds[16];
-  const long long i0 = (long long)blockIdx.x * AS_BLOCK + (long long)threadIdx.x * AS_ITEMS;
-  unsigned v[AS_ITEMS], sum = 0;
-#pragma unroll
-  for (int k = 0; k < AS_ITEMS; ++k) { v[k] = i0 + k < n ? x[i0 + k] : 0u; sum += v[k]; }
-  unsigned total;
-  unsigned run = arap_block_scan(sum, lds, total);
-#pragma unroll
-  for (int k = 0; k < AS_ITEMS; ++k) {
-    if (i0 + k < n) x[i0 + k] = run;
-    run += v[k];
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(1024) void arap_scan_totals_kernel(unsigned* __restrict__ totals, long long nb) {
-  __shared__ unsigned lds[16];
-  unsigned carry = 0;
-  for (long long b0 = 0; b0 < nb; b0 += 1024) {
-    const long long i = b0 + threadIdx.x;
-    const unsigned v = i < nb ? totals[i] : 0u;
-    unsigned total;
-    const unsigned ex = arap_block_scan(v, lds, total);
-    if (i < nb) totals[i] = carry + ex;
-    carry += total;
-  }
-}
-__global__ __launch_bounds__(AS_THREADS) void arap_scan_add_kernel(unsigned* __restrict__ x, long long n, const unsigned* __restrict__ totals) {
-  const unsigned add = totals[blockIdx.x];
-  const long long i0 = (long long)blockIdx.x * AS_BLOCK + (long long)threadIdx.x * AS_ITEMS;
-#pragma unroll
-  for (int k = 0; k < AS_ITEMS; ++k)
-    if (i0 + k < n) x[i0 + k] += add;
-}
-
 // ---------------------------------------------------------------- adjacency
-__global__ __launch_bounds__(AB) void arap_vt_degree_kernel(const int* __restrict__ t, long long nt, unsigned* __restrict__ deg) {
-  const long long f = (long long)blockIdx.x * AB + threadIdx.x;
-  if (f >= nt) return;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) atomicAdd(deg + t[3 * f + c], 1u);
-}
 // the slot order depends on atomic timing; arap_rows_kernel sorts every list before it is read
 __global__ __launch_bounds__(AB) void arap_vt_fill_kernel(const int* __restrict__ t, long long nt, const unsigned* __restrict__ off,
                                                           unsigned* __restrict__ cursor, unsigned* __restrict__ list) {
@@ -613,43 +551,34 @@ struct ArapLayout {
 };
 ArapLayout arap_layout(long long nv, long long nt, long long nc) {
   (void)nc;
-  auto up = [](long long b) { return (b + 255) / 256 * 256; };
   ArapLayout L;
-  L.nscan = (nv + 1 + AS_BLOCK - 1) / AS_BLOCK;
+  L.nscan = scan_u32_blocks(nv + 1);
   L.nb = (nv + AB - 1) / AB;
   L.state = 0;
-  L.vt_off = up(L.state + (long long)sizeof(ArapState));
-  L.vt_cur = up(L.vt_off + 4 * (nv + 1));
-  L.ccount = up(L.vt_cur + 4 * nv);
-  L.has = up(L.ccount + 4 * nv);
-  L.row = up(L.has + 4 * nv);
-  L.zero_end = up(L.row + 4 * (nv + 1));
+  L.vt_off = align_up(L.state + (long long)sizeof(ArapState), 256);
+  L.vt_cur = align_up(L.vt_off + 4 * (nv + 1), 256);
+  L.ccount = align_up(L.vt_cur + 4 * nv, 256);
+  L.has = align_up(L.ccount + 4 * nv, 256);
+  L.row = align_up(L.has + 4 * nv, 256);
+  L.zero_end = align_up(L.row + 4 * (nv + 1), 256);
   L.totals = L.zero_end;
-  L.vt_list = up(L.totals + 4 * (L.nscan + 1));
-  L.cand = up(L.vt_list + 4 * 3 * nt);
-  L.col = up(L.cand + 4 * 6 * nt);
-  L.w = up(L.col + 4 * 6 * nt);
-  L.label = up(L.w + 8 * 6 * nt);
-  L.role = up(L.label + 4 * nv);
-  L.diag = up(L.role + 4 * nv);
-  L.x = up(L.diag + 8 * nv);
-  L.r = up(L.x + 24 * nv);
-  L.z = up(L.r + 24 * nv);
-  L.pa = up(L.z + 24 * nv);
-  L.pb = up(L.pa + 24 * nv);
-  L.q = up(L.pb + 24 * nv);
-  L.R = up(L.q + 24 * nv);
-  L.part = up(L.R + 72 * nv);
-  L.bytes = up(L.part + 8 * NPART * L.nb);
+  L.vt_list = align_up(L.totals + 4 * (L.nscan + 1), 256);
+  L.cand = align_up(L.vt_list + 4 * 3 * nt, 256);
+  L.col = align_up(L.cand + 4 * 6 * nt, 256);
+  L.w = align_up(L.col + 4 * 6 * nt, 256);
+  L.label = align_up(L.w + 8 * 6 * nt, 256);
+  L.role = align_up(L.label + 4 * nv, 256);
+  L.diag = align_up(L.role + 4 * nv, 256);
+  L.x = align_up(L.diag + 8 * nv, 256);
+  L.r = align_up(L.x + 24 * nv, 256);
+  L.z = align_up(L.r + 24 * nv, 256);
+  L.pa = align_up(L.z + 24 * nv, 256);
+  L.pb = align_up(L.pa + 24 * nv, 256);
+  L.q = align_up(L.pb + 24 * nv, 256);
+  L.R = align_up(L.q + 24 * nv, 256);
+  L.part = align_up(L.R + 72 * nv, 256);
+  L.bytes = align_up(L.part + 8 * NPART * L.nb, 256);
   return L;
-}
-
-int arap_scan(unsigned* x, long long n, unsigned* totals, long long nscan, hipStream_t s) {
-  hipLaunchKernelGGL(arap_scan_blocks_kernel, dim3((unsigned)nscan), dim3(AS_THREADS), 0, s, x, n, totals);
-  hipLaunchKernelGGL(arap_scan_totals_kernel, dim3(1), dim3(1024), 0, s, totals, nscan);
-  hipLaunchKernelGGL(arap_scan_add_kernel, dim3((unsigned)nscan), dim3(AS_THREADS), 0, s, x, n, (const unsigned*)totals);
-  ISHAP_CHECK_HIP(hipGetLastError());
-  return 0;
 }
 
 int read_state(const ArapState* d, ArapState& h, hipStream_t s) {
@@ -717,11 +646,11 @@ extern "C" int ishap_arap(const float* rest, long long nverts, const int* tris, 
   ISHAP_REQUIRE(!(h.bad & 4), "arap: a repeated constraint id");
 
   // ---- adjacency and weights
-  hipLaunchKernelGGL(arap_vt_degree_kernel, dim3(tb), dim3(AB), 0, s, tris, ntris, vt_off);
-  if (int e = arap_scan(vt_off, nverts + 1, totals, L.nscan, s)) return e;
+  count_triangle_corners(tris, ntris, 1u, vt_off, s);
+  scan_exclusive_u32(vt_off, nverts + 1, totals, nullptr, s);
   hipLaunchKernelGGL(arap_vt_fill_kernel, dim3(tb), dim3(AB), 0, s, tris, ntris, (const unsigned*)vt_off, vt_cur, vt_list);
   hipLaunchKernelGGL(arap_rows_kernel, dim3(vb), dim3(AB), 0, s, tris, nv, (const unsigned*)vt_off, vt_list, cand, row);
-  if (int e = arap_scan(row, nverts + 1, totals, L.nscan, s)) return e;
+  scan_exclusive_u32(row, nverts + 1, totals, nullptr, s);
   hipLaunchKernelGGL(arap_weights_kernel, dim3(vb), dim3(AB), 0, s, rest, tris, nv, (const unsigned*)vt_off,
                      (const unsigned*)vt_list, (const unsigned*)cand, (const unsigned*)row, col, w, diag);
 

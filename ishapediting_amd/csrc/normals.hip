@@ -240,7 +240,7 @@ int knn_tile_stride(int ntiles) {
   }
 }
 
-long long orient_level_bytes(long long n) { return (n * (long long)sizeof(int) + 255) / 256 * 256; }
+long long orient_level_bytes(long long n) { return align_up(n * sizeof(int), 256); }
 
 }  // namespace
 

@@ -8,11 +8,12 @@
 // the triangles around it (indexed mesh, watertight inside the volume).
 // Pipeline (HBM-bound scans over res^3 voxels, deterministic output order = voxel order):
 //   count : per voxel, the 7 owned edges (+x, +y, +xy, +z, +xz, +yz, +xyz) that cross the level -> bit mask; per cell, the
-//           number of triangles; per-block sums          -> one-block exclusive scan of the block sums
+//           number of triangles; per-block sums          -> exclusive scan of each array of block sums (scan.h), totals
 //   emit  : vertices (block-local scan + block offset), per-voxel vertex offsets, then triangles through the
 //           (owner voxel, edge type) -> vertex index lookup.
 #include "common.h"
 #include "mc_table.h"
+#include "scan.h"
 #include "winding.h"
 
 namespace {
@@ -39,7 +40,6 @@ struct SurfArgs {
   unsigned char* tcnt;      // [n] triangles of the cell whose lower corner is this voxel
   unsigned* voff;           // [n] index of the voxel's first vertex
   unsigned* bsum;           // [2][nblocks] per-block (vertices, triangles) -> exclusive prefix after the scan
-  unsigned* counts;         // [2] totals
   int nblocks;
   int method;               // 0: marching tetrahedra (7 edge types per voxel), 1: marching cubes (the 3 axis edges, 256-case table)
 };
@@ -76,23 +76,6 @@ __device__ __forceinline__ int cell_triangles(unsigned bits) {
   return n;
 }
 
-// workgroup exclusive scan of one value per thread; returns the prefix and leaves the total in *total
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* lds, unsigned* total) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int o = 1; o < SB_THREADS; o <<= 1) {
-    unsigned add = t >= o ? lds[t - o] : 0u;
-    __syncthreads();
-    lds[t] += add;
-    __syncthreads();
-  }
-  const unsigned incl = lds[t];
-  *total = lds[SB_THREADS - 1];
-  __syncthreads();
-  return incl - v;
-}
-
 __global__ __launch_bounds__(SB_THREADS) void surf_count_kernel(SurfArgs a) {
   __shared__ unsigned red[2][SB_THREADS];
   const int r = a.res;
@@ -126,32 +109,8 @@ __global__ __launch_bounds__(SB_THREADS) void surf_count_kernel(SurfArgs a) {
   if (threadIdx.x == 0) { a.bsum[blockIdx.x] = red[0][0]; a.bsum[a.nblocks + blockIdx.x] = red[1][0]; }
 }
 
-// one workgroup: exclusive scan of the per-block sums (both arrays), totals -> counts
-__global__ __launch_bounds__(1024) void surf_scan_blocks_kernel(SurfArgs a) {
-  __shared__ unsigned part[1024];
-  for (int arr = 0; arr < 2; ++arr) {
-    unsigned* s = a.bsum + (long long)arr * a.nblocks;
-    const int per = (a.nblocks + 1023) / 1024;
-    const int b0 = threadIdx.x * per, b1 = min(a.nblocks, b0 + per);
-    unsigned sum = 0;
-    for (int i = b0; i < b1; ++i) sum += s[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      unsigned add = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0u;
-      __syncthreads();
-      part[threadIdx.x] += add;
-      __syncthreads();
-    }
-    unsigned run = part[threadIdx.x] - sum;
-    if (threadIdx.x == 1023) a.counts[arr] = part[1023];
-    for (int i = b0; i < b1; ++i) { const unsigned v = s[i]; s[i] = run; run += v; }
-    __syncthreads();
-  }
-}
-
 __global__ __launch_bounds__(SB_THREADS) void surf_emit_vertices_kernel(SurfArgs a, float* __restrict__ verts) {
-  __shared__ unsigned lds[SB_THREADS];
+  __shared__ unsigned lds[16];
   const int r = a.res;
   const long long base = (long long)blockIdx.x * SB_TILE + (long long)threadIdx.x * SB_ITEMS;
   unsigned cnt = 0;
@@ -162,7 +121,7 @@ __global__ __launch_bounds__(SB_THREADS) void surf_emit_vertices_kernel(SurfArgs
     cnt += __popc((unsigned)m[i]);
   }
   unsigned total;
-  unsigned idx = a.bsum[blockIdx.x] + block_exclusive_scan(cnt, lds, &total);
+  unsigned idx = a.bsum[blockIdx.x] + block_exclusive_scan(cnt, lds, total);
 #pragma unroll
   for (int i = 0; i < SB_ITEMS; ++i) {
     const long long p = base + i;
@@ -186,14 +145,14 @@ __global__ __launch_bounds__(SB_THREADS) void surf_emit_vertices_kernel(SurfArgs
 }
 
 __global__ __launch_bounds__(SB_THREADS) void surf_emit_triangles_kernel(SurfArgs a, int* __restrict__ tris) {
-  __shared__ unsigned lds[SB_THREADS];
+  __shared__ unsigned lds[16];
   const int r = a.res;
   const long long base = (long long)blockIdx.x * SB_TILE + (long long)threadIdx.x * SB_ITEMS;
   unsigned cnt = 0;
 #pragma unroll
   for (int i = 0; i < SB_ITEMS; ++i) cnt += base + i < a.n ? a.tcnt[base + i] : 0;
   unsigned total;
-  unsigned idx = a.bsum[a.nblocks + blockIdx.x] + block_exclusive_scan(cnt, lds, &total);
+  unsigned idx = a.bsum[a.nblocks + blockIdx.x] + block_exclusive_scan(cnt, lds, total);
   for (int i = 0; i < SB_ITEMS; ++i) {
     const long long p = base + i;
     if (p >= a.n) break;
@@ -263,72 +222,6 @@ __global__ void smooth_boundary_mask_kernel(const float* __restrict__ v, long lo
     m |= (x >= bmax ? 1u : 0u) << (2 * c + 1);
   }
   mask[i] = m;
-}
-// list lengths: every face lists two heads under each of its corners
-__global__ void smooth_degree_kernel(const int* __restrict__ tris, long long ntris, unsigned* __restrict__ deg) {
-  const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= ntris) return;
-#pragma unroll
-  for (int e = 0; e < 3; ++e) atomicAdd(deg + tris[3 * f + e], 2u);
-}
-// exclusive scan of `x` in place, three launches: per-block scan (SCAN_ITEMS per thread) + block totals, scan of the totals
-// by one workgroup, add-back; x[n] receives the grand total
-constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 8, SCAN_BLOCK = SCAN_THREADS * SCAN_ITEMS;
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* lds, unsigned& total) {
-  // wave-level inclusive scan, then the wave totals through LDS
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  unsigned inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  unsigned base = 0, tot = 0;
-  for (int w = 0; w < nw; ++w) {
-    const unsigned t = lds[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  __syncthreads();
-  total = tot;
-  return base + inc - v;
-}
-__global__ __launch_bounds__(SCAN_THREADS) void scan_blocks_kernel(unsigned* __restrict__ x, long long n, unsigned* __restrict__ totals) {
-  __shared__ unsigned lds[16];
-  const long long i0 = (long long)blockIdx.x * SCAN_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
-  unsigned v[SCAN_ITEMS], sum = 0;
-#pragma unroll
-  for (int k = 0; k < SCAN_ITEMS; ++k) { v[k] = i0 + k < n ? x[i0 + k] : 0u; sum += v[k]; }
-  unsigned total;
-  unsigned run = block_exclusive_scan(sum, lds, total);
-#pragma unroll
-  for (int k = 0; k < SCAN_ITEMS; ++k) {
-    if (i0 + k < n) x[i0 + k] = run;
-    run += v[k];
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(1024) void scan_totals_kernel(unsigned* __restrict__ totals, long long nb, unsigned* __restrict__ grand) {
-  __shared__ unsigned lds[16];
-  unsigned carry = 0;
-  for (long long b0 = 0; b0 < nb; b0 += 1024) {
-    const long long i = b0 + threadIdx.x;
-    const unsigned v = i < nb ? totals[i] : 0u;
-    unsigned total;
-    const unsigned ex = block_exclusive_scan(v, lds, total);
-    if (i < nb) totals[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *grand = carry;
-}
-__global__ __launch_bounds__(SCAN_THREADS) void scan_add_kernel(unsigned* __restrict__ x, long long n, const unsigned* __restrict__ totals) {
-  const unsigned add = totals[blockIdx.x];
-  const long long i0 = (long long)blockIdx.x * SCAN_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
-#pragma unroll
-  for (int k = 0; k < SCAN_ITEMS; ++k)
-    if (i0 + k < n) x[i0 + k] += add;
 }
 // An edge of a level-set mesh that lies IN a face of the grid box belongs to one triangle only (there is no cell on the
 // other side), every other edge to two; the lone occurrence of a boundary edge therefore counts double (bit 31 of its list
@@ -678,7 +571,7 @@ __global__ void group_mean_kernel(int G, float* __restrict__ out) {
   out[2 * G + 1] = (float)(s1 / G);
 }
 
-int fill(SurfArgs& a, const float* volume, int res, float level, void* scratch, unsigned* counts) {
+int fill(SurfArgs& a, const float* volume, int res, float level, void* scratch) {
   ISHAP_REQUIRE(volume && scratch && res >= 2 && res <= 1024, "surface: volume, scratch and 2 <= res <= 1024");
   a.vol = volume; a.res = res; a.level = level; a.n = (long long)res * res * res;
   a.nblocks = (int)((a.n + SB_TILE - 1) / SB_TILE);
@@ -687,7 +580,6 @@ int fill(SurfArgs& a, const float* volume, int res, float level, void* scratch, 
   a.bsum = (unsigned*)s;               s += 2LL * a.nblocks * sizeof(unsigned);
   a.emask = (unsigned char*)s;         s += a.n;
   a.tcnt = (unsigned char*)s;
-  a.counts = counts;
   a.method = 0;
   return 0;
 }
@@ -703,12 +595,13 @@ extern "C" long long ishap_surface_scratch_bytes(int res) {
 extern "C" int ishap_surface_count(const float* volume, int res, float level, int method, void* scratch, unsigned* counts,
                                    void* stream) {
   SurfArgs a;
-  ISHAP_TRY(fill(a, volume, res, level, scratch, counts));
+  ISHAP_TRY(fill(a, volume, res, level, scratch));
   ISHAP_REQUIRE(counts && (method == 0 || method == 1), "method: 0 marching tetrahedra, 1 marching cubes");
   a.method = method;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(surf_count_kernel, dim3(a.nblocks), dim3(SB_THREADS), 0, s, a);
-  hipLaunchKernelGGL(surf_scan_blocks_kernel, dim3(1), dim3(1024), 0, s, a);
+  scan_block_totals(a.bsum, a.nblocks, counts, s);                       // vertices
+  scan_block_totals(a.bsum + a.nblocks, a.nblocks, counts + 1, s);       // triangles
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -716,7 +609,7 @@ extern "C" int ishap_surface_count(const float* volume, int res, float level, in
 extern "C" int ishap_surface_emit(const float* volume, int res, float level, int method, void* scratch, float* verts, int* tris,
                                   void* stream) {
   SurfArgs a;
-  ISHAP_TRY(fill(a, volume, res, level, scratch, nullptr));
+  ISHAP_TRY(fill(a, volume, res, level, scratch));
   ISHAP_REQUIRE(verts && tris && (method == 0 || method == 1), "null argument / method");
   a.method = method;
   hipStream_t s = (hipStream_t)stream;
@@ -730,16 +623,15 @@ extern "C" int ishap_surface_emit(const float* volume, int res, float level, int
 namespace {
 struct SmoothLayout { long long off, cursor, totals, bmask, vtmp, adj, bytes, nblocks; };
 SmoothLayout smooth_layout(long long nverts, long long ntris) {
-  auto up = [](long long b) { return (b + 255) / 256 * 256; };
   SmoothLayout L;
-  L.nblocks = (nverts + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  L.nblocks = scan_u32_blocks(nverts + 1);
   L.off = 0;
-  L.cursor = up(L.off + 4 * (nverts + 1));
-  L.totals = up(L.cursor + 4 * nverts);
-  L.bmask = up(L.totals + 4 * (L.nblocks + 1));
-  L.vtmp = up(L.bmask + 4 * nverts);
-  L.adj = up(L.vtmp + 12 * nverts);
-  L.bytes = up(L.adj + 24 * ntris);
+  L.cursor = align_up(L.off + 4 * (nverts + 1), 256);
+  L.totals = align_up(L.cursor + 4 * nverts, 256);
+  L.bmask = align_up(L.totals + 4 * (L.nblocks + 1), 256);
+  L.vtmp = align_up(L.bmask + 4 * nverts, 256);
+  L.adj = align_up(L.vtmp + 12 * nverts, 256);
+  L.bytes = align_up(L.adj + 24 * ntris, 256);
   return L;
 }
 }  // namespace
@@ -767,10 +659,8 @@ extern "C" int ishap_mesh_smooth(float* verts, long long nverts, const int* tris
   const unsigned tb = (unsigned)((ntris + 255) / 256), vb = (unsigned)((nverts + 255) / 256);
   ISHAP_CHECK_HIP(hipMemsetAsync(base, 0, (size_t)L.totals, s));              // list lengths and fill cursors
   if (bmask) hipLaunchKernelGGL(smooth_boundary_mask_kernel, dim3(vb), dim3(256), 0, s, verts, nverts, box_max, bmask);
-  hipLaunchKernelGGL(smooth_degree_kernel, dim3(tb), dim3(256), 0, s, tris, ntris, off);
-  hipLaunchKernelGGL(scan_blocks_kernel, dim3((unsigned)L.nblocks), dim3(SCAN_THREADS), 0, s, off, nverts + 1, totals);
-  hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(1024), 0, s, totals, L.nblocks, totals + L.nblocks);
-  hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)L.nblocks), dim3(SCAN_THREADS), 0, s, off, nverts + 1, totals);
+  count_triangle_corners(tris, ntris, 2u, off, s);                           // every face lists two heads under each of its corners
+  scan_exclusive_u32(off, nverts + 1, totals, totals + L.nblocks, s);        // list lengths -> list starts, off[nverts] = their sum
   hipLaunchKernelGGL(smooth_fill_kernel, dim3(tb), dim3(256), 0, s, tris, ntris, off, cursor, adj, bmask);
   for (int it = 0; it < iterations; ++it) {
     const float* src = (it & 1) ? vtmp : verts;
@@ -828,7 +718,7 @@ extern "C" long long ishap_mesh_distance_scratch_bytes_sdf(long long ntris, long
   if (ntris < 0 || npts < 0) return -1;
   const long long boxes = ishap_mesh_distance_scratch_bytes(ntris);
   if (sdf != 2 && sdf != -2) return boxes;
-  return (boxes + 255) / 256 * 256 + ishap_winding_bytes(ntris, npts);
+  return align_up(boxes, 256) + ishap_winding_bytes(ntris, npts);
 }
 
 extern "C" int ishap_mesh_distance(const float* verts, const int* tris, long long ntris, const float* pts, long long npts, int sdf,
@@ -847,7 +737,7 @@ extern "C" int ishap_mesh_distance(const float* verts, const int* tris, long lon
   // sdf == 2: inside where the winding number exceeds 0.5 (-2: is below -0.5, a clockwise mesh); any other non-zero sdf:
   // ishap_mesh_occupancy's ray parity
   if (winding) {
-    char* wn = (char*)scratch + (ishap_mesh_distance_scratch_bytes(ntris) + 255) / 256 * 256;
+    char* wn = (char*)scratch + align_up(ishap_mesh_distance_scratch_bytes(ntris), 256);
     ishap_winding_launch_mesh(verts, tris, ntris, pts, npts, dist, sdf > 0 ? 1 : -1, wn, s);
   } else if (sdf) {
     hipLaunchKernelGGL(occupancy_kernel, dim3(blocks), dim3(256), 0, s, verts, tris, ntris, pts, npts, dist);

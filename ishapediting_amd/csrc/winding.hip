@@ -201,7 +201,7 @@ long long ishap_winding_bytes(long long nprims, long long npts) {
   if (nprims == 0 || npts == 0) return 256;
   const WnSplit sp = wn_split(nprims, npts);
   const long long b = sp.parts > 1 ? (long long)sp.parts * npts * (long long)sizeof(float) : 0;
-  return (b + 255) / 256 * 256 + 256;
+  return align_up(b, 256) + 256;
 }
 
 void ishap_winding_launch_mesh(const float* verts, const int* tris, long long ntris, const float* pts, long long npts, float* out,

@@ -122,13 +122,13 @@ def test_arap_abi():
 
 
 def test_arap_kernels_use_no_scratch():
-    """The kernels deform.hip adds, by name, in the built library's code-object metadata: private segment 0 bytes."""
+    """The kernels ishap_arap launches (deform.hip's and the shared scan.hip's), by name, in the built library's code-object metadata: private segment 0 bytes."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_meta
     ks = kernel_meta.kernels(os.path.join(ROOT, "ishapediting_amd", "libishap_hip.so"))
-    names = ["arap_check_tris_kernel", "arap_check_cons_kernel", "arap_scan_blocks_kernel", "arap_scan_totals_kernel",
-             "arap_scan_add_kernel", "arap_vt_degree_kernel", "arap_vt_fill_kernel", "arap_rows_kernel", "arap_weights_kernel",
+    names = ["arap_check_tris_kernel", "arap_check_cons_kernel", "scan_blocks_kernel", "scan_totals_kernel",
+             "scan_add_kernel", "corner_degree_kernel", "arap_vt_fill_kernel", "arap_rows_kernel", "arap_weights_kernel",
              "arap_label_init_kernel", "arap_label_sweep_kernel", "arap_label_jump_kernel", "arap_mark_kernel",
              "arap_roles_kernel", "arap_targets_kernel", "arap_local_kernel", "arap_energy_kernel", "arap_rhs_kernel",
              "arap_cg_init_kernel", "arap_cg_spmv_kernel", "arap_cg_alpha_kernel", "arap_cg_update_kernel",

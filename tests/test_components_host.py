@@ -113,7 +113,7 @@ def test_components_kernels_use_no_scratch_memory():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_meta
     ks = kernel_meta.kernels(os.path.join(ROOT, "ishapediting_amd", "libishap_hip.so"))
-    for want in ("cc_tile_kernel", "cc_seam_kernel", "cc_flatten_kernel", "cc_count_kernel", "cc_scan_kernel", "cc_rows_kernel",
+    for want in ("cc_tile_kernel", "cc_seam_kernel", "cc_flatten_kernel", "cc_count_kernel", "scan_totals_kernel", "cc_rows_kernel",
                  "cc_accum_kernel", "cc_mark_kernel", "cc_flip_kernel"):
         found = [n for n in ks if want in n]
         assert len(found) == 1, (want, found)

@@ -61,6 +61,16 @@ def bar_case():
     return v, f, static, handles, hp
 
 
+def bar2048_case():
+    """a bent bar of exactly 2 048 vertices: the scans of its nverts + 1 list lengths start a second block of one element"""
+    v, f = R.bent_bar(n=(42, 12, 12))
+    assert v.shape[0] == 2048
+    static = np.nonzero(v[:, 0] < v[:, 0].min() + 0.1)[0]
+    handles = np.nonzero(v[:, 0] > v[:, 0].max() - 0.03)[0]
+    hp = v[handles] + np.array([0.0, 0.35, 0.1], np.float32)
+    return v, f, static, handles, hp
+
+
 def mc_case():
     v, f = grid_mesh(smooth_field(22, 11), smooth=5)
     v, f = v.cpu().numpy(), f.cpu().numpy()
@@ -71,7 +81,7 @@ def mc_case():
     return v, f, static, handles, hp
 
 
-CASES = {"icosphere": sphere_case, "bent_bar": bar_case, "marching_cubes": mc_case}
+CASES = {"icosphere": sphere_case, "bent_bar": bar_case, "marching_cubes": mc_case, "bar2048": bar2048_case}
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -94,6 +104,8 @@ def test_matches_the_fp64_statement(name):
         np.testing.assert_allclose(info["energy"], E_ref, rtol=1e-6, atol=1e-12 * R.rest_energy_scale(v, f))
         assert info["converged"].all()
         assert np.array_equal(got[ids], pos.astype(np.float64))    # constraints bit for bit
+    again, _ = deform_as_rigid_as_possible(torch.from_numpy(v).to(dev()), torch.from_numpy(f).to(dev()), ids, pos, max_iter=K, tol=1e-12)
+    assert torch.equal(again, out)                                 # a repeat of the last call: the same bits
 
 
 def test_invariants_exact_constraints_unconstrained_box_and_repeatability():

@@ -1,7 +1,7 @@
 """GPU tests of the volume connected-components pass (csrc/components.hip, ishapediting_amd/volume.py) against the numpy
 statement (tests/components_ref.py): exact equality everywhere, no tolerance.  The boxes surround the kernel's 4 x 8 x 32
-tile: one voxel, a box inside one tile row but one voxel over along z, a box of 3 x 2 x 3 ragged tiles, and 64^3 (16 x 8 x 2
-tiles, a 128-block root scan)."""
+tile: one voxel, a box inside one tile row but one voxel over along z, a box of 3 x 2 x 3 ragged tiles, 64^3 (16 x 8 x 2
+tiles, a 128-block root scan), and a sparse 130 x 128 x 128 (1040 blocks: the scan of the block sums carries)."""
 import ctypes
 
 import numpy as np
@@ -54,6 +54,48 @@ def test_labels_and_table_equal_the_statement(shape, name, connectivity):
         again = volume_components(v, level, phase_name, connectivity)
         for f in ("roots", "voxels", "bbox", "border", "labels"):
             assert torch.equal(getattr(again, f), getattr(comps, f)), f
+
+
+def sparse_1040_blocks():
+    """(130, 128, 128): the root scan has 1040 blocks of 2048 voxels, so the workgroup that scans the block sums takes a second
+    pass of 1024 with a carry.  A few small pieces: in the first block, ending block 1023 (flat index 2048 * 1024 - 1),
+    starting block 1024, across x = 127 / 128 (a root in block 1023 with voxels past it), in blocks 1024 and 1039, at the very
+    end, and two voxels that touch at a corner (one component under connectivity 26, two under 6)."""
+    vol = -np.ones((130, 128, 128), np.float32)
+    vol[0:3, 2:5, 5:8] = 1.0
+    vol[64, 64, 64] = vol[65, 65, 65] = 2.0
+    vol[127:129, 120:122, 60:62] = 1.0
+    vol[127, 127, 127] = vol[128, 0, 0] = 3.0
+    vol[128, 10:12, 10:12] = 1.0
+    vol[129, 120, 5] = 0.5
+    vol[129, 126:128, 126:128] = 1.0
+    return vol
+
+
+@pytest.mark.parametrize("connectivity", [6, 26])
+def test_the_table_past_1024_scan_blocks_equals_the_statement(connectivity):
+    """The inside phase only: the outside is one component rooted at voxel 0, which no carry reaches, and costs the numpy
+    statement seconds."""
+    from ishapediting_amd.volume import label_volume, volume_components
+    vol = sparse_1040_blocks()
+    v = T(vol)
+    want = R.label(vol, 0.0, 1, connectivity)
+    tab = R.table(want)
+    assert len(tab) == (8 if connectivity == 26 else 9)
+    assert {261, 2048 * 1024 - 1, 2048 * 1024, vol.size - 130} <= set(tab[:, 0].tolist())
+    assert (tab[:, 0] // 2048 < 1024).sum() >= 4 and (tab[:, 0] // 2048 >= 1024).sum() >= 4
+    got = label_volume(v, 0.0, "inside", connectivity)
+    assert int((got.cpu().numpy() != want).sum()) == 0
+    comps = volume_components(v, 0.0, "inside", connectivity)
+    assert len(comps) == len(tab)
+    np.testing.assert_array_equal(comps.roots.cpu().numpy(), tab[:, 0])
+    np.testing.assert_array_equal(comps.voxels.cpu().numpy(), tab[:, 1])
+    np.testing.assert_array_equal(comps.bbox.cpu().numpy().reshape(-1, 6), tab[:, 2:8])
+    np.testing.assert_array_equal(comps.border.cpu().numpy(), tab[:, 8])
+    assert torch.equal(comps.labels, got)
+    again = volume_components(v, 0.0, "inside", connectivity)
+    for f in ("roots", "voxels", "bbox", "border", "labels"):
+        assert torch.equal(getattr(again, f), getattr(comps, f)), f
 
 
 def test_component_counts_of_the_constructed_cases():

@@ -119,6 +119,67 @@ def test_smoothing_and_chamfer_match_cpu_statement():
     assert abs(c_s - S.chamfer_distance(pa.cpu(), pb.cpu(), 2000, seed=4)) <= 1e-5 * max(1.0, c_o)
 
 
+TET_FACES = ((0, 1, 2), (0, 2, 3), (0, 3, 1), (1, 3, 2))
+BIPYRAMID_FACES = ((0, 2, 3), (0, 3, 4), (0, 4, 2), (1, 3, 2), (1, 4, 3), (1, 2, 4))      # apexes 0 and 1 over the ring 2, 3, 4
+
+
+def disjoint_solids(nverts, seed):
+    """A mesh of exactly `nverts` vertices, every one of them used: nverts % 4 triangular bipyramids (5 vertices, valences 3
+    and 4) and tetrahedra for the rest, all closed and disjoint, under a random renumbering of the vertices so that list
+    lengths vary along the scanned array."""
+    g = torch.Generator().manual_seed(seed)
+    k = nverts % 4
+    m = (nverts - 5 * k) // 4
+    assert m >= 0
+    bip = (torch.arange(k) * 5)[:, None, None] + torch.tensor(BIPYRAMID_FACES)[None]
+    tet = (5 * k + torch.arange(m) * 4)[:, None, None] + torch.tensor(TET_FACES)[None]
+    faces = torch.randperm(nverts, generator=g)[torch.cat([bip.reshape(-1, 3), tet.reshape(-1, 3)])]
+    verts = torch.rand((nverts, 3), generator=g) * 64.0
+    return verts, faces[torch.randperm(faces.shape[0], generator=g)].to(torch.int32)
+
+
+@pytest.mark.parametrize("nverts", [2047, 2048, 2049])
+def test_smoothing_at_the_block_edges_of_the_offset_scan(nverts):
+    """The list starts are an exclusive scan of nverts + 1 lengths in blocks of 2048: nverts + 1 ends a block exactly, starts a
+    block of one element, starts a block of two."""
+    from ishapediting_amd.mesh import smooth_mesh
+    v, f = disjoint_solids(nverts, 40 + nverts)
+    sm_d = smooth_mesh(v.to(dev()), f.to(dev()), 3)
+    sm_o = S.smooth_simple(v, f.long(), 3)
+    err = float((sm_d.cpu() - sm_o).abs().max())
+    print(f"nverts {nverts}: max abs {err:.3e}")
+    assert err < 1e-4
+    assert float((sm_d.cpu() - v).abs().max()) > 1e-3
+
+
+def test_smoothing_past_1024_scan_blocks():
+    """2048 * 1024 + 5 vertices: the block totals of the offset scan number 1025, so the one workgroup that scans them takes a
+    second pass with a carry.  Sixteen anchors around the first block, a block edge, both sides of block 1023 / 1024 and the
+    end form four disjoint closed tetrahedra; every other vertex is isolated: a list start that is wrong anywhere moves an
+    anchor to the wrong place or reads another vertex's (empty) list."""
+    from ishapediting_amd.mesh import smooth_mesh
+    B, N = 2048, 2048 * 1024
+    nverts = N + 5
+    anchors = [0, B - 1, B, B + 1, 3 * B - 2, 512 * B, 512 * B + 1, 1023 * B - 1, 1023 * B, N - 2, N - 1, N, N + 1, N + 2, N + 3, N + 4]
+    assert len(set(anchors)) == 16 and max(anchors) == nverts - 1
+    a = torch.tensor(anchors)
+    faces = torch.cat([a[k::4][torch.tensor(TET_FACES)] for k in range(4)]).to(torch.int32)      # tetrahedron k: anchors k, k+4, k+8, k+12
+    g = torch.Generator().manual_seed(77)
+    v = torch.rand((nverts, 3), generator=g) * 64.0
+    vd, fd = v.to(dev()), faces.to(dev())
+    sm_d = smooth_mesh(vd, fd, 3)
+    sm_o = S.smooth_simple(v, faces.long(), 3)
+    out = sm_d.cpu()
+    err = float((out[a] - sm_o[a]).abs().max())
+    print(f"anchors: max abs {err:.3e}")
+    assert err < 1e-4
+    assert float((out[a] - v[a]).abs().max()) > 1e-3
+    rest = torch.ones(nverts, dtype=torch.bool)
+    rest[a] = False
+    assert torch.equal(out[rest], v[rest])                              # isolated vertices: bitwise unchanged
+    assert torch.equal(smooth_mesh(vd, fd, 3), sm_d)
+
+
 def test_smoothing_rejects_an_undersized_scratch_buffer():
     """ABI version 2: the scratch size travels with the pointer; a buffer sized by the old 32-bytes-per-vertex rule
     fails the call instead of being written out of bounds."""
