@@ -50,7 +50,9 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * 14 since the front end for clouds without normals (ishap_cloud_knn, ishap_cloud_normals,
                             * ishap_cloud_orient, ishap_cloud_orient_scratch_bytes); 15 since the snapshot of a kept forward
                             * (ishap_unet_snapshot_save / _restore / _drop / _bytes); 16 since the connected components of a
-                            * volume (ishap_volume_label, ishap_volume_components_*, ishap_volume_flip) */
+                            * volume (ishap_volume_label, ishap_volume_components_*, ishap_volume_flip); 17 since the region
+                            * weights of the drag loss (the trailing `weights` of ishap_drag_args, `weights` / `weights_stride` of
+                            * ishap_drag_batch_args, ishap_region_plane_weights, ishap_region_plane_weights_scratch_bytes) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -330,6 +332,12 @@ typedef struct {
   void* grad_fx;          /* device scratch, W*W*ld*8 bytes: the gradient scatter accumulates in 64-bit fixed point so
                            * that repeated edits are bitwise identical (integer atomics commute) */
   unsigned char* chan_weight; /* device scratch [3*ld] bytes: inverse of chmap, filled by ishap_drag_setup */
+  const float* weights;   /* ABI 17, read by the loss calls only.  NULL: no weights.  Else device float[3*W*W], indexed [plane][row][col]
+                           * like `touched`: the mask term of an UNTOUCHED texel t of plane p is multiplied by weights[p][t] (>= 0,
+                           * finite; 0 frees the texel, > 1 holds it harder), the count it is divided by stays the count of untouched
+                           * texels, and the weight of a touched texel is ignored.  A map of exact ones gives bitwise the results of
+                           * NULL.  With cof <= 0 there is no mask term and the map is not used.  Built from 3-D regions by
+                           * ishap_region_plane_weights.  Last field: a positional construction that stops before it means NULL. */
 } ishap_drag_args;
 /* once per edit: rounded-texel bitmap and complement count (drag_utils.py:322-334); also zeroes acc and grad_fx, which
  * every loss call below expects zero on entry and leaves zero on return */
@@ -365,6 +373,9 @@ typedef struct {
   void* scratch;          /* device, 16-byte aligned, ishap_drag_batch_scratch_bytes(E, W, ld) bytes; zeroed by the setup call,
                            * left zero by every loss call */
   long long scratch_bytes;
+  const float* weights;   /* ABI 17, as in ishap_drag_args: NULL, or the base of device float[E][3*W*W]; edit e reads weights +
+                           * e * weights_stride.  An edit without regions reads a map of ones (bitwise its unweighted result). */
+  long long weights_stride; /* floats between the maps of consecutive edits (>= 3*W*W), or 0: one map for every edit */
 } ishap_drag_batch_args;
 long long ishap_drag_batch_scratch_bytes(int E, int W, int ld);
 /* once per batch of edits (what ishap_drag_setup does, for each edit) */
@@ -375,6 +386,34 @@ int ishap_drag_batch_loss_grad(const ishap_drag_batch_args* a, const void* edit_
 /* the same plus the fp16 cotangent [E][W*W][ld] with the batch's loss scale; bits: device uint32[1]; scale2: device float[2] */
 int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
                                     float* grad_nhwc, float* loss, void* cot_f16, unsigned* bits, float* scale2, void* stream);
+/* ---------------------------------------------------------- region-constrained edits (ABI 17; csrc/regions.hip)
+ * The weight map of the drag loss's mask term from 3-D regions in the coordinates handles use, [-1, 1]^3.  A region is a union
+ * of primitives and one voxel grid; `keep` must not move, `free` may.  Its SHADOW on plane p (axes as the drag loss: plane 0
+ * col = x, row = y; plane 1 col = y, row = z; plane 2 col = x, row = z) is a set of plane texels:
+ *   box     the texel centre (u = 2 col / (W - 1) - 1, v likewise, in double) lies in the projected rectangle, bounds inclusive;
+ *   sphere  (u - cu)^2 + (v - cv)^2 <= r^2 in double;
+ *   voxels  uint8 [D][D][D], non-zero = set, indexed [ix][iy][iz] on linspace(-1, 1, D) like a decoded volume, D >= W: every set
+ *           voxel marks the texel nearest to it on each plane, t = (2 i (W - 1) + (D - 1)) / (2 (D - 1)) in integers.
+ * Every shadow is grown by a Chebyshev radius of `dilate` texels, clipped at the map.  Then weights_out[p][row][col] =
+ * keep_weight in the keep shadow, else free_weight in the free shadow, else 1 (keep overrides free).
+ * The inherent limit: a plane texel stands for a whole column through the shape, so a region constrains its three shadows, not
+ * only its own volume.
+ * prims: device array of n_prims entries (NULL when n_prims = 0); keep_voxels / free_voxels: device, either may be NULL (then D
+ * is not used); shadow_counts: device int[2] or NULL, receives the texel counts of the keep and the free shadow over the three
+ * planes BEFORE dilation (0: the region is thinner than the texel pitch or outside the cube); scratch: device, 16-byte aligned,
+ * ishap_region_plane_weights_scratch_bytes(W) bytes, needs no initialisation.  Returns an error code (and launches nothing) for
+ * W < 2 or > 4096, D < W or > 4096 with a grid, dilate < 0, non-finite or negative weights, a NULL output. */
+typedef struct {
+  int kind;        /* 0 box, 1 sphere */
+  int role;        /* 0 keep, 1 free */
+  double a[3];     /* box: lo; sphere: centre */
+  double b[3];     /* box: hi; sphere: b[0] = radius */
+} ishap_region_prim;
+long long ishap_region_plane_weights_scratch_bytes(int W);
+int ishap_region_plane_weights(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels,
+                               const unsigned char* free_voxels, int D, int W, int dilate, float keep_weight, float free_weight,
+                               float* weights_out, int* shadow_counts, void* scratch, long long scratch_bytes, void* stream);
+
 /* fp32 gradient -> fp16 cotangent times a power-of-two loss scale picked from max|g| on the device;
  * bits: device scratch uint32[1]; scale2: device float[2] = {scale, 1/scale} */
 int ishap_grad_to_scaled_f16(const float* grad, void* out_f16, unsigned* bits, float* scale2, long long numel,

@@ -33,14 +33,19 @@ class StepCoefs(C.Structure):
 class DragArgsC(C.Structure):
     _fields_ = [("W", C.c_int), ("ld", C.c_int), ("Cc", C.c_int), ("chmap", c_void_p), ("sources", c_void_p),
                 ("targets", c_void_p), ("B", C.c_int), ("r", C.c_int), ("voxel", C.c_float), ("cof", C.c_float),
-                ("l1", C.c_int), ("touched", c_void_p), ("nmask", c_void_p), ("acc", c_void_p), ("grad_fx", c_void_p), ("chan_weight", c_void_p)]
+                ("l1", C.c_int), ("touched", c_void_p), ("nmask", c_void_p), ("acc", c_void_p), ("grad_fx", c_void_p), ("chan_weight", c_void_p),
+                ("weights", c_void_p)]      # trailing, ABI 17: a positional construction that stops before it means no weights
 
 
 class DragBatchArgsC(C.Structure):
     _fields_ = [("E", C.c_int), ("W", C.c_int), ("ld", C.c_int), ("Cc", C.c_int), ("chmap", c_void_p), ("sources", c_void_p),
                 ("targets", c_void_p), ("handle_offsets", C.POINTER(C.c_int)), ("r", C.c_int), ("voxel", C.c_float),
                 ("cof", C.POINTER(C.c_float)), ("l1", C.c_int), ("orig_stride", C.c_longlong), ("scratch", c_void_p),
-                ("scratch_bytes", C.c_longlong)]
+                ("scratch_bytes", C.c_longlong), ("weights", c_void_p), ("weights_stride", C.c_longlong)]     # the last two: ABI 17
+
+
+class RegionPrimC(C.Structure):
+    _fields_ = [("kind", C.c_int), ("role", C.c_int), ("a", C.c_double * 3), ("b", C.c_double * 3)]
 
 
 class IgemmBufC(C.Structure):
@@ -145,6 +150,9 @@ SYMBOLS = {
     "ishap_drag_batch_loss_grad": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ishap_drag_batch_loss_cotangent": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p, c_void_p, c_void_p]),
+    "ishap_region_plane_weights_scratch_bytes": (C.c_longlong, [C.c_int]),
+    "ishap_region_plane_weights": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                             c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
     "ishap_grad_to_scaled_f16": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
     "ishap_planes_prepare": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, c_void_p, c_void_p]),
     "ishap_triplane_fit_loss_grad": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, c_void_p, c_void_p,
@@ -238,9 +246,10 @@ def lib():
         # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject; 12: ishap_mesh_winding / ishap_cloud_winding /
         # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance; 13: ishap_group_norm32_run;
         # 14: ishap_cloud_knn / ishap_cloud_normals / ishap_cloud_orient / ishap_cloud_orient_scratch_bytes;
-        # 15: ishap_unet_snapshot_*; 16: ishap_volume_label / ishap_volume_components_* / ishap_volume_flip
-        if l.ishap_version() < 16:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 16): rebuild with `python -m ishapediting_amd.build`")
+        # 15: ishap_unet_snapshot_*; 16: ishap_volume_label / ishap_volume_components_* / ishap_volume_flip;
+        # 17: the weights fields of DragArgsC / DragBatchArgsC, ishap_region_plane_weights
+        if l.ishap_version() < 17:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 17): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -4,12 +4,14 @@
 #include "ddpm.h"
 #include "decode.h"
 #include "drag.h"
+#include "regions.h"
 #include "render.h"
 
 static thread_local std::string g_err;
 void ishap_set_error(const std::string& msg) { g_err = msg; }
 
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -269,7 +271,7 @@ int ishap_drag_loss_grad(const ishap_drag_args* a, const void* edit, const void*
   ISHAP_TRY(fill_drag(a, d));
   ISHAP_REQUIRE(edit && orig && grad && loss, "null argument");
   fill_drag_call(d, edit, orig, grad, loss);
-  return drag_batch_loss_launch(d, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  return drag_batch_loss_launch(d, nullptr, nullptr, nullptr, a->weights, 0, (hipStream_t)stream);
 }
 
 int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit, const void* orig, float* grad, float* loss,
@@ -278,7 +280,7 @@ int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit, const 
   ISHAP_TRY(fill_drag(a, d));
   ISHAP_REQUIRE(edit && orig && grad && loss && cot_f16 && bits && scale2, "null argument");
   fill_drag_call(d, edit, orig, grad, loss);
-  return drag_batch_loss_launch(d, (half_t*)cot_f16, bits, scale2, (hipStream_t)stream);
+  return drag_batch_loss_launch(d, (half_t*)cot_f16, bits, scale2, a->weights, 0, (hipStream_t)stream);
 }
 
 // ---- E edits per call: one scratch buffer, carved as [grad_fx E*W*W*ld int64][acc E*2 int64][nmask E int32][touched E*3*W*W]
@@ -303,6 +305,7 @@ static int fill_drag_batch(const ishap_drag_batch_args* a, DragBatchArgs& d) {
   ISHAP_REQUIRE(a && a->chmap && a->sources && a->targets && a->handle_offsets && a->cof && a->scratch, "null argument");
   ISHAP_REQUIRE(a->E >= 1 && a->E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");      // hoff / cof below hold that many
   ISHAP_REQUIRE(a->W > 1 && a->r >= 0 && a->Cc >= 1 && a->ld >= 1 && a->orig_stride >= 0, "drag dims");
+  ISHAP_REQUIRE(!a->weights || a->weights_stride >= 0, "drag batch: negative weights_stride");
   long long o_acc, o_nmask, o_touched, o_chw;
   const long long need = drag_batch_carve(a->E, a->W, a->ld, &o_acc, &o_nmask, &o_touched, &o_chw);
   ISHAP_REQUIRE(a->scratch_bytes >= need, "drag batch: scratch smaller than ishap_drag_batch_scratch_bytes(E, W, ld)");
@@ -331,7 +334,7 @@ int ishap_drag_batch_loss_grad(const ishap_drag_batch_args* a, const void* edit,
   ISHAP_TRY(fill_drag_batch(a, d));
   ISHAP_REQUIRE(edit && orig && grad && loss, "null argument");
   fill_drag_call(d, edit, orig, grad, loss);
-  return drag_batch_loss_launch(d, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  return drag_batch_loss_launch(d, nullptr, nullptr, nullptr, a->weights, a->weights_stride, (hipStream_t)stream);
 }
 
 int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* edit, const void* orig, float* grad,
@@ -340,7 +343,27 @@ int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* 
   ISHAP_TRY(fill_drag_batch(a, d));
   ISHAP_REQUIRE(edit && orig && grad && loss && cot_f16 && bits && scale2, "null argument");
   fill_drag_call(d, edit, orig, grad, loss);
-  return drag_batch_loss_launch(d, (half_t*)cot_f16, bits, scale2, (hipStream_t)stream);
+  return drag_batch_loss_launch(d, (half_t*)cot_f16, bits, scale2, a->weights, a->weights_stride, (hipStream_t)stream);
+}
+
+// ---- region weights of the drag loss's mask term (csrc/regions.hip)
+long long ishap_region_plane_weights_scratch_bytes(int W) { return W > 4096 ? -1 : region_scratch_bytes(W); }
+
+int ishap_region_plane_weights(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels,
+                               const unsigned char* free_voxels, int D, int W, int dilate, float keep_weight, float free_weight,
+                               float* weights_out, int* shadow_counts, void* scratch, long long scratch_bytes, void* stream) {
+  static_assert(sizeof(ishap_region_prim) == sizeof(RegionPrim) && sizeof(RegionPrim) == 56, "ishap_region_prim layout");
+  ISHAP_REQUIRE(W >= 2 && W <= 4096, "region weights: W must be in 2..4096");
+  ISHAP_REQUIRE(n_prims >= 0 && (prims || n_prims == 0), "region weights: null primitives");
+  if (keep_voxels || free_voxels) ISHAP_REQUIRE(D >= W && D <= REGION_MAX_D, "region weights: a voxel grid needs W <= D <= 4096");
+  ISHAP_REQUIRE(dilate >= 0, "region weights: negative dilate");
+  ISHAP_REQUIRE(std::isfinite(keep_weight) && std::isfinite(free_weight) && keep_weight >= 0.f && free_weight >= 0.f,
+                "region weights: keep_weight and free_weight must be finite and >= 0");
+  ISHAP_REQUIRE(weights_out && scratch, "null argument");
+  ISHAP_REQUIRE(scratch_bytes >= region_scratch_bytes(W), "region weights: scratch smaller than ishap_region_plane_weights_scratch_bytes(W)");
+  ISHAP_REQUIRE(((unsigned long long)scratch & 15ull) == 0, "region weights: scratch must be 16-byte aligned");
+  return region_plane_weights_launch((const RegionPrim*)prims, n_prims, keep_voxels, free_voxels, D, W, dilate, keep_weight, free_weight,
+                                     weights_out, shadow_counts, scratch, (hipStream_t)stream);
 }
 
 int ishap_grad_to_scaled_f16(const float* grad, void* out_f16, unsigned* bits, float* scale2, long long numel,

@@ -42,5 +42,7 @@ struct DragBatchArgs {
   float cof[DRAG_MAX_EDITS] = {};
 };
 int drag_batch_setup_launch(DragBatchArgs& a, hipStream_t s);     // touched bitmaps + mask counts + channel weights (once per set of edits)
-// losses + fp32 gradients; with `cot` (then `bits` and `scale2` too) also the fp16 cotangent under one loss scale
-int drag_batch_loss_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float* scale2, hipStream_t s);
+// losses + fp32 gradients; with `cot` (then `bits` and `scale2` too) also the fp16 cotangent under one loss scale; `weights`:
+// the region weight maps [E][3][W][W] of the mask term (edit e at + e * wstride floats), nullptr for the unweighted pass
+int drag_batch_loss_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float* scale2, const float* weights, long long wstride,
+                           hipStream_t s);

@@ -236,7 +236,16 @@ __device__ __forceinline__ void drag_finish(const DragArgs& a) {
 // (drag_utils.py:376-381: cof * mean over the untouched texels of |edit - orig|^2 or |.|), which is elementwise in the tap's
 // own layout once the channel map is inverted (chw) -- it used to be a second 2-million-atomic scatter.  The buffer is
 // left zero for the next call (no memset launch); with `absmax_bits` the pass also finds max|g| for the loss scale.
-__device__ __forceinline__ void drag_gather_body(const DragArgs& a, int blk, int nblk, unsigned* __restrict__ absmax_bits) {
+//
+// WEIGHTED (region-constrained edits, csrc/regions.hip): `wmap` [3][W][W] floats, one weight per plane texel, scales the mask term of
+// an UNTOUCHED texel (0 frees it, > 1 holds it harder); a touched texel's weight is never used.  The per-element weight becomes
+// sum_p untouched_p ? wmap_p * chw_p[k] : 0 in float.  With a map of exact ones that sum is the same small integer the unweighted
+// form converts from int, and every operation behind it has the same shape: the results are bitwise those of WEIGHTED = false,
+// which is what keeps "each edit's loss is bitwise its solo loss" for a batch that mixes edits with and without regions.
+// The unweighted instantiation is the code it was before the parameter existed.
+template <bool WEIGHTED>
+__device__ __forceinline__ void drag_gather_body(const DragArgs& a, int blk, int nblk, unsigned* __restrict__ absmax_bits,
+                                                 const float* __restrict__ wmap) {
   typedef long long ll2 __attribute__((ext_vector_type(2)));
   typedef unsigned char uc8 __attribute__((ext_vector_type(8)));
   const long long n = (long long)a.W * a.W * a.ld;
@@ -255,6 +264,10 @@ __device__ __forceinline__ void drag_gather_body(const DragArgs& a, int blk, int
     uc8 cw[3];
 #pragma unroll
     for (int p = 0; p < 3; ++p) cw[p] = *reinterpret_cast<const uc8*>(a.chw + p * a.ld + ch);
+    // the texel's three region weights ride with the loads above, unconditionally (a load in a conditional block of its own is
+    // closed by a full wait); an unweighted instantiation has no such loads
+    float rw[3] = {1.f, 1.f, 1.f};
+    if constexpr (WEIGHTED) { rw[0] = wmap[tex]; rw[1] = wmap[WW + tex]; rw[2] = wmap[2 * WW + tex]; }
     if ((t0 | t1 | t2) & 2) {                       // a target footprint covers this texel on some plane
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -266,16 +279,30 @@ __device__ __forceinline__ void drag_gather_body(const DragArgs& a, int blk, int
     }
     if (mask) {
       const unsigned char tp[3] = {t0, t1, t2};
-      int w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      float wf[8];
+      if constexpr (WEIGHTED) {
 #pragma unroll
-      for (int p = 0; p < 3; ++p)
-        if (!(tp[p] & 1)) {
+        for (int k = 0; k < 8; ++k) wf[k] = 0.f;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) w[k] += cw[p][k];
+        for (int p = 0; p < 3; ++p) {
+          const float wp = (tp[p] & 1) ? 0.f : rw[p];       // a select, not a branch: touched -> weight ignored
+#pragma unroll
+          for (int k = 0; k < 8; ++k) wf[k] += wp * (float)cw[p][k];
         }
+      } else {
+        int w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+          if (!(tp[p] & 1)) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) w[k] += cw[p][k];
+          }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wf[k] = (float)w[k];
+      }
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const float d = (float)e8[k] - (float)o8[k], wk = (float)w[k];
+        const float d = (float)e8[k] - (float)o8[k], wk = wf[k];
         if (a.l1) { lsum += wk * fabsf(d); g[k] += wk * (-a.cof * (float)((d > 0.f) - (d < 0.f)) / denom); }
         else { lsum += wk * d * d; g[k] += wk * (-a.cof * 2.f * d / denom); }
       }
@@ -393,7 +420,16 @@ __global__ __launch_bounds__(256) void drag_batch_terms_kernel(DragBatchArgs b, 
 }
 __global__ __launch_bounds__(256) void drag_batch_gather_kernel(DragBatchArgs b, int blocks_per_edit, unsigned* __restrict__ absmax_bits) {
   const int e = blockIdx.x / blocks_per_edit;
-  drag_gather_body(drag_edit_args(b, e), blockIdx.x - e * blocks_per_edit, blocks_per_edit, absmax_bits);
+  drag_gather_body<false>(drag_edit_args(b, e), blockIdx.x - e * blocks_per_edit, blocks_per_edit, absmax_bits, nullptr);
+}
+// The weighted form, launched only when the batch carries weight maps: edit e reads weights + e * wstride.  The maps are the
+// kernel's own trailing parameters and not fields of DragArgs / DragBatchArgs, so the kernel-argument layout of every other drag
+// kernel -- and with it their code -- is what it was (README round 6: an argument-struct change once cost 3 % per edit).
+__global__ __launch_bounds__(256) void drag_batch_gather_weighted_kernel(DragBatchArgs b, int blocks_per_edit,
+                                                                         unsigned* __restrict__ absmax_bits,
+                                                                         const float* __restrict__ weights, long long wstride) {
+  const int e = blockIdx.x / blocks_per_edit;
+  drag_gather_body<true>(drag_edit_args(b, e), blockIdx.x - e * blocks_per_edit, blocks_per_edit, absmax_bits, weights + e * wstride);
 }
 __global__ void drag_batch_finish_kernel(DragBatchArgs b) {
   for (int e = 0; e < b.E; ++e) drag_finish(drag_edit_args(b, e));
@@ -447,10 +483,14 @@ static unsigned gather_blocks(long long n) {
 }
 
 // Losses + fp32 gradients of the E edits in three launches (motion scatter, gather + mask, finish); with `cot` the third launch
-// also writes the scaled fp16 cotangent (drag_batch_scale_kernel) and `bits` / `scale2` must be given.  Requires
+// also writes the scaled fp16 cotangent (drag_batch_scale_kernel) and `bits` / `scale2` must be given.  `weights` (device
+// [E][3][W][W] floats, edit e at + e * wstride; nullptr: none) selects the weighted gather pass.  Requires
 // drag_batch_setup_launch on these buffers first.
-int drag_batch_loss_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float* scale2, hipStream_t s) {
+int drag_batch_loss_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float* scale2, const float* weights, long long wstride,
+                           hipStream_t s) {
   ISHAP_TRY(drag_batch_check(a));
+  ISHAP_REQUIRE(!weights || a.E == 1 || wstride == 0 || wstride >= 3ll * a.base.W * a.base.W,
+                "drag: weights_stride must be 0 (one map for all edits) or at least 3*W*W");
   if (!cot) bits = nullptr;
   // every workgroup of the terms and gather passes ends with same-address atomics (loss sum, max|g|) that serialise at ~10 ns
   // each: few, fat workgroups (the loops are grid-stride).  Terms: a wave per DSEG positions of a lattice row, at most `cap`
@@ -466,7 +506,10 @@ int drag_batch_loss_launch(DragBatchArgs& a, half_t* cot, unsigned* bits, float*
   hipLaunchKernelGGL(drag_batch_terms_kernel, dim3(a.tblk[a.E]), dim3(256), 0, s, a, bits);
   const long long n = (long long)a.base.W * a.base.W * a.base.ld;
   const unsigned gb = gather_blocks(n);
-  hipLaunchKernelGGL(drag_batch_gather_kernel, dim3(gb * a.E), dim3(256), 0, s, a, (int)gb, bits);
+  if (weights)
+    hipLaunchKernelGGL(drag_batch_gather_weighted_kernel, dim3(gb * a.E), dim3(256), 0, s, a, (int)gb, bits, weights, wstride);
+  else
+    hipLaunchKernelGGL(drag_batch_gather_kernel, dim3(gb * a.E), dim3(256), 0, s, a, (int)gb, bits);
   if (cot) {
     const long long nt = n * a.E;
     hipLaunchKernelGGL(drag_batch_scale_kernel, dim3((unsigned)std::min<long long>((nt / 4 + 255) / 256, 1024)), dim3(256), 0, s,

@@ -117,6 +117,27 @@ class _DragKernelsBase:
         with th.cuda.device(self.device):
             _lib.check(fn(*args, _lib.stream_ptr(self.device)))
 
+    def _weight_map(self, w):
+        """A region weight map (regions.plane_weights) as the kernels read it: float32 [3, W, W] on the device."""
+        return check_weight_map(w, self.W).to(device=self.device).contiguous()
+
+
+def check_weight_map(w, W: int) -> th.Tensor:
+    """A [3, W, W] map of finite weights >= 0 (tensor or array) -> a float32 tensor; ValueError otherwise."""
+    w = w.detach() if th.is_tensor(w) else th.as_tensor(np.asarray(w))
+    if tuple(w.shape) != (3, W, W):
+        raise ValueError(f"weights must be a [3, {W}, {W}] map (one [row, col] slice per plane), got {tuple(w.shape)}")
+    w = w.to(th.float32)
+    if not bool(th.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("weights must be finite and >= 0")
+    return w
+
+
+def check_region_cof(cof: float, has_regions: bool, what: str = "cof"):
+    """Regions act on the preservation term only, and with cof <= 0 there is none."""
+    if has_regions and not cof > 0:
+        raise ValueError(f"{what} = {cof}: keep / free regions and weights scale the preservation term, which needs cof > 0")
+
 
 class DragKernels(_DragKernelsBase):
     """Device state + calls for the drag loss (drag_utils.py:309-334 setup, :355-383 per step)."""
@@ -132,14 +153,20 @@ class DragKernels(_DragKernelsBase):
         self.loss = th.zeros(1, dtype=th.float32, device=self.device)
         self.cot = th.empty((W * W, ld), dtype=th.float16, device=self.device)
         self.cof = 0.0
+        self.weights = None
 
     def _args(self) -> _lib.DragArgsC:
         return _lib.DragArgsC(self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
                               self.targets.data_ptr(), self.sources.shape[0], self.r, self.voxel, float(self.cof),
                               self.l1, self.touched.data_ptr(), self.nmask.data_ptr(), self.acc.data_ptr(), self.gfx.data_ptr(),
-                              self.chan_weight.data_ptr())
+                              self.chan_weight.data_ptr(), _lib.ptr(self.weights))
 
-    def setup(self, sources, targets, cof: float):
+    def setup(self, sources, targets, cof: float, weights=None):
+        """weights: None, or a [3, W, W] map of the preservation term's per-texel weights (regions.plane_weights); needs cof > 0.
+        A map selects the weighted gather kernel; a map of ones gives bitwise the results of None."""
+        check_region_cof(float(cof), weights is not None)
+        self.weights = None if weights is None else self._weight_map(weights)
+
         def pts(v):
             v = v.detach() if th.is_tensor(v) else th.as_tensor(np.asarray(v))
             return v.to(device=self.device, dtype=th.float32).reshape(-1, 3).contiguous()
@@ -211,6 +238,25 @@ def per_edit(value, K: int, name: str) -> List[float]:
     return vals
 
 
+def per_edit_any(value, K: int, name: str) -> list:
+    """One value (every edit) or a list / tuple of K values -> K values."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != K:
+            raise ValueError(f"{name}: {len(value)} values for {K} edits (give one value or one per edit)")
+        return list(value)
+    return [value] * K
+
+
+def per_edit_region(value, K: int, name: str) -> list:
+    """keep / free / weights of training_batch -> K entries.  None or a single region / map: every edit gets it; a list of K
+    entries (each None, a region, a list of regions, or a map): one per edit."""
+    if value is None or not isinstance(value, (list, tuple)):
+        return [value] * K
+    if len(value) != K:
+        raise ValueError(f"{name}: {len(value)} entries for {K} edits (give one value or a list with one entry, or None, per edit)")
+    return list(value)
+
+
 class BatchDragKernels(_DragKernelsBase):
     """Device state + calls of the drag loss for E edits at once (ishap_drag_batch_*): one scratch buffer, one loss scale."""
 
@@ -224,23 +270,39 @@ class BatchDragKernels(_DragKernelsBase):
         self.grad = th.empty((self.E, W * W, ld), dtype=th.float32, device=self.device)
         self.loss = th.zeros(self.E, dtype=th.float32, device=self.device)
         self.cot = th.empty((self.E, W * W, ld), dtype=th.float16, device=self.device)
+        self.weights = None
 
-    def setup(self, sources, targets, cof):
-        """sources / targets: lists of E handle arrays; cof: a float or E floats."""
+    def setup(self, sources, targets, cof, weights=None):
+        """sources / targets: lists of E handle arrays; cof: a float or E floats; weights: None, or a list of E entries, each None
+        or a [3, W, W] map (regions.plane_weights) for an edit with cof > 0.  All None selects the unweighted launch; otherwise
+        an edit without a map reads a map of ones, which gives bitwise its unweighted result."""
         src, tgt, offs = pack_handles(sources, targets)
         if len(offs) - 1 != self.E:
             raise ValueError(f"{len(offs) - 1} edits given to drag kernels set up for {self.E}")
+        cofs = per_edit(cof, self.E, "cof")
+        self.weights = None
+        if weights is not None:
+            weights = list(weights)
+            if len(weights) != self.E:
+                raise ValueError(f"weights: {len(weights)} entries for {self.E} edits (give one map or None per edit)")
+            for e, w in enumerate(weights):
+                check_region_cof(cofs[e], w is not None, f"cof[{e}]")
+            if any(w is not None for w in weights):
+                self.weights = th.ones((self.E, 3, self.W, self.W), dtype=th.float32, device=self.device)
+                for e, w in enumerate(weights):
+                    if w is not None:
+                        self.weights[e].copy_(self._weight_map(w))
         self.sources, self.targets = src.to(self.device), tgt.to(self.device)
         self.offsets = list(offs)
         self._offs = (C.c_int * (self.E + 1))(*offs)
-        self.cof = per_edit(cof, self.E, "cof")
+        self.cof = cofs
         self._cof = (C.c_float * self.E)(*self.cof)
         self._call(self._L.ishap_drag_batch_setup, C.byref(self._args(0)))
 
     def _args(self, orig_stride: int) -> _lib.DragBatchArgsC:
         return _lib.DragBatchArgsC(self.E, self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
                                    self.targets.data_ptr(), self._offs, self.r, self.voxel, self._cof, self.l1, int(orig_stride),
-                                   self.scratch.data_ptr(), self.scratch.numel())
+                                   self.scratch.data_ptr(), self.scratch.numel(), _lib.ptr(self.weights), 3 * self.W * self.W)
 
     def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int):
         """edit: [E][W*W][ld] fp16; orig: edit e's guidance at orig + e * orig_stride halfs (0: one guidance for all edits)."""
@@ -558,21 +620,45 @@ class DragStuff:
             yield 1 - i / (w_time - 1.)
         return img, stop_time
 
-    def training(self, sources=None, targets=None, scale=600, cof=0.2):
+    def _region_weights(self, width, cof, keep, free, keep_weight, free_weight, region_dilate, weights, what="cof"):
+        """The weight map of one edit's preservation term, or None: `weights` (a ready [3, W, W] map) or the map of the keep /
+        free regions (regions.plane_weights at the tap's width).  Everything is validated before anything is launched."""
+        from . import regions
+        if weights is not None and (keep is not None or free is not None):
+            raise ValueError("weights is a ready map: give it or keep / free regions, not both")
+        has = weights is not None or keep is not None or free is not None
+        check_region_cof(float(cof), has, what)
+        if weights is not None:
+            return check_weight_map(weights, width)
+        if not has:
+            return None
+        return regions.plane_weights(keep=keep, free=free, W=width, keep_weight=keep_weight, free_weight=free_weight,
+                                     dilate=region_dilate, device=self.device)
+
+    def training(self, sources=None, targets=None, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
+                 region_dilate=0, weights=None):
         """One drag edit of the loaded shape (drag_utils.py:302-399).  Every edit starts from self.w: from the second edit of a
         shape on, the first guided step's forward is restored from a snapshot instead of run (ISHAP_FIRST_STEP_REUSE=0: always
-        run); results are bit-identical either way."""
+        run); results are bit-identical either way.
+        keep / free: 3-D regions (regions.Box / Sphere / Voxels or lists of them, in the handles' coordinates) whose shadows on
+        the three planes get keep_weight (default 4: held harder) / free_weight (default 0: free to change) in the preservation
+        term instead of 1, each shadow grown by region_dilate texels; keep overrides free.  weights: a ready [3, W, W] map
+        instead (W the side of the tap), exclusive with keep and free.  All of them need cof > 0.  A plane texel stands for a
+        whole column through the shape, so a region constrains its three shadows, not only its own volume."""
         if self.args.num_samples > 1:
             raise NotImplementedError("We can handle only one shape at each time!")
+        ch, width = self.model.tap_shape(self.args.feat_layer)
+        wmap = self._region_weights(width, cof, keep, free, keep_weight, free_weight, region_dilate, weights)
         self.sources = th.tensor(np.asarray(sources), device=self.device, dtype=th.float32)
         self.targets = th.tensor(np.asarray(targets), device=self.device, dtype=th.float32)
         assert self.sources.shape[0] == self.targets.shape[0]
         img = self.w.clone().detach()
-        ch, width = self.model.tap_shape(self.args.feat_layer)
         dk = DragKernels(self.device, W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size,
                          loss_type=self.args.loss_type)
-        dk.setup(self.sources, self.targets, cof)
+        dk.setup(self.sources, self.targets, cof, **({} if wmap is None else {"weights": wmap}))    # a plain edit: the call it always was
         self._dk = dk
+        # the regions change the loss, not the forward: the first-step snapshot depends on the latent, the timestep and the weights
+        # of the model only, so _first_step_key does not hold them and an edit with regions reuses the snapshot of a plain one
         img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), True)
         self.mesh = self.get_mesh(img=img, t=stop_time)
 
@@ -618,9 +704,13 @@ class DragStuff:
             self.volumes.append(self.volume)
         return self.meshes
 
-    def training_batch(self, sources, targets, scale=600, cof=0.2):
+    def training_batch(self, sources, targets, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
+                       region_dilate=0, weights=None):
         """K drag edits in one guided loop (the generator of training(), same progress values).  sources / targets: lists of K
-        handle arrays (their counts may differ); scale, cof: a float or K values.  After update_latent_params_batch edit k
+        handle arrays (their counts may differ); scale, cof: a float or K values.  keep, free, keep_weight, free_weight,
+        region_dilate, weights: as training(), one value for every edit or a list of K (entries of keep / free / weights may be
+        None: that edit has no such region and, if none at all, the bits of its plain batched edit; a region that is itself a
+        list goes inside the list of K).  After update_latent_params_batch edit k
         drags shape k; otherwise the K edits are variants of the single shape of update_latent_params (its w and guidance
         features, shared).  train_flag stops all edits at one stop_time; each then finishes its remaining steps unguided.
         Afterwards: meshes / volumes (K of each) and last_losses (one [K] tensor per step).  Every edit's drag loss and gradient
@@ -635,6 +725,11 @@ class DragStuff:
         scales = per_edit(scale, K, "scale")
         cofs = per_edit(cof, K, "cof")
         ch, width = self.model.tap_shape(self.args.feat_layer)
+        keeps, frees, maps = (per_edit_region(v, K, n) for v, n in ((keep, "keep"), (free, "free"), (weights, "weights")))
+        kws, fws = per_edit(keep_weight, K, "keep_weight"), per_edit(free_weight, K, "free_weight")
+        dils = per_edit_any(region_dilate, K, "region_dilate")
+        wmaps = [self._region_weights(width, cofs[k], keeps[k], frees[k], kws[k], fws[k], dils[k], maps[k], f"cof[{k}]")
+                 for k in range(K)]
         if self.w_batch is not None:
             if self.w_batch.shape[0] != K:
                 raise ValueError(f"{K} edits for the {self.w_batch.shape[0]} shapes of update_latent_params_batch")
@@ -647,7 +742,7 @@ class DragStuff:
             guidance, stride = self.feature_guidance, 0
         dk = BatchDragKernels(self.device, K, W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size,
                               loss_type=self.args.loss_type)
-        dk.setup(sources, targets, cofs)
+        dk.setup(sources, targets, cofs, **({} if all(w is None for w in wmaps) else {"weights": wmaps}))
         self._dk_batch = dk
         scales_dev = th.tensor(scales, dtype=th.float32, device=self.device)
         img, stop_time = yield from self._guided_loop(img, dk, guidance, stride, scales, scales_dev)

@@ -239,9 +239,41 @@ def marker_arrow(start, end, segments: int = 20):
     return verts.astype(np.float32), np.asarray(tris, np.int32)
 
 
-def edit_parts(mesh, sources, targets, mesh_colour=MESH_COLOUR):
+_PRISM_TRIS = np.array([[0, 2, 1], [0, 3, 2], [4, 5, 6], [4, 6, 7], [0, 1, 5], [0, 5, 4], [1, 2, 6], [1, 6, 5], [2, 3, 7], [2, 7, 6],
+                        [3, 0, 4], [3, 4, 7]], np.int32)
+
+
+def marker_box(lo, hi, thickness: float = 0.012):
+    """The wire frame of the axis-aligned box lo..hi (a keep / free region of an edit): its twelve edges as thin square prisms
+    of side `thickness`, each a closed mesh of 8 vertices and 12 triangles that overlaps its neighbours at the corners.
+    (vertices [96,3] float32, triangles [144,3] int32)."""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+        raise ValueError(f"marker_box: need finite lo <= hi, got {lo.tolist()} and {hi.tolist()}")
+    h = 0.5 * float(thickness)
+    verts, tris = [], []
+    for axis in range(3):                                   # the four edges along each axis
+        o1, o2 = (axis + 1) % 3, (axis + 2) % 3
+        for c1 in (lo[o1], hi[o1]):
+            for c2 in (lo[o2], hi[o2]):
+                a, b = np.empty(3), np.empty(3)
+                a[axis], b[axis] = lo[axis] - h, hi[axis] + h
+                a[o1], b[o1], a[o2], b[o2] = c1 - h, c1 + h, c2 - h, c2 + h
+                x0, y0, z0, x1, y1, z1 = *a, *b
+                tris.append(_PRISM_TRIS + len(verts) * 8)
+                verts.append(np.array([[x0, y0, z0], [x1, y0, z0], [x1, y1, z0], [x0, y1, z0],
+                                       [x0, y0, z1], [x1, y0, z1], [x1, y1, z1], [x0, y1, z1]]))
+    return np.concatenate(verts).astype(np.float32), np.concatenate(tris).astype(np.int32)
+
+
+KEEP_COLOUR = (1.0, 0.7, 0.0)        # amber: the frame of a keep region
+FREE_COLOUR = (0.0, 0.7, 0.7)        # teal: the frame of a free region
+
+
+def edit_parts(mesh, sources, targets, mesh_colour=MESH_COLOUR, boxes=()):
     """The scene of an edit as render_mesh parts: the mesh (lit), a red sphere at every source and a blue one at every
-    target (unlit, main.py:513-516, 543-545), a green arrow from each source to its target (lit, main.py:517, 587)."""
+    target (unlit, main.py:513-516, 543-545), a green arrow from each source to its target (lit, main.py:517, 587).
+    boxes: region frames to draw, each a marker_box mesh or a (marker_box mesh, colour) pair (default colour KEEP_COLOUR)."""
     src = np.asarray(sources, np.float64).reshape(-1, 3)
     tgt = np.asarray(targets, np.float64).reshape(-1, 3)
     if src.shape != tgt.shape:
@@ -250,6 +282,9 @@ def edit_parts(mesh, sources, targets, mesh_colour=MESH_COLOUR):
     parts += [(marker_sphere(p), RED, False) for p in src]
     parts += [(marker_sphere(p), BLUE, False) for p in tgt]
     parts += [(marker_arrow(s, e), GREEN, True) for s, e in zip(src, tgt) if np.linalg.norm(e - s) > 0]
+    for b in boxes:
+        frame, colour = b if isinstance(b[1], tuple) and len(b[1]) == 3 and not hasattr(b[1], "shape") else (b, KEEP_COLOUR)
+        parts.append((frame, colour, False))
     return parts
 
 

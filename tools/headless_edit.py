@@ -10,6 +10,12 @@ spheres and green arrows.  With synthetic weights the decoded shape is noise; th
 
 --clean largest keeps only the largest connected component of every decoded volume (DragStuff.clean, volume.clean_volume).
 
+Regions (repeatable): --keep-box x0 y0 z0 x1 y1 z1, --keep-sphere cx cy cz r hold a part of the shape, --free-box / --free-sphere
+release one (ishapediting_amd.regions; --keep-weight, --free-weight, --region-dilate as DragStuff.training).  The boxes are drawn
+into both pictures as wire frames (amber keep, teal free).  With regions the edit runs twice, without and with them, and the tool
+prints for every region the fraction of the voxels inside it whose occupancy sign changed in each run: a report, not a check --
+on synthetic weights the direction is not guaranteed.
+
 --time instead measures the renderer alone (device events around `--repeat` calls after a warm-up, medians):
   the 256^3 sphere mesh (~300 k triangles of a few pixels each) at 1024 x 1024, and 2 picture-filling triangles at 1024 x 1024
   (the second shows that large triangles do not serialise on one lane), next to the bytes each call has to move
@@ -44,6 +50,32 @@ def pick_sources(mesh, camera, depth, k, seed):
     return out
 
 
+def regions_of(a):
+    """the command line's regions -> (keep list, free list, frames for edit_parts, [(name, inside(x, y, z) -> bool array)])"""
+    from ishapediting_amd.regions import Box, Sphere
+    from ishapediting_amd.render import FREE_COLOUR, KEEP_COLOUR, marker_box
+    keep, free, frames, named = [], [], [], []
+    for role, dst, colour, boxes, spheres in (("keep", keep, KEEP_COLOUR, a.keep_box, a.keep_sphere),
+                                              ("free", free, FREE_COLOUR, a.free_box, a.free_sphere)):
+        for b in boxes or []:
+            lo, hi = np.asarray(b[:3], np.float64), np.asarray(b[3:], np.float64)
+            dst.append(Box(lo, hi))
+            frames.append((marker_box(lo, hi), colour))
+            named.append((f"{role}-box {b}", lambda x, y, z, lo=lo, hi=hi: (x >= lo[0]) & (x <= hi[0]) & (y >= lo[1]) & (y <= hi[1])
+                          & (z >= lo[2]) & (z <= hi[2])))
+        for sp in spheres or []:
+            c, r = np.asarray(sp[:3], np.float64), float(sp[3])
+            dst.append(Sphere(c, r))
+            named.append((f"{role}-sphere {sp}", lambda x, y, z, c=c, r=r: (x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2 <= r * r))
+    return keep, free, frames, named
+
+
+def changed_fraction(before, after, inside):
+    """share of the voxels selected by `inside` (a bool grid) whose occupancy sign differs between two decoded volumes"""
+    n = int(inside.sum())
+    return float(((before > 0) != (after > 0))[inside].float().mean()) if n else float("nan")
+
+
 def edit(a):
     from ishapediting_amd import synthetic
     from ishapediting_amd.drag_utils import DragStuff, get_args
@@ -69,12 +101,28 @@ def edit(a):
     targets = sources + np.asarray(a.offset, np.float32)
     for pos, idx, d, px in picked:
         print(f"pick pixel {px}: vertex {idx} at {pos.tolist()}, depth {d:.6f}")
-    save_picture(os.path.join(a.out, "before.png"), render_mesh(edit_parts(before, sources, targets), cam, a.size, a.size))
-    for _ in ds.training(sources, targets, scale=a.scale, cof=a.cof):
+    keep, free, frames, named = regions_of(a)
+    volume0 = ds.volume.clone()
+    save_picture(os.path.join(a.out, "before.png"), render_mesh(edit_parts(before, sources, targets, boxes=frames), cam, a.size, a.size))
+    report = {}
+    if named:                # the same edit without the regions first: what they change is the difference of the two runs
+        for _ in ds.training(sources, targets, scale=a.scale, cof=a.cof):
+            pass
+        plain = ds.volume.clone()
+    for _ in ds.training(sources, targets, scale=a.scale, cof=a.cof, keep=keep or None, free=free or None,
+                         keep_weight=a.keep_weight, free_weight=a.free_weight, region_dilate=a.region_dilate):
         pass
-    save_picture(os.path.join(a.out, "after.png"), render_mesh(edit_parts(ds.mesh, sources, targets), cam, a.size, a.size))
+    if named:
+        ax = torch.linspace(-1, 1, a.res, device=dev, dtype=torch.float64)
+        x, y, z = torch.meshgrid(ax, ax, ax, indexing="ij")
+        for name, inside in named:
+            m = inside(x, y, z)
+            report[name] = {"voxels": int(m.sum()), "changed_without_regions": changed_fraction(volume0, plain, m),
+                            "changed_with_regions": changed_fraction(volume0, ds.volume, m)}
+            print(f"{name}: {report[name]}")
+    save_picture(os.path.join(a.out, "after.png"), render_mesh(edit_parts(ds.mesh, sources, targets, boxes=frames), cam, a.size, a.size))
     torch.cuda.synchronize()
-    print(json.dumps({"out": a.out, "handles": a.handles, "before_triangles": int(before.triangles.shape[0]),
+    print(json.dumps({"out": a.out, "handles": a.handles, "regions": report, "before_triangles": int(before.triangles.shape[0]),
                       "after_triangles": int(ds.mesh.triangles.shape[0]), "camera": {"eye": list(cam.eye), "near": cam.near, "far": cam.far}}))
 
 
@@ -140,6 +188,14 @@ def main():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--clean", default=None, metavar="largest|K",
                    help="keep only the largest (or the K largest) connected components of each decoded volume")
+    for role in ("keep", "free"):
+        p.add_argument(f"--{role}-box", type=float, nargs=6, action="append", metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                       help=f"a {role} region: the box x0 y0 z0 x1 y1 z1 in [-1, 1]^3 (repeatable)")
+        p.add_argument(f"--{role}-sphere", type=float, nargs=4, action="append", metavar=("CX", "CY", "CZ", "R"),
+                       help=f"a {role} region: the sphere cx cy cz r (repeatable)")
+    p.add_argument("--keep-weight", type=float, default=4.0)
+    p.add_argument("--free-weight", type=float, default=0.0)
+    p.add_argument("--region-dilate", type=int, default=0)
     p.add_argument("--time", action="store_true", help="measure the renderer instead of running an edit")
     p.add_argument("--time_out", default=None, help="where --time writes its JSON (default profiles/render_times.json)")
     p.add_argument("--warmup", type=int, default=10)
