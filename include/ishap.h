@@ -52,7 +52,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * (ishap_unet_snapshot_save / _restore / _drop / _bytes); 16 since the connected components of a
                             * volume (ishap_volume_label, ishap_volume_components_*, ishap_volume_flip); 17 since the region
                             * weights of the drag loss (the trailing `weights` of ishap_drag_args, `weights` / `weights_stride` of
-                            * ishap_drag_batch_args, ishap_region_plane_weights, ishap_region_plane_weights_scratch_bytes) */
+                            * ishap_drag_batch_args, ishap_region_plane_weights, ishap_region_plane_weights_scratch_bytes);
+                            * 18 since the decoder's field in space (ishap_triplane_field_grad, ishap_triplane_project) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -440,6 +441,24 @@ int ishap_triplane_decode_points(const float* planes, int S, const ishap_decoder
  * volume[res][res][res] with x slowest, no host round trips */
 int ishap_triplane_decode_grid(const float* planes, int S, const ishap_decoder_weights* w, const float* axis, int res,
                                float* volume, void* stream);
+
+/* The field in space, extending MultiTriplane.forward (axisnetworks.py:537-562): logits [npts] and grad [npts][3] =
+ * d logit / d coordinate at coords [npts][3].  Analytic (bilinear slopes, the sin / cos features, the two ReLU layers); on a
+ * cell boundary of a plane floor() decides the cell, so the derivative is the right-sided one.  Points outside every plane
+ * have gradient exactly 0.  Requires S >= 2, npts >= 1.  No atomics: bitwise repeatable. */
+int ishap_triplane_field_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* coords,
+                              long long npts, float* logits, float* grad, void* stream);
+/* Project coords [npts][3] onto the zero level set of the same field (axisnetworks.py:537-562).  Per point x = x0,
+ * (z, g) = field(x), scale = 1; `iterations` (0..64) times: stop updating once |z| <= tol or |g|^2 < gmin, else try
+ * d = -scale z g / max(|g|^2, gmin) with |d| clipped to step_max and x + d clipped into the ball of radius max_move around
+ * x0; take the trial (and reset scale to 1) if it lowers |z|, else halve scale.  So |z_out| <= |z at x0| exactly, and
+ * |x_out - x0| <= max_move (1 + 4 * 2^-24) for every point (the ball is tested on the rounded fp32 positions).  x_out [npts][3], z_out [npts] (the logit at x_out), normal_out [npts][3] =
+ * -g / |g| at x_out: the direction of DECREASING logit, which points outward because logits are positive inside; exactly 0
+ * where |g|^2 < gmin.  accepted_out [npts] int32: steps taken.  iterations = 0: logit and normal at the given points.
+ * step_max > 0, gmin > 0, max_move >= 0, tol >= 0 (coordinate units).  Bitwise repeatable. */
+int ishap_triplane_project(const float* planes, int S, const ishap_decoder_weights* w, const float* coords, long long npts,
+                           int iterations, float step_max, float max_move, float tol, float gmin, float* x_out,
+                           float* z_out, float* normal_out, int* accepted_out, void* stream);
 
 /* real-shape guidance (drag_utils.py:447-463): prediction = decoder(0, coord); loss = -BCEWithLogitsLoss()(prediction, gt);
  * loss.backward() -- forward and backward of the decoder on sampled points.  W1T / W2T: transposed copies of

@@ -164,6 +164,11 @@ SYMBOLS = {
     "ishap_triplane_reg_values": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, c_void_p]),
     "ishap_triplane_decode_points": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_longlong,
                                                c_void_p, c_void_p]),
+    "ishap_triplane_field_grad": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_longlong, c_void_p,
+                                            c_void_p, c_void_p]),
+    "ishap_triplane_project": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_longlong, C.c_int,
+                                         C.c_float, C.c_float, C.c_float, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     "ishap_surface_scratch_bytes": (C.c_longlong, [C.c_int]),
     "ishap_surface_count": (C.c_int, [c_void_p, C.c_int, C.c_float, C.c_int, c_void_p, c_void_p, c_void_p]),
     "ishap_surface_emit": (C.c_int, [c_void_p, C.c_int, C.c_float, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -247,9 +252,10 @@ def lib():
         # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance; 13: ishap_group_norm32_run;
         # 14: ishap_cloud_knn / ishap_cloud_normals / ishap_cloud_orient / ishap_cloud_orient_scratch_bytes;
         # 15: ishap_unet_snapshot_*; 16: ishap_volume_label / ishap_volume_components_* / ishap_volume_flip;
-        # 17: the weights fields of DragArgsC / DragBatchArgsC, ishap_region_plane_weights
-        if l.ishap_version() < 17:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 17): rebuild with `python -m ishapediting_amd.build`")
+        # 17: the weights fields of DragArgsC / DragBatchArgsC, ishap_region_plane_weights;
+        # 18: ishap_triplane_field_grad / ishap_triplane_project
+        if l.ishap_version() < 18:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 18): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -421,6 +421,33 @@ int ishap_triplane_fit_loss_grad(const float* planes, int S, const ishap_decoder
   return triplane_fit_loss_grad_launch(f, (hipStream_t)stream);
 }
 
+static void fill_field(const DecodeArgs& d, FieldArgs& f) {
+  f.B = d.B; f.W1 = d.W1; f.b1 = d.b1; f.W2 = d.W2; f.b2 = d.b2; f.w3 = d.w3; f.b3 = d.b3;
+}
+
+int ishap_triplane_field_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* coords,
+                              long long npts, float* logits, float* grad, void* stream) {
+  DecodeArgs d;
+  ISHAP_TRY(fill_dec(w, d));
+  FieldArgs f;
+  fill_field(d, f);
+  f.planes = planes; f.S = S; f.coords = coords; f.npts = npts; f.logits = logits; f.grad = grad;
+  return triplane_field_grad_launch(f, (hipStream_t)stream);
+}
+
+int ishap_triplane_project(const float* planes, int S, const ishap_decoder_weights* w, const float* coords, long long npts,
+                           int iterations, float step_max, float max_move, float tol, float gmin, float* x_out,
+                           float* z_out, float* normal_out, int* accepted_out, void* stream) {
+  DecodeArgs d;
+  ISHAP_TRY(fill_dec(w, d));
+  FieldArgs f;
+  fill_field(d, f);
+  f.planes = planes; f.S = S; f.coords = coords; f.npts = npts; f.logits = z_out; f.iterations = iterations;
+  f.step_max = step_max; f.max_move = max_move; f.tol = tol; f.gmin = gmin; f.x_out = x_out; f.normal_out = normal_out;
+  f.accepted_out = accepted_out;
+  return triplane_project_launch(f, (hipStream_t)stream);
+}
+
 int ishap_triplane_reg_adam_step(const float* planes, float* planes_out, float* m, float* v, float* dplanes, int S, int* step,
                                  double lr, double beta1, double beta2, double eps, float l2_w, float tv_w, double* ws,
                                  float* reg_parts, void* stream) {

@@ -92,3 +92,23 @@ struct RegAdamArgs {
   float l2_w = 0.f, tv_w = 0.f;
 };
 int triplane_reg_adam_launch(const RegAdamArgs& a, hipStream_t s);
+
+// The decoder's field in space (extends axisnetworks.py:537-562), csrc/decode_field.hip: logit and d logit / d coordinate at
+// points, and the projection of points onto the zero level set.
+struct FieldArgs {
+  const float* planes = nullptr;   // [3][S][S][32] un-normalised, channels-last
+  int S = 0;
+  const float *B = nullptr, *W1 = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
+  const float* coords = nullptr;   // [npts][3]
+  long long npts = 0;
+  float* logits = nullptr;         // [npts] (project: the logit at x_out)
+  float* grad = nullptr;           // [npts][3] d logit / d coordinate (field_grad only)
+  // projection only
+  int iterations = 0;
+  float step_max = 0.f, max_move = 0.f, tol = 0.f, gmin = 0.f;
+  float* x_out = nullptr;          // [npts][3]
+  float* normal_out = nullptr;     // [npts][3] -g / |g| (outward), 0 where |g|^2 < gmin
+  int* accepted_out = nullptr;     // [npts] accepted steps
+};
+int triplane_field_grad_launch(const FieldArgs& a, hipStream_t s);
+int triplane_project_launch(const FieldArgs& a, hipStream_t s);

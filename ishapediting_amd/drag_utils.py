@@ -24,7 +24,7 @@ import torch as th
 
 from . import _lib
 from .script_util import args_to_dict, create_model_and_diffusion, model_and_diffusion_defaults
-from .triplane_decoder import MultiTriplane, decode_volume
+from .triplane_decoder import MultiTriplane, decode_planes_grid, decode_volume, prepare_planes
 from . import mesh as mesh_backend
 from .volume import clean_volume
 
@@ -439,6 +439,8 @@ class DragStuff:
         self.mesh0 = None
         self.volume = None            # last decoded occupancy-logit volume [res]^3 on the device
         self.clean = None             # None, or volume.clean_volume keywords (e.g. {"keep": "largest"}): get_mesh cleans the volume
+        self.refine = None            # None, or {"iterations": n, "max_move": decoder units}: get_mesh puts the smoothed vertices back
+                                      # on the decoder's zero level set and keeps its analytic normals (mesh.OccupancyMesh refine)
         self.noise = []
         self.variance = []
         self.variance_noise = []
@@ -542,11 +544,17 @@ class DragStuff:
             img = img if img is not None else th.randn((1, 96, self.args.image_size, self.args.image_size)).to(self.device)
             tri_feat = self._denoise(img, t)
         self.tri_feat = tri_feat
-        self.volume = decode_volume(self.decoder, tri_feat.to(self.device), self.range, self.middle,
-                                    self.args.shape_resolution)
+        refine = None
+        if self.refine is None:
+            self.volume = decode_volume(self.decoder, tri_feat.to(self.device), self.range, self.middle,
+                                        self.args.shape_resolution)
+        else:                         # decode_volume's two halves, keeping the planes for the projection (get_meshes comes here too)
+            planes = prepare_planes(tri_feat.to(self.device), self.range, self.middle)
+            self.volume = decode_planes_grid(self.decoder, planes, self.args.shape_resolution)
+            refine = dict(self.refine, decoder=self.decoder, planes=planes)
         if self.clean is not None:    # floaters / cavities out before the surface; self.volume is then the cleaned volume
             self.volume = clean_volume(self.volume, **self.clean)
-        return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10)
+        return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10, refine=refine)
 
     # ------------------------------------------------------------------ drag loop (:302-399)
     def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False):

@@ -156,21 +156,50 @@ class OccupancyMesh:
     `update_mesh` (Open3D is imported only there, when called).  `.vertices` / `.triangles` stay device tensors (the
     product's own consumers: Chamfer, sampling, OBJ export); `np.asarray` of them works through torch's __array__ only for
     host tensors, so GUI code goes through `to_open3d()` or `vertices_numpy()`.
-    clean: None (the volume as given), or a dict of volume.clean_volume keywords: `.volume` is then the cleaned volume."""
+    clean: None (the volume as given), or a dict of volume.clean_volume keywords: `.volume` is then the cleaned volume.
+    refine: None, or a dict {decoder, planes, iterations, max_move}: the decoder and the channels-last planes the volume was
+    decoded from.  The smoothed vertices are then put back on the decoder's zero level set
+    (triplane_decoder.project_to_surface: `iterations` steps, default 4, none further than `max_move`, default one voxel,
+    in decoder coordinates) with the triangles unchanged, and compute_vertex_normals() stores the field's analytic normals
+    -grad / |grad| (the direction of decreasing logit: outward, logits are positive inside) instead of the triangle sum.
+    Two further keys are passed on to project_to_surface when given: `step_max` (longest single step, default half a voxel)
+    and `tol` (|logit| at which a vertex is left alone); any other key raises."""
 
-    def __init__(self, volume: torch.Tensor, res: int, smooth_iterations: int = 10, clean=None):
+    def __init__(self, volume: torch.Tensor, res: int, smooth_iterations: int = 10, clean=None, refine=None):
         self.volume = volume if clean is None else _cleaned(volume, clean)
         self.res = res
         self.smooth_iterations = smooth_iterations
+        self.refine = None if refine is None else _checked_refine(refine)
         self._mesh = None
         self._vnormals = None
+        self._field_normals = None
+        self.refinement = None        # refine: (start [V,3], triplane_decoder.Projection) once the mesh is built
 
     def _build(self):
         if self._mesh is None:
             v, t = extract_surface(self.volume, 0.0)
             v = smooth_mesh(v, t, self.smooth_iterations, box_max=float(self.res - 1))     # in grid coordinates: the box is known
+            if self.refine is not None and v.shape[0] > 0:
+                v = self._refined(v)
             self._mesh = (v / self.res * 2 - 1, t)
         return self._mesh
+
+    def _refined(self, v: torch.Tensor) -> torch.Tensor:
+        """grid units -> the decoder coordinates the volume was sampled at (linspace(-1, 1, res): c = 2 g / (res - 1) - 1, NOT
+        the vertex convention g / res * 2 - 1), project, and back to grid units"""
+        from . import triplane_decoder as td              # triplane_decoder has no need of this module
+        r = self.refine
+        voxel = 2.0 / (self.res - 1)
+        kw = {"iterations": int(r.get("iterations", 4)), "max_move": float(r.get("max_move", voxel))}
+        kw["step_max"] = float(r.get("step_max", 0.5 * voxel))
+        if "tol" in r:
+            kw["tol"] = float(r["tol"])
+        start = v * 2 / (self.res - 1) - 1
+        p = td.project_to_surface(r["decoder"], r["planes"], start, **kw)
+        self._field_normals = p.normals
+        self.refinement = (start, p)                     # what went in and what came out, in decoder coordinates
+        moved = (p.accepted > 0)[:, None]                # a vertex no step was taken for stays bit for bit where it was
+        return torch.where(moved, (p.points + 1) * (self.res - 1) / 2, v)
 
     @property
     def vertices(self) -> torch.Tensor:
@@ -197,8 +226,15 @@ class OccupancyMesh:
         return False
 
     def compute_vertex_normals(self, normalized: bool = True):
-        """TriangleMesh.compute_vertex_normals: area-weighted sum of the incident triangles' normals, normalised."""
-        self._vnormals = vertex_normals(self.vertices, self.triangles, normalized)
+        """TriangleMesh.compute_vertex_normals: area-weighted sum of the incident triangles' normals, normalised.
+        With `refine` the stored normals are the field's analytic unit normals -grad / |grad| (outward), and the NORMALISED
+        triangle sum at the vertices where the field has none (a vanishing gradient): unit vectors throughout, so
+        `normalized` has no effect there."""
+        if self._field_normals is None:
+            self._vnormals = vertex_normals(self.vertices, self.triangles, normalized)
+            return self
+        has = (self._field_normals != 0).any(dim=1, keepdim=True)
+        self._vnormals = torch.where(has, self._field_normals, vertex_normals(self.vertices, self.triangles, True))
         return self
 
     @property
@@ -218,8 +254,12 @@ class OccupancyMesh:
 
     def __deepcopy__(self, memo):
         m = OccupancyMesh(self.volume.clone(), self.res, self.smooth_iterations)
+        m.refine = self.refine                           # the decoder and the planes are shared, not copied
         if self._mesh is not None:
             m._mesh = (self._mesh[0].clone(), self._mesh[1].clone())
+        if self._field_normals is not None:
+            m._field_normals = self._field_normals.clone()
+            m.refinement = self.refinement
         if self._vnormals is not None:
             m._vnormals = self._vnormals.clone()
         return m
@@ -257,12 +297,24 @@ def mesh_arrays(mesh):
     return np.asarray(v, dtype=np.float32).reshape(-1, 3), np.asarray(t, dtype=np.int32).reshape(-1, 3)
 
 
+REFINE_KEYS = ("decoder", "planes", "iterations", "max_move", "step_max", "tol")
+
+
+def _checked_refine(refine: dict) -> dict:
+    if not isinstance(refine, dict) or "decoder" not in refine or "planes" not in refine:
+        raise ValueError("refine must be a dict with at least `decoder` and `planes` (the channels-last planes of the volume)")
+    unknown = [k for k in refine if k not in REFINE_KEYS]
+    if unknown:
+        raise ValueError(f"refine: unknown keys {unknown}; known: {REFINE_KEYS}")
+    return dict(refine)
+
+
 def _cleaned(volume: torch.Tensor, clean: dict) -> torch.Tensor:
     from . import volume as volume_ops              # volume.py imports this module
     return volume_ops.clean_volume(volume, **clean)
 
 
-def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, backend: str = None, clean=None):
+def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, backend: str = None, clean=None, refine=None):
     """get_mesh's mesh (drag_utils.py:298-300).  clean: None, or a dict of volume.clean_volume keywords (e.g.
     {"keep": "largest"}): floaters / cavities are taken out of the volume before the surface is made, for every backend.
     backend None -> the module-level BACKEND:
@@ -270,16 +322,21 @@ def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, 
       "open3d"      the same device surface handed over as an open3d.geometry.TriangleMesh -- what the reference's GUI
                     expects from drag_stuff.mesh (main.py:288,314,373,478,507); only the final vertex / triangle arrays
                     cross PCIe (a few MB, not the 67 MB volume)
-      "third_party" the reference's own PyMCubes + Open3D calls on the host."""
+      "third_party" the reference's own PyMCubes + Open3D calls on the host.
+    refine: None, or OccupancyMesh's refine dict {decoder, planes, iterations, max_move}: vertices back on the decoder's
+    level set and analytic normals ("device"; "open3d" hands over that refined mesh with its normals; "third_party" raises)."""
     backend = BACKEND if backend is None else backend
     if clean is not None:
         volume = _cleaned(volume, clean)
     if backend == "device":
-        return OccupancyMesh(volume, res, smooth_iterations)
+        return OccupancyMesh(volume, res, smooth_iterations, refine=refine)
     if backend == "open3d":
-        return OccupancyMesh(volume, res, smooth_iterations).to_open3d()
+        m = OccupancyMesh(volume, res, smooth_iterations, refine=refine)
+        return (m if refine is None else m.compute_vertex_normals()).to_open3d()
     if backend != "third_party":
         raise ValueError(f"unknown mesh backend {backend!r}")
+    if refine is not None:
+        raise ValueError('refine needs the device surface (backend "device" or "open3d"): the third_party meshes are made on the host')
     import mcubes
     import open3d as o3d
     vertices, triangles = mcubes.marching_cubes(volume.detach().cpu().numpy(), 0)

@@ -9,7 +9,7 @@ instead of 336 host round trips (visualize.py:89-95).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -19,6 +19,23 @@ from .unet_spec import DECODER_SHAPES
 # train_triplane_opt's loss weights and optimiser (drag_utils.py:516-539)
 PAIR_WEIGHT, L2_WEIGHT, TV_WEIGHT = 0.3, 0.001, 0.01
 REG_WS = 576          # doubles of regulariser workspace (ISHAP_TRIPLANE_REG_WS, include/ishap.h)
+PROJECT_GMIN = 1e-12  # |d logit / d coordinate|^2 below which a point has no usable direction (project_to_surface)
+DECODE_RES = 256      # the decoding grid project_to_surface's default step lengths are voxels of (visualize.py:79-81)
+
+
+class FieldGrad(NamedTuple):
+    """field_grad_planes: logits [N] and d logit / d coordinate [N,3]"""
+    logits: torch.Tensor
+    grad: torch.Tensor
+
+
+class Projection(NamedTuple):
+    """project_to_surface: the moved points [N,3], their logits [N], unit normals [N,3] (outward; 0 where the gradient
+    vanishes) and the number of accepted steps [N] int32"""
+    points: torch.Tensor
+    logits: torch.Tensor
+    normals: torch.Tensor
+    accepted: torch.Tensor
 
 
 class _Net:
@@ -103,6 +120,14 @@ class MultiTriplane:
         return out.reshape(b, n, 1)
 
     __call__ = forward
+
+    def field_grad(self, obj_idx: int, coordinates: torch.Tensor):
+        """The forward's logits together with their derivative in space: coordinates [B, N, 3] ->
+        (logits [B, N, 1], grad [B, N, 3] = d logit / d coordinate), see field_grad_planes."""
+        b, n, d = coordinates.shape
+        assert d == 3
+        r = field_grad_planes(self, self._planes(obj_idx), coordinates)
+        return r.logits.reshape(b, n, 1), r.grad.reshape(b, n, 3)
 
     def points_loss_grad(self, planes: torch.Tensor, coords: torch.Tensor, gt: torch.Tensor):
         """drag_utils.py:455-458 on explicit planes: loss = -BCEWithLogitsLoss()(decoder(coords), gt) and
@@ -205,6 +230,50 @@ def decode_planes_grid(decoder: MultiTriplane, planes: torch.Tensor, res: int) -
 def decode_volume(decoder: MultiTriplane, latent: torch.Tensor, rng, mid, res: int) -> torch.Tensor:
     """get_mesh's decode half (drag_utils.py:295-298 + visualize.py:79-97) without leaving the device."""
     return decode_planes_grid(decoder, prepare_planes(latent, rng, mid), res)
+
+
+def _field_inputs(decoder: MultiTriplane, planes: torch.Tensor, coords: torch.Tensor):
+    assert planes.dtype == torch.float32 and planes.is_contiguous() and planes.dim() == 4 and planes.shape[0] == 3 and planes.shape[3] == 32
+    c = coords.detach().to(device=planes.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+    if c.shape[0] == 0:
+        raise ValueError("the decoder's field needs at least one point")
+    return c, decoder.net.weights_c()
+
+
+def field_grad_planes(decoder: MultiTriplane, planes: torch.Tensor, coords: torch.Tensor) -> FieldGrad:
+    """MultiTriplane.forward (axisnetworks.py:537-562) on explicit channels-last planes [3,S,S,32] with its analytic
+    derivative in space: coords [..., 3] -> FieldGrad(logits [N], grad [N,3]).  On a cell boundary of a plane the
+    derivative is the right-sided one; outside every plane it is exactly 0.  One launch, bitwise repeatable."""
+    dev = planes.device
+    c, w = _field_inputs(decoder, planes, coords)
+    logits = torch.empty(c.shape[0], dtype=torch.float32, device=dev)
+    grad = torch.empty((c.shape[0], 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ishap_triplane_field_grad(planes.data_ptr(), planes.shape[1], C.byref(w), c.data_ptr(), c.shape[0],
+                                                        logits.data_ptr(), grad.data_ptr(), _lib.stream_ptr(dev)))
+    return FieldGrad(logits, grad)
+
+
+def project_to_surface(decoder: MultiTriplane, planes: torch.Tensor, coords: torch.Tensor, iterations: int = 4,
+                       step_max: float = 0.5 * 2.0 / (DECODE_RES - 1), max_move: float = 1.0 * 2.0 / (DECODE_RES - 1),
+                       tol: float = 1e-4, gmin: float = PROJECT_GMIN) -> Projection:
+    """Move coords [..., 3] onto the zero level set of the decoder's field by `iterations` damped Newton steps along the
+    gradient (ishap_triplane_project): a step is taken only when it lowers |logit|, no single step is longer than `step_max`
+    and no point ends further than `max_move` from where it started -- by default 0.5 and 1.0 voxels of the 256^3
+    decoding grid, in decoder coordinates.  Points with |logit| <= tol are left alone.  The normals are -grad / |grad|, the
+    direction of decreasing logit: logits are positive inside (level 0, extract_surface), so they point OUTWARD.
+    iterations = 0: the logit and the normal at the given points."""
+    dev = planes.device
+    c, w = _field_inputs(decoder, planes, coords)
+    n = c.shape[0]
+    out = Projection(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+                     torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ishap_triplane_project(planes.data_ptr(), planes.shape[1], C.byref(w), c.data_ptr(), n, int(iterations),
+                                                     float(step_max), float(max_move), float(tol), float(gmin), out.points.data_ptr(),
+                                                     out.logits.data_ptr(), out.normals.data_ptr(), out.accepted.data_ptr(),
+                                                     _lib.stream_ptr(dev)))
+    return out
 
 
 def reg_values(planes: torch.Tensor) -> torch.Tensor:

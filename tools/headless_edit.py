@@ -7,8 +7,11 @@ moved by --offset, training() runs the guided loop, and before.png / after.png s
 spheres and green arrows.  With synthetic weights the decoded shape is noise; the path is the point.
 
   python tools/headless_edit.py --out /tmp/edit [--handles 3] [--num_steps 6] [--w_time 3] [--res 64] [--size 512] [--clean largest]
+                                [--refine 4]
 
 --clean largest keeps only the largest connected component of every decoded volume (DragStuff.clean, volume.clean_volume).
+--refine N puts every mesh's smoothed vertices back on the decoder's zero level set with N projection steps of at most one voxel
+in all (DragStuff.refine) and shades the pictures with the field's analytic normals.
 
 Regions (repeatable): --keep-box x0 y0 z0 x1 y1 z1, --keep-sphere cx cy cz r hold a part of the shape, --free-box / --free-sphere
 release one (ishapediting_amd.regions; --keep-weight, --free-weight, --region-dilate as DragStuff.training).  The boxes are drawn
@@ -87,10 +90,14 @@ def edit(a):
     ds = DragStuff(dev, args=args)
     if a.clean is not None:
         ds.clean = {"keep": "largest" if a.clean == "largest" else int(a.clean)}
+    if a.refine is not None:
+        ds.refine = {"iterations": a.refine, "max_move": 2.0 / (a.res - 1)}
     ds.load_weights(synthetic.round_torso_to_fp16(synthetic.unet_state_dict(full_config(), 1234)), synthetic.decoder_state_dict(4321),
                     -0.05 * np.ones(96, np.float32), 0.05 * np.ones(96, np.float32))
     ds.update_latent_params(img=synthetic.latent(0))
     before = ds.mesh0
+    if a.refine is not None:          # the renderer shades with a mesh's stored normals: the field's own
+        before.compute_vertex_normals()
     v = before.vertices
     if v.shape[0] == 0:
         raise RuntimeError("the decoded volume has no surface")
@@ -120,6 +127,8 @@ def edit(a):
             report[name] = {"voxels": int(m.sum()), "changed_without_regions": changed_fraction(volume0, plain, m),
                             "changed_with_regions": changed_fraction(volume0, ds.volume, m)}
             print(f"{name}: {report[name]}")
+    if a.refine is not None:
+        ds.mesh.compute_vertex_normals()
     save_picture(os.path.join(a.out, "after.png"), render_mesh(edit_parts(ds.mesh, sources, targets, boxes=frames), cam, a.size, a.size))
     torch.cuda.synchronize()
     print(json.dumps({"out": a.out, "handles": a.handles, "regions": report, "before_triangles": int(before.triangles.shape[0]),
@@ -188,6 +197,8 @@ def main():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--clean", default=None, metavar="largest|K",
                    help="keep only the largest (or the K largest) connected components of each decoded volume")
+    p.add_argument("--refine", type=int, default=None, metavar="N",
+                   help="project the mesh vertices back onto the decoder's level set with N steps (DragStuff.refine)")
     for role in ("keep", "free"):
         p.add_argument(f"--{role}-box", type=float, nargs=6, action="append", metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                        help=f"a {role} region: the box x0 y0 z0 x1 y1 z1 in [-1, 1]^3 (repeatable)")
