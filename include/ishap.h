@@ -53,7 +53,9 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * volume (ishap_volume_label, ishap_volume_components_*, ishap_volume_flip); 17 since the region
                             * weights of the drag loss (the trailing `weights` of ishap_drag_args, `weights` / `weights_stride` of
                             * ishap_drag_batch_args, ishap_region_plane_weights, ishap_region_plane_weights_scratch_bytes);
-                            * 18 since the decoder's field in space (ishap_triplane_field_grad, ishap_triplane_project) */
+                            * 18 since the decoder's field in space (ishap_triplane_field_grad, ishap_triplane_project); 19 since
+                            * the part edits (ishap_region_select, ishap_region_handles, ishap_region_handles_scratch_bytes,
+                            * ishap_region_transform) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -414,6 +416,39 @@ long long ishap_region_plane_weights_scratch_bytes(int W);
 int ishap_region_plane_weights(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels,
                                const unsigned char* free_voxels, int D, int W, int dilate, float keep_weight, float free_weight,
                                float* weights_out, int* shadow_counts, void* scratch, long long scratch_bytes, void* stream);
+
+/* ---------------------------------------------------------- part edits (ABI 19; csrc/parts.hip)
+ * From a region and a rigid motion to handles, targets and free regions, without a voxel going through the host.  Grids are
+ * uint8 [D][D][D], non-zero = set, indexed [ix][iy][iz] (x slowest) on linspace(-1, 1, D) like a decoded volume, 2 <= D <= 1024;
+ * a voxel's centre is x_i = 2 i / (D - 1) - 1 per axis, in double.  All arithmetic is integer or double, written so that it
+ * rounds operation by operation; the only atomics are integer ones, so every result repeats bit for bit.  Each call returns an
+ * error code and launches nothing for a size outside its limits, a NULL argument or a non-finite number.
+ *
+ * ishap_region_select: mask_out[v] = 1 where volume[v] - level > 0 (float, the inside rule of the surface) AND the voxel's centre
+ *   lies in the union of the primitives (`role` is ignored; box: lo <= x <= hi on all three axes, bounds inclusive; sphere:
+ *   (dx dx + dy dy) + dz dz <= r r) or the voxel is set in `grid` (device, may be NULL); else 0.  prims: device array (NULL when
+ *   n_prims = 0).  count: device int[1], the number of set voxels.
+ *
+ * ishap_region_handles: n farthest-point picks among the set voxels of `mask` (the candidates, M of them).  Pick 0: with
+ *   `start` (HOST int[3], a voxel of the grid, set or not) the candidate nearest to it; with start = NULL the candidate farthest
+ *   from the centre of the candidates' bounding box, comparing |2 v - (lo + hi)|^2.  Pick r >= 1: the candidate with the largest
+ *   squared distance (exact int32) to the picks made so far.  Every tie goes to the lowest linear index (ix D + iy) D + iz.
+ *   picks_out: device int[n][3]; dist2_out: device unsigned[n], the squared distance at the time of each pick (pick 0: 0), so
+ *   dist2_out[n - 1] is the smallest pairwise squared distance among the picks; M_out: device int[1].  Rounds beyond M write
+ *   (-1, -1, -1) and 0.  1 <= n <= 4096.  The rounds are stream-ordered launches that read M and the previous pick from device
+ *   memory: no host synchronisation.  scratch: device, 16-byte aligned, ishap_region_handles_scratch_bytes(D, n) bytes (room for
+ *   every voxel as a candidate: 8 D^3 bytes and a little), needs no initialisation.
+ *
+ * ishap_region_transform: the region moved by x -> R (x - pivot) + pivot + t, as an inverse map (no holes).  rigid15: HOST
+ *   double[15] = R row-major, pivot, t.  For every destination voxel j: d = x_j - pivot - t; y_a = ((R[0][a] d_0 + R[1][a] d_1) +
+ *   R[2][a] d_2) + pivot_a; i_a = rint((y_a + 1) (D - 1) / 2), half to even; mask_out[j] = 1 where every i_a is in [0, D - 1]
+ *   and mask[i] is set.  mask_out must not be mask.  count: device int[1], the number of set voxels. */
+int ishap_region_select(const float* volume, int D, float level, const ishap_region_prim* prims, int n_prims,
+                        const unsigned char* grid, unsigned char* mask_out, int* count, void* stream);
+long long ishap_region_handles_scratch_bytes(int D, int n);
+int ishap_region_handles(const unsigned char* mask, int D, int n, const int* start, int* picks_out, unsigned* dist2_out, int* M_out,
+                         void* scratch, long long scratch_bytes, void* stream);
+int ishap_region_transform(const unsigned char* mask, int D, const double* rigid15, unsigned char* mask_out, int* count, void* stream);
 
 /* fp32 gradient -> fp16 cotangent times a power-of-two loss scale picked from max|g| on the device;
  * bits: device scratch uint32[1]; scale2: device float[2] = {scale, 1/scale} */

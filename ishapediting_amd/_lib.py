@@ -153,6 +153,11 @@ SYMBOLS = {
     "ishap_region_plane_weights_scratch_bytes": (C.c_longlong, [C.c_int]),
     "ishap_region_plane_weights": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                              c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
+    "ishap_region_select": (C.c_int, [c_void_p, C.c_int, C.c_float, c_void_p, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ishap_region_handles_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "ishap_region_handles": (C.c_int, [c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), c_void_p, c_void_p, c_void_p, c_void_p,
+                                       C.c_longlong, c_void_p]),
+    "ishap_region_transform": (C.c_int, [c_void_p, C.c_int, C.POINTER(C.c_double), c_void_p, c_void_p, c_void_p]),
     "ishap_grad_to_scaled_f16": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
     "ishap_planes_prepare": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, c_void_p, c_void_p]),
     "ishap_triplane_fit_loss_grad": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, c_void_p, c_void_p,
@@ -253,9 +258,10 @@ def lib():
         # 14: ishap_cloud_knn / ishap_cloud_normals / ishap_cloud_orient / ishap_cloud_orient_scratch_bytes;
         # 15: ishap_unet_snapshot_*; 16: ishap_volume_label / ishap_volume_components_* / ishap_volume_flip;
         # 17: the weights fields of DragArgsC / DragBatchArgsC, ishap_region_plane_weights;
-        # 18: ishap_triplane_field_grad / ishap_triplane_project
-        if l.ishap_version() < 18:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 18): rebuild with `python -m ishapediting_amd.build`")
+        # 18: ishap_triplane_field_grad / ishap_triplane_project;
+        # 19: ishap_region_select / ishap_region_handles / ishap_region_handles_scratch_bytes / ishap_region_transform
+        if l.ishap_version() < 19:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 19): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

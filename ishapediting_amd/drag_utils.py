@@ -670,6 +670,21 @@ class DragStuff:
         img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), True)
         self.mesh = self.get_mesh(img=img, t=stop_time)
 
+    def training_part(self, part, rigid, handles=16, start=None, scale=600, cof=0.2, keep=None, keep_weight=4.0, free_weight=0.0,
+                      region_dilate=0):
+        """A part edit: move `part` (a regions.Voxels, e.g. from regions.select_part) by `rigid` (a regions.Rigid).  The plan --
+        regions.plan_part_edit: `handles` sources spread over the part from `start`, each one's target where the motion takes
+        it, free = [the part, the part moved] -- is kept as self.part_plan, and the edit is the generator
+        training(plan.sources, plan.targets, scale, cof, keep=keep, free=plan.free, ...), bit for bit.
+        Each handle's lattice only translates; a rotation is carried by the handles' different displacements.  r1 stays as
+        set_offset1 left it: plan.spacing / voxel_size, the handles' spacing in voxels, is the natural lattice radius to compare
+        it with (lattices much smaller leave gaps between handles, much larger ones overlap and average the rotation away).
+        The free regions, like all regions, constrain their three shadows, not only their volume."""
+        from . import regions
+        self.part_plan = plan = regions.plan_part_edit(part, rigid, handles=handles, start=start)
+        return self.training(plan.sources, plan.targets, scale=scale, cof=cof, keep=keep, free=plan.free, keep_weight=keep_weight,
+                             free_weight=free_weight, region_dilate=region_dilate)
+
     # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
     def _check_edits(self, K: int):
         check_edit_count(K, self.max_edits)

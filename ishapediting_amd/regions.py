@@ -10,9 +10,14 @@ device (csrc/regions.hip): keep_weight in the shadow of `keep`, else free_weight
 The inherent limit: a plane texel stands for a whole COLUMN through the shape -- the three planes are projections -- so a region
 constrains its three shadows, not only its own volume.  Keeping a box also holds whatever lies in front of and behind it along
 each axis on the texels the box projects to; freeing one frees those columns.
+
+Part edits (the second half of this file; csrc/parts.hip): `select_part` names a part of a decoded volume, `Rigid` is a rigid
+motion, `sample_handles` spreads handles over the part, `transform_region` moves it, and `plan_part_edit` puts them together
+into what DragStuff.training takes -- sources, targets and free = [part, moved].
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -189,3 +194,265 @@ def component_region(volume: torch.Tensor, point, level: float = 0.0) -> Voxels:
     if root < 0:
         raise ValueError(f"component_region: the point {tuple(p)} (voxel {tuple(int(i) for i in idx)}) is outside the shape")
     return Voxels(labels == root)
+
+
+# ------------------------------------------------------------------------------------------------ part edits (csrc/parts.hip)
+# From a region and a rigid motion to handles, targets and free regions.  A rotation stays within what the drag loss can do:
+# every handle's lattice still only translates; the part's rotation is carried by handles spread over the part, each with its
+# own displacement -- an approximation by translated lattices, better the more handles share the part.  The free regions are
+# the part and the place it moves to; like every region they constrain their three shadows, not only their volume.
+_PARTS_MAX_D, _PARTS_MAX_HANDLES = 1024, 4096
+
+
+def _device_volume(volume, what):
+    if not torch.is_tensor(volume) or volume.dim() != 3 or not (volume.shape[0] == volume.shape[1] == volume.shape[2]):
+        raise ValueError(f"{what}: volume must be a [D, D, D] tensor")
+    D = int(volume.shape[0])
+    if not 2 <= D <= _PARTS_MAX_D:
+        raise ValueError(f"{what}: D = {D} is outside 2..{_PARTS_MAX_D}")
+    if volume.device.type != "cuda":
+        raise ValueError(f"{what}: the volume must be on the GPU (there is no CPU path)")
+    return volume.to(torch.float32).contiguous(), D
+
+
+def _part_grid(part, what):
+    if not isinstance(part, Voxels):
+        raise ValueError(f"{what}: part must be a Voxels region, got {type(part).__name__}")
+    if part.D > _PARTS_MAX_D:
+        raise ValueError(f"{what}: D = {part.D} is above {_PARTS_MAX_D}")
+    if part.mask.device.type != "cuda":
+        raise ValueError(f"{what}: the part's mask must be on the GPU (there is no CPU path)")
+    return part.mask.contiguous().view(torch.uint8), part.D
+
+
+def _nearest_voxel(point, D, what):
+    p = np.asarray(_vec3(point, what))
+    idx = np.rint((p + 1.0) * (D - 1) / 2.0).astype(np.int64)
+    if (idx < 0).any() or (idx > D - 1).any():
+        raise ValueError(f"{what}: the point {tuple(p)} lies outside [-1, 1]^3")
+    return tuple(int(i) for i in idx)
+
+
+def select_part(volume: torch.Tensor, within, level: float = 0.0, point=None, connectivity: int = 6) -> Voxels:
+    """The part of a decoded [D, D, D] volume inside `within` (a Box, Sphere or Voxels, or a list: their union): the voxels with
+    volume - level > 0 whose centre lies in a primitive (box bounds inclusive, sphere <= r^2, in double) or that are set in a
+    grid.  With `point` (in [-1, 1]^3, e.g. what render.pick returns): only the connected piece of that selection which holds
+    the voxel nearest to the point (volume.label_volume with `connectivity`).  Raises ValueError for an empty selection and
+    for a point whose voxel is not selected.  On the device; the host reads one count."""
+    vol, D = _device_volume(volume, "select_part")
+    items = _as_list(within, "within")
+    if not items:
+        raise ValueError("select_part: `within` names no region")
+    if connectivity not in (6, 18, 26):
+        raise ValueError(f"select_part: connectivity must be 6, 18 or 26, got {connectivity!r}")
+    vox = _nearest_voxel(point, D, "select_part: point") if point is not None else None
+    dev = vol.device
+    recs, grid = [], None
+    for it in items:
+        if isinstance(it, Box):
+            recs.append((0, 0, it.lo, it.hi))
+        elif isinstance(it, Sphere):
+            recs.append((1, 0, it.centre, (it.radius, 0.0, 0.0)))
+        else:
+            if it.D != D:
+                raise ValueError(f"select_part: a Voxels grid of size {it.D} for a volume of size {D}")
+            m = it.mask.to(dev)
+            grid = m if grid is None else grid | m
+    if grid is not None:
+        grid = grid.contiguous().view(torch.uint8)
+    prims = None
+    if recs:
+        arr = (_lib.RegionPrimC * len(recs))()
+        for r, (kind, role, a, b) in zip(arr, recs):
+            r.kind, r.role = kind, role
+            r.a[:], r.b[:] = a, b
+        prims = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    out = torch.empty((D, D, D), dtype=torch.uint8, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ishap_region_select(vol.data_ptr(), D, float(level), _lib.ptr(prims), len(recs), _lib.ptr(grid),
+                                                  out.data_ptr(), count.data_ptr(), _lib.stream_ptr(dev)))
+    if int(count.cpu()) == 0:
+        raise ValueError("select_part: the selection is empty: no voxel of the shape lies in the region")
+    sel = out.view(torch.bool)
+    if vox is None:
+        return Voxels(sel)
+    from .volume import label_volume
+    # the shape masked to the selection: outside it volume - level is 0, which is not inside
+    masked = torch.where(sel, vol, torch.full((), float(level), dtype=torch.float32, device=dev))
+    labels = label_volume(masked, level=level, phase="inside", connectivity=connectivity)
+    root = int(labels[vox[0], vox[1], vox[2]])
+    if root < 0:
+        raise ValueError(f"select_part: the point {tuple(_vec3(point, 'point'))} (voxel {vox}) is not in the selection")
+    return Voxels(labels == root)
+
+
+def _axis_angle(axis, degrees):
+    k = np.asarray(_vec3(axis, "Rigid: rotation axis"))
+    norm = float(np.sqrt((k * k).sum()))
+    if norm == 0.0:
+        raise ValueError("Rigid: the rotation axis is the zero vector")
+    k = k / norm
+    deg = float(degrees)
+    if not np.isfinite(deg):
+        raise ValueError(f"Rigid: degrees must be finite, got {degrees!r}")
+    quarter = {0.0: (1.0, 0.0), 90.0: (0.0, 1.0), 180.0: (-1.0, 0.0), 270.0: (0.0, -1.0)}.get(deg % 360.0)
+    c, s = quarter if quarter is not None else (float(np.cos(np.deg2rad(deg))), float(np.sin(np.deg2rad(deg))))
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return c * np.eye(3) + s * K + (1.0 - c) * np.outer(k, k) + 0.0          # + 0.0: no negative zeros
+
+
+@dataclass(frozen=True, eq=False)
+class Rigid:
+    """The rigid motion x -> R (x - pivot) + pivot + translation.  rotation: None, (axis, degrees) -- right-handed about `axis`,
+    which need not be a unit vector -- or a 3 x 3 matrix, which must be a rotation (|R^T R - I| <= 1e-9 entrywise, det > 0: no
+    scale, no reflection).  Whole multiples of 90 degrees about a coordinate axis give entries that are exactly 0 and +-1.
+    Sines and cosines are taken here, on the host, in double."""
+    rotation: object = None
+    pivot: Sequence[float] = (0.0, 0.0, 0.0)
+    translation: Sequence[float] = (0.0, 0.0, 0.0)
+
+    def __post_init__(self):
+        object.__setattr__(self, "pivot", _vec3(self.pivot, "Rigid.pivot"))
+        object.__setattr__(self, "translation", _vec3(self.translation, "Rigid.translation"))
+        rot = self.rotation
+        if rot is None:
+            R = np.eye(3)
+        elif isinstance(rot, (tuple, list)) and len(rot) == 2 and np.ndim(rot[1]) == 0:
+            R = _axis_angle(rot[0], rot[1])
+        else:
+            R = np.array(rot.detach().cpu() if torch.is_tensor(rot) else rot, dtype=np.float64)
+            if R.shape != (3, 3) or not np.isfinite(R).all():
+                raise ValueError(f"Rigid: rotation must be (axis, degrees) or a finite 3 x 3 matrix, got {rot!r}")
+            err = float(np.abs(R.T @ R - np.eye(3)).max())
+            if err > 1e-9 or np.linalg.det(R) <= 0:
+                raise ValueError(f"Rigid: the matrix is not a rotation (|R^T R - I| = {err:.3e}, det = {np.linalg.det(R):.6f}): "
+                                 "a part moves rigidly, without scale or reflection")
+        R.setflags(write=False)
+        object.__setattr__(self, "_matrix", R)
+
+    @property
+    def matrix(self) -> np.ndarray:
+        """float64 [3, 3]"""
+        return self._matrix
+
+    def apply(self, points) -> np.ndarray:
+        """float64 [..., 3]: R (x - pivot) + pivot + translation, summed left to right"""
+        x = np.asarray(points.detach().cpu() if torch.is_tensor(points) else points, dtype=np.float64)
+        if x.shape[-1:] != (3,):
+            raise ValueError(f"Rigid.apply: points must end in 3 coordinates, got shape {x.shape}")
+        R, p, t = self._matrix, np.asarray(self.pivot), np.asarray(self.translation)
+        d = x - p
+        return np.stack([((R[a, 0] * d[..., 0] + R[a, 1] * d[..., 1]) + R[a, 2] * d[..., 2]) + p[a] + t[a] for a in range(3)], axis=-1)
+
+
+@dataclass(frozen=True, eq=False)
+class Handles:
+    """sample_handles' result.  points: float32 [n, 3] on the device, the picked voxels' centres; voxels: int32 [n, 3] on the
+    device, their indices (ix, iy, iz); spacing: the smallest distance between two picks (0 for a single pick)."""
+    points: torch.Tensor
+    voxels: torch.Tensor
+    spacing: float
+
+
+@dataclass(frozen=True, eq=False)
+class PartEdit:
+    """plan_part_edit's result: what DragStuff.training takes.  sources, targets: float32 [n, 3] arrays; free: [part, moved];
+    spacing: the handles' spacing; moved: the part after the motion, a Voxels region."""
+    sources: np.ndarray
+    targets: np.ndarray
+    free: list
+    spacing: float
+    moved: Voxels
+
+
+def handle_voxels(part: Voxels, n: int, start_voxel=None):
+    """The launch under sample_handles, as the kernels leave it on the device: (voxels int32 [n, 3], tail int32 [n + 1]), the
+    tail holding the squared distance at each pick (uint32 bits) and then M, the part's voxel count.  start_voxel: (ix, iy, iz)
+    or None.  Rounds beyond M are (-1, -1, -1) and 0: there is no n <= M check here and no read-back."""
+    grid, D = _part_grid(part, "sample_handles")
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= _PARTS_MAX_HANDLES:
+        raise ValueError(f"sample_handles: n must be an integer in 1..{_PARTS_MAX_HANDLES}, got {n!r}")
+    n = int(n)
+    st = None
+    if start_voxel is not None:
+        st = tuple(int(v) for v in start_voxel)
+        if len(st) != 3 or any(v < 0 or v >= D for v in st):
+            raise ValueError(f"sample_handles: the start voxel {st} lies outside the grid of size {D}")
+        st = (C.c_int * 3)(*st)
+    dev = grid.device
+    L = _lib.lib()
+    nbytes = int(L.ishap_region_handles_scratch_bytes(D, n))
+    if nbytes <= 0:
+        raise ValueError(f"sample_handles: D = {D}, n = {n} is out of range")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    picks = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    tail = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.ishap_region_handles(grid.data_ptr(), D, n, st, picks.data_ptr(), tail.data_ptr(), tail[n:].data_ptr(),
+                                          scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    return picks, tail
+
+
+def sample_handles(part: Voxels, n: int, start=None) -> Handles:
+    """n handles spread over a part by farthest-point sampling on the device (csrc/parts.hip): the first is the voxel nearest
+    to `start` (a point in [-1, 1]^3, in the part or not) or, without one, the voxel farthest from the centre of the part's
+    bounding box; every later one is the voxel farthest from those picked so far.  Distances are exact integers and every tie
+    goes to the lowest voxel index, so the picks repeat bit for bit.  points are the voxel centres 2 i / (D - 1) - 1, formed in
+    double and rounded once to float32.  Raises ValueError when the part has fewer than n voxels."""
+    D = part.D if isinstance(part, Voxels) else 0
+    st = _nearest_voxel(start, D, "sample_handles: start") if start is not None and D >= 2 else None
+    picks, tail = handle_voxels(part, n, st)
+    n = int(n)
+    last, M = (int(v) for v in tail[n - 1:].cpu())                    # the one read-back
+    if n > M:
+        raise ValueError(f"sample_handles: {n} handles asked of a part of {M} voxels")
+    points = (2.0 * picks.to(torch.float64) / (D - 1) - 1.0).to(torch.float32)
+    return Handles(points=points, voxels=picks, spacing=float(np.sqrt(float(last)) * 2.0 / (D - 1)))
+
+
+def transform_region(part: Voxels, rigid: Rigid) -> Voxels:
+    """The part moved by `rigid`, on the part's grid, as an inverse map: every destination voxel looks up the source voxel
+    nearest to its pre-image (round half to even), so the moved region has no holes.  What leaves the cube is cut off; a
+    region that leaves it entirely raises ValueError."""
+    grid, D = _part_grid(part, "transform_region")
+    if not isinstance(rigid, Rigid):
+        raise ValueError(f"transform_region: rigid must be a Rigid, got {type(rigid).__name__}")
+    dev = grid.device
+    out = torch.empty((D, D, D), dtype=torch.uint8, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    args = (C.c_double * 15)(*rigid.matrix.reshape(-1), *rigid.pivot, *rigid.translation)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ishap_region_transform(grid.data_ptr(), D, args, out.data_ptr(), count.data_ptr(), _lib.stream_ptr(dev)))
+    if int(count.cpu()) == 0:
+        raise ValueError("transform_region: the moved region is empty: the motion takes the part out of [-1, 1]^3 (or the part is empty)")
+    return Voxels(out.view(torch.bool))
+
+
+def handle_targets(sources: np.ndarray, rigid: Rigid) -> np.ndarray:
+    """float32(rigid.apply(float64 sources)) for float32 [n, 3] sources; a target outside [-1, 1]^3 raises ValueError naming
+    the handle (a lattice cannot be placed outside the cube)."""
+    sources = np.asarray(sources, np.float32)
+    targets = rigid.apply(sources.astype(np.float64)).astype(np.float32)
+    bad = np.nonzero((np.abs(targets) > 1.0).any(axis=1))[0]
+    if len(bad):
+        k = int(bad[0])
+        raise ValueError(f"plan_part_edit: handle {k} at {sources[k].tolist()} would move to {targets[k].tolist()}, outside [-1, 1]^3")
+    return targets
+
+
+def plan_part_edit(part: Voxels, rigid: Rigid, handles: int = 16, start=None) -> PartEdit:
+    """A part edit as a drag edit: `handles` sources spread over the part (sample_handles), each one's target where `rigid`
+    takes it -- float32(rigid.apply(float64 sources)) -- and free = [part, moved]: the part's old and new place may change.
+    A target outside [-1, 1]^3 raises ValueError naming the handle.  The lattices of the drag loss only translate: a rotation
+    is approximated by the handles' different displacements.  The free regions constrain their three shadows, not only their
+    volume.  Several planned edits run in one loop through training_batch, which takes per-edit lists:
+        plans = [plan_part_edit(part_a, rigid_a), plan_part_edit(part_b, rigid_b)]
+        ds.training_batch([p.sources for p in plans], [p.targets for p in plans], free=[p.free for p in plans])"""
+    if not isinstance(rigid, Rigid):
+        raise ValueError(f"plan_part_edit: rigid must be a Rigid, got {type(rigid).__name__}")
+    h = sample_handles(part, handles, start=start)
+    sources = h.points.cpu().numpy()
+    targets = handle_targets(sources, rigid)
+    moved = transform_region(part, rigid)
+    return PartEdit(sources=sources, targets=targets, free=[part, moved], spacing=h.spacing, moved=moved)

@@ -19,6 +19,14 @@ into both pictures as wire frames (amber keep, teal free).  With regions the edi
 prints for every region the fraction of the voxels inside it whose occupancy sign changed in each run: a report, not a check --
 on synthetic weights the direction is not guaranteed.
 
+A part edit: --part-box x0 y0 z0 x1 y1 z1 / --part-sphere cx cy cz r select the part (the shape inside them; --part-at x,y,z keeps
+only the connected piece at that point), --rotate ax,ay,az,deg --pivot x,y,z --translate x,y,z move it rigidly, and --handles n
+handles are spread over the part instead of picked by pixel (DragStuff.training_part; --offset is not used; write a list that
+starts with a minus sign with an equals sign, --pivot=-0.2,0,0).  The part and the
+place it moves to are the free regions; --keep-* still apply.  The pictures show the handles, their targets and the selecting
+boxes.  Each handle's lattice only translates, so a rotation is approximated by the handles' different displacements; with
+synthetic weights nobody can judge how good the result looks.
+
 --time instead measures the renderer alone (device events around `--repeat` calls after a warm-up, medians):
   the 256^3 sphere mesh (~300 k triangles of a few pixels each) at 1024 x 1024, and 2 picture-filling triangles at 1024 x 1024
   (the second shows that large triangles do not serialise on one lane), next to the bytes each call has to move
@@ -73,6 +81,39 @@ def regions_of(a):
     return keep, free, frames, named
 
 
+def _csv(text, n, what):
+    try:
+        v = [float(x) for x in text.split(",")]
+    except ValueError:
+        v = []
+    if len(v) != n:
+        raise SystemExit(f"{what}: {n} comma-separated numbers expected, got {text!r}")
+    return v
+
+
+def part_of(a, volume):
+    """the command line's part edit -> (part Voxels, Rigid, frames of the selecting boxes), or None without --part-box / --part-sphere"""
+    from ishapediting_amd.regions import Box, Rigid, Sphere, select_part
+    from ishapediting_amd.render import FREE_COLOUR, marker_box
+    if not (a.part_box or a.part_sphere):
+        if a.part_at or a.rotate or a.pivot or a.translate:
+            raise SystemExit("--part-at / --rotate / --pivot / --translate describe a part edit: give --part-box or --part-sphere")
+        return None
+    if a.free_box or a.free_sphere:
+        raise SystemExit("a part edit frees the part and the place it moves to: --free-box / --free-sphere do not go with it")
+    within, frames = [], []
+    for b in a.part_box or []:
+        within.append(Box(b[:3], b[3:]))
+        frames.append((marker_box(np.asarray(b[:3], np.float64), np.asarray(b[3:], np.float64)), FREE_COLOUR))
+    for sp in a.part_sphere or []:
+        within.append(Sphere(sp[:3], sp[3]))
+    part = select_part(volume, within, point=_csv(a.part_at, 3, "--part-at") if a.part_at else None)
+    rot = _csv(a.rotate, 4, "--rotate") if a.rotate else None
+    rigid = Rigid(rotation=(rot[:3], rot[3]) if rot else None, pivot=_csv(a.pivot, 3, "--pivot") if a.pivot else (0.0, 0.0, 0.0),
+                  translation=_csv(a.translate, 3, "--translate") if a.translate else (0.0, 0.0, 0.0))
+    return part, rigid, frames
+
+
 def changed_fraction(before, after, inside):
     """share of the voxels selected by `inside` (a bool grid) whose occupancy sign differs between two decoded volumes"""
     n = int(inside.sum())
@@ -102,22 +143,38 @@ def edit(a):
     if v.shape[0] == 0:
         raise RuntimeError("the decoded volume has no surface")
     cam = Camera.fit(v.min(dim=0).values.cpu().numpy(), v.max(dim=0).values.cpu().numpy(), fov=60, aspect=1.0)   # main.py:611-612
-    first = render_mesh(before, cam, a.size, a.size)
-    picked = pick_sources(before, cam, first.depth, a.handles, a.seed)
-    sources = np.stack([p[0] for p in picked])
-    targets = sources + np.asarray(a.offset, np.float32)
-    for pos, idx, d, px in picked:
-        print(f"pick pixel {px}: vertex {idx} at {pos.tolist()}, depth {d:.6f}")
     keep, free, frames, named = regions_of(a)
     volume0 = ds.volume.clone()
+    part_edit = part_of(a, volume0)
+    report, part_report = {}, None
+    if part_edit is not None:      # handles and targets come from the part and its motion; the plan is made when the edit is created
+        part, rigid, part_frames = part_edit
+        frames = frames + part_frames
+        final = ds.training_part(part, rigid, handles=a.handles, scale=a.scale, cof=a.cof, keep=keep or None, keep_weight=a.keep_weight,
+                                 free_weight=a.free_weight, region_dilate=a.region_dilate)
+        plan = ds.part_plan
+        sources, targets = plan.sources, plan.targets
+        part_report = {"voxels": int(part.mask.sum()), "moved_voxels": int(plan.moved.mask.sum()), "handles": int(sources.shape[0]),
+                       "spacing": plan.spacing, "spacing_in_voxels": plan.spacing / ds.voxel_size, "r1": int(ds.r1),
+                       "rotation": rigid.matrix.tolist(), "pivot": list(rigid.pivot), "translation": list(rigid.translation)}
+        print(f"part: {part_report}")
+        for s, t in zip(sources, targets):
+            print(f"handle {s.tolist()} -> {t.tolist()}")
+    else:
+        first = render_mesh(before, cam, a.size, a.size)
+        picked = pick_sources(before, cam, first.depth, a.handles, a.seed)
+        sources = np.stack([p[0] for p in picked])
+        targets = sources + np.asarray(a.offset, np.float32)
+        for pos, idx, d, px in picked:
+            print(f"pick pixel {px}: vertex {idx} at {pos.tolist()}, depth {d:.6f}")
+        final = ds.training(sources, targets, scale=a.scale, cof=a.cof, keep=keep or None, free=free or None,
+                            keep_weight=a.keep_weight, free_weight=a.free_weight, region_dilate=a.region_dilate)
     save_picture(os.path.join(a.out, "before.png"), render_mesh(edit_parts(before, sources, targets, boxes=frames), cam, a.size, a.size))
-    report = {}
     if named:                # the same edit without the regions first: what they change is the difference of the two runs
         for _ in ds.training(sources, targets, scale=a.scale, cof=a.cof):
             pass
         plain = ds.volume.clone()
-    for _ in ds.training(sources, targets, scale=a.scale, cof=a.cof, keep=keep or None, free=free or None,
-                         keep_weight=a.keep_weight, free_weight=a.free_weight, region_dilate=a.region_dilate):
+    for _ in final:
         pass
     if named:
         ax = torch.linspace(-1, 1, a.res, device=dev, dtype=torch.float64)
@@ -131,7 +188,7 @@ def edit(a):
         ds.mesh.compute_vertex_normals()
     save_picture(os.path.join(a.out, "after.png"), render_mesh(edit_parts(ds.mesh, sources, targets, boxes=frames), cam, a.size, a.size))
     torch.cuda.synchronize()
-    print(json.dumps({"out": a.out, "handles": a.handles, "regions": report, "before_triangles": int(before.triangles.shape[0]),
+    print(json.dumps({"out": a.out, "handles": a.handles, "regions": report, "part": part_report, "before_triangles": int(before.triangles.shape[0]),
                       "after_triangles": int(ds.mesh.triangles.shape[0]), "camera": {"eye": list(cam.eye), "near": cam.near, "far": cam.far}}))
 
 
@@ -204,6 +261,14 @@ def main():
                        help=f"a {role} region: the box x0 y0 z0 x1 y1 z1 in [-1, 1]^3 (repeatable)")
         p.add_argument(f"--{role}-sphere", type=float, nargs=4, action="append", metavar=("CX", "CY", "CZ", "R"),
                        help=f"a {role} region: the sphere cx cy cz r (repeatable)")
+    p.add_argument("--part-box", type=float, nargs=6, action="append", metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                   help="a part edit: the part is the shape inside this box (repeatable, with --part-sphere: their union)")
+    p.add_argument("--part-sphere", type=float, nargs=4, action="append", metavar=("CX", "CY", "CZ", "R"),
+                   help="a part edit: the part is the shape inside this sphere (repeatable)")
+    p.add_argument("--part-at", default=None, metavar="X,Y,Z", help="only the connected piece of the selection at this point")
+    p.add_argument("--rotate", default=None, metavar="AX,AY,AZ,DEG", help="rotate the part by DEG degrees about the axis (AX, AY, AZ)")
+    p.add_argument("--pivot", default=None, metavar="X,Y,Z", help="the point the rotation turns about (default: the origin)")
+    p.add_argument("--translate", default=None, metavar="X,Y,Z", help="then move the part by this vector")
     p.add_argument("--keep-weight", type=float, default=4.0)
     p.add_argument("--free-weight", type=float, default=0.0)
     p.add_argument("--region-dilate", type=int, default=0)
