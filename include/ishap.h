@@ -55,7 +55,7 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * ishap_drag_batch_args, ishap_region_plane_weights, ishap_region_plane_weights_scratch_bytes);
                             * 18 since the decoder's field in space (ishap_triplane_field_grad, ishap_triplane_project); 19 since
                             * the part edits (ishap_region_select, ishap_region_handles, ishap_region_handles_scratch_bytes,
-                            * ishap_region_transform) */
+                            * ishap_region_transform); 20 since ishap_unet_block_grad */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -130,6 +130,18 @@ int ishap_unet_copy_tap(const ishap_unet* u, void* dst, void* stream);
  * [N][channels][size][size] (the reference's layout).  Parity tests use it to localise a mismatch to one block. */
 int ishap_unet_block_output(const ishap_unet* u, int group, int index, int* channels, int* size, void* dst_nchw_f16,
                             void* stream);
+/* The gradient maps of the last ishap_unet_backward_input / ishap_unet_backward_from_output (ABI 20), block by block: group and
+ * index as for ishap_unet_block_output; part 0 = the gradient w.r.t. the block's OUTPUT, summed over all of its consumers (for an
+ * input block: the block after it plus its skip connection); parts 1 and 2 (group 2 only) = the gradient w.r.t. the `h` and the
+ * `skip` half of an output block's concatenated input (gd/unet.py:663).  Writes the map's channel count and side to *channels /
+ * *size; when dst is non-NULL also copies the stored fp16 values, untouched (a loss scale stays in them), as
+ * [N][channels][size][size].  The pass keeps no copy: it records where each map was written, and the maps stay there until the
+ * next forward, backward or snapshot restore on the context -- a read after one of those fails, as does a read before any
+ * backward, of an output block above the one the backward started from, or of parts 1 / 2 outside group 2.  Part 0 of the block a
+ * backward from the tap started at IS the caller's cotangent: it is read through the pointer that call was given, which must
+ * still be allocated.  Tests use it to pin each block's vector-Jacobian product on its own. */
+int ishap_unet_block_grad(const ishap_unet* u, int group, int index, int part, int* channels, int* size, void* dst_nchw_f16,
+                          void* stream);
 /* Optional, ahead of a sampling loop: compute the timestep-embedding products of n timesteps once (timestep_embedding,
  * time_embed and every ResBlock's emb_layers, gd/unet.py:651,245-250 -- none of them depends on x).  A later
  * ishap_unet_forward whose timesteps all equal one prepared value reuses its row and skips those four launches; any other

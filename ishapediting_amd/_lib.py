@@ -117,6 +117,8 @@ SYMBOLS = {
     "ishap_unet_copy_tap": (C.c_int, [c_void_p, c_void_p, c_void_p]),
     "ishap_unet_block_output": (C.c_int, [c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), c_void_p,
                                           c_void_p]),
+    "ishap_unet_block_grad": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), c_void_p,
+                                        c_void_p]),
     "ishap_unet_workspace_bytes": (C.c_longlong, [c_void_p]),
     "ishap_unet_join_tail": (C.c_int, [c_void_p, c_void_p]),
     "ishap_unet_run_tail": (C.c_int, [c_void_p]),
@@ -259,9 +261,10 @@ def lib():
         # 15: ishap_unet_snapshot_*; 16: ishap_volume_label / ishap_volume_components_* / ishap_volume_flip;
         # 17: the weights fields of DragArgsC / DragBatchArgsC, ishap_region_plane_weights;
         # 18: ishap_triplane_field_grad / ishap_triplane_project;
-        # 19: ishap_region_select / ishap_region_handles / ishap_region_handles_scratch_bytes / ishap_region_transform
-        if l.ishap_version() < 19:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 19): rebuild with `python -m ishapediting_amd.build`")
+        # 19: ishap_region_select / ishap_region_handles / ishap_region_handles_scratch_bytes / ishap_region_transform;
+        # 20: ishap_unet_block_grad
+        if l.ishap_version() < 20:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 20): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

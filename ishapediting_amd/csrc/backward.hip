@@ -190,6 +190,7 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
   e.tenant = tenancy.granted;
   u->arena.off = u->fwd_mark;
   u->stat_off = u->stat_fwd_mark;
+  u->seq++;                     // the scratch above fwd_mark is reused from here on: the previous pass's gradient maps are gone
   if (!dry) {
     ISHAP_REQUIRE(u->have_saved, "backward needs a preceding forward with keep_for_backward=1");
     if (u->bwd_since_fwd++ > 0 && u->stat_cap > u->stat_fwd_mark)   // a second backward on the same forward: fresh zeros
@@ -228,7 +229,9 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
     const int Cs = b.skip_ch, Ch = b.cin - Cs;
     ISHAP_REQUIRE(b.layers[0].kind == 1 && Ch % 8 == 0, "an output block starts with a ResBlock on the concatenation");
     Tensor gh, gs;
+    b.gout = g;
     ISHAP_TRY(block_backward(e, b, g, gh, Ch, &gs));       // the first ResBlock writes d/d[h | skip] as two tensors
+    b.gh = gh; b.gs = gs;
     skipgrad[n_in - 1 - i] = gs;     // hs.pop() order (unet.py:663)
     g = gh;
     ISHAP_TRY(bwd_mark(u, s, 100 + i, dry));
@@ -249,6 +252,7 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
   auto run = [&](BlockL& blk, const half_t* owed_next, const half_t*& pending) -> int {
     bool done = false;
     Tensor o;
+    blk.gout = g;
     ISHAP_TRY(block_backward(e, blk, g, o, 0, nullptr, owed_next, &done));
     g = o;
     pending = (owed_next && !done) ? owed_next : nullptr;
@@ -258,12 +262,9 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
   ISHAP_TRY(run(u->mid, n_in > 0 ? skipgrad[n_in - 1].p : nullptr, pending));
   ISHAP_TRY(bwd_mark(u, s, 200, dry));
   for (int i = n_in - 1; i >= 0; --i) {
-    if (pending) {                       // fall-back: a separate add
-      Tensor sum = g;
-      ISHAP_ALLOC(sum.p, e, g.numel());
-      if (!dry) ISHAP_TRY(add_f16(g.p, pending, sum.p, g.numel(), s));
-      g = sum;
-    }
+    // build_spec / unet_build accept the resblock_updown variant only: the middle block and every input block but the stem begin
+    // with a ResBlock, which takes the owed addend as add2 (tests/test_unet_ref_host.py walks the specs)
+    ISHAP_REQUIRE(!pending, "a skip gradient is still owed: the block before this one did not begin with a ResBlock");
     ISHAP_TRY(run(u->in_blocks[i], i > 0 ? skipgrad[i - 1].p : nullptr, pending));
     ISHAP_TRY(bwd_mark(u, s, 300 + i, dry));
   }
@@ -271,6 +272,7 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
     ISHAP_TRY(nhwc_f16_to_nchw_f32_scaled(g.p, dx, N, cfg.in_channels, cfg.image_size * cfg.image_size, u->in_pad,
                                           scale2 ? scale2 + 1 : nullptr, s));
   ISHAP_TRY(bwd_mark(u, s, 999, dry));
+  if (!dry) { u->grad_seq = u->seq; u->grad_F = F; }
   return 0;
 }
 

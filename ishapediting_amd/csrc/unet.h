@@ -92,6 +92,11 @@ struct BlockL {
   int cin = 0, cout = 0, res_in = 0, res_out = 0, skip_ch = 0;
   Tensor out;       // block output of the last forward
   Tensor cat;       // concat input (output blocks)
+  // Read-out of the last backward (ishap_unet_block_grad): the backward scratch is bump-allocated above fwd_mark and never reused
+  // within one pass, so every gradient map stays where it was written until the next forward / backward / restore on the context.
+  // gout: the dense gradient w.r.t. this block's output, summed over its consumers; gh, gs (output blocks): what the first
+  // ResBlock wrote for d/d[h | skip].  Valid only while ishap_unet::grad_seq == ishap_unet::seq.
+  Tensor gout, gh, gs;
 };
 
 struct ParamSlot {
@@ -174,6 +179,10 @@ struct ishap_unet {
   long long* stat_base = nullptr;   // arena of per-channel GroupNorm sums, zeroed once per forward
   size_t stat_cap = 0, stat_off = 0, stat_high = 0, stat_fwd_mark = 0;
   int bwd_since_fwd = 0;
+  // every forward, backward (dry runs included) and snapshot restore counts here; a backward that ran to its end leaves its count
+  // in grad_seq, with the output block it started from (grad_F) -- BlockL::gout / gh / gs may be read while the two agree
+  unsigned long long seq = 0, grad_seq = 0;
+  int grad_F = -1;
   size_t fwd_mark = 0;          // arena offset after the forward (backward scratch goes above it)
   // Overlapped forward tail (keep_for_backward bit 1): the output blocks after the tap and the head are enqueued on a
   // stream of the context's own, forked from the caller's stream at the tap, so that they run beside the loss and the

@@ -639,6 +639,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
   }
   u->arena.reset();
   u->stat_off = 0;
+  u->seq++;                     // the arena is reused from here on: the last backward's gradient maps are gone
   // the statistics arena is zeroed by the layout conversion below (its first use comes after it)
   const bool zero_in_convert = (u->stat_cap % 2 == 0) && (reinterpret_cast<uintptr_t>(u->stat_base) & 15) == 0;
   if (!dry && u->stat_cap && !zero_in_convert) ISHAP_CHECK_HIP(hipMemsetAsync(u->stat_base, 0, u->stat_cap * sizeof(long long), s));
@@ -749,7 +750,7 @@ static int snap_reserve(T** buf, size_t* cap, size_t need) {
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 19; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 20; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
@@ -773,6 +774,7 @@ int ishap_version(void) { return 19; }  // 2: ishap_mesh_smooth takes the scratc
                                         //     decode_field.hip)
                                         // 19: part edits (ishap_region_select, ishap_region_handles, ishap_region_handles_scratch_bytes,
                                         //     ishap_region_transform; parts.hip)
+                                        // 20: per-block gradients of the last backward (ishap_unet_block_grad)
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");
@@ -963,6 +965,29 @@ int ishap_unet_block_output(const ishap_unet* u, int group, int index, int* chan
   return nhwc_f16_to_nchw(b->out.p, dst_nchw_f16, 0, b->out.N, b->out.C, b->out.H * b->out.W, b->out.C, (hipStream_t)stream);
 }
 
+int ishap_unet_block_grad(const ishap_unet* u, int group, int index, int part, int* channels, int* size, void* dst_nchw_f16,
+                          void* stream) {
+  ISHAP_REQUIRE(u && group >= 0 && group <= 2, "group: 0 input_blocks, 1 middle_block, 2 output_blocks");
+  ISHAP_REQUIRE(part >= 0 && part <= 2, "part: 0 gradient w.r.t. the block output, 1 / 2 w.r.t. the h / skip half of an output block's input");
+  ISHAP_REQUIRE(part == 0 || group == 2, "parts 1 and 2 (the [h | skip] halves) exist for output blocks only");
+  const BlockL* b = nullptr;
+  if (group == 0) { ISHAP_REQUIRE(index >= 0 && index < (int)u->in_blocks.size(), "input block index"); b = &u->in_blocks[index]; }
+  else if (group == 1) b = &u->mid;
+  else { ISHAP_REQUIRE(index >= 0 && index < (int)u->out_blocks.size(), "output block index"); b = &u->out_blocks[index]; }
+  if (channels) *channels = part == 0 ? b->cout : (part == 1 ? b->cin - b->skip_ch : b->skip_ch);
+  if (size) *size = part == 0 ? b->res_out : b->res_in;
+  if (!dst_nchw_f16) return 0;
+  ISHAP_REQUIRE(u->grad_seq != 0, "block gradients exist only after a backward pass on this context");
+  ISHAP_REQUIRE(u->grad_seq == u->seq, "stale block gradients: a forward, a backward or a snapshot restore ran after the pass that wrote them");
+  ISHAP_REQUIRE(!(u->restored_partial && group == 2 && index > u->last_feat), "the restored snapshot holds the network up to the tap only");
+  ISHAP_REQUIRE(!(group == 2 && index > u->grad_F), "the last backward started below this output block: it has no gradient");
+  const Tensor& t = part == 0 ? b->gout : (part == 1 ? b->gh : b->gs);
+  ISHAP_REQUIRE(t.p != nullptr, "no gradient was recorded for this block");
+  ISHAP_TRY(ishap_check_status());
+  ISHAP_CHECK_HIP(hipSetDevice(u->device));
+  return nhwc_f16_to_nchw(t.p, dst_nchw_f16, 0, t.N, t.C, t.H * t.W, t.C, (hipStream_t)stream);
+}
+
 int ishap_unet_copy_tap(const ishap_unet* u, void* dst, void* stream) {
   ISHAP_REQUIRE(u && dst && u->tap.p, "no resident tap (run a forward with feat_layer >= 0 first)");
   ISHAP_CHECK_HIP(hipMemcpyAsync(dst, u->tap.p, (size_t)u->tap.numel() * sizeof(half_t), hipMemcpyDeviceToDevice,
@@ -1022,6 +1047,7 @@ int ishap_unet_snapshot_restore(ishap_unet* u, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   ISHAP_TRY(unet_join_tail(u, s));                 // a tail still in flight reads (and owns) the arena about to be overwritten
   u->have_saved = false;
+  u->seq++;                                        // the gradient maps of a backward before this restore belong to another forward
   if (sn.arena_bytes) ISHAP_CHECK_HIP(hipMemcpyAsync(u->arena.base, sn.arena, sn.arena_bytes, hipMemcpyDeviceToDevice, s));
   if (sn.stat_count) ISHAP_CHECK_HIP(hipMemcpyAsync(u->stat_base, sn.stat, sn.stat_count * sizeof(long long), hipMemcpyDeviceToDevice, s));
   u->film_cur = sn.film;                           // the snapshot's own rows: a later prepare_timesteps may rewrite the cache

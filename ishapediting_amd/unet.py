@@ -57,6 +57,7 @@ class UNetModel:
         self._param_probe = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._fp16 = False
         self._last_shape, self._last_feat = None, -1
+        self._last_cot = None
         self._snap_key = None          # (N, feat_layer, input shape) of the forward a valid snapshot holds
 
     # ------------------------------------------------------------------ module-like surface
@@ -246,6 +247,22 @@ class UNetModel:
                                                        _lib.stream_ptr(self.device)))
         return t
 
+    def block_grad(self, group: int, index: int = 0, part: int = 0) -> torch.Tensor:
+        """A gradient map of the last `backward_input` / `backward_from_output`, as fp16 NCHW, exactly as stored (a loss scale
+        stays in it): part 0 = the gradient w.r.t. the output of input_blocks[index] (group 0), middle_block (1) or
+        output_blocks[index] (2), summed over all its consumers; parts 1 / 2 (group 2 only) = the gradient w.r.t. the `h` / the
+        `skip` half of the output block's concatenated input.  The maps stay resident until the next forward, backward or
+        snapshot restore; a read after one of those raises."""
+        ch, sz = C.c_int(), C.c_int()
+        _lib.check(self._L.ishap_unet_block_grad(self._h, group, index, part, C.byref(ch), C.byref(sz), None, None))
+        if self._last_shape is None:
+            raise RuntimeError("block gradients exist only after a backward pass on this context")
+        t = torch.empty((self._last_shape[0], ch.value, sz.value, sz.value), dtype=torch.float16, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.ishap_unet_block_grad(self._h, group, index, part, C.byref(ch), C.byref(sz), t.data_ptr(),
+                                                     _lib.stream_ptr(self.device)))
+        return t
+
     def workspace_bytes(self) -> int:
         return int(self._L.ishap_unet_workspace_bytes(self._h))
 
@@ -255,6 +272,7 @@ class UNetModel:
         with torch.cuda.device(self.device):
             _lib.check(self._L.ishap_unet_backward_input(self._h, cot_nhwc_f16.data_ptr(), _lib.ptr(scale2),
                                                          dx.data_ptr(), _lib.stream_ptr(self.device)))
+        self._last_cot = cot_nhwc_f16      # block_grad reads the tapped block's incoming gradient through this buffer
         return dx
 
     def backward_from_output(self, cot_out: torch.Tensor, scale2: Optional[torch.Tensor] = None) -> torch.Tensor:
