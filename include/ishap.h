@@ -55,7 +55,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * ishap_drag_batch_args, ishap_region_plane_weights, ishap_region_plane_weights_scratch_bytes);
                             * 18 since the decoder's field in space (ishap_triplane_field_grad, ishap_triplane_project); 19 since
                             * the part edits (ishap_region_select, ishap_region_handles, ishap_region_handles_scratch_bytes,
-                            * ishap_region_transform); 20 since ishap_unet_block_grad */
+                            * ishap_region_transform); 20 since ishap_unet_block_grad; 21 since the handle
+                            * tracking (ishap_drag_track, ishap_drag_track_scratch_bytes) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -401,6 +402,27 @@ int ishap_drag_batch_loss_grad(const ishap_drag_batch_args* a, const void* edit_
 /* the same plus the fp16 cotangent [E][W*W][ld] with the batch's loss scale; bits: device uint32[1]; scale2: device float[2] */
 int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
                                     float* grad_nhwc, float* loss, void* cot_f16, unsigned* bits, float* scale2, void* stream);
+/* ---------------------------------------------------------- handle tracking (ABI 21; csrc/track.hip)
+ * Where each drag handle went, in the feature space the loss reads: for handle b the candidate offset k in [-R, R]^3 (voxels of
+ * the handle lattice, relative to K_in[b]) whose patch of the EDITED tap is nearest, in L1 over the (2 rp + 1)^2 lattice positions
+ * and Cc channels of each plane, to the patch of the GUIDANCE tap at the source.  Sampling, plane axes and channel gather are the
+ * drag loss's; coordinates are sources[b][axis] + voxel * m with the integer m summed first (source side m = i, candidate side
+ * m = K_in + k + i), so K_in + k = 0 reads the source lattice bit for bit.  D(b; k) = D_0(kx, ky) + D_1(ky, kz) + D_2(kx, kz);
+ * the winner has the smallest D, then the smallest kx^2 + ky^2 + kz^2, then the lowest ((kz+R) side + ky+R) side + kx+R,
+ * side = 2 R + 1.  K_out[b] = K_in[b] + k*, dist[b] = D(k*), dist0[b] = D(0).  No atomics: results are bitwise repeatable and a
+ * handle's do not depend on the other handles or edits of the call.  Read-only on both taps.
+ *   edit_nhwc_f16 [E][W*W][ld]; orig_nhwc_f16: edit e's guidance at + e * orig_stride halfs (0: one guidance tap for all edits)
+ *   chmap device int[3][Cc]; sources device float[Btot][3]; handle_offsets HOST int[E + 1] (CSR, as ishap_drag_batch_args)
+ *   K_in, K_out device int[Btot][3] (may be the same buffer); dist, dist0 device float[Btot]
+ *   volume: NULL, or device float[Btot][side^3], every D(b; k) at the linear index above
+ *   scratch: device, 16-byte aligned, ishap_drag_track_scratch_bytes(E, Btot, R, rp, Cc) bytes
+ * 0 <= R <= 8, 0 <= rp <= 4, 1 <= E <= 32, every edit at least one handle: anything else is an error before any launch (the
+ * scratch size call returns -1).  Two launches. */
+long long ishap_drag_track_scratch_bytes(int E, int Btot, int R, int rp, int Cc);
+int ishap_drag_track(const void* edit_nhwc_f16, const void* orig_nhwc_f16, long long orig_stride, int W, int ld, int Cc,
+                     const int* chmap, const float* sources, const int* handle_offsets, int E, float voxel, int R, int rp,
+                     const int* K_in, int* K_out, float* dist, float* dist0, float* volume, void* scratch, long long scratch_bytes,
+                     void* stream);
 /* ---------------------------------------------------------- region-constrained edits (ABI 17; csrc/regions.hip)
  * The weight map of the drag loss's mask term from 3-D regions in the coordinates handles use, [-1, 1]^3.  A region is a union
  * of primitives and one voxel grid; `keep` must not move, `free` may.  Its SHADOW on plane p (axes as the drag loss: plane 0

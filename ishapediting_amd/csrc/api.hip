@@ -4,6 +4,7 @@
 #include "ddpm.h"
 #include "decode.h"
 #include "drag.h"
+#include "track.h"
 #include "regions.h"
 #include "render.h"
 
@@ -344,6 +345,30 @@ int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* 
   ISHAP_REQUIRE(edit && orig && grad && loss && cot_f16 && bits && scale2, "null argument");
   fill_drag_call(d, edit, orig, grad, loss);
   return drag_batch_loss_launch(d, (half_t*)cot_f16, bits, scale2, a->weights, a->weights_stride, (hipStream_t)stream);
+}
+
+// ---- handle tracking (csrc/track.hip): every range is checked before anything is launched
+long long ishap_drag_track_scratch_bytes(int E, int Btot, int R, int rp, int Cc) {
+  if (E < 1 || E > DRAG_MAX_EDITS || Btot < E) return -1;
+  return track_scratch_bytes(Btot, R, rp, Cc);
+}
+
+int ishap_drag_track(const void* edit, const void* orig, long long orig_stride, int W, int ld, int Cc, const int* chmap,
+                     const float* sources, const int* handle_offsets, int E, float voxel, int R, int rp, const int* K_in, int* K_out,
+                     float* dist, float* dist0, float* volume, void* scratch, long long scratch_bytes, void* stream) {
+  ISHAP_REQUIRE(edit && orig && chmap && sources && handle_offsets && K_in && K_out && dist && dist0 && scratch, "null argument");
+  ISHAP_REQUIRE(E >= 1 && E <= DRAG_MAX_EDITS, "drag track: E must be in 1..32");      // hoff below holds that many
+  TrackArgs t;
+  t.edit = (const half_t*)edit; t.orig = (const half_t*)orig; t.orig_stride = orig_stride;
+  t.W = W; t.ld = ld; t.Cc = Cc; t.chmap = chmap; t.sources = sources; t.E = E;
+  for (int e = 0; e <= E; ++e) t.hoff[e] = handle_offsets[e];
+  t.voxel = voxel; t.R = R; t.rp = rp; t.K_in = K_in; t.K_out = K_out; t.dist = dist; t.dist0 = dist0; t.volume = volume;
+  t.partial = (float*)scratch;
+  const long long need = ishap_drag_track_scratch_bytes(E, t.hoff[E], R, rp, Cc);
+  ISHAP_REQUIRE(need >= 0, "drag track: R must be in 0..8, rp in 0..4, Cc >= 1 and every edit needs a handle");
+  ISHAP_REQUIRE(scratch_bytes >= need, "drag track: scratch smaller than ishap_drag_track_scratch_bytes(E, Btot, R, rp, Cc)");
+  ISHAP_REQUIRE(((unsigned long long)scratch & 15ull) == 0, "drag track: scratch must be 16-byte aligned");
+  return track_launch(t, (hipStream_t)stream);
 }
 
 // ---- region weights of the drag loss's mask term (csrc/regions.hip)

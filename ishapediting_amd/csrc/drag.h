@@ -2,6 +2,38 @@
 #include "common.h"
 #include <algorithm>
 
+// ---- the sampling the drag loss (drag.hip) and the handle tracker (track.hip) share: one definition, the same bits in both ----
+__device__ __forceinline__ void plane_axes(int p, int& a_col, int& a_row) {
+  // grid[...,0] indexes W (columns), grid[...,1] indexes H (rows); drag_utils.py:318-321
+  a_col = (p == 1) ? 1 : 0;
+  a_row = (p == 0) ? 1 : 2;
+}
+
+// Lattice coordinate s + voxel * k as the reference forms it (drag_utils.py:314-316: the product rounded, then the sum).  Not
+// contracted into a fused multiply-add: every call site, and the reference's float32 lattice, get the same bits.
+__device__ __forceinline__ float lattice(float s, float voxel, int k) {
+#pragma clang fp contract(off)
+  const float o = voxel * (float)k;
+  return s + o;
+}
+
+struct Bilin { int x0, y0; float w[4]; };
+__device__ __forceinline__ Bilin bilin_setup(float u, float v, int W) {
+#pragma clang fp contract(off)      // the same (u, v) must give the same weights at every call site (zero loss at zero displacement)
+  // Texel coordinates and weights in double, rounded to float once.  In float, ix = (u + 1) / 2 * (W - 1) carries up to 2^-21 of
+  // a texel of rounding that is the SAME for every channel of a position (and, at a pitch of one texel, for every position of a
+  // lattice row): it does not average out, and moved the loss by 1e-7 to 2e-7 against the float64 statement of the same lattice
+  // (two units in the last place of the float it is returned as).  A dozen wave-uniform operations per position.
+  Bilin b;
+  const double ix = (((double)u + 1.0) / 2.0) * (double)(W - 1);
+  const double iy = (((double)v + 1.0) / 2.0) * (double)(W - 1);
+  const double fx = floor(ix), fy = floor(iy);
+  b.x0 = (int)fx; b.y0 = (int)fy;
+  const double wx1 = ix - fx, wx0 = 1.0 - wx1, wy1 = iy - fy, wy0 = 1.0 - wy1;
+  b.w[0] = (float)(wx0 * wy0); b.w[1] = (float)(wx1 * wy0); b.w[2] = (float)(wx0 * wy1); b.w[3] = (float)(wx1 * wy1);
+  return b;
+}
+
 // one edit: what the device bodies of drag.hip work on (drag_edit_args cuts it out of a DragBatchArgs)
 struct DragArgs {
   const half_t* edit = nullptr;    // current tap, NHWC fp16 [W*W][ld]

@@ -750,7 +750,7 @@ static int snap_reserve(T** buf, size_t* cap, size_t need) {
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 20; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 21; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
@@ -775,6 +775,7 @@ int ishap_version(void) { return 20; }  // 2: ishap_mesh_smooth takes the scratc
                                         // 19: part edits (ishap_region_select, ishap_region_handles, ishap_region_handles_scratch_bytes,
                                         //     ishap_region_transform; parts.hip)
                                         // 20: per-block gradients of the last backward (ishap_unet_block_grad)
+                                        // 21: handle tracking (ishap_drag_track, ishap_drag_track_scratch_bytes; track.hip)
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");

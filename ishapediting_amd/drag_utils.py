@@ -13,6 +13,7 @@ What differs from the reference by design (all inside the boundary, results equa
 from __future__ import annotations
 
 import argparse
+import collections
 import copy
 import ctypes as C
 import os
@@ -318,6 +319,153 @@ class BatchDragKernels(_DragKernelsBase):
         return self.cot, self.scale2
 
 
+Track = collections.namedtuple("Track", "offsets positions dist dist0 volume")
+TRACK_DEFAULTS = {"radius": 4, "patch": 2, "every": 1}
+
+
+def track_options(track) -> Optional[dict]:
+    """The `track` keyword of training() / training_part() / training_batch(): None or False (off), True (the defaults) or a dict
+    with any of radius, patch, every -> None or the full dict."""
+    if track is None or track is False:
+        return None
+    opts = dict(TRACK_DEFAULTS)
+    if track is not True:
+        unknown = set(track) - set(opts)
+        if unknown:
+            raise ValueError(f"track: unknown keys {sorted(unknown)} (radius, patch, every)")
+        opts.update({k: int(v) for k, v in track.items()})
+    if opts["every"] < 1:
+        raise ValueError(f"track: every = {opts['every']} (must be >= 1)")
+    return opts
+
+
+class HandleTracker:
+    """Where each drag handle went, in feature space (ishap_drag_track): for every handle the offset k in
+    [-radius, radius]^3 voxels whose patch of the edited tap is nearest in L1 to the guidance tap's patch at the source.
+    Offsets are integer voxel offsets from the source; a handle's position is lattice(source, voxel, offset)."""
+
+    def __init__(self, device, W: int, ld: int, chmap, voxel: float, radius: int = 4, patch: int = 2):
+        self.device = th.device(device)
+        self.W, self.ld, self.voxel, self.R, self.rp = int(W), int(ld), float(voxel), int(radius), int(patch)
+        cm = np.asarray(chmap.detach().cpu() if th.is_tensor(chmap) else chmap).astype(np.int32).reshape(3, -1)
+        if cm.shape[1] < 1 or cm.min() < 0 or cm.max() >= self.ld:
+            raise ValueError(f"chmap must be [3][Cc >= 1] with tap channels in 0..{self.ld - 1}")
+        self.chmap = th.as_tensor(np.ascontiguousarray(cm)).to(self.device)
+        self.Cc = cm.shape[1]
+        self._L = _lib.lib()
+        if self.W < 2 or self.ld < 1 or self._L.ishap_drag_track_scratch_bytes(1, 1, self.R, self.rp, self.Cc) < 0:
+            raise ValueError(f"handle tracker: radius = {radius} (0..8), patch = {patch} (0..4), W = {W} (>= 2), ld = {ld}")
+        self.side = 2 * self.R + 1
+        self.sources = None
+
+    def setup(self, sources):
+        """sources: a list of E handle arrays [B_e, 3] (one per edit).  Allocates the per-call buffers; nothing is launched."""
+        src, _, offs = pack_handles(sources, sources)
+        self.E = len(offs) - 1
+        nbytes = int(self._L.ishap_drag_track_scratch_bytes(self.E, offs[-1], self.R, self.rp, self.Cc))
+        if nbytes < 0:
+            raise ValueError(f"handle tracker: {self.E} edits (1..32)")
+        self.sources, self.offsets = src.to(self.device), list(offs)
+        self._offs = (C.c_int * (self.E + 1))(*offs)
+        self.scratch = th.empty(nbytes, dtype=th.uint8, device=self.device)
+        self._chmap_ptr, self._src_ptr = self.chmap.data_ptr(), self.sources.data_ptr()
+        self._scratch_ptr, self._scratch_bytes = self.scratch.data_ptr(), nbytes
+        return self
+
+    @property
+    def handles(self) -> int:
+        return self.offsets[-1]
+
+    def run_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int, K_in, K_out, dist, dist0, volume=None):
+        """One tracking call on the current stream: edit [E][W*W][ld] fp16, guidance edit e at orig + e * orig_stride halfs;
+        K_in / K_out int32 [H, 3], dist / dist0 float32 [H], volume None or float32 [H, side^3], all on the device."""
+        self.run_raw(edit_ptr, orig_ptr, orig_stride, K_in.data_ptr(), K_out.data_ptr(), dist.data_ptr(), dist0.data_ptr(),
+                     _lib.ptr(volume))
+
+    def run_raw(self, edit_ptr: int, orig_ptr: int, orig_stride: int, k_in: int, k_out: int, dist: int, dist0: int, volume=None):
+        """run_ptr on device addresses (the guided loop's form: no tensor is made per step)."""
+        with th.cuda.device(self.device):
+            _lib.check(self._L.ishap_drag_track(edit_ptr, orig_ptr, int(orig_stride), self.W, self.ld, self.Cc, self._chmap_ptr,
+                                                self._src_ptr, self._offs, self.E, self.voxel, self.R, self.rp, k_in, k_out, dist, dist0,
+                                                volume, self._scratch_ptr, self._scratch_bytes, _lib.stream_ptr(self.device)))
+
+    def positions(self, offsets: th.Tensor) -> th.Tensor:
+        """lattice(source, voxel, K) in float32 (the product rounded, then the sum), for offsets [..., H, 3]."""
+        return self.sources + th.tensor(self.voxel, dtype=th.float32, device=self.device) * offsets.to(th.float32)
+
+    def _tap(self, t, lead):
+        if t.dtype != th.float16 or tuple(t.shape[-2:]) != (self.W * self.W, self.ld):
+            raise ValueError(f"taps are fp16 [..., {self.W * self.W}, {self.ld}], got {t.dtype} {tuple(t.shape)}")
+        t = t.to(self.device).contiguous()
+        if t.dim() == 2:
+            t = t[None]
+        if t.dim() != 3 or t.shape[0] not in lead:
+            raise ValueError(f"tap batch of {tuple(t.shape)} for {self.E} edits")
+        return t
+
+    def track_batch(self, edit_taps, orig_taps, sources, offsets=None, want_volume=False) -> List[Track]:
+        """E edits in one call.  edit_taps [E, W*W, ld]; orig_taps [E, W*W, ld] or one [W*W, ld] for all; sources: E handle
+        arrays; offsets: None (zeros) or E int arrays [B_e, 3], each handle's last offset.  One Track per edit."""
+        self.setup(sources)
+        edit, orig = self._tap(edit_taps, (self.E,)), self._tap(orig_taps, (1, self.E))
+        H = self.handles
+        if offsets is None:
+            K_in = th.zeros((H, 3), dtype=th.int32, device=self.device)
+        else:
+            K_in = th.cat([th.as_tensor(np.asarray(o.detach().cpu() if th.is_tensor(o) else o)).to(th.int32).reshape(-1, 3)
+                           for o in offsets]).to(self.device).contiguous()
+            if K_in.shape[0] != H:
+                raise ValueError(f"{K_in.shape[0]} offsets for {H} handles")
+        K_out = th.empty_like(K_in)
+        dist, dist0 = th.empty(H, dtype=th.float32, device=self.device), th.empty(H, dtype=th.float32, device=self.device)
+        vol = th.empty((H, self.side ** 3), dtype=th.float32, device=self.device) if want_volume else None
+        self.run_ptr(edit.data_ptr(), orig.data_ptr(), 0 if orig.shape[0] == 1 else orig[0].numel(), K_in, K_out, dist, dist0, vol)
+        pos = self.positions(K_out)
+        cut = lambda t, e: None if t is None else t[self.offsets[e]:self.offsets[e + 1]]      # noqa: E731
+        return [Track(cut(K_out, e), cut(pos, e), cut(dist, e), cut(dist0, e), cut(vol, e)) for e in range(self.E)]
+
+    def track(self, edit_tap, orig_tap, sources, offsets=None, want_volume=False) -> Track:
+        """One edit: taps [W*W, ld] fp16, sources [B, 3], offsets None or int [B, 3] -> Track(offsets int32 [B, 3], positions
+        float32 [B, 3], dist [B], dist0 [B], volume [B, side^3] or None)."""
+        return self.track_batch(edit_tap, orig_tap, [sources], None if offsets is None else [offsets], want_volume)[0]
+
+
+class _LoopTrack:
+    """The tracking of one guided loop: a device table of offsets, one row per tracked step behind a row of zeros, so that each
+    call reads the row before it and no step waits for the host."""
+
+    def __init__(self, tracker: HandleTracker, sources, steps_total: int, every: int):
+        self.tracker, self.every = tracker.setup(sources), every
+        rows = (steps_total + every - 1) // every
+        H, dev = tracker.handles, tracker.device
+        self.table = th.zeros((rows + 1, H, 3), dtype=th.int32, device=dev)
+        self.dist = th.zeros((rows, H), dtype=th.float32, device=dev)
+        self.dist0 = th.zeros((rows, H), dtype=th.float32, device=dev)
+        self.steps: List[int] = []
+        self._ptrs = (self.table.data_ptr(), self.dist.data_ptr(), self.dist0.data_ptr(), H)
+
+    def step(self, n: int, edit_ptr: int, orig_ptr: int, orig_stride: int):
+        if n % self.every:
+            return
+        r = len(self.steps)
+        table, dist, dist0, H = self._ptrs                 # rows r and r + 1 of the table, row r of the distances
+        self.tracker.run_raw(edit_ptr, orig_ptr, orig_stride, table + 12 * H * r, table + 12 * H * (r + 1), dist + 4 * H * r,
+                             dist0 + 4 * H * r)
+        self.steps.append(n)
+
+    def results(self) -> List[dict]:
+        """One dict per edit: steps (the loop's step numbers, 0 the first), offsets [rows, B, 3], positions, dist, dist0 [rows, B]."""
+        t, r = self.tracker, len(self.steps)
+        offs = self.table[1:r + 1].clone()
+        pos = t.positions(offs)
+        out = []
+        for e in range(t.E):
+            a, b = t.offsets[e], t.offsets[e + 1]
+            out.append({"steps": list(self.steps), "offsets": offs[:, a:b], "positions": pos[:, a:b],
+                        "dist": self.dist[:r, a:b].clone(), "dist0": self.dist0[:r, a:b].clone(), "radius": t.R, "patch": t.rp})
+        return out
+
+
 def synthesize_latent(model, diffusion, args=None, t1=None, t2=0, inter_latent_idx=None, inter_feat_idx=None, img=None,
                       calc_grad=False, **kwargs):
     """drag_utils.py:61-131 (no caller in the reference; kept for the call surface).  calc_grad=True keeps the autograd
@@ -446,6 +594,7 @@ class DragStuff:
         self.variance_noise = []
         self.feature_guidance: List[th.Tensor] = []     # fp16 NHWC taps [S*S, C] on the device
         self.last_losses: List[float] = []
+        self.last_track = None        # after an edit with track=...: dict of steps / offsets / positions / dist / dist0 (batch: a list)
         self._dk: Optional[DragKernels] = None
         self.step_noise = None        # optional callable i -> noise tensor (parity runs); default randn like the reference
         # batched edits (training_batch): set by update_latent_params_batch; None = edit variants of the single shape
@@ -557,7 +706,7 @@ class DragStuff:
         return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10, refine=refine)
 
     # ------------------------------------------------------------------ drag loop (:302-399)
-    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False):
+    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False, trk=None):
         """The guided loop of training() and training_batch(): a generator that yields the progress value after each step and
         returns (img, stop_time) -- the latent and the number of unguided steps left when train_flag stopped it (0: ran to
         the end).  `dk`: a DragKernels or BatchDragKernels after setup; `guidance[n]`: the guidance tap of the n-th step, edit e's
@@ -565,7 +714,8 @@ class DragStuff:
         p_sample_guidance takes it (a float, or a device tensor with one value per image).  last_losses gets one [images]
         tensor per step.
         `reuse_first` (training() only: `img` is a copy of self.w): the first step's forward comes from the snapshot of an earlier
-        edit of this shape when there is a valid one, and is saved as one otherwise."""
+        edit of this shape when there is a valid one, and is saved as one otherwise.
+        `trk`: None, or the _LoopTrack of a tracked edit: its call follows the loss's on the same stream and only reads the tap."""
         w_time = self.args.w_time
         overlap = _OVERLAP_TAIL if self.overlap_tail is None else self.overlap_tail
         reuse_first = reuse_first and _FIRST_STEP_REUSE and hasattr(self.model, "snapshot_restore")
@@ -584,6 +734,8 @@ class DragStuff:
 
             def loss_and_backward():          # needs the tap only
                 cot, scale2 = dk.loss_cotangent_ptr(self.model.tap_ptr(), origin.data_ptr(), orig_stride=stride, loss_out=slot)
+                if trk is not None:
+                    trk.step(w_time - 1 - i, self.model.tap_ptr(), origin.data_ptr(), stride)
                 got["grad"] = self.model.backward_input(cot, scale2)           # = img.grad of the reference (:384)
                 return got["grad"]
 
@@ -643,8 +795,33 @@ class DragStuff:
         return regions.plane_weights(keep=keep, free=free, W=width, keep_weight=keep_weight, free_weight=free_weight,
                                      dilate=region_dilate, device=self.device)
 
+    def _loop_track(self, topts, width, ch, sources):
+        """The tracking state of one guided loop, or None when tracking is off."""
+        if topts is None:
+            return None
+        tracker = HandleTracker(self.device, W=width, ld=ch, chmap=feat_channel_map(ch), voxel=self.voxel_size,
+                                radius=topts["radius"], patch=topts["patch"])
+        return _LoopTrack(tracker, sources, self.args.w_time, topts["every"])
+
+    def handle_error(self):
+        """How far the last tracked edit brought each handle: {"error": |last tracked position - target| in voxels [B],
+        "fraction": the share of the requested move covered, (position - source) . (target - source) / |target - source|^2 [B]
+        (1 where no move was requested)}; a list of such dicts after training_batch.  Raises if no tracked edit has run."""
+        if self.last_track is None:
+            raise RuntimeError("handle_error: no tracked edit has run (training(..., track=True))")
+        tracks = self.last_track if isinstance(self.last_track, list) else [self.last_track]
+        out = []
+        for tr, (src, tgt) in zip(tracks, self._track_ends):
+            if len(tr["steps"]) == 0:
+                raise RuntimeError("handle_error: the tracked edit stopped before its first tracked step")
+            pos, move = tr["positions"][-1], tgt - src
+            m2 = (move * move).sum(-1)
+            frac = th.where(m2 > 0, ((pos - src) * move).sum(-1) / m2.clamp_min(1e-30), th.ones_like(m2))
+            out.append({"error": (pos - tgt).norm(dim=-1) / self.voxel_size, "fraction": frac})
+        return out if isinstance(self.last_track, list) else out[0]
+
     def training(self, sources=None, targets=None, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
-                 region_dilate=0, weights=None):
+                 region_dilate=0, weights=None, track=None):
         """One drag edit of the loaded shape (drag_utils.py:302-399).  Every edit starts from self.w: from the second edit of a
         shape on, the first guided step's forward is restored from a snapshot instead of run (ISHAP_FIRST_STEP_REUSE=0: always
         run); results are bit-identical either way.
@@ -652,7 +829,11 @@ class DragStuff:
         the three planes get keep_weight (default 4: held harder) / free_weight (default 0: free to change) in the preservation
         term instead of 1, each shadow grown by region_dilate texels; keep overrides free.  weights: a ready [3, W, W] map
         instead (W the side of the tap), exclusive with keep and free.  All of them need cof > 0.  A plane texel stands for a
-        whole column through the shape, so a region constrains its three shadows, not only its own volume."""
+        whole column through the shape, so a region constrains its three shadows, not only its own volume.
+        track: None (off: no launch is added), True, or {"radius": R, "patch": rp, "every": m}: after every m-th step's loss the
+        handles are re-found in feature space (HandleTracker) without a host synchronisation; afterwards last_track holds the
+        tracks and handle_error() the distance of each handle's last position to its target.  The edit's results do not change."""
+        topts = track_options(track)
         if self.args.num_samples > 1:
             raise NotImplementedError("We can handle only one shape at each time!")
         ch, width = self.model.tap_shape(self.args.feat_layer)
@@ -665,13 +846,17 @@ class DragStuff:
                          loss_type=self.args.loss_type)
         dk.setup(self.sources, self.targets, cof, **({} if wmap is None else {"weights": wmap}))    # a plain edit: the call it always was
         self._dk = dk
+        trk = self._loop_track(topts, width, ch, [self.sources])
         # the regions change the loss, not the forward: the first-step snapshot depends on the latent, the timestep and the weights
         # of the model only, so _first_step_key does not hold them and an edit with regions reuses the snapshot of a plain one
-        img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), True)
+        img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), True,
+                                                      **({} if trk is None else {"trk": trk}))
+        if trk is not None:
+            self.last_track, self._track_ends = trk.results()[0], [(self.sources, self.targets)]
         self.mesh = self.get_mesh(img=img, t=stop_time)
 
     def training_part(self, part, rigid, handles=16, start=None, scale=600, cof=0.2, keep=None, keep_weight=4.0, free_weight=0.0,
-                      region_dilate=0):
+                      region_dilate=0, track=None):
         """A part edit: move `part` (a regions.Voxels, e.g. from regions.select_part) by `rigid` (a regions.Rigid).  The plan --
         regions.plan_part_edit: `handles` sources spread over the part from `start`, each one's target where the motion takes
         it, free = [the part, the part moved] -- is kept as self.part_plan, and the edit is the generator
@@ -679,11 +864,11 @@ class DragStuff:
         Each handle's lattice only translates; a rotation is carried by the handles' different displacements.  r1 stays as
         set_offset1 left it: plan.spacing / voxel_size, the handles' spacing in voxels, is the natural lattice radius to compare
         it with (lattices much smaller leave gaps between handles, much larger ones overlap and average the rotation away).
-        The free regions, like all regions, constrain their three shadows, not only their volume."""
+        The free regions, like all regions, constrain their three shadows, not only their volume.  track: as training()."""
         from . import regions
         self.part_plan = plan = regions.plan_part_edit(part, rigid, handles=handles, start=start)
         return self.training(plan.sources, plan.targets, scale=scale, cof=cof, keep=keep, free=plan.free, keep_weight=keep_weight,
-                             free_weight=free_weight, region_dilate=region_dilate)
+                             free_weight=free_weight, region_dilate=region_dilate, **({} if track is None else {"track": track}))
 
     # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
     def _check_edits(self, K: int):
@@ -728,7 +913,7 @@ class DragStuff:
         return self.meshes
 
     def training_batch(self, sources, targets, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
-                       region_dilate=0, weights=None):
+                       region_dilate=0, weights=None, track=None):
         """K drag edits in one guided loop (the generator of training(), same progress values).  sources / targets: lists of K
         handle arrays (their counts may differ); scale, cof: a float or K values.  keep, free, keep_weight, free_weight,
         region_dilate, weights: as training(), one value for every edit or a list of K (entries of keep / free / weights may be
@@ -740,7 +925,9 @@ class DragStuff:
         are bitwise those of a solo call; the loss scale of the fp16 backward is one power of two for the batch (exact for the
         linear backward).  Injected noise (step_noise -> [K, ...]) makes edit k repeat a solo run with noise k; drawn noise spans
         the batch and differs from a solo run's.
-        Every step runs its forward: the first-step snapshot of training() is neither used nor taken here."""
+        Every step runs its forward: the first-step snapshot of training() is neither used nor taken here.
+        track: as training(), one setting for all edits and one launch pair per tracked step; last_track is then a list of K."""
+        topts = track_options(track)
         if len(sources) != len(targets):
             raise ValueError(f"{len(sources)} source sets but {len(targets)} target sets: one of each per edit")
         K = len(sources)
@@ -767,8 +954,13 @@ class DragStuff:
                               loss_type=self.args.loss_type)
         dk.setup(sources, targets, cofs, **({} if all(w is None for w in wmaps) else {"weights": wmaps}))
         self._dk_batch = dk
+        trk = self._loop_track(topts, width, ch, sources)
         scales_dev = th.tensor(scales, dtype=th.float32, device=self.device)
-        img, stop_time = yield from self._guided_loop(img, dk, guidance, stride, scales, scales_dev)
+        img, stop_time = yield from self._guided_loop(img, dk, guidance, stride, scales, scales_dev,
+                                                      **({} if trk is None else {"trk": trk}))
+        if trk is not None:
+            self.last_track = trk.results()
+            self._track_ends = [(dk.sources[a:b], dk.targets[a:b]) for a, b in zip(dk.offsets[:-1], dk.offsets[1:])]
         self.get_meshes(img=img, t=stop_time)
 
     # ------------------------------------------------------------------ real shapes (:401-471, :552-566)

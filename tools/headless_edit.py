@@ -27,6 +27,13 @@ place it moves to are the free regions; --keep-* still apply.  The pictures show
 boxes.  Each handle's lattice only translates, so a rotation is approximated by the handles' different displacements; with
 synthetic weights nobody can judge how good the result looks.
 
+--track [R,rp,every] (default 4,2,1) re-finds every handle in feature space after every `every`-th guided step
+(DragStuff.training(track=...), HandleTracker: search radius R, patch radius rp, in voxels of the handle lattice), prints for each
+handle where it ended up -- offset in voxels, distance to its target in voxels, share of the requested move covered -- writes the
+table and the whole track to track.json next to the pictures, and marks each handle's last tracked position in after.png with a
+yellow sphere.  A handle that has not moved keeps its mark inside the red source sphere; with synthetic weights the features are
+noise and that is the usual outcome.
+
 --time instead measures the renderer alone (device events around `--repeat` calls after a warm-up, medians):
   the 256^3 sphere mesh (~300 k triangles of a few pixels each) at 1024 x 1024, and 2 picture-filling triangles at 1024 x 1024
   (the second shows that large triangles do not serialise on one lane), next to the bytes each call has to move
@@ -114,6 +121,32 @@ def part_of(a, volume):
     return part, rigid, frames
 
 
+TRACK_COLOUR = (1.0, 1.0, 0.0)       # yellow: a handle's last tracked position
+
+
+def track_of(a):
+    """--track -> the `track` keyword of DragStuff.training (None without it)"""
+    if a.track is None:
+        return None
+    R, rp, every = (int(v) for v in _csv(a.track, 3, "--track"))
+    return {"radius": R, "patch": rp, "every": every}
+
+
+def track_report(ds, sources, targets):
+    """the per-handle table of the last tracked edit (printed) and the JSON that goes next to the pictures"""
+    tr, err = ds.last_track, ds.handle_error()
+    last, pos = tr["offsets"][-1].cpu().tolist(), tr["positions"][-1].cpu().tolist()
+    rows = [{"handle": b, "source": [float(v) for v in sources[b]], "target": [float(v) for v in targets[b]], "offset_voxels": last[b],
+             "position": pos[b], "error_voxels": float(err["error"][b]), "fraction": float(err["fraction"][b]),
+             "dist": float(tr["dist"][-1, b]), "dist0": float(tr["dist0"][-1, b])} for b in range(len(last))]
+    print("handle  offset (voxels)      error (voxels)  covered   D(k*) / D(0)")
+    for r in rows:
+        print(f"{r['handle']:6d}  {str(r['offset_voxels']):19s}  {r['error_voxels']:14.2f}  {100 * r['fraction']:6.1f} %  "
+              f"{r['dist']:.4g} / {r['dist0']:.4g}")
+    return {"radius": tr["radius"], "patch": tr["patch"], "steps": tr["steps"], "voxel": ds.voxel_size, "handles": rows,
+            "offsets": tr["offsets"].cpu().tolist(), "dist": tr["dist"].cpu().tolist(), "dist0": tr["dist0"].cpu().tolist()}
+
+
 def changed_fraction(before, after, inside):
     """share of the voxels selected by `inside` (a bool grid) whose occupancy sign differs between two decoded volumes"""
     n = int(inside.sum())
@@ -123,7 +156,7 @@ def changed_fraction(before, after, inside):
 def edit(a):
     from ishapediting_amd import synthetic
     from ishapediting_amd.drag_utils import DragStuff, get_args
-    from ishapediting_amd.render import Camera, edit_parts, render_mesh, save_picture
+    from ishapediting_amd.render import Camera, edit_parts, marker_sphere, render_mesh, save_picture
     from ishapediting_amd.unet_spec import full_config
     dev = torch.device("cuda", 0)
     os.makedirs(a.out, exist_ok=True)
@@ -147,11 +180,13 @@ def edit(a):
     volume0 = ds.volume.clone()
     part_edit = part_of(a, volume0)
     report, part_report = {}, None
+    track = track_of(a)
+    tkw = {} if track is None else {"track": track}
     if part_edit is not None:      # handles and targets come from the part and its motion; the plan is made when the edit is created
         part, rigid, part_frames = part_edit
         frames = frames + part_frames
         final = ds.training_part(part, rigid, handles=a.handles, scale=a.scale, cof=a.cof, keep=keep or None, keep_weight=a.keep_weight,
-                                 free_weight=a.free_weight, region_dilate=a.region_dilate)
+                                 free_weight=a.free_weight, region_dilate=a.region_dilate, **tkw)
         plan = ds.part_plan
         sources, targets = plan.sources, plan.targets
         part_report = {"voxels": int(part.mask.sum()), "moved_voxels": int(plan.moved.mask.sum()), "handles": int(sources.shape[0]),
@@ -168,7 +203,7 @@ def edit(a):
         for pos, idx, d, px in picked:
             print(f"pick pixel {px}: vertex {idx} at {pos.tolist()}, depth {d:.6f}")
         final = ds.training(sources, targets, scale=a.scale, cof=a.cof, keep=keep or None, free=free or None,
-                            keep_weight=a.keep_weight, free_weight=a.free_weight, region_dilate=a.region_dilate)
+                            keep_weight=a.keep_weight, free_weight=a.free_weight, region_dilate=a.region_dilate, **tkw)
     save_picture(os.path.join(a.out, "before.png"), render_mesh(edit_parts(before, sources, targets, boxes=frames), cam, a.size, a.size))
     if named:                # the same edit without the regions first: what they change is the difference of the two runs
         for _ in ds.training(sources, targets, scale=a.scale, cof=a.cof):
@@ -186,9 +221,18 @@ def edit(a):
             print(f"{name}: {report[name]}")
     if a.refine is not None:
         ds.mesh.compute_vertex_normals()
-    save_picture(os.path.join(a.out, "after.png"), render_mesh(edit_parts(ds.mesh, sources, targets, boxes=frames), cam, a.size, a.size))
+    after = edit_parts(ds.mesh, sources, targets, boxes=frames)
+    tracked = None
+    if track is not None:
+        tracked = track_report(ds, np.asarray(sources), np.asarray(targets))
+        with open(os.path.join(a.out, "track.json"), "w") as fh:
+            json.dump(tracked, fh, indent=1)
+            fh.write("\n")
+        after += [(marker_sphere(np.asarray(r["position"], np.float64), radius=0.03), TRACK_COLOUR, False) for r in tracked["handles"]]
+    save_picture(os.path.join(a.out, "after.png"), render_mesh(after, cam, a.size, a.size))
     torch.cuda.synchronize()
-    print(json.dumps({"out": a.out, "handles": a.handles, "regions": report, "part": part_report, "before_triangles": int(before.triangles.shape[0]),
+    print(json.dumps({"out": a.out, "handles": a.handles, "regions": report, "part": part_report,
+                      "track": None if tracked is None else tracked["handles"], "before_triangles": int(before.triangles.shape[0]),
                       "after_triangles": int(ds.mesh.triangles.shape[0]), "camera": {"eye": list(cam.eye), "near": cam.near, "far": cam.far}}))
 
 
@@ -272,6 +316,8 @@ def main():
     p.add_argument("--keep-weight", type=float, default=4.0)
     p.add_argument("--free-weight", type=float, default=0.0)
     p.add_argument("--region-dilate", type=int, default=0)
+    p.add_argument("--track", nargs="?", const="4,2,1", default=None, metavar="R,RP,EVERY",
+                   help="track the handles in feature space (search radius, patch radius, every n-th step; default 4,2,1)")
     p.add_argument("--time", action="store_true", help="measure the renderer instead of running an edit")
     p.add_argument("--time_out", default=None, help="where --time writes its JSON (default profiles/render_times.json)")
     p.add_argument("--warmup", type=int, default=10)
