@@ -3,16 +3,11 @@
 // (l2reg / tvreg: axisnetworks.py:564-575), gradient on the three planes only, the MLP frozen.
 //
 // triplane_fit_kernel: forward AND backward of the decoder (axisnetworks.py:526-562) for the data batch and the random pairs
-// in one launch, every matrix product on the exact-fp32 matrix cores (v_mfma_f32_32x32x2_f32).  One wave owns a 32-point
-// tile: lane & 31 = point, lane >> 5 = which of the two K slots of an MFMA step it feeds.  As in decode.hip the weights
-// are the A operand and the activations the B operand, so a layer's accumulators ARE the next layer's operands
-// (register r of lane-half h = neuron kmap(r, h) of its 32-block).  One fp32 copy of W1 and W2 sits in LDS; the forward
-// reads rows (W[out][in], ds_read_b128 of 4 consecutive inputs), the backward's W^T products read the same arrays with the
-// indices swapped (32 consecutive outputs per lane half, ds_read_b32).  What the backward needs stays in registers: the 64
-// Fourier phases (sin / cos are recomputed) and the two ReLU masks as 64-bit words.  The last backward product (d features
-// = _B . d phases) swaps the operands so that its accumulator is [point][channel]: register r then holds, across the 32
-// lanes of a half, the 32 channels of ONE point -- each bilinear tap's gradient is one global_atomic_add_f32 instruction
-// over two 128-byte texel rows (cdna_hip_programming.md, Guideline 12).
+// in one launch on the fp32-MFMA tile scheme of decode_mlp.h (one wave owns a 32-point tile; mlp_forward / mlp_backward
+// with FUSED = true).  Between a tile's forward and its backward only the two ReLU masks and the logit stay in registers.
+// The backward ends in the feature cotangent as [point][channel]: register r holds, across the 32 lanes of a half, the 32
+// channels of ONE point -- each bilinear tap's gradient is one global_atomic_add_f32 instruction over two 128-byte texel
+// rows (cdna_hip_programming.md, Guideline 12).
 // A random pair (r, r + delta) is one work item: the same lane of two tiles in the same wave, so the pair's difference and
 // its cotangents +-2 * 0.3 * d / N never leave registers.  Float atomics: not bitwise repeatable (as decode_bwd.hip).
 //
@@ -21,27 +16,15 @@
 // the regulariser gradients 0.001 e / |e| + 0.01 D^T (D e) / |D e| are added to dplanes and torch's Adam step
 // (torch/optim/adam.py, single-tensor form) is applied into a second planes buffer; dplanes is left zeroed.
 // Given the same dplanes these two launches are bitwise repeatable.
-#include "decode.h"
+#include "decode_mlp.h"
 
-#define FLD 132   // row stride (floats) of W1 / W2 in LDS: 528 B = 16 B mod 256 -> conflict-free ds_read_b128
-#define BLD 68    // row stride (floats) of _B [32][64] in LDS: 272 B
 #define FIT_WAVES 4
 
 namespace {
 
-// this lane's base pointers into the LDS images; every read below is base + a compile-time offset (< 64 KB), which the
-// ds_read immediate absorbs (index arithmetic on the array start instead makes the compiler keep hundreds of addresses)
-struct FitLds {
-  const float *W1r, *W2r;   // row reads W[32qo + l31][k + 4h]
-  const float *W1c, *W2c;   // column reads W[k + 4h][32qo + l31]
-  const float *Bf, *Bb;     // _B[c + 4h][32q + l31] and _B[l31][k + 4h]
-  const float *b1, *b2, *w3;   // + 4h
-};
-
-// what the backward of one 32-point tile keeps in registers between its forward and its backward (the phases are
-// recomputed: 32 of the tile's 1088 MFMAs)
+// what the backward of one 32-point tile keeps in registers between its forward and its backward
 struct FitTile {
-  unsigned long long m1, m2;     // ReLU masks: bit 16q + r = neuron 32q + kmap(r, h)
+  unsigned long long m1, m2;     // ReLU masks (mlp_forward)
   float z;                       // logit of this lane's point
 };
 
@@ -60,202 +43,11 @@ __device__ __forceinline__ void fit_point(const FitArgs& a, int kind, long long 
   }
 }
 
-// bilinear taps of plane p (xy, yz, xz; align_corners, zero padding: axisnetworks.py:537-551): texel index or -1, weight
-__device__ __forceinline__ void fit_taps(int p, float cx, float cy, float cz, int S, int (&tex)[4], float (&w)[4]) {
-  const float u = (p == 1) ? cy : cx;
-  const float v = (p == 0) ? cy : cz;
-  const float ix = ((u + 1.f) / 2.f) * (float)(S - 1);
-  const float iy = ((v + 1.f) / 2.f) * (float)(S - 1);
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float wx1 = ix - fx, wx0 = (fx + 1.f) - ix;
-  const float wy1 = iy - fy, wy0 = (fy + 1.f) - iy;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {     // nw, ne, sw, se
-    const int xx = x0 + (q & 1), yy = y0 + (q >> 1);
-    w[q] = ((q & 1) ? wx1 : wx0) * ((q >> 1) ? wy1 : wy0);
-    tex[q] = (xx >= 0 && xx < S && yy >= 0 && yy < S) ? (p * S + yy) * S + xx : -1;
-  }
-}
-
-// features (three bilinear samples, summed) and phases y = f @ _B of this lane's point: y[q][r] = phase 32q + kmap(r, h)
-__device__ __forceinline__ void fit_phases(const FitArgs& a, const FitLds& L, float cx, float cy, float cz, int l31, int h,
-                                           f32x16 (&y)[2]) {
-  // ---- features: this lane's 16 channels {8g+4h+e}, summed over the three planes ----
-  f32x4 f[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) f[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    int tex[4];
-    float w[4];
-    fit_taps(p, cx, cy, cz, a.S, tex, w);
-    f32x4 acc[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (tex[q] >= 0) {
-        const float* tp = a.planes + (long long)tex[q] * 32 + 4 * h;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] += w[q] * *reinterpret_cast<const f32x4*>(tp + 8 * g);
-      }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) f[g] += acc[g];
-  }
-  // ---- phases y = f @ _B: A = _B^T rows (32q + i), K = channels ----
-  // (the K order of this product and of the two layers below -- 32-blocks, within a block the pairs (8g + e, 8g + 4 + e) of one
-  // K = 2 instruction -- is restated in tests/decoder_ref.py:_fit_order for the kink filter's error bound: change both together)
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) y[q][r] = 0.f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        y[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.Bf[(8 * g + e) * BLD + 32 * q], f[g][e], y[q], 0, 0, 0);
-  }
-}
-
-__device__ __forceinline__ void fit_forward(const FitArgs& a, const FitLds& L, float b3, float cx, float cy, float cz, int l31,
-                                            int h, FitTile& t) {
-  const float two_pi = 6.2831855f;      // float32(2*np.pi), axisnetworks.py:89
-  f32x16 y[2];
-  fit_phases(a, L, cx, cy, cz, l31, h, y);
-  // ---- Fourier features: blocks 0,1 = sin, 2,3 = cos ----
-  f32x16 x1[4];
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float s, c;
-      sincos_cw(two_pi * y[q][r], s, c);
-      x1[q][r] = s;
-      x1[2 + q][r] = c;
-    }
-  // ---- layer 1 ----
-  f32x16 x2[4];
-  t.m1 = 0ull;
-#pragma unroll
-  for (int qo = 0; qo < 4; ++qo) {
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(L.W1r + 32 * qo * FLD + 32 * q + 8 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[e], x1[q][4 * g + e], acc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);      // keep the weight reads next to their MFMAs (hoisted, they spill)
-      }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float v = acc[r] + L.b1[32 * qo + kmap(r, 0)];
-      if (v > 0.f) t.m1 |= 1ull << (16 * qo + r);
-      x2[qo][r] = fmaxf(v, 0.f);
-    }
-  }
-  // ---- layer 2 and the output layer ----
-  float partial = 0.f;
-  t.m2 = 0ull;
-#pragma unroll
-  for (int qo = 0; qo < 4; ++qo) {
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(L.W2r + 32 * qo * FLD + 32 * q + 8 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[e], x2[q][4 * g + e], acc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int n = 32 * qo + kmap(r, 0);
-      const float v = acc[r] + L.b2[n];
-      if (v > 0.f) {
-        t.m2 |= 1ull << (16 * qo + r);
-        partial += L.w3[n] * v;
-      }
-    }
-  }
-  partial += __shfl_xor(partial, 32);
-  t.z = partial + b3;
-}
-
 // dz: d loss / d logit of this lane's point (0 for padding lanes).  Scatters d loss / d planes with float atomics.
-__device__ __forceinline__ void fit_backward(const FitArgs& a, const FitLds& L, const FitTile& t, float dz, int kind,
+__device__ __forceinline__ void fit_backward(const FitArgs& a, const MlpLds& L, const FitTile& t, float dz, int kind,
                                              long long tile0, long long n, float cx, float cy, float cz, int l31, int h) {
-  const float two_pi = 6.2831855f;
-  // ---- d h1 = W2^T (w3 * dz * relu'(h2)), masked by relu'(h1) ----
-  f32x16 g1[4];
-#pragma unroll
-  for (int qo = 0; qo < 4; ++qo) {
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 w3v = *reinterpret_cast<const f32x4*>(L.w3 + 32 * q + 8 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          const float bv = ((t.m2 >> (16 * q + r)) & 1ull) ? w3v[e] * dz : 0.f;
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(L.W2c[(32 * q + kmap(r, 0)) * FLD + 32 * qo], bv, acc, 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) g1[qo][r] = ((t.m1 >> (16 * qo + r)) & 1ull) ? acc[r] : 0.f;
-  }
-  // ---- d Fourier features = W1^T g1 ----
-  f32x16 dff[4];
-#pragma unroll
-  for (int qo = 0; qo < 4; ++qo) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dff[qo][r] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          dff[qo] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.W1c[(32 * q + 8 * g + e) * FLD + 32 * qo],
-                                                         g1[q][4 * g + e], dff[qo], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-  }
-  // ---- d phases: 2 pi (d sin * cos - d cos * sin) ----
-  f32x16 y[2], dy[2];
-  fit_phases(a, L, cx, cy, cz, l31, h, y);
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float s, c;
-      sincos_cw(two_pi * y[q][r], s, c);
-      dy[q][r] = two_pi * (dff[q][r] * c - dff[2 + q][r] * s);
-    }
-  // ---- d features^T [point][channel] = dy^T _B^T: A = dy (point rows), B = _B rows (channel columns) ----
   f32x16 df;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) df[r] = 0.f;
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(L.Bb + 32 * q + 8 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) df = __builtin_amdgcn_mfma_f32_32x32x2f32(dy[q][4 * g + e], bv[e], df, 0, 0, 0);
-    }
+  mlp_backward<true>(a.planes, a.S, L, t.m1, t.m2, dz, cx, cy, cz, h, df);
   // ---- scatter: register r = channel l31 of point kmap(r, h); one instruction = two 128-byte texel rows ----
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -266,11 +58,11 @@ __device__ __forceinline__ void fit_backward(const FitArgs& a, const FitLds& L, 
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
         int tex[4];
-        float w[4];
-        fit_taps(p, px, py, pz, a.S, tex, w);
+        float wx[2], wy[2];
+        mlp_cell(p, px, py, pz, a.S, tex, wx, wy);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          if (tex[q] >= 0) atomicAdd(a.dplanes + (long long)tex[q] * 32 + l31, w[q] * df[r]);
+          if (tex[q] >= 0) atomicAdd(a.dplanes + (long long)tex[q] * 32 + l31, (wx[q & 1] * wy[q >> 1]) * df[r]);
       }
     }
   }
@@ -280,25 +72,10 @@ __device__ __forceinline__ void fit_backward(const FitArgs& a, const FitLds& L, 
 
 __global__ __launch_bounds__(64 * FIT_WAVES) void triplane_fit_kernel(FitArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* sW1 = lds;                       // [128][FLD] W1[out][in]
-  float* sW2 = sW1 + 128 * FLD;
-  float* sB = sW2 + 128 * FLD;            // [32][BLD]  _B[channel][phase]
-  float* sb1 = sB + 32 * BLD;
-  float* sb2 = sb1 + 128;
-  float* sw3 = sb2 + 128;
   const int tid = threadIdx.x;
-  for (int i = tid; i < 128 * 128; i += 64 * FIT_WAVES) {
-    const int r = i >> 7, k = i & 127;
-    sW1[r * FLD + k] = a.W1[i];
-    sW2[r * FLD + k] = a.W2[i];
-  }
-  for (int i = tid; i < 32 * 64; i += 64 * FIT_WAVES) sB[(i >> 6) * BLD + (i & 63)] = a.B[i];
-  if (tid < 128) { sb1[tid] = a.b1[tid]; sb2[tid] = a.b2[tid]; sw3[tid] = a.w3[tid]; }
-  __syncthreads();
+  const MlpLds L = mlp_fill_lds<64 * FIT_WAVES>(a, lds, tid);
   const int lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
-  const FitLds L{sW1 + l31 * FLD + 4 * h, sW2 + l31 * FLD + 4 * h, sW1 + 4 * h * FLD + l31, sW2 + 4 * h * FLD + l31,
-                 sB + 4 * h * BLD + l31, sB + l31 * BLD + 4 * h, sb1 + 4 * h, sb2 + 4 * h, sw3 + 4 * h};
   const float b3 = a.b3[0];
   const long long npair = (a.nrand + 31) / 32, ndata = (a.nbatch + 31) / 32;
   float bce_sum = 0.f, mse_sum = 0.f;
@@ -319,7 +96,7 @@ __global__ __launch_bounds__(64 * FIT_WAVES) void triplane_fit_kernel(FitArgs a)
       float cx, cy, cz;
       fit_point(a, pair ? 1 + k : 0, ii, cx, cy, cz);
       FitTile t;
-      fit_forward(a, L, b3, cx, cy, cz, l31, h, t);
+      mlp_forward<true>(a.planes, a.S, L, b3, cx, cy, cz, h, t.m1, t.m2, t.z);
       if (k == 0) ta = t; else tb = t;
     }
     float dza, dzb = 0.f;
@@ -356,11 +133,10 @@ __global__ __launch_bounds__(64 * FIT_WAVES) void triplane_fit_kernel(FitArgs a)
 int triplane_fit_loss_grad_launch(const FitArgs& a, hipStream_t s) {
   ISHAP_REQUIRE(a.nbatch >= 0 && a.nrand >= 0 && a.nbatch + a.nrand > 0, "no points");
   ISHAP_REQUIRE(a.S >= 2, "triplane fit_loss_grad: plane size");
-  const size_t smem = (size_t)(2 * 128 * FLD + 32 * BLD + 3 * 128) * sizeof(float);
-  ISHAP_TRY(ishap_set_max_lds((const void*)triplane_fit_kernel, (int)smem));
+  ISHAP_TRY(ishap_set_max_lds((const void*)triplane_fit_kernel, (int)MLP_SMEM));
   const long long items = (a.nrand + 31) / 32 + (a.nbatch + 31) / 32;
   const int blocks = (int)std::min<long long>((items + FIT_WAVES - 1) / FIT_WAVES, 256);
-  hipLaunchKernelGGL(triplane_fit_kernel, dim3(blocks), dim3(64 * FIT_WAVES), smem, s, a);
+  hipLaunchKernelGGL(triplane_fit_kernel, dim3(blocks), dim3(64 * FIT_WAVES), MLP_SMEM, s, a);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }

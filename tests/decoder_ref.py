@@ -1,4 +1,4 @@
-"""The triplane decoder (csrc/decode.hip, decode_bwd.hip, decode_fit.hip) restated in float64 on the kernels' fp32 inputs, with
+"""The triplane decoder (csrc/decode.hip, decode_bwd.hip, decode_fit.hip on decode_mlp.h) restated in float64 on the kernels' fp32 inputs, with
 the per-element error bounds the GPU oracle (tests/test_gpu_decoder_oracle.py) holds the kernels to.  Held to what the project
 already trusts (oracle/ref_cpu.py, golden g6_decoder, tests/triplane_opt_ref.py) by tests/test_decoder_ref_host.py.
 
@@ -57,7 +57,7 @@ Kinks.  ReLU' is discontinuous, so backward inputs keep away from it: a point is
 further from 0 than 10 x the unit's forward error bound IN THE BACKWARD KERNELS (exact-fp32 products, software sin / cos):
 the same local errors with SIN_SOFT = 2^-22 for sin / cos and, for the phases and the layers, the running error of an fp32 fma
 chain sum_k half_ulp(partial sum_k) (<= u sum_k |partial sum_k|), the largest over the summation orders the two kernels use (decode_bwd.hip: bias first, k
-ascending; decode_fit.hip: 32-blocks, within a block the pairs (8g + e, 8g + 4 + e) of one K = 2 matrix instruction, bias last),
+ascending; decode_mlp.h: 32-blocks, within a block the pairs (8g + e, 8g + 4 + e) of one K = 2 matrix instruction, bias last),
 each carried to the unit by the absolute value of the per-point derivative d pre / d (that quantity).
 """
 from types import SimpleNamespace
@@ -286,7 +286,7 @@ def forward_bound(net, planes, fw, sin_abs=SIN_ABS, local=split_local_error):
 
 # ----------------------------------------------------------------------------------------------------------- kink filter
 def _fit_order(blocks):
-    """decode_fit.hip's order inside a product of K = 32 * blocks: k = 32 q + 8 g + e and + 4 (the two K slots of one
+    """decode_mlp.h's order (the fit and field kernels) inside a product of K = 32 * blocks: k = 32 q + 8 g + e and + 4 (the two K slots of one
     v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain), either first"""
     a, b = [], []
     for q in range(blocks):
@@ -306,7 +306,7 @@ def _half_ulp(s):
 
 def _chain_error(W, x, bias, chunk=128):
     """sum_k half_ulp(partial sum_k) of pre = W x + bias as an fp32 fma chain: the largest over decode_bwd.hip's order (bias
-    first, k ascending) and decode_fit.hip's (its k order, bias last).  x [N,K], W [out,K] -> [N,out]"""
+    first, k ascending) and decode_mlp.h's (its k order, bias last).  x [N,K], W [out,K] -> [N,out]"""
     oa, ob = _fit_order(W.shape[1] // 32)
     out = np.zeros((x.shape[0], W.shape[0]))
     for i in range(0, x.shape[0], chunk):

@@ -1,4 +1,4 @@
-"""The decoder's field in space (csrc/decode_field.hip) restated in float64 on top of tests/decoder_ref.py: the analytic
+"""The decoder's field in space (csrc/decode_field.hip on decode_mlp.h) restated in float64 on top of tests/decoder_ref.py: the analytic
 d logit / d coordinate, the level-set projection, and the bounds tests/test_gpu_field.py holds the kernels to.  Held to torch
 autograd, to a central difference and to a list of mutations by tests/test_field_ref_host.py.
 
@@ -30,7 +30,7 @@ Filter.  A gradient is compared where decoder_ref.away_from_kinks holds (ReLU' j
 further than d_ix = 2 u |ix| from a cell boundary (the slopes jump).  Everywhere else the logit is still compared and the
 gradient must be finite.
 
-Logits.  decoder_ref.forward_bound with SIN_SOFT (decode.h's sincos_cw, as decode_fit.hip).  Its layer term is written for
+Logits.  decoder_ref.forward_bound with SIN_SOFT (decode.h's sincos_cw; decode_mlp.h's mlp_forward, which the fit shares).  Its layer term is written for
 decode.hip's split products; it covers this kernel's exact-fp32 products too: a K = 2 matrix instruction is a k-ordered
 fma pair, so a layer is a 128-step fma chain whose error is at most u sum_k |partial sum_k|, and inside K step s of 16 every
 partial sum is at most |C_in(s)| + sum_step |w| |x|: at most 16 u sum_s (|C_in(s)| + sum_step |w| |x|), a third of the

@@ -1,4 +1,4 @@
-"""Code-object metadata of the decoder's field kernels (csrc/decode_field.hip) through tools/kernel_meta.py, no GPU needed:
+"""Code-object metadata of the decoder's field kernels (csrc/decode_field.hip, the MLP in csrc/decode_mlp.h) through tools/kernel_meta.py, no GPU needed:
 both must keep everything in registers.  They hold the state of a forward AND a backward of a 32-point tile; a private segment
 would mean that part of it went to scratch memory."""
 import os

@@ -10,6 +10,8 @@ anywhere.  tests/test_host_cpu.py holds the hot kernels to zero scratch with thi
 
     python tools/kernel_meta.py [path/to/libishap_hip.so] [name substring]
     python tools/kernel_meta.py --diff A.so B.so      # one line per kernel whose code or metadata differs; exit status 1 if any
+    python tools/kernel_meta.py --diff A.so B.so --ops    # ... and, under each, the metadata fields and the opcodes whose counts
+                                                          # differ, as A -> B (llvm-objdump -d of the extracted code objects)
 """
 import os
 import struct
@@ -113,8 +115,35 @@ def kernel_code(lib_path: str):
     return out
 
 
-def diff(lib_a: str, lib_b: str) -> int:
+def opcodes(lib_path: str):
+    """{kernel symbol: Counter of instruction mnemonics}, from llvm-objdump -d of every gfx950 code object of the library
+    (two kernels of one internal-linkage name are counted together)"""
+    import collections
+    import re
+    import subprocess
+    import tempfile
+    out = {}
+    for triple, elf in _code_objects(open(lib_path, "rb").read()):
+        if "gfx950" not in triple:
+            continue
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(elf)
+            f.flush()
+            txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", "--no-show-raw-insn", f.name],
+                                 capture_output=True, text=True, check=True).stdout
+        cur = None
+        for line in txt.splitlines():
+            m = re.match(r"[0-9a-f]+ <(.+)>:$", line)
+            if m:
+                cur = out.setdefault(m.group(1), collections.Counter())
+            elif cur is not None and re.match(r"\s+[a-z_]", line):
+                cur[line.split()[0]] += 1
+    return out
+
+
+def diff(lib_a: str, lib_b: str, ops: bool = False) -> int:
     a, b = kernel_code(lib_a), kernel_code(lib_b)
+    oa, ob = (opcodes(lib_a), opcodes(lib_b)) if ops else ({}, {})
     dm = demangle(sorted(set(a) | set(b)))
     bad = 0
     for n in sorted(set(a) | set(b), key=lambda n: dm[n]):
@@ -130,6 +159,14 @@ def diff(lib_a: str, lib_b: str) -> int:
         if what:
             bad += 1
             print(f"DIFF {short}: {what}")
+            if "metadata" in what:
+                for x, y in zip(a[n], b[n]):
+                    print("    " + ", ".join(f"{m[1:]} {p} -> {q}" for m, p, q in zip(META_KEYS, x[0], y[0]) if p != q))
+            if ops and "code" in what:
+                ca, cb = oa.get(n, {}), ob.get(n, {})
+                for op in sorted(set(ca) | set(cb)):
+                    if ca.get(op, 0) != cb.get(op, 0):
+                        print(f"    {op:28s} {ca.get(op, 0)} -> {cb.get(op, 0)}")
     na, nb = sum(map(len, a.values())), sum(map(len, b.values()))
     print(f"{na} kernels, {sum(len(c) for v in a.values() for _, c in v)} bytes of kernel code in {lib_a}")
     print(f"{nb} kernels, {sum(len(c) for v in b.values() for _, c in v)} bytes of kernel code in {lib_b}")
@@ -147,8 +184,8 @@ def demangle(names):
 
 
 def main():
-    if len(sys.argv) == 4 and sys.argv[1] == "--diff":
-        sys.exit(diff(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) in (4, 5) and sys.argv[1] == "--diff" and sys.argv[4:] in ([], ["--ops"]):
+        sys.exit(diff(sys.argv[2], sys.argv[3], ops=len(sys.argv) == 5))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = sys.argv[1] if len(sys.argv) > 1 and os.path.exists(sys.argv[1]) else os.path.join(root, "ishapediting_amd", "libishap_hip.so")
     pat = sys.argv[-1] if len(sys.argv) > 1 and not os.path.exists(sys.argv[-1]) else ""
