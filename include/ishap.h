@@ -56,7 +56,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * 18 since the decoder's field in space (ishap_triplane_field_grad, ishap_triplane_project); 19 since
                             * the part edits (ishap_region_select, ishap_region_handles, ishap_region_handles_scratch_bytes,
                             * ishap_region_transform); 20 since ishap_unet_block_grad; 21 since the handle
-                            * tracking (ishap_drag_track, ishap_drag_track_scratch_bytes) */
+                            * tracking (ishap_drag_track, ishap_drag_track_scratch_bytes); 22 since the closed-loop drag
+                            * (ishap_drag_retarget, ishap_drag_batch_retarget, ishap_drag_batch_retarget_each) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -423,6 +424,32 @@ int ishap_drag_track(const void* edit_nhwc_f16, const void* orig_nhwc_f16, long 
                      const int* chmap, const float* sources, const int* handle_offsets, int E, float voxel, int R, int rp,
                      const int* K_in, int* K_out, float* dist, float* dist0, float* volume, void* scratch, long long scratch_bytes,
                      void* stream);
+/* ---------------------------------------------------------- closed-loop drag (ABI 22; csrc/retarget.hip)
+ * Re-aim the drag loss at the tracked handles, once per tracked step.  For handle b of edit e, with K[b] its tracked integer voxel
+ * offset from the source (ishap_drag_track's K_out; zeros before the first step), in double with contraction off, order x, y, z:
+ *   T = (final_target - source) / voxel,  rem = T - K,  d = |rem|
+ *   goal = final_target (a bit copy)                               if d <= step
+ *        = (float)(source + voxel * (K + step * rem / d))          otherwise
+ *   remaining[b] = (float)d,  arrived[b] = d <= arrive,  done[e] = every handle of edit e has arrived
+ * and the call rebuilds what ishap_drag_batch_setup derives from its targets as if it had been given targets = goals: `touched`
+ * (both bits) and the mask counts.  The fixed-point scatter buffer, the loss sums (every loss call leaves both zero) and
+ * chan_weight (independent of the handles) are not touched, so a loss call may follow at once.  With step = +inf the goals are the
+ * final targets bit for bit.
+ *   a: the struct of the drag calls on the buffers ishap_drag_batch_setup prepared; a->targets is the GOALS buffer, device
+ *      float[Btot][3], WRITTEN by this call and read by the loss calls that follow; it must not be final_targets
+ *   final_targets device float[Btot][3]; K device int[Btot][3]; step > 0 (may be +inf), arrive >= 0, in voxels
+ *   remaining device float[Btot]; arrived device int[Btot]; done device int[E]
+ * One launch of E workgroups, 3*W*W bytes of LDS each, no atomics on global memory and no memset: results are bitwise repeatable
+ * and an edit's do not depend on the edits beside it.  A null pointer, a step that is not > 0, an arrive that is not >= 0 (NaN
+ * fails both), 3*W*W > 65536 and everything the drag calls require are errors before any launch. */
+int ishap_drag_batch_retarget(const ishap_drag_batch_args* a, const float* final_targets, const int* K, float step, float arrive,
+                              float* remaining, int* arrived, int* done, void* stream);
+/* the same with one lead and one arrival radius per edit: steps, arrives HOST float[E] */
+int ishap_drag_batch_retarget_each(const ishap_drag_batch_args* a, const float* final_targets, const int* K, const float* steps,
+                                   const float* arrives, float* remaining, int* arrived, int* done, void* stream);
+/* one edit: the E = 1 call of the same kernel on the caller's own buffers (done: device int[1]) */
+int ishap_drag_retarget(const ishap_drag_args* a, const float* final_targets, const int* K, float step, float arrive,
+                        float* remaining, int* arrived, int* done, void* stream);
 /* ---------------------------------------------------------- region-constrained edits (ABI 17; csrc/regions.hip)
  * The weight map of the drag loss's mask term from 3-D regions in the coordinates handles use, [-1, 1]^3.  A region is a union
  * of primitives and one voxel grid; `keep` must not move, `free` may.  Its SHADOW on plane p (axes as the drag loss: plane 0

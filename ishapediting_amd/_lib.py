@@ -156,6 +156,12 @@ SYMBOLS = {
     "ishap_drag_track": (C.c_int, [c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, c_void_p, c_void_p,
                                    C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, C.c_longlong, c_void_p]),
+    "ishap_drag_retarget": (C.c_int, [C.POINTER(DragArgsC), c_void_p, c_void_p, C.c_float, C.c_float, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "ishap_drag_batch_retarget": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, C.c_float, C.c_float, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
+    "ishap_drag_batch_retarget_each": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, C.POINTER(C.c_float),
+                                                 C.POINTER(C.c_float), c_void_p, c_void_p, c_void_p, c_void_p]),
     "ishap_region_plane_weights_scratch_bytes": (C.c_longlong, [C.c_int]),
     "ishap_region_plane_weights": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                              c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
@@ -266,9 +272,10 @@ def lib():
         # 17: the weights fields of DragArgsC / DragBatchArgsC, ishap_region_plane_weights;
         # 18: ishap_triplane_field_grad / ishap_triplane_project;
         # 19: ishap_region_select / ishap_region_handles / ishap_region_handles_scratch_bytes / ishap_region_transform;
-        # 20: ishap_unet_block_grad; 21: ishap_drag_track / ishap_drag_track_scratch_bytes
-        if l.ishap_version() < 21:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 21): rebuild with `python -m ishapediting_amd.build`")
+        # 20: ishap_unet_block_grad; 21: ishap_drag_track / ishap_drag_track_scratch_bytes;
+        # 22: ishap_drag_retarget / ishap_drag_batch_retarget / ishap_drag_batch_retarget_each
+        if l.ishap_version() < 22:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 22): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

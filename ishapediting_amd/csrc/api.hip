@@ -5,6 +5,7 @@
 #include "decode.h"
 #include "drag.h"
 #include "track.h"
+#include "retarget.h"
 #include "regions.h"
 #include "render.h"
 
@@ -369,6 +370,44 @@ int ishap_drag_track(const void* edit, const void* orig, long long orig_stride, 
   ISHAP_REQUIRE(scratch_bytes >= need, "drag track: scratch smaller than ishap_drag_track_scratch_bytes(E, Btot, R, rp, Cc)");
   ISHAP_REQUIRE(((unsigned long long)scratch & 15ull) == 0, "drag track: scratch must be 16-byte aligned");
   return track_launch(t, (hipStream_t)stream);
+}
+
+// ---- closed-loop drag (csrc/retarget.hip): the arguments a drag call does not already check are checked here and in
+// drag_retarget_launch, before anything is launched.  `a->targets` is the goals buffer the call writes.
+static int retarget_call(DragBatchArgs& d, const float* final_targets, const int* K, const float* steps, const float* arrives,
+                         float step, float arrive, float* remaining, int* arrived, int* done, void* stream) {
+  RetargetArgs q;
+  q.final_targets = final_targets; q.K = K; q.goals = const_cast<float*>(d.base.targets);
+  q.remaining = remaining; q.arrived = arrived; q.done = done;
+  for (int e = 0; e < d.E; ++e) { q.step[e] = steps ? steps[e] : step; q.arrive[e] = arrives ? arrives[e] : arrive; }
+  return drag_retarget_launch(d, q, (hipStream_t)stream);
+}
+
+int ishap_drag_retarget(const ishap_drag_args* a, const float* final_targets, const int* K, float step, float arrive,
+                        float* remaining, int* arrived, int* done, void* stream) {
+  ISHAP_REQUIRE(a && final_targets && K && remaining && arrived && done, "null argument");
+  ISHAP_REQUIRE(a->W > 1 && 3ll * a->W * a->W <= RETARGET_LDS_BYTES, "drag retarget: 3*W*W must not exceed 65536 (the LDS bitmaps)");
+  DragBatchArgs d;
+  ISHAP_TRY(fill_drag(a, d));
+  return retarget_call(d, final_targets, K, nullptr, nullptr, step, arrive, remaining, arrived, done, stream);
+}
+
+int ishap_drag_batch_retarget(const ishap_drag_batch_args* a, const float* final_targets, const int* K, float step, float arrive,
+                              float* remaining, int* arrived, int* done, void* stream) {
+  ISHAP_REQUIRE(a && final_targets && K && remaining && arrived && done, "null argument");
+  ISHAP_REQUIRE(a->W > 1 && 3ll * a->W * a->W <= RETARGET_LDS_BYTES, "drag retarget: 3*W*W must not exceed 65536 (the LDS bitmaps)");
+  DragBatchArgs d;
+  ISHAP_TRY(fill_drag_batch(a, d));
+  return retarget_call(d, final_targets, K, nullptr, nullptr, step, arrive, remaining, arrived, done, stream);
+}
+
+int ishap_drag_batch_retarget_each(const ishap_drag_batch_args* a, const float* final_targets, const int* K, const float* steps,
+                                   const float* arrives, float* remaining, int* arrived, int* done, void* stream) {
+  ISHAP_REQUIRE(a && final_targets && K && steps && arrives && remaining && arrived && done, "null argument");
+  ISHAP_REQUIRE(a->W > 1 && 3ll * a->W * a->W <= RETARGET_LDS_BYTES, "drag retarget: 3*W*W must not exceed 65536 (the LDS bitmaps)");
+  DragBatchArgs d;
+  ISHAP_TRY(fill_drag_batch(a, d));
+  return retarget_call(d, final_targets, K, steps, arrives, 0.f, 0.f, remaining, arrived, done, stream);
 }
 
 // ---- region weights of the drag loss's mask term (csrc/regions.hip)

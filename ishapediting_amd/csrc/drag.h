@@ -54,6 +54,35 @@ struct DragArgs {
   long long* acc = nullptr;          // [2] loss sums, 64-bit fixed point (DRAG_ACC_SCALE)
   float* loss = nullptr;             // [1]
 };
+// ---- the touched-texel rule the setup (drag.hip, marks in global memory) and the per-step retarget (retarget.hip, marks in LDS)
+// share: one definition.  touched[p][row][col] is marked where a rounded lattice texel of any source / target point lands
+// (drag_utils.py:322-334).  `put(o, bit)` receives the byte offset o = (p * W + row) * W + col of a texel INSIDE the map.
+template <class Mark>
+__device__ __forceinline__ void drag_touch_marks(const DragArgs& a, int p, int b, int st, int i, int j, Mark&& put) {
+  int ac, ar;
+  plane_axes(p, ac, ar);
+  const float* pt = st ? a.targets : a.sources;
+  float u = lattice(pt[b * 3 + ac], a.voxel, i - a.r);
+  float v = lattice(pt[b * 3 + ar], a.voxel, j - a.r);
+  // th.round((p + 1) * (W - 1) / 2).type(int16): round-half-even, then wrap to int16
+  int col = (int)(short)rintf((u + 1.f) * (float)(a.W - 1) / 2.f);
+  int row = (int)(short)rintf((v + 1.f) * (float)(a.W - 1) / 2.f);
+  // bit 0: the reference's rounded-texel sets; bit 1: texels the motion scatter can reach (the four bilinear corners of a
+  // target position) -- the gather pass reads the scatter buffer only there.
+  auto mark = [&](int r_, int c_, unsigned bit) {
+    if (c_ < 0 || c_ >= a.W || r_ < 0 || r_ >= a.W) return;
+    const long long o = ((long long)p * a.W + r_) * a.W + c_;
+    put(o, bit);
+  };
+  mark(row, col, 1u);
+  if (st) {
+    const Bilin bt = bilin_setup(u, v, a.W);
+    // one texel of slack around the 2x2 corners: the scatter recomputes u, v and a differently contracted
+    // multiply-add must not put a corner outside the marked set
+    for (int dy = -1; dy <= 2; ++dy)
+      for (int dx = -1; dx <= 2; ++dx) mark(bt.y0 + dy, bt.x0 + dx, 2u);
+  }
+}
 // Integer atomics commute, so the scattered gradient and the loss are bitwise reproducible (fp32 atomics are not).
 constexpr float DRAG_FX_SCALE = 17592186044416.f;    // 2^44: |sum| < 5e5, resolution 6e-14
 constexpr float DRAG_ACC_SCALE = 16777216.f;         // 2^24
@@ -73,6 +102,26 @@ struct DragBatchArgs {
   int tblk[DRAG_MAX_EDITS + 1] = {};  // first workgroup of each edit in the terms pass (filled by the launcher)
   float cof[DRAG_MAX_EDITS] = {};
 };
+// edit e's slice of a batch
+__device__ __forceinline__ DragArgs drag_edit_args(const DragBatchArgs& b, int e) {
+  DragArgs a = b.base;
+  const long long n = (long long)a.W * a.W * a.ld;
+  const int h0 = b.hoff[e];
+  a.edit += e * n;
+  a.orig += e * b.orig_stride;
+  a.sources += 3 * h0;
+  a.targets += 3 * h0;
+  a.B = b.hoff[e + 1] - h0;
+  a.cof = b.cof[e];
+  a.touched += (long long)e * 3 * a.W * a.W;
+  a.nmask += e;
+  a.grad += e * n;
+  a.gfx += e * n;
+  a.acc += 2 * e;
+  a.loss += e;
+  return a;
+}
+int drag_batch_check(const DragBatchArgs& a);                     // the shape requirements of every drag call, solo or batched
 int drag_batch_setup_launch(DragBatchArgs& a, hipStream_t s);     // touched bitmaps + mask counts + channel weights (once per set of edits)
 // losses + fp32 gradients; with `cot` (then `bits` and `scale2` too) also the fp16 cotangent under one loss scale; `weights`:
 // the region weight maps [E][3][W][W] of the mask term (edit e at + e * wstride floats), nullptr for the unweighted pass

@@ -16,7 +16,8 @@
 #include "drag.h"
 #include <cstdlib>
 
-// plane_axes, lattice and bilin_setup (the sampling of every drag kernel, csrc/track.hip included) are in drag.h
+// plane_axes, lattice and bilin_setup (the sampling of every drag kernel, csrc/track.hip included) and drag_touch_marks (the
+// touched-texel rule, csrc/retarget.hip included) are in drag.h
 
 // workgroup sum of the per-lane loss terms, then ONE atomic on the accumulator (thousands of same-address atomics
 // -- one per wave -- were the whole run time of these kernels)
@@ -141,31 +142,12 @@ __device__ __forceinline__ void drag_motion_body(const DragArgs& a, int blk, int
   block_loss_add(lsum, a.acc + 0);
 }
 
-// touched[p][row][col] = 1 where a rounded lattice texel of any source/target point lands (drag_utils.py:322-334)
+// touched[p][row][col]: the marks of drag_touch_marks (drag.h, shared with csrc/retarget.hip) land in global memory.
+// Byte-wide atomic OR via the 32-bit word.
 __device__ __forceinline__ void drag_touch_one(const DragArgs& a, int p, int b, int st, int i, int j) {
-  int ac, ar;
-  plane_axes(p, ac, ar);
-  const float* pt = st ? a.targets : a.sources;
-  float u = lattice(pt[b * 3 + ac], a.voxel, i - a.r);
-  float v = lattice(pt[b * 3 + ar], a.voxel, j - a.r);
-  // th.round((p + 1) * (W - 1) / 2).type(int16): round-half-even, then wrap to int16
-  int col = (int)(short)rintf((u + 1.f) * (float)(a.W - 1) / 2.f);
-  int row = (int)(short)rintf((v + 1.f) * (float)(a.W - 1) / 2.f);
-  // bit 0: the reference's rounded-texel sets; bit 1: texels the motion scatter can reach (the four bilinear corners of a
-  // target position) -- the gather pass reads the scatter buffer only there.  Byte-wide atomic OR via the 32-bit word.
-  auto mark = [&](int r_, int c_, unsigned bit) {
-    if (c_ < 0 || c_ >= a.W || r_ < 0 || r_ >= a.W) return;
-    const long long o = ((long long)p * a.W + r_) * a.W + c_;
+  drag_touch_marks(a, p, b, st, i, j, [&](long long o, unsigned bit) {
     atomicOr(reinterpret_cast<unsigned*>(a.touched + (o & ~3ll)), bit << (8 * (o & 3)));
-  };
-  mark(row, col, 1u);
-  if (st) {
-    const Bilin bt = bilin_setup(u, v, a.W);
-    // one texel of slack around the 2x2 corners: the scatter recomputes u, v and a differently contracted
-    // multiply-add must not put a corner outside the marked set
-    for (int dy = -1; dy <= 2; ++dy)
-      for (int dx = -1; dx <= 2; ++dx) mark(bt.y0 + dy, bt.x0 + dx, 2u);
-  }
+  });
 }
 
 __device__ __forceinline__ void drag_count_body(const DragArgs& a) {
@@ -344,24 +326,7 @@ int grad_to_scaled_f16_launch(const float* g, half_t* o, unsigned* bits, float* 
 // its cotangent and removes the scale at its end (scale2[1]); a power-of-two rescaling of all its fp16 intermediates is exact as
 // long as none leaves the fp16 range.  One scale per batch therefore needs no change to the backward: only an edit whose
 // gradient is 2^10+ times smaller than the largest one of the batch loses low bits to fp16 subnormals.
-__device__ __forceinline__ DragArgs drag_edit_args(const DragBatchArgs& b, int e) {
-  DragArgs a = b.base;
-  const long long n = (long long)a.W * a.W * a.ld;
-  const int h0 = b.hoff[e];
-  a.edit += e * n;
-  a.orig += e * b.orig_stride;
-  a.sources += 3 * h0;
-  a.targets += 3 * h0;
-  a.B = b.hoff[e + 1] - h0;
-  a.cof = b.cof[e];
-  a.touched += (long long)e * 3 * a.W * a.W;
-  a.nmask += e;
-  a.grad += e * n;
-  a.gfx += e * n;
-  a.acc += 2 * e;
-  a.loss += e;
-  return a;
-}
+// drag_edit_args (edit e's slice of a DragBatchArgs) is in drag.h
 
 // one thread per (handle, plane, source / target, lattice i, j) over the packed handles of all edits.  Which thread takes which
 // tuple is free: drag_touch_one reads the handles and does nothing but atomicOr marks into `touched`, and OR commutes, so the
@@ -422,7 +387,7 @@ __global__ void drag_batch_scale_kernel(const float* __restrict__ g, half_t* __r
 }
 
 // the shape requirements of every drag call, solo or batched (api.hip checks only the pointers and dimensions of its structs)
-static int drag_batch_check(const DragBatchArgs& a) {
+int drag_batch_check(const DragBatchArgs& a) {
   ISHAP_REQUIRE(a.E >= 1 && a.E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");
   ISHAP_REQUIRE((3 * a.base.W * a.base.W) % 4 == 0 && a.base.ld % 8 == 0,
                 "drag: 3*W*W must be a multiple of 4 and the tap channels of 8");

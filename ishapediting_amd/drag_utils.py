@@ -113,10 +113,53 @@ class _DragKernelsBase:
         self.scale2 = th.ones(2, dtype=th.float32, device=self.device)
         self.sources = self.targets = None
         self._L = _lib.lib()
+        # closed loop (retarget): `targets` stays the final targets; the loss reads the goals at _aim_ptr once a retarget has run
+        self.goals = self.remaining = self.arrived = self.done = None
+        self._aim_ptr = None
+        self._aim_keep = None         # whatever owns the memory at _aim_ptr when that is not self.goals (the loop's table)
 
     def _call(self, fn, *args):
         with th.cuda.device(self.device):
             _lib.check(fn(*args, _lib.stream_ptr(self.device)))
+
+    def _targets_ptr(self) -> int:
+        """What the loss kernels read as targets: the final targets, or the goals of the last retarget."""
+        return self.targets.data_ptr() if self._aim_ptr is None else self._aim_ptr
+
+    def _reset_aim(self):
+        self.goals = self.remaining = self.arrived = self.done = None
+        self._aim_ptr = self._aim_keep = None
+
+    def retarget(self, K, step, arrive):
+        """Re-aim the loss (ishap_drag_retarget / ishap_drag_batch_retarget) after setup(): K int [H, 3], each
+        handle's tracked voxel offset from its source; step > 0 (may be inf), the lead in voxels; arrive >= 0 (the batched object
+        also takes one of each per edit).  Writes the object's goals buffer [H, 3], which every later loss call reads in place of
+        the targets, and rebuilds the touched sets and mask counts for it; `targets` stays the final targets.  Returns (goals,
+        remaining [H] float32, arrived [H] int32, done [edits] int32), device tensors the next call overwrites."""
+        if self.sources is None:
+            raise RuntimeError("retarget: call setup() first")
+        H, E = self.sources.shape[0], getattr(self, "E", 1)
+        K = (K.detach() if th.is_tensor(K) else th.as_tensor(np.asarray(K))).to(device=self.device, dtype=th.int32).contiguous()
+        if tuple(K.shape) != (H, 3):
+            raise ValueError(f"retarget: K must be [{H}, 3], got {tuple(K.shape)}")
+        if self.goals is None:
+            self.goals = th.empty((H, 3), dtype=th.float32, device=self.device)
+            self.remaining = th.empty(H, dtype=th.float32, device=self.device)
+            self.arrived = th.empty(H, dtype=th.int32, device=self.device)
+            self.done = th.empty(E, dtype=th.int32, device=self.device)
+        self.retarget_raw(K.data_ptr(), self.goals.data_ptr(), self.remaining.data_ptr(), self.arrived.data_ptr(),
+                          self.done.data_ptr(), step, arrive)
+        return self.goals, self.remaining, self.arrived, self.done
+
+    def retarget_raw(self, k: int, goals: int, remaining: int, arrived: int, done: int, step, arrive):
+        """retarget() on device addresses (the guided loop's form: rows of its tables; no tensor is made per step).  The loss
+        calls that follow read `goals`."""
+        keep, self._aim_ptr = self._aim_ptr, goals
+        try:
+            self._retarget_call(k, remaining, arrived, done, step, arrive)
+        except Exception:
+            self._aim_ptr = keep          # refused before any launch: the loss keeps reading what it read
+            raise
 
     def _weight_map(self, w):
         """A region weight map (regions.plane_weights) as the kernels read it: float32 [3, W, W] on the device."""
@@ -158,7 +201,7 @@ class DragKernels(_DragKernelsBase):
 
     def _args(self) -> _lib.DragArgsC:
         return _lib.DragArgsC(self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
-                              self.targets.data_ptr(), self.sources.shape[0], self.r, self.voxel, float(self.cof),
+                              self._targets_ptr(), self.sources.shape[0], self.r, self.voxel, float(self.cof),
                               self.l1, self.touched.data_ptr(), self.nmask.data_ptr(), self.acc.data_ptr(), self.gfx.data_ptr(),
                               self.chan_weight.data_ptr(), _lib.ptr(self.weights))
 
@@ -174,7 +217,12 @@ class DragKernels(_DragKernelsBase):
         self.sources, self.targets = pts(sources), pts(targets)
         assert self.sources.shape[0] == self.targets.shape[0]
         self.cof = float(cof)
+        self._reset_aim()
         self._call(self._L.ishap_drag_setup, C.byref(self._args()))
+
+    def _retarget_call(self, k, remaining, arrived, done, step, arrive):
+        self._call(self._L.ishap_drag_retarget, C.byref(self._args()), self.targets.data_ptr(), k, float(step), float(arrive),
+                   remaining, arrived, done)
 
     def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int):
         self._call(self._L.ishap_drag_loss_grad, C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
@@ -298,12 +346,37 @@ class BatchDragKernels(_DragKernelsBase):
         self._offs = (C.c_int * (self.E + 1))(*offs)
         self.cof = cofs
         self._cof = (C.c_float * self.E)(*self.cof)
+        self._reset_aim()
         self._call(self._L.ishap_drag_batch_setup, C.byref(self._args(0)))
+
+    def _retarget_call(self, k, remaining, arrived, done, step, arrive):
+        each = [not isinstance(v, (int, float, np.floating, np.integer)) for v in (step, arrive)]
+        if any(each):           # one lead / arrival radius per edit
+            st, ar = per_edit(step, self.E, "step"), per_edit(arrive, self.E, "arrive")
+            self._call(self._L.ishap_drag_batch_retarget_each, C.byref(self._args(0)), self.targets.data_ptr(), k,
+                       (C.c_float * self.E)(*st), (C.c_float * self.E)(*ar), remaining, arrived, done)
+        else:
+            self._call(self._L.ishap_drag_batch_retarget, C.byref(self._args(0)), self.targets.data_ptr(), k, float(step),
+                       float(arrive), remaining, arrived, done)
 
     def _args(self, orig_stride: int) -> _lib.DragBatchArgsC:
         return _lib.DragBatchArgsC(self.E, self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
-                                   self.targets.data_ptr(), self._offs, self.r, self.voxel, self._cof, self.l1, int(orig_stride),
+                                   self._targets_ptr(), self._offs, self.r, self.voxel, self._cof, self.l1, int(orig_stride),
                                    self.scratch.data_ptr(), self.scratch.numel(), _lib.ptr(self.weights), 3 * self.W * self.W)
+
+    def scratch_parts(self) -> dict:
+        """Views of the scratch buffer as api.hip carves it (every part on a 256-byte boundary): gfx int64 [E, W*W*ld], acc int64
+        [E, 2], nmask int32 [E], touched uint8 [E, 3*W*W], chan_weight uint8 [3*ld]."""
+        E, W, ld = self.E, self.W, self.ld
+        up = lambda v: (v + 255) & ~255      # noqa: E731
+        o_acc = up(E * W * W * ld * 8)
+        o_nmask = up(o_acc + E * 16)
+        o_touched = up(o_nmask + E * 4)
+        o_chw = up(o_touched + E * 3 * W * W)
+        s = self.scratch
+        return {"gfx": s[:E * W * W * ld * 8].view(th.int64).reshape(E, -1), "acc": s[o_acc:o_acc + E * 16].view(th.int64).reshape(E, 2),
+                "nmask": s[o_nmask:o_nmask + E * 4].view(th.int32), "touched": s[o_touched:o_touched + E * 3 * W * W].reshape(E, -1),
+                "chan_weight": s[o_chw:o_chw + 3 * ld]}
 
     def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int):
         """edit: [E][W*W][ld] fp16; orig: edit e's guidance at orig + e * orig_stride halfs (0: one guidance for all edits)."""
@@ -466,6 +539,124 @@ class _LoopTrack:
         return out
 
 
+CLOSED_LOOP_DEFAULTS = {"step": 2.0, "arrive": 1.0, "stop": False, "lag": 2}
+
+
+def _closed_loop_one(cl, what: str) -> dict:
+    opts = dict(CLOSED_LOOP_DEFAULTS)
+    if cl is not True:
+        if not isinstance(cl, dict):
+            raise ValueError(f"{what}: None, True or a dict with any of step, arrive, stop, lag (got {type(cl).__name__})")
+        unknown = set(cl) - set(opts)
+        if unknown:
+            raise ValueError(f"{what}: unknown keys {sorted(unknown)} (step, arrive, stop, lag)")
+        opts.update(cl)
+    try:
+        step, arrive = float(opts["step"]), float(opts["arrive"])
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: step and arrive must be numbers") from None
+    if not step > 0:                      # NaN fails too
+        raise ValueError(f"{what}: step = {opts['step']} (the lead in voxels: must be > 0, may be inf)")
+    if not arrive >= 0:
+        raise ValueError(f"{what}: arrive = {opts['arrive']} (voxels: must be >= 0)")
+    if not isinstance(opts["stop"], (bool, np.bool_)):
+        raise ValueError(f"{what}: stop = {opts['stop']!r} (must be True or False)")
+    lag = opts["lag"]
+    if isinstance(lag, (bool, np.bool_)) or not isinstance(lag, (int, np.integer)) or lag < 1:
+        raise ValueError(f"{what}: lag = {lag!r} (an integer >= 1: the host looks at the stop flag of `lag` steps ago)")
+    return {"step": step, "arrive": arrive, "stop": bool(opts["stop"]), "lag": int(lag)}
+
+
+def closed_loop_options(closed_loop, K: Optional[int] = None) -> Optional[dict]:
+    """The `closed_loop` keyword of training() / training_part() / training_batch(): None or False (off), True (the defaults) or
+    a dict with any of step, arrive, stop, lag -> None or the full dict.  With K (training_batch) also a list of K such entries,
+    one per edit: step and arrive then come back as lists of K floats; stop and lag belong to the loop and must agree."""
+    if closed_loop is None or closed_loop is False:
+        return None
+    if K is not None and isinstance(closed_loop, (list, tuple)):
+        if len(closed_loop) != K:
+            raise ValueError(f"closed_loop: {len(closed_loop)} entries for {K} edits (give one value or one per edit)")
+        each = [_closed_loop_one(True if c is None else c, f"closed_loop[{k}]") for k, c in enumerate(closed_loop)]
+        if any(o["stop"] != each[0]["stop"] or o["lag"] != each[0]["lag"] for o in each):
+            raise ValueError("closed_loop: stop and lag belong to the loop: every edit must give the same")
+        return {"step": [o["step"] for o in each], "arrive": [o["arrive"] for o in each], "stop": each[0]["stop"], "lag": each[0]["lag"]}
+    return _closed_loop_one(closed_loop, "closed_loop")
+
+
+def closed_loop_track(closed_loop_opts, track):
+    """The `track` keyword under a closed loop: tracking is what closes it, so it is on when not given and may not be False."""
+    if closed_loop_opts is None:
+        return track
+    if track is False:
+        raise ValueError("closed_loop needs the handle tracking: track may not be False")
+    return True if track is None else track
+
+
+class _ClosedLoop:
+    """The re-aiming of one guided loop: after every tracked step one retarget reads the row of offsets the
+    tracker just wrote and writes the next row of goals, which the loss calls read from then on.  Row 0 is the retarget on the
+    table's row of zeros, run here, before the first step.  The host passes addresses only.
+    stop: after each retarget the step's `done` row is copied to pinned memory behind an event; before enqueueing guided step n
+    the loop waits for the event of step n - lag -- a fixed step, whatever the timing -- and stops if every edit was done then."""
+
+    def __init__(self, dk, trk: "_LoopTrack", opts: dict):
+        self.dk, self.trk, self.opts = dk, trk, opts
+        H, E, dev = trk.tracker.handles, trk.tracker.E, trk.tracker.device
+        rows = trk.table.shape[0]                     # tracked steps + 1
+        self.goals = th.zeros((rows, H, 3), dtype=th.float32, device=dev)
+        self.remaining = th.zeros((rows, H), dtype=th.float32, device=dev)
+        self.arrived = th.zeros((rows, H), dtype=th.int32, device=dev)
+        self.done = th.zeros((rows, E), dtype=th.int32, device=dev)
+        self._ptrs = (trk.table.data_ptr(), self.goals.data_ptr(), self.remaining.data_ptr(), self.arrived.data_ptr(),
+                      self.done.data_ptr(), H, E)
+        self.stop, self.lag = opts["stop"], opts["lag"]
+        self.done_host = th.zeros((rows, E), dtype=th.int32).pin_memory() if self.stop else None
+        self.events: list = []                        # per loop step n: (event, row) of the newest `done` row at that step
+        dk._aim_keep = self.goals                     # the kernels object outlives the loop and keeps aiming at a row of this table
+        self._retarget(0)
+
+    def _retarget(self, r: int):
+        table, goals, rem, arr, done, H, E = self._ptrs
+        self.dk.retarget_raw(table + 12 * H * r, goals + 12 * H * r, rem + 4 * H * r, arr + 4 * H * r, done + 4 * E * r,
+                             self.opts["step"], self.opts["arrive"])
+
+    def step(self, n: int):
+        """After the tracker's call of step n, on the same stream."""
+        tracked = bool(self.trk.steps) and self.trk.steps[-1] == n
+        r = len(self.trk.steps)
+        if tracked:
+            self._retarget(r)
+        if self.stop:
+            if tracked or not self.events:
+                self.done_host[r].copy_(self.done[r], non_blocking=True)
+                ev = th.cuda.Event()
+                ev.record()
+                self.events.append((ev, r))
+            else:
+                self.events.append(self.events[-1])
+
+    def stop_before(self, n: int) -> bool:
+        """Before guided step n is enqueued: was every edit done at step n - lag?"""
+        if not self.stop or n < self.lag:
+            return False
+        ev, r = self.events[n - self.lag]
+        ev.synchronize()
+        return bool(self.done_host[r].all())
+
+    def results(self, out: List[dict]) -> List[dict]:
+        """Adds to the tracker's per-edit dicts: goals [rows, B, 3], remaining [rows, B], arrived [rows, B] (bool), row r what the
+        loss of tracked step r aimed at (formed from offsets[r - 1]; zeros for r = 0), and remaining_after [B], arrived_after [B],
+        the same after the last tracked step."""
+        t, r = self.trk.tracker, len(self.trk.steps)
+        for e, d in enumerate(out):
+            a, b = t.offsets[e], t.offsets[e + 1]
+            d.update(goals=self.goals[:r, a:b].clone(), remaining=self.remaining[:r, a:b].clone(),
+                     arrived=self.arrived[:r, a:b] != 0, remaining_after=self.remaining[r, a:b].clone(),
+                     arrived_after=self.arrived[r, a:b] != 0, step=per_edit(self.opts["step"], t.E, "step")[e],
+                     arrive=per_edit(self.opts["arrive"], t.E, "arrive")[e])
+        return out
+
+
 def synthesize_latent(model, diffusion, args=None, t1=None, t2=0, inter_latent_idx=None, inter_feat_idx=None, img=None,
                       calc_grad=False, **kwargs):
     """drag_utils.py:61-131 (no caller in the reference; kept for the call surface).  calc_grad=True keeps the autograd
@@ -595,6 +786,7 @@ class DragStuff:
         self.feature_guidance: List[th.Tensor] = []     # fp16 NHWC taps [S*S, C] on the device
         self.last_losses: List[float] = []
         self.last_track = None        # after an edit with track=...: dict of steps / offsets / positions / dist / dist0 (batch: a list)
+        self.last_stop = None         # after a closed-loop edit with stop: the guided step it stopped before, or None (ran them all)
         self._dk: Optional[DragKernels] = None
         self.step_noise = None        # optional callable i -> noise tensor (parity runs); default randn like the reference
         # batched edits (training_batch): set by update_latent_params_batch; None = edit variants of the single shape
@@ -706,7 +898,7 @@ class DragStuff:
         return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10, refine=refine)
 
     # ------------------------------------------------------------------ drag loop (:302-399)
-    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False, trk=None):
+    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False, trk=None, cl=None):
         """The guided loop of training() and training_batch(): a generator that yields the progress value after each step and
         returns (img, stop_time) -- the latent and the number of unguided steps left when train_flag stopped it (0: ran to
         the end).  `dk`: a DragKernels or BatchDragKernels after setup; `guidance[n]`: the guidance tap of the n-th step, edit e's
@@ -715,16 +907,21 @@ class DragStuff:
         tensor per step.
         `reuse_first` (training() only: `img` is a copy of self.w): the first step's forward comes from the snapshot of an earlier
         edit of this shape when there is a valid one, and is saved as one otherwise.
-        `trk`: None, or the _LoopTrack of a tracked edit: its call follows the loss's on the same stream and only reads the tap."""
+        `trk`: None, or the _LoopTrack of a tracked edit: its call follows the loss's on the same stream and only reads the tap.
+        `cl`: None, or the _ClosedLoop of a closed-loop edit (needs `trk`): its retarget follows the tracker's call, so the order on
+        the stream is loss(n), track(n), retarget(n), backward(n); with stop it may clear train_flag before a step (last_stop)."""
         w_time = self.args.w_time
         overlap = _OVERLAP_TAIL if self.overlap_tail is None else self.overlap_tail
         reuse_first = reuse_first and _FIRST_STEP_REUSE and hasattr(self.model, "snapshot_restore")
         stop_time = 0
         self.train_flag = True
+        self.last_stop = None
         losses = th.zeros((w_time, len(scales)), dtype=th.float32, device=self.device)   # one slot per iteration, no per-step copy
         self.diffusion.prepare(self.model, range(w_time))                               # timestep embeddings of the whole loop, once
         self.last_losses = []
         for i in range(w_time - 1, -1, -1):
+            if cl is not None and self.train_flag and cl.stop_before(w_time - 1 - i):
+                self.train_flag, self.last_stop = False, w_time - 1 - i
             if not self.train_flag:
                 stop_time = i + 1
                 break
@@ -736,6 +933,8 @@ class DragStuff:
                 cot, scale2 = dk.loss_cotangent_ptr(self.model.tap_ptr(), origin.data_ptr(), orig_stride=stride, loss_out=slot)
                 if trk is not None:
                     trk.step(w_time - 1 - i, self.model.tap_ptr(), origin.data_ptr(), stride)
+                    if cl is not None:
+                        cl.step(w_time - 1 - i)
                 got["grad"] = self.model.backward_input(cot, scale2)           # = img.grad of the reference (:384)
                 return got["grad"]
 
@@ -795,6 +994,10 @@ class DragStuff:
         return regions.plane_weights(keep=keep, free=free, W=width, keep_weight=keep_weight, free_weight=free_weight,
                                      dilate=region_dilate, device=self.device)
 
+    def _closed_loop(self, dk, trk, copts):
+        """The re-aiming state of one guided loop; runs the retarget on the tracker's row of zeros (after dk.setup)."""
+        return _ClosedLoop(dk, trk, copts)
+
     def _loop_track(self, topts, width, ch, sources):
         """The tracking state of one guided loop, or None when tracking is off."""
         if topts is None:
@@ -821,7 +1024,7 @@ class DragStuff:
         return out if isinstance(self.last_track, list) else out[0]
 
     def training(self, sources=None, targets=None, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
-                 region_dilate=0, weights=None, track=None):
+                 region_dilate=0, weights=None, track=None, closed_loop=None):
         """One drag edit of the loaded shape (drag_utils.py:302-399).  Every edit starts from self.w: from the second edit of a
         shape on, the first guided step's forward is restored from a snapshot instead of run (ISHAP_FIRST_STEP_REUSE=0: always
         run); results are bit-identical either way.
@@ -832,8 +1035,15 @@ class DragStuff:
         whole column through the shape, so a region constrains its three shadows, not only its own volume.
         track: None (off: no launch is added), True, or {"radius": R, "patch": rp, "every": m}: after every m-th step's loss the
         handles are re-found in feature space (HandleTracker) without a host synchronisation; afterwards last_track holds the
-        tracks and handle_error() the distance of each handle's last position to its target.  The edit's results do not change."""
-        topts = track_options(track)
+        tracks and handle_error() the distance of each handle's last position to its target.  The edit's results do not change.
+        closed_loop: None (off: no launch is added), True, or {"step": 2.0, "arrive": 1.0, "stop": False, "lag": 2} (DESIGN.md
+        5.2m): after every tracked step the loss is re-aimed at a goal `step` voxels from each handle's tracked position towards
+        its target (the target itself once within `step`), and the touched sets and the preservation term's normalisation follow
+        the goals.  Turns tracking on when track is not given.  last_track then also holds goals, remaining and arrived per tracked
+        step.  stop: once every handle was within `arrive` voxels of its target `lag` steps ago, the edit finishes with unguided
+        steps (last_stop: the step it stopped before).  step = inf is the open-loop edit, bit for bit."""
+        copts = closed_loop_options(closed_loop)
+        topts = track_options(closed_loop_track(copts, track))
         if self.args.num_samples > 1:
             raise NotImplementedError("We can handle only one shape at each time!")
         ch, width = self.model.tap_shape(self.args.feat_layer)
@@ -847,16 +1057,18 @@ class DragStuff:
         dk.setup(self.sources, self.targets, cof, **({} if wmap is None else {"weights": wmap}))    # a plain edit: the call it always was
         self._dk = dk
         trk = self._loop_track(topts, width, ch, [self.sources])
+        cl = None if copts is None else self._closed_loop(dk, trk, copts)
         # the regions change the loss, not the forward: the first-step snapshot depends on the latent, the timestep and the weights
         # of the model only, so _first_step_key does not hold them and an edit with regions reuses the snapshot of a plain one
         img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), True,
-                                                      **({} if trk is None else {"trk": trk}))
+                                                      **({} if trk is None else {"trk": trk}), **({} if cl is None else {"cl": cl}))
         if trk is not None:
-            self.last_track, self._track_ends = trk.results()[0], [(self.sources, self.targets)]
+            res = trk.results() if cl is None else cl.results(trk.results())
+            self.last_track, self._track_ends = res[0], [(self.sources, self.targets)]
         self.mesh = self.get_mesh(img=img, t=stop_time)
 
     def training_part(self, part, rigid, handles=16, start=None, scale=600, cof=0.2, keep=None, keep_weight=4.0, free_weight=0.0,
-                      region_dilate=0, track=None):
+                      region_dilate=0, track=None, closed_loop=None):
         """A part edit: move `part` (a regions.Voxels, e.g. from regions.select_part) by `rigid` (a regions.Rigid).  The plan --
         regions.plan_part_edit: `handles` sources spread over the part from `start`, each one's target where the motion takes
         it, free = [the part, the part moved] -- is kept as self.part_plan, and the edit is the generator
@@ -864,11 +1076,13 @@ class DragStuff:
         Each handle's lattice only translates; a rotation is carried by the handles' different displacements.  r1 stays as
         set_offset1 left it: plan.spacing / voxel_size, the handles' spacing in voxels, is the natural lattice radius to compare
         it with (lattices much smaller leave gaps between handles, much larger ones overlap and average the rotation away).
-        The free regions, like all regions, constrain their three shadows, not only their volume.  track: as training()."""
+        The free regions, like all regions, constrain their three shadows, not only their volume.  track, closed_loop: as
+        training()."""
         from . import regions
         self.part_plan = plan = regions.plan_part_edit(part, rigid, handles=handles, start=start)
         return self.training(plan.sources, plan.targets, scale=scale, cof=cof, keep=keep, free=plan.free, keep_weight=keep_weight,
-                             free_weight=free_weight, region_dilate=region_dilate, **({} if track is None else {"track": track}))
+                             free_weight=free_weight, region_dilate=region_dilate, **({} if track is None else {"track": track}),
+                             **({} if closed_loop is None else {"closed_loop": closed_loop}))
 
     # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
     def _check_edits(self, K: int):
@@ -913,7 +1127,7 @@ class DragStuff:
         return self.meshes
 
     def training_batch(self, sources, targets, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
-                       region_dilate=0, weights=None, track=None):
+                       region_dilate=0, weights=None, track=None, closed_loop=None):
         """K drag edits in one guided loop (the generator of training(), same progress values).  sources / targets: lists of K
         handle arrays (their counts may differ); scale, cof: a float or K values.  keep, free, keep_weight, free_weight,
         region_dilate, weights: as training(), one value for every edit or a list of K (entries of keep / free / weights may be
@@ -926,11 +1140,14 @@ class DragStuff:
         linear backward).  Injected noise (step_noise -> [K, ...]) makes edit k repeat a solo run with noise k; drawn noise spans
         the batch and differs from a solo run's.
         Every step runs its forward: the first-step snapshot of training() is neither used nor taken here.
-        track: as training(), one setting for all edits and one launch pair per tracked step; last_track is then a list of K."""
-        topts = track_options(track)
+        track: as training(), one setting for all edits and one launch pair per tracked step; last_track is then a list of K.
+        closed_loop: as training(), one dict for all edits or a list of K (step and arrive per edit; stop and lag must agree): one
+        retarget launch per tracked step for all edits; with stop the loop stops once EVERY edit was done."""
         if len(sources) != len(targets):
             raise ValueError(f"{len(sources)} source sets but {len(targets)} target sets: one of each per edit")
         K = len(sources)
+        copts = closed_loop_options(closed_loop, K)
+        topts = track_options(closed_loop_track(copts, track))
         self._check_edits(K)
         scales = per_edit(scale, K, "scale")
         cofs = per_edit(cof, K, "cof")
@@ -955,11 +1172,12 @@ class DragStuff:
         dk.setup(sources, targets, cofs, **({} if all(w is None for w in wmaps) else {"weights": wmaps}))
         self._dk_batch = dk
         trk = self._loop_track(topts, width, ch, sources)
+        cl = None if copts is None else self._closed_loop(dk, trk, copts)
         scales_dev = th.tensor(scales, dtype=th.float32, device=self.device)
         img, stop_time = yield from self._guided_loop(img, dk, guidance, stride, scales, scales_dev,
-                                                      **({} if trk is None else {"trk": trk}))
+                                                      **({} if trk is None else {"trk": trk}), **({} if cl is None else {"cl": cl}))
         if trk is not None:
-            self.last_track = trk.results()
+            self.last_track = trk.results() if cl is None else cl.results(trk.results())
             self._track_ends = [(dk.sources[a:b], dk.targets[a:b]) for a, b in zip(dk.offsets[:-1], dk.offsets[1:])]
         self.get_meshes(img=img, t=stop_time)
 

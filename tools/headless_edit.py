@@ -34,6 +34,12 @@ table and the whole track to track.json next to the pictures, and marks each han
 yellow sphere.  A handle that has not moved keeps its mark inside the red source sphere; with synthetic weights the features are
 noise and that is the usual outcome.
 
+--closed-loop STEP [--arrive A] [--stop] closes the loop (DragStuff.training(closed_loop=...)): after every tracked
+step the loss is re-aimed at a goal STEP voxels from each handle's tracked position towards its target; --arrive A (default 1) is
+the distance, in voxels, at which a handle counts as arrived, and with --stop the edit finishes unguided once all have.  It turns
+--track on; the table gains each handle's remaining distance in voxels (after the last tracked step) and whether it has arrived,
+and track.json the goals and remaining distances of every tracked step.
+
 --time instead measures the renderer alone (device events around `--repeat` calls after a warm-up, medians):
   the 256^3 sphere mesh (~300 k triangles of a few pixels each) at 1024 x 1024, and 2 picture-filling triangles at 1024 x 1024
   (the second shows that large triangles do not serialise on one lane), next to the bytes each call has to move
@@ -132,19 +138,38 @@ def track_of(a):
     return {"radius": R, "patch": rp, "every": every}
 
 
+def closed_loop_of(a):
+    """--closed-loop / --arrive / --stop -> the `closed_loop` keyword of DragStuff.training (None without --closed-loop)"""
+    if a.closed_loop is None:
+        if a.arrive is not None or a.stop:
+            raise SystemExit("--arrive / --stop belong to --closed-loop STEP")
+        return None
+    return {"step": a.closed_loop, "arrive": 1.0 if a.arrive is None else a.arrive, "stop": bool(a.stop)}
+
+
 def track_report(ds, sources, targets):
     """the per-handle table of the last tracked edit (printed) and the JSON that goes next to the pictures"""
     tr, err = ds.last_track, ds.handle_error()
+    closed = "goals" in tr
     last, pos = tr["offsets"][-1].cpu().tolist(), tr["positions"][-1].cpu().tolist()
     rows = [{"handle": b, "source": [float(v) for v in sources[b]], "target": [float(v) for v in targets[b]], "offset_voxels": last[b],
              "position": pos[b], "error_voxels": float(err["error"][b]), "fraction": float(err["fraction"][b]),
              "dist": float(tr["dist"][-1, b]), "dist0": float(tr["dist0"][-1, b])} for b in range(len(last))]
-    print("handle  offset (voxels)      error (voxels)  covered   D(k*) / D(0)")
+    if closed:
+        for b, r in enumerate(rows):
+            r.update(remaining_voxels=float(tr["remaining_after"][b]), arrived=bool(tr["arrived_after"][b]))
+    print("handle  offset (voxels)      error (voxels)  covered   D(k*) / D(0)" + ("      remaining (voxels)" if closed else ""))
     for r in rows:
         print(f"{r['handle']:6d}  {str(r['offset_voxels']):19s}  {r['error_voxels']:14.2f}  {100 * r['fraction']:6.1f} %  "
-              f"{r['dist']:.4g} / {r['dist0']:.4g}")
-    return {"radius": tr["radius"], "patch": tr["patch"], "steps": tr["steps"], "voxel": ds.voxel_size, "handles": rows,
-            "offsets": tr["offsets"].cpu().tolist(), "dist": tr["dist"].cpu().tolist(), "dist0": tr["dist0"].cpu().tolist()}
+              f"{r['dist']:.4g} / {r['dist0']:.4g}" + (f"  {r['remaining_voxels']:10.3f}{' arrived' if r['arrived'] else ''}" if closed else ""))
+    out = {"radius": tr["radius"], "patch": tr["patch"], "steps": tr["steps"], "voxel": ds.voxel_size, "handles": rows,
+           "offsets": tr["offsets"].cpu().tolist(), "dist": tr["dist"].cpu().tolist(), "dist0": tr["dist0"].cpu().tolist()}
+    if closed:
+        print(f"closed loop: lead {tr['step']} voxels, arrival within {tr['arrive']}, "
+              + ("ran every guided step" if ds.last_stop is None else f"stopped before guided step {ds.last_stop}"))
+        out.update(step=tr["step"], arrive=tr["arrive"], stopped_before=ds.last_stop, goals=tr["goals"].cpu().tolist(),
+                   remaining=tr["remaining"].cpu().tolist(), arrived=tr["arrived"].cpu().tolist())
+    return out
 
 
 def changed_fraction(before, after, inside):
@@ -180,8 +205,10 @@ def edit(a):
     volume0 = ds.volume.clone()
     part_edit = part_of(a, volume0)
     report, part_report = {}, None
-    track = track_of(a)
+    track, closed = track_of(a), closed_loop_of(a)
     tkw = {} if track is None else {"track": track}
+    if closed is not None:
+        tkw["closed_loop"] = closed
     if part_edit is not None:      # handles and targets come from the part and its motion; the plan is made when the edit is created
         part, rigid, part_frames = part_edit
         frames = frames + part_frames
@@ -223,7 +250,7 @@ def edit(a):
         ds.mesh.compute_vertex_normals()
     after = edit_parts(ds.mesh, sources, targets, boxes=frames)
     tracked = None
-    if track is not None:
+    if track is not None or closed is not None:
         tracked = track_report(ds, np.asarray(sources), np.asarray(targets))
         with open(os.path.join(a.out, "track.json"), "w") as fh:
             json.dump(tracked, fh, indent=1)
@@ -318,6 +345,10 @@ def main():
     p.add_argument("--region-dilate", type=int, default=0)
     p.add_argument("--track", nargs="?", const="4,2,1", default=None, metavar="R,RP,EVERY",
                    help="track the handles in feature space (search radius, patch radius, every n-th step; default 4,2,1)")
+    p.add_argument("--closed-loop", type=float, default=None, metavar="STEP",
+                   help="re-aim the loss STEP voxels ahead of each tracked handle after every tracked step (turns --track on)")
+    p.add_argument("--arrive", type=float, default=None, metavar="A", help="with --closed-loop: a handle has arrived within A voxels (default 1)")
+    p.add_argument("--stop", action="store_true", help="with --closed-loop: finish unguided once every handle has arrived")
     p.add_argument("--time", action="store_true", help="measure the renderer instead of running an edit")
     p.add_argument("--time_out", default=None, help="where --time writes its JSON (default profiles/render_times.json)")
     p.add_argument("--warmup", type=int, default=10)
