@@ -57,7 +57,9 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * the part edits (ishap_region_select, ishap_region_handles, ishap_region_handles_scratch_bytes,
                             * ishap_region_transform); 20 since ishap_unet_block_grad; 21 since the handle
                             * tracking (ishap_drag_track, ishap_drag_track_scratch_bytes); 22 since the closed-loop drag
-                            * (ishap_drag_retarget, ishap_drag_batch_retarget, ishap_drag_batch_retarget_each) */
+                            * (ishap_drag_retarget, ishap_drag_batch_retarget, ishap_drag_batch_retarget_each); 23 since the exact
+                            * distance transform (ishap_edt, ishap_edt_scratch_bytes) and the marks and feathered map of the
+                            * regions (ishap_region_plane_marks, ishap_region_plane_feather, ishap_region_plane_feather_scratch_bytes) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -477,6 +479,48 @@ long long ishap_region_plane_weights_scratch_bytes(int W);
 int ishap_region_plane_weights(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels,
                                const unsigned char* free_voxels, int D, int W, int dilate, float keep_weight, float free_weight,
                                float* weights_out, int* shadow_counts, void* scratch, long long scratch_bytes, void* stream);
+/* The marks themselves (ABI 23): the inputs of ishap_region_plane_weights without the two weights, the same scratch.
+ * marks_out: device uint8 [3][W][W], bit 0 = in the keep shadow, bit 1 = in the free shadow, both after `dilate`. */
+int ishap_region_plane_marks(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels,
+                             const unsigned char* free_voxels, int D, int W, int dilate, unsigned char* marks_out, int* shadow_counts,
+                             void* scratch, long long scratch_bytes, void* stream);
+/* The feathered map (ABI 23): the weights ramp over `falloff` texels outside each dilated shadow instead of jumping.  With dk, df
+ * the squared texel distances of a texel to the keep and the free shadow of its plane (ishap_edt on the marks, axes = 6; an empty
+ * shadow gives ISHAP_EDT_INF) and A[d2] = table[d2] for d2 < table_len, else 0:
+ *   a_k = A[dk], a_f = A[df]
+ *   w = keep_weight                                          if a_k == 1
+ *       free_weight                                          if a_k == 0 and a_f == 1
+ *       1                                                    if a_k == 0 and a_f == 0
+ *       (1 + (kw - 1) a_k) + ((fw - 1) a_f) (1 - a_k)        otherwise: in double, no contraction, rounded once to float
+ * table: DEVICE double[table_len], built on the host as max(0, 1 - sqrt(d2) / falloff) for d2 < ceil(falloff^2), 0 < falloff <= 64
+ * texels (1 <= table_len <= 4096): the device takes no square root, so the map is bitwise what the formula gives in double.  A
+ * table of one entry (falloff <= 1) is the hard map.  2 <= W <= 1024; scratch: ishap_region_plane_feather_scratch_bytes(W) bytes,
+ * 16-byte aligned, no initialisation; everything else as ishap_region_plane_weights.  A feathered region still constrains its
+ * three shadows, not only its own volume. */
+long long ishap_region_plane_feather_scratch_bytes(int W);
+int ishap_region_plane_feather(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels,
+                               const unsigned char* free_voxels, int D, int W, int dilate, float keep_weight, float free_weight,
+                               const double* table, int table_len, float* weights_out, int* shadow_counts, void* scratch,
+                               long long scratch_bytes, void* stream);
+
+/* ---------------------------------------------------------- exact distance transform (ABI 23; csrc/edt.hip)
+ * The exact squared Euclidean distance transform of a byte grid, on the caller's stream: no host synchronisation, no allocation.
+ *   Grids   seeds: device uint8 [n0][n1][n2], n2 fastest -- the layout of volumes, x slowest.  A voxel is a seed where its byte is
+ *           non-zero or, with invert = 1, where it is zero.
+ *   Axes    axes is a bit mask: bit a set means distance is measured along axis a.  An axis that is not set is a batch axis:
+ *           slices along it never see each other.  axes = 7 is the 3-D transform of a volume; axes = 6 on [3][W][W] is three
+ *           independent 2-D transforms of the plane maps.  axes = 0 is an error.
+ *   Output  dist2[v] = min over the seeds s of v's slice of sum over the measured axes a of (v_a - s_a)^2, an exact int32;
+ *           ISHAP_EDT_INF wherever the slice holds no seed.
+ *   Limits  every measured axis is at most 1024 long, so every real distance is below 2^22, far from ISHAP_EDT_INF;
+ *           n0 n1 n2 < 2^31; seeds and dist2 do not alias.
+ *   Errors  bad sizes, axes outside 1..7, invert outside 0..1, a NULL pointer, aliasing buffers or a scratch smaller than
+ *           ishap_edt_scratch_bytes (which is -1 for bad sizes) return an error code and launch nothing.
+ * Integer arithmetic only and no atomics: two runs give the same bits.  scratch: device, 4-byte aligned, no initialisation. */
+#define ISHAP_EDT_INF (1 << 30)
+long long ishap_edt_scratch_bytes(int n0, int n1, int n2, int axes);
+int ishap_edt(const unsigned char* seeds, int n0, int n1, int n2, int axes, int invert, int* dist2, void* scratch,
+              long long scratch_bytes, void* stream);
 
 /* ---------------------------------------------------------- part edits (ABI 19; csrc/parts.hip)
  * From a region and a rigid motion to handles, targets and free regions, without a voxel going through the host.  Grids are

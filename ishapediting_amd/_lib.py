@@ -165,6 +165,13 @@ SYMBOLS = {
     "ishap_region_plane_weights_scratch_bytes": (C.c_longlong, [C.c_int]),
     "ishap_region_plane_weights": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                              c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
+    "ishap_region_plane_marks": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, c_void_p, c_void_p,
+                                           c_void_p, C.c_longlong, c_void_p]),
+    "ishap_region_plane_feather_scratch_bytes": (C.c_longlong, [C.c_int]),
+    "ishap_region_plane_feather": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                             c_void_p, C.c_int, c_void_p, c_void_p, c_void_p, C.c_longlong, c_void_p]),
+    "ishap_edt_scratch_bytes": (C.c_longlong, [C.c_int] * 4),
+    "ishap_edt": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p, c_void_p, C.c_longlong, c_void_p]),
     "ishap_region_select": (C.c_int, [c_void_p, C.c_int, C.c_float, c_void_p, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ishap_region_handles_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int]),
     "ishap_region_handles": (C.c_int, [c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), c_void_p, c_void_p, c_void_p, c_void_p,
@@ -273,9 +280,10 @@ def lib():
         # 18: ishap_triplane_field_grad / ishap_triplane_project;
         # 19: ishap_region_select / ishap_region_handles / ishap_region_handles_scratch_bytes / ishap_region_transform;
         # 20: ishap_unet_block_grad; 21: ishap_drag_track / ishap_drag_track_scratch_bytes;
-        # 22: ishap_drag_retarget / ishap_drag_batch_retarget / ishap_drag_batch_retarget_each
-        if l.ishap_version() < 22:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 22): rebuild with `python -m ishapediting_amd.build`")
+        # 22: ishap_drag_retarget / ishap_drag_batch_retarget / ishap_drag_batch_retarget_each;
+        # 23: ishap_edt / ishap_edt_scratch_bytes / ishap_region_plane_marks / ishap_region_plane_feather[_scratch_bytes]
+        if l.ishap_version() < 23:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 23): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

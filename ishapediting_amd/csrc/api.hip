@@ -430,6 +430,44 @@ int ishap_region_plane_weights(const ishap_region_prim* prims, int n_prims, cons
                                      weights_out, shadow_counts, scratch, (hipStream_t)stream);
 }
 
+// the checks the three region map calls share
+static int region_args_check(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels, const unsigned char* free_voxels,
+                             int D, int W, int dilate, const void* out, const void* scratch) {
+  ISHAP_REQUIRE(W >= 2 && W <= 4096, "region weights: W must be in 2..4096");
+  ISHAP_REQUIRE(n_prims >= 0 && (prims || n_prims == 0), "region weights: null primitives");
+  if (keep_voxels || free_voxels) ISHAP_REQUIRE(D >= W && D <= REGION_MAX_D, "region weights: a voxel grid needs W <= D <= 4096");
+  ISHAP_REQUIRE(dilate >= 0, "region weights: negative dilate");
+  ISHAP_REQUIRE(out && scratch, "null argument");
+  ISHAP_REQUIRE(((unsigned long long)scratch & 15ull) == 0, "region weights: scratch must be 16-byte aligned");
+  return 0;
+}
+
+int ishap_region_plane_marks(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels,
+                             const unsigned char* free_voxels, int D, int W, int dilate, unsigned char* marks_out, int* shadow_counts,
+                             void* scratch, long long scratch_bytes, void* stream) {
+  ISHAP_TRY(region_args_check(prims, n_prims, keep_voxels, free_voxels, D, W, dilate, marks_out, scratch));
+  ISHAP_REQUIRE(scratch_bytes >= region_scratch_bytes(W), "region marks: scratch smaller than ishap_region_plane_weights_scratch_bytes(W)");
+  ISHAP_REQUIRE((void*)marks_out != scratch, "region marks: marks_out must not be the scratch");
+  return region_plane_marks_launch((const RegionPrim*)prims, n_prims, keep_voxels, free_voxels, D, W, dilate, marks_out, shadow_counts,
+                                   scratch, (hipStream_t)stream);
+}
+
+long long ishap_region_plane_feather_scratch_bytes(int W) { return region_feather_scratch_bytes(W); }
+
+int ishap_region_plane_feather(const ishap_region_prim* prims, int n_prims, const unsigned char* keep_voxels,
+                               const unsigned char* free_voxels, int D, int W, int dilate, float keep_weight, float free_weight,
+                               const double* table, int table_len, float* weights_out, int* shadow_counts, void* scratch,
+                               long long scratch_bytes, void* stream) {
+  ISHAP_TRY(region_args_check(prims, n_prims, keep_voxels, free_voxels, D, W, dilate, weights_out, scratch));
+  ISHAP_REQUIRE(W <= 1024, "region feather: W must be in 2..1024");
+  ISHAP_REQUIRE(std::isfinite(keep_weight) && std::isfinite(free_weight) && keep_weight >= 0.f && free_weight >= 0.f,
+                "region weights: keep_weight and free_weight must be finite and >= 0");
+  ISHAP_REQUIRE(table && table_len >= 1 && table_len <= 4096, "region feather: the table holds 1..4096 entries (falloff <= 64 texels)");
+  ISHAP_REQUIRE(scratch_bytes >= region_feather_scratch_bytes(W), "region feather: scratch smaller than ishap_region_plane_feather_scratch_bytes(W)");
+  return region_plane_feather_launch((const RegionPrim*)prims, n_prims, keep_voxels, free_voxels, D, W, dilate, keep_weight, free_weight,
+                                     table, table_len, weights_out, shadow_counts, scratch, (hipStream_t)stream);
+}
+
 int ishap_grad_to_scaled_f16(const float* grad, void* out_f16, unsigned* bits, float* scale2, long long numel,
                              void* stream) {
   ISHAP_REQUIRE(grad && out_f16 && bits && scale2, "null argument");

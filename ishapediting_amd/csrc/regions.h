@@ -17,3 +17,11 @@ long long region_scratch_bytes(int W);
 int region_plane_weights_launch(const RegionPrim* prims, int n_prims, const unsigned char* keep_vox, const unsigned char* free_vox,
                                 int D, int W, int dilate, float keep_weight, float free_weight, float* weights_out, int* counts,
                                 void* scratch, hipStream_t s);
+// ABI 23.  marks_out uint8 [3][W][W]: bit 0 keep, bit 1 free, after dilation; scratch: region_scratch_bytes(W)
+int region_plane_marks_launch(const RegionPrim* prims, int n_prims, const unsigned char* keep_vox, const unsigned char* free_vox, int D,
+                              int W, int dilate, unsigned char* marks_out, int* counts, void* scratch, hipStream_t s);
+// the feathered map (include/ishap.h, ishap_region_plane_feather); table: device double[table_len]
+long long region_feather_scratch_bytes(int W);
+int region_plane_feather_launch(const RegionPrim* prims, int n_prims, const unsigned char* keep_vox, const unsigned char* free_vox, int D,
+                                int W, int dilate, float keep_weight, float free_weight, const double* table, int table_len,
+                                float* weights_out, int* counts, void* scratch, hipStream_t s);

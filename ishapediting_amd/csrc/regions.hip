@@ -11,8 +11,13 @@
 //      atomicOr as drag_touch_one's do.
 //   3. region_compose_kernel: Chebyshev dilation by d texels (clipped at the map), then keep / free / 1 -> the float map; counts
 //      the undilated shadow texels for the caller's "empty region" check.
+//   4. region_compose_marks_kernel: the same dilation, the marks themselves out (ishap_region_plane_marks); and
+//      region_feather_kernel: from the squared distances to the two dilated shadows (edt.hip on the marks, one transform per
+//      bit, axes = 6: three independent planes) and a host-built table of doubles to the feathered map
+//      (ishap_region_plane_feather).
 // Once per edit; nothing here is on the per-step path.
 #include "regions.h"
+#include "edt.h"
 
 __device__ __forceinline__ int vox_to_texel(int i, int D, int W) { return (2 * i * (W - 1) + (D - 1)) / (2 * (D - 1)); }
 
@@ -123,6 +128,117 @@ int region_plane_weights_launch(const RegionPrim* prims, int n_prims, const unsi
   }
   hipLaunchKernelGGL(region_compose_kernel, dim3(ceil_div(ntex, 256)), dim3(256), 0, s, (const unsigned char*)marks, W, dilate,
                      keep_weight, free_weight, weights_out, counts);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the marks after dilation, and the feathered map (ABI 23)
+__global__ __launch_bounds__(256) void region_compose_marks_kernel(const unsigned char* __restrict__ marks, int W, int dilate,
+                                                                   unsigned char* __restrict__ out, int* __restrict__ counts) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = idx < 3 * W * W;
+  unsigned own = 0, m = 0;
+  if (live) {
+    const int p = idx / (W * W), rem = idx - p * W * W, row = rem / W, col = rem - row * W;
+    own = marks[idx];
+    const int r0 = max(row - dilate, 0), r1 = min(row + dilate, W - 1), c0 = max(col - dilate, 0), c1 = min(col + dilate, W - 1);
+    for (int r = r0; r <= r1; ++r)
+      for (int c = c0; c <= c1; ++c) m |= marks[(p * W + r) * W + c];
+    out[idx] = (unsigned char)(m & 3u);
+  }
+  if (counts) {
+    const int nk = __popcll(__ballot(own & 1u)), nf = __popcll(__ballot(own & 2u));
+    if ((threadIdx.x & 63) == 0) {
+      if (nk) atomicAdd(counts + 0, nk);
+      if (nf) atomicAdd(counts + 1, nf);
+    }
+  }
+}
+
+// dk, df: squared texel distances to the keep / free shadow (EDT_INF: the plane has none).  table[d2], d2 < table_len, is
+// A = max(0, 1 - sqrt(d2) / falloff) in double from the host; beyond the table A = 0.  The blend is formed in double as
+// written, operation by operation, and rounded once.
+__global__ __launch_bounds__(256) void region_feather_kernel(const int* __restrict__ dk, const int* __restrict__ df,
+                                                             const double* __restrict__ table, int table_len, int ntex, float keep_weight,
+                                                             float free_weight, float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= ntex) return;
+  const int k2 = dk[idx], f2 = df[idx];
+  const double ak = k2 < table_len ? table[k2] : 0.0, af = f2 < table_len ? table[f2] : 0.0;
+  float w;
+  if (ak == 1.0) w = keep_weight;
+  else if (ak == 0.0 && af == 1.0) w = free_weight;
+  else if (ak == 0.0 && af == 0.0) w = 1.f;
+  else {
+    const double hold = 1.0 + ((double)keep_weight - 1.0) * ak;
+    const double loose = (((double)free_weight - 1.0) * af) * (1.0 - ak);
+    w = (float)(hold + loose);
+  }
+  out[idx] = w;
+}
+
+// the shadows of region_plane_weights_launch, undilated, into `raw`
+static void region_shadows_launch(const RegionPrim* prims, int n_prims, const unsigned char* keep_vox, const unsigned char* free_vox, int D,
+                                  int W, unsigned char* raw, hipStream_t s) {
+  const int ntex = 3 * W * W;
+  hipLaunchKernelGGL(region_prim_kernel, dim3(ceil_div(ntex, 256)), dim3(256), 0, s, prims, n_prims, W, raw);
+  const unsigned char* vox[2] = {keep_vox, free_vox};
+  for (int role = 0; role < 2; ++role) {
+    if (!vox[role]) continue;
+    const unsigned bit = role ? 2u : 1u;
+    const long long waves = (long long)D * D;
+    hipLaunchKernelGGL(region_vox_xy_kernel, dim3((unsigned)((waves * 64 + 255) / 256)), dim3(256), 0, s, vox[role], D, W, bit, raw);
+    const long long nthr = (long long)((D + VOX_RUN - 1) / VOX_RUN) * D * D;
+    for (int plane = 1; plane <= 2; ++plane)
+      hipLaunchKernelGGL(region_vox_z_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, vox[role], D, W, plane, bit, raw);
+  }
+}
+
+int region_plane_marks_launch(const RegionPrim* prims, int n_prims, const unsigned char* keep_vox, const unsigned char* free_vox, int D,
+                              int W, int dilate, unsigned char* marks_out, int* counts, void* scratch, hipStream_t s) {
+  unsigned char* raw = (unsigned char*)scratch;
+  if (counts) ISHAP_CHECK_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int), s));
+  region_shadows_launch(prims, n_prims, keep_vox, free_vox, D, W, raw, s);
+  hipLaunchKernelGGL(region_compose_marks_kernel, dim3(ceil_div(3 * W * W, 256)), dim3(256), 0, s, (const unsigned char*)raw, W, dilate,
+                     marks_out, counts);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// scratch: raw marks | dilated marks | dk int[3 W W] | df int[3 W W] | the transform's own scratch
+namespace {
+struct FeatherLayout { long long marks, dk, df, edt, bytes; };
+FeatherLayout feather_layout(int W) {
+  FeatherLayout L;
+  const long long ntex = 3ll * W * W;
+  L.marks = region_scratch_bytes(W);
+  L.dk = L.marks + (long long)align_up((size_t)ntex, 256);
+  L.df = L.dk + (long long)align_up((size_t)(4 * ntex), 256);
+  L.edt = L.df + (long long)align_up((size_t)(4 * ntex), 256);
+  L.bytes = L.edt + edt_scratch_bytes(3, W, W, 6);
+  return L;
+}
+}  // namespace
+
+long long region_feather_scratch_bytes(int W) {
+  if (W < 2 || W > EDT_MAX_AXIS) return -1;
+  return feather_layout(W).bytes;
+}
+
+int region_plane_feather_launch(const RegionPrim* prims, int n_prims, const unsigned char* keep_vox, const unsigned char* free_vox, int D,
+                                int W, int dilate, float keep_weight, float free_weight, const double* table, int table_len,
+                                float* weights_out, int* counts, void* scratch, hipStream_t s) {
+  const FeatherLayout L = feather_layout(W);
+  char* base = (char*)scratch;
+  unsigned char* marks = (unsigned char*)(base + L.marks);
+  int *dk = (int*)(base + L.dk), *df = (int*)(base + L.df);
+  ISHAP_TRY(region_plane_marks_launch(prims, n_prims, keep_vox, free_vox, D, W, dilate, marks, counts, scratch, s));
+  ISHAP_TRY(edt_launch(marks, 1u, 3, W, W, 6, 0, dk, base + L.edt, s));
+  ISHAP_TRY(edt_launch(marks, 2u, 3, W, W, 6, 0, df, base + L.edt, s));
+  const int ntex = 3 * W * W;
+  hipLaunchKernelGGL(region_feather_kernel, dim3(ceil_div(ntex, 256)), dim3(256), 0, s, (const int*)dk, (const int*)df, table, table_len,
+                     ntex, keep_weight, free_weight, weights_out);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -979,12 +979,13 @@ class DragStuff:
             yield 1 - i / (w_time - 1.)
         return img, stop_time
 
-    def _region_weights(self, width, cof, keep, free, keep_weight, free_weight, region_dilate, weights, what="cof"):
+    def _region_weights(self, width, cof, keep, free, keep_weight, free_weight, region_dilate, weights, what="cof", region_falloff=0.0):
         """The weight map of one edit's preservation term, or None: `weights` (a ready [3, W, W] map) or the map of the keep /
         free regions (regions.plane_weights at the tap's width).  Everything is validated before anything is launched."""
         from . import regions
         if weights is not None and (keep is not None or free is not None):
             raise ValueError("weights is a ready map: give it or keep / free regions, not both")
+        region_falloff = regions.check_falloff(region_falloff)
         has = weights is not None or keep is not None or free is not None
         check_region_cof(float(cof), has, what)
         if weights is not None:
@@ -992,7 +993,7 @@ class DragStuff:
         if not has:
             return None
         return regions.plane_weights(keep=keep, free=free, W=width, keep_weight=keep_weight, free_weight=free_weight,
-                                     dilate=region_dilate, device=self.device)
+                                     dilate=region_dilate, device=self.device, **({} if region_falloff == 0 else {"falloff": region_falloff}))
 
     def _closed_loop(self, dk, trk, copts):
         """The re-aiming state of one guided loop; runs the retarget on the tracker's row of zeros (after dk.setup)."""
@@ -1024,13 +1025,14 @@ class DragStuff:
         return out if isinstance(self.last_track, list) else out[0]
 
     def training(self, sources=None, targets=None, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
-                 region_dilate=0, weights=None, track=None, closed_loop=None):
+                 region_dilate=0, weights=None, track=None, closed_loop=None, region_falloff=0.0):
         """One drag edit of the loaded shape (drag_utils.py:302-399).  Every edit starts from self.w: from the second edit of a
         shape on, the first guided step's forward is restored from a snapshot instead of run (ISHAP_FIRST_STEP_REUSE=0: always
         run); results are bit-identical either way.
         keep / free: 3-D regions (regions.Box / Sphere / Voxels or lists of them, in the handles' coordinates) whose shadows on
         the three planes get keep_weight (default 4: held harder) / free_weight (default 0: free to change) in the preservation
-        term instead of 1, each shadow grown by region_dilate texels; keep overrides free.  weights: a ready [3, W, W] map
+        term instead of 1, each shadow grown by region_dilate texels; keep overrides free.  region_falloff > 0 (texels) feathers
+        the edges of the map over that distance instead of a jump (regions.plane_weights, falloff).  weights: a ready [3, W, W] map
         instead (W the side of the tap), exclusive with keep and free.  All of them need cof > 0.  A plane texel stands for a
         whole column through the shape, so a region constrains its three shadows, not only its own volume.
         track: None (off: no launch is added), True, or {"radius": R, "patch": rp, "every": m}: after every m-th step's loss the
@@ -1047,7 +1049,7 @@ class DragStuff:
         if self.args.num_samples > 1:
             raise NotImplementedError("We can handle only one shape at each time!")
         ch, width = self.model.tap_shape(self.args.feat_layer)
-        wmap = self._region_weights(width, cof, keep, free, keep_weight, free_weight, region_dilate, weights)
+        wmap = self._region_weights(width, cof, keep, free, keep_weight, free_weight, region_dilate, weights, region_falloff=region_falloff)
         self.sources = th.tensor(np.asarray(sources), device=self.device, dtype=th.float32)
         self.targets = th.tensor(np.asarray(targets), device=self.device, dtype=th.float32)
         assert self.sources.shape[0] == self.targets.shape[0]
@@ -1068,7 +1070,7 @@ class DragStuff:
         self.mesh = self.get_mesh(img=img, t=stop_time)
 
     def training_part(self, part, rigid, handles=16, start=None, scale=600, cof=0.2, keep=None, keep_weight=4.0, free_weight=0.0,
-                      region_dilate=0, track=None, closed_loop=None):
+                      region_dilate=0, track=None, closed_loop=None, margin=0.0, region_falloff=0.0):
         """A part edit: move `part` (a regions.Voxels, e.g. from regions.select_part) by `rigid` (a regions.Rigid).  The plan --
         regions.plan_part_edit: `handles` sources spread over the part from `start`, each one's target where the motion takes
         it, free = [the part, the part moved] -- is kept as self.part_plan, and the edit is the generator
@@ -1076,12 +1078,15 @@ class DragStuff:
         Each handle's lattice only translates; a rotation is carried by the handles' different displacements.  r1 stays as
         set_offset1 left it: plan.spacing / voxel_size, the handles' spacing in voxels, is the natural lattice radius to compare
         it with (lattices much smaller leave gaps between handles, much larger ones overlap and average the rotation away).
-        The free regions, like all regions, constrain their three shadows, not only their volume.  track, closed_loop: as
-        training()."""
+        margin (voxels): the two free regions are grown by it in 3-D (regions.grow), so that the surface which blends the moved
+        part into the rest may change too; region_falloff: as training().  margin = 0 and region_falloff = 0 are the edit it
+        always was.  The free regions, like all regions and however grown or feathered, constrain their three shadows, not only
+        their volume.  track, closed_loop: as training()."""
         from . import regions
-        self.part_plan = plan = regions.plan_part_edit(part, rigid, handles=handles, start=start)
+        self.part_plan = plan = regions.plan_part_edit(part, rigid, handles=handles, start=start, **({} if margin == 0 else {"margin": margin}))
         return self.training(plan.sources, plan.targets, scale=scale, cof=cof, keep=keep, free=plan.free, keep_weight=keep_weight,
-                             free_weight=free_weight, region_dilate=region_dilate, **({} if track is None else {"track": track}),
+                             free_weight=free_weight, region_dilate=region_dilate, region_falloff=region_falloff,
+                             **({} if track is None else {"track": track}),
                              **({} if closed_loop is None else {"closed_loop": closed_loop}))
 
     # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
@@ -1127,10 +1132,10 @@ class DragStuff:
         return self.meshes
 
     def training_batch(self, sources, targets, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
-                       region_dilate=0, weights=None, track=None, closed_loop=None):
+                       region_dilate=0, weights=None, track=None, closed_loop=None, region_falloff=0.0):
         """K drag edits in one guided loop (the generator of training(), same progress values).  sources / targets: lists of K
         handle arrays (their counts may differ); scale, cof: a float or K values.  keep, free, keep_weight, free_weight,
-        region_dilate, weights: as training(), one value for every edit or a list of K (entries of keep / free / weights may be
+        region_dilate, region_falloff, weights: as training(), one value for every edit or a list of K (entries of keep / free / weights may be
         None: that edit has no such region and, if none at all, the bits of its plain batched edit; a region that is itself a
         list goes inside the list of K).  After update_latent_params_batch edit k
         drags shape k; otherwise the K edits are variants of the single shape of update_latent_params (its w and guidance
@@ -1155,7 +1160,8 @@ class DragStuff:
         keeps, frees, maps = (per_edit_region(v, K, n) for v, n in ((keep, "keep"), (free, "free"), (weights, "weights")))
         kws, fws = per_edit(keep_weight, K, "keep_weight"), per_edit(free_weight, K, "free_weight")
         dils = per_edit_any(region_dilate, K, "region_dilate")
-        wmaps = [self._region_weights(width, cofs[k], keeps[k], frees[k], kws[k], fws[k], dils[k], maps[k], f"cof[{k}]")
+        falls = per_edit_any(region_falloff, K, "region_falloff")
+        wmaps = [self._region_weights(width, cofs[k], keeps[k], frees[k], kws[k], fws[k], dils[k], maps[k], f"cof[{k}]", falls[k])
                  for k in range(K)]
         if self.w_batch is not None:
             if self.w_batch.shape[0] != K:

@@ -14,6 +14,10 @@ each axis on the texels the box projects to; freeing one frees those columns.
 Part edits (the second half of this file; csrc/parts.hip): `select_part` names a part of a decoded volume, `Rigid` is a rigid
 motion, `sample_handles` spreads handles over the part, `transform_region` moves it, and `plan_part_edit` puts them together
 into what DragStuff.training takes -- sources, targets and free = [part, moved].
+
+Distances (csrc/edt.hip, volume.distance_transform): `grow`, `shrink`, `open_region`, `close_region` and `shell` change a Voxels
+region in 3-D by a Euclidean radius in voxels; `plan_part_edit(margin=)` grows the free regions, `select_part(neck=)` cuts a
+selection at thin necks, and `plane_weights(falloff=)` feathers the edges of the map.
 """
 from __future__ import annotations
 
@@ -127,18 +131,51 @@ def check_dilate(value):
     return int(value)
 
 
+MAX_FALLOFF = 64.0
+
+
+def check_falloff(value):
+    v = float(value)
+    if not (np.isfinite(v) and 0.0 <= v <= MAX_FALLOFF):
+        raise ValueError(f"falloff must be in 0..{MAX_FALLOFF:g} texels, got {value!r}")
+    return v
+
+
+def falloff_table(falloff: float) -> np.ndarray:
+    """float64 [ceil(falloff^2)]: A[d2] = max(0, 1 - sqrt(d2) / falloff), the ramp of a feathered map by squared texel
+    distance.  Taken here, on the host: the device looks it up, so its map is bitwise this formula's."""
+    n = int(np.ceil(falloff * falloff))
+    return np.maximum(0.0, 1.0 - np.sqrt(np.arange(max(n, 1), dtype=np.float64)) / falloff)
+
+
 def plane_weights(keep=None, free=None, W: Optional[int] = None, keep_weight: float = 4.0, free_weight: float = 0.0, dilate: int = 0,
-                  device=None) -> torch.Tensor:
+                  device=None, falloff: float = 0.0) -> torch.Tensor:
     """float32 [3, W, W] on the device: keep_weight on the texels in the shadow of `keep`, else free_weight on those in the shadow
     of `free`, else 1 (keep overrides free).  keep / free: a Box, Sphere or Voxels, or a list of them (their union), or None.
     dilate: grow every shadow by that many texels (Chebyshev), clipped at the map.  A region whose shadow is empty on all three
     planes -- thinner than the texel pitch, or outside the cube -- raises ValueError.
+    falloff > 0 (texels, at most 64) feathers the edges: with a = max(0, 1 - distance / falloff) to the keep and to the free
+    shadow, w = (1 + (keep_weight - 1) a_k) + ((free_weight - 1) a_f) (1 - a_k), in double, rounded once; distances are exact
+    Euclidean ones on each plane (csrc/edt.hip).  falloff <= 1 is the hard map; falloff = 0 is the call it always was.
     A plane texel stands for a whole column through the shape: a region constrains its three shadows, not only its own volume."""
     if W is None or isinstance(W, bool) or int(W) != W or int(W) < 2:
         raise ValueError(f"plane_weights: W (the side of the tap) must be an integer >= 2, got {W!r}")
     W = int(W)
     keep_weight, free_weight = check_weight(keep_weight, "keep_weight"), check_weight(free_weight, "free_weight")
     dilate = check_dilate(dilate)
+    falloff = check_falloff(falloff)
+    return _plane_map(keep, free, W, keep_weight, free_weight, dilate, device, falloff, False)
+
+
+def plane_marks(keep=None, free=None, W: Optional[int] = None, dilate: int = 0, device=None) -> torch.Tensor:
+    """uint8 [3, W, W] on the device: bit 0 on the texels in the shadow of `keep`, bit 1 on those in the shadow of `free`, both
+    after `dilate` -- the sets plane_weights turns into weights.  Arguments and errors as plane_weights."""
+    if W is None or isinstance(W, bool) or int(W) != W or int(W) < 2:
+        raise ValueError(f"plane_marks: W (the side of the tap) must be an integer >= 2, got {W!r}")
+    return _plane_map(keep, free, int(W), 0.0, 0.0, check_dilate(dilate), device, 0.0, True)
+
+
+def _plane_map(keep, free, W, keep_weight, free_weight, dilate, device, falloff, marks):
     # the regions are validated before anything touches the device
     for region, name in ((keep, "keep"), (free, "free")):
         for it in _as_list(region, name):
@@ -159,16 +196,25 @@ def plane_weights(keep=None, free=None, W: Optional[int] = None, keep_weight: fl
             r.kind, r.role = kind, role
             r.a[:], r.b[:] = a, b
         prims = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-    out = torch.empty((3, W, W), dtype=torch.float32, device=dev)
+    out = torch.empty((3, W, W), dtype=torch.uint8 if marks else torch.float32, device=dev)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
-    nbytes = int(L.ishap_region_plane_weights_scratch_bytes(W))
+    nbytes = int((L.ishap_region_plane_feather_scratch_bytes if falloff > 0 else L.ishap_region_plane_weights_scratch_bytes)(W))
     if nbytes <= 0:
         raise ValueError(f"plane_weights: W = {W} is out of range")
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    region = (_lib.ptr(prims), len(recs), _lib.ptr(kgrid), _lib.ptr(fgrid), D, W, dilate)
     with torch.cuda.device(dev):
-        _lib.check(L.ishap_region_plane_weights(_lib.ptr(prims), len(recs), _lib.ptr(kgrid), _lib.ptr(fgrid), D, W, dilate,
-                                                keep_weight, free_weight, out.data_ptr(), counts.data_ptr(), scratch.data_ptr(),
-                                                nbytes, _lib.stream_ptr(dev)))
+        if marks:
+            _lib.check(L.ishap_region_plane_marks(*region, out.data_ptr(), counts.data_ptr(), scratch.data_ptr(), nbytes,
+                                                  _lib.stream_ptr(dev)))
+        elif falloff > 0:
+            table = torch.from_numpy(falloff_table(falloff)).to(dev)                # uploaded with the call
+            _lib.check(L.ishap_region_plane_feather(*region, keep_weight, free_weight, table.data_ptr(), table.numel(),
+                                                    out.data_ptr(), counts.data_ptr(), scratch.data_ptr(), nbytes,
+                                                    _lib.stream_ptr(dev)))
+        else:
+            _lib.check(L.ishap_region_plane_weights(*region, keep_weight, free_weight, out.data_ptr(), counts.data_ptr(),
+                                                    scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
     nk, nf = (int(v) for v in counts.cpu())
     for region, name, n in ((keep, "keep", nk), (free, "free", nf)):
         if _as_list(region, name) and n == 0:
@@ -194,6 +240,57 @@ def component_region(volume: torch.Tensor, point, level: float = 0.0) -> Voxels:
     if root < 0:
         raise ValueError(f"component_region: the point {tuple(p)} (voxel {tuple(int(i) for i in idx)}) is outside the shape")
     return Voxels(labels == root)
+
+
+# ------------------------------------------------------------------------------------------------ morphology (csrc/edt.hip)
+# Growing, shrinking, opening and closing a Voxels region in 3-D, by Euclidean radii in voxels: thresholds of the exact squared
+# distance transform (volume.distance_transform).  Nothing lies outside the grid: the cube's walls do not erode a region.
+def _radius2(r, what):
+    """floor(r^2), taken on the host in double: the integer the squared distances are compared with"""
+    v = float(r)
+    if not (np.isfinite(v) and v >= 0):
+        raise ValueError(f"{what}: the radius must be finite and >= 0 voxels, got {r!r}")
+    from .volume import EDT_INF
+    return min(int(np.floor(v * v)), EDT_INF - 1)
+
+
+def _morph_mask(region, what):
+    if not isinstance(region, Voxels):
+        raise ValueError(f"{what}: region must be a Voxels region, got {type(region).__name__}")
+    if region.mask.device.type != "cuda":
+        raise ValueError(f"{what}: the region's mask must be on the GPU (there is no CPU path)")
+    return region.mask
+
+
+def grow(region: Voxels, r: float) -> Voxels:
+    """The voxels within r of the region: {d^2 <= floor(r^2)}, d^2 the exact squared distance to the region.  r = 0 returns the
+    region itself and launches nothing."""
+    from .volume import distance_transform
+    k, mask = _radius2(r, "grow"), _morph_mask(region, "grow")
+    return region if k == 0 else Voxels(distance_transform(mask) <= k)
+
+
+def shrink(region: Voxels, r: float) -> Voxels:
+    """The voxels farther than r from everything outside the region: the complement of the complement's grow.  The walls of the
+    cube do not erode.  r = 0 returns the region itself and launches nothing."""
+    from .volume import distance_transform
+    k, mask = _radius2(r, "shrink"), _morph_mask(region, "shrink")
+    return region if k == 0 else Voxels(distance_transform(mask, invert=True) > k)
+
+
+def open_region(region: Voxels, r: float) -> Voxels:
+    """grow(shrink(region, r), r): necks and spurs thinner than 2 r go, convex edges are rounded; a subset of the region."""
+    return grow(shrink(region, r), r)
+
+
+def close_region(region: Voxels, r: float) -> Voxels:
+    """shrink(grow(region, r), r): gaps and holes narrower than 2 r fill; a superset of the region."""
+    return shrink(grow(region, r), r)
+
+
+def shell(region: Voxels, inner: float, outer: float) -> Voxels:
+    """grow(region, outer) & ~shrink(region, inner): the band from `inner` voxels inside the region's boundary to `outer` outside."""
+    return Voxels(grow(region, outer).mask & ~shrink(region, inner).mask)
 
 
 # ------------------------------------------------------------------------------------------------ part edits (csrc/parts.hip)
@@ -233,13 +330,45 @@ def _nearest_voxel(point, D, what):
     return tuple(int(i) for i in idx)
 
 
-def select_part(volume: torch.Tensor, within, level: float = 0.0, point=None, connectivity: int = 6) -> Voxels:
+def _neck_component(sel: torch.Tensor, vol, level, vox, r, connectivity, point) -> Voxels:
+    """select_part's `neck`: the selection cut at necks thinner than 2 r.  E = shrink(selection, r) is labelled; the piece is
+    the component of E owning the voxel of E nearest to the pick voxel among those with d^2 <= floor(r^2) (ties: the lowest
+    linear index), found in a small cube of labels read back around the pick; grown back by r inside the selection."""
+    from .volume import label_volume
+    k, D = _radius2(r, "select_part: neck"), int(sel.shape[0])
+    whole = Voxels(sel)
+    core = shrink(whole, r).mask
+    masked = torch.where(core, vol, torch.full((), float(level), dtype=torch.float32, device=vol.device))
+    labels = label_volume(masked, level=level, phase="inside", connectivity=connectivity)
+    R = int(np.floor(np.sqrt(float(k))))
+    lo = [max(v - R, 0) for v in vox]
+    hi = [min(v + R, D - 1) for v in vox]
+    cube = labels[lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1].cpu().numpy()                 # the one host read
+    ix, iy, iz = np.meshgrid(*(np.arange(l, h + 1, dtype=np.int64) for l, h in zip(lo, hi)), indexing="ij")
+    d2 = (ix - vox[0]) ** 2 + (iy - vox[1]) ** 2 + (iz - vox[2]) ** 2
+    ok = (cube >= 0) & (d2 <= k)
+    if not ok.any():
+        raise ValueError(f"select_part: the point {tuple(_vec3(point, 'point'))} (voxel {vox}) sits on something thinner than "
+                         f"2 x neck = {2 * float(r):g} voxels: nothing of the selection within {float(r):g} voxels of it survives")
+    key = np.where(ok, d2 * (D ** 3) + (ix * D + iy) * D + iz, np.iinfo(np.int64).max)      # nearest first, then lowest index
+    root = int(cube.reshape(-1)[int(np.argmin(key))])
+    return Voxels(grow(Voxels(labels == root), r).mask & sel)
+
+
+def select_part(volume: torch.Tensor, within, level: float = 0.0, point=None, connectivity: int = 6, neck: float = 0.0) -> Voxels:
     """The part of a decoded [D, D, D] volume inside `within` (a Box, Sphere or Voxels, or a list: their union): the voxels with
     volume - level > 0 whose centre lies in a primitive (box bounds inclusive, sphere <= r^2, in double) or that are set in a
     grid.  With `point` (in [-1, 1]^3, e.g. what render.pick returns): only the connected piece of that selection which holds
     the voxel nearest to the point (volume.label_volume with `connectivity`).  Raises ValueError for an empty selection and
-    for a point whose voxel is not selected.  On the device; the host reads one count."""
+    for a point whose voxel is not selected.  On the device; the host reads one count.
+    neck = r > 0 (voxels, with `point`) cuts the selection at necks thinner than 2 r, so that an armrest joined to the seat by
+    a thin neck is a part of its own: the selection is shrunk by r, the piece of what is left nearest to the pick (within r of
+    it; ValueError if there is none -- the pick sits on something thinner than 2 r) is grown back by r inside the selection.
+    The result is that piece opened by r: its convex edges are rounded.  neck = 0 is the call it always was."""
     vol, D = _device_volume(volume, "select_part")
+    neck2 = _radius2(neck, "select_part: neck")
+    if neck2 > 0 and point is None:
+        raise ValueError("select_part: neck needs a point: it names the piece on the pick's side of the neck")
     items = _as_list(within, "within")
     if not items:
         raise ValueError("select_part: `within` names no region")
@@ -277,6 +406,8 @@ def select_part(volume: torch.Tensor, within, level: float = 0.0, point=None, co
     sel = out.view(torch.bool)
     if vox is None:
         return Voxels(sel)
+    if neck2 > 0:
+        return _neck_component(sel, vol, level, vox, neck, connectivity, point)
     from .volume import label_volume
     # the shape masked to the selection: outside it volume - level is 0, which is not inside
     masked = torch.where(sel, vol, torch.full((), float(level), dtype=torch.float32, device=dev))
@@ -441,18 +572,21 @@ def handle_targets(sources: np.ndarray, rigid: Rigid) -> np.ndarray:
     return targets
 
 
-def plan_part_edit(part: Voxels, rigid: Rigid, handles: int = 16, start=None) -> PartEdit:
+def plan_part_edit(part: Voxels, rigid: Rigid, handles: int = 16, start=None, margin: float = 0.0) -> PartEdit:
     """A part edit as a drag edit: `handles` sources spread over the part (sample_handles), each one's target where `rigid`
     takes it -- float32(rigid.apply(float64 sources)) -- and free = [part, moved]: the part's old and new place may change.
     A target outside [-1, 1]^3 raises ValueError naming the handle.  The lattices of the drag loss only translate: a rotation
     is approximated by the handles' different displacements.  The free regions constrain their three shadows, not only their
-    volume.  Several planned edits run in one loop through training_batch, which takes per-edit lists:
+    volume.  margin (voxels): free = [grow(part, margin), grow(moved, margin)], so that the surface which blends the moved part
+    into the rest, just outside both sets, may change too; `moved` stays the ungrown region and margin = 0 is the plan it always
+    was.  Several planned edits run in one loop through training_batch, which takes per-edit lists:
         plans = [plan_part_edit(part_a, rigid_a), plan_part_edit(part_b, rigid_b)]
         ds.training_batch([p.sources for p in plans], [p.targets for p in plans], free=[p.free for p in plans])"""
     if not isinstance(rigid, Rigid):
         raise ValueError(f"plan_part_edit: rigid must be a Rigid, got {type(rigid).__name__}")
+    _radius2(margin, "plan_part_edit: margin")
     h = sample_handles(part, handles, start=start)
     sources = h.points.cpu().numpy()
     targets = handle_targets(sources, rigid)
     moved = transform_region(part, rigid)
-    return PartEdit(sources=sources, targets=targets, free=[part, moved], spacing=h.spacing, moved=moved)
+    return PartEdit(sources=sources, targets=targets, free=[grow(part, margin), grow(moved, margin)], spacing=h.spacing, moved=moved)

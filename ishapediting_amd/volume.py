@@ -7,6 +7,9 @@ the surface it was.  This module only allocates and selects; the voxel work is t
 A voxel is inside where `volume - level > 0` (extract_surface's rule: a NaN is outside).  connectivity 6 joins face
 neighbours, 26 face, edge and corner neighbours.  A component is named by its ROOT, the lowest linear index
 (x * ny + y) * nz + z of its voxels.
+
+Distances (csrc/edt.hip, ishap_edt): `distance_transform` is the exact squared Euclidean distance from every voxel to a set, as
+integers; `signed_distance` the voxel-grid signed distance of a decoded volume, negative inside.
 """
 from __future__ import annotations
 
@@ -164,3 +167,63 @@ def clean_volume(volume: torch.Tensor, level: float = 0.0, keep="largest", min_v
         if info["cavities"]:
             _flip(out, out, outside.labels, level, outside.roots[closed], scratch)
     return (out, info) if return_info else out
+
+
+# ------------------------------------------------------------------------------------------------ distances (csrc/edt.hip)
+EDT_INF = 1 << 30          # ISHAP_EDT_INF: the squared distance where a slice holds no seed
+EDT_MAX_AXIS = 1024
+
+
+def _edt(seeds: torch.Tensor, axes: int, invert: bool) -> torch.Tensor:
+    """ishap_edt on a contiguous uint8 [n0, n1, n2] device tensor -> int32 of that shape, on torch's current stream"""
+    n0, n1, n2 = seeds.shape
+    L = _lib.lib()
+    nbytes = int(L.ishap_edt_scratch_bytes(n0, n1, n2, axes))
+    if nbytes <= 0:
+        raise ValueError(f"distance_transform: a grid of {(n0, n1, n2)} with axes mask {axes} is outside the limits (every "
+                         f"measured axis <= {EDT_MAX_AXIS}, fewer than 2^31 voxels)")
+    out = torch.empty((n0, n1, n2), dtype=torch.int32, device=seeds.device)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=seeds.device)
+    with torch.cuda.device(seeds.device):
+        _lib.check(L.ishap_edt(seeds.data_ptr(), n0, n1, n2, axes, int(bool(invert)), out.data_ptr(), scratch.data_ptr(), nbytes,
+                               _lib.stream_ptr(seeds.device)))
+    return out
+
+
+def distance_transform(mask: torch.Tensor, axes=None, invert: bool = False) -> torch.Tensor:
+    """The exact squared Euclidean distance, in voxels, from every element of `mask` to the nearest set one (with `invert`: to
+    the nearest one that is not set): int32 of mask's shape, EDT_INF where there is none.  mask: a bool or uint8 tensor of 1 to
+    3 dimensions on the device.  axes: the dimensions of `mask` along which distance is measured (default: all); the others are
+    batch dimensions whose slices never see each other -- axes=(1, 2) on a [3, W, W] stack is three 2-D transforms.  Integer
+    arithmetic on the device (csrc/edt.hip): two runs give the same bits."""
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or not 1 <= mask.dim() <= 3 or mask.numel() == 0:
+        raise ValueError("distance_transform: mask must be a non-empty bool or uint8 tensor of 1 to 3 dimensions")
+    _need_gpu(mask, "distance_transform")
+    nd = mask.dim()
+    if axes is None:
+        axes = tuple(range(nd))
+    if isinstance(axes, int) and not isinstance(axes, bool):
+        axes = (axes,)
+    axes = tuple(axes)
+    if not axes or any(isinstance(a, bool) or int(a) != a or not -nd <= a < nd for a in axes):
+        raise ValueError(f"distance_transform: axes must name at least one of the {nd} dimensions of mask, got {axes!r}")
+    bits = 0
+    for a in axes:
+        bits |= 1 << (int(a) % nd + 3 - nd)
+    seeds = mask.contiguous().view(torch.uint8).reshape((1,) * (3 - nd) + tuple(mask.shape))
+    return _edt(seeds, bits, invert).reshape(mask.shape)
+
+
+def signed_distance(volume: torch.Tensor, level: float = 0.0) -> torch.Tensor:
+    """float32 [D, D, D]: the signed distance, in voxels, of every voxel of a decoded volume to the shape's boundary on the grid:
+    sqrt(d^2 to the nearest inside voxel) - sqrt(d^2 to the nearest outside voxel), inside where volume - level > 0.  Negative
+    inside (the sign of metrics.calc_implicit_field(sdf=True)), +inf with no inside voxel, -inf with no outside voxel.  The
+    squared distances are exact integers; the square roots are taken in float64 and the difference is rounded once."""
+    vol = _check(volume, "inside", 6, "signed_distance")
+    inside = ((vol - float(level)) > 0).view(torch.uint8)
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=vol.device)
+
+    def root(invert):
+        d2 = _edt(inside, 7, invert)
+        return torch.where(d2 >= EDT_INF, inf, torch.sqrt(d2.to(torch.float64)))
+    return (root(False) - root(True)).to(torch.float32)

@@ -25,7 +25,10 @@ handles are spread over the part instead of picked by pixel (DragStuff.training_
 starts with a minus sign with an equals sign, --pivot=-0.2,0,0).  The part and the
 place it moves to are the free regions; --keep-* still apply.  The pictures show the handles, their targets and the selecting
 boxes.  Each handle's lattice only translates, so a rotation is approximated by the handles' different displacements; with
-synthetic weights nobody can judge how good the result looks.
+synthetic weights nobody can judge how good the result looks.  --neck V (with --part-at) cuts the selection at necks thinner
+than 2 V voxels and keeps the piece on the point's side; --margin V also frees what lies within V voxels of the part and of its
+new place; the voxel counts before and after are printed.  --region-falloff T feathers the edges of every region's weights over
+T texels of the planes instead of a jump.
 
 --track [R,rp,every] (default 4,2,1) re-finds every handle in feature space after every `every`-th guided step
 (DragStuff.training(track=...), HandleTracker: search radius R, patch radius rp, in voxels of the handle lattice), prints for each
@@ -120,7 +123,13 @@ def part_of(a, volume):
         frames.append((marker_box(np.asarray(b[:3], np.float64), np.asarray(b[3:], np.float64)), FREE_COLOUR))
     for sp in a.part_sphere or []:
         within.append(Sphere(sp[:3], sp[3]))
-    part = select_part(volume, within, point=_csv(a.part_at, 3, "--part-at") if a.part_at else None)
+    at = _csv(a.part_at, 3, "--part-at") if a.part_at else None
+    if a.neck and at is None:
+        raise SystemExit("--neck cuts the selection at necks on the way from a point: give --part-at")
+    part = select_part(volume, within, point=at, neck=a.neck)
+    if a.neck:
+        print(f"part: {int(select_part(volume, within, point=at).mask.sum())} voxels connected to --part-at, "
+              f"{int(part.mask.sum())} after cutting necks thinner than {2 * a.neck:g} voxels")
     rot = _csv(a.rotate, 4, "--rotate") if a.rotate else None
     rigid = Rigid(rotation=(rot[:3], rot[3]) if rot else None, pivot=_csv(a.pivot, 3, "--pivot") if a.pivot else (0.0, 0.0, 0.0),
                   translation=_csv(a.translate, 3, "--translate") if a.translate else (0.0, 0.0, 0.0))
@@ -213,10 +222,12 @@ def edit(a):
         part, rigid, part_frames = part_edit
         frames = frames + part_frames
         final = ds.training_part(part, rigid, handles=a.handles, scale=a.scale, cof=a.cof, keep=keep or None, keep_weight=a.keep_weight,
-                                 free_weight=a.free_weight, region_dilate=a.region_dilate, **tkw)
+                                 free_weight=a.free_weight, region_dilate=a.region_dilate, margin=a.margin,
+                                 region_falloff=a.region_falloff, **tkw)
         plan = ds.part_plan
         sources, targets = plan.sources, plan.targets
-        part_report = {"voxels": int(part.mask.sum()), "moved_voxels": int(plan.moved.mask.sum()), "handles": int(sources.shape[0]),
+        part_report = {"voxels": int(part.mask.sum()), "moved_voxels": int(plan.moved.mask.sum()), "margin": a.margin,
+                       "free_voxels": [int(r.mask.sum()) for r in plan.free], "handles": int(sources.shape[0]),
                        "spacing": plan.spacing, "spacing_in_voxels": plan.spacing / ds.voxel_size, "r1": int(ds.r1),
                        "rotation": rigid.matrix.tolist(), "pivot": list(rigid.pivot), "translation": list(rigid.translation)}
         print(f"part: {part_report}")
@@ -230,7 +241,8 @@ def edit(a):
         for pos, idx, d, px in picked:
             print(f"pick pixel {px}: vertex {idx} at {pos.tolist()}, depth {d:.6f}")
         final = ds.training(sources, targets, scale=a.scale, cof=a.cof, keep=keep or None, free=free or None,
-                            keep_weight=a.keep_weight, free_weight=a.free_weight, region_dilate=a.region_dilate, **tkw)
+                            keep_weight=a.keep_weight, free_weight=a.free_weight, region_dilate=a.region_dilate,
+                            **({"region_falloff": a.region_falloff} if (keep or free) else {}), **tkw)
     save_picture(os.path.join(a.out, "before.png"), render_mesh(edit_parts(before, sources, targets, boxes=frames), cam, a.size, a.size))
     if named:                # the same edit without the regions first: what they change is the difference of the two runs
         for _ in ds.training(sources, targets, scale=a.scale, cof=a.cof):
@@ -343,6 +355,12 @@ def main():
     p.add_argument("--keep-weight", type=float, default=4.0)
     p.add_argument("--free-weight", type=float, default=0.0)
     p.add_argument("--region-dilate", type=int, default=0)
+    p.add_argument("--region-falloff", type=float, default=0.0, metavar="T",
+                   help="feather the edges of the region weights over T texels of the planes (at most 64) instead of a jump")
+    p.add_argument("--margin", type=float, default=0.0, metavar="V",
+                   help="part edit: also free what lies within V voxels of the part and of the place it moves to")
+    p.add_argument("--neck", type=float, default=0.0, metavar="V",
+                   help="with --part-at: cut the selection at necks thinner than 2 V voxels, keep the piece on the point's side")
     p.add_argument("--track", nargs="?", const="4,2,1", default=None, metavar="R,RP,EVERY",
                    help="track the handles in feature space (search radius, patch radius, every n-th step; default 4,2,1)")
     p.add_argument("--closed-loop", type=float, default=None, metavar="STEP",
