@@ -1,7 +1,9 @@
 """tests/unet_ref.py on the CPU: the float64 restatement of the UNet agrees with the project's statement of it
 (oracle/ref_cpu.UNetOracle), its hand-written per-block VJP equals autograd, every mutation of that VJP is far outside the bound
 tests/test_gpu_backward_blocks.py asserts, the three configurations of that test reach every GroupNorm-backward route, and no
-block can leave a skip gradient owed (csrc/backward.hip's former `pending` fall-back)."""
+block can leave a skip gradient owed (csrc/backward.hip's former `pending` fall-back).  For tests/test_gpu_forward_blocks.py: the
+forward's yardstick is fp16 rounding at every block, every mutation of the forward's composition is far outside that test's
+bound, the head's split restatement meets the head's two conditions, and the forward configurations reach every launch form."""
 import ctypes as C
 
 import pytest
@@ -162,3 +164,192 @@ def test_no_block_can_leave_a_skip_gradient_owed():
             assert blk.layers[0].kind == "res", blk.name
         # the stem is the only block that cannot take an addend, and nothing is owed to its input
         assert all(b.skip_ch > 0 for b in spec.output_blocks) and len(spec.output_blocks) == len(spec.input_blocks)
+
+
+# ------------------------------------------------------------------------------------------------------------ the forward, block by block
+@pytest.fixture(scope="module")
+def forwards():
+    """per forward configuration, the rounded forward on the CPU once: (ref, ts, N, x16, acts, out, positions, per-position
+    (statement, e_r whole batch, e_r per image)); the head's `out` is its split restatement"""
+    out = {}
+    for name, (_, _, N, ts) in U.FORWARD_CONFIGS.items():
+        cfg, sd, x, ts = U.make_forward_inputs(name)
+        ref = U.UNetRef(cfg, sd)
+        emb = ref.emb(ts)
+        _, acts = ref.forward(x, ts, rnd=True)
+        head = ref.head_restatement(acts[(2, len(ref.spec.output_blocks) - 1)])
+        pos = ref.forward_positions(U.f16r(x), acts, head)
+        base = []
+        for p in pos:
+            st, e_r, _, _ = U.forward_position_errors(ref, p, emb)
+            base.append((st, e_r[0], e_r[1]))
+        out[name] = (ref, ts, N, U.f16r(x), acts, head, pos, base)
+    return out
+
+
+def _head_l2_bound(ref, p, st):
+    """the GPU test's second head condition: one tenth of the error of the head with its lo products dropped"""
+    return 0.1 * U.rel_l2(ref.head_restatement(p.x_in, lo=False), st)
+
+
+@pytest.mark.parametrize("name", list(U.FORWARD_CONFIGS))
+def test_forward_yardstick_is_fp16_rounding(forwards, name):
+    """e_r of every block of every forward configuration, for the whole batch and for each image, lies in (1e-4, 1e-3): 2.1e-4 for
+    the stem's single rounding, 3.0e-4 .. 6.1e-4 for the others.  No activation has saturated or sunk into fp16 subnormals, so
+    FACTOR * e_r means a few fp16 roundings.  The head is fp32-grade and has a criterion of its own: its split restatement is
+    3.2e-7 .. 5.5e-7 from the statement, the head without the lo products 3.0e-4 .. 3.2e-4 (an fp16 rounding)."""
+    ref, ts, N, x16, acts, head, pos, base = forwards[name]
+    for p, (st, e, e_img) in zip(pos, base):
+        print(f"{name} {p.name:18s} {p.kind:30s} e_r {e:.2e}  per image {min(e_img):.2e} .. {max(e_img):.2e}")
+        if p.blk is None:
+            e_lo = 10.0 * _head_l2_bound(ref, p, st)
+            print(f"{name} head without lo: {e_lo:.2e}")
+            assert e < 1e-6 and 1e-4 < e_lo < 1e-3, (name, e, e_lo)
+        else:
+            assert all(1e-4 < v < 1e-3 for v in [e] + e_img), (name, p.name, e, e_img)
+
+
+@pytest.mark.parametrize("name", list(U.FORWARD_CONFIGS))
+def test_every_forward_mutation_is_far_outside_the_bound(forwards, name):
+    """Each mistake the forward's composition could make (unet_ref.FORWARD_MUTATIONS) moves a position it applies to by more than
+    ten times that position's bound in tests/test_gpu_forward_blocks.py: FACTOR * e_r for the whole batch or for one image
+    (whichever ratio is larger -- the GPU test asserts both), for the head one tenth of the lo-dropped head's error.  On the 128^2
+    configurations a mutation is evaluated until the first position that shows it (each evaluation is a float64 block at 128^2);
+    elsewhere at every position it applies to.  Smallest .. largest ratio over the 6 configurations, in units of the bound:
+        film_row               80 .. 153       film_dropped           71 .. 121       film_halves_swapped    44 .. 83
+        emb_silu_dropped       65 .. 152       temb_sincos_swapped    78 .. 145       stats_other_image      21 .. 2071
+        skip_identity_dropped 320 .. 810       pool_one_tap          515 .. 673       up_shifted            275 .. 414
+        attn_residual_dropped 406 .. 650       attn_heads_new_order  131 .. 353       attn_scale             23 .. 111
+        halves_swapped        415 .. 1214      seam_shifted          250 .. 641       skips_swapped         174 .. 278
+        head_silu_dropped   30000 .. 36000     head_lo_dropped        10 (by construction: the bound IS a tenth of its error)
+    Every mutation is above 10 at every position evaluated; the GPU test can see each of these mistakes wherever it can be made.
+    (With two randn images of one scale at 128^2 the other image's GroupNorm statistics moved the first ResBlock by 4.4 bounds only:
+    the forward-only configurations scale their images, unet_ref.IMAGE_SCALES.  attn_heads_new_order has no place in `top` /
+    `top2`, whose attention has one head.)"""
+    ref, ts, N, x16, acts, head, pos, base = forwards[name]
+    emb = ref.emb(ts)
+    first_hit = ref.cfg.image_size >= 128
+    seen, best = set(), {}
+    for mut in U.FORWARD_MUTATIONS:
+        mpos = ref.forward_positions(x16, acts, head, mut)
+        memb = ref.emb(ts, mut)
+        for p, mp, (st, e, e_img) in zip(pos, mpos, base):
+            if not ref.forward_applies(mut, p, N) or (first_hit and mut in seen):
+                continue
+            mv = ref.position_forward(mp, memb, rnd=False, mut=mut)
+            if p.blk is None:
+                ratio = U.rel_l2(mv, st) / _head_l2_bound(ref, p, st)
+            else:
+                ratio = max([U.rel_l2(mv, st) / (FACTOR * e)] + [m / (FACTOR * r) for m, r in zip(U.rel_l2_images(mv, st), e_img)])
+            print(f"{name} {p.name:18s} {mut:22s} moves the result by {ratio:9.1f} x bound")
+            best[mut] = max(best.get(mut, 0.0), ratio)
+            if ratio > 10.0 or (mut == "head_lo_dropped" and ratio > 10.0 - 1e-9):
+                seen.add(mut)
+            assert ratio > 10.0 - 1e-9, (name, p.name, mut, ratio)
+    layers = [l for p in pos if p.blk is not None for l in p.blk.layers]
+    want = set(U.FORWARD_MUTATIONS)
+    if N == 1:
+        want -= {"film_row", "stats_other_image"}
+    if not any(l.kind == "res" and l.up for l in layers):
+        want.discard("up_shifted")
+    if not any(l.kind == "res" and l.down for l in layers):
+        want.discard("pool_one_tap")
+    if not any(l.kind == "attn" for l in layers):
+        want -= {"attn_residual_dropped", "attn_scale"}
+    if not any(l.kind == "attn" and l.heads > 1 for l in layers):
+        want.discard("attn_heads_new_order")
+    if all(ref.forward_swap_partner(j) is None for j in range(len(ref.spec.input_blocks))):
+        want.discard("skips_swapped")
+    assert seen == want, (want ^ seen, best)
+    assert name not in ("deep", "deep8") or seen == set(U.FORWARD_MUTATIONS)      # these have a place for every one of them
+
+
+@pytest.mark.parametrize("name", list(U.FORWARD_CONFIGS))
+def test_head_restatement_is_inside_the_head_bounds(forwards, name):
+    """The head's hi/lo-split restatement (a_hi w_hi + a_lo w_hi + a_hi w_lo on fp32 statistics) at the rounded forward's last block
+    output meets both head conditions of the GPU test -- every element inside conv(b_a, |w|) + ACC_REL (conv(|a|, |w|) + |bias|),
+    relative L2 below a tenth of the lo-dropped head's error -- while the head without its lo products or without its SiLU is more
+    than 10 times outside the second.  Measured: split 3.2e-7 .. 5.5e-7 relative L2 (worst element 0.007 .. 0.008 of its bound),
+    lo dropped 3.0e-4 .. 3.2e-4 (worst element 3.9 .. 6.5 of its bound: the elementwise condition alone does not separate a plain
+    fp16 head by an order of magnitude, the L2 condition does), SiLU dropped 0.97 .. 1.10."""
+    ref, ts, N, x16, acts, head, pos, base = forwards[name]
+    p, (st, e, _) = pos[-1], base[-1]
+    assert p.blk is None
+    bound = ref.head_bound(p.x_in)
+    l2 = _head_l2_bound(ref, p, st)
+    lo = ref.head_restatement(p.x_in, lo=False)
+    nosilu = ref.head(p.x_in, "head_silu_dropped")
+    worst = lambda t: float(((t - st).abs() / bound).max())
+    print(f"{name}: split {e:.2e} (worst element {worst(head):.4f} of its bound), lo dropped {U.rel_l2(lo, st):.2e} "
+          f"(worst element {worst(lo):.2f}), SiLU dropped {U.rel_l2(nosilu, st):.2e}; L2 bound {l2:.2e}")
+    assert worst(head) <= 1.0 and e <= l2
+    assert U.rel_l2(lo, st) >= 10.0 * l2 * (1 - 1e-12) and U.rel_l2(nosilu, st) > 10.0 * l2
+    import tests.test_gpu_igemm_oracle as I
+    assert U.ACC_REL == I.ACC_REL
+
+
+def test_forward_configurations_reach_every_launch_form():
+    """(HW, C, FiLM, SiLU, pool, split) of every GroupNorm forward and (M, cin, cout, taps, folded skip, upsampled input) of every
+    convolution of the forward configurations (unet_ref.forward_sites), with what the planners give each (no GPU needed).
+    GroupNorm, route x form -- reached:
+        group-local (routes 2 / 3: deep, tiny2, deep8, wide)   SiLU | FiLM + SiLU | SiLU + 2x2 pool | plain (attention)
+        full map (routes 1 / 4: top, top2)                     SiLU | FiLM + SiLU | SiLU + 2x2 pool | plain (attention) | hi/lo split
+      not reachable: group-local x split -- csrc/unet.hip's gn_forward_op sends the head's split form down the full-map route on
+      every map (`!split && local_gn`): deep, tiny2, deep8 and wide run the head's split form through the full-map kernels on 32^2
+      and 16^2 maps.  Inputs still pending (the producer's K slices) reach the group-local route with and without FiLM.
+    Convolutions -- reached: K split above 1 with the slices left pending (deep, tiny2, deep8, wide: conv1 in front of a group-local
+      GroupNorm, conv2 with and without the folded 1x1 skip, splits 2 .. 8); K split above 1 reduced IN PLACE (wide only: conv2
+      behind a separately launched 1x1 skip and the head, K = 2592, split 4); no split; 3x3 with an upsampled input; the folded
+      and the separately launched 1x1 skip; qkv / proj_out GEMMs and the fused 8x8 attention (deep) beside the unfused one on the
+      same map (deep8: 8 images x 4 heads x 12 parts exceed the 256 compute units the fused form may claim; tiny2, wide: heads of 32).
+      In CONFIGS' three, top2, deep8 and in full_config itself NO forward launch is reduced in place: wherever K is long enough to
+      split the map is small and the consumer adds the slices up, and where the forward does not ask for that (full maps, qkv,
+      the separately launched skip) K stays below the 36 K-steps of the split policy or the grid fills the chip already."""
+    from ishapediting_amd import _lib
+    L = _lib.lib()
+    gn_seen, conv_seen = set(), set()
+    per_cfg_inplace = {}
+    cfgs = {name: (fn(), N) for name, (fn, _, N, _) in U.FORWARD_CONFIGS.items()}
+    cfgs["full_config"] = (full_config(), 1)
+    for name, (cfg, N) in cfgs.items():
+        gns, convs = U.forward_sites(build_spec(cfg), N)
+        per_cfg_inplace[name] = 0
+        for g in gns:
+            side = int(round(g.HW ** 0.5))
+            route, kern = C.c_int(), C.create_string_buffer(256)
+            assert L.ishap_group_norm32_plan(N, side, side, g.C, 0, g.pending, g.film, g.act, g.pool, 0, 0, C.byref(route), *[None] * 7,
+                                             kern, len(kern)) == 0, (name, g)
+            local = route.value in (2, 3)
+            assert local == (g.HW <= 1024), (name, g, route.value)          # forward_sites' `small map` is the planner's
+            form = "split" if g.split else ("film" if g.film else ("pool" if g.pool else ("silu" if g.act else "plain")))
+            where = "full" if g.split or not local else "local"             # gn_forward_op: the split form has no group-local kernel
+            if name != "full_config":
+                gn_seen.add((where, form))
+                if g.pending and local:
+                    gn_seen.add(("local-pending", form))
+        for c in convs:
+            ks, slot, kern = C.c_int(), C.c_int(), C.create_string_buffer(256)
+            assert L.ishap_igemm_plan(c.M, c.cin, c.cout, c.taps, c.K2, c.H, c.W, 1, c.pending, c.sums, C.byref(ks), C.byref(slot), kern,
+                                      len(kern)) == 0, (name, c)
+            tags = ["pending" if ks.value > 1 and c.pending else ("in place" if ks.value > 1 else "no split")]
+            if ks.value > 1 and not c.pending:
+                per_cfg_inplace[name] += 1
+            tags += ["ups"] * c.ups + ["folded skip"] * (c.K2 > 0) + ["skip 1x1"] * c.what.endswith("skip") + ["sums"] * c.sums
+            tags += ["qkv"] * c.what.endswith("qkv")
+            if name != "full_config":
+                conv_seen.update(tags)
+                print(f"{name:6s} {c.what:32s} M {c.M:6d} K {c.taps * c.cin + c.K2:5d} -> {c.cout:4d}  split {ks.value}  "
+                      f"{' '.join(tags):24s} {kern.value.decode()}")
+        n_attn = sum(1 for g in gns if g.what.endswith("norm"))
+        n_unfused = sum(1 for c in convs if c.what.endswith("qkv"))
+        if name != "full_config":
+            conv_seen.update(["fused attention"] * (n_attn > n_unfused) + ["unfused attention"] * (n_unfused > 0))
+    print(sorted(gn_seen), sorted(conv_seen), per_cfg_inplace)
+    for where in ("local", "full"):
+        for form in ("silu", "film", "pool", "plain"):
+            assert (where, form) in gn_seen, (where, form)
+    assert ("full", "split") in gn_seen and ("local", "split") not in gn_seen
+    assert ("local-pending", "film") in gn_seen and ("local-pending", "silu") in gn_seen
+    for tag in ("pending", "in place", "no split", "ups", "folded skip", "skip 1x1", "sums", "qkv", "fused attention", "unfused attention"):
+        assert tag in conv_seen, tag
+    assert [k for k, v in per_cfg_inplace.items() if v] == ["wide"], per_cfg_inplace
