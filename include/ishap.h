@@ -304,12 +304,19 @@ typedef struct {
    * `noise` is NULL -- no randn launch and no noise tensor in front of the step.  Philox4x32-10 (Salmon et al., Random123) with
    * key = rng_seed ^ 0x9E3779B97F4A7C15 and counter = {index of the 4-float vector in x (64 bit), rng_offset (64 bit)}; the four
    * words become four standard normals by two Box-Muller pairs (u = ((w >> 8) + 0.5) * 2^-24): element 4 i + j of x takes normal j
-   * of vector i.  noise_out: optional [N][C][HW] that receives the noise used (the dict's "noise"). */
+   * of vector i.  u is the fp32 number: (float)(w >> 8) + 0.5f needs 25 bits from 2^23 on and rounds to even there, so u lies in
+   * (0, 1] and is up to 2^-25 from the exactly formed value -- visible only at u0 -> 1, where the radius sqrt(-2 log u0) goes to
+   * 0 (u0 == 1: both normals of the pair are 0).  noise_out: optional [N][C][HW] that receives the noise used (the dict's "noise"). */
   int rng;
   unsigned long long rng_seed, rng_offset;
   float* noise_out;
 } ishap_step_coefs;
-/* any of sample / pred_xstart / variance / mean may be NULL; noise NULL = zeros (or drawn, ishap_step_coefs::rng); variance_in optional */
+/* any of sample / pred_xstart / variance / mean may be NULL; noise NULL = zeros (or drawn, ishap_step_coefs::rng); variance_in optional.
+ * `variance` receives the LEARNED variance exp(log_variance) also when variance_in is given: variance_in replaces it in the
+ * sample's noise term and in `guided` only (the reference's dict returns the caller's own tensor then, :510, which the caller
+ * already holds).  `nonzero` multiplies the noise term as given, in modes 0, 1 and 3.  A `noise` that is given wins over
+ * `rng`; noise_out is then not written.  clip_denoised is torch's x.clamp(-1, 1): +-inf become +-1, a NaN pred_xstart stays
+ * NaN and reaches mean, sample and guided.  Checked launch by launch against float64 in tests/test_gpu_step_oracle.py. */
 int ishap_ddpm_step(const float* x, const float* model_out, const float* noise, const float* variance_in,
                     const ishap_step_coefs* k, int N, int C, int HW,
                     float* sample, float* pred_xstart, float* variance, float* mean, void* stream);

@@ -26,7 +26,7 @@ __device__ __forceinline__ f32x4 step_noise4(unsigned long long vec, unsigned lo
   f32x4 n;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const float u0 = ((float)(w[2 * h] >> 8) + 0.5f) * 0x1p-24f, u1 = ((float)(w[2 * h + 1] >> 8) + 0.5f) * 0x1p-24f;   // in (0, 1)
+    const float u0 = ((float)(w[2 * h] >> 8) + 0.5f) * 0x1p-24f, u1 = ((float)(w[2 * h + 1] >> 8) + 0.5f) * 0x1p-24f;   // in (0, 1]: + 0.5f rounds to even from 2^23 on (ishap.h)
     const float rad = sqrtf(-2.f * logf(u0));
     float sn, cs;
     sincosf(6.283185307179586f * u1, &sn, &cs);
@@ -72,8 +72,12 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(DdpmStepArgs a) {
       float frac = (v[k] + 1.f) / 2.f;
       float logvar = frac * a.max_log + (1.f - frac) * a.min_log;
       float var = expf(logvar);
-      float x0 = a.sqrt_recip * x[k] - a.sqrt_recipm1 * eps[k];
-      if (a.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+      // sqrt_recip * x - sqrt_recipm1 * eps with the second product fused, written out: which product the compiler contracts
+      // depended on what reads x0 afterwards, and this is the form every build so far has had (the same bits)
+      float x0 = fmaf(-a.sqrt_recipm1, eps[k], a.sqrt_recip * x[k]);
+      // x.clamp(-1, 1) (:299-300) keeps a NaN; fminf(fmaxf(x0, -1.f), 1.f) returns the other operand for one, so an fp16
+      // overflow inside the UNet left the step as a finite latent with -1 in it.  One compare and select on registers.
+      if (a.clip && x0 == x0) x0 = fminf(fmaxf(x0, -1.f), 1.f);
       float mean = a.coef1 * x0 + a.coef2 * x[k];
       float s;
       if (a.mode == DDPM_MODE_DDIM) {
