@@ -59,7 +59,9 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * tracking (ishap_drag_track, ishap_drag_track_scratch_bytes); 22 since the closed-loop drag
                             * (ishap_drag_retarget, ishap_drag_batch_retarget, ishap_drag_batch_retarget_each); 23 since the exact
                             * distance transform (ishap_edt, ishap_edt_scratch_bytes) and the marks and feathered map of the
-                            * regions (ishap_region_plane_marks, ishap_region_plane_feather, ishap_region_plane_feather_scratch_bytes) */
+                            * regions (ishap_region_plane_marks, ishap_region_plane_feather, ishap_region_plane_feather_scratch_bytes);
+                            * 24 since the volume constraints (ishap_constraint_setup, ishap_constraint_setup_scratch_bytes,
+                            * ishap_constraint_loss_grad) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -613,6 +615,32 @@ int ishap_triplane_project(const float* planes, int S, const ishap_decoder_weigh
 int ishap_triplane_points_loss_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* W1T,
                                     const float* W2T, const float* coords, const float* gt, long long npts,
                                     float* dplanes, float* loss, float* logits, void* stream);
+
+/* Volume constraints of a drag edit (csrc/constrain.hip): the same loss at FIXED points with a weight per point,
+ *   L = -(1 / wsum) sum_j w_j BCEWithLogits(decoder(planes)(q_j), g_j),
+ * and d L / d planes without float atomics: the scatter of the points' bilinear taps is built once as a gather list and
+ * summed in a fixed order at every step.  All calls run on `stream`, allocate nothing, do not synchronise with the host,
+ * and on bad sizes (1 <= M <= 2^20, 2 <= S <= 1024) or a NULL argument return an error code and launch nothing;
+ * ishap_constraint_setup_scratch_bytes is -1 for bad sizes.
+ * ishap_constraint_setup, once per edit: coords [M][3] (device) -> row_start int[3 S S + 1], entry int[<= 12 M], entry_w
+ * float[<= 12 M].  The 12 taps of every point (three planes x the four taps of the decoder's bilinear cell, out-of-range
+ * taps dropped) grouped by texel row (p S + y) S + x: row r owns entries row_start[r] .. row_start[r + 1] - 1,
+ * row_start[3 S S] is their number; entry = 4 j + q (point j, tap q: nw ne sw se), ascending within a row; entry_w = the
+ * tap's bilinear weight.  The three arrays depend on coords and S alone (integer atomics count, a ranking pass orders):
+ * identical from run to run.  The ranking costs (entries of a row)^2 / 64 steps per row.
+ * ishap_constraint_loss_grad, once per step, two launches: targets [M] in {0, 1}, weights [M] >= 0, wsum = their sum
+ * (> 0; summed in double by the caller), the gather list of the same coords and S; scratch dfeat float[M][32] and
+ * partials float[ceil(M / 32)].  Outputs: dplanes [3][S][S][32] with EVERY texel written (0.0 where no tap reaches: no
+ * memset is needed), loss[1], optional logits[M] -- the bits ishap_triplane_field_grad returns for the same planes,
+ * weights and coords.  A point of weight 0 contributes exactly 0.  Bitwise repeatable.  As with every region feature the
+ * constraint acts through the planes; unlike the plane weights of the drag loss it is stated at points of the volume. */
+long long ishap_constraint_setup_scratch_bytes(long long M, int S);
+int ishap_constraint_setup(const float* coords, long long M, int S, int* row_start, int* entry, float* entry_w,
+                           void* scratch, long long scratch_bytes, void* stream);
+int ishap_constraint_loss_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* coords,
+                               const float* targets, const float* weights, long long M, double wsum, const int* row_start,
+                               const int* entry, const float* entry_w, float* dfeat, float* partials, float* dplanes,
+                               float* loss, float* logits, void* stream);
 /* direct triplane fitting (drag_utils.py:473-550, train_triplane_opt), one Adam step = these two calls:
  * (1) dplanes [3][S][S][32] += d(BCE + pair_w * mse)/d planes and loss_parts[2] += {BCEWithLogits mean, mse} for the batch
  *     coords[idx[i]] / gt[idx[i]] (i < nbatch; coords [P][3], gt [P], idx int32) and the random pairs r = rand_coords[j],

@@ -190,6 +190,12 @@ SYMBOLS = {
                                                c_void_p, c_void_p]),
     "ishap_triplane_field_grad": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_longlong, c_void_p,
                                             c_void_p, c_void_p]),
+    "ishap_constraint_setup_scratch_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "ishap_constraint_setup": (C.c_int, [c_void_p, C.c_longlong, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, C.c_longlong,
+                                         c_void_p]),
+    "ishap_constraint_loss_grad": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, c_void_p, c_void_p,
+                                             C.c_longlong, C.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
     "ishap_triplane_project": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_longlong, C.c_int,
                                          C.c_float, C.c_float, C.c_float, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
@@ -281,9 +287,10 @@ def lib():
         # 19: ishap_region_select / ishap_region_handles / ishap_region_handles_scratch_bytes / ishap_region_transform;
         # 20: ishap_unet_block_grad; 21: ishap_drag_track / ishap_drag_track_scratch_bytes;
         # 22: ishap_drag_retarget / ishap_drag_batch_retarget / ishap_drag_batch_retarget_each;
-        # 23: ishap_edt / ishap_edt_scratch_bytes / ishap_region_plane_marks / ishap_region_plane_feather[_scratch_bytes]
-        if l.ishap_version() < 23:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 23): rebuild with `python -m ishapediting_amd.build`")
+        # 23: ishap_edt / ishap_edt_scratch_bytes / ishap_region_plane_marks / ishap_region_plane_feather[_scratch_bytes];
+        # 24: ishap_constraint_setup / ishap_constraint_setup_scratch_bytes / ishap_constraint_loss_grad
+        if l.ishap_version() < 24:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 24): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "ddpm.h"
 #include "decode.h"
+#include "constrain.h"
 #include "drag.h"
 #include "track.h"
 #include "retarget.h"
@@ -505,6 +506,30 @@ int ishap_triplane_points_loss_grad(const float* planes, int S, const ishap_deco
   b.planes = planes; b.S = S; b.B = d.B; b.W1 = d.W1; b.b1 = d.b1; b.W2 = d.W2; b.b2 = d.b2; b.w3 = d.w3; b.b3 = d.b3;
   b.W1T = W1T; b.W2T = W2T; b.coords = coords; b.gt = gt; b.npts = npts; b.dplanes = dplanes; b.loss = loss; b.logits = logits;
   return decode_points_bwd_launch(b, (hipStream_t)stream);
+}
+
+long long ishap_constraint_setup_scratch_bytes(long long M, int S) { return constraint_setup_scratch_bytes(M, S); }
+
+int ishap_constraint_setup(const float* coords, long long M, int S, int* row_start, int* entry, float* entry_w, void* scratch,
+                           long long scratch_bytes, void* stream) {
+  ConstraintSetupArgs a;
+  a.coords = coords; a.M = M; a.S = S; a.row_start = row_start; a.entry = entry; a.entry_w = entry_w; a.scratch = scratch;
+  a.scratch_bytes = scratch_bytes;
+  return constraint_setup_launch(a, (hipStream_t)stream);
+}
+
+int ishap_constraint_loss_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* coords,
+                               const float* targets, const float* weights, long long M, double wsum, const int* row_start,
+                               const int* entry, const float* entry_w, float* dfeat, float* partials, float* dplanes,
+                               float* loss, float* logits, void* stream) {
+  DecodeArgs d;
+  ISHAP_TRY(fill_dec(w, d));
+  ConstraintArgs c;
+  c.B = d.B; c.W1 = d.W1; c.b1 = d.b1; c.W2 = d.W2; c.b2 = d.b2; c.w3 = d.w3; c.b3 = d.b3;
+  c.planes = planes; c.S = S; c.coords = coords; c.gt = targets; c.pw = weights; c.npts = M; c.wsum = (float)wsum;
+  c.row_start = row_start; c.entry = entry; c.entry_w = entry_w; c.dfeat = dfeat; c.partials = partials; c.dplanes = dplanes;
+  c.loss = loss; c.logits = logits;
+  return constraint_loss_grad_launch(c, (hipStream_t)stream);
 }
 
 int ishap_triplane_fit_loss_grad(const float* planes, int S, const ishap_decoder_weights* w, const float* coords,

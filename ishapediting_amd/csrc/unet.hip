@@ -750,7 +750,7 @@ static int snap_reserve(T** buf, size_t* cap, size_t need) {
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 23; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 24; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
@@ -780,6 +780,8 @@ int ishap_version(void) { return 23; }  // 2: ishap_mesh_smooth takes the scratc
                                         //     retarget.hip)
                                         // 23: exact distance transform (ishap_edt, ishap_edt_scratch_bytes; edt.hip) and the regions' marks and
                                         //     feathered map (ishap_region_plane_marks, ishap_region_plane_feather[_scratch_bytes]; regions.hip)
+                                        // 24: volume constraints (ishap_constraint_setup[_scratch_bytes], ishap_constraint_loss_grad;
+                                        //     constrain.hip)
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");

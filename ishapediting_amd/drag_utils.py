@@ -657,6 +657,58 @@ class _ClosedLoop:
         return out
 
 
+class VolumeGuidance:
+    """The volume constraints of one guided loop (constraints.py): per step the gradient of
+    L_vol = -(1 / sum w) sum_j w_j BCEWithLogits(decoder(planes of pred_xstart)(q_j), g_j) with respect to the step's latent,
+    composed as DragStuff.reconstruct composes its own -- pred_xstart, prepare_planes, the loss on the planes,
+    ishap_x0_grad_to_cotangent, ishap_grad_to_scaled_f16, the full-depth backward, plus the direct route -- and its mix into the
+    drag gradient.  The points are fixed for the edit: their gather list is built once (MultiTriplane.constraint_setup)."""
+
+    def __init__(self, ds: "DragStuff", cons, ratio: float):
+        self.ds, self.ratio = ds, float(ratio)
+        dev, S = ds.device, ds.args.image_size
+        self.state = ds.decoder.constraint_setup(cons.points, cons.targets, cons.weights, S)
+        self.rng = ds.range.reshape(-1).contiguous() if th.is_tensor(ds.range) else None
+        self.dplanes = th.empty((3, S, S, 32), dtype=th.float32, device=dev)
+        self.cot = th.empty((1, 192, S, S), dtype=th.float32, device=dev)
+        self.cot16 = th.empty((1, 192, S, S), dtype=th.float16, device=dev)
+        self.bits = th.zeros(1, dtype=th.int32, device=dev)
+        self.scale2 = th.ones(2, dtype=th.float32, device=dev)
+
+    def gradient(self, x, i, model_output, loss_out=None):
+        """d L_vol / d x of the step (x, i) whose complete model output is `model_output` and whose forward the model keeps;
+        L_vol goes to loss_out (device float[1]).  A full-depth backward: runs after the forward's tail has been joined."""
+        ds, d, L = self.ds, self.ds.diffusion, _lib.lib()
+        dev, S = ds.device, ds.args.image_size
+        ti = d._t_index(i)
+        # the step kernel with pred_xstart as its only output: the one extra elementwise launch (the guided loop clips, as its step does)
+        x0 = d._step(x, model_output, ti, None, None, True, 0, ("pred_xstart",))["pred_xstart"]
+        planes = prepare_planes(x0, ds.range, ds.middle)
+        ds.decoder.constraint_loss_grad(planes, self.state, dplanes=self.dplanes, loss=loss_out)
+        g_direct = th.empty_like(x)
+        sr = float(np.float32(d.sqrt_recip_alphas_cumprod[ti]))
+        srm1 = float(np.float32(d.sqrt_recipm1_alphas_cumprod[ti]))
+        with th.cuda.device(dev):
+            s = _lib.stream_ptr(dev)
+            _lib.check(L.ishap_x0_grad_to_cotangent(self.dplanes.data_ptr(), _lib.ptr(self.rng), x.data_ptr(), model_output.data_ptr(),
+                                                    sr, srm1, 1, S, g_direct.data_ptr(), self.cot.data_ptr(), s))
+            _lib.check(L.ishap_grad_to_scaled_f16(self.cot.data_ptr(), self.cot16.data_ptr(), self.bits.data_ptr(),
+                                                  self.scale2.data_ptr(), self.cot.numel(), s))
+        dx = ds.model.backward_from_output(self.cot16, self.scale2)
+        grad = th.empty_like(dx)
+        with th.cuda.device(dev):
+            _lib.check(L.ishap_axpby(dx.data_ptr(), g_direct.data_ptr(), 1.0, 1.0, dx.numel(), grad.data_ptr(), _lib.stream_ptr(dev)))
+        return grad
+
+    def mix(self, grad_drag, grad_vol):
+        """grad_drag + (volume_scale / scale) grad_vol: what the guided update multiplies by scale"""
+        out = th.empty_like(grad_drag)
+        with th.cuda.device(self.ds.device):
+            _lib.check(_lib.lib().ishap_axpby(grad_drag.data_ptr(), grad_vol.data_ptr(), 1.0, self.ratio, grad_drag.numel(),
+                                              out.data_ptr(), _lib.stream_ptr(self.ds.device)))
+        return out
+
+
 def synthesize_latent(model, diffusion, args=None, t1=None, t2=0, inter_latent_idx=None, inter_feat_idx=None, img=None,
                       calc_grad=False, **kwargs):
     """drag_utils.py:61-131 (no caller in the reference; kept for the call surface).  calc_grad=True keeps the autograd
@@ -776,6 +828,8 @@ class DragStuff:
         self.sources = None
         self.mesh = None
         self.mesh0 = None
+        self.tri_feat0 = None         # the final latent of the UNEDITED shape [1, 96, S, S] on the device: volume_keep's targets
+        self.last_volume_losses: List[th.Tensor] = []    # after an edit with volume constraints: L_vol per step, device scalars
         self.volume = None            # last decoded occupancy-logit volume [res]^3 on the device
         self.clean = None             # None, or volume.clean_volume keywords (e.g. {"keep": "largest"}): get_mesh cleans the volume
         self.refine = None            # None, or {"iterations": n, "max_move": decoder units}: get_mesh puts the smoothed vertices back
@@ -876,6 +930,7 @@ class DragStuff:
         img = self._denoise(img, self.args.num_steps, each=record, **kwargs)
         assert len(self.feature_guidance) == self.args.w_time
         self.mesh0 = self.get_mesh(tri_feat=img)
+        self.tri_feat0 = img.detach().clone()
         self.mesh = copy.deepcopy(self.mesh0)
         return img
 
@@ -898,7 +953,7 @@ class DragStuff:
         return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10, refine=refine)
 
     # ------------------------------------------------------------------ drag loop (:302-399)
-    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False, trk=None, cl=None):
+    def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False, trk=None, cl=None, vol=None):
         """The guided loop of training() and training_batch(): a generator that yields the progress value after each step and
         returns (img, stop_time) -- the latent and the number of unguided steps left when train_flag stopped it (0: ran to
         the end).  `dk`: a DragKernels or BatchDragKernels after setup; `guidance[n]`: the guidance tap of the n-th step, edit e's
@@ -909,8 +964,15 @@ class DragStuff:
         edit of this shape when there is a valid one, and is saved as one otherwise.
         `trk`: None, or the _LoopTrack of a tracked edit: its call follows the loss's on the same stream and only reads the tap.
         `cl`: None, or the _ClosedLoop of a closed-loop edit (needs `trk`): its retarget follows the tracker's call, so the order on
-        the stream is loss(n), track(n), retarget(n), backward(n); with stop it may clear train_flag before a step (last_stop)."""
+        the stream is loss(n), track(n), retarget(n), backward(n); with stop it may clear train_flag before a step (last_stop).
+        `vol`: None, or the VolumeGuidance of an edit with volume constraints (training() only, one image): once the model output
+        is complete (p_sample_guidance's after_tail) the step adds (volume_scale / scale) d L_vol / d x to the drag gradient -- a
+        second, full-depth backward on the same forward -- and last_volume_losses gets one device scalar per step.  Such an edit
+        runs with reuse_first=False: a restored snapshot holds the network up to the tap only."""
         w_time = self.args.w_time
+        assert vol is None or not reuse_first
+        vol_losses = None if vol is None else th.zeros(w_time, dtype=th.float32, device=self.device)
+        self.last_volume_losses = []
         overlap = _OVERLAP_TAIL if self.overlap_tail is None else self.overlap_tail
         reuse_first = reuse_first and _FIRST_STEP_REUSE and hasattr(self.model, "snapshot_restore")
         stop_time = 0
@@ -958,6 +1020,11 @@ class DragStuff:
                         if self.model.snapshot_save():
                             self._first_step = {"key": key, "out": mo.clone()}
                     first["after_tail"] = keep_first
+            if vol is not None:
+                def add_volume(mo, x=img, i=i):        # after the tail: pred_xstart needs the whole model output
+                    got["grad"] = vol.mix(got["grad"], vol.gradient(x, i, mo, vol_losses[i:i + 1]))
+                    return got["grad"]
+                first["after_tail"] = add_volume
             outs = self.diffusion.p_sample_guidance(self.model, img, i, feat_layer=self.args.feat_layer,
                                                     keep_for_backward=True, want_inter_feat=False,
                                                     noise=self._noise(i, img), between=loss_and_backward,
@@ -976,6 +1043,8 @@ class DragStuff:
                             new[k].data_ptr(), _lib.stream_ptr(self.device)))
                 img = new
             self.last_losses.append(slot)
+            if vol is not None:
+                self.last_volume_losses.append(vol_losses[i])
             yield 1 - i / (w_time - 1.)
         return img, stop_time
 
@@ -994,6 +1063,33 @@ class DragStuff:
             return None
         return regions.plane_weights(keep=keep, free=free, W=width, keep_weight=keep_weight, free_weight=free_weight,
                                      dilate=region_dilate, device=self.device, **({} if region_falloff == 0 else {"falloff": region_falloff}))
+
+    def _volume_constraints(self, scale, volume_keep, carve, fill, volume_scale, volume_points, volume_res):
+        """-> (constraints.VolumeConstraints, volume_scale / scale), or (None, 0.0) when the edit has none: no region given, or
+        volume_scale = 0.  Everything is validated before the edit launches anything."""
+        if volume_keep is None and carve is None and fill is None:
+            return None, 0.0
+        from . import constraints
+        from .triplane_decoder import field_grad_planes
+        vs = float(scale) if volume_scale is None else float(volume_scale)
+        if not np.isfinite(vs):
+            raise ValueError(f"volume_scale must be finite, got {volume_scale!r}")
+        roles = constraints.check_builder_args(volume_keep, carve, fill, volume_res, volume_points, (1.0, 1.0, 1.0))[0]
+        if vs == 0.0:
+            return None, 0.0
+        if float(scale) == 0.0:
+            raise ValueError("scale = 0 with volume constraints: the guided update multiplies the whole gradient by scale, so "
+                             "volume_scale / scale has no value")
+        ref = None
+        if roles[0]:
+            if self.tri_feat0 is None:
+                raise ValueError("volume_keep needs the unedited shape: load one first (update_latent_params, latent_inversion, "
+                                 "train_triplane)")
+            planes0 = prepare_planes(self.tri_feat0, self.range, self.middle)
+            ref = lambda p: field_grad_planes(self.decoder, planes0, p).logits      # noqa: E731
+        cons = constraints.volume_constraints(keep=volume_keep, carve=carve, fill=fill, reference_logits_fn=ref, D=int(volume_res),
+                                              max_points=int(volume_points), device=self.device)
+        return cons, vs / float(scale)
 
     def _closed_loop(self, dk, trk, copts):
         """The re-aiming state of one guided loop; runs the retarget on the tracker's row of zeros (after dk.setup)."""
@@ -1025,7 +1121,8 @@ class DragStuff:
         return out if isinstance(self.last_track, list) else out[0]
 
     def training(self, sources=None, targets=None, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
-                 region_dilate=0, weights=None, track=None, closed_loop=None, region_falloff=0.0):
+                 region_dilate=0, weights=None, track=None, closed_loop=None, region_falloff=0.0, volume_keep=None, carve=None,
+                 fill=None, volume_scale=None, volume_points=16384, volume_res=128):
         """One drag edit of the loaded shape (drag_utils.py:302-399).  Every edit starts from self.w: from the second edit of a
         shape on, the first guided step's forward is restored from a snapshot instead of run (ISHAP_FIRST_STEP_REUSE=0: always
         run); results are bit-identical either way.
@@ -1043,13 +1140,23 @@ class DragStuff:
         its target (the target itself once within `step`), and the touched sets and the preservation term's normalisation follow
         the goals.  Turns tracking on when track is not given.  last_track then also holds goals, remaining and arrived per tracked
         step.  stop: once every handle was within `arrive` voxels of its target `lag` steps ago, the edit finishes with unguided
-        steps (last_stop: the step it stopped before).  step = inf is the open-loop edit, bit for bit."""
+        steps (last_stop: the step it stopped before).  step = inf is the open-loop edit, bit for bit.
+        volume_keep / carve / fill: 3-D regions (Box / Sphere / Voxels of grid size volume_res, or lists) constrained IN THE
+        VOLUME, through the decoder (constraints.py): at up to volume_points voxel centres per role of a
+        [volume_res]^3 grid the decoded occupancy of every step's pred_xstart is pushed towards that of the unedited shape
+        (volume_keep), towards empty (carve) or towards solid (fill); carve and fill override volume_keep, and a voxel in both is a
+        ValueError.  The update becomes sample + variance (scale grad_drag + volume_scale grad_vol); volume_scale defaults to
+        scale.  With no region, or volume_scale = 0, nothing is launched and the edit is the one it always was, bit for bit;
+        constraints with scale = 0 are a ValueError.  A constrained edit costs one full-depth backward more per step and neither
+        uses nor takes the first-step snapshot (an earlier one stays valid).  last_volume_losses: L_vol of every step, device
+        scalars.  track and closed_loop work as without constraints."""
         copts = closed_loop_options(closed_loop)
         topts = track_options(closed_loop_track(copts, track))
         if self.args.num_samples > 1:
             raise NotImplementedError("We can handle only one shape at each time!")
         ch, width = self.model.tap_shape(self.args.feat_layer)
         wmap = self._region_weights(width, cof, keep, free, keep_weight, free_weight, region_dilate, weights, region_falloff=region_falloff)
+        cons, ratio = self._volume_constraints(scale, volume_keep, carve, fill, volume_scale, volume_points, volume_res)
         self.sources = th.tensor(np.asarray(sources), device=self.device, dtype=th.float32)
         self.targets = th.tensor(np.asarray(targets), device=self.device, dtype=th.float32)
         assert self.sources.shape[0] == self.targets.shape[0]
@@ -1062,15 +1169,19 @@ class DragStuff:
         cl = None if copts is None else self._closed_loop(dk, trk, copts)
         # the regions change the loss, not the forward: the first-step snapshot depends on the latent, the timestep and the weights
         # of the model only, so _first_step_key does not hold them and an edit with regions reuses the snapshot of a plain one
-        img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), True,
-                                                      **({} if trk is None else {"trk": trk}), **({} if cl is None else {"cl": cl}))
+        # volume constraints need a full-depth backward, which a restored snapshot cannot give: that edit runs its first forward
+        vol = None if cons is None else VolumeGuidance(self, cons, ratio)
+        img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), vol is None,
+                                                      **({} if trk is None else {"trk": trk}), **({} if cl is None else {"cl": cl}),
+                                                      **({} if vol is None else {"vol": vol}))
         if trk is not None:
             res = trk.results() if cl is None else cl.results(trk.results())
             self.last_track, self._track_ends = res[0], [(self.sources, self.targets)]
         self.mesh = self.get_mesh(img=img, t=stop_time)
 
     def training_part(self, part, rigid, handles=16, start=None, scale=600, cof=0.2, keep=None, keep_weight=4.0, free_weight=0.0,
-                      region_dilate=0, track=None, closed_loop=None, margin=0.0, region_falloff=0.0):
+                      region_dilate=0, track=None, closed_loop=None, margin=0.0, region_falloff=0.0, solid=False, volume_scale=None,
+                      volume_points=16384):
         """A part edit: move `part` (a regions.Voxels, e.g. from regions.select_part) by `rigid` (a regions.Rigid).  The plan --
         regions.plan_part_edit: `handles` sources spread over the part from `start`, each one's target where the motion takes
         it, free = [the part, the part moved] -- is kept as self.part_plan, and the edit is the generator
@@ -1081,13 +1192,23 @@ class DragStuff:
         margin (voxels): the two free regions are grown by it in 3-D (regions.grow), so that the surface which blends the moved
         part into the rest may change too; region_falloff: as training().  margin = 0 and region_falloff = 0 are the edit it
         always was.  The free regions, like all regions and however grown or feathered, constrain their three shadows, not only
-        their volume.  track, closed_loop: as training()."""
+        their volume.  track, closed_loop: as training().
+        solid=True adds volume constraints on the part's own grid (training(): carve, fill, volume_scale, volume_points): the place
+        the part moves to must fill (fill = plan.moved) and what it leaves must clear (carve = part & ~moved; none when the moved
+        part covers the part).  self.part_solid then holds that pair as {"fill": Voxels, "carve": Voxels or None}."""
         from . import regions
         self.part_plan = plan = regions.plan_part_edit(part, rigid, handles=handles, start=start, **({} if margin == 0 else {"margin": margin}))
+        self.part_solid = None
+        vkw = {}
+        if solid:
+            left = part.mask.to(plan.moved.mask.device) & ~plan.moved.mask
+            self.part_solid = {"fill": plan.moved, "carve": regions.Voxels(left) if bool(left.any()) else None}
+            vkw = dict(fill=plan.moved, carve=self.part_solid["carve"], volume_scale=volume_scale, volume_points=volume_points,
+                       volume_res=part.D)
         return self.training(plan.sources, plan.targets, scale=scale, cof=cof, keep=keep, free=plan.free, keep_weight=keep_weight,
                              free_weight=free_weight, region_dilate=region_dilate, region_falloff=region_falloff,
                              **({} if track is None else {"track": track}),
-                             **({} if closed_loop is None else {"closed_loop": closed_loop}))
+                             **({} if closed_loop is None else {"closed_loop": closed_loop}), **vkw)
 
     # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
     def _check_edits(self, K: int):
@@ -1132,7 +1253,8 @@ class DragStuff:
         return self.meshes
 
     def training_batch(self, sources, targets, scale=600, cof=0.2, keep=None, free=None, keep_weight=4.0, free_weight=0.0,
-                       region_dilate=0, weights=None, track=None, closed_loop=None, region_falloff=0.0):
+                       region_dilate=0, weights=None, track=None, closed_loop=None, region_falloff=0.0, volume_keep=None, carve=None,
+                       fill=None, volume_scale=None):
         """K drag edits in one guided loop (the generator of training(), same progress values).  sources / targets: lists of K
         handle arrays (their counts may differ); scale, cof: a float or K values.  keep, free, keep_weight, free_weight,
         region_dilate, region_falloff, weights: as training(), one value for every edit or a list of K (entries of keep / free / weights may be
@@ -1147,7 +1269,12 @@ class DragStuff:
         Every step runs its forward: the first-step snapshot of training() is neither used nor taken here.
         track: as training(), one setting for all edits and one launch pair per tracked step; last_track is then a list of K.
         closed_loop: as training(), one dict for all edits or a list of K (step and arrive per edit; stop and lag must agree): one
-        retarget launch per tracked step for all edits; with stop the loop stops once EVERY edit was done."""
+        retarget launch per tracked step for all edits; with stop the loop stops once EVERY edit was done.
+        volume_keep, carve, fill, volume_scale (training()'s volume constraints) are not available for batched edits:
+        NotImplementedError."""
+        if any(v is not None for v in (volume_keep, carve, fill, volume_scale)):
+            raise NotImplementedError("volume constraints (volume_keep, carve, fill, volume_scale) are not available in training_batch: "
+                                      "run such an edit with training()")
         if len(sources) != len(targets):
             raise ValueError(f"{len(sources)} source sets but {len(targets)} target sets: one of each per edit")
         K = len(sources)
@@ -1211,6 +1338,7 @@ class DragStuff:
                 img = img.unsqueeze(0)
             self.mesh = self.get_mesh(img)
             self.mesh0 = copy.deepcopy(self.mesh)
+            self.tri_feat0 = img.detach().to(self.device).clone()
             self.latent_inversion(tri_feat=img)
             return
         if points is None and cloud is not None:
@@ -1228,6 +1356,7 @@ class DragStuff:
         self.clear_params()
         self.mesh = self.get_mesh(tri_feat=img)
         self.mesh0 = copy.deepcopy(self.mesh)
+        self.tri_feat0 = img.detach().clone()
         mesh_backend.write_mesh(os.path.join(path, "mesh_recon.obj"), self.mesh0)
         self.latent_inversion(tri_feat=img)
 
@@ -1338,6 +1467,7 @@ class DragStuff:
         self.feature_guidance = list(self._sink)
         self.mesh = self.get_mesh(tri_feat=outs["sample"])
         self.mesh0 = copy.deepcopy(self.mesh)
+        self.tri_feat0 = outs["sample"].detach().to(self.device).clone()
         self.variance = [v.clone().detach() for v in outs["variance"]]
         self.variance_noise = [v.clone().detach() for v in outs["variance_noise"]]
 
@@ -1348,6 +1478,7 @@ class DragStuff:
     def clear_params(self):
         self._shape_changed()
         self.mesh0 = None
+        self.tri_feat0 = None
         self.mesh = None
         self.latent_code = None
         self.w0 = None

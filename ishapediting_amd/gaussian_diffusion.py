@@ -223,7 +223,9 @@ class SpacedDiffusion:
         `model_output`: the model's output for (x, t) kept from an earlier call whose kept state the caller has put back
         (UNetModel.snapshot_restore): the model is not called and no tail is planned; `between` and the step run as always
         ("inter_feat" is None).  `after_tail(model_output)`: called once `between` has returned and a planned tail has been
-        joined -- the point at which the model output is complete and a snapshot of the forward can be taken."""
+        joined -- the point at which the model output is complete and a snapshot of the forward can be taken.  When it returns a
+        tensor, the guided update takes that in place of what `between` returned (the drag loop's volume constraints: the drag
+        gradient plus a gradient through pred_xstart, which needs the whole output)."""
         assert denoised_fn is None and cond_fn is None, "not used on the path"
         ti = self._t_index(t)
         if torch.is_tensor(x) and x.requires_grad and torch.is_grad_enabled() and hasattr(model, "backward_from_output"):
@@ -256,7 +258,9 @@ class SpacedDiffusion:
                 raise
             self._close_tail(model, kw)
         if after_tail is not None:
-            after_tail(mo)
+            more = after_tail(mo)
+            if more is not None:              # a gradient that needed the complete model output, already added to `between`'s
+                grad = more
         if guided_scale is not None and grad is not None and variance_noise is None:
             rng = None
             if noise is None:

@@ -38,6 +38,26 @@ class Projection(NamedTuple):
     accepted: torch.Tensor
 
 
+class ConstraintState(NamedTuple):
+    """MultiTriplane.constraint_setup: the points of an edit's volume constraints (coords [M,3], targets [M], weights [M], the
+    weights' sum as a Python float), the gather list of their taps on planes of side S (row_start int32 [3 S S + 1], entry int32
+    and entry_w float32 [12 M], the first row_start[-1] used) and the per-step scratch (dfeat [M,32], partials [ceil(M / 32)])"""
+    coords: torch.Tensor
+    targets: torch.Tensor
+    weights: torch.Tensor
+    wsum: float
+    S: int
+    row_start: torch.Tensor
+    entry: torch.Tensor
+    entry_w: torch.Tensor
+    dfeat: torch.Tensor
+    partials: torch.Tensor
+
+    @property
+    def M(self) -> int:
+        return int(self.coords.shape[0])
+
+
 class _Net:
     """Stands in for the nn.Sequential `net` (axisnetworks.py:526-535): holds the seven tensors on the device."""
 
@@ -148,6 +168,58 @@ class MultiTriplane:
                 _lib.stream_ptr(self.device)))
         return loss, dplanes, logits
 
+    def constraint_setup(self, coords: torch.Tensor, targets: torch.Tensor, weights: torch.Tensor, S: int) -> "ConstraintState":
+        """Once per edit (ishap_constraint_setup): the gather list of the 12 bilinear taps of every constraint point on planes
+        of side S, and the buffers constraint_loss_grad works in.  coords [M, 3], targets [M] in {0, 1}, weights [M] >= 0 with a
+        positive sum (summed here in double: the one host read)."""
+        dev = self.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        coords = coords.detach().to(**f32).reshape(-1, 3).contiguous()
+        targets = targets.detach().to(**f32).reshape(-1).contiguous()
+        weights = weights.detach().to(**f32).reshape(-1).contiguous()
+        M, S = coords.shape[0], int(S)
+        if targets.shape[0] != M or weights.shape[0] != M:
+            raise ValueError(f"constraint_setup: {M} points, {targets.shape[0]} targets, {weights.shape[0]} weights")
+        L = _lib.lib()
+        nbytes = int(L.ishap_constraint_setup_scratch_bytes(M, S))
+        if nbytes < 0:
+            raise ValueError(f"constraint_setup: M = {M}, S = {S} is outside 1 <= M <= 2^20, 2 <= S <= 1024")
+        if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
+            raise ValueError("constraint_setup: weights must be finite and >= 0")
+        wsum = float(weights.double().sum())
+        if not wsum > 0:
+            raise ValueError("constraint_setup: the weights must have a positive sum")
+        row_start = torch.empty(3 * S * S + 1, dtype=torch.int32, device=dev)
+        entry = torch.empty(12 * M, dtype=torch.int32, device=dev)
+        entry_w = torch.empty(12 * M, **f32)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.ishap_constraint_setup(coords.data_ptr(), M, S, row_start.data_ptr(), entry.data_ptr(), entry_w.data_ptr(),
+                                                scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+        return ConstraintState(coords, targets, weights, wsum, S, row_start, entry, entry_w,
+                               torch.empty((M, 32), **f32), torch.empty((M + 31) // 32, **f32))
+
+    def constraint_loss_grad(self, planes: torch.Tensor, state: "ConstraintState", dplanes: Optional[torch.Tensor] = None,
+                             loss: Optional[torch.Tensor] = None, logits: Optional[torch.Tensor] = None):
+        """L_vol = -(1 / sum w) sum_j w_j BCEWithLogits(decoder(planes)(q_j), g_j) at the points of `state` and d L_vol / d planes
+        ([3,S,S,32], every texel written) -> (loss [1], dplanes, logits or None).  dplanes / loss are allocated when None;
+        logits [M] are written only into a tensor given here.  Two launches, no float atomics: bitwise repeatable."""
+        dev = self.device
+        assert planes.dtype == torch.float32 and planes.is_contiguous() and tuple(planes.shape) == (3, state.S, state.S, 32)
+        if dplanes is None:
+            dplanes = torch.empty_like(planes)
+        if loss is None:
+            loss = torch.empty(1, dtype=torch.float32, device=dev)
+        assert dplanes.is_contiguous() and dplanes.shape == planes.shape and dplanes.dtype == torch.float32
+        assert logits is None or (logits.dtype == torch.float32 and logits.numel() == state.M and logits.is_contiguous())
+        w = self.net.weights_c()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ishap_constraint_loss_grad(
+                planes.data_ptr(), state.S, C.byref(w), state.coords.data_ptr(), state.targets.data_ptr(), state.weights.data_ptr(),
+                state.M, state.wsum, state.row_start.data_ptr(), state.entry.data_ptr(), state.entry_w.data_ptr(),
+                state.dfeat.data_ptr(), state.partials.data_ptr(), dplanes.data_ptr(), loss.data_ptr(), _lib.ptr(logits),
+                _lib.stream_ptr(dev)))
+        return loss, dplanes, logits
 
     def fit_loss_grad(self, planes: torch.Tensor, coords: torch.Tensor, gt: torch.Tensor, idx: torch.Tensor,
                       rand_coords: torch.Tensor, rand_noise: torch.Tensor, dplanes: Optional[torch.Tensor] = None,

@@ -43,6 +43,11 @@ the distance, in voxels, at which a handle counts as arrived, and with --stop th
 --track on; the table gains each handle's remaining distance in voxels (after the last tracked step) and whether it has arrived,
 and track.json the goals and remaining distances of every tracked step.
 
+--keep3d-box / --carve-box / --fill-box X0 Y0 Z0 X1 Y1 Z1 (each may repeat) [--volume-scale V] constrain boxes in the VOLUME,
+through the decoder (DragStuff.training(volume_keep=, carve=, fill=)): keep the decoded occupancy of the box,
+empty it, or fill it.  With a part edit, --solid makes the place the part moves to fill and the place it leaves clear
+(training_part(solid=True)).  Either costs one more full-depth backward per guided step.
+
 --time instead measures the renderer alone (device events around `--repeat` calls after a warm-up, medians):
   the 256^3 sphere mesh (~300 k triangles of a few pixels each) at 1024 x 1024, and 2 picture-filling triangles at 1024 x 1024
   (the second shows that large triangles do not serialise on one lane), next to the bytes each call has to move
@@ -218,12 +223,28 @@ def edit(a):
     tkw = {} if track is None else {"track": track}
     if closed is not None:
         tkw["closed_loop"] = closed
-    if part_edit is not None:      # handles and targets come from the part and its motion; the plan is made when the edit is created
+    # volume constraints: boxes constrained in the volume itself, through the decoder
+    from ishapediting_amd.regions import Box
+    vkw = {role: [Box(b[:3], b[3:]) for b in getattr(a, flag)]
+           for role, flag in (("volume_keep", "keep3d_box"), ("carve", "carve_box"), ("fill", "fill_box")) if getattr(a, flag)}
+    if a.solid and part_edit is None:
+        raise SystemExit("--solid belongs to a part edit (--part-box / --part-sphere)")
+    if vkw and part_edit is not None:
+        raise SystemExit("--keep3d-box / --carve-box / --fill-box go with a handle edit; a part edit takes --solid")
+    if vkw:
+        print(f"volume constraints: {({k: len(v) for k, v in vkw.items()})} box(es), volume_scale "
+              f"{a.volume_scale if a.volume_scale is not None else a.scale}")
+        vkw["volume_res"] = min(a.res, 128)
+        if a.volume_scale is not None:
+            vkw["volume_scale"] = a.volume_scale
+        tkw.update(vkw)
+    if part_edit is not None:     # handles and targets come from the part and its motion; the plan is made when the edit is created
         part, rigid, part_frames = part_edit
         frames = frames + part_frames
         final = ds.training_part(part, rigid, handles=a.handles, scale=a.scale, cof=a.cof, keep=keep or None, keep_weight=a.keep_weight,
                                  free_weight=a.free_weight, region_dilate=a.region_dilate, margin=a.margin,
-                                 region_falloff=a.region_falloff, **tkw)
+                                 region_falloff=a.region_falloff, **tkw,
+                                 **({"solid": True, **({"volume_scale": a.volume_scale} if a.volume_scale is not None else {})} if a.solid else {}))
         plan = ds.part_plan
         sources, targets = plan.sources, plan.targets
         part_report = {"voxels": int(part.mask.sum()), "moved_voxels": int(plan.moved.mask.sum()), "margin": a.margin,
@@ -352,6 +373,12 @@ def main():
     p.add_argument("--rotate", default=None, metavar="AX,AY,AZ,DEG", help="rotate the part by DEG degrees about the axis (AX, AY, AZ)")
     p.add_argument("--pivot", default=None, metavar="X,Y,Z", help="the point the rotation turns about (default: the origin)")
     p.add_argument("--translate", default=None, metavar="X,Y,Z", help="then move the part by this vector")
+    for flag, what in (("keep3d", "keep the decoded occupancy of this box as it is"), ("carve", "this box must end up empty"),
+                       ("fill", "this box must end up solid")):
+        p.add_argument(f"--{flag}-box", type=float, nargs=6, action="append", metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                       help=f"volume constraint: {what} (constrained in 3-D through the decoder; one more full-depth backward per step)")
+    p.add_argument("--volume-scale", type=float, default=None, metavar="V", help="guidance scale of the volume constraints (default: --scale)")
+    p.add_argument("--solid", action="store_true", help="with a part edit: the place the part moves to must fill, the place it leaves must clear")
     p.add_argument("--keep-weight", type=float, default=4.0)
     p.add_argument("--free-weight", type=float, default=0.0)
     p.add_argument("--region-dilate", type=int, default=0)
