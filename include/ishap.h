@@ -61,7 +61,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * distance transform (ishap_edt, ishap_edt_scratch_bytes) and the marks and feathered map of the
                             * regions (ishap_region_plane_marks, ishap_region_plane_feather, ishap_region_plane_feather_scratch_bytes);
                             * 24 since the volume constraints (ishap_constraint_setup, ishap_constraint_setup_scratch_bytes,
-                            * ishap_constraint_loss_grad) */
+                            * ishap_constraint_loss_grad); 25 since the sparse high-resolution surface
+                            * (ishap_triplane_decode_bricks, ishap_sparse_*) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -682,6 +683,70 @@ int ishap_surface_count(const float* volume, int res, float level, int method, v
 /* verts: device float[3*vertices]; tris: device int[3*triangles]; same volume / level / method / scratch as the count call */
 int ishap_surface_emit(const float* volume, int res, float level, int method, void* scratch, float* verts, int* tris,
                        void* stream);
+
+/* ------------------------------------------------------------------ sparse high-resolution surface (csrc/sparse_surface.hip)
+ * The marching-cubes surface (`method` 1 above: same tables, same tie rule value - level > 0 = inside, same edge interpolation,
+ * compiled from one header) of the decoder's field on a FINE grid without its dense volume.
+ * Fine grid: R nodes per axis at axis[R] = torch.linspace(-1, 1, R), 9 <= R <= 2048.  Brick: 8^3 cells; nb = ceil((R - 1) / 8)
+ * per axis, id = (bx nb + by) nb + bz.  Brick b samples the 9^3 nodes 8 b .. 8 b + 8 per axis, indices above R - 1 clamped to
+ * R - 1 (duplicates of the last node: they are never cut).  It owns the nodes and cells of local index 0..7 that exist, the
+ * last brick of an axis also node plane 8 when that is the grid's last (R - 1 = 8 nb), and the +x / +y / +z edges leaving its
+ * nodes.  Vertices are in fine-grid coordinates.
+ * State, all caller-allocated device memory: map unsigned char[nb^3] (0 inactive, 1 seeded, 2 grown), slot_map int[nb^3]
+ * (brick -> slot, -1 inactive), list int[<= nb^3] (slot -> brick, discovery order), values float[n][9][9][9] by slot,
+ * reach: ishap_sparse_reach_bytes(n) bytes by slot, ZEROED for a brick when it joins (a byte per sample node, bit a = the edge
+ * leaving the node along axis a carries a vertex of the result).
+ * Every call runs on `stream`, allocates nothing, does not synchronise with the host, and on bad sizes or a NULL argument
+ * returns an error code and launches nothing (the *_bytes queries return -1).  Integer atomics only: bitwise repeatable.
+ *
+ * ishap_sparse_seed_volume: every cell of the coarse dense volume coarse[Rc^3] (x slowest; 2 <= Rc <= 2048) whose 8 corners
+ *   are not all on one side of `level` stores 1 into the map bytes of the bricks that overlap the cell's extent, per axis the
+ *   bricks ishap_sparse_seed_range gives (a host function, the same integer arithmetic on j (R - 1) against b (Rc - 1): brick b
+ *   meets coarse cell j when 8 b (Rc - 1) <= (j + 1)(R - 1) and min(8 b + 8, R - 1)(Rc - 1) >= j (R - 1)).  The map is the
+ *   caller's to clear; any other seed source (every brick, an explicit list) is a map the caller fills with 1.  One thread
+ *   stores the brick box of its coarse cell, so the grids are bounded against each other: R - 1 <= 64 (Rc - 1) (at most 10^3
+ *   bricks a cell), an error otherwise.
+ * ishap_sparse_compact: the marked bricks as an ASCENDING list of ids and count[1] = their number (entries beyond
+ *   list_capacity are dropped, the count is not).  mode 0: all marked bricks, slot_map = rank or -1 (every entry written);
+ *   mode 1: the marked bricks that have no slot yet, slot_map = first_slot + rank; mode 2: all marked bricks, slot_map untouched
+ *   (the order of emission).  scratch: ishap_sparse_compact_scratch_bytes(R), 16-byte aligned.
+ * ishap_triplane_decode_bricks: values[i][9][9][9] (i < nbricks <= 2^21) of bricks[i] -- a separate instantiation of the dense decode's
+ *   tile loop whose coordinates are axis[clamped node index]; no coordinate buffer.  Each logit has the bits
+ *   ishap_triplane_decode_grid(axis, R) gives the same node.
+ * ishap_sparse_grow, one round over the n active bricks list[0 .. n): floods `reach` through the triangles of every brick's
+ *   owned cells (the three edges of a triangle are reached together; a seeded brick reaches every edge its cells cut), records
+ *   each newly reached edge with the brick that owns it, marks (map = 2) the inactive bricks among those of the up-to-4 cells
+ *   around it (cells outside the grid do not exist) and adds the number of newly recorded edge bits to changed[1].  The caller
+ *   compacts (mode 1), decodes and appends the new bricks and repeats until a round leaves changed == 0 and adds no brick.
+ *   Then the owner brick of every reached edge is active, and the reached edges are exactly the vertices of the connected
+ *   components (triangles joined through shared vertices) of the dense-at-R surface that cut a cell of a seeded brick.
+ *   The reached set and the active bricks are that least fixed point whatever the order of the workgroups; the NUMBER of rounds
+ *   is not: a brick reads its neighbours' bytes with plain loads while the same launch ors into them, so it may see a new bit
+ *   in this round or the next.  Host read-backs of a whole extraction: the seed count after the first compaction (coarse seeds:
+ *   the first decode has to be sized), {changed, new bricks} once per round, the counts before emit.
+ * ishap_sparse_surface_count / _emit: `ordered` = the active bricks ascending (compact mode 2).  count: counts[2] =
+ *   {vertices, triangles}; emit: verts float[3 vertices] over (brick ascending, owned node x-slowest, axis x, y, z), tris
+ *   int[3 triangles] over (brick, owned cell x-slowest), neighbour vertices through slot_map -> per-brick vertex offsets.
+ *   scratch: ishap_sparse_surface_scratch_bytes(R, n), 16-byte aligned, the same buffer for both calls. */
+int ishap_sparse_bricks_per_axis(int R);       /* nb, -1 for R outside 9 .. 2048 */
+int ishap_sparse_seed_range(int Rc, int R, int j, int* first, int* last);
+int ishap_sparse_seed_volume(const float* coarse, int Rc, float level, int R, unsigned char* map, void* stream);
+long long ishap_sparse_compact_scratch_bytes(int R);
+int ishap_sparse_compact(const unsigned char* map, int R, int mode, int first_slot, int* slot_map, int* list,
+                         long long list_capacity, unsigned* count, void* scratch, long long scratch_bytes, void* stream);
+int ishap_triplane_decode_bricks(const float* planes, int S, const ishap_decoder_weights* w, const float* axis, int res,
+                                 const int* bricks, long long nbricks, float* values, void* stream);
+long long ishap_sparse_reach_bytes(long long nbricks);
+int ishap_sparse_grow(const float* values, const int* list, long long nbricks, int R, float level, unsigned char* map,
+                      const int* slot_map, unsigned* reach, unsigned* changed, void* stream);
+long long ishap_sparse_surface_scratch_bytes(int R, long long nbricks);
+int ishap_sparse_surface_count(const float* values, const int* ordered, long long nbricks, int R, float level,
+                               const int* slot_map, unsigned* reach, void* scratch, long long scratch_bytes, unsigned* counts,
+                               void* stream);
+int ishap_sparse_surface_emit(const float* values, const int* ordered, long long nbricks, int R, float level,
+                              const int* slot_map, unsigned* reach, void* scratch, long long scratch_bytes, float* verts,
+                              int* tris, void* stream);
+
 /* in place: v <- (v + sum of neighbours) / (1 + number of neighbours), `iterations` Jacobi sweeps (each neighbour once:
  * Open3D's filter_smooth_simple).  box_max > 0: the vertices are in grid coordinates of a [0, box_max]^3 volume and the
  * mesh may be open where the surface leaves the box (edges lying in a box face belong to one triangle); box_max <= 0: the

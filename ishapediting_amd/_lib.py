@@ -250,6 +250,22 @@ SYMBOLS = {
     "ishap_attention8_run": (C.c_int, [C.POINTER(Attn8DescC), C.c_int, C.c_int, c_void_p, C.POINTER(C.c_int)]),
     "ishap_triplane_decode_grid": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_int,
                                              c_void_p, c_void_p]),
+    "ishap_sparse_bricks_per_axis": (C.c_int, [C.c_int]),
+    "ishap_sparse_seed_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ishap_sparse_seed_volume": (C.c_int, [c_void_p, C.c_int, C.c_float, C.c_int, c_void_p, c_void_p]),
+    "ishap_sparse_compact_scratch_bytes": (C.c_longlong, [C.c_int]),
+    "ishap_sparse_compact": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, c_void_p, c_void_p, C.c_longlong, c_void_p, c_void_p,
+                                       C.c_longlong, c_void_p]),
+    "ishap_triplane_decode_bricks": (C.c_int, [c_void_p, C.c_int, C.POINTER(DecoderWeightsC), c_void_p, C.c_int, c_void_p,
+                                               C.c_longlong, c_void_p, c_void_p]),
+    "ishap_sparse_reach_bytes": (C.c_longlong, [C.c_longlong]),
+    "ishap_sparse_grow": (C.c_int, [c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    "ishap_sparse_surface_scratch_bytes": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "ishap_sparse_surface_count": (C.c_int, [c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_float, c_void_p, c_void_p, c_void_p,
+                                             C.c_longlong, c_void_p, c_void_p]),
+    "ishap_sparse_surface_emit": (C.c_int, [c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_float, c_void_p, c_void_p, c_void_p,
+                                            C.c_longlong, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -288,9 +304,10 @@ def lib():
         # 20: ishap_unet_block_grad; 21: ishap_drag_track / ishap_drag_track_scratch_bytes;
         # 22: ishap_drag_retarget / ishap_drag_batch_retarget / ishap_drag_batch_retarget_each;
         # 23: ishap_edt / ishap_edt_scratch_bytes / ishap_region_plane_marks / ishap_region_plane_feather[_scratch_bytes];
-        # 24: ishap_constraint_setup / ishap_constraint_setup_scratch_bytes / ishap_constraint_loss_grad
-        if l.ishap_version() < 24:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 24): rebuild with `python -m ishapediting_amd.build`")
+        # 24: ishap_constraint_setup / ishap_constraint_setup_scratch_bytes / ishap_constraint_loss_grad;
+        # 25: ishap_triplane_decode_bricks / ishap_sparse_*
+        if l.ishap_version() < 25:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 25): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

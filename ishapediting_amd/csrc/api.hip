@@ -610,6 +610,16 @@ int ishap_triplane_decode_grid(const float* planes, int S, const ishap_decoder_w
   return triplane_decode_launch(d, (hipStream_t)stream);
 }
 
+int ishap_triplane_decode_bricks(const float* planes, int S, const ishap_decoder_weights* w, const float* axis, int res,
+                                 const int* bricks, long long nbricks, float* values, void* stream) {
+  DecodeArgs d;
+  ISHAP_TRY(fill_dec(w, d));
+  ISHAP_REQUIRE(planes && axis && bricks && values, "null argument");
+  ISHAP_REQUIRE(nbricks >= 1 && nbricks <= (1ll << 21), "decode bricks: 1 <= bricks <= 2^21");
+  d.planes = planes; d.S = S; d.lin = axis; d.res = res; d.npts = 729 * nbricks; d.out = values;
+  return triplane_decode_bricks_launch(d, bricks, nbricks, (hipStream_t)stream);
+}
+
 // ---- headless rendering (csrc/render.hip) ----
 long long ishap_render_scratch_bytes(long long nverts, long long ntris, int width, int height) {
   return render_scratch_bytes(nverts, ntris, width, height);

@@ -41,6 +41,9 @@ struct DecodeArgs {
   float* out = nullptr;            // [npts] logits
 };
 int triplane_decode_launch(const DecodeArgs& a, hipStream_t s);
+// the 9^3 sample nodes of `nbricks` bricks of the fine grid a.lin [a.res] (brick ids (bx nb + by) nb + bz, nb = ceil((res - 1) / 8))
+// into a.out [nbricks][9][9][9]; a.npts = 729 nbricks, a.coords unused
+int triplane_decode_bricks_launch(const DecodeArgs& a, const int* bricks, long long nbricks, hipStream_t s);
 
 struct DecBwdArgs {
   const float* planes = nullptr;   // [3][S][S][32]

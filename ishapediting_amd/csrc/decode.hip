@@ -55,7 +55,12 @@ int planes_prepare_launch(const float* latent, const float* rng, const float* mi
   return 0;
 }
 
-__global__ __launch_bounds__(512) void triplane_decode_kernel(DecodeArgs a) {
+// The tile loop of the decode kernels.  BRICKS = false: the points / dense-grid kernel.  BRICKS = true: the points are the 9^3
+// sample nodes of the listed bricks of a fine grid (csrc/sparse_surface.hip), point -> (slot, node) -> axis[clamped index], so no
+// coordinate buffer exists; everything after the coordinate fetch is the same code, and a node's logit has the bits the dense
+// grid decode gives it at the same res.
+template <bool BRICKS>
+__device__ __forceinline__ void decode_tiles(const DecodeArgs& a, const int* __restrict__ bricks, int nb) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   half_t* sW1h = reinterpret_cast<half_t*>(lds);          // [128][LDH] hi parts, K in fragment order
   half_t* sW1l = sW1h + 128 * LDH;
@@ -96,7 +101,14 @@ __global__ __launch_bounds__(512) void triplane_decode_kernel(DecodeArgs a) {
     const bool valid = pt < a.npts;
     if (!valid) pt = a.npts - 1;
     float cx, cy, cz;
-    if (a.coords) {
+    if constexpr (BRICKS) {   // values[slot][9][9][9]: brick (bx, by, bz) samples nodes 8 b .. 8 b + 8, clamped to res - 1
+      const unsigned p32 = (unsigned)pt;              // 729 * 2^21 points at the most
+      const unsigned slot = p32 / 729u, node = p32 - 729u * slot;
+      const unsigned id = (unsigned)bricks[slot], unb = (unsigned)nb, m = (unsigned)a.res - 1u;
+      const unsigned bxy = id / unb, bz = id - bxy * unb, bx = bxy / unb, by = bxy - bx * unb;
+      const unsigned lx = node / 81u, lyz = node - 81u * lx, ly = lyz / 9u, lz = lyz - 9u * ly;
+      cx = a.lin[min(8u * bx + lx, m)]; cy = a.lin[min(8u * by + ly, m)]; cz = a.lin[min(8u * bz + lz, m)];
+    } else if (a.coords) {
       cx = a.coords[pt * 3 + 0]; cy = a.coords[pt * 3 + 1]; cz = a.coords[pt * 3 + 2];
     } else {   // dense grid, x slowest (visualize.py:84-86, indexing='ij')
       const int res = a.res;
@@ -221,15 +233,39 @@ __global__ __launch_bounds__(512) void triplane_decode_kernel(DecodeArgs a) {
       }
     }
     partial += __shfl_xor(partial, 32);
-    if (h == 0 && valid) a.out[pt] = partial + b3;
+    if constexpr (BRICKS) {     // the point index is rebuilt from the tile: nothing of the fetch stays live across the MLP
+      if (h == 0 && tile * 32 + l31 < a.npts) a.out[tile * 32 + l31] = partial + b3;
+    } else {
+      if (h == 0 && valid) a.out[pt] = partial + b3;
+    }
   }
+}
+
+__global__ __launch_bounds__(512) void triplane_decode_kernel(DecodeArgs a) { decode_tiles<false>(a, nullptr, 0); }
+__global__ __launch_bounds__(512) void triplane_decode_bricks_kernel(DecodeArgs a, const int* __restrict__ bricks, int nb) {
+  decode_tiles<true>(a, bricks, nb);
+}
+
+static constexpr size_t DECODE_SMEM = (size_t)4 * 128 * LDH * sizeof(half_t) + (size_t)(64 * LDB + 3 * 128) * sizeof(float);
+
+int triplane_decode_bricks_launch(const DecodeArgs& a, const int* bricks, long long nbricks, hipStream_t s) {
+  ISHAP_REQUIRE(a.S >= 1, "triplane decode: plane size");
+  ISHAP_REQUIRE(a.res >= 9 && a.res <= 2048, "decode bricks: 9 <= res <= 2048");
+  ISHAP_REQUIRE(nbricks >= 1 && nbricks <= (1ll << 21), "decode bricks: 1 <= bricks <= 2^21");
+  ISHAP_REQUIRE(a.lin && bricks && a.out && a.npts == 729 * nbricks, "decode bricks: null argument");
+  ISHAP_TRY(ishap_set_max_lds((const void*)triplane_decode_bricks_kernel, (int)DECODE_SMEM));
+  const long long ntiles = (a.npts + 31) / 32;
+  const int blocks = (int)std::min<long long>((ntiles + 7) / 8, 256);
+  hipLaunchKernelGGL(triplane_decode_bricks_kernel, dim3(blocks), dim3(512), DECODE_SMEM, s, a, bricks, (a.res - 1 + 7) / 8);
+  ISHAP_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 int triplane_decode_launch(const DecodeArgs& a, hipStream_t s) {
   ISHAP_REQUIRE(a.npts > 0, "triplane decode: no points");
   ISHAP_REQUIRE(a.S >= 1, "triplane decode: plane size");
   ISHAP_REQUIRE(a.coords != nullptr || (a.lin != nullptr && a.res > 0), "either coords or a grid axis");
-  const size_t smem = (size_t)4 * 128 * LDH * sizeof(half_t) + (size_t)(64 * LDB + 3 * 128) * sizeof(float);
+  const size_t smem = DECODE_SMEM;
   ISHAP_TRY(ishap_set_max_lds((const void*)triplane_decode_kernel, (int)smem));
   long long ntiles = (a.npts + 31) / 32;
   int blocks = (int)std::min<long long>((ntiles + 7) / 8, 256);

@@ -11,9 +11,11 @@
 //           number of triangles; per-block sums          -> exclusive scan of each array of block sums (scan.h), totals
 //   emit  : vertices (block-local scan + block offset), per-voxel vertex offsets, then triangles through the
 //           (owner voxel, edge type) -> vertex index lookup.
+// The inside test, the tie rule and the edge interpolation are surface_rules.h, shared with the brick surface (sparse_surface.hip).
 #include "common.h"
 #include "mc_table.h"
 #include "scan.h"
+#include "surface_rules.h"
 #include "winding.h"
 
 namespace {
@@ -49,7 +51,7 @@ struct SurfArgs {
 __device__ __forceinline__ unsigned corner_bits(const SurfArgs& a, int x, int y, int z, bool& cell) {
   const int r = a.res;
   const long long p = ((long long)x * r + y) * r + z;
-  const bool in0 = a.vol[p] - a.level > 0.f;
+  const bool in0 = surf_inside(a.vol[p], a.level);
   const bool hx = x + 1 < r, hy = y + 1 < r, hz = z + 1 < r;
   cell = hx && hy && hz;
   unsigned bits = 0;
@@ -57,7 +59,7 @@ __device__ __forceinline__ unsigned corner_bits(const SurfArgs& a, int x, int y,
   for (int c = 0; c < 8; ++c) {
     const bool ok = (!(c & 1) || hx) && (!(c & 2) || hy) && (!(c & 4) || hz);
     bool in = in0;
-    if (ok && c) in = a.vol[p + ((long long)(c & 1) * r + ((c >> 1) & 1)) * r + ((c >> 2) & 1)] - a.level > 0.f;
+    if (ok && c) in = surf_inside(a.vol[p + ((long long)(c & 1) * r + ((c >> 1) & 1)) * r + ((c >> 2) & 1)], a.level);
     bits |= (in ? 1u : 0u) << c;
   }
   return bits;
@@ -135,10 +137,7 @@ __global__ __launch_bounds__(SB_THREADS) void surf_emit_vertices_kernel(SurfArgs
       if (!((m[i] >> (d - 1)) & 1)) continue;
       const int dx = d & 1, dy = (d >> 1) & 1, dz = (d >> 2) & 1;
       const float vb = a.vol[p + ((long long)dx * r + dy) * r + dz] - a.level;
-      const float t = va / (va - vb);
-      verts[3LL * idx + 0] = (float)x + t * (float)dx;
-      verts[3LL * idx + 1] = (float)y + t * (float)dy;
-      verts[3LL * idx + 2] = (float)z + t * (float)dz;
+      surf_edge_vertex(verts + 3LL * idx, x, y, z, dx, dy, dz, surf_edge_t(va, vb));
       ++idx;
     }
   }

@@ -834,6 +834,9 @@ class DragStuff:
         self.clean = None             # None, or volume.clean_volume keywords (e.g. {"keep": "largest"}): get_mesh cleans the volume
         self.refine = None            # None, or {"iterations": n, "max_move": decoder units}: get_mesh puts the smoothed vertices back
                                       # on the decoder's zero level set and keeps its analytic normals (mesh.OccupancyMesh refine)
+        self.mesh_resolution = None   # None, or an int above args.shape_resolution (up to 2048): get_mesh returns the surface at THAT
+                                      # resolution, cut from bricks near the surface only (mesh.SparseOccupancyMesh) and seeded from the
+                                      # shape_resolution volume, which stays `self.volume` for the metrics, regions and parts
         self.noise = []
         self.variance = []
         self.variance_noise = []
@@ -935,21 +938,36 @@ class DragStuff:
         return img
 
     # ------------------------------------------------------------------ decode (:282-300)
+    def _sparse_mesh_resolution(self):
+        """mesh_resolution when it asks for the sparse path (an int above shape_resolution), else None"""
+        r = self.mesh_resolution
+        if r is None:
+            return None
+        if isinstance(r, bool) or int(r) != r or not 9 <= int(r) <= 2048:
+            raise ValueError(f"mesh_resolution must be None or an int in 9 .. 2048, not {r!r}")
+        if int(r) - 1 > 64 * (self.args.shape_resolution - 1):
+            raise ValueError(f"mesh_resolution {r} is too fine for a shape_resolution of {self.args.shape_resolution}: the volume "
+                             f"seeds meshes up to {64 * (self.args.shape_resolution - 1) + 1}")
+        return int(r) if int(r) > self.args.shape_resolution else None
+
     def get_mesh(self, tri_feat=None, img=None, t=0):
         if tri_feat is None:
             img = img if img is not None else th.randn((1, 96, self.args.image_size, self.args.image_size)).to(self.device)
             tri_feat = self._denoise(img, t)
         self.tri_feat = tri_feat
         refine = None
-        if self.refine is None:
+        sparse = self._sparse_mesh_resolution()
+        if self.refine is None and sparse is None:
             self.volume = decode_volume(self.decoder, tri_feat.to(self.device), self.range, self.middle,
                                         self.args.shape_resolution)
         else:                         # decode_volume's two halves, keeping the planes for the projection (get_meshes comes here too)
             planes = prepare_planes(tri_feat.to(self.device), self.range, self.middle)
             self.volume = decode_planes_grid(self.decoder, planes, self.args.shape_resolution)
-            refine = dict(self.refine, decoder=self.decoder, planes=planes)
+            refine = None if self.refine is None else dict(self.refine, decoder=self.decoder, planes=planes)
         if self.clean is not None:    # floaters / cavities out before the surface; self.volume is then the cleaned volume
             self.volume = clean_volume(self.volume, **self.clean)
+        if sparse is not None:        # the volume decoded anyway seeds the bricks of the fine grid
+            return mesh_backend.sparse_volume_to_mesh(self.decoder, planes, sparse, self.volume, smooth_iterations=10, refine=refine)
         return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10, refine=refine)
 
     # ------------------------------------------------------------------ drag loop (:302-399)

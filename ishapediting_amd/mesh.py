@@ -4,12 +4,14 @@ vertices/res*2-1; drag_utils.py:300 = Open3D filter_smooth_simple(10); meshProce
 Those are third-party CPU calls outside the kernel path.  Here the surface is produced ON THE
 DEVICE by csrc/surface.hip (marching cubes on the resident volume, smoothing, nearest-neighbour Chamfer on area-uniform
 surface samples) through the C ABI (ishap_surface_count / _emit, ishap_mesh_smooth, ishap_chamfer); this module only
-allocates the outputs.  The backend is an explicit choice, never an import probe: BACKEND = "device" (default) or
+allocates the outputs.  extract_surface_sparse / SparseOccupancyMesh cut the same surface at resolutions the dense volume cannot
+reach, from bricks near the surface only (csrc/sparse_surface.hip).  The backend is an explicit choice, never an import probe: BACKEND = "device" (default) or
 "third_party" (the reference's own PyMCubes / Open3D calls on the host, for users who have them and want that exact mesh).
 """
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -17,7 +19,8 @@ import torch
 from . import _lib
 
 
-MAX_OBJ_VERTICES = 4_000_000      # text export limit (a 256^3 shape has well under a million surface vertices)
+MAX_OBJ_VERTICES = 4_000_000      # text export of a DENSE volume's mesh: more is noise, not a surface (a 256^3 shape has well under
+                                  # a million vertices); sparse high-resolution meshes have their own limit, MAX_SPARSE_OBJ_VERTICES
 BACKEND = "device"                # "device" | "open3d" | "third_party"; set explicitly, results never depend on what happens to be installed
 METHODS = {"marching_tetrahedra": 0, "marching_cubes": 1}
 
@@ -265,6 +268,214 @@ class OccupancyMesh:
         return m
 
 
+class SparseSurfaceInfo(NamedTuple):
+    """extract_surface_sparse: active bricks at the end, growth rounds that changed something (may vary from run to run with the
+    scheduling of a round's workgroups; the other fields and the mesh do not), points decoded (729 per brick) and the bytes of
+    device memory the call held at its end (maps, lists, values and reached bits with their reserve, scratch, the mesh)"""
+    bricks: int
+    rounds: int
+    points: int
+    bytes: int
+
+
+SPARSE_MIN_RES, SPARSE_MAX_RES = 9, 2048
+SPARSE_MAX_RATIO = 64      # a coarse seed volume [Rc]^3 serves fine grids with res - 1 <= 64 (Rc - 1): a coarse cell then marks at most 10^3 bricks
+
+
+def extract_surface_sparse(decoder, planes: torch.Tensor, res: int, seeds, level: float = 0.0, max_rounds: int = 64,
+                           max_bricks: int = 1 << 20):
+    """The marching-cubes surface of the decoder's field on the FINE grid linspace(-1, 1, res)^3 (9 <= res <= 2048) without its
+    dense volume: only bricks of 8^3 cells near the surface are decoded (triplane_decoder.decode_bricks) and cut
+    (csrc/sparse_surface.hip; include/ishap.h states the scheme).  -> (vertices [V,3] float32 in fine-grid coordinates,
+    triangles [F,3] int32, SparseSurfaceInfo), on the device.
+    seeds: a coarse dense volume [Rc,Rc,Rc] of the same field (every brick that overlaps one of its crossing cells), "all"
+    (every brick), or an int tensor [n,3] of brick coordinates (bx, by, bz), each in 0 .. ceil((res - 1) / 8) - 1.
+    The result is exactly the connected components (triangles joined through shared vertices) of
+    extract_surface(decode_planes_grid(decoder, planes, res), level) that cut a cell of a seeded brick, followed to their end
+    through bricks the seeds did not name; with seeds="all" it is that mesh (the same vertices and triangles bit for bit, in
+    brick order instead of voxel order).  Repeats bit for bit, whatever the order of the seeds.
+    The growth stops when a round changes nothing; more than `max_rounds` rounds or `max_bricks` active bricks (2916 bytes of
+    values each) raise RuntimeError -- never a partial mesh.  The host waits for the device at the count read-backs only: the
+    seed count (coarse seeds only: the first decode has to be sized), one per growth round, one before the mesh is allocated.
+    A coarse seed volume [Rc]^3 must satisfy res - 1 <= 64 (Rc - 1).
+    info.rounds is NOT a property of the field: whether a brick sees a neighbour's newly reached edges in the same round or the
+    next depends on how the round's workgroups were scheduled.  The mesh, info.bricks and info.points are (the reached set is a
+    least fixed point); rounds has a lower bound (the brick distance the surface travels from the seeds) and may differ run to run."""
+    from . import triplane_decoder as td              # triplane_decoder has no need of this module
+    _need_gpu(planes, "extract_surface_sparse")
+    res, max_rounds, max_bricks = int(res), int(max_rounds), int(max_bricks)
+    L = _lib.lib()
+    nb = int(L.ishap_sparse_bricks_per_axis(res))
+    if nb < 0:
+        raise ValueError(f"extract_surface_sparse: res = {res} is outside {SPARSE_MIN_RES} .. {SPARSE_MAX_RES}")
+    assert planes.dtype == torch.float32 and planes.is_contiguous() and planes.dim() == 4 and planes.shape[0] == 3 and planes.shape[3] == 32
+    dev = planes.device
+    N = nb ** 3
+    i32 = dict(dtype=torch.int32, device=dev)
+    bmap = torch.zeros(N, dtype=torch.uint8, device=dev)
+    slot_map = torch.empty(N, **i32)
+    blist = torch.empty(N + 1, **i32)                  # slot -> brick id, discovery order
+    counters = torch.zeros(2, **i32)                   # {edge bits a growth round recorded, bricks a compaction listed}
+    cbytes = int(L.ishap_sparse_compact_scratch_bytes(res))
+    cscratch = torch.empty(cbytes, dtype=torch.uint8, device=dev)
+    axis = torch.linspace(-1, 1, res).to(dev)          # the table decode_planes_grid reads
+    held = [bmap, slot_map, blist, cscratch]
+    n0 = None
+    with torch.cuda.device(dev):
+        s = _lib.stream_ptr(dev)
+        if isinstance(seeds, str):
+            if seeds != "all":
+                raise ValueError(f'extract_surface_sparse: seeds must be a coarse volume, "all" or brick coordinates [n,3], not {seeds!r}')
+            bmap.fill_(1)
+            n0 = N
+        elif torch.is_tensor(seeds) and seeds.is_floating_point():
+            if seeds.dim() != 3 or not (seeds.shape[0] == seeds.shape[1] == seeds.shape[2]) or not 2 <= seeds.shape[0] <= SPARSE_MAX_RES:
+                raise ValueError(f"extract_surface_sparse: a coarse seed volume is [Rc,Rc,Rc] with 2 <= Rc <= {SPARSE_MAX_RES}, not {tuple(seeds.shape)}")
+            if res - 1 > SPARSE_MAX_RATIO * (seeds.shape[0] - 1):
+                raise ValueError(f"extract_surface_sparse: a coarse volume of {seeds.shape[0]}^3 seeds fine grids up to "
+                                 f"{SPARSE_MAX_RATIO * (seeds.shape[0] - 1) + 1} (res - 1 <= {SPARSE_MAX_RATIO} (Rc - 1)), not {res}")
+            coarse = seeds.detach().to(device=dev, dtype=torch.float32).contiguous()
+            _lib.check(L.ishap_sparse_seed_volume(coarse.data_ptr(), coarse.shape[0], float(level), res, bmap.data_ptr(), s))
+        else:
+            b = torch.as_tensor(seeds)
+            if b.is_floating_point() or b.dim() != 2 or b.shape[1] != 3:
+                raise ValueError("extract_surface_sparse: explicit seeds are an int tensor [n,3] of brick coordinates")
+            b = b.detach().to(torch.int64).cpu()
+            if b.numel() and (int(b.min()) < 0 or int(b.max()) >= nb):
+                raise ValueError(f"extract_surface_sparse: brick coordinates must lie in 0 .. {nb - 1} (res = {res})")
+            ids = torch.unique((b[:, 0] * nb + b[:, 1]) * nb + b[:, 2])
+            bmap[ids.to(dev)] = 1
+            n0 = int(ids.numel())
+        _lib.check(L.ishap_sparse_compact(bmap.data_ptr(), res, 0, 0, slot_map.data_ptr(), blist.data_ptr(), N,
+                                          counters[1:].data_ptr(), cscratch.data_ptr(), cbytes, s))
+        if n0 is None:
+            n0 = int(counters[1])                      # read-back: the seed count
+        empty = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), **i32))
+        if n0 == 0:
+            return empty[0], empty[1], SparseSurfaceInfo(0, 0, 0, sum(t.numel() * t.element_size() for t in held))
+        if n0 > max_bricks:
+            raise RuntimeError(f"extract_surface_sparse: the seeds name {n0} bricks, more than max_bricks = {max_bricks}")
+        n, rounds = n0, 0
+        rbytes = int(L.ishap_sparse_reach_bytes(1))
+        # values and reached bits live in buffers with room to grow: a round that adds bricks decodes them in place behind the
+        # others; a full buffer is replaced by one half as large again (a copy per growth of 1.5x, not per round)
+        cap = min(N, n + n // 4 + 16)
+        values = torch.empty((cap, 729), dtype=torch.float32, device=dev)
+        reach = torch.zeros((cap, rbytes), dtype=torch.uint8, device=dev)
+        td._decode_bricks_into(decoder, planes, axis, res, blist[:n], values[:n])
+        while True:
+            counters.zero_()
+            _lib.check(L.ishap_sparse_grow(values.data_ptr(), blist.data_ptr(), n, res, float(level), bmap.data_ptr(),
+                                           slot_map.data_ptr(), reach.data_ptr(), counters.data_ptr(), s))
+            _lib.check(L.ishap_sparse_compact(bmap.data_ptr(), res, 1, n, slot_map.data_ptr(), blist[n:].data_ptr(), N - n,
+                                              counters[1:].data_ptr(), cscratch.data_ptr(), cbytes, s))
+            changed, new = (int(c) for c in counters.tolist())     # read-back: one per growth round
+            if changed == 0 and new == 0:
+                break
+            rounds += 1
+            if rounds > max_rounds:
+                raise RuntimeError(f"extract_surface_sparse: the surface was still growing after max_rounds = {max_rounds} rounds "
+                                   f"({n} bricks active)")
+            if new:
+                if n + new > max_bricks:
+                    raise RuntimeError(f"extract_surface_sparse: round {rounds} reaches {n + new} active bricks, more than "
+                                       f"max_bricks = {max_bricks}")
+                if n + new > cap:
+                    cap = min(N, max(n + new, cap + cap // 2))
+                    grown = torch.empty((cap, 729), dtype=torch.float32, device=dev)
+                    grown[:n] = values[:n]
+                    values = grown
+                    grown = torch.zeros((cap, rbytes), dtype=torch.uint8, device=dev)
+                    grown[:n] = reach[:n]
+                    reach = grown
+                    del grown
+                td._decode_bricks_into(decoder, planes, axis, res, blist[n:n + new], values[n:n + new])
+                n += new
+        # emission order: ascending brick id, so the order of discovery does not show
+        ordered = torch.empty(n + 1, **i32)
+        _lib.check(L.ishap_sparse_compact(bmap.data_ptr(), res, 2, 0, slot_map.data_ptr(), ordered.data_ptr(), n,
+                                          counters[1:].data_ptr(), cscratch.data_ptr(), cbytes, s))
+        ebytes = int(L.ishap_sparse_surface_scratch_bytes(res, n))
+        escratch = torch.empty(ebytes, dtype=torch.uint8, device=dev)
+        counts = torch.zeros(2, **i32)
+        common = (values.data_ptr(), ordered.data_ptr(), n, res, float(level), slot_map.data_ptr(), reach.data_ptr(),
+                  escratch.data_ptr(), ebytes)
+        _lib.check(L.ishap_sparse_surface_count(*common, counts.data_ptr(), s))
+        nv, nt = (int(c) for c in counts.tolist())                 # read-back: output sizes
+        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        tris = torch.empty((nt, 3), **i32)
+        if nv and nt:
+            _lib.check(L.ishap_sparse_surface_emit(*common, verts.data_ptr(), tris.data_ptr(), s))
+        held += [values, reach, ordered, escratch, verts, tris]
+    return verts, tris, SparseSurfaceInfo(n, rounds, 729 * n, sum(t.numel() * t.element_size() for t in held))
+
+
+class SparseOccupancyMesh(OccupancyMesh):
+    """OccupancyMesh at a resolution the dense volume cannot reach: the surface of the decoder's field on the fine grid
+    linspace(-1, 1, res)^3 (res up to 2048), cut by extract_surface_sparse from the bricks that `coarse` -- the dense volume the
+    caller has anyway, e.g. DragStuff.volume at shape_resolution, after any cleaning -- shows a crossing in, and followed to its
+    end.  `.volume` is that coarse volume; `.info` the SparseSurfaceInfo once the mesh is built.  Same public surface as
+    OccupancyMesh: vertices (the reference's convention g / res * 2 - 1 of the fine grid coordinates g), triangles, counts,
+    compute_vertex_normals, to_open3d, deepcopy; smoothing with box_max = res - 1.
+    refine: None, or OccupancyMesh's dict WITHOUT decoder / planes (they are this mesh's own): the smoothed vertices go back on
+    the zero level set through the same projection, by default no further than one FINE voxel.  It inherits what `_refined`
+    documents: the projection works at the sampling convention 2 g / (res - 1) - 1, the vertices are handed out at
+    g / res * 2 - 1, and the two differ by up to one voxel."""
+
+    def __init__(self, decoder, planes: torch.Tensor, res: int, coarse: torch.Tensor, smooth_iterations: int = 10, refine=None,
+                 max_rounds: int = 64, max_bricks: int = 1 << 20):
+        if not SPARSE_MIN_RES <= int(res) <= SPARSE_MAX_RES:
+            raise ValueError(f"SparseOccupancyMesh: res = {res} is outside {SPARSE_MIN_RES} .. {SPARSE_MAX_RES}")
+        super().__init__(coarse, int(res), smooth_iterations,
+                         refine=None if refine is None else dict(refine, decoder=decoder, planes=planes))
+        self.decoder, self.planes = decoder, planes
+        self.max_rounds, self.max_bricks = int(max_rounds), int(max_bricks)
+        self.info = None
+
+    def _build(self):
+        if self._mesh is None:
+            v, t, self.info = extract_surface_sparse(self.decoder, self.planes, self.res, self.volume, 0.0, self.max_rounds,
+                                                     self.max_bricks)
+            v = smooth_mesh(v, t, self.smooth_iterations, box_max=float(self.res - 1))
+            if self.refine is not None and v.shape[0] > 0:
+                v = self._refined(v)
+            self._mesh = (v / self.res * 2 - 1, t)
+        return self._mesh
+
+    def counts(self):
+        v, t = self._build()
+        return int(v.shape[0]), int(t.shape[0])
+
+    def __deepcopy__(self, memo):
+        m = SparseOccupancyMesh(self.decoder, self.planes, self.res, self.volume.clone(), self.smooth_iterations,
+                                max_rounds=self.max_rounds, max_bricks=self.max_bricks)      # decoder and planes are shared
+        m.refine, m.info = self.refine, self.info
+        if self._mesh is not None:
+            m._mesh = (self._mesh[0].clone(), self._mesh[1].clone())
+        if self._field_normals is not None:
+            m._field_normals = self._field_normals.clone()
+            m.refinement = self.refinement
+        if self._vnormals is not None:
+            m._vnormals = self._vnormals.clone()
+        return m
+
+
+def sparse_volume_to_mesh(decoder, planes: torch.Tensor, res: int, coarse: torch.Tensor, smooth_iterations: int = 10,
+                          backend: str = None, refine=None):
+    """volume_to_mesh's counterpart for a mesh resolution above the decoded volume's: a SparseOccupancyMesh ("device") or its
+    open3d.geometry.TriangleMesh ("open3d"); "third_party" has no sparse path and raises.  coarse: the dense volume (cleaned
+    by the caller if it is to be), refine: OccupancyMesh's dict, decoder / planes taken from the arguments."""
+    backend = BACKEND if backend is None else backend
+    if backend not in ("device", "open3d"):
+        raise ValueError(f'a sparse mesh needs the device surface (backend "device" or "open3d"), not {backend!r}')
+    if refine is not None:
+        refine = {k: v for k, v in refine.items() if k not in ("decoder", "planes")}
+    m = SparseOccupancyMesh(decoder, planes, res, coarse, smooth_iterations, refine=refine)
+    if backend == "device":
+        return m
+    return (m if refine is None else m.compute_vertex_normals()).to_open3d()
+
+
 def vertex_normals(verts: torch.Tensor, tris: torch.Tensor, normalized: bool = True) -> torch.Tensor:
     """Per-vertex normals as Open3D's compute_vertex_normals defines them: the sum over incident triangles of the
     (unnormalised, i.e. area-weighted) face normal cross(v1 - v0, v2 - v0), then normalised.  Display-side plumbing in
@@ -347,16 +558,81 @@ def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, 
     return mesh.filter_smooth_simple(number_of_iterations=smooth_iterations) if smooth_iterations > 0 else mesh
 
 
+EXPORT_CHUNK = 1 << 18                 # rows that cross to the host and become text / bytes at a time
+MAX_SPARSE_OBJ_VERTICES = 64_000_000   # a sparse mesh as OBJ text (about 100 bytes per vertex with its faces); beyond: .ply, or an error
+
+
 def _write_obj(path, verts: torch.Tensor, tris: torch.Tensor):
-    v = verts.detach().cpu().numpy()
-    f = tris.detach().cpu().numpy() + 1
+    """Wavefront OBJ, streamed EXPORT_CHUNK rows at a time: neither the host copy nor the text of a mesh of tens of millions of
+    vertices exists as a whole (the bytes are those of writing it in one piece)"""
     with open(path, "w") as fh:
-        fh.write("".join(f"v {p[0]:.6f} {p[1]:.6f} {p[2]:.6f}\n" for p in v))
-        fh.write("".join(f"f {t[0]} {t[1]} {t[2]}\n" for t in f))
+        for s in range(0, verts.shape[0], EXPORT_CHUNK):
+            v = verts[s:s + EXPORT_CHUNK].detach().cpu().numpy()
+            fh.write("".join(f"v {p[0]:.6f} {p[1]:.6f} {p[2]:.6f}\n" for p in v))
+        for s in range(0, tris.shape[0], EXPORT_CHUNK):
+            f = tris[s:s + EXPORT_CHUNK].detach().cpu().numpy().astype(np.int64) + 1
+            fh.write("".join(f"f {t[0]} {t[1]} {t[2]}\n" for t in f))
+
+
+PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def write_ply(path, verts: torch.Tensor, tris: torch.Tensor):
+    """binary little-endian PLY (float x y z; faces as uchar 3 + int32 indices), streamed EXPORT_CHUNK rows at a time: 12 bytes a
+    vertex and 13 a triangle, no text formatting -- the format for meshes of tens of millions of vertices"""
+    with open(path, "wb") as fh:
+        fh.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {int(verts.shape[0])}\nproperty float x\nproperty float y\n"
+                  f"property float z\nelement face {int(tris.shape[0])}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii"))
+        for s in range(0, verts.shape[0], EXPORT_CHUNK):
+            fh.write(verts[s:s + EXPORT_CHUNK].detach().to(torch.float32).cpu().numpy().astype("<f4").tobytes())
+        for s in range(0, tris.shape[0], EXPORT_CHUNK):
+            t = tris[s:s + EXPORT_CHUNK].detach().cpu().numpy()
+            rec = np.empty(t.shape[0], PLY_FACE)
+            rec["n"], rec["v"] = 3, t
+            fh.write(rec.tobytes())
+
+
+def read_ply(path: str):
+    """reader of write_ply's files: (vertices [V,3] float32, triangles [F,3] int32)"""
+    with open(path, "rb") as fh:
+        nv = nf = None
+        while True:
+            line = fh.readline().decode("ascii").strip()
+            if line.startswith("element vertex"):
+                nv = int(line.split()[-1])
+            elif line.startswith("element face"):
+                nf = int(line.split()[-1])
+            elif line == "end_header":
+                break
+            elif not line:
+                raise ValueError(f"{path}: no end_header")
+        v = np.frombuffer(fh.read(12 * nv), "<f4").reshape(nv, 3)
+        f = np.frombuffer(fh.read(PLY_FACE.itemsize * nf), PLY_FACE)
+    if nf and not (f["n"] == 3).all():
+        raise ValueError(f"{path}: only triangles are read")
+    return v.astype(np.float32), f["v"].astype(np.int32).reshape(nf, 3)
+
+
+def write_surface(path, verts: torch.Tensor, tris: torch.Tensor):
+    """A sparse (high-resolution) mesh to a file, whatever its size: binary PLY when `path` ends in .ply, else streamed OBJ text up
+    to MAX_SPARSE_OBJ_VERTICES vertices.  More than that as text raises RuntimeError naming the limit -- a mesh is never silently
+    replaced by a stub."""
+    if str(path).lower().endswith(".ply"):
+        write_ply(path, verts, tris)
+        return
+    if verts.shape[0] > MAX_SPARSE_OBJ_VERTICES:
+        raise RuntimeError(f"{path}: {int(verts.shape[0])} vertices / {int(tris.shape[0])} triangles exceed the OBJ text limit "
+                           f"MAX_SPARSE_OBJ_VERTICES = {MAX_SPARSE_OBJ_VERTICES}; write a .ply (binary) instead")
+    _write_obj(path, verts, tris)
 
 
 def write_mesh(path, mesh):
-    """o3d.io.write_triangle_mesh (drag_utils.py:470) when the mesh is an Open3D object; Wavefront OBJ of the device mesh otherwise."""
+    """o3d.io.write_triangle_mesh (drag_utils.py:470) when the mesh is an Open3D object; Wavefront OBJ of the device mesh otherwise.
+    A SparseOccupancyMesh goes through write_surface (streamed OBJ, or binary PLY by extension; an error, never a stub, above its text
+    limit); the MAX_OBJ_VERTICES stub is for dense volumes that are noise, not a surface."""
+    if isinstance(mesh, SparseOccupancyMesh):
+        write_surface(path, mesh.vertices, mesh.triangles)
+        return
     if isinstance(mesh, OccupancyMesh):
         nv, nt = mesh.counts()
         if nv > MAX_OBJ_VERTICES:

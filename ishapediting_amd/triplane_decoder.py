@@ -299,6 +299,36 @@ def decode_planes_grid(decoder: MultiTriplane, planes: torch.Tensor, res: int) -
     return vol
 
 
+def decode_bricks(decoder: MultiTriplane, planes: torch.Tensor, res: int, bricks: torch.Tensor) -> torch.Tensor:
+    """Occupancy logits on the 9^3 sample nodes of `bricks` (int [n] ids (bx nb + by) nb + bz, nb = ceil((res - 1) / 8)) of the
+    fine grid linspace(-1, 1, res)^3 -> [n,9,9,9] on the device: brick b samples nodes 8 b .. 8 b + 8 per axis, indices above
+    res - 1 clamped.  Bit for bit decode_planes_grid(decoder, planes, res) at those nodes, without the res^3 volume
+    (ishap_triplane_decode_bricks; mesh.extract_surface_sparse is its user)."""
+    dev = planes.device
+    res = int(res)
+    ids = bricks.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    n = int(ids.shape[0])
+    L = _lib.lib()
+    nb = int(L.ishap_sparse_bricks_per_axis(res))
+    if nb < 0:
+        raise ValueError(f"decode_bricks: res = {res} is outside 9 .. 2048")
+    if n == 0:
+        return torch.empty((0, 9, 9, 9), dtype=torch.float32, device=dev)
+    if int(ids.min()) < 0 or int(ids.max()) >= nb ** 3:
+        raise ValueError(f"decode_bricks: brick ids must lie in 0 .. {nb ** 3 - 1} (res = {res}: {nb} bricks per axis)")
+    out = torch.empty((n, 9, 9, 9), dtype=torch.float32, device=dev)
+    _decode_bricks_into(decoder, planes, torch.linspace(-1, 1, res).to(dev), res, ids, out)
+    return out
+
+
+def _decode_bricks_into(decoder: MultiTriplane, planes: torch.Tensor, axis: torch.Tensor, res: int, ids: torch.Tensor, out: torch.Tensor):
+    """ishap_triplane_decode_bricks on checked arguments: ids int32 [n] (n >= 1) -> out float32 [n,9,9,9], both contiguous"""
+    w = decoder.net.weights_c()
+    with torch.cuda.device(planes.device):
+        _lib.check(_lib.lib().ishap_triplane_decode_bricks(planes.data_ptr(), planes.shape[1], C.byref(w), axis.data_ptr(), res,
+                                                           ids.data_ptr(), ids.shape[0], out.data_ptr(), _lib.stream_ptr(planes.device)))
+
+
 def decode_volume(decoder: MultiTriplane, latent: torch.Tensor, rng, mid, res: int) -> torch.Tensor:
     """get_mesh's decode half (drag_utils.py:295-298 + visualize.py:79-97) without leaving the device."""
     return decode_planes_grid(decoder, prepare_planes(latent, rng, mid), res)

@@ -39,6 +39,20 @@ def create_obj(model: MultiTriplane, obj_idx: int, res: int = 128, max_batch_siz
     return vol
 
 
+def create_obj_sparse(model: MultiTriplane, obj_idx: int, res: int, mesh_res: int, output_path: str = "output.obj"):
+    """create_obj at a mesh resolution above the decoded grid's: the dense res^3 volume only seeds the bricks of the fine grid
+    (mesh.extract_surface_sparse); vertices / (mesh_res - 1) * 2 - 1, create_obj's convention (255 = 256 - 1) at that grid.
+    Written by mesh.write_surface: streamed OBJ text (binary PLY if output_path ends in .ply); more than
+    mesh.MAX_SPARSE_OBJ_VERTICES vertices as text raise -- no stub file."""
+    model.eval()
+    planes = model._planes(obj_idx)
+    vol = decode_planes_grid(model, planes, res)
+    verts, tris, info = mesh_backend.extract_surface_sparse(model, planes, mesh_res, vol)
+    del info
+    mesh_backend.write_surface(output_path, verts / (mesh_res - 1) * 2 - 1, tris)
+    return vol
+
+
 def create_obj_o3d(model: MultiTriplane, obj_idx: int, res: int = 128, max_batch_size: int = 50000):
     """visualize.py:76-105: the mesh of the decoded grid, vertices / res * 2 - 1, NOT smoothed (get_mesh applies
     filter_smooth_simple itself, drag_utils.py:300).  Returns what mesh.BACKEND selects: an OccupancyMesh ("device"), an
@@ -73,7 +87,11 @@ def main(args=None, feature=None, state_dict=None):
     triplanes = triplanes.reshape(3, 32, side, side)      # the reference hard-codes 128 (:121); any square side works here
     for i in range(3):
         model.embeddings[i] = torch.as_tensor(triplanes[[i]], device=device)
-    create_obj(model, 0, res=args.res, output_path=args.output)
+    mesh_res = getattr(args, "mesh_res", None)          # generate.py --mesh_resolution; absent or not above res: the dense path
+    if mesh_res is not None and int(mesh_res) > args.res:
+        create_obj_sparse(model, 0, args.res, int(mesh_res), output_path=args.output)
+    else:
+        create_obj(model, 0, res=args.res, output_path=args.output)
 
 
 if __name__ == "__main__":

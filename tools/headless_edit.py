@@ -7,8 +7,9 @@ moved by --offset, training() runs the guided loop, and before.png / after.png s
 spheres and green arrows.  With synthetic weights the decoded shape is noise; the path is the point.
 
   python tools/headless_edit.py --out /tmp/edit [--handles 3] [--num_steps 6] [--w_time 3] [--res 64] [--size 512] [--clean largest]
-                                [--refine 4]
+                                [--refine 4] [--mesh-resolution 512]
 
+--mesh-resolution R (above --res) cuts every mesh at R from bricks near the surface only (DragStuff.mesh_resolution).
 --clean largest keeps only the largest connected component of every decoded volume (DragStuff.clean, volume.clean_volume).
 --refine N puts every mesh's smoothed vertices back on the decoder's zero level set with N projection steps of at most one voxel
 in all (DragStuff.refine) and shades the pictures with the field's analytic normals.
@@ -205,6 +206,7 @@ def edit(a):
         ds.clean = {"keep": "largest" if a.clean == "largest" else int(a.clean)}
     if a.refine is not None:
         ds.refine = {"iterations": a.refine, "max_move": 2.0 / (a.res - 1)}
+    ds.mesh_resolution = a.mesh_resolution
     ds.load_weights(synthetic.round_torso_to_fp16(synthetic.unet_state_dict(full_config(), 1234)), synthetic.decoder_state_dict(4321),
                     -0.05 * np.ones(96, np.float32), 0.05 * np.ones(96, np.float32))
     ds.update_latent_params(img=synthetic.latent(0))
@@ -344,7 +346,7 @@ def time_renderer(a):
     print(json.dumps(out))
 
 
-def main():
+def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--out", default="headless_edit_out")
     p.add_argument("--handles", type=int, default=3)
@@ -358,6 +360,9 @@ def main():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--clean", default=None, metavar="largest|K",
                    help="keep only the largest (or the K largest) connected components of each decoded volume")
+    p.add_argument("--mesh-resolution", type=int, default=None, metavar="R",
+                   help="above --res (up to 2048): every mesh at this resolution, cut from bricks near the surface only "
+                        "(DragStuff.mesh_resolution); the volume, the metrics and the parts stay at --res")
     p.add_argument("--refine", type=int, default=None, metavar="N",
                    help="project the mesh vertices back onto the decoder's level set with N steps (DragStuff.refine)")
     for role in ("keep", "free"):
@@ -398,7 +403,11 @@ def main():
     p.add_argument("--time_out", default=None, help="where --time writes its JSON (default profiles/render_times.json)")
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--repeat", type=int, default=200)
-    a = p.parse_args()
+    return p
+
+
+def main():
+    a = build_parser().parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("headless_edit needs the GPU: rendering has no CPU fallback")
     (time_renderer if a.time else edit)(a)
