@@ -414,42 +414,91 @@ __global__ __launch_bounds__(MD_TILE) void mesh_tile_box_kernel(const float* __r
   }
 }
 
-__device__ __forceinline__ float seg_dist2(float apx, float apy, float apz, float abx, float aby, float abz) {
-  const float l2 = abx * abx + aby * aby + abz * abz;
-  const float s = l2 > 0.f ? fminf(fmaxf((apx * abx + apy * aby + apz * abz) / l2, 0.f), 1.f) : 0.f;
-  const float dx = apx - s * abx, dy = apy - s * aby, dz = apz - s * abz;
-  return dx * dx + dy * dy + dz * dz;
+// A triangle as the distance kernel stages it: a frame of its own and the triangle in that frame, built once per staged
+// triangle (tri_frame) and read by every lane (tri_dist2).
+//   r0 = {a.xyz, L}    a: first vertex after rotating the triangle so that its longest edge is a-b;  L = |ab|
+//   r1 = {e1.xyz, cx}  e1 = ab / L
+//   r2 = {e2.xyz, cy}  e2: unit, across e1 in the triangle's plane, towards c;  c = a + cx e1 + cy e2, cy >= 0
+//   r3 = {1/|ac|^2, 1/|bc|^2, 0, 0}  (0 for an edge without length)
+// A triangle without area has e2 = 0 (it is its longest edge), one without extent e1 = e2 = 0 (it is the point a).
+//
+// Why a frame and not Ericson's selection on the 3-D dot products: on a thin triangle the normal, and every barycentric
+// coordinate made from products of dot products, is a difference of nearly equal numbers; in float32 a triangle whose height
+// is 1e-3 of its length gets coordinates that are wrong by several percent, hence a closest point that far along the
+// triangle.  Here the only ill-conditioned quantity is the direction of e2, off by about (ulp * length / height) radians on
+// a thin triangle; turning the frame about the line a-b by that angle moves no point of the triangle by more than
+// angle * height = a few ulp of its length.  e2 is orthogonalised against e1 twice, so that rounding noise standing in
+// for the height of a (nearly) collinear triangle still gives an orthonormal frame.
+__device__ __forceinline__ void tri_frame(const float* __restrict__ A, const float* __restrict__ B, const float* __restrict__ Cv,
+                                          float4* __restrict__ out) {
+  float a[3] = {A[0], A[1], A[2]}, b[3] = {B[0], B[1], B[2]}, c[3] = {Cv[0], Cv[1], Cv[2]};
+  float lab = 0.f, lbc = 0.f, lca = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    lab += (b[k] - a[k]) * (b[k] - a[k]); lbc += (c[k] - b[k]) * (c[k] - b[k]); lca += (a[k] - c[k]) * (a[k] - c[k]);
+  }
+  const bool rot1 = lbc > lab && lbc >= lca, rot2 = !rot1 && lca > lab && lca > lbc;      // (b, c, a) or (c, a, b)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float a0 = a[k], b0 = b[k], c0 = c[k];
+    a[k] = rot1 ? b0 : rot2 ? c0 : a0; b[k] = rot1 ? c0 : rot2 ? a0 : b0; c[k] = rot1 ? a0 : rot2 ? b0 : c0;
+  }
+  float e1[3] = {0.f, 0.f, 0.f}, e2[3] = {0.f, 0.f, 0.f}, ac[3], L = 0.f, cx = 0.f, cy = 0.f, iac = 0.f, ibc = 0.f;
+  float l2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { ac[k] = c[k] - a[k]; l2 += (b[k] - a[k]) * (b[k] - a[k]); }
+  if (l2 > 0.f) {
+    L = sqrtf(l2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e1[k] = (b[k] - a[k]) / L;
+    cx = ac[0] * e1[0] + ac[1] * e1[1] + ac[2] * e1[2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e2[k] = ac[k] - cx * e1[k];
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {        // normalise; twice more after removing what is left along e1
+      const float n2 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
+      const float inv = n2 > 0.f ? 1.f / sqrtf(n2) : 0.f;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) e2[k] *= inv;
+      if (pass < 2) {
+        const float along = e2[0] * e1[0] + e2[1] * e1[1] + e2[2] * e1[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e2[k] -= along * e1[k];
+      }
+    }
+    cy = ac[0] * e2[0] + ac[1] * e2[1] + ac[2] * e2[2];
+    if (cy < 0.f) { cy = -cy; e2[0] = -e2[0]; e2[1] = -e2[1]; e2[2] = -e2[2]; }
+    const float lac = cx * cx + cy * cy, lcb = (cx - L) * (cx - L) + cy * cy;
+    iac = lac > 0.f ? 1.f / lac : 0.f;
+    ibc = lcb > 0.f ? 1.f / lcb : 0.f;
+  }
+  out[0] = make_float4(a[0], a[1], a[2], L);
+  out[1] = make_float4(e1[0], e1[1], e1[2], cx);
+  out[2] = make_float4(e2[0], e2[1], e2[2], cy);
+  out[3] = make_float4(iac, ibc, 0.f, 0.f);
 }
 
-// Squared distance from p to triangle (a, b, c): the closest point by Voronoi region (vertex, edge, face) as in Ericson,
-// Real-Time Collision Detection 5.1.5, written as selections so a wave runs one straight path.  Each region gives the
-// closest point as a + (nv ab + nw ac) / den; the last assignment that holds is Ericson's first matching region.
-__device__ __forceinline__ float tri_dist2(float px, float py, float pz, float4 r0, float4 r1, float4 r2) {
-  const float ax = r0.x, ay = r0.y, az = r0.z, bx = r0.w, by = r1.x, bz = r1.y, cx = r1.z, cy = r1.w, cz = r2.x;
-  const float abx = bx - ax, aby = by - ay, abz = bz - az;
-  const float acx = cx - ax, acy = cy - ay, acz = cz - az;
-  const float apx = px - ax, apy = py - ay, apz = pz - az;
-  const float bpx = px - bx, bpy = py - by, bpz = pz - bz;
-  const float cpx = px - cx, cpy = py - cy, cpz = pz - cz;
-  const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
-  const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
-  const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
-  const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-  float nv = vb, nw = vc, den = va + vb + vc;                                              // face
-  if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) { nv = d5 - d6; nw = d4 - d3; den = nv + nw; }   // edge bc
-  if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { nv = 0.f; nw = d2; den = d2 - d6; }           // edge ac
-  if (d6 >= 0.f && d5 <= d6) { nv = 0.f; nw = 1.f; den = 1.f; }                           // vertex c
-  if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { nv = d1; nw = 0.f; den = d1 - d3; }           // edge ab
-  if (d3 >= 0.f && d4 <= d3) { nv = 1.f; nw = 0.f; den = 1.f; }                           // vertex b
-  if (d1 <= 0.f && d2 <= 0.f) { nv = 0.f; nw = 0.f; den = 1.f; }                          // vertex a
-  const float r = 1.f / den, sv = nv * r, sw = nw * r;
-  const float dx = apx - sv * abx - sw * acx, dy = apy - sv * aby - sw * acy, dz = apz - sv * abz - sw * acz;
-  float dd = dx * dx + dy * dy + dz * dz;
-  if (!(dd <= 3.0e38f)) {    // degenerate triangle (no area: den = 0 in the face region): nearest of its three edges
-    dd = fminf(seg_dist2(apx, apy, apz, abx, aby, abz), seg_dist2(apx, apy, apz, acx, acy, acz));
-    dd = fminf(dd, seg_dist2(bpx, bpy, bpz, cx - bx, cy - by, cz - bz));
-  }
-  return dd;
+// Squared distance from p to a staged triangle: p in the triangle's frame is (x, y) in its plane and a remainder across it;
+// the answer is |remainder|^2 plus the squared 2-D distance from (x, y) to the triangle (0,0), (L,0), (cx,cy): zero strictly
+// inside, else the nearest of the three clamped edges.  Straight-line code, no division.  A wrong inside decision next to
+// an edge costs at most the rounding of the edge's position, because the 2-D distance goes to zero there.
+__device__ __forceinline__ float tri_dist2(float px, float py, float pz, float4 r0, float4 r1, float4 r2, float4 r3) {
+  const float apx = px - r0.x, apy = py - r0.y, apz = pz - r0.z;
+  const float L = r0.w, cx = r1.w, cy = r2.w;
+  const float x = apx * r1.x + apy * r1.y + apz * r1.z, y = apx * r2.x + apy * r2.y + apz * r2.z;
+  const float rx = apx - x * r1.x - y * r2.x, ry = apy - x * r1.y - y * r2.y, rz = apz - x * r1.z - y * r2.z;
+  const float z2 = rx * rx + ry * ry + rz * rz;
+  const float u0 = x - fminf(fmaxf(x, 0.f), L);                                            // edge a-b
+  const float d0 = u0 * u0 + y * y;
+  const float t1 = fminf(fmaxf((x * cx + y * cy) * r3.x, 0.f), 1.f);                       // edge a-c
+  const float u1 = x - t1 * cx, v1 = y - t1 * cy;
+  const float d1 = u1 * u1 + v1 * v1;
+  const float bx = x - L, ex = cx - L;
+  const float t2 = fminf(fmaxf((bx * ex + y * cy) * r3.y, 0.f), 1.f);                      // edge b-c
+  const float u2 = bx - t2 * ex, v2 = y - t2 * cy;
+  const float d2 = u2 * u2 + v2 * v2;
+  const bool inside = y > 0.f && ex * y - cy * bx > 0.f && cy * x - cx * y > 0.f;
+  return z2 + (inside ? 0.f : fminf(fminf(d0, d1), d2));
 }
 
 // d2[i] = min over triangles of the squared distance, tri[i] = its lowest index (tiles and triangles are visited in index
@@ -459,7 +508,7 @@ __global__ __launch_bounds__(MD_TILE) void mesh_distance_kernel(const float* __r
                                                                 long long nt, const float4* __restrict__ box,
                                                                 const float* __restrict__ pts, long long np, const float* occ,
                                                                 float* out, int* __restrict__ tri_out) {
-  __shared__ float4 tri[MD_TILE][3];
+  __shared__ float4 tri[MD_TILE][4];
   const long long i = (long long)blockIdx.x * MD_TILE + threadIdx.x;
   const bool live = i < np;
   float px = 0.f, py = 0.f, pz = 0.f;
@@ -487,17 +536,12 @@ __global__ __launch_bounds__(MD_TILE) void mesh_distance_kernel(const float* __r
     const int m = (int)min((long long)MD_TILE, nt - f0);
     if ((int)threadIdx.x < m) {
       const long long f = f0 + threadIdx.x;
-      const float* A = v + 3LL * t[3 * f];
-      const float* B = v + 3LL * t[3 * f + 1];
-      const float* Cv = v + 3LL * t[3 * f + 2];
-      tri[threadIdx.x][0] = make_float4(A[0], A[1], A[2], B[0]);
-      tri[threadIdx.x][1] = make_float4(B[1], B[2], Cv[0], Cv[1]);
-      tri[threadIdx.x][2] = make_float4(Cv[2], 0.f, 0.f, 0.f);
+      tri_frame(v + 3LL * t[3 * f], v + 3LL * t[3 * f + 1], v + 3LL * t[3 * f + 2], tri[threadIdx.x]);
     }
     __syncthreads();
     if (need) {
       for (int k = 0; k < m; ++k) {
-        const float dd = tri_dist2(px, py, pz, tri[k][0], tri[k][1], tri[k][2]);
+        const float dd = tri_dist2(px, py, pz, tri[k][0], tri[k][1], tri[k][2], tri[k][3]);
         if (dd < best) { best = dd; best_f = (int)(f0 + k); }
       }
     }

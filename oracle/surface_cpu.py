@@ -206,15 +206,16 @@ def smooth_simple(verts: torch.Tensor, faces: torch.Tensor, iterations: int = 10
     return v.float()
 
 
-def mesh_occupancy(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, chunk: int = 4096) -> torch.Tensor:
+def mesh_occupancy(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, chunk: int = 4096,
+                   dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Ray-parity occupancy (the device kernel's rule: crossings of p + s*(1,0,0), s > 0, counted when the point's (y,z)
     is strictly inside the triangle's (y,z) projection; barycentric form about a triangle vertex, edge-on triangles skipped).  Stands in for Open3D's RaycastingScene.compute_occupancy
-    (drag_utils.py:437-440), which is absent here."""
-    v = verts.float()
+    (drag_utils.py:437-440), which is absent here.  dtype: the arithmetic (float32 as the device, float64 as its reference)."""
+    v = verts.to(dtype)
     A, B, C = v[faces[:, 0].long()], v[faces[:, 1].long()], v[faces[:, 2].long()]
     out = torch.empty(points.shape[0])
     for i in range(0, points.shape[0], chunk):
-        p = points[i:i + chunk].float()
+        p = points[i:i + chunk].to(dtype)
         uy, uz = (B[:, 1] - A[:, 1])[None], (B[:, 2] - A[:, 2])[None]
         wy, wz = (C[:, 1] - A[:, 1])[None], (C[:, 2] - A[:, 2])[None]
         qy, qz = p[:, None, 1] - A[None, :, 1], p[:, None, 2] - A[None, :, 2]

@@ -21,13 +21,33 @@ def _seg_d2(p, a, b):
     return ((p - q) ** 2).sum(-1)
 
 
+def _two_prod(a, b):
+    """a * b as an unevaluated sum (product, rounding error) of two float64 (Dekker's splitting)"""
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    ah, bh = ca - (ca - a), cb - (cb - b)
+    al, bl = a - ah, b - bh
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def cross_accurate(u, w):
+    """u x w with every component a - b of two products rounded once, not once per product: on a thin triangle the
+    products cancel, and the plain float64 cross product keeps only 1e-16 / (height / length) of the normal."""
+    def dop(a, b, c, d):
+        p, e = _two_prod(a, b)
+        q, f = _two_prod(c, d)
+        return (p - q) + (e - f)
+    return np.stack([dop(u[..., 1], w[..., 2], u[..., 2], w[..., 1]), dop(u[..., 2], w[..., 0], u[..., 0], w[..., 2]),
+                     dop(u[..., 0], w[..., 1], u[..., 1], w[..., 0])], axis=-1)
+
+
 def point_triangle_d2(points, verts, faces):
     """[P,F] fp64 squared distances from every point to every triangle."""
     p = np.asarray(points, np.float64)[:, None, :]
     v = np.asarray(verts, np.float64)
     f = np.asarray(faces, np.int64)
     A, B, C = v[f[:, 0]][None], v[f[:, 1]][None], v[f[:, 2]][None]
-    n = np.cross(B - A, C - A)
+    n = cross_accurate(B - A, C - A)
     nn = (n * n).sum(-1)
     ok = nn > 0
     nsafe = np.where(ok[..., None], n, 1.0)
