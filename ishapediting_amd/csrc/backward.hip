@@ -15,9 +15,8 @@
 
 static int gn_bwd_op(Exec& e, GnBwdArgs g) {
   if (!g.sums_ready) ISHAP_SALLOC(g.csums, e, (size_t)g.N * g.C * 2);     // zeroed with the rest of the stats arena at the start of the forward
-  if (e.dry) return 0;
   ISHAP_REQUIRE(g.csums != nullptr, "stats arena exhausted");
-  return gn_backward_launch(g, e.s);
+  return e.launch([g](hipStream_t s) { return gn_backward_launch(g, s); });
 }
 
 // dY [N,H,W,cout] -> dX [N,H,W,rows of wT] through the transposed / flipped operand
@@ -45,8 +44,8 @@ static int gn_bwd_local_op(Exec& e, const GnBwdArgs& g, Tensor& up) {
   up.pend = SlabSrc{};
   long long* rec = nullptr;
   ISHAP_SALLOC(rec, e, (size_t)g.N * 32 * GN_REC_STRIDE);       // zeroed with the rest of the statistics arena
-  if (e.dry) return 0;
-  return gn_bwd_local_launch(gn_bwd_local_fill(g, slab, exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr), e.s);   // see gn_local_op
+  const GnBwdLocalArgs a = gn_bwd_local_fill(g, slab, exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr);   // see gn_local_op
+  return e.launch([a](hipStream_t s) { return gn_bwd_local_launch(a, s); });
 }
 static bool local_gn_bwd(const GnBwdArgs& g) { return gn_route(g.H * g.W, g.C, g.gmode, true) == GnRoute::local; }
 
@@ -75,10 +74,9 @@ static int conv_gn_backward(Exec& e, const ConvW& c, const Tensor& dy, GnBwdArgs
 // `split` > 0: the block input was a skip concatenation [h | skip]; its gradient is written as two dense tensors
 // (dx = first `split` channels, *dx2 = the rest) so no slicing pass is needed afterwards.
 // `add2`: a gradient map of the block input's shape (the skip-connection gradient of an input block) added to the result.
-static int res_backward(Exec& e, ResL& L, const Tensor& dy, Tensor& dx, int split = 0, Tensor* dx2 = nullptr,
+static int res_backward(Exec& e, const ResL& L, const ResSaved& sv, const Tensor& dy, Tensor& dx, int split = 0, Tensor* dx2 = nullptr,
                         const half_t* add2 = nullptr) {
-  ishap_unet* u = e.u;
-  const ResSaved& sv = L.sv;
+  const KeptForward& k = e.u->kept;
   const Tensor& x = sv.x;
   const Tensor& h1 = sv.h1;
   ISHAP_REQUIRE(dy.C == L.cout && dy.H == h1.H && dy.N == x.N, "ResBlock gradient shape");
@@ -86,7 +84,7 @@ static int res_backward(Exec& e, ResL& L, const Tensor& dy, Tensor& dx, int spli
   Tensor dh1 = h1;
   GnBwdArgs g2;
   g2.x = h1.p; g2.stats = sv.stats2; g2.gamma = L.n2.gamma; g2.beta = L.n2.beta;
-  g2.emb = u->film_cur + L.emb_off; g2.emb_ld = u->film_cur_ld;
+  g2.emb = k.film + L.emb_off; g2.emb_ld = k.film_ld;
   g2.N = h1.N; g2.H = h1.H; g2.W = h1.W; g2.C = L.cout; g2.film = 1; g2.act = 1; g2.gmode = GB_SAME;
   ISHAP_TRY(conv_gn_backward(e, L.c2, dy, g2, dh1));
   // in_layers: conv1 <- (up/down sample) <- SiLU <- GN1
@@ -119,9 +117,8 @@ static int res_backward(Exec& e, ResL& L, const Tensor& dy, Tensor& dx, int spli
   return conv_gn_norm(e, g1, da);
 }
 
-static int attn_backward(Exec& e, AttnL& L, const Tensor& dy, Tensor& dx) {
+static int attn_backward(Exec& e, const AttnL& L, const AttnSaved& sv, const Tensor& dy, Tensor& dx) {
   ishap_unet* u = e.u;
-  const AttnSaved& sv = L.sv;
   const Tensor& x = sv.x;
   const int N = x.N, T = x.H * x.W, C = L.C, heads = L.heads, d = C / heads;
   const float alpha = 1.f / sqrtf((float)d);
@@ -130,14 +127,11 @@ static int attn_backward(Exec& e, AttnL& L, const Tensor& dy, Tensor& dx) {
   Tensor dqkv{nullptr, N, x.H, x.W, 3 * C};
   ISHAP_ALLOC(dqkv.p, e, dqkv.numel());
   const size_t d_need = (size_t)N * heads * T;
-  if (e.dry) {
-    if (d_need > u->attn_D_floats) u->attn_D_floats = d_need;
-  } else {
-    AttnArgs g;
-    g.qkv = sv.qkv.p; g.out = sv.a.p; g.dout = dA.p; g.dqkv = dqkv.p; g.lse = sv.lse; g.Dbuf = u->attn_D;
-    g.N = N; g.T = T; g.C = C; g.heads = heads; g.d = d; g.alpha = alpha; g.xcd_map = attn_xcd_setting();
-    ISHAP_TRY(attn_backward_launch(g, e.s));
-  }
+  if (e.dry && d_need > u->attn_D_floats) u->attn_D_floats = d_need;
+  AttnArgs ga;
+  ga.qkv = sv.qkv.p; ga.out = sv.a.p; ga.dout = dA.p; ga.dqkv = dqkv.p; ga.lse = sv.lse; ga.Dbuf = u->attn_D;
+  ga.N = N; ga.T = T; ga.C = C; ga.heads = heads; ga.d = d; ga.alpha = alpha; ga.xcd_map = attn_xcd_setting();
+  ISHAP_TRY(e.launch([ga](hipStream_t s) { return attn_backward_launch(ga, s); }));
   dx = x;
   GnBwdArgs g;
   g.x = x.p; g.stats = sv.stats; g.gamma = L.n.gamma; g.beta = L.n.beta;
@@ -155,11 +149,11 @@ static int block_backward(Exec& e, BlockL& b, Tensor g, Tensor& out, int split =
     if (l.kind == 0) {
       ISHAP_TRY(dgrad_op(e, u->stem, g, dx, u->in_pad));
     } else if (l.kind == 1) {
-      if (i == 0 && split > 0) ISHAP_TRY(res_backward(e, u->res[l.idx], g, dx, split, out2, nullptr));
-      else if (i == 0 && add2) { ISHAP_TRY(res_backward(e, u->res[l.idx], g, dx, 0, nullptr, add2)); *add2_done = true; }
-      else ISHAP_TRY(res_backward(e, u->res[l.idx], g, dx, 0, nullptr, nullptr));
+      if (i == 0 && split > 0) ISHAP_TRY(res_backward(e, u->res[l.idx], u->kept.res[l.idx], g, dx, split, out2, nullptr));
+      else if (i == 0 && add2) { ISHAP_TRY(res_backward(e, u->res[l.idx], u->kept.res[l.idx], g, dx, 0, nullptr, add2)); *add2_done = true; }
+      else ISHAP_TRY(res_backward(e, u->res[l.idx], u->kept.res[l.idx], g, dx, 0, nullptr, nullptr));
     } else {
-      ISHAP_TRY(attn_backward(e, u->attn[l.idx], g, dx));
+      ISHAP_TRY(attn_backward(e, u->attn[l.idx], u->kept.attn[l.idx], g, dx));
     }
     g = dx;
   }
@@ -188,39 +182,40 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
   Exec e{u, s, dry};
   TenancyScope tenancy(u, s, dry);
   e.tenant = tenancy.granted;
-  u->arena.off = u->fwd_mark;
-  u->stat_off = u->stat_fwd_mark;
+  KeptForward& k = u->kept;
+  u->arena.off = k.fwd_mark;
+  u->stat_off = k.stat_fwd_mark;
   u->seq++;                     // the scratch above fwd_mark is reused from here on: the previous pass's gradient maps are gone
   if (!dry) {
-    ISHAP_REQUIRE(u->have_saved, "backward needs a preceding forward with keep_for_backward=1");
-    if (u->bwd_since_fwd++ > 0 && u->stat_cap > u->stat_fwd_mark)   // a second backward on the same forward: fresh zeros
-      ISHAP_CHECK_HIP(hipMemsetAsync(u->stat_base + u->stat_fwd_mark, 0, (u->stat_cap - u->stat_fwd_mark) * sizeof(long long), s));
+    ISHAP_REQUIRE(k.have_saved, "backward needs a preceding forward with keep_for_backward=1");
+    if (k.bwd_since_fwd++ > 0 && u->stat_cap > k.stat_fwd_mark)   // a second backward on the same forward: fresh zeros
+      ISHAP_CHECK_HIP(hipMemsetAsync(u->stat_base + k.stat_fwd_mark, 0, (u->stat_cap - k.stat_fwd_mark) * sizeof(long long), s));
   }
   ISHAP_TRY(bwd_mark(u, s, 0, dry));
   const ishap_unet_config& cfg = u->cfg;
-  const int N = u->last_N;            // dry runs follow a dry forward of the same batch size
+  const int N = k.N;            // dry runs follow a dry forward of the same batch size
   const int n_in = (int)u->in_blocks.size(), n_out = (int)u->out_blocks.size();
   int F;
   Tensor g;
   if (cot_out) {
-    ISHAP_REQUIRE(dry || !u->restored_partial, "the restored snapshot holds the network up to the tap only: no full-depth backward on it");
+    ISHAP_REQUIRE(dry || !k.restored_partial, "the restored snapshot holds the network up to the tap only: no full-depth backward on it");
     if (!dry) ISHAP_TRY(unet_join_tail(u, s));    // full depth: needs the blocks an overlapped forward put on the side stream
     // head backward: out = conv3x3(silu(gn(h)))  (unet.py:612-616,667-669)
     F = n_out - 1;
     const int S = cfg.image_size, opad = u->head.cout_pad;
     Tensor dout{nullptr, N, S, S, opad};
     ISHAP_ALLOC(dout.p, e, dout.numel());
-    if (!dry) ISHAP_TRY(nchw_to_nhwc_f16_scaled(cot_out, cot_out_f16 ? 0 : 1, dout.p, N, cfg.out_channels, S * S, opad, 1.f, s));
+    ISHAP_TRY(e.launch([=](hipStream_t s) { return nchw_to_nhwc_f16_scaled(cot_out, cot_out_f16 ? 0 : 1, dout.p, N, u->cfg.out_channels, S * S, opad, 1.f, s); }));
     GnBwdArgs a;
-    a.x = u->h_final.p; a.stats = u->head_stats; a.gamma = u->head_norm.gamma;
+    a.x = k.h_final.p; a.stats = k.head_stats; a.gamma = u->head_norm.gamma;
     a.beta = u->head_norm.beta; a.N = N; a.H = S; a.W = S; a.C = u->final_ch; a.act = 1;
-    g = u->h_final;
+    g = k.h_final;
     if (dry) g = Tensor{nullptr, N, S, S, u->final_ch};
     ISHAP_TRY(conv_gn_backward(e, u->head, dout, a, g));
   } else {
-    F = dry ? n_out - 1 : u->last_feat;
+    F = dry ? n_out - 1 : k.feat;
     ISHAP_REQUIRE(F >= 0, "the last forward had no tap (feat_layer < 0)");
-    g = u->out_blocks[F].out;
+    g = k.out[u->out_blocks[F].slot];
     g.p = const_cast<half_t*>(cot_tap);
   }
   std::vector<Tensor> skipgrad(n_in);
@@ -268,9 +263,10 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
     ISHAP_TRY(run(u->in_blocks[i], i > 0 ? skipgrad[i - 1].p : nullptr, pending));
     ISHAP_TRY(bwd_mark(u, s, 300 + i, dry));
   }
-  if (!dry)
-    ISHAP_TRY(nhwc_f16_to_nchw_f32_scaled(g.p, dx, N, cfg.in_channels, cfg.image_size * cfg.image_size, u->in_pad,
-                                          scale2 ? scale2 + 1 : nullptr, s));
+  ISHAP_TRY(e.launch([=](hipStream_t s) {
+    return nhwc_f16_to_nchw_f32_scaled(g.p, dx, N, u->cfg.in_channels, u->cfg.image_size * u->cfg.image_size, u->in_pad,
+                                       scale2 ? scale2 + 1 : nullptr, s);
+  }));
   ISHAP_TRY(bwd_mark(u, s, 999, dry));
   if (!dry) { u->grad_seq = u->seq; u->grad_F = F; }
   return 0;

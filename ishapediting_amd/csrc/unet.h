@@ -1,5 +1,6 @@
 // UNet graph + executor (host side).  Structure mirrors guided_diffusion/unet.py:427-616.
 #pragma once
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -76,22 +77,19 @@ struct ResL {
   ConvW c1, c2, skip;
   bool has_skip = false;
   int emb_off = 0;     // row offset into the concatenated emb_layers matrix (2*cout rows)
-  ResSaved sv;
 };
 struct AttnL {
   std::string path;
   int C = 0, heads = 0;
   NormW n;
   ConvW qkv, proj;
-  AttnSaved sv;
 };
 struct LayerRef { int kind; int idx; };   // 0 conv(stem) 1 res 2 attn
 struct BlockL {
   std::string name;
   std::vector<LayerRef> layers;
   int cin = 0, cout = 0, res_in = 0, res_out = 0, skip_ch = 0;
-  Tensor out;       // block output of the last forward
-  Tensor cat;       // concat input (output blocks)
+  int slot = 0;     // index into KeptForward::out / ::cat: the input blocks, the middle block, the output blocks
   // Read-out of the last backward (ishap_unet_block_grad): the backward scratch is bump-allocated above fwd_mark and never reused
   // within one pass, so every gradient map stays where it was written until the next forward / backward / restore on the context.
   // gout: the dense gradient w.r.t. this block's output, summed over its consumers; gh, gs (output blocks): what the first
@@ -115,9 +113,28 @@ struct ParamSlot {
   }
 };
 
+// Everything a kept forward leaves for later readers (the backward, the block read-outs, the snapshot): the forward writes it,
+// nobody else does except a snapshot restore, which puts a saved one back.
+struct KeptForward {
+  int N = 0, feat = -1;              // batch size, tapped output block
+  bool have_saved = false;           // the forward ran with keep_for_backward: a backward may read this record
+  Tensor tap, x0, h_final;
+  float* head_stats = nullptr;
+  size_t fwd_mark = 0, stat_fwd_mark = 0;   // arena offsets after the forward (backward scratch goes above them)
+  const float* film = nullptr;       // FiLM rows the forward / backward reads: d_film (stride film_rows) or a prepared row (stride 0)
+  int film_ld = 0;
+  bool tail_planned = false;         // the blocks after the tap and the head went to the deferred tail, which allocated
+  size_t tail_arena_off = 0, tail_stat_off = 0;   // from these offsets up to the marks
+  bool restored_partial = false;     // put back from a snapshot without the tail's blocks: no full-depth backward on it
+  int bwd_since_fwd = 0;
+  std::vector<ResSaved> res;         // indexed like ishap_unet::res / ::attn
+  std::vector<AttnSaved> attn;
+  std::vector<Tensor> out, cat;      // by BlockL::slot: block output; concat input (output blocks)
+};
+
 // A copy of what ishap_unet_backward_input reads of one kept forward (ishap_unet_snapshot_save): the bytes of the activation and
 // statistics arenas below the forward's marks (below the planned tail's when one was planned: the backward from the tap reads
-// nothing of the tail's blocks), the FiLM rows, and the host records that point into them.  Restoring copies the bytes back to
+// nothing of the tail's blocks), the FiLM rows, and the record that points into them.  Restoring copies the bytes back to
 // the same offsets, so the recorded pointers hold again.
 struct UnetSnapshot {
   bool valid = false;
@@ -125,14 +142,7 @@ struct UnetSnapshot {
   char* arena = nullptr;      size_t arena_cap = 0, arena_bytes = 0;
   long long* stat = nullptr;  size_t stat_cap = 0, stat_count = 0;
   float* film = nullptr;      size_t film_cap = 0, film_floats = 0;
-  int film_ld = 0;
-  size_t fwd_mark = 0, stat_fwd_mark = 0;
-  int last_N = 0, last_feat = -1;
-  Tensor tap, x0, h_final;
-  float* head_stats = nullptr;
-  std::vector<ResSaved> res;
-  std::vector<AttnSaved> attn;
-  std::vector<Tensor> outs, cats;     // BlockL::out / ::cat of the input blocks, the middle block, the output blocks
+  KeptForward kept;
   size_t bytes() const { return arena_cap + stat_cap * sizeof(long long) + film_cap * sizeof(float); }
 };
 
@@ -160,8 +170,6 @@ struct ishap_unet {
   size_t film_cache_rows = 0;
   std::vector<float> film_cache_ts;
   float *pc_temb = nullptr, *pc_e1 = nullptr, *pc_emb = nullptr;     // 16-row scratch of the prepare call
-  const float* film_cur = nullptr;   // what the current forward / backward reads: d_film (stride film_rows) or a cache row (stride 0)
-  int film_cur_ld = 0;
   // parameter table
   std::vector<ParamSlot> params;
   std::map<std::string, int> param_index;
@@ -170,20 +178,13 @@ struct ishap_unet {
   Arena arena;
   float* ws = nullptr;          size_t ws_floats = 0;       // split-K partials
   float* gn_partial = nullptr;  size_t gn_partial_floats = 0;
-  // last forward
-  int last_N = 0, last_feat = -1;
-  bool have_saved = false;
-  Tensor tap;
-  Tensor x0, h_final;
-  float* head_stats = nullptr;
+  KeptForward kept;                 // the last forward
   long long* stat_base = nullptr;   // arena of per-channel GroupNorm sums, zeroed once per forward
-  size_t stat_cap = 0, stat_off = 0, stat_high = 0, stat_fwd_mark = 0;
-  int bwd_since_fwd = 0;
+  size_t stat_cap = 0, stat_off = 0, stat_high = 0;
   // every forward, backward (dry runs included) and snapshot restore counts here; a backward that ran to its end leaves its count
   // in grad_seq, with the output block it started from (grad_F) -- BlockL::gout / gh / gs may be read while the two agree
   unsigned long long seq = 0, grad_seq = 0;
   int grad_F = -1;
-  size_t fwd_mark = 0;          // arena offset after the forward (backward scratch goes above it)
   // Overlapped forward tail (keep_for_backward bit 1): the output blocks after the tap and the head are enqueued on a
   // stream of the context's own, forked from the caller's stream at the tap, so that they run beside the loss and the
   // backward pass the caller enqueues next (those need nothing after the tap).  ishap_unet_join_tail orders a stream
@@ -199,29 +200,31 @@ struct ishap_unet {
   hipEvent_t mark_tail_begin = nullptr, mark_tail_end = nullptr;
   bool mark_tail_set = false;
   bool tail_pending = false;
-  // deferred tail (ISHAP_TAIL_DEFER): planned by the forward, enqueued by ishap_unet_run_tail behind ev_mid (recorded by the
-  // backward after its first output blocks)
-  struct TailState { size_t split; Tensor h; std::vector<Tensor> hs; int N; float* out; size_t arena_off, stat_off; bool keep; };
-  TailState tail{};
+  // deferred tail (ISHAP_TAIL_DEFER): the forward records the tail's launches once, with the settings they run under;
+  // ishap_unet_run_tail enqueues them behind ev_mid (recorded by the backward after its first output blocks)
+  std::vector<std::function<int(hipStream_t)>> tail_tape;
   bool tail_deferred = false, mid_recorded = false;
   float* ws_side = nullptr;          // the side stream's own copies of the shared scratch buffers
   float* gn_partial_side = nullptr;
   float* attn_D = nullptr;      // backward attention row sums
   size_t attn_D_floats = 0;
-  bool last_overlap = false;    // the last forward planned a tail (tail.arena_off / tail.stat_off are its)
   UnetSnapshot snap;
-  bool restored_partial = false;   // the kept state came from a snapshot without the tail's blocks: no full-depth backward on it
 };
 
 struct Exec {
   ishap_unet* u;
   hipStream_t s;
   bool dry;
-  bool keep = false;   // the forward keeps what a following backward re-reads
   float* ws = nullptr;          // split-K / GroupNorm-statistics scratch of this launch sequence (null: the context's)
   float* gn_partial = nullptr;
   int chunk_tiles = 0;          // > 0: the dx-reuse convolutions of this sequence run as launches of at most that many tiles (the overlapped forward tail)
   bool tenant = true;           // this sequence holds the device's rendezvous tenancy (common.h ishap_rendezvous_begin)
+  std::vector<std::function<int(hipStream_t)>>* tape = nullptr;   // set: launches are recorded here, not made (the deferred tail)
+  // THE gate of every device launch of the forward and backward walks; f(stream) makes the launch and captures its arguments by value
+  template <class F> int launch(F&& f) {
+    if (tape) { tape->emplace_back(std::forward<F>(f)); return 0; }
+    return dry ? 0 : f(s);
+  }
 };
 // Arena allocation that FAILS THE CALL when the arena sized by the create-time dry runs is exceeded (a null pointer
 // must never reach a kernel): ISHAP_ALLOC(ptr, e, count) inside any function returning an int status.

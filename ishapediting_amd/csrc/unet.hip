@@ -119,6 +119,12 @@ int unet_build(ishap_unet* u) {
       u->out_blocks.push_back(b);
     }
   }
+  int slot = 0;
+  for (auto& b : u->in_blocks) b.slot = slot++;
+  u->mid.slot = slot++;
+  for (auto& b : u->out_blocks) b.slot = slot++;
+  u->kept.out.resize(slot); u->kept.cat.resize(slot);
+  u->kept.res.resize(u->res.size()); u->kept.attn.resize(u->attn.size());
   u->final_ch = ch;
   u->film_rows = film;
   u->head_norm.C = ch;
@@ -284,15 +290,12 @@ int conv_op(Exec& e, const ConvLaunch& c) {
     SlabSrc& p = *c.pend_out;
     p.ws = a.ws; p.nslab = a.ksplit; p.zstride = (long long)a.M * a.N;
     p.bias = c.bias; p.bias2 = c.bias2; p.res = c.res; p.ldr = c.ldr; p.res_ups = c.res_ups;
-    return e.dry ? 0 : igemm_launch(a, e.s);
+  } else {
+    if (e.dry && need > e.u->ws_floats) e.u->ws_floats = need;
+    ISHAP_REQUIRE(need <= e.u->ws_floats, "split-K workspace too small");
+    a.ws = e.ws ? e.ws : e.u->ws;
   }
-  if (e.dry) {
-    if (need > e.u->ws_floats) e.u->ws_floats = need;
-    return 0;
-  }
-  ISHAP_REQUIRE(need <= e.u->ws_floats, "split-K workspace too small");
-  a.ws = e.ws ? e.ws : e.u->ws;
-  return igemm_launch(a, e.s);
+  return e.launch([a](hipStream_t s) { return igemm_launch(a, s); });
 }
 
 // A pending tensor whose next consumer cannot add the slices up itself: the stand-alone reduce (bias, residual, fp16).
@@ -300,18 +303,16 @@ int slab_materialize(Exec& e, Tensor& t) {
   if (!t.pend.pending()) return 0;
   const SlabSrc p = t.pend;
   t.pend = SlabSrc{};
-  if (e.dry) return 0;
-  return igemm_reduce_launch(igemm_reduce_fill(p, (int)t.rows(), t.C, t.H, t.W, t.p, t.C), e.s);
+  const IgemmArgs a = igemm_reduce_fill(p, (int)t.rows(), t.C, t.H, t.W, t.p, t.C);
+  return e.launch([a](hipStream_t s) { return igemm_reduce_launch(a, s); });
 }
 
 int gn_stats_op(Exec& e, const Tensor& x, float* stats) {
   size_t need = gn_partial_floats(x.N, x.H * x.W, x.C);
-  if (e.dry) {
-    if (need > e.u->gn_partial_floats) e.u->gn_partial_floats = need;
-    return 0;
-  }
+  if (e.dry && need > e.u->gn_partial_floats) e.u->gn_partial_floats = need;
   ISHAP_REQUIRE(need <= e.u->gn_partial_floats, "GroupNorm statistics scratch too small");
-  return gn_stats_launch(x.p, e.gn_partial ? e.gn_partial : e.u->gn_partial, stats, x.N, x.H * x.W, x.C, e.s);
+  float* part = e.gn_partial ? e.gn_partial : e.u->gn_partial;
+  return e.launch([=](hipStream_t s) { return gn_stats_launch(x.p, part, stats, x.N, x.H * x.W, x.C, s); });
 }
 
 // The GroupNorm pass `g` on a small map: one group-local launch that also adds up `x` when it is still pending (and its first
@@ -322,10 +323,10 @@ static int gn_local_op(Exec& e, Tensor& x, const GnApplyArgs& g) {
   x.cat_pend = SlabSrc{};
   long long* rec = nullptr;
   ISHAP_SALLOC(rec, e, (size_t)x.N * 32 * GN_REC_STRIDE);       // zeroed with the statistics arena at the start of the forward
-  if (e.dry) return 0;
   // several workgroups per group rendezvous inside the launch: only while this launch sequence is the context's only one
   // (beside an overlapped forward tail two half-resident rendezvous grids could wait on each other's compute units)
-  return gn_local_launch(gn_local_fill(g, slab, exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr), e.s);
+  const GnLocalArgs a = gn_local_fill(g, slab, exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr);
+  return e.launch([a](hipStream_t s) { return gn_local_launch(a, s); });
 }
 
 // out = act(film(GN(x))) (+ 2x2 pool with the pooled raw input in xpool | the head's hi/lo split); `stats` receives (mean, rstd)
@@ -333,16 +334,12 @@ static int gn_local_op(Exec& e, Tensor& x, const GnApplyArgs& g) {
 // map takes ONE group-local launch; else pending slices are added up by the stand-alone reduce, the statistics pass runs unless
 // the producer (or the two producers of a lazy concatenation) gathered the sums, and the apply kernel finalises those sums into
 // `stats` itself.  The split form has no group-local kernel (the head's map is full-size in the real model anyway).
-// Plan equals replay: the deferred forward tail is walked twice, dry by the forward and for real by unet_run_tail, and both walks
-// must make the same allocations.  The route here reads only the shape (local_gn) and fields of x that the plan walk sets as the
-// replay does (pend, sums, cat_*); the outputs are the caller's, allocated before the call; gn_local_op's record and
-// gn_stats_op's scratch bound are taken in dry runs too.  The tenancy (exec_is_solo) only picks launch forms inside gn_local_op.
 static int gn_forward_op(Exec& e, Tensor& x, const NormW& nw, half_t* out, half_t* xpool, float* stats, const float* emb,
                          int film, int act, int pool, int split = 0) {
   const bool lazy_cat = x.cat_a != nullptr;
   GnApplyArgs g;
   g.x = x.p; g.out = out; g.xpool = xpool; g.stats_out = stats;
-  g.gamma = nw.gamma; g.beta = nw.beta; g.emb = emb; g.emb_ld = emb ? e.u->film_cur_ld : 0;
+  g.gamma = nw.gamma; g.beta = nw.beta; g.emb = emb; g.emb_ld = emb ? e.u->kept.film_ld : 0;
   g.N = x.N; g.H = x.H; g.W = x.W; g.C = x.C; g.film = film; g.act = act; g.pool = pool; g.split = split;
   if (lazy_cat) { g.x = x.cat_a; g.x2 = x.cat_b; g.csplit = x.cat_ca; g.xcopy = x.p; }
   if (!split && local_gn(x.H * x.W, x.C)) return gn_local_op(e, x, g);
@@ -350,14 +347,13 @@ static int gn_forward_op(Exec& e, Tensor& x, const NormW& nw, half_t* out, half_
   ISHAP_TRY(slab_materialize(e, x));
   const bool summed = x.sums || lazy_cat;
   if (!summed) ISHAP_TRY(gn_stats_op(e, x, stats));
-  if (e.dry) return 0;
   g.stats = stats; g.sums = x.sums;
   if (lazy_cat) { g.sums = x.cat_sa; g.sums2 = x.cat_sb; }
   if (!summed) g.stats_out = nullptr;
-  return gn_apply_launch(g, e.s);
+  return e.launch([g](hipStream_t s) { return gn_apply_launch(g, s); });
 }
 
-static int res_forward(Exec& e, ResL& L, Tensor x, Tensor& y) {
+static int res_forward(Exec& e, const ResL& L, ResSaved& sv, Tensor x, Tensor& y) {
   ishap_unet* u = e.u;
   const int N = x.N, H = x.H, W = x.W;
   const int Ho = L.down ? H / 2 : (L.up ? H * 2 : H), Wo = L.down ? W / 2 : (L.up ? W * 2 : W);
@@ -383,7 +379,7 @@ static int res_forward(Exec& e, ResL& L, Tensor x, Tensor& y) {
   ConvLaunch k1 = conv_launch(a, L.c1, h1);
   k1.ups = L.up; k1.pend_out = loc_out ? &h1.pend : nullptr;
   ISHAP_TRY(conv_op(e, k1));
-  ISHAP_TRY(gn_forward_op(e, h1, L.n2, c.p, nullptr, st2, u->film_cur + L.emb_off, 1, 1, 0));
+  ISHAP_TRY(gn_forward_op(e, h1, L.n2, c.p, nullptr, st2, u->kept.film + L.emb_off, 1, 1, 0));
   y = h1;
   y.pend = SlabSrc{};
   ISHAP_ALLOC(y.p, e, h1.numel());
@@ -408,11 +404,11 @@ static int res_forward(Exec& e, ResL& L, Tensor x, Tensor& y) {
   ISHAP_TRY(conv_op(e, k2));
   h1.pend = SlabSrc{};
   x.pend = SlabSrc{}; x.cat_pend = SlabSrc{};
-  L.sv.x = x; L.sv.h1 = h1; L.sv.xs = xs; L.sv.stats1 = st1; L.sv.stats2 = st2;
+  sv = ResSaved{x, h1, xs, st1, st2};
   return 0;
 }
 
-static int attn_forward(Exec& e, AttnL& L, Tensor x, Tensor& y) {
+static int attn_forward(Exec& e, const AttnL& L, AttnSaved& sv, Tensor x, Tensor& y) {
   const int N = x.N, T = x.H * x.W, C = L.C, heads = L.heads, d = C / heads;
   ISHAP_REQUIRE(x.C == C, "attention channels");
   ISHAP_REQUIRE(d % 32 == 0, "head width must be a multiple of 32");
@@ -441,28 +437,27 @@ static int attn_forward(Exec& e, AttnL& L, Tensor x, Tensor& y) {
     y.sums = nullptr;
     y.pend.ws = slices; y.pend.nslab = heads; y.pend.zstride = (long long)N * T * C;
     y.pend.bias = L.proj.bias; y.pend.res = x.p; y.pend.ldr = C;
-    if (!e.dry) {
-      Attn8Args g;
-      g.xn = nrm.p; g.wqkv = L.qkv.w; g.bqkv = L.qkv.bias; g.wproj = L.proj.w; g.qkv = qkv.p; g.aout = a.p; g.lse = lse;
-      g.slices = slices; g.flags = reinterpret_cast<unsigned*>(fl); g.status = ishap_status_word();
+    Attn8Args g;
+    g.xn = nrm.p; g.wqkv = L.qkv.w; g.bqkv = L.qkv.bias; g.wproj = L.proj.w; g.qkv = qkv.p; g.aout = a.p; g.lse = lse;
+    g.slices = slices; g.flags = reinterpret_cast<unsigned*>(fl);
+    g.N = N; g.C = C; g.heads = heads; g.alpha = 1.f / sqrtf((float)d);
+    ISHAP_TRY(e.launch([g, solo = exec_is_solo(e)](hipStream_t s) mutable {
+      g.status = ishap_status_word();        // looked up at the launch: a dry run allocates nothing
       ISHAP_REQUIRE(g.status != nullptr, "device status word");
-      g.N = N; g.C = C; g.heads = heads; g.alpha = 1.f / sqrtf((float)d);
-      ISHAP_TRY(attn8_fused_launch(g, e.s, exec_is_solo(e)));
-    }
-    L.sv.x = x; L.sv.qkv = qkv; L.sv.a = a; L.sv.stats = st; L.sv.lse = lse;
+      return attn8_fused_launch(g, s, solo);
+    }));
+    sv = AttnSaved{x, qkv, a, st, lse};
     return 0;
   }
   ISHAP_TRY(conv_op(e, conv_launch(nrm, L.qkv, qkv)));
   Tensor a = x;
   ISHAP_ALLOC(a.p, e, x.numel());
-  if (!e.dry) {
-    // fused flash-style attention: w = softmax((q*s)^T (k*s)), a = w v   (unet.py:347-353)
-    AttnArgs g;
-    g.qkv = qkv.p; g.out = a.p; g.lse = lse; g.N = N; g.T = T; g.C = C; g.heads = heads; g.d = d;
-    g.alpha = 1.f / sqrtf((float)d);
-    g.xcd_map = attn_xcd_setting();
-    ISHAP_TRY(attn_forward_launch(g, e.s));
-  }
+  // fused flash-style attention: w = softmax((q*s)^T (k*s)), a = w v   (unet.py:347-353)
+  AttnArgs g;
+  g.qkv = qkv.p; g.out = a.p; g.lse = lse; g.N = N; g.T = T; g.C = C; g.heads = heads; g.d = d;
+  g.alpha = 1.f / sqrtf((float)d);
+  g.xcd_map = attn_xcd_setting();
+  ISHAP_TRY(e.launch([g](hipStream_t s) { return attn_forward_launch(g, s); }));
   y = x;
   y.pend = SlabSrc{};
   ISHAP_ALLOC(y.p, e, x.numel());
@@ -472,7 +467,7 @@ static int attn_forward(Exec& e, AttnL& L, Tensor x, Tensor& y) {
   ConvLaunch kp = conv_launch(a, L.proj, y);
   kp.res = x.p; kp.ldr = C; kp.pend_out = nosum ? &y.pend : nullptr;
   ISHAP_TRY(conv_op(e, kp));
-  L.sv.x = x; L.sv.qkv = qkv; L.sv.a = a; L.sv.stats = st; L.sv.lse = lse;
+  sv = AttnSaved{x, qkv, a, st, lse};
   return 0;
 }
 
@@ -486,15 +481,15 @@ static int block_forward(Exec& e, BlockL& b, Tensor h, Tensor& out) {
       if (!small_map(h.H * h.W)) ISHAP_SALLOC(y.sums, e, (size_t)h.N * u->stem.cout * 2);
       ISHAP_TRY(conv_op(e, conv_launch(h, u->stem, y)));
     } else if (l.kind == 1) {
-      ISHAP_TRY(res_forward(e, u->res[l.idx], h, y));
+      ISHAP_TRY(res_forward(e, u->res[l.idx], u->kept.res[l.idx], h, y));
     } else {
-      ISHAP_TRY(attn_forward(e, u->attn[l.idx], h, y));
+      ISHAP_TRY(attn_forward(e, u->attn[l.idx], u->kept.attn[l.idx], h, y));
     }
     h = y;
   }
   out = h;
-  b.out = h;                      // what later readers see: by then the next GroupNorm pass has added up a pending output
-  b.out.pend = SlabSrc{};
+  u->kept.out[b.slot] = h;        // what later readers see: by then the next GroupNorm pass has added up a pending output
+  u->kept.out[b.slot].pend = SlabSrc{};
   return 0;
 }
 
@@ -539,16 +534,16 @@ static int out_blocks_range(Exec& e, ishap_unet* u, size_t i0, size_t i1, Tensor
     } else {
       ISHAP_TRY(slab_materialize(e, h));
       cat.sums = (h.sums && skip.sums) ? salloc(e, (size_t)cat.N * cat.C * 2) : nullptr;
-      if (!e.dry) ISHAP_TRY(concat2(h.p, skip.p, cat.p, cat.rows(), h.C, skip.C, e.s, h.sums, skip.sums, cat.sums, cat.N));
+      ISHAP_TRY(e.launch([=](hipStream_t s) { return concat2(h.p, skip.p, cat.p, cat.rows(), h.C, skip.C, s, h.sums, skip.sums, cat.sums, cat.N); }));
     }
-    b.cat = cat;
-    b.cat.cat_pend = SlabSrc{};
+    u->kept.cat[b.slot] = cat;
+    u->kept.cat[b.slot].cat_pend = SlabSrc{};
     Tensor y;
     ISHAP_TRY(block_forward(e, b, cat, y));
     h = y;
     if ((int)i == feat_layer) {
-      u->tap = h;
-      u->tap.pend = SlabSrc{};
+      u->kept.tap = h;
+      u->kept.tap.pend = SlabSrc{};
     }
   }
   return 0;
@@ -558,51 +553,37 @@ static int out_blocks_range(Exec& e, ishap_unet* u, size_t i0, size_t i1, Tensor
 //      formed on the fp16 MFMA from hi/lo splits of both operands (3 partial products, fp32 accumulate). ----
 static int forward_head(Exec& e, ishap_unet* u, Tensor h, int N, float* out) {
   const int S = u->cfg.image_size;
-  ISHAP_ALLOC(u->head_stats, e, (size_t)N * 64);
+  ISHAP_ALLOC(u->kept.head_stats, e, (size_t)N * 64);
   half_t* hsplit = nullptr; ISHAP_ALLOC(hsplit, e, (size_t)h.numel() * 3);
-  ISHAP_TRY(gn_forward_op(e, h, u->head_norm, hsplit, nullptr, u->head_stats, nullptr, 0, 1, 0, 1));
-  u->h_final = h;
+  ISHAP_TRY(gn_forward_op(e, h, u->head_norm, hsplit, nullptr, u->kept.head_stats, nullptr, 0, 1, 0, 1));
+  u->kept.h_final = h;
   ConvLaunch c = conv_launch(Tensor{hsplit, N, S, S, 3 * h.C}, u->head, Tensor{nullptr, N, S, S, 0});
   c.out = out; c.out_mode = IG_OUT_NCHW_F32;      // NCHW fp32: no row stride
   return conv_op(e, c);
 }
 
-// the deferred forward tail (ISHAP_TAIL_DEFER): the launches unet_forward_impl only planned, on the side stream, behind the event
-// the backward recorded after its first blocks (or behind the fork when it recorded none)
-static int unet_run_tail_body(ishap_unet* u) {
-  ISHAP_CHECK_HIP(hipStreamWaitEvent(u->side, u->mid_recorded ? u->ev_mid : u->ev_fork, 0));
-  if (u->marks_on && u->marks_n > 0) {           // diagnostic marks (unet.h): the tail's span on the side stream
-    if (!u->mark_tail_begin) { ISHAP_CHECK_HIP(hipEventCreate(&u->mark_tail_begin)); ISHAP_CHECK_HIP(hipEventCreate(&u->mark_tail_end)); }
-    ISHAP_CHECK_HIP(hipEventRecord(u->mark_tail_begin, u->side));
-  }
-  Exec e{u, u->side, false};
-  e.tenant = false;
-  e.keep = u->tail.keep;
-  tail_exec(e, u);
-  Tensor h = u->tail.h;
-  std::vector<Tensor> hs = u->tail.hs;
-  ISHAP_TRY(out_blocks_range(e, u, u->tail.split, u->out_blocks.size(), h, hs, u->last_feat));
-  ISHAP_TRY(forward_head(e, u, h, u->tail.N, u->tail.out));
-  if (u->marks_on && u->marks_n > 0 && u->mark_tail_begin) {
-    ISHAP_CHECK_HIP(hipEventRecord(u->mark_tail_end, u->side));
-    u->mark_tail_set = true;
-  }
-  ISHAP_REQUIRE(u->arena.off == u->fwd_mark && u->stat_off == u->stat_fwd_mark, "the deferred tail allocated differently from its plan");
-  return 0;
-}
-
+// the deferred forward tail (ISHAP_TAIL_DEFER): the launches unet_forward_impl recorded, on the side stream, behind the event the
+// backward recorded after its first blocks (or behind the fork when it recorded none)
 int unet_run_tail(ishap_unet* u) {
   if (!u->tail_deferred) return 0;
   u->tail_deferred = false;
-  const size_t keep_arena = u->arena.off, keep_stat = u->stat_off;
-  u->arena.off = u->tail.arena_off;
-  u->stat_off = u->tail.stat_off;
-  const int r = unet_run_tail_body(u);
-  // on EVERY exit path: the caller's arena offsets come back, and whatever was enqueued on the side stream before a failure is
-  // closed by ev_tail, so that the next join (forward, full-depth backward, read-out) still orders behind it before the arena
-  // or `out` is reused
-  u->arena.off = keep_arena;
-  u->stat_off = keep_stat;
+  const bool marks = u->marks_on && u->marks_n > 0;      // diagnostic marks (unet.h): the tail's span on the side stream
+  auto body = [&]() -> int {
+    ISHAP_CHECK_HIP(hipStreamWaitEvent(u->side, u->mid_recorded ? u->ev_mid : u->ev_fork, 0));
+    if (marks) {
+      if (!u->mark_tail_begin) { ISHAP_CHECK_HIP(hipEventCreate(&u->mark_tail_begin)); ISHAP_CHECK_HIP(hipEventCreate(&u->mark_tail_end)); }
+      ISHAP_CHECK_HIP(hipEventRecord(u->mark_tail_begin, u->side));
+    }
+    for (auto& launch : u->tail_tape) ISHAP_TRY(launch(u->side));
+    if (marks) {
+      ISHAP_CHECK_HIP(hipEventRecord(u->mark_tail_end, u->side));
+      u->mark_tail_set = true;
+    }
+    return 0;
+  };
+  const int r = body();
+  // on EVERY exit path: whatever was enqueued on the side stream before a failure is closed by ev_tail, so that the next join
+  // (forward, full-depth backward, read-out) still orders behind it before the arena or `out` is reused
   if (hipEventRecord(u->ev_tail, u->side) == hipSuccess) u->tail_pending = true;
   else if (r == 0) { ishap_set_error("hipEventRecord(ev_tail) failed after the deferred forward tail"); return -1; }
   return r;
@@ -616,7 +597,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
   Exec e{u, s, dry};
   TenancyScope tenancy(u, s, dry);       // in-launch rendezvous only while no other context / stream of the process runs such grids here
   e.tenant = tenancy.granted;
-  e.keep = (keep & 1) != 0;
+  KeptForward& k = u->kept;
   // the overlapped tail fills what ONE edit leaves idle; when another context / stream of the process is running sequences on the
   // device (no tenancy: common.h) the chip is shared already and a second stream per edit only oversubscribes the hardware
   // queues (three interleaved edits: 0.120 s/shape in the plain sequence, 0.248 with three overlapped tails, 0.143 with the
@@ -624,7 +605,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
   const bool overlap = (keep & 2) != 0 && !dry && feat_layer >= 0 && feat_layer + 1 < (int)u->out_blocks.size() && tenancy.granted &&
                        !ishap_rendezvous_contended(u, s);
   if (!dry) ISHAP_TRY(unet_join_tail(u, s));       // the previous forward's tail still owns the arena it is about to reuse
-  if (!dry && u->snap.valid && (u->snap.last_N != N || u->snap.last_feat != feat_layer)) u->snap.valid = false;   // another shape of call
+  if (!dry && u->snap.valid && (u->snap.kept.N != N || u->snap.kept.feat != feat_layer)) u->snap.valid = false;   // another shape of call
   if (overlap && !u->side) {
     // lowest priority: the tail is throughput work that should fill what the latency-bound chain on the caller's stream
     // leaves idle, not compete with it for compute units
@@ -643,38 +624,42 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
   // the statistics arena is zeroed by the layout conversion below (its first use comes after it)
   const bool zero_in_convert = (u->stat_cap % 2 == 0) && (reinterpret_cast<uintptr_t>(u->stat_base) & 15) == 0;
   if (!dry && u->stat_cap && !zero_in_convert) ISHAP_CHECK_HIP(hipMemsetAsync(u->stat_base, 0, u->stat_cap * sizeof(long long), s));
-  u->have_saved = false;
-  u->restored_partial = false;
+  k.have_saved = false;
+  k.restored_partial = false;
   const int S = cfg.image_size, HW = S * S;
   // ---- timestep embedding -> emb -> every ResBlock's (scale | shift)   (unet.py:651, :245-250) ----
-  u->film_cur = u->d_film;
-  u->film_cur_ld = u->film_rows;
+  k.film = u->d_film;
+  k.film_ld = u->film_rows;
   bool prepared = false;
   if (!dry && !u->film_cache_ts.empty()) {
     bool same = true;
     for (int i = 1; i < N; ++i) same = same && ts[i] == ts[0];
     if (same)
-      for (size_t k = 0; k < u->film_cache_ts.size() && !prepared; ++k)
-        if (u->film_cache_ts[k] == ts[0]) {
-          u->film_cur = u->film_cache + k * (size_t)u->film_rows;
-          u->film_cur_ld = 0;
+      for (size_t i = 0; i < u->film_cache_ts.size() && !prepared; ++i)
+        if (u->film_cache_ts[i] == ts[0]) {
+          k.film = u->film_cache + i * (size_t)u->film_rows;
+          k.film_ld = 0;
           prepared = true;
         }
   }
-  if (!dry && !prepared) {
+  if (!prepared) {
     TsArg ta;
     for (int i = 0; i < 16; ++i) ta.t[i] = i < N ? ts[i] : 0.f;
-    ISHAP_TRY(timestep_embedding(ta, u->d_temb, N, cfg.model_channels, s));
-    ISHAP_TRY(gemv_f32(u->te_w0, u->te_b0, u->d_temb, u->d_e1, u->ted, cfg.model_channels, N, 0, s));
-    ISHAP_TRY(gemv_f32(u->te_w2, u->te_b2, u->d_e1, u->d_emb, u->ted, u->ted, N, 1, s));
-    ISHAP_TRY(gemv_f32(u->emb_w, u->emb_b, u->d_emb, u->d_film, u->film_rows, u->ted, N, 1, s));
+    ISHAP_TRY(e.launch([=](hipStream_t s) {
+      ISHAP_TRY(timestep_embedding(ta, u->d_temb, N, u->cfg.model_channels, s));
+      ISHAP_TRY(gemv_f32(u->te_w0, u->te_b0, u->d_temb, u->d_e1, u->ted, u->cfg.model_channels, N, 0, s));
+      ISHAP_TRY(gemv_f32(u->te_w2, u->te_b2, u->d_e1, u->d_emb, u->ted, u->ted, N, 1, s));
+      return gemv_f32(u->emb_w, u->emb_b, u->d_emb, u->d_film, u->film_rows, u->ted, N, 1, s);
+    }));
   }
   // ---- x: NCHW fp32 -> NHWC fp16 (h = x.type(self.dtype), unet.py:657) ----
   Tensor h{nullptr, N, S, S, u->in_pad};
   ISHAP_ALLOC(h.p, e, h.numel());
-  if (!dry) ISHAP_TRY(nchw_f32_to_nhwc_f16(x, h.p, N, cfg.in_channels, HW, u->in_pad, s, zero_in_convert ? u->stat_base : nullptr,
-                                           zero_in_convert ? u->stat_cap * sizeof(long long) : 0));
-  u->x0 = h;
+  ISHAP_TRY(e.launch([=](hipStream_t s) {
+    return nchw_f32_to_nhwc_f16(x, h.p, N, u->cfg.in_channels, HW, u->in_pad, s, zero_in_convert ? u->stat_base : nullptr,
+                                zero_in_convert ? u->stat_cap * sizeof(long long) : 0);
+  }));
+  k.x0 = h;
   std::vector<Tensor> hs;
   for (auto& b : u->in_blocks) {
     Tensor y;
@@ -688,7 +673,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
     ISHAP_TRY(block_forward(e, u->mid, h, y));
     h = y;
   }
-  u->tap = Tensor{};
+  k.tap = Tensor{};
   const size_t n_out = u->out_blocks.size();
   const size_t split = overlap ? (size_t)feat_layer + 1 : n_out;
   ISHAP_TRY(out_blocks_range(e, u, 0, split, h, hs, feat_layer));
@@ -696,44 +681,40 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
     // everything after the tap needs only what exists now; whatever the caller enqueues on `s` after this call (loss,
     // backward) needs nothing of what follows: fork
     ISHAP_TRY(slab_materialize(e, h));             // the tap is complete on the caller's stream
-    u->tap = h;
+    k.tap = h;
     ISHAP_CHECK_HIP(hipEventRecord(u->ev_fork, s));
-    // DEFERRED tail (round 5: -2.2 % against a tail enqueued here, at the tap; that form was removed in round 6): only PLAN the
-    // rest -- allocate what it will allocate, launch nothing -- so that the caller's backward gets its scratch above the whole
-    // forward; ishap_unet_run_tail enqueues the launches later, behind an event the backward records after its first blocks
-    // (the tail then runs beside the backward's latency-bound middle, not beside its chip-filling first and last launches).
-    // The plan and the replay make the same allocations: no route depends on the tenancy, only launch forms do (gn_forward_op;
-    // attn8_fused_launch's one- or two-launch form)
-    u->tail = ishap_unet::TailState{split, h, hs, N, out, u->arena.off, u->stat_off, (keep & 1) != 0};
-    Exec plan = e;
-    plan.dry = true;
-    Tensor hp = h;
-    std::vector<Tensor> hsp = hs;
-    ISHAP_TRY(out_blocks_range(plan, u, split, n_out, hp, hsp, feat_layer));
-    ISHAP_TRY(forward_head(plan, u, hp, N, out));
+    // DEFERRED tail (round 5: -2.2 % against a tail enqueued here, at the tap; that form was removed in round 6): the rest is
+    // allocated now -- so that the caller's backward gets its scratch above the whole forward -- and its launches are recorded
+    // once, with the settings they run under; ishap_unet_run_tail enqueues them later, behind an event the backward records
+    // after its first blocks (the tail then runs beside the backward's latency-bound middle, not beside its chip-filling first
+    // and last launches)
+    k.tail_arena_off = u->arena.off;
+    k.tail_stat_off = u->stat_off;
+    u->tail_tape.clear();
+    Exec rec{u, u->side, false};
+    rec.tenant = false;
+    rec.tape = &u->tail_tape;
+    tail_exec(rec, u);
+    ISHAP_TRY(out_blocks_range(rec, u, split, n_out, h, hs, feat_layer));
+    ISHAP_TRY(forward_head(rec, u, h, N, out));
     u->tail_deferred = true;
     u->mid_recorded = false;
   } else {
     ISHAP_TRY(forward_head(e, u, h, N, out));
   }
-  if (feat_layer >= 0 && inter_feat && !dry)
-    ISHAP_TRY(nhwc_f16_to_nchw(u->tap.p, inter_feat, 0, N, u->tap.C, u->tap.H * u->tap.W, u->tap.C, s));
-  u->last_N = N;
-  u->last_feat = feat_layer;
-  u->last_overlap = overlap;
-  u->have_saved = (keep & 1) != 0 && !dry;
-  u->fwd_mark = u->arena.off;
-  u->stat_fwd_mark = u->stat_off;
-  u->bwd_since_fwd = 0;
+  if (feat_layer >= 0 && inter_feat)
+    ISHAP_TRY(e.launch([=, t = k.tap](hipStream_t s) { return nhwc_f16_to_nchw(t.p, inter_feat, 0, N, t.C, t.H * t.W, t.C, s); }));
+  k.N = N;
+  k.feat = feat_layer;
+  k.tail_planned = overlap;
+  k.have_saved = (keep & 1) != 0 && !dry;
+  k.fwd_mark = u->arena.off;
+  k.stat_fwd_mark = u->stat_off;
+  k.bwd_since_fwd = 0;
   return 0;
 }
 
-// ---- helpers of the snapshot calls below ----
-static void snap_blocks(ishap_unet* u, std::vector<BlockL*>& v) {
-  for (auto& b : u->in_blocks) v.push_back(&b);
-  v.push_back(&u->mid);
-  for (auto& b : u->out_blocks) v.push_back(&b);
-}
+// ---- helper of the snapshot calls below ----
 template <typename T>
 static int snap_reserve(T** buf, size_t* cap, size_t need) {
   if (need <= *cap) return 0;
@@ -819,7 +800,7 @@ int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out
   u->stat_cap = (u->stat_high + 1023) / 1024 * 1024;
   ISHAP_CHECK_HIP(hipMalloc((void**)&u->stat_base, std::max<size_t>(u->stat_cap, 1024) * sizeof(long long)));
   if (u->attn_D_floats) ISHAP_CHECK_HIP(hipMalloc((void**)&u->attn_D, u->attn_D_floats * sizeof(float)));
-  u->have_saved = false;
+  u->kept.have_saved = false;
   *out = u;
   return 0;
 }
@@ -889,7 +870,7 @@ int ishap_unet_prepare_timesteps(ishap_unet* u, const float* ts, int n, void* st
   u->film_cache_ts.clear();
   // a kept forward may be reading a prepared row (its backward needs the FiLM values again): the rows are about to be
   // rewritten, so that forward can no longer be differentiated
-  if (u->film_cur != u->d_film) { u->have_saved = false; u->film_cur = u->d_film; u->film_cur_ld = u->film_rows; }
+  if (u->kept.film != u->d_film) { u->kept.have_saved = false; u->kept.film = u->d_film; u->kept.film_ld = u->film_rows; }
   if (n == 0) return 0;
   ISHAP_REQUIRE(u->n_loaded == (int)u->params.size(), "prepare_timesteps before all parameters are loaded");
   const int mc = u->cfg.model_channels;
@@ -948,7 +929,7 @@ int ishap_unet_tap_shape(const ishap_unet* u, int feat_layer, int* channels, int
   return 0;
 }
 
-const void* ishap_unet_tap_ptr(const ishap_unet* u) { return u ? u->tap.p : nullptr; }
+const void* ishap_unet_tap_ptr(const ishap_unet* u) { return u ? u->kept.tap.p : nullptr; }
 
 long long ishap_unet_workspace_bytes(const ishap_unet* u) {
   if (!u) return 0;
@@ -966,12 +947,13 @@ int ishap_unet_block_output(const ishap_unet* u, int group, int index, int* chan
   if (channels) *channels = b->cout;
   if (size) *size = b->res_out;
   if (!dst_nchw_f16) return 0;
-  ISHAP_REQUIRE(u->have_saved && b->out.p, "block outputs stay resident only after a forward with keep_for_backward=1");
-  ISHAP_REQUIRE(!(u->restored_partial && group == 2 && index > u->last_feat), "the restored snapshot holds the network up to the tap only");
+  const Tensor& t = u->kept.out[b->slot];
+  ISHAP_REQUIRE(u->kept.have_saved && t.p, "block outputs stay resident only after a forward with keep_for_backward=1");
+  ISHAP_REQUIRE(!(u->kept.restored_partial && group == 2 && index > u->kept.feat), "the restored snapshot holds the network up to the tap only");
   ISHAP_TRY(ishap_check_status());
   ISHAP_CHECK_HIP(hipSetDevice(u->device));
   ISHAP_TRY(unet_join_tail(const_cast<ishap_unet*>(u), (hipStream_t)stream));
-  return nhwc_f16_to_nchw(b->out.p, dst_nchw_f16, 0, b->out.N, b->out.C, b->out.H * b->out.W, b->out.C, (hipStream_t)stream);
+  return nhwc_f16_to_nchw(t.p, dst_nchw_f16, 0, t.N, t.C, t.H * t.W, t.C, (hipStream_t)stream);
 }
 
 int ishap_unet_block_grad(const ishap_unet* u, int group, int index, int part, int* channels, int* size, void* dst_nchw_f16,
@@ -988,7 +970,7 @@ int ishap_unet_block_grad(const ishap_unet* u, int group, int index, int part, i
   if (!dst_nchw_f16) return 0;
   ISHAP_REQUIRE(u->grad_seq != 0, "block gradients exist only after a backward pass on this context");
   ISHAP_REQUIRE(u->grad_seq == u->seq, "stale block gradients: a forward, a backward or a snapshot restore ran after the pass that wrote them");
-  ISHAP_REQUIRE(!(u->restored_partial && group == 2 && index > u->last_feat), "the restored snapshot holds the network up to the tap only");
+  ISHAP_REQUIRE(!(u->kept.restored_partial && group == 2 && index > u->kept.feat), "the restored snapshot holds the network up to the tap only");
   ISHAP_REQUIRE(!(group == 2 && index > u->grad_F), "the last backward started below this output block: it has no gradient");
   const Tensor& t = part == 0 ? b->gout : (part == 1 ? b->gh : b->gs);
   ISHAP_REQUIRE(t.p != nullptr, "no gradient was recorded for this block");
@@ -998,8 +980,8 @@ int ishap_unet_block_grad(const ishap_unet* u, int group, int index, int part, i
 }
 
 int ishap_unet_copy_tap(const ishap_unet* u, void* dst, void* stream) {
-  ISHAP_REQUIRE(u && dst && u->tap.p, "no resident tap (run a forward with feat_layer >= 0 first)");
-  ISHAP_CHECK_HIP(hipMemcpyAsync(dst, u->tap.p, (size_t)u->tap.numel() * sizeof(half_t), hipMemcpyDeviceToDevice,
+  ISHAP_REQUIRE(u && dst && u->kept.tap.p, "no resident tap (run a forward with feat_layer >= 0 first)");
+  ISHAP_CHECK_HIP(hipMemcpyAsync(dst, u->kept.tap.p, (size_t)u->kept.tap.numel() * sizeof(half_t), hipMemcpyDeviceToDevice,
                                  (hipStream_t)stream));
   return 0;
 }
@@ -1009,9 +991,9 @@ int ishap_unet_copy_tap(const ishap_unet* u, void* dst, void* stream) {
 //      up to the tap and the tail) ----
 int ishap_unet_snapshot_save(ishap_unet* u, void* stream) {
   ISHAP_REQUIRE(u, "null argument");
-  ISHAP_REQUIRE(u->have_saved, "a snapshot needs a preceding forward with keep_for_backward=1");
+  ISHAP_REQUIRE(u->kept.have_saved, "a snapshot needs a preceding forward with keep_for_backward=1");
   if (ishap_profile_recording()) return 1;         // unavailable: the recorded edit runs (and counts) every forward
-  if (u->snap.film && u->film_cur == u->snap.film) {       // the kept state IS the restored snapshot
+  if (u->snap.film && u->kept.film == u->snap.film) {       // the kept state IS the restored snapshot
     ISHAP_REQUIRE(u->snap.valid, "the kept state came from a snapshot that is no longer valid");
     return 0;
   }
@@ -1021,27 +1003,19 @@ int ishap_unet_snapshot_save(ishap_unet* u, void* stream) {
   ISHAP_TRY(unet_join_tail(u, s));
   UnetSnapshot& sn = u->snap;
   sn.valid = false;
-  sn.partial = u->last_overlap;
-  sn.arena_bytes = sn.partial ? u->tail.arena_off : u->fwd_mark;
-  sn.stat_count = sn.partial ? u->tail.stat_off : u->stat_fwd_mark;
-  sn.film_ld = u->film_cur_ld;
-  sn.film_floats = (size_t)u->film_rows * (sn.film_ld ? (size_t)u->last_N : 1);
+  const KeptForward& k = u->kept;
+  sn.partial = k.tail_planned;
+  sn.arena_bytes = sn.partial ? k.tail_arena_off : k.fwd_mark;
+  sn.stat_count = sn.partial ? k.tail_stat_off : k.stat_fwd_mark;
+  sn.film_floats = (size_t)u->film_rows * (k.film_ld ? (size_t)k.N : 1);
   ISHAP_REQUIRE(sn.arena_bytes <= u->arena.cap && sn.stat_count <= u->stat_cap, "forward marks beyond the arenas");
   ISHAP_TRY(snap_reserve(&sn.arena, &sn.arena_cap, sn.arena_bytes));
   ISHAP_TRY(snap_reserve(&sn.stat, &sn.stat_cap, sn.stat_count));
   ISHAP_TRY(snap_reserve(&sn.film, &sn.film_cap, sn.film_floats));
   if (sn.arena_bytes) ISHAP_CHECK_HIP(hipMemcpyAsync(sn.arena, u->arena.base, sn.arena_bytes, hipMemcpyDeviceToDevice, s));
   if (sn.stat_count) ISHAP_CHECK_HIP(hipMemcpyAsync(sn.stat, u->stat_base, sn.stat_count * sizeof(long long), hipMemcpyDeviceToDevice, s));
-  ISHAP_CHECK_HIP(hipMemcpyAsync(sn.film, u->film_cur, sn.film_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
-  sn.fwd_mark = u->fwd_mark; sn.stat_fwd_mark = u->stat_fwd_mark;
-  sn.last_N = u->last_N; sn.last_feat = u->last_feat;
-  sn.tap = u->tap; sn.x0 = u->x0; sn.h_final = u->h_final; sn.head_stats = u->head_stats;
-  sn.res.clear(); sn.attn.clear(); sn.outs.clear(); sn.cats.clear();
-  for (auto& r : u->res) sn.res.push_back(r.sv);
-  for (auto& a : u->attn) sn.attn.push_back(a.sv);
-  std::vector<BlockL*> blocks;
-  snap_blocks(u, blocks);
-  for (BlockL* b : blocks) { sn.outs.push_back(b->out); sn.cats.push_back(b->cat); }
+  ISHAP_CHECK_HIP(hipMemcpyAsync(sn.film, k.film, sn.film_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+  sn.kept = k;
   sn.valid = true;
   return 0;
 }
@@ -1055,28 +1029,19 @@ int ishap_unet_snapshot_restore(ishap_unet* u, void* stream) {
   ISHAP_CHECK_HIP(hipSetDevice(u->device));
   hipStream_t s = (hipStream_t)stream;
   ISHAP_TRY(unet_join_tail(u, s));                 // a tail still in flight reads (and owns) the arena about to be overwritten
-  u->have_saved = false;
+  u->kept.have_saved = false;
   u->seq++;                                        // the gradient maps of a backward before this restore belong to another forward
   if (sn.arena_bytes) ISHAP_CHECK_HIP(hipMemcpyAsync(u->arena.base, sn.arena, sn.arena_bytes, hipMemcpyDeviceToDevice, s));
   if (sn.stat_count) ISHAP_CHECK_HIP(hipMemcpyAsync(u->stat_base, sn.stat, sn.stat_count * sizeof(long long), hipMemcpyDeviceToDevice, s));
-  u->film_cur = sn.film;                           // the snapshot's own rows: a later prepare_timesteps may rewrite the cache
-  u->film_cur_ld = sn.film_ld;
-  u->fwd_mark = sn.fwd_mark; u->stat_fwd_mark = sn.stat_fwd_mark;
-  u->arena.off = sn.fwd_mark; u->stat_off = sn.stat_fwd_mark;
-  u->last_N = sn.last_N; u->last_feat = sn.last_feat;
-  u->tap = sn.tap; u->x0 = sn.x0; u->h_final = sn.h_final; u->head_stats = sn.head_stats;
-  for (size_t i = 0; i < u->res.size(); ++i) u->res[i].sv = sn.res[i];
-  for (size_t i = 0; i < u->attn.size(); ++i) u->attn[i].sv = sn.attn[i];
-  std::vector<BlockL*> blocks;
-  snap_blocks(u, blocks);
-  for (size_t i = 0; i < blocks.size(); ++i) { blocks[i]->out = sn.outs[i]; blocks[i]->cat = sn.cats[i]; }
-  u->last_overlap = false;
+  u->kept = sn.kept;                               // have_saved comes back with it: a snapshot is only taken of a kept forward
+  u->arena.off = u->kept.fwd_mark; u->stat_off = u->kept.stat_fwd_mark;
+  u->kept.film = sn.film;                          // the snapshot's own rows: a later prepare_timesteps may rewrite the cache
+  u->kept.tail_planned = false;                    // no tail is planned or deferred: the snapshot holds none
   u->tail_deferred = false;
   u->mid_recorded = false;
-  u->restored_partial = sn.partial;
-  u->bwd_since_fwd = 1;                            // the statistics scratch above the mark is whatever the last backward left:
-  u->have_saved = true;                            // the next backward zeroes it, as a second backward on one forward does
-  return 0;
+  u->kept.restored_partial = sn.partial;
+  u->kept.bwd_since_fwd = 1;                       // the statistics scratch above the mark is whatever the last backward left:
+  return 0;                                        // the next backward zeroes it, as a second backward on one forward does
 }
 
 int ishap_unet_snapshot_drop(ishap_unet* u) {
@@ -1084,8 +1049,8 @@ int ishap_unet_snapshot_drop(ishap_unet* u) {
   ISHAP_CHECK_HIP(hipSetDevice(u->device));
   UnetSnapshot& sn = u->snap;
   sn.valid = false;
-  if (u->restored_partial || u->film_cur == sn.film) u->have_saved = false;    // the kept state reads the rows about to be freed
-  if (u->film_cur == sn.film) { u->film_cur = u->d_film; u->film_cur_ld = u->film_rows; }
+  if (u->kept.restored_partial || u->kept.film == sn.film) u->kept.have_saved = false;    // the kept state reads the rows about to be freed
+  if (u->kept.film == sn.film) { u->kept.film = u->d_film; u->kept.film_ld = u->film_rows; }
   if (sn.arena) ISHAP_CHECK_HIP(hipFree(sn.arena));
   sn.arena = nullptr; sn.arena_cap = 0;
   if (sn.stat) ISHAP_CHECK_HIP(hipFree(sn.stat));

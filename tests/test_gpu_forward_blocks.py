@@ -183,7 +183,8 @@ def test_every_block_output_vs_float64_block(name):
 def test_every_block_output_with_the_deferred_tail(name):
     """`overlap_tail=True` at a middle output block: the blocks after the tap and the head are planned by the forward and launched
     by `run_tail()` on the context's side stream; every block (those after the tap too) and the output under the plain pass's
-    bounds, and bitwise the plain pass's."""
+    bounds, and bitwise the plain pass's.  On deep also a tail that only the NEXT forward's join enqueues: its output buffer must
+    come out as the plain pass's, bit for bit, although that forward records a tail of its own at other timesteps."""
     from ishapediting_amd import _lib
     t0 = time.time()
     m, ref, sd, x, ts, emb = _model(name)
@@ -214,13 +215,25 @@ def test_every_block_output_with_the_deferred_tail(name):
     m.join_tail()
     torch.cuda.synchronize()
     assert torch.equal(out2, out0) and _same(acts2, acts0)
+    if name != "deep":
+        return
+    # a tail nobody enqueued, with another forward started on the context: that forward's own join enqueues the first call's tail
+    # before anything of the second is recorded -- a stale or early-cleared record of the tail's launches would show in `out3`
+    out3, _ = m(xd, ts, feat_layer=k, keep_for_backward=True, overlap_tail=True)
+    torch.cuda.synchronize()
+    out3.fill_(float("nan"))            # as above: only a tail enqueued from here on can make it finite again
+    out4, _ = m(xd, [t + 100.0 for t in ts], feat_layer=k, keep_for_backward=True, overlap_tail=True)
+    m.join_tail()
+    torch.cuda.synchronize()
+    assert torch.equal(out3, out0), "the first call's output, its tail enqueued by the next forward's join"
+    assert bool(torch.isfinite(out4).all()) and not torch.equal(out4, out0), "the second call ran at its own timesteps"
 
 
 @pytest.mark.parametrize("name", ["deep", "tiny2"])
 def test_forward_bit_equalities(name):
     """What must not change a bit of the model output or of any block: running the forward again (the statistics arena is zeroed
     again by the layout conversion's extra blocks: a short zeroing shows here), a backward in between, keep_for_backward=False
-    (no launch decision reads Exec::keep), prepared timestep rows (include/ishap.h promises bit identity) and dropping them again,
+    (no launch decision reads the flag), prepared timestep rows (include/ishap.h promises bit identity) and dropping them again,
     and a context created for a larger batch than it serves."""
     from ishapediting_amd.unet import UNetModel
     m, ref, sd, x, ts, emb = _model(name)
