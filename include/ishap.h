@@ -62,7 +62,8 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * regions (ishap_region_plane_marks, ishap_region_plane_feather, ishap_region_plane_feather_scratch_bytes);
                             * 24 since the volume constraints (ishap_constraint_setup, ishap_constraint_setup_scratch_bytes,
                             * ishap_constraint_loss_grad); 25 since the sparse high-resolution surface
-                            * (ishap_triplane_decode_bricks, ishap_sparse_*) */
+                            * (ishap_triplane_decode_bricks, ishap_sparse_*); 26 since the quadric vertex clustering
+                            * (ishap_mesh_simplify_scratch_bytes, ishap_mesh_simplify_count, ishap_mesh_simplify_emit) */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -746,6 +747,53 @@ int ishap_sparse_surface_count(const float* values, const int* ordered, long lon
 int ishap_sparse_surface_emit(const float* values, const int* ordered, long long nbricks, int R, float level,
                               const int* slot_map, unsigned* reach, void* scratch, long long scratch_bytes, float* verts,
                               int* tris, void* stream);
+
+/* ---------------------------------------------------------------- Mesh simplification (ABI 26, csrc/simplify.hip)
+ * Quadric vertex clustering: Open3D's simplify_vertex_clustering(voxel_size, contraction = Quadric | Average) on the device,
+ * one pass, integer atomics only, bitwise repeatable and independent of the order of the input.  The reference has no
+ * counterpart (its meshes stop at 256^3).  THE RULE (tests/simplify_ref.py restates it in float64 numpy; every float64
+ * expression below is evaluated as written, left to right, without fused multiply-add):
+ * Inputs: verts float[V][3], tris int[F][3] (device); a grid: origin lo[3] (double), cell size h > 0 (double), dims
+ *   g = (gx, gy, gz) >= 1 with gx gy gz <= 2^30.  A triangle with a corner outside 0 .. V - 1 takes part in nothing.
+ * Cells: per axis q = ((double)v - lo) / h, c = clamp(floor(q), 0, g - 1) with a NaN floor taken as 0; cell id
+ *   (cx gy + cy) gz + cz; local coordinate p = clamp(q - (c + 0.5), -0.5, 0.5), a NaN p taken as 0.
+ * Clusters: the non-empty cells, numbered in ascending cell id.
+ * Per-cluster sums, all 64-bit integers (one row of 16 per cluster): [0] vertex count; [1..3] sum rint(p 2^32) per axis;
+ *   [4] lowest vertex index; [5..14] the quadric; [15] sum ceil(w).  Every triangle whose corners are valid adds, once per corner,
+ *   to the cluster of that corner in that corner's cell frame: P = q (unclamped), N = (P1 - P0) x (P2 - P0),
+ *   L = sqrt((Nx Nx + Ny Ny) + Nz Nz); skipped if L is 0 or not finite; n = N / L, w = L / 2,
+ *   d = -((nx px + ny py) + nz pz) with the corner's p; the ten values w (a b) over (a, b) = nx nx, nx ny, nx nz, ny ny, ny nz,
+ *   nz nz, nx d, ny d, nz d, d d, each added as rint(value 2^36); and ceil(w) to [15].  A triangle with w >= 2^26 adds 2^26 to
+ *   [15] and no quadric entry.
+ * Overflow guard: |n| <= 1 and |d| <= sqrt(3) / 2 bound every quadric entry by sum w, so below sum ceil(w) = 2^26 no sum
+ *   reaches 2^62.  If the [15] of a cluster that a kept triangle references reaches 2^26 (contraction quadric), count sets
+ *   bit 0 of its status word: the caller must not emit (use a larger cell, or contraction average).  Nothing wraps silently.
+ * Representative of a cluster, x in cell units: count 1: the vertex itself, its float bits copied.  Otherwise
+ *   mean = (double)[1..3] / ((double)count 2^32); A, b = (double)[5..13] / 2^36, tr = (A00 + A11) + A22; contraction average
+ *   or tr == 0: x = mean; else x solves (A + mu I) x = mu mean - b, mu = regularization tr (any direct float64 3x3 method:
+ *   the eigenvalues of A lie in [0, tr], so the matrix is symmetric positive definite with condition <= (1 + reg) / reg);
+ *   x clamped to [-0.5, 0.5] per axis; out = (float)(lo + h ((c + 0.5) + x)): a representative never leaves its cell.
+ * Triangles: corners -> clusters; dropped with two equal corners; rotated so that the smallest cluster comes first
+ *   (orientation kept); among equal rotated triples the lowest input index stays; emitted in ascending input index.  The
+ *   same three clusters in the opposite orientation are another triangle.
+ * Vertices out: the clusters a kept triangle references, in ascending cell id; vertex_map int[V] = the output index of each
+ *   input vertex's cluster, -1 if it has none.
+ * ishap_mesh_simplify_count: counts int[3] (device) = {vertices out, triangles out, status}; the first two ints of `scratch`
+ *   then hold {clusters, triangles with three distinct clusters}.  ishap_mesh_simplify_emit: same arguments and the SAME
+ *   scratch, untouched in between; out_verts float[3 vertices], out_tris int[3 triangles], vertex_map int[V];
+ *   vertex_cluster: NULL, or int[V] that receives the cluster of every input vertex (the partition itself; -1 for an empty mesh).
+ *   contraction: 0 quadric, 1 average.  scratch: ishap_mesh_simplify_scratch_bytes(V, F, dims) (-1 on bad sizes), 16-byte
+ *   aligned: the cell bitmap and its ranks (2 x 4 bytes per 32 cells), 4 bytes per vertex, 132 per possible cluster
+ *   (min(V, cells)), the triangle table (a power of two >= 2 F words) and 4 bytes per triangle.
+ *   Refused with -2 and a message before anything is enqueued: a NULL pointer, h <= 0 or not finite, a dim < 1, more than 2^30
+ *   cells, a scratch too small, an unknown contraction, 3 F or V beyond int32.  F = 0 or V = 0: an empty mesh (counts 0,
+ *   vertex_map -1), set by memsets, no kernel launch.  lo and dims are HOST pointers, read during the call. */
+long long ishap_mesh_simplify_scratch_bytes(long long nverts, long long ntris, const int* dims);
+int ishap_mesh_simplify_count(const float* verts, long long nverts, const int* tris, long long ntris, const double* lo, double h,
+                              const int* dims, int contraction, void* scratch, long long scratch_bytes, int* counts, void* stream);
+int ishap_mesh_simplify_emit(const float* verts, long long nverts, const int* tris, long long ntris, const double* lo, double h,
+                             const int* dims, int contraction, double regularization, void* scratch, long long scratch_bytes,
+                             float* out_verts, int* out_tris, int* vertex_map, int* vertex_cluster, void* stream);
 
 /* in place: v <- (v + sum of neighbours) / (1 + number of neighbours), `iterations` Jacobi sweeps (each neighbour once:
  * Open3D's filter_smooth_simple).  box_max > 0: the vertices are in grid coordinates of a [0, box_max]^3 volume and the

@@ -266,6 +266,12 @@ SYMBOLS = {
                                              C.c_longlong, c_void_p, c_void_p]),
     "ishap_sparse_surface_emit": (C.c_int, [c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_float, c_void_p, c_void_p, c_void_p,
                                             C.c_longlong, c_void_p, c_void_p, c_void_p]),
+    "ishap_mesh_simplify_scratch_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.POINTER(C.c_int)]),
+    "ishap_mesh_simplify_count": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, C.POINTER(C.c_double), C.c_double,
+                                            C.POINTER(C.c_int), C.c_int, c_void_p, C.c_longlong, c_void_p, c_void_p]),
+    "ishap_mesh_simplify_emit": (C.c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, C.POINTER(C.c_double), C.c_double,
+                                           C.POINTER(C.c_int), C.c_int, C.c_double, c_void_p, C.c_longlong, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -305,9 +311,9 @@ def lib():
         # 22: ishap_drag_retarget / ishap_drag_batch_retarget / ishap_drag_batch_retarget_each;
         # 23: ishap_edt / ishap_edt_scratch_bytes / ishap_region_plane_marks / ishap_region_plane_feather[_scratch_bytes];
         # 24: ishap_constraint_setup / ishap_constraint_setup_scratch_bytes / ishap_constraint_loss_grad;
-        # 25: ishap_triplane_decode_bricks / ishap_sparse_*
-        if l.ishap_version() < 25:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 25): rebuild with `python -m ishapediting_amd.build`")
+        # 25: ishap_triplane_decode_bricks / ishap_sparse_*; 26: ishap_mesh_simplify_*
+        if l.ishap_version() < 26:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 26): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 

@@ -731,7 +731,7 @@ static int snap_reserve(T** buf, size_t* cap, size_t need) {
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 25; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 26; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
@@ -765,6 +765,7 @@ int ishap_version(void) { return 25; }  // 2: ishap_mesh_smooth takes the scratc
                                         //     constrain.hip)
                                         // 25: sparse high-resolution surface (ishap_triplane_decode_bricks, ishap_sparse_*;
                                         //     sparse_surface.hip, decode.hip)
+                                        // 26: quadric vertex clustering (ishap_mesh_simplify_scratch_bytes / _count / _emit; simplify.hip)
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");

@@ -837,6 +837,8 @@ class DragStuff:
         self.mesh_resolution = None   # None, or an int above args.shape_resolution (up to 2048): get_mesh returns the surface at THAT
                                       # resolution, cut from bricks near the surface only (mesh.SparseOccupancyMesh) and seeded from the
                                       # shape_resolution volume, which stays `self.volume` for the metrics, regions and parts
+        self.mesh_simplify = None     # None, or a cell size in voxels of the mesh's grid (or mesh.OccupancyMesh's simplify dict): get_mesh
+                                      # reduces the smoothed mesh by quadric vertex clustering before refine (mesh.simplify_vertex_clustering)
         self.noise = []
         self.variance = []
         self.variance_noise = []
@@ -967,8 +969,10 @@ class DragStuff:
         if self.clean is not None:    # floaters / cavities out before the surface; self.volume is then the cleaned volume
             self.volume = clean_volume(self.volume, **self.clean)
         if sparse is not None:        # the volume decoded anyway seeds the bricks of the fine grid
-            return mesh_backend.sparse_volume_to_mesh(self.decoder, planes, sparse, self.volume, smooth_iterations=10, refine=refine)
-        return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10, refine=refine)
+            return mesh_backend.sparse_volume_to_mesh(self.decoder, planes, sparse, self.volume, smooth_iterations=10, refine=refine,
+                                                      simplify=self.mesh_simplify)
+        return mesh_backend.volume_to_mesh(self.volume, self.args.shape_resolution, smooth_iterations=10, refine=refine,
+                                           simplify=self.mesh_simplify)
 
     # ------------------------------------------------------------------ drag loop (:302-399)
     def _guided_loop(self, img, dk, guidance, stride, scales, guided_scale, reuse_first=False, trk=None, cl=None, vol=None):

@@ -31,6 +31,8 @@ def build_parser():
     p.add_argument("--shape_resolution", type=int, default=256)
     p.add_argument("--mesh_resolution", type=int, default=None,
                    help="above --shape_resolution (up to 2048): write each mesh at this resolution, cut from bricks near the surface only")
+    p.add_argument("--mesh_simplify", type=float, default=None,
+                   help="cell size in voxels of the mesh's grid: reduce each mesh by quadric vertex clustering before it is written")
     p.add_argument("--synthetic", action="store_true", help="seeded random weights instead of checkpoints")
     return p
 
@@ -86,7 +88,8 @@ def main(argv=None, overrides=None):
     for idx, triplane in enumerate(samples):
         print(f"Decoding triplane {idx}...")
         decoder_args = Namespace(input=f"{args.save_dir}/triplanes/{idx}.npy", output=f"{args.save_dir}/objects/{idx}.obj",
-                                 model_path=args.decoder_ckpt, res=args.shape_resolution, mesh_res=args.mesh_resolution)
+                                 model_path=args.decoder_ckpt, res=args.shape_resolution, mesh_res=args.mesh_resolution,
+                                 mesh_simplify=args.mesh_simplify)
         visualize.main(args=decoder_args, state_dict=dec_sd)        # generate.py:88-95
     print("Done!")
     print("decode time:", time.time() - t2)

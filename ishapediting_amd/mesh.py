@@ -90,6 +90,124 @@ def smooth_mesh(verts: torch.Tensor, tris: torch.Tensor, iterations: int = 10, b
     return out
 
 
+class SimplifyInfo(NamedTuple):
+    """simplify_vertex_clustering: non-empty cells, vertices in / out, triangles in / with three distinct clusters / out (the
+    difference of the last two is the duplicates dropped) and the bytes of device memory the call held at its end (scratch,
+    counts and the outputs)"""
+    clusters: int
+    vertices_in: int
+    vertices_out: int
+    triangles_in: int
+    triangles_nondegenerate: int
+    triangles_out: int
+    bytes: int
+
+
+CONTRACTIONS = {"quadric": 0, "average": 1}
+SIMPLIFY_MAX_CELLS = 1 << 30
+
+
+def _checked_simplify(simplify) -> dict:
+    """the `simplify` keyword of the mesh classes: None, a cell size in voxels, or {"cell": voxels, "contraction": ...,
+    "regularization": ...}"""
+    if simplify is None:
+        return None
+    if not isinstance(simplify, dict):
+        simplify = {"cell": simplify}
+    unknown = [k for k in simplify if k not in ("cell", "contraction", "regularization")]
+    if unknown or "cell" not in simplify:
+        raise ValueError(f'simplify must be None, a cell size or a dict with "cell" (and "contraction", "regularization"); got {simplify!r}')
+    out = dict(simplify)
+    out["cell"] = float(out["cell"])
+    if not (out["cell"] > 0 and np.isfinite(out["cell"])):
+        raise ValueError(f"simplify: the cell size must be positive and finite, not {out['cell']}")
+    _check_choice("simplify contraction", out.get("contraction", "quadric"), tuple(CONTRACTIONS))
+    return out
+
+
+def simplify_vertex_clustering(verts: torch.Tensor, tris: torch.Tensor, cell: float, contraction: str = "quadric", origin=None,
+                               dims=None, regularization: float = 1e-3, return_map: bool = False, return_clusters: bool = False):
+    """Open3D's simplify_vertex_clustering(voxel_size=cell, contraction=Quadric | Average) on the device (csrc/simplify.hip; the
+    rule: include/ishap.h, "Mesh simplification"): the vertices of each cell of the grid `origin + cell * [0, dims)` become one
+    vertex -- the point that minimises the area-weighted squared distance to the planes of the cluster's triangles, pulled
+    towards the cluster's mean by `regularization` and kept inside the cell ("quadric"), or the mean ("average") -- triangles
+    with two corners in one cell go, and of several triangles on the same three cells in the same orientation the first stays.
+    Returns (vertices [Vo,3] float32, triangles [Fo,3] int32, SimplifyInfo), with return_map also vertex_map [V] int32 (the
+    output vertex of each input vertex, -1 where its cell is touched by no kept triangle), with return_clusters after it
+    vertex_cluster [V] int32 (the cluster of each input vertex, clusters numbered in ascending cell id: the partition itself,
+    also where no triangle is kept), all on the device.  Only integer
+    atomics: the result is bit for bit the same from run to run and does not depend on the order of the input triangles or
+    vertices (the output rows follow the cell ids and the input triangle order).
+    origin: default verts.amin(0) as float64; dims: default floor((max - origin) / cell) + 1 per axis; vertices outside the
+    grid are clamped into its border cells.  At most 2^30 cells.
+    Memory: the scratch is sized before the number of clusters is known, 132 bytes for each of min(V, cells) POSSIBLE clusters
+    besides 8 bytes per 32 cells, 4 per vertex and 8 to 20 per triangle -- about 1.3 GB of rows for a 10 M vertex mesh, of which
+    the clusters there are use a fraction (SimplifyInfo.bytes reports what was held).
+    Host read-backs: ONE for the output sizes (with the status word and the info counts); one more, before it, for the bounding
+    box when origin or dims is left to the default.
+    Raises RuntimeError if the accumulated triangle area of a cluster could overflow the 64-bit sums (2^26 cell faces in one
+    cell): use a larger cell or contraction="average".
+    Clustering can leave non-manifold edges and vertices where a feature is thinner than a cell (two sheets that fall into one
+    cell are joined); nothing here repairs that."""
+    _need_gpu(verts, "simplify_vertex_clustering")
+    _check_choice("contraction", contraction, tuple(CONTRACTIONS))
+    cell, regularization = float(cell), float(regularization)
+    if not (cell > 0 and np.isfinite(cell)):
+        raise ValueError(f"simplify_vertex_clustering: the cell size must be positive and finite, not {cell}")
+    if not (regularization > 0 and np.isfinite(regularization)):
+        raise ValueError(f"simplify_vertex_clustering: regularization must be positive and finite, not {regularization}")
+    dev = verts.device
+    v = verts.detach().to(torch.float32).contiguous().reshape(-1, 3)
+    t = tris.detach().to(device=dev, dtype=torch.int32).contiguous().reshape(-1, 3)
+    nv, nt = int(v.shape[0]), int(t.shape[0])
+    if nv > 0x7fffffff or 3 * nt > 0x7fffffff:
+        raise ValueError("simplify_vertex_clustering: vertex indices and 3 * triangles must fit int32")
+    i32 = dict(dtype=torch.int32, device=dev)
+    if nv == 0 or nt == 0:
+        out = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), **i32), SimplifyInfo(0, nv, 0, nt, 0, 0, 0))
+        out = out + (torch.full((nv,), -1, **i32),) if return_map else out
+        return out + (torch.full((nv,), -1, **i32),) if return_clusters else out
+    if origin is None or dims is None:
+        box = torch.stack([v.amin(0), v.amax(0)]).to(torch.float64).cpu().numpy()          # the bounding-box read-back
+        if not np.isfinite(box).all():
+            raise ValueError("simplify_vertex_clustering: the vertices are not finite; pass origin and dims")
+        if origin is None:
+            origin = box[0]
+    lo = np.asarray(origin, dtype=np.float64).reshape(3)
+    if dims is None:
+        dims = np.maximum(np.floor((box[1] - lo) / cell), 0).astype(np.int64) + 1
+    dims = [int(d) for d in np.asarray(dims).reshape(3)]
+    if min(dims) < 1 or dims[0] * dims[1] * dims[2] > SIMPLIFY_MAX_CELLS:
+        raise ValueError(f"simplify_vertex_clustering: dims {dims} must be >= 1 with at most 2^30 cells; use a larger cell")
+    L = _lib.lib()
+    lo_c, dims_c = (C.c_double * 3)(*lo.tolist()), (C.c_int * 3)(*dims)
+    nbytes = int(L.ishap_mesh_simplify_scratch_bytes(nv, nt, dims_c))
+    if nbytes < 0:
+        raise RuntimeError("ishap_mesh_simplify_scratch_bytes: invalid sizes")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(3, **i32)
+    mode = CONTRACTIONS[contraction]
+    with torch.cuda.device(dev):
+        s = _lib.stream_ptr(dev)
+        common = (v.data_ptr(), nv, t.data_ptr(), nt, lo_c, cell, dims_c, mode)
+        _lib.check(L.ishap_mesh_simplify_count(*common, scratch.data_ptr(), nbytes, counts.data_ptr(), s))
+        vo, to, status, clusters, nondeg = torch.cat([counts, scratch[:8].view(torch.int32)]).tolist()     # the one host read-back
+        if status != 0:
+            raise RuntimeError("simplify_vertex_clustering: the triangle area gathered in one cell reaches 2^26 cell faces, the "
+                               "64-bit quadric sums could overflow; use a larger cell or contraction=\"average\"")
+        out_v = torch.empty((max(vo, 1), 3), dtype=torch.float32, device=dev)      # an empty result still needs an address
+        out_t = torch.empty((max(to, 1), 3), **i32)
+        vmap = torch.empty(nv, **i32)
+        vclus = torch.empty(nv, **i32) if return_clusters else None
+        _lib.check(L.ishap_mesh_simplify_emit(*common, regularization, scratch.data_ptr(), nbytes, out_v.data_ptr(), out_t.data_ptr(),
+                                              vmap.data_ptr(), _lib.ptr(vclus), s))
+    out_v, out_t = out_v[:vo], out_t[:to]
+    held = sum(x.numel() * x.element_size() for x in (scratch, counts, out_v, out_t, vmap))
+    info = SimplifyInfo(int(clusters), nv, int(vo), nt, int(nondeg), int(to), held)
+    out = (out_v, out_t, info, vmap) if return_map else (out_v, out_t, info)
+    return out + (vclus,) if return_clusters else out
+
+
 def chamfer_distance(pa: torch.Tensor, pb: torch.Tensor, point_num=20000, seed: int = 0, query_num=None) -> float:
     """meshProcess.py:18-35: mean squared nearest-neighbour distance a->b plus b->a on `point_num` samples per side
     (the reference samples mesh surfaces with Open3D; here the samples are drawn from the given point sets).
@@ -166,13 +284,20 @@ class OccupancyMesh:
     in decoder coordinates) with the triangles unchanged, and compute_vertex_normals() stores the field's analytic normals
     -grad / |grad| (the direction of decreasing logit: outward, logits are positive inside) instead of the triangle sum.
     Two further keys are passed on to project_to_surface when given: `step_max` (longest single step, default half a voxel)
-    and `tol` (|logit| at which a vertex is left alone); any other key raises."""
+    and `tol` (|logit| at which a vertex is left alone); any other key raises.
+    simplify: None (nothing new runs: the mesh is bit for bit what it was), a cell size in voxels, or a dict {"cell": voxels,
+    "contraction": "quadric" | "average", "regularization": 1e-3}: after smoothing and BEFORE refine the mesh goes through
+    simplify_vertex_clustering in grid units with origin 0, so the cells line up with the voxel grid; refine then puts the
+    fewer, moved vertices back on the level set and the field normals are per output vertex.  `.simplification` is the
+    SimplifyInfo once the mesh is built."""
 
-    def __init__(self, volume: torch.Tensor, res: int, smooth_iterations: int = 10, clean=None, refine=None):
+    def __init__(self, volume: torch.Tensor, res: int, smooth_iterations: int = 10, clean=None, refine=None, simplify=None):
         self.volume = volume if clean is None else _cleaned(volume, clean)
         self.res = res
         self.smooth_iterations = smooth_iterations
         self.refine = None if refine is None else _checked_refine(refine)
+        self.simplify = _checked_simplify(simplify)
+        self.simplification = None    # simplify: the SimplifyInfo once the mesh is built
         self._mesh = None
         self._vnormals = None
         self._field_normals = None
@@ -182,10 +307,21 @@ class OccupancyMesh:
         if self._mesh is None:
             v, t = extract_surface(self.volume, 0.0)
             v = smooth_mesh(v, t, self.smooth_iterations, box_max=float(self.res - 1))     # in grid coordinates: the box is known
+            v, t = self._simplified(v, t)
             if self.refine is not None and v.shape[0] > 0:
                 v = self._refined(v)
             self._mesh = (v / self.res * 2 - 1, t)
         return self._mesh
+
+    def _simplified(self, v: torch.Tensor, t: torch.Tensor):
+        """grid units, origin 0, cells of `cell` voxels over the box [0, res - 1]: aligned with the voxel grid"""
+        if self.simplify is None or v.shape[0] == 0 or t.shape[0] == 0:
+            return v, t
+        sp = self.simplify
+        dims = [int(np.floor((self.res - 1) / sp["cell"])) + 1] * 3
+        v, t, self.simplification = simplify_vertex_clustering(v, t, sp["cell"], sp.get("contraction", "quadric"), origin=(0.0, 0.0, 0.0),
+                                                               dims=dims, regularization=sp.get("regularization", 1e-3))
+        return v, t
 
     def _refined(self, v: torch.Tensor) -> torch.Tensor:
         """grid units -> the decoder coordinates the volume was sampled at (linspace(-1, 1, res): c = 2 g / (res - 1) - 1, NOT
@@ -256,8 +392,9 @@ class OccupancyMesh:
         return m
 
     def __deepcopy__(self, memo):
-        m = OccupancyMesh(self.volume.clone(), self.res, self.smooth_iterations)
+        m = OccupancyMesh(self.volume.clone(), self.res, self.smooth_iterations, simplify=self.simplify)
         m.refine = self.refine                           # the decoder and the planes are shared, not copied
+        m.simplification = self.simplification
         if self._mesh is not None:
             m._mesh = (self._mesh[0].clone(), self._mesh[1].clone())
         if self._field_normals is not None:
@@ -423,11 +560,11 @@ class SparseOccupancyMesh(OccupancyMesh):
     g / res * 2 - 1, and the two differ by up to one voxel."""
 
     def __init__(self, decoder, planes: torch.Tensor, res: int, coarse: torch.Tensor, smooth_iterations: int = 10, refine=None,
-                 max_rounds: int = 64, max_bricks: int = 1 << 20):
+                 max_rounds: int = 64, max_bricks: int = 1 << 20, simplify=None):
         if not SPARSE_MIN_RES <= int(res) <= SPARSE_MAX_RES:
             raise ValueError(f"SparseOccupancyMesh: res = {res} is outside {SPARSE_MIN_RES} .. {SPARSE_MAX_RES}")
         super().__init__(coarse, int(res), smooth_iterations,
-                         refine=None if refine is None else dict(refine, decoder=decoder, planes=planes))
+                         refine=None if refine is None else dict(refine, decoder=decoder, planes=planes), simplify=simplify)
         self.decoder, self.planes = decoder, planes
         self.max_rounds, self.max_bricks = int(max_rounds), int(max_bricks)
         self.info = None
@@ -437,6 +574,7 @@ class SparseOccupancyMesh(OccupancyMesh):
             v, t, self.info = extract_surface_sparse(self.decoder, self.planes, self.res, self.volume, 0.0, self.max_rounds,
                                                      self.max_bricks)
             v = smooth_mesh(v, t, self.smooth_iterations, box_max=float(self.res - 1))
+            v, t = self._simplified(v, t)                # cells in FINE voxels
             if self.refine is not None and v.shape[0] > 0:
                 v = self._refined(v)
             self._mesh = (v / self.res * 2 - 1, t)
@@ -448,8 +586,8 @@ class SparseOccupancyMesh(OccupancyMesh):
 
     def __deepcopy__(self, memo):
         m = SparseOccupancyMesh(self.decoder, self.planes, self.res, self.volume.clone(), self.smooth_iterations,
-                                max_rounds=self.max_rounds, max_bricks=self.max_bricks)      # decoder and planes are shared
-        m.refine, m.info = self.refine, self.info
+                                max_rounds=self.max_rounds, max_bricks=self.max_bricks, simplify=self.simplify)      # decoder and planes are shared
+        m.refine, m.info, m.simplification = self.refine, self.info, self.simplification
         if self._mesh is not None:
             m._mesh = (self._mesh[0].clone(), self._mesh[1].clone())
         if self._field_normals is not None:
@@ -461,16 +599,17 @@ class SparseOccupancyMesh(OccupancyMesh):
 
 
 def sparse_volume_to_mesh(decoder, planes: torch.Tensor, res: int, coarse: torch.Tensor, smooth_iterations: int = 10,
-                          backend: str = None, refine=None):
+                          backend: str = None, refine=None, simplify=None):
     """volume_to_mesh's counterpart for a mesh resolution above the decoded volume's: a SparseOccupancyMesh ("device") or its
     open3d.geometry.TriangleMesh ("open3d"); "third_party" has no sparse path and raises.  coarse: the dense volume (cleaned
-    by the caller if it is to be), refine: OccupancyMesh's dict, decoder / planes taken from the arguments."""
+    by the caller if it is to be), refine: OccupancyMesh's dict, decoder / planes taken from the arguments; simplify:
+    OccupancyMesh's keyword, the cell in voxels of the FINE grid."""
     backend = BACKEND if backend is None else backend
     if backend not in ("device", "open3d"):
         raise ValueError(f'a sparse mesh needs the device surface (backend "device" or "open3d"), not {backend!r}')
     if refine is not None:
         refine = {k: v for k, v in refine.items() if k not in ("decoder", "planes")}
-    m = SparseOccupancyMesh(decoder, planes, res, coarse, smooth_iterations, refine=refine)
+    m = SparseOccupancyMesh(decoder, planes, res, coarse, smooth_iterations, refine=refine, simplify=simplify)
     if backend == "device":
         return m
     return (m if refine is None else m.compute_vertex_normals()).to_open3d()
@@ -525,7 +664,8 @@ def _cleaned(volume: torch.Tensor, clean: dict) -> torch.Tensor:
     return volume_ops.clean_volume(volume, **clean)
 
 
-def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, backend: str = None, clean=None, refine=None):
+def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, backend: str = None, clean=None, refine=None,
+                   simplify=None):
     """get_mesh's mesh (drag_utils.py:298-300).  clean: None, or a dict of volume.clean_volume keywords (e.g.
     {"keep": "largest"}): floaters / cavities are taken out of the volume before the surface is made, for every backend.
     backend None -> the module-level BACKEND:
@@ -535,19 +675,23 @@ def volume_to_mesh(volume: torch.Tensor, res: int, smooth_iterations: int = 10, 
                     cross PCIe (a few MB, not the 67 MB volume)
       "third_party" the reference's own PyMCubes + Open3D calls on the host.
     refine: None, or OccupancyMesh's refine dict {decoder, planes, iterations, max_move}: vertices back on the decoder's
-    level set and analytic normals ("device"; "open3d" hands over that refined mesh with its normals; "third_party" raises)."""
+    level set and analytic normals ("device"; "open3d" hands over that refined mesh with its normals; "third_party" raises).
+    simplify: None, or OccupancyMesh's simplify keyword (a cell size in voxels or a dict): the smoothed mesh is reduced by
+    quadric vertex clustering before refine ("device" and "open3d"; "third_party" raises)."""
     backend = BACKEND if backend is None else backend
     if clean is not None:
         volume = _cleaned(volume, clean)
     if backend == "device":
-        return OccupancyMesh(volume, res, smooth_iterations, refine=refine)
+        return OccupancyMesh(volume, res, smooth_iterations, refine=refine, simplify=simplify)
     if backend == "open3d":
-        m = OccupancyMesh(volume, res, smooth_iterations, refine=refine)
+        m = OccupancyMesh(volume, res, smooth_iterations, refine=refine, simplify=simplify)
         return (m if refine is None else m.compute_vertex_normals()).to_open3d()
     if backend != "third_party":
         raise ValueError(f"unknown mesh backend {backend!r}")
     if refine is not None:
         raise ValueError('refine needs the device surface (backend "device" or "open3d"): the third_party meshes are made on the host')
+    if simplify is not None:
+        raise ValueError('simplify needs the device surface (backend "device" or "open3d"): the third_party meshes are made on the host')
     import mcubes
     import open3d as o3d
     vertices, triangles = mcubes.marching_cubes(volume.detach().cpu().numpy(), 0)

@@ -39,16 +39,35 @@ def create_obj(model: MultiTriplane, obj_idx: int, res: int = 128, max_batch_siz
     return vol
 
 
-def create_obj_sparse(model: MultiTriplane, obj_idx: int, res: int, mesh_res: int, output_path: str = "output.obj"):
+def _simplified(verts, tris, grid_res: int, cell):
+    """mesh.simplify_vertex_clustering on a surface in grid coordinates of a grid_res^3 grid, cells of `cell` voxels from origin 0"""
+    if cell is None or verts.shape[0] == 0 or tris.shape[0] == 0:
+        return verts, tris
+    dims = [int(np.floor((grid_res - 1) / float(cell))) + 1] * 3
+    return mesh_backend.simplify_vertex_clustering(verts, tris, float(cell), origin=(0.0, 0.0, 0.0), dims=dims)[:2]
+
+
+def create_obj_simplified(model: MultiTriplane, obj_idx: int, res: int, cell: float, output_path: str = "output.obj"):
+    """create_obj with the surface reduced by quadric vertex clustering (cells of `cell` voxels) before it is written; the same
+    vertex convention, / 255 * 2 - 1"""
+    vol = decode_grid(model, obj_idx, res)
+    verts, tris = _simplified(*mesh_backend.extract_surface(vol, 0.0), res, cell)
+    mesh_backend.write_surface(output_path, verts / 255.0 * 2 - 1, tris)
+    return vol
+
+
+def create_obj_sparse(model: MultiTriplane, obj_idx: int, res: int, mesh_res: int, output_path: str = "output.obj", simplify=None):
     """create_obj at a mesh resolution above the decoded grid's: the dense res^3 volume only seeds the bricks of the fine grid
     (mesh.extract_surface_sparse); vertices / (mesh_res - 1) * 2 - 1, create_obj's convention (255 = 256 - 1) at that grid.
     Written by mesh.write_surface: streamed OBJ text (binary PLY if output_path ends in .ply); more than
-    mesh.MAX_SPARSE_OBJ_VERTICES vertices as text raise -- no stub file."""
+    mesh.MAX_SPARSE_OBJ_VERTICES vertices as text raise -- no stub file.
+    simplify: None, or a cell size in fine voxels: the surface is reduced by quadric vertex clustering before it is written."""
     model.eval()
     planes = model._planes(obj_idx)
     vol = decode_planes_grid(model, planes, res)
     verts, tris, info = mesh_backend.extract_surface_sparse(model, planes, mesh_res, vol)
     del info
+    verts, tris = _simplified(verts, tris, mesh_res, simplify)
     mesh_backend.write_surface(output_path, verts / (mesh_res - 1) * 2 - 1, tris)
     return vol
 
@@ -88,8 +107,11 @@ def main(args=None, feature=None, state_dict=None):
     for i in range(3):
         model.embeddings[i] = torch.as_tensor(triplanes[[i]], device=device)
     mesh_res = getattr(args, "mesh_res", None)          # generate.py --mesh_resolution; absent or not above res: the dense path
+    cell = getattr(args, "mesh_simplify", None)         # generate.py --mesh_simplify; absent: the mesh as cut
     if mesh_res is not None and int(mesh_res) > args.res:
-        create_obj_sparse(model, 0, args.res, int(mesh_res), output_path=args.output)
+        create_obj_sparse(model, 0, args.res, int(mesh_res), output_path=args.output, simplify=cell)
+    elif cell is not None:
+        create_obj_simplified(model, 0, args.res, float(cell), output_path=args.output)
     else:
         create_obj(model, 0, res=args.res, output_path=args.output)
 

@@ -7,9 +7,10 @@ moved by --offset, training() runs the guided loop, and before.png / after.png s
 spheres and green arrows.  With synthetic weights the decoded shape is noise; the path is the point.
 
   python tools/headless_edit.py --out /tmp/edit [--handles 3] [--num_steps 6] [--w_time 3] [--res 64] [--size 512] [--clean largest]
-                                [--refine 4] [--mesh-resolution 512]
+                                [--refine 4] [--mesh-resolution 512] [--simplify 2]
 
 --mesh-resolution R (above --res) cuts every mesh at R from bricks near the surface only (DragStuff.mesh_resolution).
+--simplify CELL reduces every mesh by quadric vertex clustering with cells of CELL voxels of the mesh's grid (DragStuff.mesh_simplify).
 --clean largest keeps only the largest connected component of every decoded volume (DragStuff.clean, volume.clean_volume).
 --refine N puts every mesh's smoothed vertices back on the decoder's zero level set with N projection steps of at most one voxel
 in all (DragStuff.refine) and shades the pictures with the field's analytic normals.
@@ -207,6 +208,7 @@ def edit(a):
     if a.refine is not None:
         ds.refine = {"iterations": a.refine, "max_move": 2.0 / (a.res - 1)}
     ds.mesh_resolution = a.mesh_resolution
+    ds.mesh_simplify = a.simplify
     ds.load_weights(synthetic.round_torso_to_fp16(synthetic.unet_state_dict(full_config(), 1234)), synthetic.decoder_state_dict(4321),
                     -0.05 * np.ones(96, np.float32), 0.05 * np.ones(96, np.float32))
     ds.update_latent_params(img=synthetic.latent(0))
@@ -363,6 +365,8 @@ def build_parser():
     p.add_argument("--mesh-resolution", type=int, default=None, metavar="R",
                    help="above --res (up to 2048): every mesh at this resolution, cut from bricks near the surface only "
                         "(DragStuff.mesh_resolution); the volume, the metrics and the parts stay at --res")
+    p.add_argument("--simplify", type=float, default=None, metavar="CELL",
+                   help="reduce every mesh by quadric vertex clustering, cells of CELL voxels of the mesh's grid (DragStuff.mesh_simplify)")
     p.add_argument("--refine", type=int, default=None, metavar="N",
                    help="project the mesh vertices back onto the decoder's level set with N steps (DragStuff.refine)")
     for role in ("keep", "free"):
