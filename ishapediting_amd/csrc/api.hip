@@ -288,20 +288,16 @@ int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit, const 
 
 // ---- E edits per call: one scratch buffer, carved as [grad_fx E*W*W*ld int64][acc E*2 int64][nmask E int32][touched E*3*W*W]
 // [chan_weight 3*ld], every part starting on a 256-byte boundary
-static long long drag_batch_carve(int E, int W, int ld, long long* o_acc, long long* o_nmask, long long* o_touched, long long* o_chw) {
-  auto up = [](long long v) { return (v + 255) & ~255ll; };
-  long long o = up((long long)E * W * W * ld * 8);
-  *o_acc = o; o = up(o + (long long)E * 16);
-  *o_nmask = o; o = up(o + (long long)E * 4);
-  *o_touched = o; o = up(o + (long long)E * 3 * W * W);
-  *o_chw = o; o = up(o + 3ll * ld);
-  return o;
+struct DragBatchScratch { long long *gfx, *acc; int* nmask; unsigned char *touched, *chw; long long bytes; };
+static DragBatchScratch drag_batch_carve(void* base, int E, int W, int ld) {
+  Carve c{(char*)base};
+  return {c.take<long long>((long long)E * W * W * ld), c.take<long long>(2ll * E), c.take<int>(E),
+          c.take<unsigned char>(3ll * E * W * W), c.take<unsigned char>(3ll * ld), c.total()};
 }
 
 long long ishap_drag_batch_scratch_bytes(int E, int W, int ld) {
   if (E < 1 || W < 2 || ld < 1) return -1;
-  long long a, b, c, d;
-  return drag_batch_carve(E, W, ld, &a, &b, &c, &d);
+  return drag_batch_carve(nullptr, E, W, ld).bytes;
 }
 
 static int fill_drag_batch(const ishap_drag_batch_args* a, DragBatchArgs& d) {
@@ -309,15 +305,12 @@ static int fill_drag_batch(const ishap_drag_batch_args* a, DragBatchArgs& d) {
   ISHAP_REQUIRE(a->E >= 1 && a->E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");      // hoff / cof below hold that many
   ISHAP_REQUIRE(a->W > 1 && a->r >= 0 && a->Cc >= 1 && a->ld >= 1 && a->orig_stride >= 0, "drag dims");
   ISHAP_REQUIRE(!a->weights || a->weights_stride >= 0, "drag batch: negative weights_stride");
-  long long o_acc, o_nmask, o_touched, o_chw;
-  const long long need = drag_batch_carve(a->E, a->W, a->ld, &o_acc, &o_nmask, &o_touched, &o_chw);
-  ISHAP_REQUIRE(a->scratch_bytes >= need, "drag batch: scratch smaller than ishap_drag_batch_scratch_bytes(E, W, ld)");
+  const DragBatchScratch S = drag_batch_carve(a->scratch, a->E, a->W, a->ld);
+  ISHAP_REQUIRE(a->scratch_bytes >= S.bytes, "drag batch: scratch smaller than ishap_drag_batch_scratch_bytes(E, W, ld)");
   ISHAP_REQUIRE(((unsigned long long)a->scratch & 15ull) == 0, "drag batch: scratch must be 16-byte aligned");
-  char* sc = (char*)a->scratch;
   DragArgs& b = d.base;
   fill_drag_shared(a, b);
-  b.gfx = (long long*)sc; b.acc = (long long*)(sc + o_acc); b.nmask = (int*)(sc + o_nmask);
-  b.touched = (unsigned char*)(sc + o_touched); b.chw = (unsigned char*)(sc + o_chw);
+  b.gfx = S.gfx; b.acc = S.acc; b.nmask = S.nmask; b.touched = S.touched; b.chw = S.chw;
   d.E = a->E;
   d.orig_stride = a->orig_stride;
   for (int e = 0; e <= a->E; ++e) d.hoff[e] = a->handle_offsets[e];

@@ -116,6 +116,24 @@ __device__ __forceinline__ void store_out16(half_t* p, const half8& v) {
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// How a C-ABI entry lays out caller-supplied scratch: ONE function per scratch takes (base, sizes...), takes its buffers in
+// order and returns their typed pointers plus total().  The *_scratch_bytes entry calls it with a null base (null pointers,
+// the same offsets), the launcher with the caller's pointer; nothing else computes an offset into that scratch.  A short layout
+// is one braced list, `return {c.take<A>(n), c.take<B>(m), c.total()};`: its elements are evaluated in the order written.
+struct Carve {
+  char* base;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t count, size_t align = 256) {          // `count` elements of T from the next multiple of `align` bytes
+    off = align_up(off, align);
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += count * sizeof(T);
+    return p;
+  }
+  char* bytes(size_t n, size_t align = 256) { return take<char>(n, align); }       // a nested scratch, or fixed slack
+  long long total(size_t align = 256) const { return (long long)align_up(off, align); }   // taken so far: the size, or a prefix to zero
+};
+
 // ---------------------------------------------------------------------------------------
 // implicit GEMM (igemm.hip):  out[m][n] = alpha * sum_k X(m,k) * Wt[n][k]  (+bias[n]) (+res[m][n])
 //   X is either a row-major matrix (MODE_GEMM) or an NHWC feature map gathered as 3x3 patches

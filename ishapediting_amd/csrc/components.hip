@@ -309,14 +309,18 @@ int fill_box(Box& b, int nx, int ny, int nz) {
   return 0;
 }
 unsigned tiles(const Box& b) { return (unsigned)((b.nx + CC_TX - 1) / CC_TX) * (unsigned)b.tby * (unsigned)b.tbz; }
-// scratch: rank int[n] (flip: mark bytes[n]) | block sums, 256-byte aligned
-long long sums_offset(long long n) { return align_up(4 * n, 256); }
+// scratch: rank int[n] (flip: mark bytes[n], the same bytes) | block sums, 256-byte aligned
+struct CompScratch { int* rank; unsigned* bsum; long long bytes; };
+CompScratch comp_scratch(void* base, long long n) {
+  Carve c{(char*)base};
+  return {c.take<int>(n), c.take<unsigned>(scan_u32_blocks(n)), c.total()};
+}
 
 }  // namespace
 
 extern "C" long long ishap_volume_components_scratch_bytes(long long n) {
   if (n <= 0 || n >= (1ll << 31)) return -1;
-  return sums_offset(n) + align_up(4 * scan_u32_blocks(n), 256);
+  return comp_scratch(nullptr, n).bytes;
 }
 
 extern "C" int ishap_volume_label(const float* vol, int nx, int ny, int nz, float level, int phase, int connectivity, int* labels,
@@ -341,7 +345,7 @@ extern "C" int ishap_volume_components_count(const int* labels, int nx, int ny, 
   ISHAP_TRY(fill_box(b, nx, ny, nz));
   ISHAP_REQUIRE(labels && scratch && count, "volume_components_count: null argument");
   const long long n = (long long)nx * ny * nz, nb = scan_u32_blocks(n);
-  unsigned* bsum = (unsigned*)((char*)scratch + sums_offset(n));
+  unsigned* bsum = comp_scratch(scratch, n).bsum;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(cc_count_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, labels, n, bsum);
   scan_block_totals(bsum, nb, (unsigned*)count, s);              // the count is below 2^31: fill_box bounds n
@@ -354,8 +358,8 @@ extern "C" int ishap_volume_components_emit(const int* labels, int nx, int ny, i
   ISHAP_TRY(fill_box(b, nx, ny, nz));
   ISHAP_REQUIRE(labels && scratch && table, "volume_components_emit: null argument");
   const long long n = (long long)nx * ny * nz, nb = scan_u32_blocks(n);
-  int* rank = (int*)scratch;
-  const unsigned* bsum = (const unsigned*)((char*)scratch + sums_offset(n));
+  const CompScratch S = comp_scratch(scratch, n);
+  int* rank = S.rank; const unsigned* bsum = S.bsum;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(cc_rows_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, labels, n, bsum, rank, table);
   hipLaunchKernelGGL(cc_accum_kernel, dim3(tiles(b)), dim3(CC_THREADS), 0, s, labels, b, (const int*)rank, table);
@@ -370,7 +374,7 @@ extern "C" int ishap_volume_flip(const float* vol_in, float* vol_out, const int*
   ISHAP_REQUIRE(vol_in && vol_out && labels && scratch && nroots >= 0 && (roots || nroots == 0), "volume_flip: null argument");
   const int n = nx * ny * nz;
   hipStream_t s = (hipStream_t)stream;
-  unsigned char* mark = (unsigned char*)scratch;
+  unsigned char* mark = (unsigned char*)comp_scratch(scratch, n).rank;
   ISHAP_CHECK_HIP(hipMemsetAsync(mark, 0, (size_t)n, s));
   if (nroots > 0)
     hipLaunchKernelGGL(cc_mark_kernel, dim3((unsigned)((nroots + 255) / 256)), dim3(256), 0, s, roots, nroots, n, mark);

@@ -154,17 +154,11 @@ struct SetupScratch {
   size_t bytes;
 };
 
-SetupScratch setup_scratch(long long M, int S, void* base) {
+SetupScratch setup_scratch(void* base, long long M, int S) {
   const size_t rows = (size_t)3 * S * S;
-  char* p = (char*)base;
-  size_t off = 0;
-  SetupScratch r;
-  r.totals = (unsigned*)(p + off); off += align_up((size_t)(scan_u32_blocks((long long)rows + 1) + 1) * sizeof(unsigned), 256);
-  r.cursor = (unsigned*)(p + off); off += align_up(rows * sizeof(unsigned), 256);
-  r.key = (int*)(p + off); off += align_up((size_t)12 * M * sizeof(int), 256);
-  r.keyw = (float*)(p + off); off += align_up((size_t)12 * M * sizeof(float), 256);
-  r.bytes = off;
-  return r;
+  Carve c{(char*)base};
+  return {c.take<unsigned>(scan_u32_blocks((long long)rows + 1) + 1), c.take<unsigned>(rows), c.take<int>((size_t)12 * M),
+          c.take<float>((size_t)12 * M), (size_t)c.total()};
 }
 
 bool sizes_ok(long long M, int S) { return M >= 1 && M <= CONSTRAINT_MAX_POINTS && S >= 2 && S <= CONSTRAINT_MAX_S; }
@@ -173,13 +167,13 @@ bool sizes_ok(long long M, int S) { return M >= 1 && M <= CONSTRAINT_MAX_POINTS 
 
 long long constraint_setup_scratch_bytes(long long M, int S) {
   if (!sizes_ok(M, S)) return -1;
-  return (long long)setup_scratch(M, S, nullptr).bytes;
+  return (long long)setup_scratch(nullptr, M, S).bytes;
 }
 
 int constraint_setup_launch(const ConstraintSetupArgs& a, hipStream_t s) {
   ISHAP_REQUIRE(sizes_ok(a.M, a.S), "constraint setup: 1 <= M <= 2^20 points and 2 <= S <= 1024");
   ISHAP_REQUIRE(a.coords && a.row_start && a.entry && a.entry_w && a.scratch, "null argument");
-  const SetupScratch sc = setup_scratch(a.M, a.S, a.scratch);
+  const SetupScratch sc = setup_scratch(a.scratch, a.M, a.S);
   ISHAP_REQUIRE(a.scratch_bytes >= (long long)sc.bytes, "constraint setup: scratch too small (ishap_constraint_setup_scratch_bytes)");
   const long long rows = (long long)3 * a.S * a.S, taps = 12 * a.M;
   unsigned* count = (unsigned*)a.row_start;

@@ -545,39 +545,40 @@ __global__ __launch_bounds__(256) void nearest_vertex_kernel(const float* __rest
 
 // ---------------------------------------------------------------- scratch layout
 struct ArapLayout {
-  long long state, vt_off, vt_cur, ccount, has, row, zero_end;     // [state, zero_end) is cleared at the start of a call
-  long long totals, vt_list, cand, col, w, label, role, diag, x, r, z, pa, pb, q, R, part, bytes;
-  long long nscan, nb;
+  ArapState* st;
+  unsigned *vt_off, *vt_cur, *row, *totals, *vt_list, *cand, *col;
+  int *ccount, *has, *label, *role;
+  double *w, *diag, *x, *r, *z, *pbuf[2], *q, *R, *part;
+  long long zero_end, bytes, nb;           // [0, zero_end) is cleared at the start of a call
 };
-ArapLayout arap_layout(long long nv, long long nt, long long nc) {
-  (void)nc;
+ArapLayout arap_layout(void* base, long long nv, long long nt) {
+  Carve c{(char*)base};
   ArapLayout L;
-  L.nscan = scan_u32_blocks(nv + 1);
   L.nb = (nv + AB - 1) / AB;
-  L.state = 0;
-  L.vt_off = align_up(L.state + (long long)sizeof(ArapState), 256);
-  L.vt_cur = align_up(L.vt_off + 4 * (nv + 1), 256);
-  L.ccount = align_up(L.vt_cur + 4 * nv, 256);
-  L.has = align_up(L.ccount + 4 * nv, 256);
-  L.row = align_up(L.has + 4 * nv, 256);
-  L.zero_end = align_up(L.row + 4 * (nv + 1), 256);
-  L.totals = L.zero_end;
-  L.vt_list = align_up(L.totals + 4 * (L.nscan + 1), 256);
-  L.cand = align_up(L.vt_list + 4 * 3 * nt, 256);
-  L.col = align_up(L.cand + 4 * 6 * nt, 256);
-  L.w = align_up(L.col + 4 * 6 * nt, 256);
-  L.label = align_up(L.w + 8 * 6 * nt, 256);
-  L.role = align_up(L.label + 4 * nv, 256);
-  L.diag = align_up(L.role + 4 * nv, 256);
-  L.x = align_up(L.diag + 8 * nv, 256);
-  L.r = align_up(L.x + 24 * nv, 256);
-  L.z = align_up(L.r + 24 * nv, 256);
-  L.pa = align_up(L.z + 24 * nv, 256);
-  L.pb = align_up(L.pa + 24 * nv, 256);
-  L.q = align_up(L.pb + 24 * nv, 256);
-  L.R = align_up(L.q + 24 * nv, 256);
-  L.part = align_up(L.R + 72 * nv, 256);
-  L.bytes = align_up(L.part + 8 * NPART * L.nb, 256);
+  L.st = c.take<ArapState>(1);
+  L.vt_off = c.take<unsigned>(nv + 1);
+  L.vt_cur = c.take<unsigned>(nv);
+  L.ccount = c.take<int>(nv);
+  L.has = c.take<int>(nv);
+  L.row = c.take<unsigned>(nv + 1);
+  L.zero_end = c.total();
+  L.totals = c.take<unsigned>(scan_u32_blocks(nv + 1) + 1);
+  L.vt_list = c.take<unsigned>(3 * nt);
+  L.cand = c.take<unsigned>(6 * nt);
+  L.col = c.take<unsigned>(6 * nt);
+  L.w = c.take<double>(6 * nt);
+  L.label = c.take<int>(nv);
+  L.role = c.take<int>(nv);
+  L.diag = c.take<double>(nv);
+  L.x = c.take<double>(3 * nv);
+  L.r = c.take<double>(3 * nv);
+  L.z = c.take<double>(3 * nv);
+  L.pbuf[0] = c.take<double>(3 * nv);
+  L.pbuf[1] = c.take<double>(3 * nv);
+  L.q = c.take<double>(3 * nv);
+  L.R = c.take<double>(9 * nv);
+  L.part = c.take<double>(NPART * L.nb);
+  L.bytes = c.total();
   return L;
 }
 
@@ -591,7 +592,7 @@ int read_state(const ArapState* d, ArapState& h, hipStream_t s) {
 
 extern "C" long long ishap_arap_scratch_bytes(long long nverts, long long ntris, long long ncons) {
   if (nverts < 0 || ntris < 0 || ncons < 0) return -1;
-  return arap_layout(nverts, ntris, ncons).bytes;
+  return arap_layout(nullptr, nverts, ntris).bytes;
 }
 
 extern "C" int ishap_arap(const float* rest, long long nverts, const int* tris, long long ntris, const int* cons_ids,
@@ -607,35 +608,18 @@ extern "C" int ishap_arap(const float* rest, long long nverts, const int* tris, 
   ISHAP_REQUIRE(scratch_bytes >= ishap_arap_scratch_bytes(nverts, ntris, ncons),
                 "arap: scratch smaller than ishap_arap_scratch_bytes(nverts, ntris, ncons)");
   hipStream_t s = (hipStream_t)stream;
-  const ArapLayout L = arap_layout(nverts, ntris, ncons);
-  char* base = (char*)scratch;
-  ArapState* st = (ArapState*)(base + L.state);
-  unsigned* vt_off = (unsigned*)(base + L.vt_off);
-  unsigned* vt_cur = (unsigned*)(base + L.vt_cur);
-  int* ccount = (int*)(base + L.ccount);
-  int* has = (int*)(base + L.has);
-  unsigned* row = (unsigned*)(base + L.row);
-  unsigned* totals = (unsigned*)(base + L.totals);
-  unsigned* vt_list = (unsigned*)(base + L.vt_list);
-  unsigned* cand = (unsigned*)(base + L.cand);
-  unsigned* col = (unsigned*)(base + L.col);
-  double* w = (double*)(base + L.w);
-  int* label = (int*)(base + L.label);
-  int* role = (int*)(base + L.role);
-  double* diag = (double*)(base + L.diag);
-  double* x = (double*)(base + L.x);
-  double* r = (double*)(base + L.r);
-  double* z = (double*)(base + L.z);
-  double* pbuf[2] = {(double*)(base + L.pa), (double*)(base + L.pb)};
-  double* q = (double*)(base + L.q);
-  double* R = (double*)(base + L.R);
-  double* part = (double*)(base + L.part);
+  const ArapLayout L = arap_layout(scratch, nverts, ntris);
+  ArapState* st = L.st;
+  unsigned *vt_off = L.vt_off, *vt_cur = L.vt_cur, *row = L.row, *totals = L.totals, *vt_list = L.vt_list, *cand = L.cand, *col = L.col;
+  int *ccount = L.ccount, *has = L.has, *label = L.label, *role = L.role;
+  double *w = L.w, *diag = L.diag, *x = L.x, *r = L.r, *z = L.z, *q = L.q, *R = L.R, *part = L.part;
+  double* const* pbuf = L.pbuf;
   const int nv = (int)nverts, nc = (int)ncons, nb = (int)L.nb;
   const unsigned vb = (unsigned)L.nb, tb = (unsigned)((ntris + AB - 1) / AB);
   const unsigned t3b = (unsigned)((3 * ntris + AB - 1) / AB), cb = (unsigned)((ncons + AB - 1) / AB);
 
   // ---- ids in range and distinct, checked on the device before any kernel indexes with them
-  ISHAP_CHECK_HIP(hipMemsetAsync(base, 0, (size_t)L.zero_end, s));
+  ISHAP_CHECK_HIP(hipMemsetAsync(scratch, 0, (size_t)L.zero_end, s));
   hipLaunchKernelGGL(arap_check_tris_kernel, dim3(t3b), dim3(AB), 0, s, tris, 3 * ntris, nv, st);
   if (nc) hipLaunchKernelGGL(arap_check_cons_kernel, dim3(cb), dim3(AB), 0, s, cons_ids, nc, nv, ccount, st);
   ISHAP_CHECK_HIP(hipGetLastError());

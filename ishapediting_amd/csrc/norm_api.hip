@@ -15,17 +15,6 @@
 
 namespace {
 
-struct Carve {
-  char* base;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t count) {
-    off = align_up(off, 256);
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += count * sizeof(T);
-    return p;
-  }
-};
 struct Scratch {
   unsigned long long* rec;
   long long* csums;
@@ -40,11 +29,11 @@ Scratch carve(void* base, int N, int HW, int C) {
   Scratch s;
   s.rec = c.take<unsigned long long>((size_t)N * 32 * GN_REC_STRIDE);
   s.csums = c.take<long long>((size_t)N * C * 2);
-  s.zero_bytes = align_up(c.off, 256);
+  s.zero_bytes = c.total();
   s.partial = c.take<float>(gn_partial_floats(N, HW, C) + 64);
   s.ident = c.take<half_t>((size_t)align_up((size_t)C, 128) * C);
   s.copy = c.take<half_t>((size_t)N * HW * C);
-  s.total = align_up(c.off, 256);
+  s.total = c.total();
   return s;
 }
 

@@ -240,7 +240,11 @@ int knn_tile_stride(int ntiles) {
   }
 }
 
-long long orient_level_bytes(long long n) { return align_up(n * sizeof(int), 256); }
+struct OrientScratch { int* level; OrientState* st; long long bytes; };
+OrientScratch orient_scratch(void* base, long long n) {
+  Carve c{(char*)base};
+  return {c.take<int>(n), c.take<OrientState>(1), c.total()};
+}
 
 }  // namespace
 
@@ -272,7 +276,7 @@ extern "C" int ishap_cloud_normals(const float* points, long long npoints, const
 
 extern "C" long long ishap_cloud_orient_scratch_bytes(long long npoints) {
   if (npoints < 0) return -1;
-  return orient_level_bytes(npoints) + 256;
+  return orient_scratch(nullptr, npoints).bytes;
 }
 
 extern "C" int ishap_cloud_orient(const float* points, float* normals, const int* idx, long long npoints, int k, void* scratch,
@@ -286,8 +290,8 @@ extern "C" int ishap_cloud_orient(const float* points, float* normals, const int
   ISHAP_REQUIRE(((unsigned long long)scratch & 3ull) == 0, "cloud_orient: scratch must be 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int n = (int)npoints;
-  int* level = (int*)scratch;
-  OrientState* st = (OrientState*)((char*)scratch + orient_level_bytes(npoints));
+  const OrientScratch S = orient_scratch(scratch, npoints);
+  int* level = S.level; OrientState* st = S.st;
   ISHAP_CHECK_HIP(hipMemsetAsync(level, 0, (size_t)npoints * sizeof(int), s));
   hipLaunchKernelGGL(orient_init_kernel, dim3(1), dim3(1), 0, s, st, n);
   const dim3 grid((unsigned)((npoints + NR_THREADS - 1) / NR_THREADS));

@@ -221,18 +221,22 @@ __global__ void parts_emit_kernel(const u64* __restrict__ slots, const int* __re
   d2[r] = d;
 }
 
-struct HandlesLayout { long long runs, off, totals, box, slots, cand, mind, bytes; };
-HandlesLayout handles_layout(int D, int n) {
+// box and slots, clear_bytes from box on, are cleared at the start of a call
+struct HandlesLayout { unsigned *off, *totals, *cand, *mind; int* box; u64* slots; long long runs, clear_bytes, bytes; };
+HandlesLayout handles_layout(void* base, int D, int n) {
+  Carve c{(char*)base};
   HandlesLayout L;
   const long long N = (long long)D * D * D;
   L.runs = 4 * ((N + PT - 1) / PT);
-  L.off = 0;
-  L.totals = (long long)align_up((size_t)(L.off + 4 * L.runs), 256);
-  L.box = (long long)align_up((size_t)(L.totals + 4 * (scan_u32_blocks(L.runs) + 1)), 256);
-  L.slots = L.box + 256;
-  L.cand = (long long)align_up((size_t)(L.slots + 8ll * n), 256);
-  L.mind = (long long)align_up((size_t)(L.cand + 4 * N), 256);           // M is known to the device only: room for every voxel
-  L.bytes = (long long)align_up((size_t)(L.mind + 4 * N), 256);
+  L.off = c.take<unsigned>(L.runs);
+  L.totals = c.take<unsigned>(scan_u32_blocks(L.runs) + 1);
+  const long long box_at = c.total();
+  L.box = (int*)c.bytes(256);
+  L.slots = c.take<u64>(n);
+  L.clear_bytes = c.total() - box_at;
+  L.cand = c.take<unsigned>(N);
+  L.mind = c.take<unsigned>(N);            // M is known to the device only: room for every voxel
+  L.bytes = c.total();
   return L;
 }
 }  // namespace
@@ -255,7 +259,7 @@ extern "C" int ishap_region_select(const float* volume, int D, float level, cons
 
 extern "C" long long ishap_region_handles_scratch_bytes(int D, int n) {
   if (D < 2 || D > PARTS_MAX_D || n < 1 || n > PARTS_MAX_HANDLES) return -1;
-  return handles_layout(D, n).bytes;
+  return handles_layout(nullptr, D, n).bytes;
 }
 
 extern "C" int ishap_region_handles(const unsigned char* mask, int D, int n, const int* start, int* picks_out, unsigned* dist2_out,
@@ -266,19 +270,16 @@ extern "C" int ishap_region_handles(const unsigned char* mask, int D, int n, con
   if (start)
     ISHAP_REQUIRE(start[0] >= 0 && start[0] < D && start[1] >= 0 && start[1] < D && start[2] >= 0 && start[2] < D,
                   "region handles: the start voxel lies outside the grid");
-  const HandlesLayout L = handles_layout(D, n);
+  const HandlesLayout L = handles_layout(scratch, D, n);
   ISHAP_REQUIRE(scratch_bytes >= L.bytes, "region handles: scratch smaller than ishap_region_handles_scratch_bytes(D, n)");
   ISHAP_REQUIRE(((unsigned long long)scratch & 15ull) == 0, "region handles: scratch must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  unsigned *off = (unsigned*)(base + L.off), *totals = (unsigned*)(base + L.totals);
-  int* box = (int*)(base + L.box);
-  u64* slots = (u64*)(base + L.slots);
-  unsigned *cand = (unsigned*)(base + L.cand), *mind = (unsigned*)(base + L.mind);
+  unsigned *off = L.off, *totals = L.totals, *cand = L.cand, *mind = L.mind;
+  int* box = L.box; u64* slots = L.slots;
   const long long N = (long long)D * D * D;
   const unsigned vb = (unsigned)((N + PT - 1) / PT);
   const unsigned gb = (unsigned)std::min<long long>(1024, std::max<long long>(1, (N + 4 * PT - 1) / (4 * PT)));   // the rounds' fixed grid
-  ISHAP_CHECK_HIP(hipMemsetAsync(base + L.box, 0, (size_t)(L.cand - L.box), s));                                   // box and slots
+  ISHAP_CHECK_HIP(hipMemsetAsync(box, 0, (size_t)L.clear_bytes, s));
   hipLaunchKernelGGL(parts_count_kernel, dim3(vb), dim3(PT), 0, s, mask, N, off);
   scan_exclusive_u32(off, L.runs, totals, (unsigned*)M_out, s);              // M <= N <= 2^30: an int holds it
   hipLaunchKernelGGL(parts_compact_kernel, dim3(vb), dim3(PT), 0, s, mask, D, N, (const unsigned*)off, cand, mind);

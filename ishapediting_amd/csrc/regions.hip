@@ -106,7 +106,9 @@ __global__ __launch_bounds__(256) void region_compose_kernel(const unsigned char
 
 long long region_scratch_bytes(int W) {
   if (W < 2) return -1;
-  return (long long)align_up((size_t)3 * W * W, 256);          // the marks; the tail keeps the last 32-bit atomicOr inside
+  Carve c{nullptr};
+  c.take<unsigned char>((size_t)3 * W * W);                    // the marks; the tail keeps the last 32-bit atomicOr inside
+  return c.total();
 }
 
 int region_plane_weights_launch(const RegionPrim* prims, int n_prims, const unsigned char* keep_vox, const unsigned char* free_vox,
@@ -208,34 +210,29 @@ int region_plane_marks_launch(const RegionPrim* prims, int n_prims, const unsign
 
 // scratch: raw marks | dilated marks | dk int[3 W W] | df int[3 W W] | the transform's own scratch
 namespace {
-struct FeatherLayout { long long marks, dk, df, edt, bytes; };
-FeatherLayout feather_layout(int W) {
-  FeatherLayout L;
+struct FeatherLayout { void* raw; unsigned char* marks; int *dk, *df; void* edt; long long bytes; };
+FeatherLayout feather_layout(void* base, int W) {
+  Carve c{(char*)base};
   const long long ntex = 3ll * W * W;
-  L.marks = region_scratch_bytes(W);
-  L.dk = L.marks + (long long)align_up((size_t)ntex, 256);
-  L.df = L.dk + (long long)align_up((size_t)(4 * ntex), 256);
-  L.edt = L.df + (long long)align_up((size_t)(4 * ntex), 256);
-  L.bytes = L.edt + edt_scratch_bytes(3, W, W, 6);
-  return L;
+  return {c.bytes(region_scratch_bytes(W)), c.take<unsigned char>(ntex), c.take<int>(ntex), c.take<int>(ntex),
+          c.bytes(edt_scratch_bytes(3, W, W, 6)), c.total()};
 }
 }  // namespace
 
 long long region_feather_scratch_bytes(int W) {
   if (W < 2 || W > EDT_MAX_AXIS) return -1;
-  return feather_layout(W).bytes;
+  return feather_layout(nullptr, W).bytes;
 }
 
 int region_plane_feather_launch(const RegionPrim* prims, int n_prims, const unsigned char* keep_vox, const unsigned char* free_vox, int D,
                                 int W, int dilate, float keep_weight, float free_weight, const double* table, int table_len,
                                 float* weights_out, int* counts, void* scratch, hipStream_t s) {
-  const FeatherLayout L = feather_layout(W);
-  char* base = (char*)scratch;
-  unsigned char* marks = (unsigned char*)(base + L.marks);
-  int *dk = (int*)(base + L.dk), *df = (int*)(base + L.df);
-  ISHAP_TRY(region_plane_marks_launch(prims, n_prims, keep_vox, free_vox, D, W, dilate, marks, counts, scratch, s));
-  ISHAP_TRY(edt_launch(marks, 1u, 3, W, W, 6, 0, dk, base + L.edt, s));
-  ISHAP_TRY(edt_launch(marks, 2u, 3, W, W, 6, 0, df, base + L.edt, s));
+  const FeatherLayout L = feather_layout(scratch, W);
+  unsigned char* marks = L.marks;
+  int *dk = L.dk, *df = L.df;
+  ISHAP_TRY(region_plane_marks_launch(prims, n_prims, keep_vox, free_vox, D, W, dilate, marks, counts, L.raw, s));
+  ISHAP_TRY(edt_launch(marks, 1u, 3, W, W, 6, 0, dk, L.edt, s));
+  ISHAP_TRY(edt_launch(marks, 2u, 3, W, W, 6, 0, df, L.edt, s));
   const int ntex = 3 * W * W;
   hipLaunchKernelGGL(region_feather_kernel, dim3(ceil_div(ntex, 256)), dim3(256), 0, s, (const int*)dk, (const int*)df, table, table_len,
                      ntex, keep_weight, free_weight, weights_out);

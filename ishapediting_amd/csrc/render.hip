@@ -281,7 +281,13 @@ __global__ __launch_bounds__(256) void render_unproject_kernel(RenderCam cam, co
     world[3 * i + k] = (float)(cam.eye[k] + xv * cam.right[k] + yv * cam.upv[k] + zv * cam.fwd[k]);
 }
 
-inline long long up16(long long v) { return (v + 15) & ~15ll; }
+// scratch layout: visibility keys u64[width height] | VRec[nverts] | LargeRec[ntris] | the list counter (16 bytes), each on a 16-byte boundary
+struct RenderScratch { unsigned long long* vis; VRec* vr; LargeRec* list; unsigned* counter; long long bytes; };
+RenderScratch render_scratch(void* base, long long nverts, long long ntris, int width, int height) {
+  Carve c{(char*)base};
+  return {c.take<unsigned long long>((long long)width * height, 16), c.take<VRec>(nverts, 16), c.take<LargeRec>(ntris, 16),
+          c.take<unsigned>(4, 16), c.total(16)};
+}
 
 }  // namespace
 
@@ -289,7 +295,7 @@ long long render_scratch_bytes(long long nverts, long long ntris, int width, int
   if (nverts < 0 || ntris < 0 || nverts >= (1ll << 31) || ntris >= (1ll << 31) || width < 1 || height < 1 ||
       width > RENDER_MAX_SIDE || height > RENDER_MAX_SIDE)
     return -1;
-  return up16((long long)width * height * 8) + nverts * (long long)sizeof(VRec) + ntris * (long long)sizeof(LargeRec) + 16;
+  return render_scratch(nullptr, nverts, ntris, width, height).bytes;
 }
 
 int render_camera(const float* eye, const float* centre, const float* up, float fov_y_deg, float near, float far, int width,
@@ -316,11 +322,9 @@ int render_camera(const float* eye, const float* centre, const float* up, float 
 
 int render_mesh_launch(const RenderArgs& a, hipStream_t s) {
   const long long npix = (long long)a.width * a.height;
-  char* base = (char*)a.scratch;
-  unsigned long long* vis = (unsigned long long*)base;
-  VRec* vr = (VRec*)(base + up16(npix * 8));
-  LargeRec* list = (LargeRec*)((char*)vr + a.nverts * (long long)sizeof(VRec));
-  unsigned* counter = (unsigned*)((char*)list + a.ntris * (long long)sizeof(LargeRec));
+  const RenderScratch S = render_scratch(a.scratch, a.nverts, a.ntris, a.width, a.height);
+  unsigned long long* vis = S.vis;
+  VRec* vr = S.vr; LargeRec* list = S.list; unsigned* counter = S.counter;
   const unsigned pb = (unsigned)((npix + 255) / 256);
   DepthConst dc;
   dc.kf = (float)(a.cam.far / (a.cam.far - a.cam.near)); dc.near = (float)a.cam.near;

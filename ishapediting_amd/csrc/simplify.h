@@ -23,14 +23,18 @@ struct SimplifyGrid {
   int g[3];
 };
 
-// device scratch of one count / emit pair, byte offsets (each 256-byte aligned)
+// device scratch of one count / emit pair (each buffer 256-byte aligned; the header is at offset 0)
 struct SimplifyLayout {
   long long words;      // 32-bit words of the cell bitmap
   long long cmax;       // most clusters there can be: min(nverts, cells)
   long long table;      // slots of the triangle table: a power of two >= max(2 ntris, 64)
-  long long hdr, bitmap, prefix, vcluster, rows, ref, tab, flag, totals, bytes;
+  int *hdr, *vcluster;  // hdr: int[0] clusters, int[1] non-degenerate triangles, int[64..127] partial counts
+  unsigned *bitmap, *prefix, *ref, *tab, *flag, *totals;
+  unsigned long long* rows;
+  long long bytes;
 };
-inline SimplifyLayout simplify_layout(long long nverts, long long ntris, long long cells) {
+inline SimplifyLayout simplify_layout(void* base, long long nverts, long long ntris, long long cells) {
+  Carve c{(char*)base};
   SimplifyLayout L;
   L.words = (cells + 31) / 32;
   L.cmax = nverts < cells ? nverts : cells;
@@ -38,15 +42,15 @@ inline SimplifyLayout simplify_layout(long long nverts, long long ntris, long lo
   while (L.table < 2 * ntris) L.table <<= 1;
   long long longest = L.words > L.cmax + 1 ? L.words : L.cmax + 1;
   if (ntris + 1 > longest) longest = ntris + 1;
-  L.hdr = 0;                                                      // int[0] clusters, int[1] non-degenerate triangles, int[64..127] partial counts
-  L.bitmap = SIMPLIFY_HDR_BYTES;
-  L.prefix = (long long)align_up(L.bitmap + 4 * L.words, 256);
-  L.vcluster = (long long)align_up(L.prefix + 4 * L.words, 256);
-  L.rows = (long long)align_up(L.vcluster + 4 * nverts, 256);
-  L.ref = (long long)align_up(L.rows + 8 * SIMPLIFY_ROW * L.cmax, 256);
-  L.tab = (long long)align_up(L.ref + 4 * (L.cmax + 1), 256);
-  L.flag = (long long)align_up(L.tab + 4 * L.table, 256);
-  L.totals = (long long)align_up(L.flag + 4 * (ntris + 1), 256);
-  L.bytes = (long long)align_up(L.totals + 4 * (scan_u32_blocks(longest) + 1), 256);
+  L.hdr = c.take<int>(SIMPLIFY_HDR_BYTES / sizeof(int));
+  L.bitmap = c.take<unsigned>(L.words);
+  L.prefix = c.take<unsigned>(L.words);
+  L.vcluster = c.take<int>(nverts);
+  L.rows = c.take<unsigned long long>(SIMPLIFY_ROW * L.cmax);
+  L.ref = c.take<unsigned>(L.cmax + 1);
+  L.tab = c.take<unsigned>(L.table);
+  L.flag = c.take<unsigned>(ntris + 1);
+  L.totals = c.take<unsigned>(scan_u32_blocks(longest) + 1);
+  L.bytes = c.total();
   return L;
 }

@@ -377,7 +377,7 @@ bool dims_ok(const int* dims, long long& cells) {
 }
 
 int fill(Args& a, const float* verts, long long nverts, const int* tris, long long ntris, const double* lo, double h, const int* dims,
-         int contraction, const void* scratch, long long scratch_bytes) {
+         int contraction, void* scratch, long long scratch_bytes) {
   ISHAP_REQUIRE(lo && dims, "mesh simplify: null argument (lo, dims)");
   ISHAP_REQUIRE(nverts >= 0 && nverts <= 0x7fffffffll, "mesh simplify: 0 <= nverts <= 2^31 - 1 (vertex indices are int32)");
   ISHAP_REQUIRE(ntris >= 0 && ntris <= 0x7fffffffll / 3, "mesh simplify: 0 <= 3 ntris <= 2^31 - 1");
@@ -388,7 +388,7 @@ int fill(Args& a, const float* verts, long long nverts, const int* tris, long lo
   ISHAP_REQUIRE(contraction == SIMPLIFY_QUADRIC || contraction == SIMPLIFY_AVERAGE, "mesh simplify: unknown contraction (0 quadric, 1 average)");
   ISHAP_REQUIRE((verts || nverts == 0) && (tris || ntris == 0), "mesh simplify: null argument (verts, tris)");
   ISHAP_REQUIRE(scratch, "mesh simplify: null scratch");
-  a.L = simplify_layout(nverts, ntris, a.cells);
+  a.L = simplify_layout(scratch, nverts, ntris, a.cells);
   ISHAP_REQUIRE(scratch_bytes >= a.L.bytes, "mesh simplify: scratch smaller than ishap_mesh_simplify_scratch_bytes(nverts, ntris, dims)");
   ISHAP_REQUIRE(((uintptr_t)scratch & 15) == 0, "mesh simplify: scratch must be 16-byte aligned");
   for (int k = 0; k < 3; ++k) { a.G.lo[k] = lo[k]; a.G.g[k] = dims[k]; }
@@ -401,7 +401,7 @@ int fill(Args& a, const float* verts, long long nverts, const int* tris, long lo
 extern "C" long long ishap_mesh_simplify_scratch_bytes(long long nverts, long long ntris, const int* dims) {
   long long cells;
   if (nverts < 0 || nverts > 0x7fffffffll || ntris < 0 || ntris > 0x7fffffffll / 3 || !dims_ok(dims, cells)) return -1;
-  return simplify_layout(nverts, ntris, cells).bytes;
+  return simplify_layout(nullptr, nverts, ntris, cells).bytes;
 }
 
 extern "C" int ishap_mesh_simplify_count(const float* verts, long long nverts, const int* tris, long long ntris, const double* lo, double h,
@@ -412,19 +412,12 @@ extern "C" int ishap_mesh_simplify_count(const float* verts, long long nverts, c
   ISHAP_REQUIRE(counts, "mesh simplify: null argument (counts)");
   const SimplifyLayout& L = a.L;
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  int* hdr = (int*)(base + L.hdr);
+  int* hdr = L.hdr;
   ISHAP_CHECK_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int), s));
   ISHAP_CHECK_HIP(hipMemsetAsync(hdr, 0, SIMPLIFY_HDR_BYTES, s));
   if (nverts == 0 || ntris == 0) return 0;                 // an empty mesh: nothing is launched
-  unsigned* bitmap = (unsigned*)(base + L.bitmap);
-  unsigned* prefix = (unsigned*)(base + L.prefix);
-  int* vcluster = (int*)(base + L.vcluster);
-  u64* rows = (u64*)(base + L.rows);
-  unsigned* ref = (unsigned*)(base + L.ref);
-  unsigned* table = (unsigned*)(base + L.tab);
-  unsigned* flag = (unsigned*)(base + L.flag);
-  unsigned* totals = (unsigned*)(base + L.totals);
+  unsigned *bitmap = L.bitmap, *prefix = L.prefix, *ref = L.ref, *table = L.tab, *flag = L.flag, *totals = L.totals;
+  int* vcluster = L.vcluster; u64* rows = L.rows;
   ISHAP_CHECK_HIP(hipMemsetAsync(bitmap, 0, 4 * L.words, s));
   ISHAP_CHECK_HIP(hipMemsetAsync(ref, 0, 4 * (L.cmax + 1), s));
   ISHAP_CHECK_HIP(hipMemsetAsync(table, 0xff, 4 * L.table, s));
@@ -475,11 +468,8 @@ extern "C" int ishap_mesh_simplify_emit(const float* verts, long long nverts, co
   }
   ISHAP_REQUIRE(out_verts && out_tris, "mesh simplify: null argument (out_verts, out_tris)");
   const SimplifyLayout& L = a.L;
-  char* base = (char*)scratch;
-  const int* vcluster = (const int*)(base + L.vcluster);
-  const u64* rows = (const u64*)(base + L.rows);
-  const unsigned* ref = (const unsigned*)(base + L.ref);
-  const unsigned* flag = (const unsigned*)(base + L.flag);
+  const int* vcluster = L.vcluster; const u64* rows = L.rows;
+  const unsigned *ref = L.ref, *flag = L.flag;
   hipLaunchKernelGGL(simplify_emit_vertices_kernel, dim3(blocks_of(L.cmax)), dim3(SM_THREADS), 0, s, verts, a.G, rows, ref, L.cmax,
                      contraction == SIMPLIFY_AVERAGE ? 1 : 0, regularization, out_verts);
   hipLaunchKernelGGL(simplify_emit_triangles_kernel, dim3(blocks_of(ntris)), dim3(SM_THREADS), 0, s, tris, ntris, nverts, vcluster, flag, ref,

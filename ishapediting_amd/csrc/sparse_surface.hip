@@ -327,16 +327,18 @@ __global__ void sparse_scatter_kernel(const unsigned char* __restrict__ map, int
 bool sizes_ok(int R) { return R >= 9 && R <= 2048; }
 int bricks_per_axis(int R) { return (R - 1 + 7) / 8; }
 
-struct EmitLayout { long long info, cntv, cntt, vbase, totals, bytes; };
-EmitLayout emit_layout(long long n) {
-  EmitLayout L;
-  L.info = 0;
-  L.cntv = align_up(L.info + 2 * INFO_STRIDE * n, 256);
-  L.cntt = align_up(L.cntv + 4 * n, 256);
-  L.vbase = align_up(L.cntt + 4 * n, 256);
-  L.totals = align_up(L.vbase + 4 * n, 256);
-  L.bytes = align_up(L.totals + 4 * (scan_u32_blocks(n > 0 ? n : 1) + 1), 256);
-  return L;
+struct EmitLayout { unsigned short* info; unsigned *cntv, *cntt, *vbase, *totals; long long bytes; };
+EmitLayout emit_layout(void* base, long long n) {
+  Carve c{(char*)base};
+  return {c.take<unsigned short>(INFO_STRIDE * n), c.take<unsigned>(n), c.take<unsigned>(n), c.take<unsigned>(n),
+          c.take<unsigned>(scan_u32_blocks(n > 0 ? n : 1) + 1), c.total()};
+}
+// flag[n] | block totals of its scan, n = bricks_per_axis(R)^3
+struct CompactLayout { long long n; unsigned *flag, *totals; long long bytes; };
+CompactLayout compact_layout(void* base, int R) {
+  Carve c{(char*)base};
+  const long long nb = bricks_per_axis(R), n = nb * nb * nb;
+  return {n, c.take<unsigned>(n), c.take<unsigned>(scan_u32_blocks(n) + 1), c.total()};
 }
 
 int fill(SparseArgs& a, const float* values, const int* list, long long n, int R, float level, const int* slot, unsigned* reach) {
@@ -347,14 +349,13 @@ int fill(SparseArgs& a, const float* values, const int* list, long long n, int R
   a.info = nullptr; a.cntv = a.cntt = a.vbase = nullptr;
   return 0;
 }
-int fill_emit(SparseArgs& a, void* scratch, long long scratch_bytes, long long n) {
-  const EmitLayout L = emit_layout(n);
+int fill_emit(SparseArgs& a, void* scratch, long long scratch_bytes, long long n, unsigned** totals = nullptr) {
+  const EmitLayout L = emit_layout(scratch, n);
   ISHAP_REQUIRE(scratch, "sparse surface: null scratch");
   ISHAP_REQUIRE(scratch_bytes >= L.bytes, "sparse surface: scratch smaller than ishap_sparse_surface_scratch_bytes(R, bricks)");
   ISHAP_REQUIRE(((uintptr_t)scratch & 15) == 0, "sparse surface: scratch must be 16-byte aligned");
-  char* s = (char*)scratch;
-  a.info = (unsigned short*)(s + L.info); a.cntv = (unsigned*)(s + L.cntv); a.cntt = (unsigned*)(s + L.cntt);
-  a.vbase = (unsigned*)(s + L.vbase);
+  a.info = L.info; a.cntv = L.cntv; a.cntt = L.cntt; a.vbase = L.vbase;
+  if (totals) *totals = L.totals;
   return 0;
 }
 
@@ -383,8 +384,7 @@ extern "C" int ishap_sparse_seed_volume(const float* coarse, int Rc, float level
 
 extern "C" long long ishap_sparse_compact_scratch_bytes(int R) {
   if (!sizes_ok(R)) return -1;
-  const long long nb = bricks_per_axis(R), n = nb * nb * nb;
-  return (long long)align_up(4 * n, 256) + (long long)align_up(4 * (scan_u32_blocks(n) + 1), 256);
+  return compact_layout(nullptr, R).bytes;
 }
 
 extern "C" int ishap_sparse_compact(const unsigned char* map, int R, int mode, int first_slot, int* slot_map, int* list,
@@ -394,9 +394,9 @@ extern "C" int ishap_sparse_compact(const unsigned char* map, int R, int mode, i
   ISHAP_REQUIRE(mode >= 0 && mode <= 2 && first_slot >= 0 && list_capacity >= 0, "sparse compact: mode 0..2, first_slot >= 0, capacity >= 0");
   ISHAP_REQUIRE(scratch_bytes >= ishap_sparse_compact_scratch_bytes(R), "sparse compact: scratch smaller than ishap_sparse_compact_scratch_bytes(R)");
   ISHAP_REQUIRE(((uintptr_t)scratch & 15) == 0, "sparse compact: scratch must be 16-byte aligned");
-  const long long nb = bricks_per_axis(R), n = nb * nb * nb;
-  unsigned* flag = (unsigned*)scratch;
-  unsigned* totals = (unsigned*)((char*)scratch + align_up(4 * n, 256));
+  const CompactLayout L = compact_layout(scratch, R);
+  const long long n = L.n;
+  unsigned *flag = L.flag, *totals = L.totals;
   hipStream_t s = (hipStream_t)stream;
   const unsigned blocks = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(sparse_flag_kernel, dim3(blocks), dim3(256), 0, s, map, (const int*)slot_map, n, mode, flag);
@@ -420,7 +420,7 @@ extern "C" int ishap_sparse_grow(const float* values, const int* list, long long
 
 extern "C" long long ishap_sparse_surface_scratch_bytes(int R, long long nbricks) {
   if (!sizes_ok(R) || nbricks < 0 || nbricks > (1ll << 21)) return -1;
-  return emit_layout(nbricks).bytes;
+  return emit_layout(nullptr, nbricks).bytes;
 }
 extern "C" long long ishap_sparse_reach_bytes(long long nbricks) { return nbricks < 0 ? -1 : nbricks * REACH_WORDS * 4; }
 
@@ -430,9 +430,9 @@ extern "C" int ishap_sparse_surface_count(const float* values, const int* ordere
   SparseArgs a;
   ISHAP_TRY(fill(a, values, ordered, nbricks, R, level, slot_map, reach));
   ISHAP_REQUIRE(counts, "sparse surface: null argument");
-  ISHAP_TRY(fill_emit(a, scratch, scratch_bytes, nbricks));
+  unsigned* totals;
+  ISHAP_TRY(fill_emit(a, scratch, scratch_bytes, nbricks, &totals));
   hipStream_t s = (hipStream_t)stream;
-  unsigned* totals = (unsigned*)((char*)scratch + emit_layout(nbricks).totals);
   hipLaunchKernelGGL(sparse_count_kernel, dim3((unsigned)nbricks), dim3(SS_THREADS), 0, s, a);
   scan_exclusive_u32(a.cntv, nbricks, totals, counts, s);
   scan_exclusive_u32(a.cntt, nbricks, totals, counts + 1, s);

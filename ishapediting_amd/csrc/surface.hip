@@ -614,26 +614,29 @@ __global__ void group_mean_kernel(int G, float* __restrict__ out) {
   out[2 * G + 1] = (float)(s1 / G);
 }
 
+// the scratch, packed: voff[n] | bsum[2 nblocks] | emask[n] | tcnt[n] | 256 bytes of slack.  Sets a's sizes and pointers, returns the bytes
+long long surf_carve(SurfArgs& a, void* base, int res) {
+  a.n = (long long)res * res * res;
+  const long long nb = (a.n + SB_TILE - 1) / SB_TILE;
+  a.nblocks = (int)nb;
+  Carve c{(char*)base};
+  a.voff = c.take<unsigned>(a.n, 1);
+  a.bsum = c.take<unsigned>(2 * nb, 1);
+  a.emask = c.take<unsigned char>(a.n, 1);
+  a.tcnt = c.take<unsigned char>(a.n, 1);
+  c.bytes(256, 1);
+  return c.total(1);
+}
 int fill(SurfArgs& a, const float* volume, int res, float level, void* scratch) {
   ISHAP_REQUIRE(volume && scratch && res >= 2 && res <= 1024, "surface: volume, scratch and 2 <= res <= 1024");
-  a.vol = volume; a.res = res; a.level = level; a.n = (long long)res * res * res;
-  a.nblocks = (int)((a.n + SB_TILE - 1) / SB_TILE);
-  char* s = (char*)scratch;
-  a.voff = (unsigned*)s;               s += a.n * sizeof(unsigned);
-  a.bsum = (unsigned*)s;               s += 2LL * a.nblocks * sizeof(unsigned);
-  a.emask = (unsigned char*)s;         s += a.n;
-  a.tcnt = (unsigned char*)s;
-  a.method = 0;
+  a.vol = volume; a.res = res; a.level = level; a.method = 0;
+  surf_carve(a, scratch, res);
   return 0;
 }
 
 }  // namespace
 
-extern "C" long long ishap_surface_scratch_bytes(int res) {
-  const long long n = (long long)res * res * res;
-  const long long nb = (n + SB_TILE - 1) / SB_TILE;
-  return n * 6 + 2 * nb * 4 + 256;
-}
+extern "C" long long ishap_surface_scratch_bytes(int res) { SurfArgs a; return surf_carve(a, nullptr, res); }
 
 extern "C" int ishap_surface_count(const float* volume, int res, float level, int method, void* scratch, unsigned* counts,
                                    void* stream) {
@@ -664,24 +667,26 @@ extern "C" int ishap_surface_emit(const float* volume, int res, float level, int
 
 // scratch layout: off[nverts + 1] | cursor[nverts] | block totals | boundary mask[nverts] | second vertex buffer | adj[6 ntris]
 namespace {
-struct SmoothLayout { long long off, cursor, totals, bmask, vtmp, adj, bytes, nblocks; };
-SmoothLayout smooth_layout(long long nverts, long long ntris) {
+struct SmoothLayout { unsigned *off, *cursor, *totals, *bmask, *adj; float* vtmp; long long zero_end, bytes, nblocks; };
+SmoothLayout smooth_layout(void* base, long long nverts, long long ntris) {
+  Carve c{(char*)base};
   SmoothLayout L;
   L.nblocks = scan_u32_blocks(nverts + 1);
-  L.off = 0;
-  L.cursor = align_up(L.off + 4 * (nverts + 1), 256);
-  L.totals = align_up(L.cursor + 4 * nverts, 256);
-  L.bmask = align_up(L.totals + 4 * (L.nblocks + 1), 256);
-  L.vtmp = align_up(L.bmask + 4 * nverts, 256);
-  L.adj = align_up(L.vtmp + 12 * nverts, 256);
-  L.bytes = align_up(L.adj + 24 * ntris, 256);
+  L.off = c.take<unsigned>(nverts + 1);
+  L.cursor = c.take<unsigned>(nverts);
+  L.zero_end = c.total();                    // [0, zero_end): list lengths and fill cursors, cleared at the start of a call
+  L.totals = c.take<unsigned>(L.nblocks + 1);
+  L.bmask = c.take<unsigned>(nverts);
+  L.vtmp = c.take<float>(3 * nverts);
+  L.adj = c.take<unsigned>(6 * ntris);
+  L.bytes = c.total();
   return L;
 }
 }  // namespace
 
 extern "C" long long ishap_mesh_smooth_scratch_bytes(long long nverts, long long ntris) {
   if (nverts < 0 || ntris < 0) return -1;
-  return smooth_layout(nverts, ntris).bytes;
+  return smooth_layout(nullptr, nverts, ntris).bytes;
 }
 
 extern "C" int ishap_mesh_smooth(float* verts, long long nverts, const int* tris, long long ntris, int iterations, float box_max,
@@ -691,16 +696,11 @@ extern "C" int ishap_mesh_smooth(float* verts, long long nverts, const int* tris
   ISHAP_REQUIRE(nverts < (1ll << 31) && 6 * ntris < (1ll << 32), "mesh_smooth: 32-bit vertex indices and list offsets");
   if (nverts == 0 || ntris == 0 || iterations == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const SmoothLayout L = smooth_layout(nverts, ntris);
-  char* base = (char*)scratch;
-  unsigned* off = (unsigned*)(base + L.off);
-  unsigned* cursor = (unsigned*)(base + L.cursor);
-  unsigned* totals = (unsigned*)(base + L.totals);
-  unsigned* bmask = box_max > 0.f ? (unsigned*)(base + L.bmask) : nullptr;
-  float* vtmp = (float*)(base + L.vtmp);
-  unsigned* adj = (unsigned*)(base + L.adj);
+  const SmoothLayout L = smooth_layout(scratch, nverts, ntris);
+  unsigned *off = L.off, *cursor = L.cursor, *totals = L.totals, *adj = L.adj, *bmask = box_max > 0.f ? L.bmask : nullptr;
+  float* vtmp = L.vtmp;
   const unsigned tb = (unsigned)((ntris + 255) / 256), vb = (unsigned)((nverts + 255) / 256);
-  ISHAP_CHECK_HIP(hipMemsetAsync(base, 0, (size_t)L.totals, s));              // list lengths and fill cursors
+  ISHAP_CHECK_HIP(hipMemsetAsync(scratch, 0, (size_t)L.zero_end, s));         // list lengths and fill cursors
   if (bmask) hipLaunchKernelGGL(smooth_boundary_mask_kernel, dim3(vb), dim3(256), 0, s, verts, nverts, box_max, bmask);
   count_triangle_corners(tris, ntris, 2u, off, s);                           // every face lists two heads under each of its corners
   scan_exclusive_u32(off, nverts + 1, totals, totals + L.nblocks, s);        // list lengths -> list starts, off[nverts] = their sum
@@ -750,18 +750,25 @@ extern "C" int ishap_mesh_occupancy(const float* verts, const int* tris, long lo
   return 0;
 }
 
+// scratch layout: the tile boxes; sdf == 2 / -2 adds the winding number's part sums behind them (256-byte aligned)
+namespace {
+struct DistScratch { float4* box; char* wn; long long bytes; };
+DistScratch dist_scratch(void* base, long long ntris, long long npts, bool winding) {
+  Carve c{(char*)base};
+  return {c.take<float4>((ntris + MD_TILE - 1) / MD_TILE * 2), winding ? c.bytes(ishap_winding_bytes(ntris, npts)) : nullptr,
+          c.total(1)};
+}
+}  // namespace
+
 extern "C" long long ishap_mesh_distance_scratch_bytes(long long ntris) {
   if (ntris < 0) return -1;
-  return (ntris + MD_TILE - 1) / MD_TILE * 2 * (long long)sizeof(float4);
+  return dist_scratch(nullptr, ntris, 0, false).bytes;
 }
 
-// sdf == 2 / -2 adds the winding number's part sums behind the tile boxes (256-byte aligned); every other value is what
-// ishap_mesh_distance makes of it: unsigned (0) or signed by parity
+// every sdf other than 2 / -2 is what ishap_mesh_distance makes of it: unsigned (0) or signed by parity
 extern "C" long long ishap_mesh_distance_scratch_bytes_sdf(long long ntris, long long npts, int sdf) {
   if (ntris < 0 || npts < 0) return -1;
-  const long long boxes = ishap_mesh_distance_scratch_bytes(ntris);
-  if (sdf != 2 && sdf != -2) return boxes;
-  return align_up(boxes, 256) + ishap_winding_bytes(ntris, npts);
+  return dist_scratch(nullptr, ntris, npts, sdf == 2 || sdf == -2).bytes;
 }
 
 extern "C" int ishap_mesh_distance(const float* verts, const int* tris, long long ntris, const float* pts, long long npts, int sdf,
@@ -775,18 +782,17 @@ extern "C" int ishap_mesh_distance(const float* verts, const int* tris, long lon
                 "mesh_distance: sdf == 2 / -2 needs ishap_mesh_distance_scratch_bytes_sdf(ntris, npts, 2) bytes of scratch");
   hipStream_t s = (hipStream_t)stream;
   const unsigned tiles = (unsigned)((ntris + MD_TILE - 1) / MD_TILE), blocks = (unsigned)((npts + MD_TILE - 1) / MD_TILE);
-  float4* box = (float4*)scratch;
+  const DistScratch S = dist_scratch(scratch, ntris, npts, winding);
   // the sign is an inside flag per point: its 0/1 value lands in dist and the distance kernel reads it back per point.
   // sdf == 2: inside where the winding number exceeds 0.5 (-2: is below -0.5, a clockwise mesh); any other non-zero sdf:
   // ishap_mesh_occupancy's ray parity
   if (winding) {
-    char* wn = (char*)scratch + align_up(ishap_mesh_distance_scratch_bytes(ntris), 256);
-    ishap_winding_launch_mesh(verts, tris, ntris, pts, npts, dist, sdf > 0 ? 1 : -1, wn, s);
+    ishap_winding_launch_mesh(verts, tris, ntris, pts, npts, dist, sdf > 0 ? 1 : -1, S.wn, s);
   } else if (sdf) {
     hipLaunchKernelGGL(occupancy_kernel, dim3(blocks), dim3(256), 0, s, verts, tris, ntris, pts, npts, dist);
   }
-  hipLaunchKernelGGL(mesh_tile_box_kernel, dim3(tiles), dim3(MD_TILE), 0, s, verts, tris, ntris, box);
-  hipLaunchKernelGGL(mesh_distance_kernel, dim3(blocks), dim3(MD_TILE), 0, s, verts, tris, ntris, (const float4*)box, pts, npts,
+  hipLaunchKernelGGL(mesh_tile_box_kernel, dim3(tiles), dim3(MD_TILE), 0, s, verts, tris, ntris, S.box);
+  hipLaunchKernelGGL(mesh_distance_kernel, dim3(blocks), dim3(MD_TILE), 0, s, verts, tris, ntris, (const float4*)S.box, pts, npts,
                      sdf ? (const float*)dist : nullptr, dist, tri);
   ISHAP_CHECK_HIP(hipGetLastError());
   return 0;
