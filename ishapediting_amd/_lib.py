@@ -274,6 +274,8 @@ SYMBOLS = {
                                            c_void_p, c_void_p]),
 }
 
+ABI = 26          # the ishap_version() this module's SYMBOLS and structures describe
+
 _lib = None
 
 
@@ -297,23 +299,9 @@ def lib():
             fn = getattr(l, name)     # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
-        # 3: ishap_step_coefs ends with the rng fields this module's StepCoefs declares; 4: ishap_drag_batch_*; 5: ishap_igemm_run;
-        # 6: ishap_triplane_fit_loss_grad / ishap_triplane_reg_*; 7: ishap_mesh_distance / ishap_hausdorff / ishap_group_field_stats;
-        # 8: ishap_arap / ishap_nearest_vertices; 9: ishap_attention_run / ishap_attention8_run; 10: ishap_group_norm32_plan;
-        # 11: ishap_render_mesh / ishap_render_scratch_bytes / ishap_unproject; 12: ishap_mesh_winding / ishap_cloud_winding /
-        # ishap_cloud_areas / ishap_winding_scratch_bytes and sdf == 2 / -2 of ishap_mesh_distance; 13: ishap_group_norm32_run;
-        # 14: ishap_cloud_knn / ishap_cloud_normals / ishap_cloud_orient / ishap_cloud_orient_scratch_bytes;
-        # 15: ishap_unet_snapshot_*; 16: ishap_volume_label / ishap_volume_components_* / ishap_volume_flip;
-        # 17: the weights fields of DragArgsC / DragBatchArgsC, ishap_region_plane_weights;
-        # 18: ishap_triplane_field_grad / ishap_triplane_project;
-        # 19: ishap_region_select / ishap_region_handles / ishap_region_handles_scratch_bytes / ishap_region_transform;
-        # 20: ishap_unet_block_grad; 21: ishap_drag_track / ishap_drag_track_scratch_bytes;
-        # 22: ishap_drag_retarget / ishap_drag_batch_retarget / ishap_drag_batch_retarget_each;
-        # 23: ishap_edt / ishap_edt_scratch_bytes / ishap_region_plane_marks / ishap_region_plane_feather[_scratch_bytes];
-        # 24: ishap_constraint_setup / ishap_constraint_setup_scratch_bytes / ishap_constraint_loss_grad;
-        # 25: ishap_triplane_decode_bricks / ishap_sparse_*; 26: ishap_mesh_simplify_*
-        if l.ishap_version() < 26:
-            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < 26): rebuild with `python -m ishapediting_amd.build`")
+        # which ABI added which symbol: the version notes of include/ishap.h
+        if l.ishap_version() < ABI:
+            raise RuntimeError(f"{LIB_PATH} is an older build (ABI {l.ishap_version()} < {ABI}): rebuild with `python -m ishapediting_amd.build`")
         _lib = l
     return _lib
 
@@ -333,3 +321,54 @@ def stream_ptr(device=None):
     """hipStream_t of torch's current stream, so library work is ordered with torch ops."""
     import torch
     return torch.cuda.current_stream(device).cuda_stream
+
+
+class ScratchError(RuntimeError):
+    """a *_scratch_bytes entry refused its sizes (a negative return)"""
+
+
+def need_gpu(t_or_device, what: str, verb: str = "runs"):
+    """The GPU `what` runs on: the device of a tensor, a given device as it is, or torch's current GPU for None.  Raises for a
+    host tensor, and for None without a GPU: there is no CPU fallback."""
+    import torch
+    if torch.is_tensor(t_or_device):
+        if t_or_device.is_cuda:
+            return t_or_device.device
+    elif t_or_device is not None:
+        return torch.device(t_or_device)
+    elif torch.cuda.is_available():
+        return torch.device("cuda", torch.cuda.current_device())
+    raise RuntimeError(f"{what} {verb} on the GPU (libishap_hip.so); there is no CPU fallback")
+
+
+def tensor(x, dtype, device=None, shape=None):
+    """`x` (a tensor, or anything numpy.asarray takes) detached, on `device` (None: where it is) as `dtype`, reshaped to
+    `shape` when given, contiguous: the input's own storage when it already conforms."""
+    import torch
+    if not torch.is_tensor(x):
+        import numpy as np
+        x = torch.from_numpy(np.asarray(x))
+    t = x.detach().to(device=device, dtype=dtype)
+    return (t if shape is None else t.reshape(shape)).contiguous()
+
+
+def scratch(device, name: str, *sizes):
+    """(uint8 tensor on `device`, its bytes) of the size the `name` (*_scratch_bytes) entry states for `sizes`"""
+    import torch
+    nbytes = int(getattr(lib(), name)(*sizes))
+    if nbytes < 0:
+        raise ScratchError(f"{name}{sizes}: the library refuses these sizes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def call(device, name: str, *args, stream=True):
+    """Run the library entry `name` with `device` current and raise on a non-zero return code.  The last argument is the
+    stream: torch's current one on `device` (stream=True), one fetched before (a stream_ptr value), or none (stream=False,
+    for entries that take no stream)."""
+    import torch
+    with torch.cuda.device(device):
+        if stream is True:
+            args += (stream_ptr(device),)
+        elif stream is not False:
+            args += (stream,)
+        check(getattr(lib(), name)(*args))

@@ -105,9 +105,8 @@ def rasterise(items, D: int, device) -> torch.Tensor:
     ones = torch.ones((D, D, D), dtype=torch.float32, device=dev)
     out = torch.empty((D, D, D), dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_region_select(ones.data_ptr(), D, 0.0, _lib.ptr(prims), len(recs), _lib.ptr(grid),
-                                                  out.data_ptr(), count.data_ptr(), _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_region_select", ones.data_ptr(), D, 0.0, _lib.ptr(prims), len(recs), _lib.ptr(grid), out.data_ptr(),
+              count.data_ptr())
     return out.view(torch.bool)
 
 

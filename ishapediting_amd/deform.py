@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from .mesh import OccupancyMesh, _write_obj, read_obj
-from .metrics import _device, _points, device_mesh
+from .metrics import device_mesh
 
 
 def _host_ids(ids, name: str) -> np.ndarray:
@@ -82,27 +82,21 @@ def deform_as_rigid_as_possible(verts, tris, constraint_ids, constraint_pos, max
         raise ValueError(f"max_iter >= 0 and tol >= 0 required, got {max_iter}, {tol}")
     if max_cg is not None and not 0 < int(max_cg) < 2 ** 31:
         raise ValueError(f"max_cg must be in [1, 2^31), got {max_cg}")
-    dev = verts.device if torch.is_tensor(verts) and verts.is_cuda else _device(device)
-    v = (verts if torch.is_tensor(verts) else torch.from_numpy(np.asarray(verts, np.float32))).detach().to(
-        device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    t = (tris if torch.is_tensor(tris) else torch.from_numpy(np.asarray(tris, np.int64))).detach().to(
-        device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+    dev = verts.device if torch.is_tensor(verts) and verts.is_cuda else _lib.need_gpu(device, "mesh metrics", "run")
+    v = _lib.tensor(verts, torch.float32, dev, (-1, 3))
+    t = _lib.tensor(tris, torch.int32, dev, (-1, 3))
     if v.shape[0] == 0 or t.shape[0] == 0:
         raise ValueError("deform_as_rigid_as_possible: the mesh has no vertices or no triangles")
     c = torch.from_numpy(ids.astype(np.int32)).to(dev)
-    cp = _points(pos, dev) if ids.size else torch.zeros((0, 3), dtype=torch.float32, device=dev)
+    cp = _lib.tensor(pos, torch.float32, dev, (-1, 3)) if ids.size else torch.zeros((0, 3), dtype=torch.float32, device=dev)
     K = int(max_iter)
     out = torch.empty_like(v)
     energy = torch.zeros(max(K, 1), dtype=torch.float64, device=dev)
     iters = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    nbytes = int(L.ishap_arap_scratch_bytes(v.shape[0], t.shape[0], c.shape[0]))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.ishap_arap(v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0], c.data_ptr() if ids.size else None,
-                                cp.data_ptr() if ids.size else None, c.shape[0], K, float(tol),
-                                0 if max_cg is None else int(max_cg), out.data_ptr(), energy.data_ptr(), iters.data_ptr(),
-                                scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    scratch, nbytes = _lib.scratch(dev, "ishap_arap_scratch_bytes", v.shape[0], t.shape[0], c.shape[0])
+    _lib.call(dev, "ishap_arap", v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0], c.data_ptr() if ids.size else None,
+              cp.data_ptr() if ids.size else None, c.shape[0], K, float(tol), 0 if max_cg is None else int(max_cg),
+              out.data_ptr(), energy.data_ptr(), iters.data_ptr(), scratch.data_ptr(), nbytes)
     it = iters[:K].cpu().numpy().astype(np.int64)
     info = {"energy": energy[:K].cpu().numpy(), "cg_iters": np.abs(it), "converged": it >= 0}
     return out, info
@@ -124,7 +118,7 @@ def arap(mesh, static_ids, handle_ids, handle_pos, max_iter: int = 50, path=None
     v, t = device_mesh(mesh, device)
     dev = v.device
     ids = np.concatenate([static, handles])
-    pos = torch.cat([v[torch.from_numpy(static).to(dev)], _points(hp, dev) if handles.size else v[:0]]).contiguous()
+    pos = torch.cat([v[torch.from_numpy(static).to(dev)], _lib.tensor(hp, torch.float32, dev, (-1, 3)) if handles.size else v[:0]]).contiguous()
     new_v, _ = deform_as_rigid_as_possible(v, t, ids, pos, max_iter=max_iter)
     if path is not None:
         _write_obj(path, new_v, t)
@@ -135,13 +129,11 @@ def nearest_vertices(mesh, points, device=None) -> torch.Tensor:
     """For every point the index of its nearest mesh vertex (fp64 squared distance), the lowest index on ties: main.py's
     KD-tree pick of drag handles.  int64 [P] on the device."""
     v, _ = device_mesh(mesh, device)
-    p = _points(points, v.device)
+    p = _lib.tensor(points, torch.float32, v.device, (-1, 3))
     idx = torch.empty(p.shape[0], dtype=torch.int32, device=v.device)
     if p.shape[0] == 0:
         return idx.long()
     if v.shape[0] == 0:
         raise ValueError("nearest_vertices: the mesh has no vertices")
-    with torch.cuda.device(v.device):
-        _lib.check(_lib.lib().ishap_nearest_vertices(v.data_ptr(), v.shape[0], p.data_ptr(), p.shape[0], idx.data_ptr(),
-                                                      _lib.stream_ptr(v.device)))
+    _lib.call(v.device, "ishap_nearest_vertices", v.data_ptr(), v.shape[0], p.data_ptr(), p.shape[0], idx.data_ptr())
     return idx.long()

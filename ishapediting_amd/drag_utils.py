@@ -118,9 +118,8 @@ class _DragKernelsBase:
         self._aim_ptr = None
         self._aim_keep = None         # whatever owns the memory at _aim_ptr when that is not self.goals (the loop's table)
 
-    def _call(self, fn, *args):
-        with th.cuda.device(self.device):
-            _lib.check(fn(*args, _lib.stream_ptr(self.device)))
+    def _call(self, name: str, *args):
+        _lib.call(self.device, name, *args)
 
     def _targets_ptr(self) -> int:
         """What the loss kernels read as targets: the final targets, or the goals of the last retarget."""
@@ -139,7 +138,7 @@ class _DragKernelsBase:
         if self.sources is None:
             raise RuntimeError("retarget: call setup() first")
         H, E = self.sources.shape[0], getattr(self, "E", 1)
-        K = (K.detach() if th.is_tensor(K) else th.as_tensor(np.asarray(K))).to(device=self.device, dtype=th.int32).contiguous()
+        K = _lib.tensor(K, th.int32, self.device)
         if tuple(K.shape) != (H, 3):
             raise ValueError(f"retarget: K must be [{H}, 3], got {tuple(K.shape)}")
         if self.goals is None:
@@ -218,14 +217,14 @@ class DragKernels(_DragKernelsBase):
         assert self.sources.shape[0] == self.targets.shape[0]
         self.cof = float(cof)
         self._reset_aim()
-        self._call(self._L.ishap_drag_setup, C.byref(self._args()))
+        self._call("ishap_drag_setup", C.byref(self._args()))
 
     def _retarget_call(self, k, remaining, arrived, done, step, arrive):
-        self._call(self._L.ishap_drag_retarget, C.byref(self._args()), self.targets.data_ptr(), k, float(step), float(arrive),
+        self._call("ishap_drag_retarget", C.byref(self._args()), self.targets.data_ptr(), k, float(step), float(arrive),
                    remaining, arrived, done)
 
     def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int):
-        self._call(self._L.ishap_drag_loss_grad, C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
+        self._call("ishap_drag_loss_grad", C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
                    self.loss.data_ptr())
         return self.grad, self.loss
 
@@ -238,13 +237,13 @@ class DragKernels(_DragKernelsBase):
         `orig_stride`: the batched object's argument, 0 here (one edit reads one guidance tap)."""
         assert orig_stride == 0
         loss = self.loss if loss_out is None else loss_out
-        self._call(self._L.ishap_drag_loss_cotangent, C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
+        self._call("ishap_drag_loss_cotangent", C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
                    loss.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(), self.scale2.data_ptr())
         return self.cot, self.scale2
 
     def scaled_cotangent(self):
         """fp32 gradient -> fp16 cotangent * 2^k (k from max|g|) so the fp16 backward neither under- nor overflows."""
-        self._call(self._L.ishap_grad_to_scaled_f16, self.grad.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(),
+        self._call("ishap_grad_to_scaled_f16", self.grad.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(),
                    self.scale2.data_ptr(), self.grad.numel())
         return self.cot, self.scale2
 
@@ -347,16 +346,16 @@ class BatchDragKernels(_DragKernelsBase):
         self.cof = cofs
         self._cof = (C.c_float * self.E)(*self.cof)
         self._reset_aim()
-        self._call(self._L.ishap_drag_batch_setup, C.byref(self._args(0)))
+        self._call("ishap_drag_batch_setup", C.byref(self._args(0)))
 
     def _retarget_call(self, k, remaining, arrived, done, step, arrive):
         each = [not isinstance(v, (int, float, np.floating, np.integer)) for v in (step, arrive)]
         if any(each):           # one lead / arrival radius per edit
             st, ar = per_edit(step, self.E, "step"), per_edit(arrive, self.E, "arrive")
-            self._call(self._L.ishap_drag_batch_retarget_each, C.byref(self._args(0)), self.targets.data_ptr(), k,
+            self._call("ishap_drag_batch_retarget_each", C.byref(self._args(0)), self.targets.data_ptr(), k,
                        (C.c_float * self.E)(*st), (C.c_float * self.E)(*ar), remaining, arrived, done)
         else:
-            self._call(self._L.ishap_drag_batch_retarget, C.byref(self._args(0)), self.targets.data_ptr(), k, float(step),
+            self._call("ishap_drag_batch_retarget", C.byref(self._args(0)), self.targets.data_ptr(), k, float(step),
                        float(arrive), remaining, arrived, done)
 
     def _args(self, orig_stride: int) -> _lib.DragBatchArgsC:
@@ -380,14 +379,14 @@ class BatchDragKernels(_DragKernelsBase):
 
     def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int):
         """edit: [E][W*W][ld] fp16; orig: edit e's guidance at orig + e * orig_stride halfs (0: one guidance for all edits)."""
-        self._call(self._L.ishap_drag_batch_loss_grad, C.byref(self._args(orig_stride)), edit_ptr, orig_ptr, self.grad.data_ptr(),
+        self._call("ishap_drag_batch_loss_grad", C.byref(self._args(orig_stride)), edit_ptr, orig_ptr, self.grad.data_ptr(),
                    self.loss.data_ptr())
         return self.grad, self.loss
 
     def loss_cotangent_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int, loss_out=None):
         """losses + gradients + the batch's fp16 cotangent (one loss scale, scale2) in three launches; `loss_out`: device float[E]."""
         loss = self.loss if loss_out is None else loss_out
-        self._call(self._L.ishap_drag_batch_loss_cotangent, C.byref(self._args(orig_stride)), edit_ptr, orig_ptr,
+        self._call("ishap_drag_batch_loss_cotangent", C.byref(self._args(orig_stride)), edit_ptr, orig_ptr,
                    self.grad.data_ptr(), loss.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(), self.scale2.data_ptr())
         return self.cot, self.scale2
 
@@ -435,12 +434,12 @@ class HandleTracker:
         """sources: a list of E handle arrays [B_e, 3] (one per edit).  Allocates the per-call buffers; nothing is launched."""
         src, _, offs = pack_handles(sources, sources)
         self.E = len(offs) - 1
-        nbytes = int(self._L.ishap_drag_track_scratch_bytes(self.E, offs[-1], self.R, self.rp, self.Cc))
-        if nbytes < 0:
-            raise ValueError(f"handle tracker: {self.E} edits (1..32)")
+        try:
+            self.scratch, nbytes = _lib.scratch(self.device, "ishap_drag_track_scratch_bytes", self.E, offs[-1], self.R, self.rp, self.Cc)
+        except _lib.ScratchError:
+            raise ValueError(f"handle tracker: {self.E} edits (1..32)") from None
         self.sources, self.offsets = src.to(self.device), list(offs)
         self._offs = (C.c_int * (self.E + 1))(*offs)
-        self.scratch = th.empty(nbytes, dtype=th.uint8, device=self.device)
         self._chmap_ptr, self._src_ptr = self.chmap.data_ptr(), self.sources.data_ptr()
         self._scratch_ptr, self._scratch_bytes = self.scratch.data_ptr(), nbytes
         return self
@@ -457,10 +456,9 @@ class HandleTracker:
 
     def run_raw(self, edit_ptr: int, orig_ptr: int, orig_stride: int, k_in: int, k_out: int, dist: int, dist0: int, volume=None):
         """run_ptr on device addresses (the guided loop's form: no tensor is made per step)."""
-        with th.cuda.device(self.device):
-            _lib.check(self._L.ishap_drag_track(edit_ptr, orig_ptr, int(orig_stride), self.W, self.ld, self.Cc, self._chmap_ptr,
-                                                self._src_ptr, self._offs, self.E, self.voxel, self.R, self.rp, k_in, k_out, dist, dist0,
-                                                volume, self._scratch_ptr, self._scratch_bytes, _lib.stream_ptr(self.device)))
+        _lib.call(self.device, "ishap_drag_track", edit_ptr, orig_ptr, int(orig_stride), self.W, self.ld, self.Cc, self._chmap_ptr,
+                  self._src_ptr, self._offs, self.E, self.voxel, self.R, self.rp, k_in, k_out, dist, dist0, volume,
+                  self._scratch_ptr, self._scratch_bytes)
 
     def positions(self, offsets: th.Tensor) -> th.Tensor:
         """lattice(source, voxel, K) in float32 (the product rounded, then the sum), for offsets [..., H, 3]."""
@@ -678,7 +676,7 @@ class VolumeGuidance:
     def gradient(self, x, i, model_output, loss_out=None):
         """d L_vol / d x of the step (x, i) whose complete model output is `model_output` and whose forward the model keeps;
         L_vol goes to loss_out (device float[1]).  A full-depth backward: runs after the forward's tail has been joined."""
-        ds, d, L = self.ds, self.ds.diffusion, _lib.lib()
+        ds, d = self.ds, self.ds.diffusion
         dev, S = ds.device, ds.args.image_size
         ti = d._t_index(i)
         # the step kernel with pred_xstart as its only output: the one extra elementwise launch (the guided loop clips, as its step does)
@@ -688,24 +686,20 @@ class VolumeGuidance:
         g_direct = th.empty_like(x)
         sr = float(np.float32(d.sqrt_recip_alphas_cumprod[ti]))
         srm1 = float(np.float32(d.sqrt_recipm1_alphas_cumprod[ti]))
-        with th.cuda.device(dev):
-            s = _lib.stream_ptr(dev)
-            _lib.check(L.ishap_x0_grad_to_cotangent(self.dplanes.data_ptr(), _lib.ptr(self.rng), x.data_ptr(), model_output.data_ptr(),
-                                                    sr, srm1, 1, S, g_direct.data_ptr(), self.cot.data_ptr(), s))
-            _lib.check(L.ishap_grad_to_scaled_f16(self.cot.data_ptr(), self.cot16.data_ptr(), self.bits.data_ptr(),
-                                                  self.scale2.data_ptr(), self.cot.numel(), s))
+        _lib.call(dev, "ishap_x0_grad_to_cotangent", self.dplanes.data_ptr(), _lib.ptr(self.rng), x.data_ptr(), model_output.data_ptr(),
+                  sr, srm1, 1, S, g_direct.data_ptr(), self.cot.data_ptr())
+        _lib.call(dev, "ishap_grad_to_scaled_f16", self.cot.data_ptr(), self.cot16.data_ptr(), self.bits.data_ptr(),
+                  self.scale2.data_ptr(), self.cot.numel())
         dx = ds.model.backward_from_output(self.cot16, self.scale2)
         grad = th.empty_like(dx)
-        with th.cuda.device(dev):
-            _lib.check(L.ishap_axpby(dx.data_ptr(), g_direct.data_ptr(), 1.0, 1.0, dx.numel(), grad.data_ptr(), _lib.stream_ptr(dev)))
+        _lib.call(dev, "ishap_axpby", dx.data_ptr(), g_direct.data_ptr(), 1.0, 1.0, dx.numel(), grad.data_ptr())
         return grad
 
     def mix(self, grad_drag, grad_vol):
         """grad_drag + (volume_scale / scale) grad_vol: what the guided update multiplies by scale"""
         out = th.empty_like(grad_drag)
-        with th.cuda.device(self.ds.device):
-            _lib.check(_lib.lib().ishap_axpby(grad_drag.data_ptr(), grad_vol.data_ptr(), 1.0, self.ratio, grad_drag.numel(),
-                                              out.data_ptr(), _lib.stream_ptr(self.ds.device)))
+        _lib.call(self.ds.device, "ishap_axpby", grad_drag.data_ptr(), grad_vol.data_ptr(), 1.0, self.ratio, grad_drag.numel(),
+                  out.data_ptr())
         return out
 
 
@@ -1058,11 +1052,9 @@ class DragStuff:
             else:
                 new = th.empty_like(img)
                 n1 = img[0].numel()
-                with th.cuda.device(self.device):
-                    for k, sc in enumerate(scales):
-                        _lib.check(_lib.lib().ishap_guided_update(
-                            outs["sample"][k].data_ptr(), outs["variance"][k].data_ptr(), got["grad"][k].data_ptr(), sc, None, n1,
-                            new[k].data_ptr(), _lib.stream_ptr(self.device)))
+                for k, sc in enumerate(scales):
+                    _lib.call(self.device, "ishap_guided_update", outs["sample"][k].data_ptr(), outs["variance"][k].data_ptr(),
+                              got["grad"][k].data_ptr(), sc, None, n1, new[k].data_ptr())
                 img = new
             self.last_losses.append(slot)
             if vol is not None:
@@ -1388,7 +1380,6 @@ class DragStuff:
         `batch_fn(i) -> (coord, gt)`, `img` and `steps` (step indices to run) replace the random batch / initial noise /
         full schedule for parity runs.  Every step runs its forward (no first-step snapshot: the input differs from call to
         call); the snapshot training() keeps of the loaded shape stays valid."""
-        L = _lib.lib()
         d = self.diffusion
         if img is None:
             img = th.randn((1, 96, self.args.image_size, self.args.image_size), dtype=th.float32, device=self.device)
@@ -1414,20 +1405,16 @@ class DragStuff:
             srm1 = float(np.float32(d.sqrt_recipm1_alphas_cumprod[i]))
             new = th.empty_like(img)
             cot16 = th.empty((1, 192, S, S), dtype=th.float16, device=self.device)
-            with th.cuda.device(self.device):
-                s = _lib.stream_ptr(self.device)
-                _lib.check(L.ishap_x0_grad_to_cotangent(dplanes.data_ptr(), _lib.ptr(rng_t.reshape(-1).contiguous()) if rng_t is not None else None,
-                                                        img.data_ptr(), outs["model_output"].data_ptr(), sr, srm1,
-                                                        int(self.args.clip_denoised), S, g_direct.data_ptr(), cot.data_ptr(), s))
-                _lib.check(L.ishap_grad_to_scaled_f16(cot.data_ptr(), cot16.data_ptr(), bits.data_ptr(), scale2.data_ptr(),
-                                                      cot.numel(), s))
+            _lib.call(self.device, "ishap_x0_grad_to_cotangent", dplanes.data_ptr(),
+                      _lib.ptr(rng_t.reshape(-1).contiguous()) if rng_t is not None else None, img.data_ptr(),
+                      outs["model_output"].data_ptr(), sr, srm1, int(self.args.clip_denoised), S, g_direct.data_ptr(), cot.data_ptr())
+            _lib.call(self.device, "ishap_grad_to_scaled_f16", cot.data_ptr(), cot16.data_ptr(), bits.data_ptr(), scale2.data_ptr(),
+                      cot.numel())
             dx = self.model.backward_from_output(cot16, scale2)
             grads1 = th.empty_like(dx)                               # = img.grad of the reference (:459): UNet path + direct path
-            with th.cuda.device(self.device):
-                _lib.check(L.ishap_axpby(dx.data_ptr(), g_direct.data_ptr(), 1.0, 1.0, dx.numel(), grads1.data_ptr(),
-                                         _lib.stream_ptr(self.device)))
-                _lib.check(L.ishap_guided_update(outs["sample"].data_ptr(), outs["variance"].data_ptr(), grads1.data_ptr(),
-                                                 float(scale), None, img.numel(), new.data_ptr(), _lib.stream_ptr(self.device)))
+            _lib.call(self.device, "ishap_axpby", dx.data_ptr(), g_direct.data_ptr(), 1.0, 1.0, dx.numel(), grads1.data_ptr())
+            _lib.call(self.device, "ishap_guided_update", outs["sample"].data_ptr(), outs["variance"].data_ptr(), grads1.data_ptr(),
+                      float(scale), None, img.numel(), new.data_ptr())
             img = new
             self.last_losses.append(loss)
         return img

@@ -157,28 +157,25 @@ class SpacedDiffusion:
             outs["guided"] = torch.empty_like(x)
             if torch.is_tensor(scale):        # one scale per image (batched drag edits): device float[N]
                 assert scale.shape == (N,) and scale.dtype == torch.float32 and scale.device == x.device
-                with torch.cuda.device(x.device):
-                    _lib.check(_lib.lib().ishap_ddpm_step_guided_scales(
-                        x.data_ptr(), model_output.data_ptr(), _lib.ptr(noise), _lib.ptr(variance_in), C.byref(k), N, Cc, HW,
-                        grad.data_ptr(), scale.data_ptr(), None, outs["guided"].data_ptr(), _lib.ptr(outs.get("sample")),
-                        _lib.ptr(outs.get("variance")), _lib.stream_ptr(x.device)))
+                _lib.call(x.device, "ishap_ddpm_step_guided_scales",
+                          x.data_ptr(), model_output.data_ptr(), _lib.ptr(noise), _lib.ptr(variance_in), C.byref(k), N, Cc, HW,
+                          grad.data_ptr(), scale.data_ptr(), None, outs["guided"].data_ptr(), _lib.ptr(outs.get("sample")),
+                          _lib.ptr(outs.get("variance")))
                 return outs
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().ishap_ddpm_step_guided(
-                    x.data_ptr(), model_output.data_ptr(), _lib.ptr(noise), _lib.ptr(variance_in), C.byref(k), N, Cc, HW,
-                    grad.data_ptr(), scale, None, outs["guided"].data_ptr(), _lib.ptr(outs.get("sample")),
-                    _lib.ptr(outs.get("variance")), _lib.stream_ptr(x.device)))
+            _lib.call(x.device, "ishap_ddpm_step_guided",
+                      x.data_ptr(), model_output.data_ptr(), _lib.ptr(noise), _lib.ptr(variance_in), C.byref(k), N, Cc, HW,
+                      grad.data_ptr(), scale, None, outs["guided"].data_ptr(), _lib.ptr(outs.get("sample")),
+                      _lib.ptr(outs.get("variance")))
             return outs
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ishap_ddpm_step(
-                x.data_ptr(), model_output.data_ptr(), _lib.ptr(noise), _lib.ptr(variance_in), C.byref(k), N, Cc, HW,
-                _lib.ptr(outs.get("sample")), _lib.ptr(outs.get("pred_xstart")), _lib.ptr(outs.get("variance")),
-                _lib.ptr(outs.get("mean")), _lib.stream_ptr(x.device)))
+        _lib.call(x.device, "ishap_ddpm_step",
+                  x.data_ptr(), model_output.data_ptr(), _lib.ptr(noise), _lib.ptr(variance_in), C.byref(k), N, Cc, HW,
+                  _lib.ptr(outs.get("sample")), _lib.ptr(outs.get("pred_xstart")), _lib.ptr(outs.get("variance")),
+                  _lib.ptr(outs.get("mean")))
         return outs
 
     @staticmethod
     def _prep(x):
-        return x.detach().to(dtype=torch.float32).contiguous()
+        return _lib.tensor(x, torch.float32)
 
     def _guidance_step_autograd(self, model, x, ti, noise, variance, variance_noise, clip_denoised, feat_layer):
         """p_sample_guidance with the graph kept (gaussian_diffusion.py:232-331 for LEARNED_RANGE + EPSILON, :489-510): what
@@ -382,7 +379,6 @@ class SpacedDiffusion:
         is called after every reverse step so the caller can keep the resident tap (guidance cache)."""
         feat, variance_noise, variance = [], [], []
         x = self._prep(x_0)
-        L = _lib.lib()
         self.prepare(model, range(steps))
         img_inter = [x]
         for i in range(steps):
@@ -390,9 +386,7 @@ class SpacedDiffusion:
             a, b = float(np.sqrt(np.float32(cof))), float(np.sqrt(np.float32(1) - cof))
             eps = self._prep(fwd_noise[i]) if fwd_noise is not None else torch.randn_like(x)
             nxt = torch.empty_like(x)
-            with torch.cuda.device(x.device):
-                _lib.check(L.ishap_axpby(x.data_ptr(), eps.data_ptr(), a, b, x.numel(), nxt.data_ptr(),
-                                         _lib.stream_ptr(x.device)))
+            _lib.call(x.device, "ishap_axpby", x.data_ptr(), eps.data_ptr(), a, b, x.numel(), nxt.data_ptr())
             x = nxt
             img_inter.append(x)
         img = img_inter[-1]
@@ -406,10 +400,9 @@ class SpacedDiffusion:
             # z_i = x_i - mean_i and img = mean_i + z_i (:527-529) through the library's elementwise kernel (a, b = +-1 are
             # exact, so these are the reference's fp32 subtraction / addition): no torch arithmetic on the path
             z, nxt = torch.empty_like(img), torch.empty_like(img)
-            with torch.cuda.device(img.device):
-                s_ = _lib.stream_ptr(img.device)
-                _lib.check(L.ishap_axpby(img_inter[i].data_ptr(), outs["mean"].data_ptr(), 1.0, -1.0, img.numel(), z.data_ptr(), s_))
-                _lib.check(L.ishap_axpby(outs["mean"].data_ptr(), z.data_ptr(), 1.0, 1.0, img.numel(), nxt.data_ptr(), s_))
+            s_ = _lib.stream_ptr(img.device)       # one fetch for the two launches
+            _lib.call(img.device, "ishap_axpby", img_inter[i].data_ptr(), outs["mean"].data_ptr(), 1.0, -1.0, img.numel(), z.data_ptr(), stream=s_)
+            _lib.call(img.device, "ishap_axpby", outs["mean"].data_ptr(), z.data_ptr(), 1.0, 1.0, img.numel(), nxt.data_ptr(), stream=s_)
             variance_noise.append(z)
             img = nxt
         return {"inter_feat": feat, "latent": img_inter[-1], "variance_noise": variance_noise, "variance": variance,

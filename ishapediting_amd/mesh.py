@@ -25,49 +25,38 @@ BACKEND = "device"                # "device" | "open3d" | "third_party"; set exp
 METHODS = {"marching_tetrahedra": 0, "marching_cubes": 1}
 
 
-def _need_gpu(t: torch.Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} runs on the GPU (libishap_hip.so); there is no CPU fallback")
-
-
 def extract_surface(volume: torch.Tensor, level: float = 0.0, method: str = "marching_cubes"):
     """Level-`level` triangle mesh of a [res,res,res] volume: (vertices [V,3] float32 in grid coordinates,
     triangles [F,3] int32), both on the device, in voxel order (deterministic).  method: "marching_cubes" (what the
     reference calls, visualize.py:100) or "marching_tetrahedra"."""
     meth = METHODS[method]
-    _need_gpu(volume, "extract_surface")
+    _lib.need_gpu(volume, "extract_surface")
     assert volume.dim() == 3 and volume.shape[0] == volume.shape[1] == volume.shape[2]
     res = volume.shape[0]
     dev = volume.device
-    vol = volume.detach().to(torch.float32).contiguous()
-    L = _lib.lib()
-    scratch = torch.empty(int(L.ishap_surface_scratch_bytes(res)), dtype=torch.uint8, device=dev)
+    vol = _lib.tensor(volume, torch.float32)
+    scratch, _ = _lib.scratch(dev, "ishap_surface_scratch_bytes", res)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        s = _lib.stream_ptr(dev)
-        _lib.check(L.ishap_surface_count(vol.data_ptr(), res, float(level), meth, scratch.data_ptr(), counts.data_ptr(), s))
-        nv, nt = (int(c) for c in counts.tolist())                 # the one host read-back: output sizes
-        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        tris = torch.empty((nt, 3), dtype=torch.int32, device=dev)
-        if nv and nt:
-            _lib.check(L.ishap_surface_emit(vol.data_ptr(), res, float(level), meth, scratch.data_ptr(), verts.data_ptr(),
-                                            tris.data_ptr(), s))
+    _lib.call(dev, "ishap_surface_count", vol.data_ptr(), res, float(level), meth, scratch.data_ptr(), counts.data_ptr())
+    nv, nt = (int(c) for c in counts.tolist())                 # the one host read-back: output sizes
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    tris = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    if nv and nt:
+        _lib.call(dev, "ishap_surface_emit", vol.data_ptr(), res, float(level), meth, scratch.data_ptr(), verts.data_ptr(),
+                  tris.data_ptr())
     return verts, tris
 
 
 def surface_counts(volume: torch.Tensor, level: float = 0.0, method: str = "marching_cubes"):
     """(vertices, triangles) of the level surface without emitting it."""
     meth = METHODS[method]
-    _need_gpu(volume, "surface_counts")
+    _lib.need_gpu(volume, "surface_counts")
     res = volume.shape[0]
     dev = volume.device
-    vol = volume.detach().to(torch.float32).contiguous()
-    L = _lib.lib()
-    scratch = torch.empty(int(L.ishap_surface_scratch_bytes(res)), dtype=torch.uint8, device=dev)
+    vol = _lib.tensor(volume, torch.float32)
+    scratch, _ = _lib.scratch(dev, "ishap_surface_scratch_bytes", res)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.ishap_surface_count(vol.data_ptr(), res, float(level), meth, scratch.data_ptr(), counts.data_ptr(),
-                                         _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_surface_count", vol.data_ptr(), res, float(level), meth, scratch.data_ptr(), counts.data_ptr())
     nv, nt = counts.tolist()
     return int(nv), int(nt)
 
@@ -75,18 +64,17 @@ def surface_counts(volume: torch.Tensor, level: float = 0.0, method: str = "marc
 def smooth_mesh(verts: torch.Tensor, tris: torch.Tensor, iterations: int = 10, box_max: float = 0.0) -> torch.Tensor:
     """filter_smooth_simple (drag_utils.py:300) on the device; returns new vertex positions.  box_max > 0: `verts` are grid
     coordinates of a [0, box_max]^3 volume whose surface may be cut open by the box (each neighbour still counts once)."""
-    _need_gpu(verts, "smooth_mesh")
-    out = verts.detach().to(torch.float32).contiguous().clone()
-    tris = tris.detach().to(torch.int32).contiguous()
+    _lib.need_gpu(verts, "smooth_mesh")
+    out = _lib.tensor(verts, torch.float32).clone()
+    tris = _lib.tensor(tris, torch.int32)
     if out.shape[0] == 0 or tris.shape[0] == 0 or iterations <= 0:
         return out
-    nbytes = int(_lib.lib().ishap_mesh_smooth_scratch_bytes(out.shape[0], tris.shape[0]))
-    if nbytes < 0:
-        raise RuntimeError("ishap_mesh_smooth_scratch_bytes: invalid sizes")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.lib().ishap_mesh_smooth(out.data_ptr(), out.shape[0], tris.data_ptr(), tris.shape[0], int(iterations),
-                                                float(box_max), scratch.data_ptr(), nbytes, _lib.stream_ptr(out.device)))
+    try:
+        scratch, nbytes = _lib.scratch(out.device, "ishap_mesh_smooth_scratch_bytes", out.shape[0], tris.shape[0])
+    except _lib.ScratchError:
+        raise RuntimeError("ishap_mesh_smooth_scratch_bytes: invalid sizes") from None
+    _lib.call(out.device, "ishap_mesh_smooth", out.data_ptr(), out.shape[0], tris.data_ptr(), tris.shape[0], int(iterations),
+              float(box_max), scratch.data_ptr(), nbytes)
     return out
 
 
@@ -149,7 +137,7 @@ def simplify_vertex_clustering(verts: torch.Tensor, tris: torch.Tensor, cell: fl
     cell): use a larger cell or contraction="average".
     Clustering can leave non-manifold edges and vertices where a feature is thinner than a cell (two sheets that fall into one
     cell are joined); nothing here repairs that."""
-    _need_gpu(verts, "simplify_vertex_clustering")
+    _lib.need_gpu(verts, "simplify_vertex_clustering")
     _check_choice("contraction", contraction, tuple(CONTRACTIONS))
     cell, regularization = float(cell), float(regularization)
     if not (cell > 0 and np.isfinite(cell)):
@@ -157,8 +145,8 @@ def simplify_vertex_clustering(verts: torch.Tensor, tris: torch.Tensor, cell: fl
     if not (regularization > 0 and np.isfinite(regularization)):
         raise ValueError(f"simplify_vertex_clustering: regularization must be positive and finite, not {regularization}")
     dev = verts.device
-    v = verts.detach().to(torch.float32).contiguous().reshape(-1, 3)
-    t = tris.detach().to(device=dev, dtype=torch.int32).contiguous().reshape(-1, 3)
+    v = _lib.tensor(verts, torch.float32, shape=(-1, 3))
+    t = _lib.tensor(tris, torch.int32, dev, (-1, 3))
     nv, nt = int(v.shape[0]), int(t.shape[0])
     if nv > 0x7fffffff or 3 * nt > 0x7fffffff:
         raise ValueError("simplify_vertex_clustering: vertex indices and 3 * triangles must fit int32")
@@ -179,28 +167,24 @@ def simplify_vertex_clustering(verts: torch.Tensor, tris: torch.Tensor, cell: fl
     dims = [int(d) for d in np.asarray(dims).reshape(3)]
     if min(dims) < 1 or dims[0] * dims[1] * dims[2] > SIMPLIFY_MAX_CELLS:
         raise ValueError(f"simplify_vertex_clustering: dims {dims} must be >= 1 with at most 2^30 cells; use a larger cell")
-    L = _lib.lib()
     lo_c, dims_c = (C.c_double * 3)(*lo.tolist()), (C.c_int * 3)(*dims)
-    nbytes = int(L.ishap_mesh_simplify_scratch_bytes(nv, nt, dims_c))
-    if nbytes < 0:
-        raise RuntimeError("ishap_mesh_simplify_scratch_bytes: invalid sizes")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    try:
+        scratch, nbytes = _lib.scratch(dev, "ishap_mesh_simplify_scratch_bytes", nv, nt, dims_c)
+    except _lib.ScratchError:
+        raise RuntimeError("ishap_mesh_simplify_scratch_bytes: invalid sizes") from None
     counts = torch.empty(3, **i32)
-    mode = CONTRACTIONS[contraction]
-    with torch.cuda.device(dev):
-        s = _lib.stream_ptr(dev)
-        common = (v.data_ptr(), nv, t.data_ptr(), nt, lo_c, cell, dims_c, mode)
-        _lib.check(L.ishap_mesh_simplify_count(*common, scratch.data_ptr(), nbytes, counts.data_ptr(), s))
-        vo, to, status, clusters, nondeg = torch.cat([counts, scratch[:8].view(torch.int32)]).tolist()     # the one host read-back
-        if status != 0:
-            raise RuntimeError("simplify_vertex_clustering: the triangle area gathered in one cell reaches 2^26 cell faces, the "
-                               "64-bit quadric sums could overflow; use a larger cell or contraction=\"average\"")
-        out_v = torch.empty((max(vo, 1), 3), dtype=torch.float32, device=dev)      # an empty result still needs an address
-        out_t = torch.empty((max(to, 1), 3), **i32)
-        vmap = torch.empty(nv, **i32)
-        vclus = torch.empty(nv, **i32) if return_clusters else None
-        _lib.check(L.ishap_mesh_simplify_emit(*common, regularization, scratch.data_ptr(), nbytes, out_v.data_ptr(), out_t.data_ptr(),
-                                              vmap.data_ptr(), _lib.ptr(vclus), s))
+    common = (v.data_ptr(), nv, t.data_ptr(), nt, lo_c, cell, dims_c, CONTRACTIONS[contraction])
+    _lib.call(dev, "ishap_mesh_simplify_count", *common, scratch.data_ptr(), nbytes, counts.data_ptr())
+    vo, to, status, clusters, nondeg = torch.cat([counts, scratch[:8].view(torch.int32)]).tolist()     # the one host read-back
+    if status != 0:
+        raise RuntimeError("simplify_vertex_clustering: the triangle area gathered in one cell reaches 2^26 cell faces, the "
+                           "64-bit quadric sums could overflow; use a larger cell or contraction=\"average\"")
+    out_v = torch.empty((max(vo, 1), 3), dtype=torch.float32, device=dev)      # an empty result still needs an address
+    out_t = torch.empty((max(to, 1), 3), **i32)
+    vmap = torch.empty(nv, **i32)
+    vclus = torch.empty(nv, **i32) if return_clusters else None
+    _lib.call(dev, "ishap_mesh_simplify_emit", *common, regularization, scratch.data_ptr(), nbytes, out_v.data_ptr(),
+              out_t.data_ptr(), vmap.data_ptr(), _lib.ptr(vclus))
     out_v, out_t = out_v[:vo], out_t[:to]
     held = sum(x.numel() * x.element_size() for x in (scratch, counts, out_v, out_t, vmap))
     info = SimplifyInfo(int(clusters), nv, int(vo), nt, int(nondeg), int(to), held)
@@ -215,7 +199,7 @@ def chamfer_distance(pa: torch.Tensor, pb: torch.Tensor, point_num=20000, seed: 
     direction is a random subset of that many points, the nearest neighbour is searched in the COMPLETE other set -- an
     unbiased estimate of the all-points value without its quadratic cost and without a sampling floor (the floor of the
     sampled form comes from thinning the target set)."""
-    _need_gpu(pa, "chamfer_distance")
+    _lib.need_gpu(pa, "chamfer_distance")
     g = torch.Generator(device="cpu").manual_seed(seed)
 
     def pick(p, n):
@@ -226,12 +210,10 @@ def chamfer_distance(pa: torch.Tensor, pb: torch.Tensor, point_num=20000, seed: 
     def run(a, b):
         nearest = torch.empty(max(a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
         out2 = torch.empty(2, dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().ishap_chamfer(a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], nearest.data_ptr(),
-                                                out2.data_ptr(), _lib.stream_ptr(a.device)))
+        _lib.call(a.device, "ishap_chamfer", a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], nearest.data_ptr(), out2.data_ptr())
         return out2.tolist()
-    a = pick(pa, point_num).detach().to(torch.float32).contiguous()
-    b = pick(pb, point_num).detach().to(device=a.device, dtype=torch.float32).contiguous()
+    a = _lib.tensor(pick(pa, point_num), torch.float32)
+    b = _lib.tensor(pick(pb, point_num), torch.float32, a.device)
     if a.shape[0] == 0 or b.shape[0] == 0:
         return float("nan")
     if query_num is not None and point_num is None:
@@ -439,7 +421,7 @@ def extract_surface_sparse(decoder, planes: torch.Tensor, res: int, seeds, level
     next depends on how the round's workgroups were scheduled.  The mesh, info.bricks and info.points are (the reached set is a
     least fixed point); rounds has a lower bound (the brick distance the surface travels from the seeds) and may differ run to run."""
     from . import triplane_decoder as td              # triplane_decoder has no need of this module
-    _need_gpu(planes, "extract_surface_sparse")
+    _lib.need_gpu(planes, "extract_surface_sparse")
     res, max_rounds, max_bricks = int(res), int(max_rounds), int(max_bricks)
     L = _lib.lib()
     nb = int(L.ishap_sparse_bricks_per_axis(res))
@@ -453,97 +435,93 @@ def extract_surface_sparse(decoder, planes: torch.Tensor, res: int, seeds, level
     slot_map = torch.empty(N, **i32)
     blist = torch.empty(N + 1, **i32)                  # slot -> brick id, discovery order
     counters = torch.zeros(2, **i32)                   # {edge bits a growth round recorded, bricks a compaction listed}
-    cbytes = int(L.ishap_sparse_compact_scratch_bytes(res))
-    cscratch = torch.empty(cbytes, dtype=torch.uint8, device=dev)
+    cscratch, cbytes = _lib.scratch(dev, "ishap_sparse_compact_scratch_bytes", res)
     axis = torch.linspace(-1, 1, res).to(dev)          # the table decode_planes_grid reads
     held = [bmap, slot_map, blist, cscratch]
     n0 = None
-    with torch.cuda.device(dev):
-        s = _lib.stream_ptr(dev)
-        if isinstance(seeds, str):
-            if seeds != "all":
-                raise ValueError(f'extract_surface_sparse: seeds must be a coarse volume, "all" or brick coordinates [n,3], not {seeds!r}')
-            bmap.fill_(1)
-            n0 = N
-        elif torch.is_tensor(seeds) and seeds.is_floating_point():
-            if seeds.dim() != 3 or not (seeds.shape[0] == seeds.shape[1] == seeds.shape[2]) or not 2 <= seeds.shape[0] <= SPARSE_MAX_RES:
-                raise ValueError(f"extract_surface_sparse: a coarse seed volume is [Rc,Rc,Rc] with 2 <= Rc <= {SPARSE_MAX_RES}, not {tuple(seeds.shape)}")
-            if res - 1 > SPARSE_MAX_RATIO * (seeds.shape[0] - 1):
-                raise ValueError(f"extract_surface_sparse: a coarse volume of {seeds.shape[0]}^3 seeds fine grids up to "
-                                 f"{SPARSE_MAX_RATIO * (seeds.shape[0] - 1) + 1} (res - 1 <= {SPARSE_MAX_RATIO} (Rc - 1)), not {res}")
-            coarse = seeds.detach().to(device=dev, dtype=torch.float32).contiguous()
-            _lib.check(L.ishap_sparse_seed_volume(coarse.data_ptr(), coarse.shape[0], float(level), res, bmap.data_ptr(), s))
-        else:
-            b = torch.as_tensor(seeds)
-            if b.is_floating_point() or b.dim() != 2 or b.shape[1] != 3:
-                raise ValueError("extract_surface_sparse: explicit seeds are an int tensor [n,3] of brick coordinates")
-            b = b.detach().to(torch.int64).cpu()
-            if b.numel() and (int(b.min()) < 0 or int(b.max()) >= nb):
-                raise ValueError(f"extract_surface_sparse: brick coordinates must lie in 0 .. {nb - 1} (res = {res})")
-            ids = torch.unique((b[:, 0] * nb + b[:, 1]) * nb + b[:, 2])
-            bmap[ids.to(dev)] = 1
-            n0 = int(ids.numel())
-        _lib.check(L.ishap_sparse_compact(bmap.data_ptr(), res, 0, 0, slot_map.data_ptr(), blist.data_ptr(), N,
-                                          counters[1:].data_ptr(), cscratch.data_ptr(), cbytes, s))
-        if n0 is None:
-            n0 = int(counters[1])                      # read-back: the seed count
-        empty = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), **i32))
-        if n0 == 0:
-            return empty[0], empty[1], SparseSurfaceInfo(0, 0, 0, sum(t.numel() * t.element_size() for t in held))
-        if n0 > max_bricks:
-            raise RuntimeError(f"extract_surface_sparse: the seeds name {n0} bricks, more than max_bricks = {max_bricks}")
-        n, rounds = n0, 0
-        rbytes = int(L.ishap_sparse_reach_bytes(1))
-        # values and reached bits live in buffers with room to grow: a round that adds bricks decodes them in place behind the
-        # others; a full buffer is replaced by one half as large again (a copy per growth of 1.5x, not per round)
-        cap = min(N, n + n // 4 + 16)
-        values = torch.empty((cap, 729), dtype=torch.float32, device=dev)
-        reach = torch.zeros((cap, rbytes), dtype=torch.uint8, device=dev)
-        td._decode_bricks_into(decoder, planes, axis, res, blist[:n], values[:n])
-        while True:
-            counters.zero_()
-            _lib.check(L.ishap_sparse_grow(values.data_ptr(), blist.data_ptr(), n, res, float(level), bmap.data_ptr(),
-                                           slot_map.data_ptr(), reach.data_ptr(), counters.data_ptr(), s))
-            _lib.check(L.ishap_sparse_compact(bmap.data_ptr(), res, 1, n, slot_map.data_ptr(), blist[n:].data_ptr(), N - n,
-                                              counters[1:].data_ptr(), cscratch.data_ptr(), cbytes, s))
-            changed, new = (int(c) for c in counters.tolist())     # read-back: one per growth round
-            if changed == 0 and new == 0:
-                break
-            rounds += 1
-            if rounds > max_rounds:
-                raise RuntimeError(f"extract_surface_sparse: the surface was still growing after max_rounds = {max_rounds} rounds "
-                                   f"({n} bricks active)")
-            if new:
-                if n + new > max_bricks:
-                    raise RuntimeError(f"extract_surface_sparse: round {rounds} reaches {n + new} active bricks, more than "
-                                       f"max_bricks = {max_bricks}")
-                if n + new > cap:
-                    cap = min(N, max(n + new, cap + cap // 2))
-                    grown = torch.empty((cap, 729), dtype=torch.float32, device=dev)
-                    grown[:n] = values[:n]
-                    values = grown
-                    grown = torch.zeros((cap, rbytes), dtype=torch.uint8, device=dev)
-                    grown[:n] = reach[:n]
-                    reach = grown
-                    del grown
-                td._decode_bricks_into(decoder, planes, axis, res, blist[n:n + new], values[n:n + new])
-                n += new
-        # emission order: ascending brick id, so the order of discovery does not show
-        ordered = torch.empty(n + 1, **i32)
-        _lib.check(L.ishap_sparse_compact(bmap.data_ptr(), res, 2, 0, slot_map.data_ptr(), ordered.data_ptr(), n,
-                                          counters[1:].data_ptr(), cscratch.data_ptr(), cbytes, s))
-        ebytes = int(L.ishap_sparse_surface_scratch_bytes(res, n))
-        escratch = torch.empty(ebytes, dtype=torch.uint8, device=dev)
-        counts = torch.zeros(2, **i32)
-        common = (values.data_ptr(), ordered.data_ptr(), n, res, float(level), slot_map.data_ptr(), reach.data_ptr(),
-                  escratch.data_ptr(), ebytes)
-        _lib.check(L.ishap_sparse_surface_count(*common, counts.data_ptr(), s))
-        nv, nt = (int(c) for c in counts.tolist())                 # read-back: output sizes
-        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        tris = torch.empty((nt, 3), **i32)
-        if nv and nt:
-            _lib.check(L.ishap_sparse_surface_emit(*common, verts.data_ptr(), tris.data_ptr(), s))
-        held += [values, reach, ordered, escratch, verts, tris]
+    if isinstance(seeds, str):
+        if seeds != "all":
+            raise ValueError(f'extract_surface_sparse: seeds must be a coarse volume, "all" or brick coordinates [n,3], not {seeds!r}')
+        bmap.fill_(1)
+        n0 = N
+    elif torch.is_tensor(seeds) and seeds.is_floating_point():
+        if seeds.dim() != 3 or not (seeds.shape[0] == seeds.shape[1] == seeds.shape[2]) or not 2 <= seeds.shape[0] <= SPARSE_MAX_RES:
+            raise ValueError(f"extract_surface_sparse: a coarse seed volume is [Rc,Rc,Rc] with 2 <= Rc <= {SPARSE_MAX_RES}, not {tuple(seeds.shape)}")
+        if res - 1 > SPARSE_MAX_RATIO * (seeds.shape[0] - 1):
+            raise ValueError(f"extract_surface_sparse: a coarse volume of {seeds.shape[0]}^3 seeds fine grids up to "
+                             f"{SPARSE_MAX_RATIO * (seeds.shape[0] - 1) + 1} (res - 1 <= {SPARSE_MAX_RATIO} (Rc - 1)), not {res}")
+        coarse = _lib.tensor(seeds, torch.float32, dev)
+        _lib.call(dev, "ishap_sparse_seed_volume", coarse.data_ptr(), coarse.shape[0], float(level), res, bmap.data_ptr())
+    else:
+        b = torch.as_tensor(seeds)
+        if b.is_floating_point() or b.dim() != 2 or b.shape[1] != 3:
+            raise ValueError("extract_surface_sparse: explicit seeds are an int tensor [n,3] of brick coordinates")
+        b = b.detach().to(torch.int64).cpu()
+        if b.numel() and (int(b.min()) < 0 or int(b.max()) >= nb):
+            raise ValueError(f"extract_surface_sparse: brick coordinates must lie in 0 .. {nb - 1} (res = {res})")
+        ids = torch.unique((b[:, 0] * nb + b[:, 1]) * nb + b[:, 2])
+        bmap[ids.to(dev)] = 1
+        n0 = int(ids.numel())
+    _lib.call(dev, "ishap_sparse_compact", bmap.data_ptr(), res, 0, 0, slot_map.data_ptr(), blist.data_ptr(), N,
+              counters[1:].data_ptr(), cscratch.data_ptr(), cbytes)
+    if n0 is None:
+        n0 = int(counters[1])                      # read-back: the seed count
+    empty = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), **i32))
+    if n0 == 0:
+        return empty[0], empty[1], SparseSurfaceInfo(0, 0, 0, sum(t.numel() * t.element_size() for t in held))
+    if n0 > max_bricks:
+        raise RuntimeError(f"extract_surface_sparse: the seeds name {n0} bricks, more than max_bricks = {max_bricks}")
+    n, rounds = n0, 0
+    rbytes = int(L.ishap_sparse_reach_bytes(1))
+    # values and reached bits live in buffers with room to grow: a round that adds bricks decodes them in place behind the
+    # others; a full buffer is replaced by one half as large again (a copy per growth of 1.5x, not per round)
+    cap = min(N, n + n // 4 + 16)
+    values = torch.empty((cap, 729), dtype=torch.float32, device=dev)
+    reach = torch.zeros((cap, rbytes), dtype=torch.uint8, device=dev)
+    td._decode_bricks_into(decoder, planes, axis, res, blist[:n], values[:n])
+    while True:
+        counters.zero_()
+        _lib.call(dev, "ishap_sparse_grow", values.data_ptr(), blist.data_ptr(), n, res, float(level), bmap.data_ptr(),
+                  slot_map.data_ptr(), reach.data_ptr(), counters.data_ptr())
+        _lib.call(dev, "ishap_sparse_compact", bmap.data_ptr(), res, 1, n, slot_map.data_ptr(), blist[n:].data_ptr(), N - n,
+                  counters[1:].data_ptr(), cscratch.data_ptr(), cbytes)
+        changed, new = (int(c) for c in counters.tolist())     # read-back: one per growth round
+        if changed == 0 and new == 0:
+            break
+        rounds += 1
+        if rounds > max_rounds:
+            raise RuntimeError(f"extract_surface_sparse: the surface was still growing after max_rounds = {max_rounds} rounds "
+                               f"({n} bricks active)")
+        if new:
+            if n + new > max_bricks:
+                raise RuntimeError(f"extract_surface_sparse: round {rounds} reaches {n + new} active bricks, more than "
+                                   f"max_bricks = {max_bricks}")
+            if n + new > cap:
+                cap = min(N, max(n + new, cap + cap // 2))
+                grown = torch.empty((cap, 729), dtype=torch.float32, device=dev)
+                grown[:n] = values[:n]
+                values = grown
+                grown = torch.zeros((cap, rbytes), dtype=torch.uint8, device=dev)
+                grown[:n] = reach[:n]
+                reach = grown
+                del grown
+            td._decode_bricks_into(decoder, planes, axis, res, blist[n:n + new], values[n:n + new])
+            n += new
+    # emission order: ascending brick id, so the order of discovery does not show
+    ordered = torch.empty(n + 1, **i32)
+    _lib.call(dev, "ishap_sparse_compact", bmap.data_ptr(), res, 2, 0, slot_map.data_ptr(), ordered.data_ptr(), n,
+              counters[1:].data_ptr(), cscratch.data_ptr(), cbytes)
+    escratch, ebytes = _lib.scratch(dev, "ishap_sparse_surface_scratch_bytes", res, n)
+    counts = torch.zeros(2, **i32)
+    common = (values.data_ptr(), ordered.data_ptr(), n, res, float(level), slot_map.data_ptr(), reach.data_ptr(),
+              escratch.data_ptr(), ebytes)
+    _lib.call(dev, "ishap_sparse_surface_count", *common, counts.data_ptr())
+    nv, nt = (int(c) for c in counts.tolist())                 # read-back: output sizes
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    tris = torch.empty((nt, 3), **i32)
+    if nv and nt:
+        _lib.call(dev, "ishap_sparse_surface_emit", *common, verts.data_ptr(), tris.data_ptr())
+    held += [values, reach, ordered, escratch, verts, tris]
     return verts, tris, SparseSurfaceInfo(n, rounds, 729 * n, sum(t.numel() * t.element_size() for t in held))
 
 
@@ -838,22 +816,19 @@ def mesh_winding_number(verts: torch.Tensor, tris: torch.Tensor, points: torch.T
     """Generalized winding number of `points` about the triangle mesh (ishap_mesh_winding; Jacobson et al. 2013):
     1 inside / 0 outside a closed mesh that is counter-clockwise seen from outside, -1 inside a clockwise one, and a
     smooth value in between where the surface is open.  verts [V,3], tris [F,3], points [P,3] -> [P] float32."""
-    _need_gpu(verts, "mesh_winding_number")
+    _lib.need_gpu(verts, "mesh_winding_number")
     dev = verts.device
-    v = verts.detach().to(torch.float32).contiguous()
-    t = tris.detach().to(device=dev, dtype=torch.int32).contiguous()
-    p = points.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    v = _lib.tensor(verts, torch.float32)
+    t = _lib.tensor(tris, torch.int32, dev)
+    p = _lib.tensor(points, torch.float32, dev, (-1, 3))
     w = torch.empty(p.shape[0], dtype=torch.float32, device=dev)
     if p.shape[0] == 0:
         return w
     if t.shape[0] == 0:
         raise ValueError("mesh_winding_number: the mesh has no triangles")
-    L = _lib.lib()
-    nbytes = int(L.ishap_winding_scratch_bytes(t.shape[0], p.shape[0]))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.ishap_mesh_winding(v.data_ptr(), t.data_ptr(), t.shape[0], p.data_ptr(), p.shape[0], w.data_ptr(),
-                                        scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    scratch, nbytes = _lib.scratch(dev, "ishap_winding_scratch_bytes", t.shape[0], p.shape[0])
+    _lib.call(dev, "ishap_mesh_winding", v.data_ptr(), t.data_ptr(), t.shape[0], p.data_ptr(), p.shape[0], w.data_ptr(),
+              scratch.data_ptr(), nbytes)
     return w
 
 
@@ -862,13 +837,12 @@ def cloud_areas(points: torch.Tensor, k: int = 8) -> torch.Tensor:
     (ishap_cloud_areas; brute force on the device).  points [N,3] -> [N] float32; 1 <= k <= 16, k < N."""
     if not (1 <= int(k) <= 16):
         raise ValueError(f"cloud_areas: k must be in 1..16, got {k!r}")
-    _need_gpu(points, "cloud_areas")
-    p = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    _lib.need_gpu(points, "cloud_areas")
+    p = _lib.tensor(points, torch.float32, shape=(-1, 3))
     if p.shape[0] <= int(k):
         raise ValueError(f"cloud_areas: k = {k} needs more than {k} points, got {p.shape[0]}")
     a = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        _lib.check(_lib.lib().ishap_cloud_areas(p.data_ptr(), p.shape[0], int(k), a.data_ptr(), _lib.stream_ptr(p.device)))
+    _lib.call(p.device, "ishap_cloud_areas", p.data_ptr(), p.shape[0], int(k), a.data_ptr())
     return a
 
 
@@ -886,20 +860,15 @@ def _check_cloud_k(what: str, points, k):
 def _knn_launch(p: torch.Tensor, k: int):
     idx = torch.empty((p.shape[0], k), dtype=torch.int32, device=p.device)
     d2 = torch.empty((p.shape[0], k), dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        _lib.check(_lib.lib().ishap_cloud_knn(p.data_ptr(), p.shape[0], k, idx.data_ptr(), d2.data_ptr(), _lib.stream_ptr(p.device)))
+    _lib.call(p.device, "ishap_cloud_knn", p.data_ptr(), p.shape[0], k, idx.data_ptr(), d2.data_ptr())
     return idx, d2
 
 
 def _orient_launch(p: torch.Tensor, n: torch.Tensor, idx: torch.Tensor, k: int):
     """orients n in place; (rounds, seeds)"""
-    L = _lib.lib()
-    nbytes = int(L.ishap_cloud_orient_scratch_bytes(p.shape[0]))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    scratch, nbytes = _lib.scratch(p.device, "ishap_cloud_orient_scratch_bytes", p.shape[0])
     info = (C.c_int * 2)()
-    with torch.cuda.device(p.device):
-        _lib.check(L.ishap_cloud_orient(p.data_ptr(), n.data_ptr(), idx.data_ptr(), p.shape[0], k, scratch.data_ptr(), nbytes, info,
-                                        _lib.stream_ptr(p.device)))
+    _lib.call(p.device, "ishap_cloud_orient", p.data_ptr(), n.data_ptr(), idx.data_ptr(), p.shape[0], k, scratch.data_ptr(), nbytes, info)
     return int(info[0]), int(info[1])
 
 
@@ -908,8 +877,8 @@ def cloud_knn(points: torch.Tensor, k: int = 8):
     (squared distance, index): equal distances go to the smaller index, equal points are neighbours at distance 0.
     points [N,3] -> (idx [N,k] int32, d2 [N,k] float32); 1 <= k <= 16, k < N."""
     k, _ = _check_cloud_k("cloud_knn", points, k)
-    _need_gpu(points, "cloud_knn")
-    return _knn_launch(points.detach().to(torch.float32).contiguous(), k)
+    _lib.need_gpu(points, "cloud_knn")
+    return _knn_launch(_lib.tensor(points, torch.float32), k)
 
 
 def estimate_normals(points: torch.Tensor, k: int = 12, orient: bool = True, return_info: bool = False):
@@ -921,14 +890,12 @@ def estimate_normals(points: torch.Tensor, k: int = 12, orient: bool = True, ret
     magnitude is positive), not an orientation.  return_info: also a dict with `variation` [N] (l0 / (l0 + l1 + l2), 0 on a
     plane), `rounds` and `seeds` (None without `orient`).  1 <= k <= 16, k < N."""
     k, _ = _check_cloud_k("estimate_normals", points, k)
-    _need_gpu(points, "estimate_normals")
-    p = points.detach().to(torch.float32).contiguous()
+    _lib.need_gpu(points, "estimate_normals")
+    p = _lib.tensor(points, torch.float32)
     idx, _ = _knn_launch(p, k)
     n = torch.empty_like(p)
     var = torch.empty(p.shape[0], dtype=torch.float32, device=p.device) if return_info else None
-    with torch.cuda.device(p.device):
-        _lib.check(_lib.lib().ishap_cloud_normals(p.data_ptr(), p.shape[0], idx.data_ptr(), k, n.data_ptr(), _lib.ptr(var),
-                                                 _lib.stream_ptr(p.device)))
+    _lib.call(p.device, "ishap_cloud_normals", p.data_ptr(), p.shape[0], idx.data_ptr(), k, n.data_ptr(), _lib.ptr(var))
     rounds, seeds = _orient_launch(p, n, idx, k) if orient else (None, None)
     return (n, {"variation": var, "rounds": rounds, "seeds": seeds}) if return_info else n
 
@@ -945,8 +912,8 @@ def orient_normals(points: torch.Tensor, normals: torch.Tensor, k: int = 12, ret
     length = torch.linalg.norm(n, dim=1, keepdim=True)
     if not bool((length > 0).all()):                       # also false for NaN
         raise ValueError(f"orient_normals: {int((~(length > 0)).sum())} normals are zero or not a number")
-    _need_gpu(points, "orient_normals")
-    p = points.detach().to(torch.float32).contiguous()
+    _lib.need_gpu(points, "orient_normals")
+    p = _lib.tensor(points, torch.float32)
     n = (n / length).to(p.device).contiguous()
     idx, _ = _knn_launch(p, k)
     rounds, seeds = _orient_launch(p, n, idx, k)
@@ -957,25 +924,22 @@ def cloud_winding_number(points: torch.Tensor, normals: torch.Tensor, query: tor
     """Winding number of `query` about an oriented point cloud (ishap_cloud_winding; Barill et al. 2018): about 1 inside,
     0 outside when `normals` are unit and point outward.  areas [N]: the area each point stands for, cloud_areas(points)
     when None.  points, normals [N,3], query [P,3] -> [P] float32."""
-    _need_gpu(points, "cloud_winding_number")
+    _lib.need_gpu(points, "cloud_winding_number")
     dev = points.device
-    p = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
-    n = normals.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    p = _lib.tensor(points, torch.float32, shape=(-1, 3))
+    n = _lib.tensor(normals, torch.float32, dev, (-1, 3))
     if n.shape != p.shape:
         raise ValueError(f"cloud_winding_number: {p.shape[0]} points but {n.shape[0]} normals")
-    a = cloud_areas(p) if areas is None else areas.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    a = cloud_areas(p) if areas is None else _lib.tensor(areas, torch.float32, dev, (-1,))
     if a.shape[0] != p.shape[0]:
         raise ValueError(f"cloud_winding_number: {p.shape[0]} points but {a.shape[0]} areas")
-    q = query.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    q = _lib.tensor(query, torch.float32, dev, (-1, 3))
     w = torch.empty(q.shape[0], dtype=torch.float32, device=dev)
     if q.shape[0] == 0:
         return w
-    L = _lib.lib()
-    nbytes = int(L.ishap_winding_scratch_bytes(p.shape[0], q.shape[0]))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.ishap_cloud_winding(p.data_ptr(), n.data_ptr(), a.data_ptr(), p.shape[0], q.data_ptr(), q.shape[0],
-                                         w.data_ptr(), scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    scratch, nbytes = _lib.scratch(dev, "ishap_winding_scratch_bytes", p.shape[0], q.shape[0])
+    _lib.call(dev, "ishap_cloud_winding", p.data_ptr(), n.data_ptr(), a.data_ptr(), p.shape[0], q.data_ptr(), q.shape[0],
+              w.data_ptr(), scratch.data_ptr(), nbytes)
     return w
 
 
@@ -988,18 +952,16 @@ def mesh_occupancy(verts: torch.Tensor, tris: torch.Tensor, points: torch.Tensor
     open; `orientation` (this method only, orientation_sign): "auto" negates w for a mesh whose signed volume is negative."""
     _check_choice("method", method, OCCUPANCY_METHODS)
     _check_choice("orientation", orientation, ORIENTATIONS)
-    _need_gpu(verts, "mesh_occupancy")
+    _lib.need_gpu(verts, "mesh_occupancy")
     dev = verts.device
-    v = verts.detach().to(torch.float32).contiguous()
-    t = tris.detach().to(device=dev, dtype=torch.int32).contiguous()
-    p = points.detach().to(device=dev, dtype=torch.float32).contiguous()
+    v = _lib.tensor(verts, torch.float32)
+    t = _lib.tensor(tris, torch.int32, dev)
+    p = _lib.tensor(points, torch.float32, dev)
     if method == "winding":
         w = mesh_winding_number(v, t, p)
         return ((-w if orientation_sign(v, t, orientation) < 0 else w) > 0.5).to(torch.float32)
     occ = torch.empty(p.shape[0], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_mesh_occupancy(v.data_ptr(), t.data_ptr(), t.shape[0], p.data_ptr(), p.shape[0], occ.data_ptr(),
-                                                   _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_mesh_occupancy", v.data_ptr(), t.data_ptr(), t.shape[0], p.data_ptr(), p.shape[0], occ.data_ptr())
     return occ
 
 
@@ -1010,26 +972,23 @@ def sample_surface_points(verts: torch.Tensor, tris: torch.Tensor, n: int, gener
     Above `multinomial_max` triangles (torch.multinomial's category limit, 2^24) the triangle is drawn by inverse CDF instead:
     the same distribution from ONE uniform per sample, so the samples of a given seed differ between the two branches
     (only meshes beyond 16.7 M triangles -- random-weight noise surfaces -- take the second)."""
-    _need_gpu(verts, "sample_surface_points")
+    _lib.need_gpu(verts, "sample_surface_points")
     dev = verts.device
-    v = verts.detach().to(torch.float32).contiguous()
-    t = tris.detach().to(device=dev, dtype=torch.int32).contiguous()
+    v = _lib.tensor(verts, torch.float32)
+    t = _lib.tensor(tris, torch.int32, dev)
     areas = torch.empty(t.shape[0], dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        _lib.check(L.ishap_mesh_tri_areas(v.data_ptr(), t.data_ptr(), t.shape[0], areas.data_ptr(), _lib.stream_ptr(dev)))
-        if areas.numel() <= multinomial_max:
-            idx = torch.multinomial(areas.double().cpu(), n, replacement=True, generator=generator).to(device=dev, dtype=torch.int32)
-        else:      # torch.multinomial stops at 2^24 categories (a 256^3 noise surface has 3e7 triangles): inverse CDF instead
-            cdf = torch.cumsum(areas.double().cpu(), 0)
-            u = torch.rand(n, generator=generator, dtype=torch.float64) * cdf[-1]
-            # right=True: triangle i owns [cdf[i-1], cdf[i]) -- a draw that lands ON a cdf value (u = 0 in front of leading
-            # zero-area triangles included) goes to the next triangle with area, never to a degenerate one
-            idx = torch.searchsorted(cdf, u, right=True).clamp_(max=areas.numel() - 1).to(device=dev, dtype=torch.int32)
-        uw = torch.rand((n, 2), generator=generator).to(dev).contiguous()
-        pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        _lib.check(L.ishap_mesh_points_on_tris(v.data_ptr(), t.data_ptr(), idx.data_ptr(), uw.data_ptr(), n, pts.data_ptr(),
-                                               _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_mesh_tri_areas", v.data_ptr(), t.data_ptr(), t.shape[0], areas.data_ptr())
+    if areas.numel() <= multinomial_max:
+        idx = torch.multinomial(areas.double().cpu(), n, replacement=True, generator=generator).to(device=dev, dtype=torch.int32)
+    else:      # torch.multinomial stops at 2^24 categories (a 256^3 noise surface has 3e7 triangles): inverse CDF instead
+        cdf = torch.cumsum(areas.double().cpu(), 0)
+        u = torch.rand(n, generator=generator, dtype=torch.float64) * cdf[-1]
+        # right=True: triangle i owns [cdf[i-1], cdf[i]) -- a draw that lands ON a cdf value (u = 0 in front of leading
+        # zero-area triangles included) goes to the next triangle with area, never to a degenerate one
+        idx = torch.searchsorted(cdf, u, right=True).clamp_(max=areas.numel() - 1).to(device=dev, dtype=torch.int32)
+    uw = torch.rand((n, 2), generator=generator).to(dev).contiguous()
+    pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    _lib.call(dev, "ishap_mesh_points_on_tris", v.data_ptr(), t.data_ptr(), idx.data_ptr(), uw.data_ptr(), n, pts.data_ptr())
     return pts
 
 
@@ -1180,11 +1139,10 @@ def cloud_to_mesh(points, normals=None, res: int = 256, smooth_iterations: int =
     cloud: 0.24 s at 128^3 and 1.6 s at 256^3 (1.7e12 pairs), linear in both counts -- a million-point
     cloud at 256^3 takes about 16 s.  Fitting from sample_cloud_occupancy labels needs no mesh and is the main route.
     normals=None: a cloud without normals; estimate_normals(points, k=normals_k) supplies them."""
-    _need_gpu(points, "cloud_to_mesh")
+    _lib.need_gpu(points, "cloud_to_mesh")
     dev = points.device
-    p = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
-    n = (estimate_normals(p, k=normals_k) if normals is None
-         else normals.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous())
+    p = _lib.tensor(points, torch.float32, shape=(-1, 3))
+    n = estimate_normals(p, k=normals_k) if normals is None else _lib.tensor(normals, torch.float32, dev, (-1, 3))
     a = cloud_areas(p)
     ax = torch.linspace(-1, 1, res, device=dev)
     vol = torch.empty(res ** 3, dtype=torch.float32, device=dev)

@@ -24,31 +24,18 @@ from .mesh import (OCCUPANCY_METHODS, OccupancyMesh, _check_choice, mesh_arrays,
 METRICS = ("IoU", "L2", "CD")
 
 
-def _device(device=None) -> torch.device:
-    if device is not None:
-        return torch.device(device)
-    if not torch.cuda.is_available():
-        raise RuntimeError("mesh metrics run on the GPU (libishap_hip.so); there is no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def device_mesh(mesh, device=None):
     """(vertices [V,3] float32, triangles [F,3] int32) on the device from any accepted mesh form."""
-    dev = _device(device)
+    dev = _lib.need_gpu(device, "mesh metrics", "run")
     if isinstance(mesh, str):
         v, t = read_obj(mesh)
     elif isinstance(mesh, OccupancyMesh) and mesh.vertices.device == dev:
-        return mesh.vertices.detach().float().contiguous(), mesh.triangles.detach().int().contiguous()
+        return _lib.tensor(mesh.vertices, torch.float32), _lib.tensor(mesh.triangles, torch.int32)
     elif isinstance(mesh, tuple) and all(torch.is_tensor(x) and x.device == dev for x in mesh):
-        return mesh[0].detach().float().contiguous(), mesh[1].detach().int().contiguous()
+        return _lib.tensor(mesh[0], torch.float32), _lib.tensor(mesh[1], torch.int32)
     else:
         v, t = mesh_arrays(mesh)
     return torch.from_numpy(np.ascontiguousarray(v)).to(dev), torch.from_numpy(np.ascontiguousarray(t)).to(dev)
-
-
-def _points(points, dev) -> torch.Tensor:
-    p = points if torch.is_tensor(points) else torch.from_numpy(np.asarray(points, dtype=np.float32))
-    return p.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
 
 
 def mesh_distance(verts: torch.Tensor, tris: torch.Tensor, points: torch.Tensor, sdf=True, orientation: str = "auto"):
@@ -58,47 +45,41 @@ def mesh_distance(verts: torch.Tensor, tris: torch.Tensor, points: torch.Tensor,
     meshes that are not watertight.  The closest triangle is the lowest index on exact ties."""
     winding = sdf is not True and sdf is not False and int(sdf) == 2
     dev = verts.device
-    v = verts.detach().to(torch.float32).contiguous()
-    t = tris.detach().to(device=dev, dtype=torch.int32).contiguous()
-    p = _points(points, dev)
+    v = _lib.tensor(verts, torch.float32)
+    t = _lib.tensor(tris, torch.int32, dev)
+    p = _lib.tensor(points, torch.float32, dev, (-1, 3))
     dist = torch.empty(p.shape[0], dtype=torch.float32, device=dev)
     tri = torch.empty(p.shape[0], dtype=torch.int32, device=dev)
     if p.shape[0] == 0:
         return dist, tri
     if t.shape[0] == 0:
         raise ValueError("mesh_distance: the mesh has no triangles")
-    L = _lib.lib()
     mode = 2 * orientation_sign(v, t, orientation) if winding else int(bool(sdf))
-    nbytes = int(L.ishap_mesh_distance_scratch_bytes_sdf(t.shape[0], p.shape[0], mode))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.ishap_mesh_distance(v.data_ptr(), t.data_ptr(), t.shape[0], p.data_ptr(), p.shape[0], mode,
-                                         dist.data_ptr(), tri.data_ptr(), scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    scratch, nbytes = _lib.scratch(dev, "ishap_mesh_distance_scratch_bytes_sdf", t.shape[0], p.shape[0], mode)
+    _lib.call(dev, "ishap_mesh_distance", v.data_ptr(), t.data_ptr(), t.shape[0], p.data_ptr(), p.shape[0], mode,
+              dist.data_ptr(), tri.data_ptr(), scratch.data_ptr(), nbytes)
     return dist, tri
 
 
 def field_stats(fa: torch.Tensor, fb: torch.Tensor, groups: int, occupancy: bool = False) -> torch.Tensor:
     """ishap_group_field_stats: fa, fb [groups * P] on the device -> [2 groups + 2]: per-group IoU, per-group mean squared
     difference, then the means of both over the groups (inside: < 0, or != 0 for occupancy)."""
-    a = fa.detach().to(torch.float32).contiguous()
-    b = fb.detach().to(device=a.device, dtype=torch.float32).contiguous()
+    a = _lib.tensor(fa, torch.float32)
+    b = _lib.tensor(fb, torch.float32, a.device)
     assert a.numel() == b.numel() and a.numel() % groups == 0 and a.numel() > 0
     out = torch.empty(2 * groups + 2, dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.lib().ishap_group_field_stats(a.data_ptr(), b.data_ptr(), groups, a.numel() // groups, int(bool(occupancy)),
-                                                      out.data_ptr(), _lib.stream_ptr(a.device)))
+    _lib.call(a.device, "ishap_group_field_stats", a.data_ptr(), b.data_ptr(), groups, a.numel() // groups, int(bool(occupancy)),
+              out.data_ptr())
     return out
 
 
 def hausdorff_sq(pa: torch.Tensor, pb: torch.Tensor):
     """(max over a of min_b |a-b|^2, max over b of min_a |a-b|^2, per-point minima [na + nb]) of two device point sets."""
-    a = _points(pa, pa.device)
-    b = _points(pb, a.device)
+    a = _lib.tensor(pa, torch.float32, pa.device, (-1, 3))
+    b = _lib.tensor(pb, torch.float32, a.device, (-1, 3))
     nearest = torch.empty(a.shape[0] + b.shape[0], dtype=torch.float32, device=a.device)
     out2 = torch.empty(2, dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.lib().ishap_hausdorff(a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], nearest.data_ptr(),
-                                              out2.data_ptr(), _lib.stream_ptr(a.device)))
+    _lib.call(a.device, "ishap_hausdorff", a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], nearest.data_ptr(), out2.data_ptr())
     d = out2.tolist()
     return d[0], d[1], nearest
 
@@ -112,7 +93,7 @@ def calc_implicit_field(mesh, points, sdf: bool = True, device=None, sign: str =
     Returns a [P] float32 device tensor."""
     _check_choice("sign", sign, OCCUPANCY_METHODS)
     v, t = device_mesh(mesh, device)
-    p = _points(points, v.device)
+    p = _lib.tensor(points, torch.float32, v.device, (-1, 3))
     if sdf:
         return mesh_distance(v, t, p, sdf=2 if sign == "winding" else True)[0]
     return mesh_occupancy(v, t, p, method=sign)
@@ -184,7 +165,7 @@ def calc_local_distance(mesh_a, mesh_b, points_a, points_b, r: float, point_num:
     va, ta = device_mesh(mesh_a, device)
     vb, tb = device_mesh(mesh_b, va.device)
     dev = va.device
-    ha, hb = _points(pa, dev), _points(pb, dev)
+    ha, hb = _lib.tensor(pa, torch.float32, dev, (-1, 3)), _lib.tensor(pb, torch.float32, dev, (-1, 3))
     G = ha.shape[0]
     g = torch.Generator(device="cpu").manual_seed(seed)
     offs = ((torch.rand((point_num, 3), generator=g) * 2 - 1) * r).to(dev)
@@ -205,7 +186,7 @@ def calc_mesh_points_normals(mesh, pcd=None, seed: int = 0, device=None) -> dict
     if pcd is None:
         pts = sample_surface_points(v, t, 2048, torch.Generator(device="cpu").manual_seed(seed))
     else:
-        pts = _points(pcd.points if hasattr(pcd, "points") else pcd, dev)
+        pts = _lib.tensor(pcd.points if hasattr(pcd, "points") else pcd, torch.float32, dev, (-1, 3))
     _, tri = mesh_distance(v, t, pts, sdf=False)
     f = t[tri.long()].long()
     n = torch.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]], dim=1)

@@ -188,7 +188,6 @@ def _plane_map(keep, free, W, keep_weight, free_weight, dilate, device, falloff,
         raise ValueError(f"the Voxels grids of keep and free must have one size ({kD} and {fD})")
     D = kD or fD
     recs = kp + fp
-    L = _lib.lib()
     prims = None
     if recs:
         arr = (_lib.RegionPrimC * len(recs))()
@@ -198,23 +197,20 @@ def _plane_map(keep, free, W, keep_weight, free_weight, dilate, device, falloff,
         prims = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
     out = torch.empty((3, W, W), dtype=torch.uint8 if marks else torch.float32, device=dev)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
-    nbytes = int((L.ishap_region_plane_feather_scratch_bytes if falloff > 0 else L.ishap_region_plane_weights_scratch_bytes)(W))
+    nbytes = int(getattr(_lib.lib(), f"ishap_region_plane_{'feather' if falloff > 0 else 'weights'}_scratch_bytes")(W))
     if nbytes <= 0:
         raise ValueError(f"plane_weights: W = {W} is out of range")
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     region = (_lib.ptr(prims), len(recs), _lib.ptr(kgrid), _lib.ptr(fgrid), D, W, dilate)
-    with torch.cuda.device(dev):
-        if marks:
-            _lib.check(L.ishap_region_plane_marks(*region, out.data_ptr(), counts.data_ptr(), scratch.data_ptr(), nbytes,
-                                                  _lib.stream_ptr(dev)))
-        elif falloff > 0:
-            table = torch.from_numpy(falloff_table(falloff)).to(dev)                # uploaded with the call
-            _lib.check(L.ishap_region_plane_feather(*region, keep_weight, free_weight, table.data_ptr(), table.numel(),
-                                                    out.data_ptr(), counts.data_ptr(), scratch.data_ptr(), nbytes,
-                                                    _lib.stream_ptr(dev)))
-        else:
-            _lib.check(L.ishap_region_plane_weights(*region, keep_weight, free_weight, out.data_ptr(), counts.data_ptr(),
-                                                    scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    if marks:
+        _lib.call(dev, "ishap_region_plane_marks", *region, out.data_ptr(), counts.data_ptr(), scratch.data_ptr(), nbytes)
+    elif falloff > 0:
+        table = torch.from_numpy(falloff_table(falloff)).to(dev)                # uploaded with the call
+        _lib.call(dev, "ishap_region_plane_feather", *region, keep_weight, free_weight, table.data_ptr(), table.numel(),
+                  out.data_ptr(), counts.data_ptr(), scratch.data_ptr(), nbytes)
+    else:
+        _lib.call(dev, "ishap_region_plane_weights", *region, keep_weight, free_weight, out.data_ptr(), counts.data_ptr(),
+                  scratch.data_ptr(), nbytes)
     nk, nf = (int(v) for v in counts.cpu())
     for region, name, n in ((keep, "keep", nk), (free, "free", nf)):
         if _as_list(region, name) and n == 0:
@@ -398,9 +394,8 @@ def select_part(volume: torch.Tensor, within, level: float = 0.0, point=None, co
         prims = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
     out = torch.empty((D, D, D), dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_region_select(vol.data_ptr(), D, float(level), _lib.ptr(prims), len(recs), _lib.ptr(grid),
-                                                  out.data_ptr(), count.data_ptr(), _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_region_select", vol.data_ptr(), D, float(level), _lib.ptr(prims), len(recs), _lib.ptr(grid), out.data_ptr(),
+              count.data_ptr())
     if int(count.cpu()) == 0:
         raise ValueError("select_part: the selection is empty: no voxel of the shape lies in the region")
     sel = out.view(torch.bool)
@@ -512,16 +507,14 @@ def handle_voxels(part: Voxels, n: int, start_voxel=None):
             raise ValueError(f"sample_handles: the start voxel {st} lies outside the grid of size {D}")
         st = (C.c_int * 3)(*st)
     dev = grid.device
-    L = _lib.lib()
-    nbytes = int(L.ishap_region_handles_scratch_bytes(D, n))
+    nbytes = int(_lib.lib().ishap_region_handles_scratch_bytes(D, n))
     if nbytes <= 0:
         raise ValueError(f"sample_handles: D = {D}, n = {n} is out of range")
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     picks = torch.empty((n, 3), dtype=torch.int32, device=dev)
     tail = torch.empty(n + 1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.ishap_region_handles(grid.data_ptr(), D, n, st, picks.data_ptr(), tail.data_ptr(), tail[n:].data_ptr(),
-                                          scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_region_handles", grid.data_ptr(), D, n, st, picks.data_ptr(), tail.data_ptr(), tail[n:].data_ptr(),
+              scratch.data_ptr(), nbytes)
     return picks, tail
 
 
@@ -553,8 +546,7 @@ def transform_region(part: Voxels, rigid: Rigid) -> Voxels:
     out = torch.empty((D, D, D), dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     args = (C.c_double * 15)(*rigid.matrix.reshape(-1), *rigid.pivot, *rigid.translation)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_region_transform(grid.data_ptr(), D, args, out.data_ptr(), count.data_ptr(), _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_region_transform", grid.data_ptr(), D, args, out.data_ptr(), count.data_ptr())
     if int(count.cpu()) == 0:
         raise ValueError("transform_region: the moved region is empty: the motion takes the part out of [-1, 1]^3 (or the part is empty)")
     return Voxels(out.view(torch.bool))

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .mesh import OccupancyMesh
-from .metrics import _device, device_mesh
+from .metrics import device_mesh
 
 MESH_COLOUR = (0.7, 0.7, 0.7)
 RED, BLUE, GREEN = (1.0, 0.0, 0.0), (0.0, 0.0, 1.0), (0.0, 1.0, 0.0)      # main.py:513, 516, 550
@@ -96,7 +96,7 @@ def render_mesh(mesh_or_parts, camera: Camera, width: int, height: int, device=N
     """Renders a mesh (anything mesh.mesh_arrays accepts, or an OBJ path), or a LIST of (mesh, colour, lit) parts
     (colour: r, g, b in [0, 1]; lit parts are shaded with their area-weighted vertex normals, unlit ones are painted flat),
     in one call: the parts are concatenated, `tri_id` counts through them in order."""
-    dev = _device(device)
+    dev = _lib.need_gpu(device, "mesh metrics", "run")
     parts = mesh_or_parts if isinstance(mesh_or_parts, list) else [(mesh_or_parts, MESH_COLOUR, True)]
     vs, ts, ns, ids, table, base = [], [], [], [], [], 0
     for k, (m, colour, lit) in enumerate(parts):
@@ -117,42 +117,37 @@ def render_arrays(verts: torch.Tensor, tris: torch.Tensor, camera: Camera, width
                   tri_part=None, parts=None) -> RenderResult:
     """ishap_render_mesh on device arrays: verts [V,3] float32, tris [F,3] int32, normals [V,3] or None (flat face normals),
     tri_part [F] int32 or None, parts [P,4] (r, g, b, lit) or None (one lit grey part)."""
-    if not verts.is_cuda:
-        raise RuntimeError("render runs on the GPU (libishap_hip.so); there is no CPU fallback")
-    dev = verts.device
+    dev = _lib.need_gpu(verts, "render")
     width, height = int(width), int(height)
-    v = verts.detach().to(torch.float32).reshape(-1, 3).contiguous()
-    t = tris.detach().to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
-    nrm = None if normals is None else normals.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    tp = None if tri_part is None else tri_part.detach().to(device=dev, dtype=torch.int32).contiguous()
+    v = _lib.tensor(verts, torch.float32, shape=(-1, 3))
+    t = _lib.tensor(tris, torch.int32, dev, (-1, 3))
+    nrm = None if normals is None else _lib.tensor(normals, torch.float32, dev, (-1, 3))
+    tp = None if tri_part is None else _lib.tensor(tri_part, torch.int32, dev)
     if parts is None:
         parts = torch.tensor([[*MESH_COLOUR, 1.0]], dtype=torch.float32, device=dev)
-    pt = parts.detach().to(device=dev, dtype=torch.float32).reshape(-1, 4).contiguous()
+    pt = _lib.tensor(parts, torch.float32, dev, (-1, 4))
     if nrm is not None and nrm.shape != v.shape:
         raise ValueError(f"normals {tuple(nrm.shape)} do not match vertices {tuple(v.shape)}")
     if tp is not None and tp.shape[0] != t.shape[0]:
         raise ValueError(f"tri_part has {tp.shape[0]} entries for {t.shape[0]} triangles")
-    L = _lib.lib()
-    nbytes = int(L.ishap_render_scratch_bytes(v.shape[0], t.shape[0], width, height))
-    if nbytes < 0:
-        raise ValueError(f"render: invalid sizes ({v.shape[0]} vertices, {t.shape[0]} triangles, {width} x {height})")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    try:
+        scratch, nbytes = _lib.scratch(dev, "ishap_render_scratch_bytes", v.shape[0], t.shape[0], width, height)
+    except _lib.ScratchError:
+        raise ValueError(f"render: invalid sizes ({v.shape[0]} vertices, {t.shape[0]} triangles, {width} x {height})") from None
     rgb = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
     depth = torch.empty((height, width), dtype=torch.float32, device=dev)
     tri_id = torch.empty((height, width), dtype=torch.int32, device=dev)
     cam = camera._c()
-    with torch.cuda.device(dev):
-        _lib.check(L.ishap_render_mesh(_lib.ptr(v) if v.shape[0] else None, v.shape[0], _lib.ptr(t) if t.shape[0] else None,
-                                       t.shape[0], _lib.ptr(nrm), _lib.ptr(tp) if tp is not None and tp.shape[0] else None,
-                                       pt.data_ptr(), pt.shape[0], C.byref(cam), width, height, scratch.data_ptr(), nbytes,
-                                       rgb.data_ptr(), depth.data_ptr(), tri_id.data_ptr(), _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_render_mesh", _lib.ptr(v) if v.shape[0] else None, v.shape[0], _lib.ptr(t) if t.shape[0] else None,
+              t.shape[0], _lib.ptr(nrm), _lib.ptr(tp) if tp is not None and tp.shape[0] else None, pt.data_ptr(), pt.shape[0],
+              C.byref(cam), width, height, scratch.data_ptr(), nbytes, rgb.data_ptr(), depth.data_ptr(), tri_id.data_ptr())
     return RenderResult(rgb, depth, tri_id)
 
 
 def unproject(camera: Camera, x, y, depth, width: int, height: int, device=None) -> torch.Tensor:
     """camera.unproject(x, y, depth, width, height): the world point of pixel (x, y) -- its centre -- at `depth`.  Scalars
     give a [3] tensor, arrays of n values an [n, 3] tensor, float32 on the device."""
-    dev = _device(device)
+    dev = _lib.need_gpu(device, "mesh metrics", "run")
     scalar = np.ndim(x) == 0 and np.ndim(y) == 0 and np.ndim(depth) == 0
 
     def host(a):
@@ -161,9 +156,8 @@ def unproject(camera: Camera, x, y, depth, width: int, height: int, device=None)
     d_xyd = torch.from_numpy(np.ascontiguousarray(xyd)).to(dev)
     world = torch.empty((xyd.shape[0], 3), dtype=torch.float32, device=dev)
     cam = camera._c()
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_unproject(C.byref(cam), int(width), int(height), _lib.ptr(d_xyd) if xyd.shape[0] else None,
-                                              xyd.shape[0], _lib.ptr(world) if xyd.shape[0] else None, _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_unproject", C.byref(cam), int(width), int(height), _lib.ptr(d_xyd) if xyd.shape[0] else None,
+              xyd.shape[0], _lib.ptr(world) if xyd.shape[0] else None)
     return world[0] if scalar else world
 
 

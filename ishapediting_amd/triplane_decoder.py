@@ -77,7 +77,7 @@ class _Net:
                 v = sd[k]
                 if tuple(v.shape) != tuple(shape):
                     raise RuntimeError(f"size mismatch for {k}")
-                self.sd[k] = v.detach().to(device=self.device, dtype=torch.float32).contiguous()
+                self.sd[k] = _lib.tensor(v, torch.float32, self.device)
         self.loaded = True
 
     def state_dict(self):
@@ -120,9 +120,7 @@ class MultiTriplane:
         S = e[0].shape[-1]
         latent = torch.cat([t.reshape(1, 32, S, S) for t in e], dim=1).to(device=self.device, dtype=torch.float32).contiguous()
         planes = torch.empty((3, S, S, 32), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().ishap_planes_prepare(latent.data_ptr(), None, None, S, planes.data_ptr(),
-                                                       _lib.stream_ptr(self.device)))
+        _lib.call(self.device, "ishap_planes_prepare", latent.data_ptr(), None, None, S, planes.data_ptr())
         return planes
 
     def forward(self, obj_idx: int, coordinates: torch.Tensor, debug: bool = False) -> torch.Tensor:
@@ -130,13 +128,11 @@ class MultiTriplane:
         b, n, d = coordinates.shape
         assert d == 3
         planes = self._planes(obj_idx)
-        coords = coordinates.detach().to(device=self.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+        coords = _lib.tensor(coordinates, torch.float32, self.device, (-1, 3))
         out = torch.empty(coords.shape[0], dtype=torch.float32, device=self.device)
         w = self.net.weights_c()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().ishap_triplane_decode_points(planes.data_ptr(), planes.shape[1], C.byref(w),
-                                                               coords.data_ptr(), coords.shape[0], out.data_ptr(),
-                                                               _lib.stream_ptr(self.device)))
+        _lib.call(self.device, "ishap_triplane_decode_points", planes.data_ptr(), planes.shape[1], C.byref(w), coords.data_ptr(),
+                  coords.shape[0], out.data_ptr())
         return out.reshape(b, n, 1)
 
     __call__ = forward
@@ -152,8 +148,8 @@ class MultiTriplane:
     def points_loss_grad(self, planes: torch.Tensor, coords: torch.Tensor, gt: torch.Tensor):
         """drag_utils.py:455-458 on explicit planes: loss = -BCEWithLogitsLoss()(decoder(coords), gt) and
         d loss / d planes ([3,S,S,32]); also returns the logits."""
-        coords = coords.detach().to(device=self.device, dtype=torch.float32).reshape(-1, 3).contiguous()
-        gt = gt.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        coords = _lib.tensor(coords, torch.float32, self.device, (-1, 3))
+        gt = _lib.tensor(gt, torch.float32, self.device, (-1,))
         assert coords.shape[0] == gt.shape[0]
         sd = self.net.sd
         w1t, w2t = sd["1.weight"].t().contiguous(), sd["3.weight"].t().contiguous()
@@ -161,11 +157,9 @@ class MultiTriplane:
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         logits = torch.empty(coords.shape[0], dtype=torch.float32, device=self.device)
         w = self.net.weights_c()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().ishap_triplane_points_loss_grad(
-                planes.data_ptr(), planes.shape[1], C.byref(w), w1t.data_ptr(), w2t.data_ptr(), coords.data_ptr(),
-                gt.data_ptr(), coords.shape[0], dplanes.data_ptr(), loss.data_ptr(), logits.data_ptr(),
-                _lib.stream_ptr(self.device)))
+        _lib.call(self.device, "ishap_triplane_points_loss_grad",
+                  planes.data_ptr(), planes.shape[1], C.byref(w), w1t.data_ptr(), w2t.data_ptr(), coords.data_ptr(),
+                  gt.data_ptr(), coords.shape[0], dplanes.data_ptr(), loss.data_ptr(), logits.data_ptr())
         return loss, dplanes, logits
 
     def constraint_setup(self, coords: torch.Tensor, targets: torch.Tensor, weights: torch.Tensor, S: int) -> "ConstraintState":
@@ -174,16 +168,16 @@ class MultiTriplane:
         positive sum (summed here in double: the one host read)."""
         dev = self.device
         f32 = dict(device=dev, dtype=torch.float32)
-        coords = coords.detach().to(**f32).reshape(-1, 3).contiguous()
-        targets = targets.detach().to(**f32).reshape(-1).contiguous()
-        weights = weights.detach().to(**f32).reshape(-1).contiguous()
+        coords = _lib.tensor(coords, torch.float32, dev, (-1, 3))
+        targets = _lib.tensor(targets, torch.float32, dev, (-1,))
+        weights = _lib.tensor(weights, torch.float32, dev, (-1,))
         M, S = coords.shape[0], int(S)
         if targets.shape[0] != M or weights.shape[0] != M:
             raise ValueError(f"constraint_setup: {M} points, {targets.shape[0]} targets, {weights.shape[0]} weights")
-        L = _lib.lib()
-        nbytes = int(L.ishap_constraint_setup_scratch_bytes(M, S))
-        if nbytes < 0:
-            raise ValueError(f"constraint_setup: M = {M}, S = {S} is outside 1 <= M <= 2^20, 2 <= S <= 1024")
+        try:
+            scratch, nbytes = _lib.scratch(dev, "ishap_constraint_setup_scratch_bytes", M, S)
+        except _lib.ScratchError:
+            raise ValueError(f"constraint_setup: M = {M}, S = {S} is outside 1 <= M <= 2^20, 2 <= S <= 1024") from None
         if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
             raise ValueError("constraint_setup: weights must be finite and >= 0")
         wsum = float(weights.double().sum())
@@ -192,10 +186,8 @@ class MultiTriplane:
         row_start = torch.empty(3 * S * S + 1, dtype=torch.int32, device=dev)
         entry = torch.empty(12 * M, dtype=torch.int32, device=dev)
         entry_w = torch.empty(12 * M, **f32)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.ishap_constraint_setup(coords.data_ptr(), M, S, row_start.data_ptr(), entry.data_ptr(), entry_w.data_ptr(),
-                                                scratch.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+        _lib.call(dev, "ishap_constraint_setup", coords.data_ptr(), M, S, row_start.data_ptr(), entry.data_ptr(), entry_w.data_ptr(),
+                  scratch.data_ptr(), nbytes)
         return ConstraintState(coords, targets, weights, wsum, S, row_start, entry, entry_w,
                                torch.empty((M, 32), **f32), torch.empty((M + 31) // 32, **f32))
 
@@ -213,12 +205,10 @@ class MultiTriplane:
         assert dplanes.is_contiguous() and dplanes.shape == planes.shape and dplanes.dtype == torch.float32
         assert logits is None or (logits.dtype == torch.float32 and logits.numel() == state.M and logits.is_contiguous())
         w = self.net.weights_c()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ishap_constraint_loss_grad(
-                planes.data_ptr(), state.S, C.byref(w), state.coords.data_ptr(), state.targets.data_ptr(), state.weights.data_ptr(),
-                state.M, state.wsum, state.row_start.data_ptr(), state.entry.data_ptr(), state.entry_w.data_ptr(),
-                state.dfeat.data_ptr(), state.partials.data_ptr(), dplanes.data_ptr(), loss.data_ptr(), _lib.ptr(logits),
-                _lib.stream_ptr(dev)))
+        _lib.call(dev, "ishap_constraint_loss_grad",
+                  planes.data_ptr(), state.S, C.byref(w), state.coords.data_ptr(), state.targets.data_ptr(), state.weights.data_ptr(),
+                  state.M, state.wsum, state.row_start.data_ptr(), state.entry.data_ptr(), state.entry_w.data_ptr(),
+                  state.dfeat.data_ptr(), state.partials.data_ptr(), dplanes.data_ptr(), loss.data_ptr(), _lib.ptr(logits))
         return loss, dplanes, logits
 
     def fit_loss_grad(self, planes: torch.Tensor, coords: torch.Tensor, gt: torch.Tensor, idx: torch.Tensor,
@@ -230,11 +220,11 @@ class MultiTriplane:
         tensors) and returns (loss_parts, dplanes).  One kernel launch, no host synchronisation."""
         dev = self.device
         f32 = dict(device=dev, dtype=torch.float32)
-        coords = coords.detach().to(**f32).reshape(-1, 3).contiguous()
-        gt = gt.detach().to(**f32).reshape(-1).contiguous()
-        idx = idx.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-        rc = rand_coords.detach().to(**f32).reshape(-1, 3).contiguous()
-        rn = rand_noise.detach().to(**f32).reshape(-1, 3).contiguous()
+        coords = _lib.tensor(coords, torch.float32, dev, (-1, 3))
+        gt = _lib.tensor(gt, torch.float32, dev, (-1,))
+        idx = _lib.tensor(idx, torch.int32, dev, (-1,))
+        rc = _lib.tensor(rand_coords, torch.float32, dev, (-1, 3))
+        rn = _lib.tensor(rand_noise, torch.float32, dev, (-1, 3))
         assert coords.shape[0] == gt.shape[0] and rc.shape == rn.shape
         assert planes.dtype == torch.float32 and planes.is_contiguous() and planes.shape[0] == 3 and planes.shape[3] == 32
         if dplanes is None:
@@ -242,11 +232,9 @@ class MultiTriplane:
         if loss_parts is None:
             loss_parts = torch.zeros(2, **f32)
         w = self.net.weights_c()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ishap_triplane_fit_loss_grad(
-                planes.data_ptr(), planes.shape[1], C.byref(w), coords.data_ptr(), gt.data_ptr(), idx.data_ptr(), idx.numel(),
-                rc.data_ptr(), rn.data_ptr(), rc.shape[0], float(pair_weight), dplanes.data_ptr(), loss_parts.data_ptr(),
-                _lib.stream_ptr(dev)))
+        _lib.call(dev, "ishap_triplane_fit_loss_grad",
+                  planes.data_ptr(), planes.shape[1], C.byref(w), coords.data_ptr(), gt.data_ptr(), idx.data_ptr(), idx.numel(),
+                  rc.data_ptr(), rn.data_ptr(), rc.shape[0], float(pair_weight), dplanes.data_ptr(), loss_parts.data_ptr())
         return loss_parts, dplanes
 
     def _reg_values(self) -> torch.Tensor:
@@ -270,7 +258,7 @@ def prepare_planes(latent: torch.Tensor, rng: Optional[torch.Tensor], mid: Optio
     assert latent.shape[0] == 1 and latent.shape[1] == 96
     dev = latent.device
     S = latent.shape[-1]
-    latent = latent.detach().to(dtype=torch.float32).contiguous()
+    latent = _lib.tensor(latent, torch.float32)
 
     def vec(v, default):
         if v is None:
@@ -281,9 +269,7 @@ def prepare_planes(latent: torch.Tensor, rng: Optional[torch.Tensor], mid: Optio
         return None if float(v) == default else torch.full((96,), float(v), dtype=torch.float32, device=dev)
     r, m = vec(rng, 1.0), vec(mid, 0.0)
     planes = torch.empty((3, S, S, 32), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_planes_prepare(latent.data_ptr(), _lib.ptr(r), _lib.ptr(m), S, planes.data_ptr(),
-                                                   _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_planes_prepare", latent.data_ptr(), _lib.ptr(r), _lib.ptr(m), S, planes.data_ptr())
     return planes
 
 
@@ -293,9 +279,7 @@ def decode_planes_grid(decoder: MultiTriplane, planes: torch.Tensor, res: int) -
     axis = torch.linspace(-1, 1, res).to(dev)          # same values the reference builds on the host (:79-81)
     vol = torch.empty((res, res, res), dtype=torch.float32, device=dev)
     w = decoder.net.weights_c()
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_triplane_decode_grid(planes.data_ptr(), planes.shape[1], C.byref(w), axis.data_ptr(),
-                                                         res, vol.data_ptr(), _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_triplane_decode_grid", planes.data_ptr(), planes.shape[1], C.byref(w), axis.data_ptr(), res, vol.data_ptr())
     return vol
 
 
@@ -306,10 +290,9 @@ def decode_bricks(decoder: MultiTriplane, planes: torch.Tensor, res: int, bricks
     (ishap_triplane_decode_bricks; mesh.extract_surface_sparse is its user)."""
     dev = planes.device
     res = int(res)
-    ids = bricks.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    ids = _lib.tensor(bricks, torch.int32, dev, (-1,))
     n = int(ids.shape[0])
-    L = _lib.lib()
-    nb = int(L.ishap_sparse_bricks_per_axis(res))
+    nb = int(_lib.lib().ishap_sparse_bricks_per_axis(res))
     if nb < 0:
         raise ValueError(f"decode_bricks: res = {res} is outside 9 .. 2048")
     if n == 0:
@@ -324,9 +307,8 @@ def decode_bricks(decoder: MultiTriplane, planes: torch.Tensor, res: int, bricks
 def _decode_bricks_into(decoder: MultiTriplane, planes: torch.Tensor, axis: torch.Tensor, res: int, ids: torch.Tensor, out: torch.Tensor):
     """ishap_triplane_decode_bricks on checked arguments: ids int32 [n] (n >= 1) -> out float32 [n,9,9,9], both contiguous"""
     w = decoder.net.weights_c()
-    with torch.cuda.device(planes.device):
-        _lib.check(_lib.lib().ishap_triplane_decode_bricks(planes.data_ptr(), planes.shape[1], C.byref(w), axis.data_ptr(), res,
-                                                           ids.data_ptr(), ids.shape[0], out.data_ptr(), _lib.stream_ptr(planes.device)))
+    _lib.call(planes.device, "ishap_triplane_decode_bricks", planes.data_ptr(), planes.shape[1], C.byref(w), axis.data_ptr(), res,
+              ids.data_ptr(), ids.shape[0], out.data_ptr())
 
 
 def decode_volume(decoder: MultiTriplane, latent: torch.Tensor, rng, mid, res: int) -> torch.Tensor:
@@ -336,7 +318,7 @@ def decode_volume(decoder: MultiTriplane, latent: torch.Tensor, rng, mid, res: i
 
 def _field_inputs(decoder: MultiTriplane, planes: torch.Tensor, coords: torch.Tensor):
     assert planes.dtype == torch.float32 and planes.is_contiguous() and planes.dim() == 4 and planes.shape[0] == 3 and planes.shape[3] == 32
-    c = coords.detach().to(device=planes.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+    c = _lib.tensor(coords, torch.float32, planes.device, (-1, 3))
     if c.shape[0] == 0:
         raise ValueError("the decoder's field needs at least one point")
     return c, decoder.net.weights_c()
@@ -350,9 +332,8 @@ def field_grad_planes(decoder: MultiTriplane, planes: torch.Tensor, coords: torc
     c, w = _field_inputs(decoder, planes, coords)
     logits = torch.empty(c.shape[0], dtype=torch.float32, device=dev)
     grad = torch.empty((c.shape[0], 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_triplane_field_grad(planes.data_ptr(), planes.shape[1], C.byref(w), c.data_ptr(), c.shape[0],
-                                                        logits.data_ptr(), grad.data_ptr(), _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_triplane_field_grad", planes.data_ptr(), planes.shape[1], C.byref(w), c.data_ptr(), c.shape[0],
+              logits.data_ptr(), grad.data_ptr())
     return FieldGrad(logits, grad)
 
 
@@ -370,11 +351,9 @@ def project_to_surface(decoder: MultiTriplane, planes: torch.Tensor, coords: tor
     n = c.shape[0]
     out = Projection(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
                      torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_triplane_project(planes.data_ptr(), planes.shape[1], C.byref(w), c.data_ptr(), n, int(iterations),
-                                                     float(step_max), float(max_move), float(tol), float(gmin), out.points.data_ptr(),
-                                                     out.logits.data_ptr(), out.normals.data_ptr(), out.accepted.data_ptr(),
-                                                     _lib.stream_ptr(dev)))
+    _lib.call(dev, "ishap_triplane_project", planes.data_ptr(), planes.shape[1], C.byref(w), c.data_ptr(), n, int(iterations),
+              float(step_max), float(max_move), float(tol), float(gmin), out.points.data_ptr(), out.logits.data_ptr(),
+              out.normals.data_ptr(), out.accepted.data_ptr())
     return out
 
 
@@ -383,10 +362,8 @@ def reg_values(planes: torch.Tensor) -> torch.Tensor:
     dev = planes.device
     out = torch.empty(2, dtype=torch.float32, device=dev)
     ws = torch.empty(REG_WS, dtype=torch.float64, device=dev)
-    planes = planes.detach().to(dtype=torch.float32).contiguous()
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ishap_triplane_reg_values(planes.data_ptr(), planes.shape[1], ws.data_ptr(), out.data_ptr(),
-                                                        _lib.stream_ptr(dev)))
+    planes = _lib.tensor(planes, torch.float32)
+    _lib.call(dev, "ishap_triplane_reg_values", planes.data_ptr(), planes.shape[1], ws.data_ptr(), out.data_ptr())
     return out
 
 
@@ -411,12 +388,10 @@ class TriplaneAdam:
 
     def step(self, reg_parts: Optional[torch.Tensor] = None):
         """One Adam step; `reg_parts` (device float[2] or None) receives {l2reg, tvreg} of the planes before the step."""
-        dev = self.planes.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ishap_triplane_reg_adam_step(
-                self.planes.data_ptr(), self._spare.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.dplanes.data_ptr(),
-                self.planes.shape[1], self.step_count.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                self.l2_weight, self.tv_weight, self.ws.data_ptr(), _lib.ptr(reg_parts), _lib.stream_ptr(dev)))
+        _lib.call(self.planes.device, "ishap_triplane_reg_adam_step",
+                  self.planes.data_ptr(), self._spare.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.dplanes.data_ptr(),
+                  self.planes.shape[1], self.step_count.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
+                  self.l2_weight, self.tv_weight, self.ws.data_ptr(), _lib.ptr(reg_parts))
         self.planes, self._spare = self._spare, self.planes
         return self.planes
 
@@ -444,8 +419,8 @@ def fit_triplanes(decoder: MultiTriplane, points: torch.Tensor, occupancies: tor
     Returns (planes [3,S,S,32], losses [steps, 4] = (bce, mse, l2reg, tvreg) per step, on the device).  The host never
     waits on the device inside the loop."""
     dev = decoder.device
-    points = torch.as_tensor(points).detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    occupancies = torch.as_tensor(occupancies).detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    points = _lib.tensor(points, torch.float32, dev, (-1, 3))
+    occupancies = _lib.tensor(occupancies, torch.float32, dev, (-1,))
     n = points.shape[0]
     assert occupancies.shape[0] == n
     sched = batch_schedule(n, batch_size)

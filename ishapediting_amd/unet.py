@@ -33,7 +33,7 @@ class UNetModel:
         self.model_channels = cfg.model_channels
         self.dtype = torch.float16
         self.max_batch = max_batch
-        L = _lib.lib()
+        self._L = _lib.lib()
         c = _lib.UNetConfigC()
         c.image_size, c.in_channels, c.model_channels = cfg.image_size, cfg.in_channels, cfg.model_channels
         c.out_channels, c.num_res_blocks = cfg.out_channels, cfg.num_res_blocks
@@ -50,15 +50,17 @@ class UNetModel:
         c.num_head_channels = cfg.num_head_channels
         c.max_batch = max_batch
         h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(L.ishap_unet_create(C.byref(c), self.device.index or 0, C.byref(h)))
+        _lib.call(self.device, "ishap_unet_create", C.byref(c), self.device.index or 0, C.byref(h), stream=False)
         self._h = h
-        self._L = L
         self._param_probe = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._fp16 = False
         self._last_shape, self._last_feat = None, -1
         self._last_cot = None
         self._snap_key = None          # (N, feat_layer, input shape) of the forward a valid snapshot holds
+
+    def _call(self, name: str, *args, stream=True):
+        """the library entry `name` on this context: _lib.call with the handle as first argument"""
+        _lib.call(self.device, name, self._h, *args, stream=stream)
 
     # ------------------------------------------------------------------ module-like surface
     def __del__(self):
@@ -87,12 +89,12 @@ class UNetModel:
         self.snapshot_drop()
 
     def param_table(self) -> Dict[str, tuple]:
-        L, out = self._L, {}
+        out = {}
         name = C.create_string_buffer(256)
         nd = C.c_int()
         shp = (C.c_longlong * 4)()
-        for i in range(L.ishap_unet_num_params(self._h)):
-            _lib.check(L.ishap_unet_param_info(self._h, i, name, 256, C.byref(nd), shp))
+        for i in range(self._L.ishap_unet_num_params(self._h)):
+            self._call("ishap_unet_param_info", i, name, 256, C.byref(nd), shp, stream=False)
             out[name.value.decode()] = tuple(int(shp[k]) for k in range(nd.value))
         return out
 
@@ -105,17 +107,16 @@ class UNetModel:
                                f"unexpected keys {unexpected[:5]}...")
         s = _lib.stream_ptr(self.device)
         self._snap_key = None          # the library drops the snapshot's validity with the first tensor it loads
-        with torch.cuda.device(self.device):
-            for k, shape in table.items():
-                if k not in sd:
-                    continue
-                v = sd[k]
-                if tuple(v.shape) != tuple(shape):
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(shape)}")
-                v = v.detach().to(device=self.device, dtype=torch.float32).contiguous()
-                _lib.check(self._L.ishap_unet_load_param(self._h, k.encode(), v.data_ptr(), v.numel(), s))
-                del v
-            torch.cuda.current_stream(self.device).synchronize()
+        for k, shape in table.items():
+            if k not in sd:
+                continue
+            v = sd[k]
+            if tuple(v.shape) != tuple(shape):
+                raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(shape)}")
+            v = _lib.tensor(v, torch.float32, self.device)
+            self._call("ishap_unet_load_param", k.encode(), v.data_ptr(), v.numel(), stream=s)     # the stream fetched once
+            del v
+        torch.cuda.current_stream(self.device).synchronize()
         return self
 
     # ------------------------------------------------------------------ forward / backward
@@ -128,19 +129,17 @@ class UNetModel:
         assert y is None, "class conditioning is not on the path"
         assert x.dim() == 4 and x.shape[1] == self.in_channels and x.shape[2] == x.shape[3] == self.image_size
         N = x.shape[0]
-        x = x.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        x = _lib.tensor(x, torch.float32, self.device)
         ts = (C.c_float * N)(*[float(t) for t in (timesteps.tolist() if torch.is_tensor(timesteps) else timesteps)])
         out = torch.empty((N, self.out_channels, self.image_size, self.image_size), dtype=torch.float32,
                           device=self.device)
         inter = None
         if feat_layer >= 0 and want_inter_feat:
             ch, sz = C.c_int(), C.c_int()
-            _lib.check(self._L.ishap_unet_tap_shape(self._h, feat_layer, C.byref(ch), C.byref(sz)))
+            self._call("ishap_unet_tap_shape", feat_layer, C.byref(ch), C.byref(sz), stream=False)
             inter = torch.empty((N, ch.value, sz.value, sz.value), dtype=torch.float16, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_forward(self._h, x.data_ptr(), ts, N, int(feat_layer), out.data_ptr(),
-                                                  _lib.ptr(inter), int(bool(keep_for_backward)) | (2 if overlap_tail else 0),
-                                                  _lib.stream_ptr(self.device)))
+        self._call("ishap_unet_forward", x.data_ptr(), ts, N, int(feat_layer), out.data_ptr(), _lib.ptr(inter),
+                   int(bool(keep_for_backward)) | (2 if overlap_tail else 0))
         self._last_shape, self._last_feat = tuple(x.shape), int(feat_layer)
         if self._snap_key is not None and self._snap_key[:2] != (N, int(feat_layer)):
             self._snap_key = None      # the library invalidates a snapshot when a forward has another batch size or tap
@@ -153,13 +152,11 @@ class UNetModel:
 
     def run_tail(self):
         """Enqueue the forward tail that `forward(overlap_tail=True)` only planned; no-op when there is none."""
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_run_tail(self._h))
+        self._call("ishap_unet_run_tail", stream=False)
 
     def join_tail(self):
         """Order the current stream behind an overlapped forward tail (no-op when there is none)."""
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_join_tail(self._h, _lib.stream_ptr(self.device)))
+        self._call("ishap_unet_join_tail")
         self._tail_out = None
 
     # ------------------------------------------------------------------ snapshot of a kept forward
@@ -198,8 +195,7 @@ class UNetModel:
     def snapshot_drop(self):
         self._snap_key = None
         if getattr(self, "_h", None):
-            with torch.cuda.device(self.device):
-                _lib.check(self._L.ishap_unet_snapshot_drop(self._h))
+            self._call("ishap_unet_snapshot_drop", stream=False)
 
     def snapshot_bytes(self) -> int:
         return int(self._L.ishap_unet_snapshot_bytes(self._h))
@@ -209,12 +205,11 @@ class UNetModel:
         timesteps skip the embedding launches.  An empty list drops them.  Values are bit-identical either way."""
         ts = [float(t) for t in timesteps]
         arr = (C.c_float * max(len(ts), 1))(*ts)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_prepare_timesteps(self._h, arr, len(ts), _lib.stream_ptr(self.device)))
+        self._call("ishap_unet_prepare_timesteps", arr, len(ts))
 
     def tap_shape(self, feat_layer: int):
         ch, sz = C.c_int(), C.c_int()
-        _lib.check(self._L.ishap_unet_tap_shape(self._h, feat_layer, C.byref(ch), C.byref(sz)))
+        self._call("ishap_unet_tap_shape", feat_layer, C.byref(ch), C.byref(sz), stream=False)
         return ch.value, sz.value
 
     def tap_ptr(self) -> int:
@@ -229,8 +224,7 @@ class UNetModel:
             raise ValueError(f"copy_tap: the resident tap holds {last} image(s), not {N}")
         N = last
         t = torch.empty((N, sz * sz, ch), dtype=torch.float16, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_copy_tap(self._h, t.data_ptr(), _lib.stream_ptr(self.device)))
+        self._call("ishap_unet_copy_tap", t.data_ptr())
         return t
 
     def block_output(self, group: int, index: int = 0) -> torch.Tensor:
@@ -238,13 +232,11 @@ class UNetModel:
         forward(keep_for_backward=True), as fp16 NCHW like the reference's activations.  The batch size is the kept
         forward's (the library writes that many images)."""
         ch, sz = C.c_int(), C.c_int()
-        _lib.check(self._L.ishap_unet_block_output(self._h, group, index, C.byref(ch), C.byref(sz), None, None))
+        self._call("ishap_unet_block_output", group, index, C.byref(ch), C.byref(sz), None, None, stream=False)
         if self._last_shape is None:
             raise RuntimeError("block outputs stay resident only after a forward with keep_for_backward=1")
         t = torch.empty((self._last_shape[0], ch.value, sz.value, sz.value), dtype=torch.float16, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_block_output(self._h, group, index, C.byref(ch), C.byref(sz), t.data_ptr(),
-                                                       _lib.stream_ptr(self.device)))
+        self._call("ishap_unet_block_output", group, index, C.byref(ch), C.byref(sz), t.data_ptr())
         return t
 
     def block_grad(self, group: int, index: int = 0, part: int = 0) -> torch.Tensor:
@@ -254,13 +246,11 @@ class UNetModel:
         `skip` half of the output block's concatenated input.  The maps stay resident until the next forward, backward or
         snapshot restore; a read after one of those raises."""
         ch, sz = C.c_int(), C.c_int()
-        _lib.check(self._L.ishap_unet_block_grad(self._h, group, index, part, C.byref(ch), C.byref(sz), None, None))
+        self._call("ishap_unet_block_grad", group, index, part, C.byref(ch), C.byref(sz), None, None, stream=False)
         if self._last_shape is None:
             raise RuntimeError("block gradients exist only after a backward pass on this context")
         t = torch.empty((self._last_shape[0], ch.value, sz.value, sz.value), dtype=torch.float16, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_block_grad(self._h, group, index, part, C.byref(ch), C.byref(sz), t.data_ptr(),
-                                                     _lib.stream_ptr(self.device)))
+        self._call("ishap_unet_block_grad", group, index, part, C.byref(ch), C.byref(sz), t.data_ptr())
         return t
 
     def workspace_bytes(self) -> int:
@@ -269,9 +259,7 @@ class UNetModel:
     def backward_input(self, cot_nhwc_f16: torch.Tensor, scale2: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Gradient w.r.t. x of sum(tap * cot) for the last forward(keep_for_backward=True)."""
         dx = torch.empty(self._last_shape, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_backward_input(self._h, cot_nhwc_f16.data_ptr(), _lib.ptr(scale2),
-                                                         dx.data_ptr(), _lib.stream_ptr(self.device)))
+        self._call("ishap_unet_backward_input", cot_nhwc_f16.data_ptr(), _lib.ptr(scale2), dx.data_ptr())
         self._last_cot = cot_nhwc_f16      # block_grad reads the tapped block's incoming gradient through this buffer
         return dx
 
@@ -279,10 +267,8 @@ class UNetModel:
         """Full-depth input gradient of sum(out * cot).  `cot_out` fp32, or fp16 pre-multiplied by scale2[0]."""
         dx = torch.empty(self._last_shape, dtype=torch.float32, device=self.device)
         is_f16 = cot_out.dtype == torch.float16
-        cot_out = cot_out.detach().to(device=self.device).contiguous()
+        cot_out = _lib.tensor(cot_out, None, self.device)
         if not is_f16:
             cot_out = cot_out.float()
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.ishap_unet_backward_from_output(self._h, cot_out.data_ptr(), int(is_f16), _lib.ptr(scale2),
-                                                               dx.data_ptr(), _lib.stream_ptr(self.device)))
+        self._call("ishap_unet_backward_from_output", cot_out.data_ptr(), int(is_f16), _lib.ptr(scale2), dx.data_ptr())
         return dx

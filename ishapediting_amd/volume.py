@@ -18,7 +18,6 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .mesh import _need_gpu
 
 PHASES = {"outside": 0, "inside": 1}
 CONNECTIVITIES = (6, 26)
@@ -34,48 +33,43 @@ def _check(volume, phase, connectivity, what):
                          f"{tuple(volume.shape) if torch.is_tensor(volume) else type(volume).__name__}")
     if volume.numel() >= 1 << 31:
         raise ValueError(f"{what}: {volume.numel()} voxels, the limit is 2^31 - 1")
-    _need_gpu(volume, what)
-    return volume.detach().to(torch.float32).contiguous()
+    _lib.need_gpu(volume, what)
+    return _lib.tensor(volume, torch.float32)
 
 
 def _label(vol: torch.Tensor, level: float, phase: str, connectivity: int) -> torch.Tensor:
     labels = torch.empty(vol.shape, dtype=torch.int32, device=vol.device)
     nx, ny, nz = vol.shape
-    with torch.cuda.device(vol.device):
-        _lib.check(_lib.lib().ishap_volume_label(vol.data_ptr(), nx, ny, nz, float(level), PHASES[phase], int(connectivity),
-                                                 labels.data_ptr(), _lib.stream_ptr(vol.device)))
+    _lib.call(vol.device, "ishap_volume_label", vol.data_ptr(), nx, ny, nz, float(level), PHASES[phase], int(connectivity),
+              labels.data_ptr())
     return labels
 
 
 def _scratch(vol: torch.Tensor) -> torch.Tensor:
-    nbytes = int(_lib.lib().ishap_volume_components_scratch_bytes(vol.numel()))
-    if nbytes < 0:
-        raise RuntimeError("ishap_volume_components_scratch_bytes: invalid size")
-    return torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+    try:
+        return _lib.scratch(vol.device, "ishap_volume_components_scratch_bytes", vol.numel())[0]
+    except _lib.ScratchError:
+        raise RuntimeError("ishap_volume_components_scratch_bytes: invalid size") from None
 
 
 def _table(labels: torch.Tensor, scratch: torch.Tensor) -> torch.Tensor:
     """int32 [C, 9] rows (root, voxels, xmin, xmax, ymin, ymax, zmin, zmax, border) in ascending root order"""
-    L = _lib.lib()
     nx, ny, nz = labels.shape
     dev = labels.device
     count = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        s = _lib.stream_ptr(dev)
-        _lib.check(L.ishap_volume_components_count(labels.data_ptr(), nx, ny, nz, scratch.data_ptr(), count.data_ptr(), s))
-        c = int(count.item())                                          # the one host read-back: the table's size
-        table = torch.empty((c, 9), dtype=torch.int32, device=dev)
-        if c:
-            _lib.check(L.ishap_volume_components_emit(labels.data_ptr(), nx, ny, nz, scratch.data_ptr(), table.data_ptr(), s))
+    _lib.call(dev, "ishap_volume_components_count", labels.data_ptr(), nx, ny, nz, scratch.data_ptr(), count.data_ptr())
+    c = int(count.item())                                          # the one host read-back: the table's size
+    table = torch.empty((c, 9), dtype=torch.int32, device=dev)
+    if c:
+        _lib.call(dev, "ishap_volume_components_emit", labels.data_ptr(), nx, ny, nz, scratch.data_ptr(), table.data_ptr())
     return table
 
 
 def _flip(vol_in: torch.Tensor, vol_out: torch.Tensor, labels: torch.Tensor, level: float, roots: torch.Tensor, scratch: torch.Tensor):
     nx, ny, nz = vol_in.shape
-    roots = roots.to(device=vol_in.device, dtype=torch.int32).contiguous()
-    with torch.cuda.device(vol_in.device):
-        _lib.check(_lib.lib().ishap_volume_flip(vol_in.data_ptr(), vol_out.data_ptr(), labels.data_ptr(), nx, ny, nz, float(level),
-                                                roots.data_ptr(), roots.numel(), scratch.data_ptr(), _lib.stream_ptr(vol_in.device)))
+    roots = _lib.tensor(roots, torch.int32, vol_in.device)
+    _lib.call(vol_in.device, "ishap_volume_flip", vol_in.data_ptr(), vol_out.data_ptr(), labels.data_ptr(), nx, ny, nz, float(level),
+              roots.data_ptr(), roots.numel(), scratch.data_ptr())
     return vol_out
 
 
@@ -177,16 +171,14 @@ EDT_MAX_AXIS = 1024
 def _edt(seeds: torch.Tensor, axes: int, invert: bool) -> torch.Tensor:
     """ishap_edt on a contiguous uint8 [n0, n1, n2] device tensor -> int32 of that shape, on torch's current stream"""
     n0, n1, n2 = seeds.shape
-    L = _lib.lib()
-    nbytes = int(L.ishap_edt_scratch_bytes(n0, n1, n2, axes))
+    nbytes = int(_lib.lib().ishap_edt_scratch_bytes(n0, n1, n2, axes))
     if nbytes <= 0:
         raise ValueError(f"distance_transform: a grid of {(n0, n1, n2)} with axes mask {axes} is outside the limits (every "
                          f"measured axis <= {EDT_MAX_AXIS}, fewer than 2^31 voxels)")
     out = torch.empty((n0, n1, n2), dtype=torch.int32, device=seeds.device)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=seeds.device)
-    with torch.cuda.device(seeds.device):
-        _lib.check(L.ishap_edt(seeds.data_ptr(), n0, n1, n2, axes, int(bool(invert)), out.data_ptr(), scratch.data_ptr(), nbytes,
-                               _lib.stream_ptr(seeds.device)))
+    _lib.call(seeds.device, "ishap_edt", seeds.data_ptr(), n0, n1, n2, axes, int(bool(invert)), out.data_ptr(), scratch.data_ptr(),
+              nbytes)
     return out
 
 
@@ -198,7 +190,7 @@ def distance_transform(mask: torch.Tensor, axes=None, invert: bool = False) -> t
     arithmetic on the device (csrc/edt.hip): two runs give the same bits."""
     if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or not 1 <= mask.dim() <= 3 or mask.numel() == 0:
         raise ValueError("distance_transform: mask must be a non-empty bool or uint8 tensor of 1 to 3 dimensions")
-    _need_gpu(mask, "distance_transform")
+    _lib.need_gpu(mask, "distance_transform")
     nd = mask.dim()
     if axes is None:
         axes = tuple(range(nd))

@@ -196,6 +196,55 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
         UNetModel(tiny_config(1), torch.device("cpu"))
 
 
+def test_an_older_build_is_refused_with_the_required_abi(monkeypatch):
+    from ishapediting_amd import _lib
+    have = _lib.lib().ishap_version()
+    assert have == _lib.ABI
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "ABI", have + 1)
+    with pytest.raises(RuntimeError, match=rf"older build \(ABI {have} < {have + 1}\): rebuild"):
+        _lib.lib()
+
+
+def test_need_gpu_messages(monkeypatch):
+    """the three checks it replaced: mesh.py's per function, metrics.py's for a device left open, render.py's"""
+    from ishapediting_amd import _lib, mesh, metrics, render
+    tail = " on the GPU (libishap_hip.so); there is no CPU fallback"
+    host = torch.zeros((4, 3))
+    with pytest.raises(RuntimeError) as e:
+        _lib.need_gpu(host, "extract_surface")
+    assert str(e.value) == "extract_surface runs" + tail
+    with pytest.raises(RuntimeError) as e:
+        mesh.cloud_areas(host, 2)
+    assert str(e.value) == "cloud_areas runs" + tail
+    with pytest.raises(RuntimeError) as e:
+        render.render_arrays(host, torch.zeros((0, 3), dtype=torch.int32), render.Camera((0.0, 0.0, 3.0)), 4, 4)
+    assert str(e.value) == "render runs" + tail
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    with pytest.raises(RuntimeError) as e:
+        metrics.device_mesh((np.zeros((3, 3), np.float32), np.zeros((1, 3), np.int32)))
+    assert str(e.value) == "mesh metrics run" + tail
+    assert _lib.need_gpu("cuda:1", "anything") == torch.device("cuda", 1)        # a named device is taken as it is
+
+
+def test_tensor_coerces_host_inputs_and_keeps_conforming_ones():
+    from ishapediting_amd import _lib
+    t = torch.arange(12, dtype=torch.float32).reshape(4, 3)
+    assert _lib.tensor(t, torch.float32).data_ptr() == t.data_ptr()
+    assert _lib.tensor(t, torch.float32, shape=(-1, 3)).data_ptr() == t.data_ptr()
+    assert _lib.tensor(t.requires_grad_(), torch.float32).requires_grad is False
+    flat = _lib.tensor(t.detach(), torch.float32, shape=(-1,))
+    assert tuple(flat.shape) == (12,) and flat.data_ptr() == t.data_ptr()
+    for x in ([[0.1, 0.2, 0.3]], np.array([0.1, 0.2, 0.3]), (0.1, 0.2, 0.3)):          # what numpy.asarray takes
+        got = _lib.tensor(x, torch.float32, shape=(-1, 3))
+        assert got.dtype == torch.float32 and tuple(got.shape) == (1, 3) and got.is_contiguous()
+        assert np.array_equal(got.numpy(), np.array([[0.1, 0.2, 0.3]], np.float32))
+    i = _lib.tensor(np.array([[3, 1, 2]], np.int64), torch.int32)
+    assert i.dtype == torch.int32 and i.tolist() == [[3, 1, 2]]
+    col = _lib.tensor(t.detach()[:, 1], torch.float64)
+    assert col.dtype == torch.float64 and col.is_contiguous() and col.tolist() == [1.0, 4.0, 7.0, 10.0]
+
+
 def test_visualize_mirrors_the_reference_signatures():
     """triplane_decoder/visualize.py:36,76,108: same parameter names, order and defaults (SURVEY 8b keeps these callable)."""
     import inspect
