@@ -51,19 +51,22 @@ int ishap_version(void);   /* 2 since ishap_mesh_smooth takes (and checks) the s
                             * ishap_cloud_orient, ishap_cloud_orient_scratch_bytes); 15 since the snapshot of a kept forward
                             * (ishap_unet_snapshot_save / _restore / _drop / _bytes); 16 since the connected components of a
                             * volume (ishap_volume_label, ishap_volume_components_*, ishap_volume_flip); 17 since the region
-                            * weights of the drag loss (the trailing `weights` of ishap_drag_args, `weights` / `weights_stride` of
-                            * ishap_drag_batch_args, ishap_region_plane_weights, ishap_region_plane_weights_scratch_bytes);
+                            * weights of the drag loss (`weights` / `weights_stride` of ishap_drag_batch_args, ishap_region_plane_weights, ishap_region_plane_weights_scratch_bytes);
                             * 18 since the decoder's field in space (ishap_triplane_field_grad, ishap_triplane_project); 19 since
                             * the part edits (ishap_region_select, ishap_region_handles, ishap_region_handles_scratch_bytes,
                             * ishap_region_transform); 20 since ishap_unet_block_grad; 21 since the handle
                             * tracking (ishap_drag_track, ishap_drag_track_scratch_bytes); 22 since the closed-loop drag
-                            * (ishap_drag_retarget, ishap_drag_batch_retarget, ishap_drag_batch_retarget_each); 23 since the exact
+                            * (ishap_drag_batch_retarget, ishap_drag_batch_retarget_each); 23 since the exact
                             * distance transform (ishap_edt, ishap_edt_scratch_bytes) and the marks and feathered map of the
                             * regions (ishap_region_plane_marks, ishap_region_plane_feather, ishap_region_plane_feather_scratch_bytes);
                             * 24 since the volume constraints (ishap_constraint_setup, ishap_constraint_setup_scratch_bytes,
                             * ishap_constraint_loss_grad); 25 since the sparse high-resolution surface
                             * (ishap_triplane_decode_bricks, ishap_sparse_*); 26 since the quadric vertex clustering
-                            * (ishap_mesh_simplify_scratch_bytes, ishap_mesh_simplify_count, ishap_mesh_simplify_emit) */
+                            * (ishap_mesh_simplify_scratch_bytes, ishap_mesh_simplify_count, ishap_mesh_simplify_emit); 27 since the
+                            * single-edit drag interface was REMOVED (ishap_drag_args, ishap_drag_setup, ishap_drag_loss_grad,
+                            * ishap_drag_loss_cotangent, ishap_drag_retarget): one edit is the ishap_drag_batch_* call of the same
+                            * name on an ishap_drag_batch_args with E = 1, handle_offsets = {0, B}, cof = {cof} and a scratch of
+                            * ishap_drag_batch_scratch_bytes(1, W, ld) bytes */
 
 /* ---------------------------------------------------------------- UNet (gd/unet.py:396-671) */
 typedef struct ishap_unet ishap_unet;
@@ -344,76 +347,54 @@ int ishap_guided_update(const float* sample, const float* variance, const float*
 int ishap_axpby(const float* x, const float* y, float a, float b, long long numel, float* out, void* stream);
 
 /* ---------------------------------------------------------- drag loss (drag_utils.py:141-159, 309-382) */
+/* E drag edits in one call, in the launches of one (loss + gradient: terms, gather, finish; + cotangent: terms, gather, scale);
+ * one edit is E = 1.  Per edit: its handles (a CSR range of one packed sources / targets array), cof, rounded-texel bitmap, mask
+ * count, loss sums and fixed-point scatter buffer; its tap slice edit + e*W*W*ld and guidance slice orig + e*orig_stride.
+ * Shared: W, ld, Cc, chmap, r, voxel, l1, and ONE power-of-two loss scale for the whole batch, picked from max|g| over all edits.
+ * An edit's loss and fp32 gradient do NOT depend on the edits beside it, bit for bit: they are what the same edit gives alone,
+ * as E = 1, because an edit's workgroups do the same work whatever stands beside them.  Its fp16 cotangent is its E = 1 value
+ * times the power of two 2^(k_batch - k_alone) of the two loss scales (bitwise where both are normal fp16 numbers).  The
+ * input-gradient backward is linear in the cotangent and removes scale2[1] at its end, so a batched backward needs nothing else. */
 typedef struct {
+  int E;                /* edits, 1..32 */
   int W;                /* side of the tap feature map (64) */
   int ld;               /* channels of the tap (512) */
   int Cc;               /* channels per plane after resize_feat_align (170) */
   const int* chmap;     /* device int[3*Cc]: (plane, c) -> tap channel (resize_feat_align's mapping) */
-  const float* sources; /* device [B][3] */
-  const float* targets; /* device [B][3] */
-  int B;
-  int r;                /* lattice radius r1 (12) */
-  float voxel;          /* 2 / shape_resolution */
-  float cof;
-  int l1;               /* loss_type == 'l1' */
-  unsigned char* touched; /* device scratch [3*W*W], 3*W*W % 4 == 0: bit 0 = the reference's rounded-texel sets, bit 1 = target footprints */
-  int* nmask;             /* device scratch [1] */
-  void* acc;              /* device scratch, 16 bytes (two 64-bit fixed-point loss sums) */
-  void* grad_fx;          /* device scratch, W*W*ld*8 bytes: the gradient scatter accumulates in 64-bit fixed point so
-                           * that repeated edits are bitwise identical (integer atomics commute) */
-  unsigned char* chan_weight; /* device scratch [3*ld] bytes: inverse of chmap, filled by ishap_drag_setup */
-  const float* weights;   /* ABI 17, read by the loss calls only.  NULL: no weights.  Else device float[3*W*W], indexed [plane][row][col]
-                           * like `touched`: the mask term of an UNTOUCHED texel t of plane p is multiplied by weights[p][t] (>= 0,
-                           * finite; 0 frees the texel, > 1 holds it harder), the count it is divided by stays the count of untouched
-                           * texels, and the weight of a touched texel is ignored.  A map of exact ones gives bitwise the results of
-                           * NULL.  With cof <= 0 there is no mask term and the map is not used.  Built from 3-D regions by
-                           * ishap_region_plane_weights.  Last field: a positional construction that stops before it means NULL. */
-} ishap_drag_args;
-/* once per edit: rounded-texel bitmap and complement count (drag_utils.py:322-334); also zeroes acc and grad_fx, which
- * every loss call below expects zero on entry and leaves zero on return */
-int ishap_drag_setup(const ishap_drag_args* a, void* stream);
-/* per step: loss (device float[1]) and d loss / d tap as fp32 NHWC [W*W][ld] (drag_utils.py:355-383) */
-int ishap_drag_loss_grad(const ishap_drag_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
-                         float* grad_nhwc, float* loss, void* stream);
-/* the same followed by ishap_grad_to_scaled_f16 (below) on that gradient, as three launches instead of ten: the form the
- * guided step uses (drag_utils.py:355-383 up to loss.backward()) */
-int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
-                              float* grad_nhwc, float* loss, void* cot_f16, unsigned* bits, float* scale2, void* stream);
-/* E drag edits in one call, in the launches of one (loss + gradient: terms, gather, finish; + cotangent: terms, gather, scale).
- * Per edit: its handles (a CSR range of one packed sources / targets array), cof, rounded-texel bitmap, mask count, loss sums
- * and fixed-point scatter buffer; its tap slice edit + e*W*W*ld and guidance slice orig + e*orig_stride.  Shared: W, ld, Cc,
- * chmap, r, voxel, l1, and ONE power-of-two loss scale for the whole batch, picked from max|g| over all edits.
- * Each edit's loss and fp32 gradient are BITWISE those of ishap_drag_loss_grad on that edit alone, by construction: the
- * single-edit calls above are the E = 1 case of these, the same kernels on the caller's own buffers, and an edit's workgroups do
- * the same work whatever stands beside them.  Its fp16 cotangent is the solo one times 2^(k_batch - k_solo) (bitwise where both
- * are normal fp16 numbers).  The input-gradient backward is linear in
- * the cotangent and removes scale2[1] at its end, so a batched backward needs nothing else. */
-typedef struct {
-  int E;                /* edits, 1..32 */
-  int W, ld, Cc;        /* as in ishap_drag_args */
-  const int* chmap;     /* device int[3*Cc] */
   const float* sources; /* device [handle_offsets[E]][3]: the handles of all edits, edit by edit */
   const float* targets; /* device, same layout */
   const int* handle_offsets; /* HOST int[E+1], CSR: edit e owns handles [handle_offsets[e], handle_offsets[e+1]); [0] = 0, each range non-empty */
-  int r;
-  float voxel;
+  int r;                /* lattice radius r1 (12) */
+  float voxel;          /* 2 / shape_resolution */
   const float* cof;     /* HOST float[E] */
-  int l1;
+  int l1;               /* loss_type == 'l1' */
   long long orig_stride;  /* halfs between the guidance features of consecutive edits; 0 = every edit reads the same one */
   void* scratch;          /* device, 16-byte aligned, ishap_drag_batch_scratch_bytes(E, W, ld) bytes; zeroed by the setup call,
-                           * left zero by every loss call */
+                           * left zero by every loss call.  Holds, per edit: the gradient scatter (W*W*ld 64-bit fixed-point sums,
+                           * so that repeated edits are bitwise identical: integer atomics commute), two 64-bit fixed-point loss
+                           * sums, the mask count, the touched bitmap [3*W*W] (3*W*W % 4 == 0; bit 0 = the reference's
+                           * rounded-texel sets, bit 1 = target footprints); and once the inverse of chmap [3*ld] */
   long long scratch_bytes;
-  const float* weights;   /* ABI 17, as in ishap_drag_args: NULL, or the base of device float[E][3*W*W]; edit e reads weights +
-                           * e * weights_stride.  An edit without regions reads a map of ones (bitwise its unweighted result). */
+  const float* weights;   /* ABI 17, read by the loss calls only.  NULL: no weights.  Else the base of device float[E][3*W*W], each
+                           * map indexed [plane][row][col] like the touched bitmap; edit e reads weights + e * weights_stride.  The
+                           * mask term of an UNTOUCHED texel t of plane p is multiplied by weights[p][t] (>= 0, finite; 0 frees the
+                           * texel, > 1 holds it harder), the count it is divided by stays the count of untouched texels, and the
+                           * weight of a touched texel is ignored.  A map of exact ones gives bitwise the results of NULL, so an
+                           * edit without regions reads a map of ones.  With cof <= 0 there is no mask term and the map is not
+                           * used.  Built from 3-D regions by ishap_region_plane_weights. */
   long long weights_stride; /* floats between the maps of consecutive edits (>= 3*W*W), or 0: one map for every edit */
 } ishap_drag_batch_args;
 long long ishap_drag_batch_scratch_bytes(int E, int W, int ld);
-/* once per batch of edits (what ishap_drag_setup does, for each edit) */
+/* once per batch of edits: each edit's rounded-texel bitmap and complement count (drag_utils.py:322-334); also zeroes the loss
+ * sums and the scatter buffer, which every loss call below expects zero on entry and leaves zero on return */
 int ishap_drag_batch_setup(const ishap_drag_batch_args* a, void* stream);
-/* edit_nhwc_f16 [E][W*W][ld] (the resident tap of a batch-E forward); loss device float[E]; grad_nhwc fp32 [E][W*W][ld] */
+/* per step: loss (device float[E]) and d loss / d tap as fp32 NHWC [E][W*W][ld] (drag_utils.py:355-383); edit_nhwc_f16
+ * [E][W*W][ld] (the resident tap of a batch-E forward) */
 int ishap_drag_batch_loss_grad(const ishap_drag_batch_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
                                float* grad_nhwc, float* loss, void* stream);
-/* the same plus the fp16 cotangent [E][W*W][ld] with the batch's loss scale; bits: device uint32[1]; scale2: device float[2] */
+/* the same followed by ishap_grad_to_scaled_f16 (below) on that gradient, as three launches instead of ten: the form the
+ * guided step uses (drag_utils.py:355-383 up to loss.backward()).  cot_f16 [E][W*W][ld] with the batch's loss scale; bits: device
+ * uint32[1]; scale2: device float[2] */
 int ishap_drag_batch_loss_cotangent(const ishap_drag_batch_args* a, const void* edit_nhwc_f16, const void* orig_nhwc_f16,
                                     float* grad_nhwc, float* loss, void* cot_f16, unsigned* bits, float* scale2, void* stream);
 /* ---------------------------------------------------------- handle tracking (ABI 21; csrc/track.hip)
@@ -460,9 +441,6 @@ int ishap_drag_batch_retarget(const ishap_drag_batch_args* a, const float* final
 /* the same with one lead and one arrival radius per edit: steps, arrives HOST float[E] */
 int ishap_drag_batch_retarget_each(const ishap_drag_batch_args* a, const float* final_targets, const int* K, const float* steps,
                                    const float* arrives, float* remaining, int* arrived, int* done, void* stream);
-/* one edit: the E = 1 call of the same kernel on the caller's own buffers (done: device int[1]) */
-int ishap_drag_retarget(const ishap_drag_args* a, const float* final_targets, const int* K, float step, float arrive,
-                        float* remaining, int* arrived, int* done, void* stream);
 /* ---------------------------------------------------------- region-constrained edits (ABI 17; csrc/regions.hip)
  * The weight map of the drag loss's mask term from 3-D regions in the coordinates handles use, [-1, 1]^3.  A region is a union
  * of primitives and one voxel grid; `keep` must not move, `free` may.  Its SHADOW on plane p (axes as the drag loss: plane 0

@@ -30,13 +30,6 @@ class StepCoefs(C.Structure):
                 ("rng", C.c_int), ("rng_seed", C.c_ulonglong), ("rng_offset", C.c_ulonglong), ("noise_out", c_void_p)]
 
 
-class DragArgsC(C.Structure):
-    _fields_ = [("W", C.c_int), ("ld", C.c_int), ("Cc", C.c_int), ("chmap", c_void_p), ("sources", c_void_p),
-                ("targets", c_void_p), ("B", C.c_int), ("r", C.c_int), ("voxel", C.c_float), ("cof", C.c_float),
-                ("l1", C.c_int), ("touched", c_void_p), ("nmask", c_void_p), ("acc", c_void_p), ("grad_fx", c_void_p), ("chan_weight", c_void_p),
-                ("weights", c_void_p)]      # trailing, ABI 17: a positional construction that stops before it means no weights
-
-
 class DragBatchArgsC(C.Structure):
     _fields_ = [("E", C.c_int), ("W", C.c_int), ("ld", C.c_int), ("Cc", C.c_int), ("chmap", c_void_p), ("sources", c_void_p),
                 ("targets", c_void_p), ("handle_offsets", C.POINTER(C.c_int)), ("r", C.c_int), ("voxel", C.c_float),
@@ -143,10 +136,6 @@ SYMBOLS = {
     "ishap_guided_update": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_float, c_void_p, C.c_longlong, c_void_p,
                                       c_void_p]),
     "ishap_axpby": (C.c_int, [c_void_p, c_void_p, C.c_float, C.c_float, C.c_longlong, c_void_p, c_void_p]),
-    "ishap_drag_setup": (C.c_int, [C.POINTER(DragArgsC), c_void_p]),
-    "ishap_drag_loss_grad": (C.c_int, [C.POINTER(DragArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "ishap_drag_loss_cotangent": (C.c_int, [C.POINTER(DragArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                            c_void_p, c_void_p]),
     "ishap_drag_batch_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "ishap_drag_batch_setup": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p]),
     "ishap_drag_batch_loss_grad": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -156,8 +145,6 @@ SYMBOLS = {
     "ishap_drag_track": (C.c_int, [c_void_p, c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, c_void_p, c_void_p,
                                    C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, C.c_longlong, c_void_p]),
-    "ishap_drag_retarget": (C.c_int, [C.POINTER(DragArgsC), c_void_p, c_void_p, C.c_float, C.c_float, c_void_p, c_void_p, c_void_p,
-                                      c_void_p]),
     "ishap_drag_batch_retarget": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, C.c_float, C.c_float, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
     "ishap_drag_batch_retarget_each": (C.c_int, [C.POINTER(DragBatchArgsC), c_void_p, c_void_p, C.POINTER(C.c_float),
@@ -274,7 +261,7 @@ SYMBOLS = {
                                            c_void_p, c_void_p]),
 }
 
-ABI = 26          # the ishap_version() this module's SYMBOLS and structures describe
+ABI = 27          # the ishap_version() this module's SYMBOLS and structures describe
 
 _lib = None
 

@@ -235,59 +235,9 @@ int ishap_axpby(const float* x, const float* y, float a, float b, long long nume
   return axpby_launch(x, y, out, a, b, numel, (hipStream_t)stream);
 }
 
-// ---- drag loss: one set of launches (csrc/drag.hip) that takes E edits; the shape requirements are checked there
-static const auto fill_drag_shared = [](const auto* a, DragArgs& b) {     // what the solo and the batched struct both hold
-  b.W = a->W; b.ld = a->ld; b.Cc = a->Cc; b.chmap = a->chmap; b.sources = a->sources; b.targets = a->targets;
-  b.r = a->r; b.voxel = a->voxel; b.l1 = a->l1;
-};
-
-// the per-call pointers of a loss call (nullptr for a setup call, which reads none of them)
-static void fill_drag_call(DragBatchArgs& d, const void* edit, const void* orig, float* grad, float* loss) {
-  d.base.edit = (const half_t*)edit; d.base.orig = (const half_t*)orig; d.base.grad = grad; d.base.loss = loss;
-}
-
-// the solo ABI: E = 1 on the caller's own buffers (a batch of one owns slice 0 of every per-edit array, i.e. the array)
-static int fill_drag(const ishap_drag_args* a, DragBatchArgs& d) {
-  ISHAP_REQUIRE(a && a->chmap && a->sources && a->targets && a->touched && a->nmask && a->acc && a->grad_fx && a->chan_weight,
-                "null argument");
-  ISHAP_REQUIRE(a->W > 1 && a->B >= 1 && a->r >= 0 && a->Cc >= 1 && a->ld >= 1, "drag dims");
-  DragArgs& b = d.base;
-  fill_drag_shared(a, b);
-  b.touched = a->touched; b.nmask = a->nmask; b.acc = (long long*)a->acc; b.gfx = (long long*)a->grad_fx;
-  b.chw = a->chan_weight;
-  d.E = 1;
-  d.orig_stride = 0;
-  d.hoff[0] = 0; d.hoff[1] = a->B;
-  d.cof[0] = a->cof;
-  return 0;
-}
-
-int ishap_drag_setup(const ishap_drag_args* a, void* stream) {
-  DragBatchArgs d;
-  ISHAP_TRY(fill_drag(a, d));
-  return drag_batch_setup_launch(d, (hipStream_t)stream);
-}
-
-int ishap_drag_loss_grad(const ishap_drag_args* a, const void* edit, const void* orig, float* grad, float* loss,
-                         void* stream) {
-  DragBatchArgs d;
-  ISHAP_TRY(fill_drag(a, d));
-  ISHAP_REQUIRE(edit && orig && grad && loss, "null argument");
-  fill_drag_call(d, edit, orig, grad, loss);
-  return drag_batch_loss_launch(d, nullptr, nullptr, nullptr, a->weights, 0, (hipStream_t)stream);
-}
-
-int ishap_drag_loss_cotangent(const ishap_drag_args* a, const void* edit, const void* orig, float* grad, float* loss,
-                              void* cot_f16, unsigned* bits, float* scale2, void* stream) {
-  DragBatchArgs d;
-  ISHAP_TRY(fill_drag(a, d));
-  ISHAP_REQUIRE(edit && orig && grad && loss && cot_f16 && bits && scale2, "null argument");
-  fill_drag_call(d, edit, orig, grad, loss);
-  return drag_batch_loss_launch(d, (half_t*)cot_f16, bits, scale2, a->weights, 0, (hipStream_t)stream);
-}
-
-// ---- E edits per call: one scratch buffer, carved as [grad_fx E*W*W*ld int64][acc E*2 int64][nmask E int32][touched E*3*W*W]
-// [chan_weight 3*ld], every part starting on a 256-byte boundary
+// ---- drag loss: one set of launches (csrc/drag.hip) that takes E edits (one edit is E = 1); the shape requirements are checked
+// there.  One scratch buffer, carved as [grad_fx E*W*W*ld int64][acc E*2 int64][nmask E int32][touched E*3*W*W][chan_weight 3*ld],
+// every part starting on a 256-byte boundary
 struct DragBatchScratch { long long *gfx, *acc; int* nmask; unsigned char *touched, *chw; long long bytes; };
 static DragBatchScratch drag_batch_carve(void* base, int E, int W, int ld) {
   Carve c{(char*)base};
@@ -309,13 +259,19 @@ static int fill_drag_batch(const ishap_drag_batch_args* a, DragBatchArgs& d) {
   ISHAP_REQUIRE(a->scratch_bytes >= S.bytes, "drag batch: scratch smaller than ishap_drag_batch_scratch_bytes(E, W, ld)");
   ISHAP_REQUIRE(((unsigned long long)a->scratch & 15ull) == 0, "drag batch: scratch must be 16-byte aligned");
   DragArgs& b = d.base;
-  fill_drag_shared(a, b);
+  b.W = a->W; b.ld = a->ld; b.Cc = a->Cc; b.chmap = a->chmap; b.sources = a->sources; b.targets = a->targets;
+  b.r = a->r; b.voxel = a->voxel; b.l1 = a->l1;
   b.gfx = S.gfx; b.acc = S.acc; b.nmask = S.nmask; b.touched = S.touched; b.chw = S.chw;
   d.E = a->E;
   d.orig_stride = a->orig_stride;
   for (int e = 0; e <= a->E; ++e) d.hoff[e] = a->handle_offsets[e];
   for (int e = 0; e < a->E; ++e) d.cof[e] = a->cof[e];
   return 0;
+}
+
+// the per-call pointers of a loss call (nullptr for a setup call, which reads none of them)
+static void fill_drag_call(DragBatchArgs& d, const void* edit, const void* orig, float* grad, float* loss) {
+  d.base.edit = (const half_t*)edit; d.base.orig = (const half_t*)orig; d.base.grad = grad; d.base.loss = loss;
 }
 
 int ishap_drag_batch_setup(const ishap_drag_batch_args* a, void* stream) {
@@ -368,8 +324,12 @@ int ishap_drag_track(const void* edit, const void* orig, long long orig_stride, 
 
 // ---- closed-loop drag (csrc/retarget.hip): the arguments a drag call does not already check are checked here and in
 // drag_retarget_launch, before anything is launched.  `a->targets` is the goals buffer the call writes.
-static int retarget_call(DragBatchArgs& d, const float* final_targets, const int* K, const float* steps, const float* arrives,
-                         float step, float arrive, float* remaining, int* arrived, int* done, void* stream) {
+static int retarget_call(const ishap_drag_batch_args* a, const float* final_targets, const int* K, const float* steps,
+                         const float* arrives, float step, float arrive, float* remaining, int* arrived, int* done, void* stream) {
+  ISHAP_REQUIRE(a && final_targets && K && remaining && arrived && done, "null argument");
+  ISHAP_REQUIRE(a->W > 1 && 3ll * a->W * a->W <= RETARGET_LDS_BYTES, "drag retarget: 3*W*W must not exceed 65536 (the LDS bitmaps)");
+  DragBatchArgs d;
+  ISHAP_TRY(fill_drag_batch(a, d));
   RetargetArgs q;
   q.final_targets = final_targets; q.K = K; q.goals = const_cast<float*>(d.base.targets);
   q.remaining = remaining; q.arrived = arrived; q.done = done;
@@ -377,31 +337,15 @@ static int retarget_call(DragBatchArgs& d, const float* final_targets, const int
   return drag_retarget_launch(d, q, (hipStream_t)stream);
 }
 
-int ishap_drag_retarget(const ishap_drag_args* a, const float* final_targets, const int* K, float step, float arrive,
-                        float* remaining, int* arrived, int* done, void* stream) {
-  ISHAP_REQUIRE(a && final_targets && K && remaining && arrived && done, "null argument");
-  ISHAP_REQUIRE(a->W > 1 && 3ll * a->W * a->W <= RETARGET_LDS_BYTES, "drag retarget: 3*W*W must not exceed 65536 (the LDS bitmaps)");
-  DragBatchArgs d;
-  ISHAP_TRY(fill_drag(a, d));
-  return retarget_call(d, final_targets, K, nullptr, nullptr, step, arrive, remaining, arrived, done, stream);
-}
-
 int ishap_drag_batch_retarget(const ishap_drag_batch_args* a, const float* final_targets, const int* K, float step, float arrive,
                               float* remaining, int* arrived, int* done, void* stream) {
-  ISHAP_REQUIRE(a && final_targets && K && remaining && arrived && done, "null argument");
-  ISHAP_REQUIRE(a->W > 1 && 3ll * a->W * a->W <= RETARGET_LDS_BYTES, "drag retarget: 3*W*W must not exceed 65536 (the LDS bitmaps)");
-  DragBatchArgs d;
-  ISHAP_TRY(fill_drag_batch(a, d));
-  return retarget_call(d, final_targets, K, nullptr, nullptr, step, arrive, remaining, arrived, done, stream);
+  return retarget_call(a, final_targets, K, nullptr, nullptr, step, arrive, remaining, arrived, done, stream);
 }
 
 int ishap_drag_batch_retarget_each(const ishap_drag_batch_args* a, const float* final_targets, const int* K, const float* steps,
                                    const float* arrives, float* remaining, int* arrived, int* done, void* stream) {
-  ISHAP_REQUIRE(a && final_targets && K && steps && arrives && remaining && arrived && done, "null argument");
-  ISHAP_REQUIRE(a->W > 1 && 3ll * a->W * a->W <= RETARGET_LDS_BYTES, "drag retarget: 3*W*W must not exceed 65536 (the LDS bitmaps)");
-  DragBatchArgs d;
-  ISHAP_TRY(fill_drag_batch(a, d));
-  return retarget_call(d, final_targets, K, steps, arrives, 0.f, 0.f, remaining, arrived, done, stream);
+  ISHAP_REQUIRE(steps && arrives, "null argument");
+  return retarget_call(a, final_targets, K, steps, arrives, 0.f, 0.f, remaining, arrived, done, stream);
 }
 
 // ---- region weights of the drag loss's mask term (csrc/regions.hip)

@@ -89,7 +89,7 @@ constexpr float DRAG_ACC_SCALE = 16777216.f;         // 2^24
 int grad_to_scaled_f16_launch(const float* g, half_t* o, unsigned* bits, float* scale2, long long n, hipStream_t s);
 
 // ---- the launches: E edits per call (include/ishap.h, ishap_drag_batch_*), each pass one launch whose grid covers all of them;
-// the solo ABI (ishap_drag_setup / _loss_grad / _loss_cotangent) is E = 1 with `base` pointing at the caller's own buffers ----
+// one edit is E = 1 ----
 constexpr int DRAG_MAX_EDITS = 32;
 struct DragBatchArgs {
   // the shared fields (W, ld, Cc, chmap, chw, r, voxel, l1) and the BASE of every per-edit array: edit e reads edit + e*W*W*ld,
@@ -121,7 +121,7 @@ __device__ __forceinline__ DragArgs drag_edit_args(const DragBatchArgs& b, int e
   a.loss += e;
   return a;
 }
-int drag_batch_check(const DragBatchArgs& a);                     // the shape requirements of every drag call, solo or batched
+int drag_batch_check(const DragBatchArgs& a);                     // the shape requirements of every drag call
 int drag_batch_setup_launch(DragBatchArgs& a, hipStream_t s);     // touched bitmaps + mask counts + channel weights (once per set of edits)
 // losses + fp32 gradients; with `cot` (then `bits` and `scale2` too) also the fp16 cotangent under one loss scale; `weights`:
 // the region weight maps [E][3][W][W] of the mask term (edit e at + e * wstride floats), nullptr for the unweighted pass

@@ -12,7 +12,7 @@
 // over channels, which are contiguous in NHWC (coalesced 2-byte reads, fp32 atomics for the scatter).
 //
 // One set of kernels: the per-edit device bodies first, then the kernels and launches, which take E edits per call
-// (DragBatchArgs).  The single-edit ABI is the E = 1 call of the same kernels on the caller's own buffers.
+// (DragBatchArgs).  One edit is the E = 1 call.
 #include "drag.h"
 #include <cstdlib>
 
@@ -313,7 +313,7 @@ int grad_to_scaled_f16_launch(const float* g, half_t* o, unsigned* bits, float* 
   return 0;
 }
 
-// ==== the launches: E edits per call; the solo ABI (ishap_drag_setup / _loss_grad / _loss_cotangent) is E = 1 ====
+// ==== the launches: E edits per call; one edit is E = 1 ====
 // Every pass is one launch whose grid is the concatenation of one grid per edit: workgroup blk of edit e runs the body above on
 // edit e's slice (drag_edit_args) with that edit's own workgroup count as its grid stride, whatever E is and whichever edits
 // stand beside it.  So each edit's float partial sums are formed in the same groups and order as alone, its fixed-point totals
@@ -386,7 +386,7 @@ __global__ void drag_batch_scale_kernel(const float* __restrict__ g, half_t* __r
   }
 }
 
-// the shape requirements of every drag call, solo or batched (api.hip checks only the pointers and dimensions of its structs)
+// the shape requirements of every drag call (api.hip checks only the pointers and dimensions of its structs)
 int drag_batch_check(const DragBatchArgs& a) {
   ISHAP_REQUIRE(a.E >= 1 && a.E <= DRAG_MAX_EDITS, "drag batch: E must be in 1..32");
   ISHAP_REQUIRE((3 * a.base.W * a.base.W) % 4 == 0 && a.base.ld % 8 == 0,

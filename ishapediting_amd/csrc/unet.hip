@@ -731,7 +731,7 @@ static int snap_reserve(T** buf, size_t* cap, size_t need) {
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ishap_version(void) { return 26; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
+int ishap_version(void) { return 27; }  // 2: ishap_mesh_smooth takes the scratch size; 3: ishap_step_coefs carries the rng fields;
                                         // 4: batched drag edits (ishap_drag_batch_*, ishap_ddpm_step_guided_scales);
                                         // 5: one implicit-GEMM launch through the ABI (ishap_igemm_run, ishap_igemm_reduce);
                                         // 6: direct triplane fitting (ishap_triplane_fit_loss_grad, ishap_triplane_reg_*)
@@ -757,8 +757,7 @@ int ishap_version(void) { return 26; }  // 2: ishap_mesh_smooth takes the scratc
                                         //     ishap_region_transform; parts.hip)
                                         // 20: per-block gradients of the last backward (ishap_unet_block_grad)
                                         // 21: handle tracking (ishap_drag_track, ishap_drag_track_scratch_bytes; track.hip)
-                                        // 22: closed-loop drag (ishap_drag_retarget, ishap_drag_batch_retarget, ishap_drag_batch_retarget_each;
-                                        //     retarget.hip)
+                                        // 22: closed-loop drag (ishap_drag_batch_retarget, ishap_drag_batch_retarget_each; retarget.hip)
                                         // 23: exact distance transform (ishap_edt, ishap_edt_scratch_bytes; edt.hip) and the regions' marks and
                                         //     feathered map (ishap_region_plane_marks, ishap_region_plane_feather[_scratch_bytes]; regions.hip)
                                         // 24: volume constraints (ishap_constraint_setup[_scratch_bytes], ishap_constraint_loss_grad;
@@ -766,6 +765,9 @@ int ishap_version(void) { return 26; }  // 2: ishap_mesh_smooth takes the scratc
                                         // 25: sparse high-resolution surface (ishap_triplane_decode_bricks, ishap_sparse_*;
                                         //     sparse_surface.hip, decode.hip)
                                         // 26: quadric vertex clustering (ishap_mesh_simplify_scratch_bytes / _count / _emit; simplify.hip)
+                                        // 27: the single-edit drag interface is removed (ishap_drag_args, ishap_drag_setup, ishap_drag_loss_grad,
+                                        //     ishap_drag_loss_cotangent, ishap_drag_retarget): one edit is the ishap_drag_batch_* entry of the same
+                                        //     name with E = 1
 
 int ishap_unet_create(const ishap_unet_config* cfg, int device, ishap_unet** out) {
   ISHAP_REQUIRE(cfg && out, "null argument");

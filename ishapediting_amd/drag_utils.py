@@ -100,71 +100,6 @@ _OVERLAP_TAIL = os.environ.get("ISHAP_OVERLAP_TAIL", "1") == "1"      # round 5:
 _FIRST_STEP_REUSE = os.environ.get("ISHAP_FIRST_STEP_REUSE", "1") == "1"
 
 
-class _DragKernelsBase:
-    """What the solo and the batched kernels object share: the dimensions of the tap, the channel map and the loss scale."""
-
-    def __init__(self, device, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str):
-        self.device = th.device(device)
-        self.W, self.ld, self.r, self.voxel = W, ld, r, float(voxel)
-        self.l1 = 1 if loss_type == "l1" else 0
-        self.chmap = th.as_tensor(np.asarray(chmap), dtype=th.int32).reshape(3, -1).contiguous().to(self.device)
-        self.Cc = self.chmap.shape[1]
-        self.bits = th.zeros(1, dtype=th.int32, device=self.device)
-        self.scale2 = th.ones(2, dtype=th.float32, device=self.device)
-        self.sources = self.targets = None
-        self._L = _lib.lib()
-        # closed loop (retarget): `targets` stays the final targets; the loss reads the goals at _aim_ptr once a retarget has run
-        self.goals = self.remaining = self.arrived = self.done = None
-        self._aim_ptr = None
-        self._aim_keep = None         # whatever owns the memory at _aim_ptr when that is not self.goals (the loop's table)
-
-    def _call(self, name: str, *args):
-        _lib.call(self.device, name, *args)
-
-    def _targets_ptr(self) -> int:
-        """What the loss kernels read as targets: the final targets, or the goals of the last retarget."""
-        return self.targets.data_ptr() if self._aim_ptr is None else self._aim_ptr
-
-    def _reset_aim(self):
-        self.goals = self.remaining = self.arrived = self.done = None
-        self._aim_ptr = self._aim_keep = None
-
-    def retarget(self, K, step, arrive):
-        """Re-aim the loss (ishap_drag_retarget / ishap_drag_batch_retarget) after setup(): K int [H, 3], each
-        handle's tracked voxel offset from its source; step > 0 (may be inf), the lead in voxels; arrive >= 0 (the batched object
-        also takes one of each per edit).  Writes the object's goals buffer [H, 3], which every later loss call reads in place of
-        the targets, and rebuilds the touched sets and mask counts for it; `targets` stays the final targets.  Returns (goals,
-        remaining [H] float32, arrived [H] int32, done [edits] int32), device tensors the next call overwrites."""
-        if self.sources is None:
-            raise RuntimeError("retarget: call setup() first")
-        H, E = self.sources.shape[0], getattr(self, "E", 1)
-        K = _lib.tensor(K, th.int32, self.device)
-        if tuple(K.shape) != (H, 3):
-            raise ValueError(f"retarget: K must be [{H}, 3], got {tuple(K.shape)}")
-        if self.goals is None:
-            self.goals = th.empty((H, 3), dtype=th.float32, device=self.device)
-            self.remaining = th.empty(H, dtype=th.float32, device=self.device)
-            self.arrived = th.empty(H, dtype=th.int32, device=self.device)
-            self.done = th.empty(E, dtype=th.int32, device=self.device)
-        self.retarget_raw(K.data_ptr(), self.goals.data_ptr(), self.remaining.data_ptr(), self.arrived.data_ptr(),
-                          self.done.data_ptr(), step, arrive)
-        return self.goals, self.remaining, self.arrived, self.done
-
-    def retarget_raw(self, k: int, goals: int, remaining: int, arrived: int, done: int, step, arrive):
-        """retarget() on device addresses (the guided loop's form: rows of its tables; no tensor is made per step).  The loss
-        calls that follow read `goals`."""
-        keep, self._aim_ptr = self._aim_ptr, goals
-        try:
-            self._retarget_call(k, remaining, arrived, done, step, arrive)
-        except Exception:
-            self._aim_ptr = keep          # refused before any launch: the loss keeps reading what it read
-            raise
-
-    def _weight_map(self, w):
-        """A region weight map (regions.plane_weights) as the kernels read it: float32 [3, W, W] on the device."""
-        return check_weight_map(w, self.W).to(device=self.device).contiguous()
-
-
 def check_weight_map(w, W: int) -> th.Tensor:
     """A [3, W, W] map of finite weights >= 0 (tensor or array) -> a float32 tensor; ValueError otherwise."""
     w = w.detach() if th.is_tensor(w) else th.as_tensor(np.asarray(w))
@@ -180,72 +115,6 @@ def check_region_cof(cof: float, has_regions: bool, what: str = "cof"):
     """Regions act on the preservation term only, and with cof <= 0 there is none."""
     if has_regions and not cof > 0:
         raise ValueError(f"{what} = {cof}: keep / free regions and weights scale the preservation term, which needs cof > 0")
-
-
-class DragKernels(_DragKernelsBase):
-    """Device state + calls for the drag loss (drag_utils.py:309-334 setup, :355-383 per step)."""
-
-    def __init__(self, device, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str = "l2"):
-        super().__init__(device, W, ld, chmap, r, voxel, loss_type)
-        self.touched = th.zeros(3 * W * W, dtype=th.uint8, device=self.device)
-        self.nmask = th.zeros(1, dtype=th.int32, device=self.device)
-        self.chan_weight = th.zeros(3 * ld, dtype=th.uint8, device=self.device)
-        self.acc = th.zeros(2, dtype=th.int64, device=self.device)
-        self.gfx = th.zeros(W * W * ld, dtype=th.int64, device=self.device)     # fixed-point scatter scratch
-        self.grad = th.empty((W * W, ld), dtype=th.float32, device=self.device)
-        self.loss = th.zeros(1, dtype=th.float32, device=self.device)
-        self.cot = th.empty((W * W, ld), dtype=th.float16, device=self.device)
-        self.cof = 0.0
-        self.weights = None
-
-    def _args(self) -> _lib.DragArgsC:
-        return _lib.DragArgsC(self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
-                              self._targets_ptr(), self.sources.shape[0], self.r, self.voxel, float(self.cof),
-                              self.l1, self.touched.data_ptr(), self.nmask.data_ptr(), self.acc.data_ptr(), self.gfx.data_ptr(),
-                              self.chan_weight.data_ptr(), _lib.ptr(self.weights))
-
-    def setup(self, sources, targets, cof: float, weights=None):
-        """weights: None, or a [3, W, W] map of the preservation term's per-texel weights (regions.plane_weights); needs cof > 0.
-        A map selects the weighted gather kernel; a map of ones gives bitwise the results of None."""
-        check_region_cof(float(cof), weights is not None)
-        self.weights = None if weights is None else self._weight_map(weights)
-
-        def pts(v):
-            v = v.detach() if th.is_tensor(v) else th.as_tensor(np.asarray(v))
-            return v.to(device=self.device, dtype=th.float32).reshape(-1, 3).contiguous()
-        self.sources, self.targets = pts(sources), pts(targets)
-        assert self.sources.shape[0] == self.targets.shape[0]
-        self.cof = float(cof)
-        self._reset_aim()
-        self._call("ishap_drag_setup", C.byref(self._args()))
-
-    def _retarget_call(self, k, remaining, arrived, done, step, arrive):
-        self._call("ishap_drag_retarget", C.byref(self._args()), self.targets.data_ptr(), k, float(step), float(arrive),
-                   remaining, arrived, done)
-
-    def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int):
-        self._call("ishap_drag_loss_grad", C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
-                   self.loss.data_ptr())
-        return self.grad, self.loss
-
-    def loss_grad(self, edit: th.Tensor, orig: th.Tensor):
-        assert edit.dtype == th.float16 and orig.dtype == th.float16 and edit.is_contiguous() and orig.is_contiguous()
-        return self.loss_grad_ptr(edit.data_ptr(), orig.data_ptr())
-
-    def loss_cotangent_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int = 0, loss_out=None):
-        """loss + gradient + scaled fp16 cotangent in one call (three launches); `loss_out`: a device float to write the loss to;
-        `orig_stride`: the batched object's argument, 0 here (one edit reads one guidance tap)."""
-        assert orig_stride == 0
-        loss = self.loss if loss_out is None else loss_out
-        self._call("ishap_drag_loss_cotangent", C.byref(self._args()), edit_ptr, orig_ptr, self.grad.data_ptr(),
-                   loss.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(), self.scale2.data_ptr())
-        return self.cot, self.scale2
-
-    def scaled_cotangent(self):
-        """fp32 gradient -> fp16 cotangent * 2^k (k from max|g|) so the fp16 backward neither under- nor overflows."""
-        self._call("ishap_grad_to_scaled_f16", self.grad.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(),
-                   self.scale2.data_ptr(), self.grad.numel())
-        return self.cot, self.scale2
 
 
 def pack_handles(sources, targets):
@@ -305,12 +174,20 @@ def per_edit_region(value, K: int, name: str) -> list:
     return list(value)
 
 
-class BatchDragKernels(_DragKernelsBase):
-    """Device state + calls of the drag loss for E edits at once (ishap_drag_batch_*): one scratch buffer, one loss scale."""
+class BatchDragKernels:
+    """Device state + calls of the drag loss for E edits at once (ishap_drag_batch_*): one scratch buffer, one loss scale.  One
+    edit is E = 1 (DragKernels below)."""
 
     def __init__(self, device, E: int, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str = "l2"):
-        super().__init__(device, W, ld, chmap, r, voxel, loss_type)
-        self.E = int(E)
+        self.device = th.device(device)
+        self.E, self.W, self.ld, self.r, self.voxel = int(E), W, ld, r, float(voxel)
+        self.l1 = 1 if loss_type == "l1" else 0
+        self.chmap = th.as_tensor(np.asarray(chmap), dtype=th.int32).reshape(3, -1).contiguous().to(self.device)
+        self.Cc = self.chmap.shape[1]
+        self.bits = th.zeros(1, dtype=th.int32, device=self.device)
+        self.scale2 = th.ones(2, dtype=th.float32, device=self.device)
+        self.sources = self.targets = self.weights = None
+        self._L = _lib.lib()
         nbytes = int(self._L.ishap_drag_batch_scratch_bytes(self.E, W, ld))
         if nbytes <= 0:
             raise ValueError(f"drag batch: bad dimensions E={E}, W={W}, ld={ld}")
@@ -318,7 +195,22 @@ class BatchDragKernels(_DragKernelsBase):
         self.grad = th.empty((self.E, W * W, ld), dtype=th.float32, device=self.device)
         self.loss = th.zeros(self.E, dtype=th.float32, device=self.device)
         self.cot = th.empty((self.E, W * W, ld), dtype=th.float16, device=self.device)
-        self.weights = None
+        # closed loop (retarget): `targets` stays the final targets; the loss reads the goals at _aim_ptr once a retarget has run
+        self.goals = self.remaining = self.arrived = self.done = None
+        self._aim_ptr = None
+        self._aim_keep = None         # whatever owns the memory at _aim_ptr when that is not self.goals (the loop's table)
+
+    def _call(self, name: str, *args):
+        _lib.call(self.device, name, *args)
+
+    def _targets_ptr(self) -> int:
+        """What the loss kernels read as targets: the final targets, or the goals of the last retarget."""
+        return self.targets.data_ptr() if self._aim_ptr is None else self._aim_ptr
+
+    def _args(self, orig_stride: int = 0) -> _lib.DragBatchArgsC:
+        return _lib.DragBatchArgsC(self.E, self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
+                                   self._targets_ptr(), self._offs, self.r, self.voxel, self._cof, self.l1, int(orig_stride),
+                                   self.scratch.data_ptr(), self.scratch.numel(), _lib.ptr(self.weights), 3 * self.W * self.W)
 
     def setup(self, sources, targets, cof, weights=None):
         """sources / targets: lists of E handle arrays; cof: a float or E floats; weights: None, or a list of E entries, each None
@@ -327,6 +219,10 @@ class BatchDragKernels(_DragKernelsBase):
         src, tgt, offs = pack_handles(sources, targets)
         if len(offs) - 1 != self.E:
             raise ValueError(f"{len(offs) - 1} edits given to drag kernels set up for {self.E}")
+        self._setup(src.to(self.device), tgt.to(self.device), offs, cof, weights)
+
+    def _setup(self, src, tgt, offs, cof, weights):
+        """setup() on packed handles: src / tgt float32 [H, 3] on the device, offs the E + 1 CSR offsets."""
         cofs = per_edit(cof, self.E, "cof")
         self.weights = None
         if weights is not None:
@@ -335,33 +231,59 @@ class BatchDragKernels(_DragKernelsBase):
                 raise ValueError(f"weights: {len(weights)} entries for {self.E} edits (give one map or None per edit)")
             for e, w in enumerate(weights):
                 check_region_cof(cofs[e], w is not None, f"cof[{e}]")
-            if any(w is not None for w in weights):
+            maps = [None if w is None else check_weight_map(w, self.W).to(device=self.device).contiguous() for w in weights]
+            if self.E == 1 and maps[0] is not None:
+                self.weights = maps[0][None]          # one edit reads its map where it is
+            elif any(m is not None for m in maps):
                 self.weights = th.ones((self.E, 3, self.W, self.W), dtype=th.float32, device=self.device)
-                for e, w in enumerate(weights):
-                    if w is not None:
-                        self.weights[e].copy_(self._weight_map(w))
-        self.sources, self.targets = src.to(self.device), tgt.to(self.device)
+                for e, m in enumerate(maps):
+                    if m is not None:
+                        self.weights[e].copy_(m)
+        self.sources, self.targets = src, tgt
         self.offsets = list(offs)
         self._offs = (C.c_int * (self.E + 1))(*offs)
         self.cof = cofs
         self._cof = (C.c_float * self.E)(*self.cof)
-        self._reset_aim()
-        self._call("ishap_drag_batch_setup", C.byref(self._args(0)))
+        self.goals = self.remaining = self.arrived = self.done = None
+        self._aim_ptr = self._aim_keep = None
+        self._call("ishap_drag_batch_setup", C.byref(self._args()))
 
-    def _retarget_call(self, k, remaining, arrived, done, step, arrive):
-        each = [not isinstance(v, (int, float, np.floating, np.integer)) for v in (step, arrive)]
-        if any(each):           # one lead / arrival radius per edit
-            st, ar = per_edit(step, self.E, "step"), per_edit(arrive, self.E, "arrive")
-            self._call("ishap_drag_batch_retarget_each", C.byref(self._args(0)), self.targets.data_ptr(), k,
-                       (C.c_float * self.E)(*st), (C.c_float * self.E)(*ar), remaining, arrived, done)
-        else:
-            self._call("ishap_drag_batch_retarget", C.byref(self._args(0)), self.targets.data_ptr(), k, float(step),
-                       float(arrive), remaining, arrived, done)
+    def retarget(self, K, step, arrive):
+        """Re-aim the loss (ishap_drag_batch_retarget) after setup(): K int [H, 3], each handle's tracked voxel
+        offset from its source; step > 0 (may be inf), the lead in voxels; arrive >= 0 (each a float, or one value per edit).
+        Writes the object's goals buffer [H, 3], which every later loss call reads in place of the targets, and rebuilds the
+        touched sets and mask counts for it; `targets` stays the final targets.  Returns (goals, remaining [H] float32, arrived [H]
+        int32, done [E] int32), device tensors the next call overwrites."""
+        if self.sources is None:
+            raise RuntimeError("retarget: call setup() first")
+        H = self.sources.shape[0]
+        K = _lib.tensor(K, th.int32, self.device)
+        if tuple(K.shape) != (H, 3):
+            raise ValueError(f"retarget: K must be [{H}, 3], got {tuple(K.shape)}")
+        if self.goals is None:
+            self.goals = th.empty((H, 3), dtype=th.float32, device=self.device)
+            self.remaining = th.empty(H, dtype=th.float32, device=self.device)
+            self.arrived = th.empty(H, dtype=th.int32, device=self.device)
+            self.done = th.empty(self.E, dtype=th.int32, device=self.device)
+        self.retarget_raw(K.data_ptr(), self.goals.data_ptr(), self.remaining.data_ptr(), self.arrived.data_ptr(),
+                          self.done.data_ptr(), step, arrive)
+        return self.goals, self.remaining, self.arrived, self.done
 
-    def _args(self, orig_stride: int) -> _lib.DragBatchArgsC:
-        return _lib.DragBatchArgsC(self.E, self.W, self.ld, self.Cc, self.chmap.data_ptr(), self.sources.data_ptr(),
-                                   self._targets_ptr(), self._offs, self.r, self.voxel, self._cof, self.l1, int(orig_stride),
-                                   self.scratch.data_ptr(), self.scratch.numel(), _lib.ptr(self.weights), 3 * self.W * self.W)
+    def retarget_raw(self, k: int, goals: int, remaining: int, arrived: int, done: int, step, arrive):
+        """retarget() on device addresses (the guided loop's form: rows of its tables; no tensor is made per step).  The loss
+        calls that follow read `goals`."""
+        keep, self._aim_ptr = self._aim_ptr, goals
+        try:
+            if any(not isinstance(v, (int, float, np.floating, np.integer)) for v in (step, arrive)):     # one lead / arrival radius per edit
+                st, ar = per_edit(step, self.E, "step"), per_edit(arrive, self.E, "arrive")
+                self._call("ishap_drag_batch_retarget_each", C.byref(self._args()), self.targets.data_ptr(), k,
+                           (C.c_float * self.E)(*st), (C.c_float * self.E)(*ar), remaining, arrived, done)
+            else:
+                self._call("ishap_drag_batch_retarget", C.byref(self._args()), self.targets.data_ptr(), k, float(step),
+                           float(arrive), remaining, arrived, done)
+        except Exception:
+            self._aim_ptr = keep          # refused before any launch: the loss keeps reading what it read
+            raise
 
     def scratch_parts(self) -> dict:
         """Views of the scratch buffer as api.hip carves it (every part on a 256-byte boundary): gfx int64 [E, W*W*ld], acc int64
@@ -377,18 +299,58 @@ class BatchDragKernels(_DragKernelsBase):
                 "nmask": s[o_nmask:o_nmask + E * 4].view(th.int32), "touched": s[o_touched:o_touched + E * 3 * W * W].reshape(E, -1),
                 "chan_weight": s[o_chw:o_chw + 3 * ld]}
 
-    def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int):
+    def loss_grad_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int = 0):
         """edit: [E][W*W][ld] fp16; orig: edit e's guidance at orig + e * orig_stride halfs (0: one guidance for all edits)."""
         self._call("ishap_drag_batch_loss_grad", C.byref(self._args(orig_stride)), edit_ptr, orig_ptr, self.grad.data_ptr(),
                    self.loss.data_ptr())
         return self.grad, self.loss
 
-    def loss_cotangent_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int, loss_out=None):
+    def loss_grad(self, edit: th.Tensor, orig: th.Tensor):
+        """loss_grad_ptr on tensors: edit the E taps, orig E guidance taps or one for all edits."""
+        assert edit.dtype == th.float16 and orig.dtype == th.float16 and edit.is_contiguous() and orig.is_contiguous()
+        n = self.W * self.W * self.ld
+        assert edit.numel() == self.E * n and orig.numel() in (n, self.E * n)
+        return self.loss_grad_ptr(edit.data_ptr(), orig.data_ptr(), 0 if orig.numel() == n else n)
+
+    def loss_cotangent_ptr(self, edit_ptr: int, orig_ptr: int, orig_stride: int = 0, loss_out=None):
         """losses + gradients + the batch's fp16 cotangent (one loss scale, scale2) in three launches; `loss_out`: device float[E]."""
         loss = self.loss if loss_out is None else loss_out
         self._call("ishap_drag_batch_loss_cotangent", C.byref(self._args(orig_stride)), edit_ptr, orig_ptr,
                    self.grad.data_ptr(), loss.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(), self.scale2.data_ptr())
         return self.cot, self.scale2
+
+    def scaled_cotangent(self):
+        """fp32 gradient -> fp16 cotangent * 2^k (k from max|g|) so the fp16 backward neither under- nor overflows."""
+        self._call("ishap_grad_to_scaled_f16", self.grad.data_ptr(), self.cot.data_ptr(), self.bits.data_ptr(),
+                   self.scale2.data_ptr(), self.grad.numel())
+        return self.cot, self.scale2
+
+
+class DragKernels(BatchDragKernels):
+    """One edit (drag_utils.py:309-334 setup, :355-383 per step): BatchDragKernels with E = 1, set up from one handle array, one
+    cof and one map, its buffers seen without the edit axis (the same memory)."""
+
+    def __init__(self, device, W: int, ld: int, chmap, r: int, voxel: float, loss_type: str = "l2"):
+        super().__init__(device, 1, W, ld, chmap, r, voxel, loss_type)
+        self.grad, self.cot = self.grad[0], self.cot[0]
+        part = self.scratch_parts()
+        self.touched, self.gfx, self.acc = part["touched"][0], part["gfx"][0], part["acc"][0]
+        self.nmask, self.chan_weight = part["nmask"], part["chan_weight"]
+
+    def setup(self, sources, targets, cof: float, weights=None):
+        """weights: None, or a [3, W, W] map of the preservation term's per-texel weights (regions.plane_weights); needs cof > 0.
+        A map selects the weighted gather kernel; a map of ones gives bitwise the results of None.  Handles already on the
+        device stay there: one edit needs no packing, so nothing comes back to the host."""
+        check_region_cof(float(cof), weights is not None)
+
+        def pts(v):
+            v = v.detach() if th.is_tensor(v) else th.as_tensor(np.asarray(v))
+            return v.to(device=self.device, dtype=th.float32).reshape(-1, 3).contiguous()
+        src, tgt = pts(sources), pts(targets)
+        if src.shape[0] != tgt.shape[0] or src.shape[0] == 0:
+            raise ValueError(f"{src.shape[0]} sources and {tgt.shape[0]} targets (need the same, non-zero count)")
+        self._setup(src, tgt, [0, src.shape[0]], float(cof), None if weights is None else [weights])
+        self.weights = None if self.weights is None else self.weights[0]
 
 
 Track = collections.namedtuple("Track", "offsets positions dist dist0 volume")
@@ -1076,7 +1038,7 @@ class DragStuff:
         if not has:
             return None
         return regions.plane_weights(keep=keep, free=free, W=width, keep_weight=keep_weight, free_weight=free_weight,
-                                     dilate=region_dilate, device=self.device, **({} if region_falloff == 0 else {"falloff": region_falloff}))
+                                     dilate=region_dilate, device=self.device, falloff=region_falloff)
 
     def _volume_constraints(self, scale, volume_keep, carve, fill, volume_scale, volume_points, volume_res):
         """-> (constraints.VolumeConstraints, volume_scale / scale), or (None, 0.0) when the edit has none: no region given, or
@@ -1104,10 +1066,6 @@ class DragStuff:
         cons = constraints.volume_constraints(keep=volume_keep, carve=carve, fill=fill, reference_logits_fn=ref, D=int(volume_res),
                                               max_points=int(volume_points), device=self.device)
         return cons, vs / float(scale)
-
-    def _closed_loop(self, dk, trk, copts):
-        """The re-aiming state of one guided loop; runs the retarget on the tracker's row of zeros (after dk.setup)."""
-        return _ClosedLoop(dk, trk, copts)
 
     def _loop_track(self, topts, width, ch, sources):
         """The tracking state of one guided loop, or None when tracking is off."""
@@ -1164,34 +1122,71 @@ class DragStuff:
         constraints with scale = 0 are a ValueError.  A constrained edit costs one full-depth backward more per step and neither
         uses nor takes the first-step snapshot (an earlier one stays valid).  last_volume_losses: L_vol of every step, device
         scalars.  track and closed_loop work as without constraints."""
-        copts = closed_loop_options(closed_loop)
-        topts = track_options(closed_loop_track(copts, track))
-        if self.args.num_samples > 1:
+        yield from self._edits([sources], [targets], [scale], [cof], [keep], [free], [keep_weight], [free_weight], [region_dilate],
+                               [weights], track, closed_loop, [region_falloff], one=True,
+                               volume=(volume_keep, carve, fill, volume_scale, volume_points, volume_res))
+
+    def _edits(self, sources, targets, scale, cof, keep, free, keep_weight, free_weight, region_dilate, weights, track, closed_loop,
+               region_falloff, one=False, volume=None):
+        """The edit of training() and training_batch(): K edits in one guided loop, the arguments as training_batch() takes them.
+        `one`: training()'s edit -- the single shape (self.w), a single closed_loop setting, a DragKernels kept as self._dk, the
+        float guidance scale (the single-scale step kernel), the first-step reuse, `volume` (the arguments of _volume_constraints
+        after scale), and afterwards self.sources / self.targets, last_track as one dict and get_mesh."""
+        if one and self.args.num_samples > 1:
             raise NotImplementedError("We can handle only one shape at each time!")
+        if len(sources) != len(targets):
+            raise ValueError(f"{len(sources)} source sets but {len(targets)} target sets: one of each per edit")
+        K = len(sources)
+        copts = closed_loop_options(closed_loop, None if one else K)
+        topts = track_options(closed_loop_track(copts, track))
+        check_edit_count(K, self.max_edits)
+        scales = per_edit(scale, K, "scale")
+        cofs = per_edit(cof, K, "cof")
         ch, width = self.model.tap_shape(self.args.feat_layer)
-        wmap = self._region_weights(width, cof, keep, free, keep_weight, free_weight, region_dilate, weights, region_falloff=region_falloff)
-        cons, ratio = self._volume_constraints(scale, volume_keep, carve, fill, volume_scale, volume_points, volume_res)
-        self.sources = th.tensor(np.asarray(sources), device=self.device, dtype=th.float32)
-        self.targets = th.tensor(np.asarray(targets), device=self.device, dtype=th.float32)
-        assert self.sources.shape[0] == self.targets.shape[0]
-        img = self.w.clone().detach()
-        dk = DragKernels(self.device, W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size,
-                         loss_type=self.args.loss_type)
-        dk.setup(self.sources, self.targets, cof, **({} if wmap is None else {"weights": wmap}))    # a plain edit: the call it always was
-        self._dk = dk
-        trk = self._loop_track(topts, width, ch, [self.sources])
-        cl = None if copts is None else self._closed_loop(dk, trk, copts)
+        keeps, frees, maps = (per_edit_region(v, K, n) for v, n in ((keep, "keep"), (free, "free"), (weights, "weights")))
+        kws, fws = per_edit(keep_weight, K, "keep_weight"), per_edit(free_weight, K, "free_weight")
+        dils = per_edit_any(region_dilate, K, "region_dilate")
+        falls = per_edit_any(region_falloff, K, "region_falloff")
+        wmaps = [self._region_weights(width, cofs[k], keeps[k], frees[k], kws[k], fws[k], dils[k], maps[k], "cof" if one else f"cof[{k}]",
+                                      falls[k]) for k in range(K)]
+        cons, ratio = self._volume_constraints(scales[0], *volume) if one else (None, 0.0)
+        if self.w_batch is not None and not one:
+            if self.w_batch.shape[0] != K:
+                raise ValueError(f"{K} edits for the {self.w_batch.shape[0]} shapes of update_latent_params_batch")
+            img = self.w_batch.clone().detach()
+            guidance, stride = self.feature_guidance_batch, width * width * ch
+        else:
+            if self.w is None:
+                raise RuntimeError("an edit needs update_latent_params (variants of one shape) or update_latent_params_batch first")
+            img = self.w.clone().detach() if one else self.w.expand(K, *self.w.shape[1:]).contiguous()
+            guidance, stride = self.feature_guidance, 0
+        dims = dict(W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size, loss_type=self.args.loss_type)
+        # an edit without regions makes the call it always made: setup(sources, targets, cof)
+        regions = {} if all(w is None for w in wmaps) else {"weights": wmaps[0] if one else wmaps}
+        if one:           # the handles go up once, here; the kernels object takes them where they are
+            self.sources = th.tensor(np.asarray(sources[0]), device=self.device, dtype=th.float32)
+            self.targets = th.tensor(np.asarray(targets[0]), device=self.device, dtype=th.float32)
+            dk = self._dk = DragKernels(self.device, **dims)
+            dk.setup(self.sources, self.targets, cofs[0], **regions)
+        else:
+            dk = self._dk_batch = BatchDragKernels(self.device, K, **dims)
+            dk.setup(sources, targets, cofs, **regions)
+        trk = self._loop_track(topts, width, ch, sources)
+        cl = None if copts is None else _ClosedLoop(dk, trk, copts)       # runs the retarget on the tracker's row of zeros
         # the regions change the loss, not the forward: the first-step snapshot depends on the latent, the timestep and the weights
         # of the model only, so _first_step_key does not hold them and an edit with regions reuses the snapshot of a plain one
         # volume constraints need a full-depth backward, which a restored snapshot cannot give: that edit runs its first forward
         vol = None if cons is None else VolumeGuidance(self, cons, ratio)
-        img, stop_time = yield from self._guided_loop(img, dk, self.feature_guidance, 0, [float(scale)], float(scale), vol is None,
-                                                      **({} if trk is None else {"trk": trk}), **({} if cl is None else {"cl": cl}),
-                                                      **({} if vol is None else {"vol": vol}))
+        guided_scale = scales[0] if one else th.tensor(scales, dtype=th.float32, device=self.device)
+        img, stop_time = yield from self._guided_loop(img, dk, guidance, stride, scales, guided_scale, one and vol is None, trk, cl, vol)
         if trk is not None:
             res = trk.results() if cl is None else cl.results(trk.results())
-            self.last_track, self._track_ends = res[0], [(self.sources, self.targets)]
-        self.mesh = self.get_mesh(img=img, t=stop_time)
+            self.last_track = res[0] if one else res
+            self._track_ends = [(dk.sources[a:b], dk.targets[a:b]) for a, b in zip(dk.offsets[:-1], dk.offsets[1:])]
+        if one:
+            self.mesh = self.get_mesh(img=img, t=stop_time)
+        else:
+            self.get_meshes(img=img, t=stop_time)
 
     def training_part(self, part, rigid, handles=16, start=None, scale=600, cof=0.2, keep=None, keep_weight=4.0, free_weight=0.0,
                       region_dilate=0, track=None, closed_loop=None, margin=0.0, region_falloff=0.0, solid=False, volume_scale=None,
@@ -1211,7 +1206,7 @@ class DragStuff:
         the part moves to must fill (fill = plan.moved) and what it leaves must clear (carve = part & ~moved; none when the moved
         part covers the part).  self.part_solid then holds that pair as {"fill": Voxels, "carve": Voxels or None}."""
         from . import regions
-        self.part_plan = plan = regions.plan_part_edit(part, rigid, handles=handles, start=start, **({} if margin == 0 else {"margin": margin}))
+        self.part_plan = plan = regions.plan_part_edit(part, rigid, handles=handles, start=start, margin=margin)
         self.part_solid = None
         vkw = {}
         if solid:
@@ -1220,14 +1215,10 @@ class DragStuff:
             vkw = dict(fill=plan.moved, carve=self.part_solid["carve"], volume_scale=volume_scale, volume_points=volume_points,
                        volume_res=part.D)
         return self.training(plan.sources, plan.targets, scale=scale, cof=cof, keep=keep, free=plan.free, keep_weight=keep_weight,
-                             free_weight=free_weight, region_dilate=region_dilate, region_falloff=region_falloff,
-                             **({} if track is None else {"track": track}),
-                             **({} if closed_loop is None else {"closed_loop": closed_loop}), **vkw)
+                             free_weight=free_weight, region_dilate=region_dilate, region_falloff=region_falloff, track=track,
+                             closed_loop=closed_loop, **vkw)
 
     # ------------------------------------------------------------------ batched edits: K drag edits in one guided loop
-    def _check_edits(self, K: int):
-        check_edit_count(K, self.max_edits)
-
     def update_latent_params_batch(self, imgs, **kwargs):
         """update_latent_params for K shapes at once: imgs [K, 96, S, S].  Records w_batch [K, ...], one [K, S*S, C] guidance tap
         per guided step (feature_guidance_batch) and meshes0 (K meshes).  training_batch then edits shape k with edit k."""
@@ -1236,7 +1227,7 @@ class DragStuff:
         if not th.is_tensor(imgs) or imgs.dim() != 4:
             raise ValueError("update_latent_params_batch: imgs must be a [K, C, S, S] tensor or array")
         K = imgs.shape[0]
-        self._check_edits(K)
+        check_edit_count(K, self.max_edits)
         img = imgs.to(device=self.device, dtype=th.float32).contiguous()
         self.latent_code = img.clone().detach()
         self._shape_changed()
@@ -1289,44 +1280,8 @@ class DragStuff:
         if any(v is not None for v in (volume_keep, carve, fill, volume_scale)):
             raise NotImplementedError("volume constraints (volume_keep, carve, fill, volume_scale) are not available in training_batch: "
                                       "run such an edit with training()")
-        if len(sources) != len(targets):
-            raise ValueError(f"{len(sources)} source sets but {len(targets)} target sets: one of each per edit")
-        K = len(sources)
-        copts = closed_loop_options(closed_loop, K)
-        topts = track_options(closed_loop_track(copts, track))
-        self._check_edits(K)
-        scales = per_edit(scale, K, "scale")
-        cofs = per_edit(cof, K, "cof")
-        ch, width = self.model.tap_shape(self.args.feat_layer)
-        keeps, frees, maps = (per_edit_region(v, K, n) for v, n in ((keep, "keep"), (free, "free"), (weights, "weights")))
-        kws, fws = per_edit(keep_weight, K, "keep_weight"), per_edit(free_weight, K, "free_weight")
-        dils = per_edit_any(region_dilate, K, "region_dilate")
-        falls = per_edit_any(region_falloff, K, "region_falloff")
-        wmaps = [self._region_weights(width, cofs[k], keeps[k], frees[k], kws[k], fws[k], dils[k], maps[k], f"cof[{k}]", falls[k])
-                 for k in range(K)]
-        if self.w_batch is not None:
-            if self.w_batch.shape[0] != K:
-                raise ValueError(f"{K} edits for the {self.w_batch.shape[0]} shapes of update_latent_params_batch")
-            img = self.w_batch.clone().detach()
-            guidance, stride = self.feature_guidance_batch, width * width * ch
-        else:
-            if self.w is None:
-                raise RuntimeError("training_batch needs update_latent_params (variants of one shape) or update_latent_params_batch first")
-            img = self.w.expand(K, *self.w.shape[1:]).contiguous()
-            guidance, stride = self.feature_guidance, 0
-        dk = BatchDragKernels(self.device, K, W=width, ld=ch, chmap=feat_channel_map(ch), r=self.r1, voxel=self.voxel_size,
-                              loss_type=self.args.loss_type)
-        dk.setup(sources, targets, cofs, **({} if all(w is None for w in wmaps) else {"weights": wmaps}))
-        self._dk_batch = dk
-        trk = self._loop_track(topts, width, ch, sources)
-        cl = None if copts is None else self._closed_loop(dk, trk, copts)
-        scales_dev = th.tensor(scales, dtype=th.float32, device=self.device)
-        img, stop_time = yield from self._guided_loop(img, dk, guidance, stride, scales, scales_dev,
-                                                      **({} if trk is None else {"trk": trk}), **({} if cl is None else {"cl": cl}))
-        if trk is not None:
-            self.last_track = trk.results() if cl is None else cl.results(trk.results())
-            self._track_ends = [(dk.sources[a:b], dk.targets[a:b]) for a, b in zip(dk.offsets[:-1], dk.offsets[1:])]
-        self.get_meshes(img=img, t=stop_time)
+        yield from self._edits(sources, targets, scale, cof, keep, free, keep_weight, free_weight, region_dilate, weights, track,
+                               closed_loop, region_falloff)
 
     # ------------------------------------------------------------------ real shapes (:401-471, :552-566)
     def _cloud_samples(self, cloud, center, generator=None):

@@ -199,23 +199,25 @@ def _loop_dragstuff(monkeypatch, log):
     ds.feature_guidance = [torch.zeros(16, 16, dtype=torch.float16) for _ in range(3)]
     ds.get_mesh = lambda tri_feat=None, img=None, t=0: log.append(("get_mesh", float(img.mean()), t))
     ds.get_meshes = lambda img, t=0: log.append(("get_meshes", float(img.mean()), t))
-    loops = []
-    inner = du.DragStuff._guided_loop
+    loops, bodies = [], []
+    inner, body = du.DragStuff._guided_loop, du.DragStuff._edits
     monkeypatch.setattr(du.DragStuff, "_guided_loop", lambda self, *a: (loops.append(1), inner(self, *a))[1])
-    return ds, loops
+    monkeypatch.setattr(du.DragStuff, "_edits", lambda self, *a, **kw: (bodies.append(1), body(self, *a, **kw))[1])
+    return ds, loops, bodies
 
 
 def test_training_and_training_batch_drive_one_guided_loop(monkeypatch):
-    """Both entry points run DragStuff._guided_loop; for K = 1 the steps they issue differ in the guidance scale (a float
-    against a device tensor) and in nothing else -- same keyword set, same loss slot, same progress values."""
+    """Both entry points run the one edit body, DragStuff._edits, and through it DragStuff._guided_loop; for K = 1 the steps they
+    issue differ in the guidance scale (a float against a device tensor) and in nothing else -- same keyword set, same loss
+    slot, same progress values."""
     h = np.array([[0.1, 0.2, 0.3]], np.float32)
     runs = {}
     for name in ("training", "training_batch"):
         log = []
-        ds, loops = _loop_dragstuff(monkeypatch, log)
+        ds, loops, bodies = _loop_dragstuff(monkeypatch, log)
         args = (h, h + 0.1) if name == "training" else ([h], [h + 0.1])
         prog = list(getattr(ds, name)(*args, scale=50, cof=0.4))
-        assert loops == [1], name
+        assert loops == [1] and bodies == [1], name
         assert prog == [0.0, 0.5, 1.0] and len(ds.last_losses) == 3 and all(l.shape == (1,) for l in ds.last_losses)
         runs[name] = log
     solo, batch = runs["training"], runs["training_batch"]

@@ -49,7 +49,7 @@ def _solo(W, ld, chmap, r, voxel, loss_type, src, tgt, cof, edit, orig):
 @pytest.mark.parametrize("shared", [False, True])
 def test_batched_drag_loss_is_bitwise_the_solo_loss(gold, loss_type, shared):
     """E = 3 edits with 1, 3 and 2 handles and cof 0 / 0.2 / 0.4: per edit the loss and the fp32 gradient are bitwise those of
-    ishap_drag_loss_grad on that edit alone; the fp16 cotangent is the solo one times 2^(k_batch - k_solo) wherever it is a normal
+    the same edit alone (E = 1); the fp16 cotangent is the solo one times 2^(k_batch - k_solo) wherever it is a normal
     fp16 number; the batch's loss scale is the smallest solo scale; two calls give the same bits and leave the scratch zero."""
     from ishapediting_amd.drag_utils import BatchDragKernels
     g = gold("g7_drag")
@@ -112,9 +112,9 @@ def _touched_of(bk, E, W, ld):
 @pytest.mark.parametrize("loss_type", ["l2", "l1"])
 @pytest.mark.parametrize("cof", [0.0, 0.4])
 def test_one_edit_through_the_solo_and_the_batch_abi_gives_the_same_bits(gold, loss_type, cof):
-    """E = 1: ishap_drag_* (its own touched / nmask / acc / grad_fx / chan_weight buffers) against ishap_drag_batch_* (one carved
-    scratch) on the G7 edit -- the same kernels, so gradient, loss, cotangent, loss scale and both bits of the touched bitmap
-    are equal bit for bit."""
+    """E = 1: DragKernels, the one-edit face (one handle array, one cof, buffers seen without the edit axis), against
+    BatchDragKernels(..., 1, ...) on the G7 edit -- the same object underneath, so gradient, loss, cotangent, loss scale, both
+    bits of the touched bitmap, the mask count and chan_weight are equal bit for bit, and both leave the scratch zero."""
     from ishapediting_amd.drag_utils import BatchDragKernels, DragKernels
     g = gold("g7_drag")
     edit, chmap, ld = _tap_from_planes(T(g["edit"]))
@@ -134,7 +134,14 @@ def test_one_edit_through_the_solo_and_the_batch_abi_gives_the_same_bits(gold, l
     tb, ts = _touched_of(bk, 1, W, ld)[0], dk.touched
     assert int((ts & 1).sum()) > 0 and int((ts & 2).sum()) > 0
     assert torch.equal(tb & 1, ts & 1) and torch.equal(tb & 2, ts & 2)
-    # the separate calls of the solo ABI (loss_grad, then the generic scaling) give the fused call's bits too
+    pb = bk.scratch_parts()
+    assert torch.equal(pb["touched"][0], ts) and torch.equal(pb["nmask"], dk.nmask) and int(dk.nmask) > 0
+    assert torch.equal(pb["chan_weight"], dk.chan_weight) and int(dk.chan_weight.max()) > 0
+    for k in (bk, dk):                     # every loss call leaves the scatter buffer and the loss sums zero
+        p = k.scratch_parts()
+        assert int(p["gfx"].abs().max()) == 0 and int(p["acc"].abs().max()) == 0
+    assert int(dk.gfx.abs().max()) == 0 and int(dk.acc.abs().max()) == 0 and dk.gfx.data_ptr() == dk.scratch.data_ptr()
+    # the separate calls (loss_grad, then the generic scaling) give the fused call's bits too
     g2, l2_ = dk.loss_grad(e_d, o_d)
     g2, l2_ = g2.clone(), l2_.clone()
     cot2, sc2 = dk.scaled_cotangent()

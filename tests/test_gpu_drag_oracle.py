@@ -230,7 +230,7 @@ def test_loss_scale_is_a_power_of_two_over_the_whole_range():
 
 def test_cotangent_is_the_round_to_nearest_even_fp16_of_the_scaled_gradient():
     """A random buffer with magnitudes over thirty octaves (fp16 subnormals and zeros at the low end), and case A through the fused
-    ishap_drag_loss_cotangent."""
+    loss + cotangent call."""
     from ishapediting_amd.drag_utils import DragKernels
     c = R.make_case("A")
     dk = DragKernels(dev(), W=c.W, ld=c.ld, chmap=c.chmap, r=c.r, voxel=c.voxel)

@@ -209,7 +209,7 @@ def test_invalid_arguments_error_before_any_launch():
 
     for form in ("solo", "batch"):
         dk = _solo_kernels(c, 0) if form == "solo" else _batch_kernels(c)
-        fn = L.ishap_drag_retarget if form == "solo" else L.ishap_drag_batch_retarget
+        fn = L.ishap_drag_batch_retarget               # one edit: the same entry with E = 1
         K = torch.zeros(B, 3, dtype=torch.int32, device=dev())
         goals, rem, arr, done = sentinels()
         before = _state(dk)
@@ -217,7 +217,7 @@ def test_invalid_arguments_error_before_any_launch():
         def call(step, arrive, final=dk.targets, k=K, outs=None):
             g, r_, a_, d_ = outs or (goals, rem, arr, done)
             dk._aim_ptr = g.data_ptr()                 # the struct's `targets`: the goals buffer the call writes
-            args = dk._args() if form == "solo" else dk._args(0)
+            args = dk._args()
             return fn(C.byref(args), _lib.ptr(final), _lib.ptr(k), step, arrive, _lib.ptr(r_), _lib.ptr(a_), _lib.ptr(d_), sp)
         for step, arrive, word in ((0.0, 1.0, b"step"), (-2.0, 1.0, b"step"), (float("nan"), 1.0, b"step"), (1.0, -0.5, b"arrive"),
                                    (1.0, float("nan"), b"arrive")):

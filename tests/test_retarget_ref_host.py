@@ -129,7 +129,7 @@ def test_abi_22_exports_the_retarget_calls():
     from ishapediting_amd import _lib
     L = _lib.lib()
     assert int(L.ishap_version()) >= 22
-    assert hasattr(L, "ishap_drag_retarget") and hasattr(L, "ishap_drag_batch_retarget")
+    assert hasattr(L, "ishap_drag_batch_retarget") and hasattr(L, "ishap_drag_batch_retarget_each")
 
 
 # ------------------------------------------------------------------------------------------------ the keyword

@@ -4,7 +4,7 @@ and closed-loop with a stop that never fires.
 
   python tools/closed_loop_bench.py [--reps 4] [--warmup 1] [--call-reps 200] [--skip-edit]
 
-Call: DragKernels.retarget_raw (ishap_drag_retarget: one launch of one 1024-thread workgroup) on prepared buffers at W = 64,
+Call: DragKernels.retarget_raw (ishap_drag_batch_retarget with E = 1: one launch of one 1024-thread workgroup) on prepared buffers at W = 64,
 ld = 512, r = 12, voxel = 2 / 256, for 1 / 4 / 16 handles with a lead of 2 voxels, between two device events (median of `call-reps`
 calls after 10 warm-up calls), and as the time per call of 50 calls enqueued back to back between two events
 (`burst_ms_per_call`: the larger of the device's time per call and the host's time to enqueue one).  Next to them the lattice

@@ -1,8 +1,9 @@
 """One sha256 per output of the drag loss kernels on fixed inputs, to compare two builds of the library bit for bit:
 gradient, loss, cotangent, scale2 and the touched bitmap of
-  * the solo ABI (ishap_drag_setup / _loss_cotangent) on the four G7 cases (l2 / l1, cof 0 / 0.4; tests/golden/g7_drag.npz),
-  * the batch ABI on the E = 3 case of tests/test_gpu_batched_drag.py (1, 3 and 2 handles, cof 0 / 0.2 / 0.4, own guidance),
-  * the solo ABI at full size (W = 64, ld = 512, feat_channel_map(512), DragStuff's r1 = 12 and voxel = 2 / 256, three seeded
+  * one edit (DragKernels: ishap_drag_batch_setup / _loss_cotangent with E = 1) on the four G7 cases (l2 / l1, cof 0 / 0.4;
+    tests/golden/g7_drag.npz),
+  * a batch on the E = 3 case of tests/test_gpu_batched_drag.py (1, 3 and 2 handles, cof 0 / 0.2 / 0.4, own guidance),
+  * one edit at full size (W = 64, ld = 512, feat_channel_map(512), DragStuff's r1 = 12 and voxel = 2 / 256, three seeded
     handles, seeded fp16 taps, cof 0.2).
 Run it once per installed library and diff the outputs.  Usage: python tools/drag_bits.py"""
 import hashlib
@@ -69,9 +70,7 @@ def main():
         e_d, o_d = edits.to(dev).contiguous(), origs.to(dev).contiguous()
         cot, sc = bk.loss_cotangent_ptr(e_d.data_ptr(), o_d.data_ptr(), W * W * ld)
         torch.cuda.synchronize()
-        up = lambda v: (v + 255) // 256 * 256       # the carve rule of ishap_drag_batch_scratch_bytes
-        o_touched = up(up(up(E * W * W * ld * 8) + 16 * E) + 4 * E)
-        report(f"batch E=3 {lt}", bk.grad, bk.loss, cot, sc, bk.scratch[o_touched:o_touched + E * 3 * W * W])
+        report(f"batch E=3 {lt}", bk.grad, bk.loss, cot, sc, bk.scratch_parts()["touched"])
     # full size
     W, ld = 64, 512
     gen = torch.Generator().manual_seed(23)
