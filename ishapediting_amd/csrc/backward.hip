@@ -23,25 +23,30 @@ static int gn_bwd_op(Exec& e, GnBwdArgs g) {
 // `gb`: the GroupNorm whose activation this gradient arrives at, at the same resolution (GB_SAME) -- its per-channel
 // backward sums are then accumulated in this launch's epilogue (gb->csums allocated here, gb->sums_ready set).
 // `may_pend`: the only reader of dx_out is a group-local GroupNorm-backward pass, which adds up split-K slices itself.
-static int dgrad_op(Exec& e, const ConvW& c, const Tensor& dy, Tensor& dx_out, int n_out, GnBwdArgs* gb = nullptr,
+static int dgrad_op(Exec& e, const ConvW& c, const Tensor& dy, Flow& dx_out, int n_out, GnBwdArgs* gb = nullptr,
                     bool may_pend = false) {
-  dx_out = Tensor{nullptr, dy.N, dy.H, dy.W, n_out};
-  ISHAP_ALLOC(dx_out.p, e, dx_out.numel());
+  dx_out = Flow{shaped(dy, n_out)};
+  ISHAP_ALLOC(dx_out.t.p, e, dx_out.t.numel());
   if (gb) {
     ISHAP_SALLOC(gb->csums, e, (size_t)gb->N * gb->C * 2);
     gb->sums_ready = 1;
     ISHAP_REQUIRE(gb->C == n_out && gb->gmode == GB_SAME, "fused GroupNorm-backward sums need the gradient at the GN resolution");
   }
-  ConvLaunch k = conv_launch(dy, c, dx_out);
+  ConvLaunch k = conv_launch(dy, c, dx_out.t);
   k.Wt = c.wT; k.kpad = c.cout_pad; k.cout = n_out; k.bias = nullptr;      // the transposed operand: dy's channels are its K
   k.gb = gb; k.pend_out = may_pend ? &dx_out.pend : nullptr;
   return conv_op(e, k);
 }
+// the same for a reader that is no GroupNorm-backward pass (`who`: the skip convolution, proj_out, the stem): a finished tensor
+static int dgrad_tensor(Exec& e, const ConvW& c, const Tensor& dy, Tensor& dx_out, int n_out, const char* who) {
+  Flow f;
+  ISHAP_TRY(dgrad_op(e, c, dy, f, n_out));
+  return finished(f, who, dx_out);
+}
 
 // group-local input gradient of act(film(GN(x))) on a small map; the upstream gradient `up` (g.g) may still be pending (norm_local.hip)
-static int gn_bwd_local_op(Exec& e, const GnBwdArgs& g, Tensor& up) {
-  const SlabSrc slab = up.pend;
-  up.pend = SlabSrc{};
+static int gn_bwd_local_op(Exec& e, const GnBwdArgs& g, Flow& up) {
+  const SlabSrc slab = up.take();
   long long* rec = nullptr;
   ISHAP_SALLOC(rec, e, (size_t)g.N * 32 * GN_REC_STRIDE);       // zeroed with the rest of the statistics arena
   const GnBwdLocalArgs a = gn_bwd_local_fill(g, slab, exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr);   // see gn_local_op
@@ -53,18 +58,20 @@ static bool local_gn_bwd(const GnBwdArgs& g) { return gn_route(g.H * g.W, g.C, g
 // weights, FiLM row, shape, gmode).  The route is a function of g's shape alone, so both parts (and a dry run) take the same one.
 // Dgrad part: dy -> dact, the gradient arriving at the activation.  Group-local route: dact may stay pending (the norm part adds
 // the slices up); else, with the gradient at the GroupNorm's own resolution, the launch gathers the backward sums in its epilogue.
-static int conv_gn_dgrad(Exec& e, const ConvW& c, const Tensor& dy, GnBwdArgs& g, Tensor& dact) {
+static int conv_gn_dgrad(Exec& e, const ConvW& c, const Tensor& dy, GnBwdArgs& g, Flow& dact) {
   const bool loc = local_gn_bwd(g);
   return dgrad_op(e, c, dy, dact, g.C, (!loc && g.gmode == GB_SAME) ? &g : nullptr, loc);
 }
 // Norm part: dact -> g.dx (allocated by the caller between the two parts, with g.add / add2 / dx2 / csplit as it needs them)
-static int conv_gn_norm(Exec& e, GnBwdArgs& g, Tensor& dact) {
-  g.g = dact.p;
-  return local_gn_bwd(g) ? gn_bwd_local_op(e, g, dact) : gn_bwd_op(e, g);
+static int conv_gn_norm(Exec& e, GnBwdArgs& g, Flow& dact) {
+  g.g = dact.t.p;
+  if (local_gn_bwd(g)) return gn_bwd_local_op(e, g, dact);
+  ISHAP_REQUIRE(!dact.pending(), "the full-map GroupNorm backward reads a gradient that is still the split-K slices of its dgrad");
+  return gn_bwd_op(e, g);
 }
 // both parts with the plain result between them: dx (its shape set by the caller) is allocated here
 static int conv_gn_backward(Exec& e, const ConvW& c, const Tensor& dy, GnBwdArgs g, Tensor& dx) {
-  Tensor dact;
+  Flow dact;
   ISHAP_TRY(conv_gn_dgrad(e, c, dy, g, dact));
   ISHAP_ALLOC(dx.p, e, dx.numel());
   g.dx = dx.p;
@@ -81,7 +88,7 @@ static int res_backward(Exec& e, const ResL& L, const ResSaved& sv, const Tensor
   const Tensor& h1 = sv.h1;
   ISHAP_REQUIRE(dy.C == L.cout && dy.H == h1.H && dy.N == x.N, "ResBlock gradient shape");
   // out_layers: conv2 <- SiLU <- FiLM <- GN2
-  Tensor dh1 = h1;
+  Tensor dh1 = shaped(h1);
   GnBwdArgs g2;
   g2.x = h1.p; g2.stats = sv.stats2; g2.gamma = L.n2.gamma; g2.beta = L.n2.beta;
   g2.emb = k.film + L.emb_off; g2.emb_ld = k.film_ld;
@@ -92,27 +99,21 @@ static int res_backward(Exec& e, const ResL& L, const ResSaved& sv, const Tensor
   g1.x = x.p; g1.stats = sv.stats1; g1.gamma = L.n1.gamma; g1.beta = L.n1.beta;
   g1.N = x.N; g1.H = x.H; g1.W = x.W; g1.C = L.cin; g1.film = 0; g1.act = 1;
   g1.gmode = L.down ? GB_UNPOOL : (L.up ? GB_SUM4 : GB_SAME);
-  Tensor da;
+  Flow da;
   ISHAP_TRY(conv_gn_dgrad(e, L.c1, dh1, g1, da));
   const half_t* add = dy.p;     // identity skip: gradient of `x_upd(x)` (unet.py:241,256)
   if (L.has_skip) {
     Tensor dxs;
-    ISHAP_TRY(dgrad_op(e, L.skip, dy, dxs, L.cin));
+    ISHAP_TRY(dgrad_tensor(e, L.skip, dy, dxs, L.cin, "the sum with the skip convolution's input gradient"));
     add = dxs.p;
   }
-  dx = x;
+  dx = shaped(x, split);        // split 0: all of x's channels
+  ISHAP_ALLOC(dx.p, e, dx.numel());
   if (split > 0) {
-    dx.C = split;
-    *dx2 = x;
-    dx2->C = x.C - split;
-    dx2->sums = nullptr;
-    ISHAP_ALLOC(dx.p, e, dx.numel());
+    *dx2 = shaped(x, x.C - split);
     ISHAP_ALLOC(dx2->p, e, dx2->numel());
     g1.dx2 = dx2->p; g1.csplit = split;
-  } else {
-    ISHAP_ALLOC(dx.p, e, x.numel());
   }
-  dx.sums = nullptr;
   g1.add = add; g1.dx = dx.p; g1.add2 = add2;
   return conv_gn_norm(e, g1, da);
 }
@@ -123,7 +124,7 @@ static int attn_backward(Exec& e, const AttnL& L, const AttnSaved& sv, const Ten
   const int N = x.N, T = x.H * x.W, C = L.C, heads = L.heads, d = C / heads;
   const float alpha = 1.f / sqrtf((float)d);
   Tensor dA;
-  ISHAP_TRY(dgrad_op(e, L.proj, dy, dA, C));
+  ISHAP_TRY(dgrad_tensor(e, L.proj, dy, dA, C, "the attention backward"));
   Tensor dqkv{nullptr, N, x.H, x.W, 3 * C};
   ISHAP_ALLOC(dqkv.p, e, dqkv.numel());
   const size_t d_need = (size_t)N * heads * T;
@@ -132,7 +133,7 @@ static int attn_backward(Exec& e, const AttnL& L, const AttnSaved& sv, const Ten
   ga.qkv = sv.qkv.p; ga.out = sv.a.p; ga.dout = dA.p; ga.dqkv = dqkv.p; ga.lse = sv.lse; ga.Dbuf = u->attn_D;
   ga.N = N; ga.T = T; ga.C = C; ga.heads = heads; ga.d = d; ga.alpha = alpha; ga.xcd_map = attn_xcd_setting();
   ISHAP_TRY(e.launch([ga](hipStream_t s) { return attn_backward_launch(ga, s); }));
-  dx = x;
+  dx = shaped(x);
   GnBwdArgs g;
   g.x = x.p; g.stats = sv.stats; g.gamma = L.n.gamma; g.beta = L.n.beta;
   g.N = N; g.H = x.H; g.W = x.W; g.C = C; g.film = 0; g.act = 0; g.gmode = GB_SAME;
@@ -147,7 +148,7 @@ static int block_backward(Exec& e, BlockL& b, Tensor g, Tensor& out, int split =
     const LayerRef& l = b.layers[i];
     Tensor dx;
     if (l.kind == 0) {
-      ISHAP_TRY(dgrad_op(e, u->stem, g, dx, u->in_pad));
+      ISHAP_TRY(dgrad_tensor(e, u->stem, g, dx, u->in_pad, "the input gradient's read-out"));
     } else if (l.kind == 1) {
       if (i == 0 && split > 0) ISHAP_TRY(res_backward(e, u->res[l.idx], u->kept.res[l.idx], g, dx, split, out2, nullptr));
       else if (i == 0 && add2) { ISHAP_TRY(res_backward(e, u->res[l.idx], u->kept.res[l.idx], g, dx, 0, nullptr, add2)); *add2_done = true; }
@@ -209,13 +210,12 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
     GnBwdArgs a;
     a.x = k.h_final.p; a.stats = k.head_stats; a.gamma = u->head_norm.gamma;
     a.beta = u->head_norm.beta; a.N = N; a.H = S; a.W = S; a.C = u->final_ch; a.act = 1;
-    g = k.h_final;
-    if (dry) g = Tensor{nullptr, N, S, S, u->final_ch};
+    g = Tensor{nullptr, N, S, S, u->final_ch};      // k.h_final's shape (dry runs follow a dry forward of the same batch size)
     ISHAP_TRY(conv_gn_backward(e, u->head, dout, a, g));
   } else {
     F = dry ? n_out - 1 : k.feat;
     ISHAP_REQUIRE(F >= 0, "the last forward had no tap (feat_layer < 0)");
-    g = k.out[u->out_blocks[F].slot];
+    g = shaped(k.out[u->out_blocks[F].slot]);
     g.p = const_cast<half_t*>(cot_tap);
   }
   std::vector<Tensor> skipgrad(n_in);
@@ -223,12 +223,10 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
     BlockL& b = u->out_blocks[i];
     const int Cs = b.skip_ch, Ch = b.cin - Cs;
     ISHAP_REQUIRE(b.layers[0].kind == 1 && Ch % 8 == 0, "an output block starts with a ResBlock on the concatenation");
-    Tensor gh, gs;
     b.gout = g;
-    ISHAP_TRY(block_backward(e, b, g, gh, Ch, &gs));       // the first ResBlock writes d/d[h | skip] as two tensors
-    b.gh = gh; b.gs = gs;
-    skipgrad[n_in - 1 - i] = gs;     // hs.pop() order (unet.py:663)
-    g = gh;
+    ISHAP_TRY(block_backward(e, b, g, b.gh, Ch, &b.gs));   // the first ResBlock writes d/d[h | skip] as two tensors
+    skipgrad[n_in - 1 - i] = b.gs;   // hs.pop() order (unet.py:663)
+    g = b.gh;
     ISHAP_TRY(bwd_mark(u, s, 100 + i, dry));
     // a deferred forward tail starts behind this point: the backward's first (chip-filling) blocks have the GPU to themselves.
     // Default: once the first output block on a map of at most 16 x 16 pixels has been differentiated (the real model: after
@@ -246,10 +244,8 @@ int unet_backward_impl(ishap_unet* u, const half_t* cot_tap, const void* cot_out
   // gradient itself; `pending` is the addend still owed when that was not possible.
   auto run = [&](BlockL& blk, const half_t* owed_next, const half_t*& pending) -> int {
     bool done = false;
-    Tensor o;
     blk.gout = g;
-    ISHAP_TRY(block_backward(e, blk, g, o, 0, nullptr, owed_next, &done));
-    g = o;
+    ISHAP_TRY(block_backward(e, blk, g, g, 0, nullptr, owed_next, &done));
     pending = (owed_next && !done) ? owed_next : nullptr;
     return 0;
   };

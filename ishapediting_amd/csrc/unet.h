@@ -8,20 +8,38 @@
 #include "../../include/ishap.h"
 #include "common.h"
 
+// A finished activation, or the buffer it will be in once the op being built has run.  Everything kept for later readers is one.
 struct Tensor {
   half_t* p = nullptr;
   int N = 0, H = 0, W = 0, C = 0;
   long long* sums = nullptr;   // [N][C][2] per-channel (sum, sum of squares), fixed point, gathered by the producer; or null
-  // a skip concatenation that has not been materialised yet: p is the buffer the first consumer (the ResBlock's GroupNorm
-  // pass) fills while it reads the two halves (cat_a: first cat_ca channels with sums cat_sa; cat_b: the rest, sums cat_sb)
-  const half_t* cat_a = nullptr; const half_t* cat_b = nullptr; const long long* cat_sa = nullptr; const long long* cat_sb = nullptr;
-  int cat_ca = 0;
-  // the tensor is still the split-K slices of its producing convolution (common.h SlabSrc): `p` is where the fp16 values go
-  // once the next GroupNorm pass (or slab_materialize) has added them up; cat_pend: the same for cat_a of a lazy concatenation
-  SlabSrc pend, cat_pend;
   long long rows() const { return (long long)N * H * W; }
   long long numel() const { return rows() * C; }
 };
+// a tensor of t's shape, with C channels when given: no buffer, no sums (new tensors are made from shapes, never from copies)
+inline Tensor shaped(const Tensor& t, int C = 0) { return Tensor{nullptr, t.N, t.H, t.W, C > 0 ? C : t.C}; }
+
+// a skip concatenation nobody has written yet: the first consumer (the ResBlock's GroupNorm pass) fills the Flow's t.p while it
+// reads the two halves (a: the first ca channels, with the sums sa; b: the rest, with the sums sb)
+struct LazyCat { const half_t *a = nullptr, *b = nullptr; const long long *sa = nullptr, *sb = nullptr; int ca = 0; };
+// The value that walks from layer to layer: a Tensor plus the state that exists only between a producer and its first consumer.
+// Read t's shape and allocate its buffer freely; t as a VALUE leaves a Flow through finished() or filled_by_next_gn() only.
+struct Flow {
+  Tensor t;
+  // t is still the split-K slices of its producer (common.h SlabSrc): t.p is where the fp16 values go once the consumer has added
+  // them up; cat_pend: the same for cat.a.  Writers: conv_op (ConvLaunch::pend_out) and the fused 8x8 attention block, no one else
+  SlabSrc pend, cat_pend;
+  LazyCat cat;
+  bool pending() const { return pend.pending() || cat_pend.pending(); }
+  // THE hand-over of the pending source to the one consumer that adds the slices up (gn_local_op, gn_bwd_local_op,
+  // slab_materialize; a lazy concatenation taking over its first half): nothing is pending afterwards
+  SlabSrc take() { const SlabSrc s = cat.a ? cat_pend : pend; pend = cat_pend = SlabSrc{}; return s; }
+};
+int finished(const Flow& f, const char* who, Tensor& out);   // f as a finished Tensor; fails, naming the reader `who`, otherwise
+// The one exception: a record of f for readers that come only after the next GroupNorm pass (which adds up a pending f, or
+// writes a lazy concatenation into t.p) has run: block outputs and concatenations kept for the backward and the read-outs, the
+// skip stack (read again only after the next block's first GroupNorm), the tap of a plain sequence
+inline Tensor filled_by_next_gn(const Flow& f) { return f.t; }
 
 struct Arena {
   char* base = nullptr;
@@ -59,7 +77,7 @@ struct NormW {
 };
 
 struct ResSaved {   // what the backward pass re-reads
-  Tensor x, h1, xs;     // block input, conv1 output, (pooled / plain) skip input
+  Tensor x, h1;         // block input, conv1 output
   float* stats1 = nullptr;
   float* stats2 = nullptr;
 };
@@ -243,12 +261,12 @@ static inline int aalloc_checked(Exec& e, size_t count, T** out) {
 // One convolution launch (ConvLaunch, common.h): picks split-K and uses the context workspace.  With c.pend_out (the consumer is a
 // group-local GroupNorm pass) a split launch leaves its slices in an arena buffer described by *c.pend_out: no reduce kernel
 int conv_op(Exec& e, const ConvLaunch& c);
-// the launch y = w (*) x with w's bias, gathering the sums y carries; call sites add what else they use
+// the launch y = w (*) x with w's bias, gathering the sums y carries; call sites add what else they use (x: finished data)
 ConvLaunch conv_launch(const Tensor& x, const ConvW& w, const Tensor& y);
 int unet_join_tail(ishap_unet* u, hipStream_t s);
 bool ishap_profile_recording();     // between ishap_profile_begin and ishap_profile_end (igemm.hip)
 bool exec_is_solo(const Exec& e);   // no other stream of this context has work in flight (in-launch rendezvous allowed)
-int slab_materialize(Exec& e, Tensor& t);    // add up a pending tensor with the stand-alone reduce kernel (consumers that cannot)
+int slab_materialize(Exec& e, Flow& f);      // add up a pending flow with the stand-alone reduce kernel (consumers that cannot)
 long long* salloc(Exec& e, size_t count);   // from the stats arena
 int gn_stats_op(Exec& e, const Tensor& x, float* stats);
 

@@ -298,12 +298,18 @@ int conv_op(Exec& e, const ConvLaunch& c) {
   return e.launch([a](hipStream_t s) { return igemm_launch(a, s); });
 }
 
-// A pending tensor whose next consumer cannot add the slices up itself: the stand-alone reduce (bias, residual, fp16).
-int slab_materialize(Exec& e, Tensor& t) {
-  if (!t.pend.pending()) return 0;
-  const SlabSrc p = t.pend;
-  t.pend = SlabSrc{};
-  const IgemmArgs a = igemm_reduce_fill(p, (int)t.rows(), t.C, t.H, t.W, t.p, t.C);
+int finished(const Flow& f, const char* who, Tensor& out) {
+  ISHAP_REQUIRE(!f.pending(), std::string(who) + " reads a tensor that is still the split-K slices of its producer");
+  ISHAP_REQUIRE(f.cat.a == nullptr, std::string(who) + " reads a skip concatenation that nobody has written yet");
+  out = f.t;
+  return 0;
+}
+
+// A pending flow whose next consumer cannot add the slices up itself: the stand-alone reduce (bias, residual, fp16).
+int slab_materialize(Exec& e, Flow& f) {
+  if (!f.pending()) return 0;
+  ISHAP_REQUIRE(f.cat.a == nullptr, "only the group-local GroupNorm pass adds up the pending half of a lazy concatenation");
+  const IgemmArgs a = igemm_reduce_fill(f.take(), (int)f.t.rows(), f.t.C, f.t.H, f.t.W, f.t.p, f.t.C);
   return e.launch([a](hipStream_t s) { return igemm_reduce_launch(a, s); });
 }
 
@@ -317,12 +323,10 @@ int gn_stats_op(Exec& e, const Tensor& x, float* stats) {
 
 // The GroupNorm pass `g` on a small map: one group-local launch that also adds up `x` when it is still pending (and its first
 // half when x is a lazy skip concatenation), see norm_local.hip
-static int gn_local_op(Exec& e, Tensor& x, const GnApplyArgs& g) {
-  const SlabSrc slab = x.cat_a ? x.cat_pend : x.pend;
-  x.pend = SlabSrc{};
-  x.cat_pend = SlabSrc{};
+static int gn_local_op(Exec& e, Flow& x, const GnApplyArgs& g) {
+  const SlabSrc slab = x.take();
   long long* rec = nullptr;
-  ISHAP_SALLOC(rec, e, (size_t)x.N * 32 * GN_REC_STRIDE);       // zeroed with the statistics arena at the start of the forward
+  ISHAP_SALLOC(rec, e, (size_t)x.t.N * 32 * GN_REC_STRIDE);     // zeroed with the statistics arena at the start of the forward
   // several workgroups per group rendezvous inside the launch: only while this launch sequence is the context's only one
   // (beside an overlapped forward tail two half-resident rendezvous grids could wait on each other's compute units)
   const GnLocalArgs a = gn_local_fill(g, slab, exec_is_solo(e) ? reinterpret_cast<unsigned long long*>(rec) : nullptr);
@@ -330,156 +334,146 @@ static int gn_local_op(Exec& e, Tensor& x, const GnApplyArgs& g) {
 }
 
 // out = act(film(GN(x))) (+ 2x2 pool with the pooled raw input in xpool | the head's hi/lo split); `stats` receives (mean, rstd)
-// for the backward pass; emb: the FiLM row (null without film).  x may be pending or a lazy skip concatenation.  Route: a small
-// map takes ONE group-local launch; else pending slices are added up by the stand-alone reduce, the statistics pass runs unless
-// the producer (or the two producers of a lazy concatenation) gathered the sums, and the apply kernel finalises those sums into
-// `stats` itself.  The split form has no group-local kernel (the head's map is full-size in the real model anyway).
-static int gn_forward_op(Exec& e, Tensor& x, const NormW& nw, half_t* out, half_t* xpool, float* stats, const float* emb,
+// for the backward pass; emb: the FiLM row (null without film).  THE forward consumer of a Flow: f may be pending or a lazy skip
+// concatenation and is finished once this pass has run.  Route: a small map takes ONE group-local launch; else pending slices are
+// added up by the stand-alone reduce, the statistics pass runs unless the producer(s) gathered the sums, and the apply kernel
+// finalises those sums into `stats` itself.  The split form has no group-local kernel (the head's map is full-size anyway).
+static int gn_forward_op(Exec& e, Flow& f, const NormW& nw, half_t* out, half_t* xpool, float* stats, const float* emb,
                          int film, int act, int pool, int split = 0) {
-  const bool lazy_cat = x.cat_a != nullptr;
+  const Tensor& x = f.t;
+  const LazyCat cat = f.cat;
+  const bool lazy_cat = cat.a != nullptr;
   GnApplyArgs g;
   g.x = x.p; g.out = out; g.xpool = xpool; g.stats_out = stats;
   g.gamma = nw.gamma; g.beta = nw.beta; g.emb = emb; g.emb_ld = emb ? e.u->kept.film_ld : 0;
   g.N = x.N; g.H = x.H; g.W = x.W; g.C = x.C; g.film = film; g.act = act; g.pool = pool; g.split = split;
-  if (lazy_cat) { g.x = x.cat_a; g.x2 = x.cat_b; g.csplit = x.cat_ca; g.xcopy = x.p; }
-  if (!split && local_gn(x.H * x.W, x.C)) return gn_local_op(e, x, g);
-  ISHAP_REQUIRE(!lazy_cat || (x.cat_sa && x.cat_sb), "a lazy concatenation on a large map carries the producers' sums");
-  ISHAP_TRY(slab_materialize(e, x));
+  if (lazy_cat) { g.x = cat.a; g.x2 = cat.b; g.csplit = cat.ca; g.xcopy = x.p; }
+  const bool local = !split && local_gn(x.H * x.W, x.C);
+  ISHAP_REQUIRE(local || !lazy_cat || (cat.sa && cat.sb), "a lazy concatenation on a large map carries the producers' sums");
+  ISHAP_TRY(local ? gn_local_op(e, f, g) : slab_materialize(e, f));
+  f.cat = LazyCat{};           // either route writes the concatenation into x.p as it goes
+  if (local) return 0;
   const bool summed = x.sums || lazy_cat;
   if (!summed) ISHAP_TRY(gn_stats_op(e, x, stats));
   g.stats = stats; g.sums = x.sums;
-  if (lazy_cat) { g.sums = x.cat_sa; g.sums2 = x.cat_sb; }
+  if (lazy_cat) { g.sums = cat.sa; g.sums2 = cat.sb; }
   if (!summed) g.stats_out = nullptr;
   return e.launch([g](hipStream_t s) { return gn_apply_launch(g, s); });
 }
 
-static int res_forward(Exec& e, const ResL& L, ResSaved& sv, Tensor x, Tensor& y) {
+static int res_forward(Exec& e, const ResL& L, ResSaved& sv, Flow x, Flow& y) {
   ishap_unet* u = e.u;
-  const int N = x.N, H = x.H, W = x.W;
+  const int N = x.t.N, H = x.t.H, W = x.t.W;
   const int Ho = L.down ? H / 2 : (L.up ? H * 2 : H), Wo = L.down ? W / 2 : (L.up ? W * 2 : W);
-  ISHAP_REQUIRE(x.C == L.cin, "ResBlock input channels");
+  ISHAP_REQUIRE(x.t.C == L.cin, "ResBlock input channels");
   float* st1 = nullptr; ISHAP_ALLOC(st1, e, (size_t)N * 64);
   float* st2 = nullptr; ISHAP_ALLOC(st2, e, (size_t)N * 64);
-  const bool lazy_cat = x.cat_a != nullptr;
-  ISHAP_REQUIRE(!lazy_cat || (!L.down && !L.up), "a skip concatenation feeds a plain ResBlock");
+  ISHAP_REQUIRE(x.cat.a == nullptr || (!L.down && !L.up), "a skip concatenation feeds a plain ResBlock");
   const bool loc_out = local_gn(Ho * Wo, L.cout);     // conv1 may then leave its split-K slices to the second GroupNorm
   const bool nosum_out = small_map(Ho * Wo);      // the consumers of an activation on a small map gather their own statistics
   Tensor a{nullptr, N, L.down ? Ho : H, L.down ? Wo : W, L.cin};
   ISHAP_ALLOC(a.p, e, a.numel());
-  Tensor xs = x;
-  xs.pend = SlabSrc{}; xs.cat_pend = SlabSrc{};
+  Tensor xs = filled_by_next_gn(x);      // the skip path reads x after the pass below -- or the pooled x that pass writes
   if (L.down) { xs = a; ISHAP_ALLOC(xs.p, e, a.numel()); }
   ISHAP_TRY(gn_forward_op(e, x, L.n1, a.p, L.down ? xs.p : nullptr, st1, nullptr, 0, 1, L.down));
-  Tensor h1{nullptr, N, Ho, Wo, L.cout};
-  ISHAP_ALLOC(h1.p, e, h1.numel());
-  if (!nosum_out) ISHAP_SALLOC(h1.sums, e, (size_t)N * L.cout * 2);
-  Tensor c = h1;
-  c.pend = SlabSrc{};
-  ISHAP_ALLOC(c.p, e, h1.numel());
-  ConvLaunch k1 = conv_launch(a, L.c1, h1);
+  Flow h1{Tensor{nullptr, N, Ho, Wo, L.cout}};
+  ISHAP_ALLOC(h1.t.p, e, h1.t.numel());
+  if (!nosum_out) ISHAP_SALLOC(h1.t.sums, e, (size_t)N * L.cout * 2);
+  Tensor c = shaped(h1.t);
+  ISHAP_ALLOC(c.p, e, c.numel());
+  ConvLaunch k1 = conv_launch(a, L.c1, h1.t);
   k1.ups = L.up; k1.pend_out = loc_out ? &h1.pend : nullptr;
   ISHAP_TRY(conv_op(e, k1));
   ISHAP_TRY(gn_forward_op(e, h1, L.n2, c.p, nullptr, st2, u->kept.film + L.emb_off, 1, 1, 0));
-  y = h1;
-  y.pend = SlabSrc{};
-  ISHAP_ALLOC(y.p, e, h1.numel());
-  y.sums = nullptr;
-  if (!nosum_out) ISHAP_SALLOC(y.sums, e, (size_t)N * L.cout * 2);
+  y = Flow{shaped(h1.t)};
+  ISHAP_ALLOC(y.t.p, e, y.t.numel());
+  if (!nosum_out) ISHAP_SALLOC(y.t.sums, e, (size_t)N * L.cout * 2);
   // the block output's next reader is always a GroupNorm pass (the next ResBlock's, an attention block's, the head's):
   // on a small map it may stay pending
   SlabSrc* ypend = small_map(Ho * Wo) ? &y.pend : nullptr;
-  ConvLaunch k2 = conv_launch(c, L.c2, y);
+  ConvLaunch k2 = conv_launch(c, L.c2, y.t);
   if (L.has_skip && L.c2.cat) {
     // y = conv2(c) + skip(x) as ONE launch: the 1x1 skip convolution is L.cin more K columns read from x
     k2.Wt = L.c2.cat; k2.ldw = L.c2.cat_ld; k2.X2 = xs.p; k2.ldx2 = L.cin; k2.K2 = L.skip.kpad; k2.bias2 = L.skip.bias;
     k2.pend_out = ypend;
   } else if (L.has_skip) {
-    ConvLaunch ks = conv_launch(xs, L.skip, y);
+    ConvLaunch ks = conv_launch(xs, L.skip, y.t);
     ks.stat_out = nullptr;              // y is complete, and its sums gathered, only after conv2 below
     ISHAP_TRY(conv_op(e, ks));
-    k2.res = y.p; k2.ldr = L.cout;
+    k2.res = y.t.p; k2.ldr = L.cout;
   } else {
     k2.res = xs.p; k2.ldr = L.cin; k2.res_ups = L.up; k2.pend_out = ypend;
   }
   ISHAP_TRY(conv_op(e, k2));
-  h1.pend = SlabSrc{};
-  x.pend = SlabSrc{}; x.cat_pend = SlabSrc{};
-  sv = ResSaved{x, h1, xs, st1, st2};
-  return 0;
+  sv.stats1 = st1; sv.stats2 = st2;
+  ISHAP_TRY(finished(x, "the record of a ResBlock's input", sv.x));
+  return finished(h1, "the record of a ResBlock's conv1 output", sv.h1);
 }
 
-static int attn_forward(Exec& e, const AttnL& L, AttnSaved& sv, Tensor x, Tensor& y) {
-  const int N = x.N, T = x.H * x.W, C = L.C, heads = L.heads, d = C / heads;
-  ISHAP_REQUIRE(x.C == C, "attention channels");
+static int attn_forward(Exec& e, const AttnL& L, AttnSaved& sv, Flow in, Flow& y) {
+  const int N = in.t.N, T = in.t.H * in.t.W, C = L.C, heads = L.heads, d = C / heads;
+  ISHAP_REQUIRE(in.t.C == C, "attention channels");
   ISHAP_REQUIRE(d % 32 == 0, "head width must be a multiple of 32");
   float* st = nullptr; ISHAP_ALLOC(st, e, (size_t)N * 64);
   float* lse = nullptr; ISHAP_ALLOC(lse, e, (size_t)N * heads * T);
-  Tensor nrm = x;
-  nrm.pend = SlabSrc{};
-  ISHAP_ALLOC(nrm.p, e, x.numel());
-  ISHAP_TRY(gn_forward_op(e, x, L.n, nrm.p, nullptr, st, nullptr, 0, 0, 0));
+  Tensor nrm = shaped(in.t);
+  ISHAP_ALLOC(nrm.p, e, nrm.numel());
+  ISHAP_TRY(gn_forward_op(e, in, L.n, nrm.p, nullptr, st, nullptr, 0, 0, 0));
+  Tensor x;                             // the residual and the backward read the input the pass above completed
+  ISHAP_TRY(finished(in, "the attention block's residual", x));
   Tensor qkv{nullptr, N, x.H, x.W, 3 * C};
   ISHAP_ALLOC(qkv.p, e, qkv.numel());
+  Tensor a = shaped(x);                 // ahead of the plain route's qkv conv_op, which allocates nothing (no pend_out): the arena order holds
+  ISHAP_ALLOC(a.p, e, a.numel());
+  sv = AttnSaved{x, qkv, a, st, lse};
   if (attn8_applicable(N, T, C, d) && L.qkv.kpad == C && L.proj.kpad == C && small_map(T)) {
     // 8x8 map: qkv GEMM + attention + proj_out in ONE launch (attention.hip, attn8_fused_kernel); proj_out leaves as per-head
     // K slices that the next GroupNorm pass adds up with its bias and the residual x (ISHAP_ATTN8=1).  The route depends on the
     // shape only: a sequence without the rendezvous tenancy (a second context, the deferred forward tail's replay) makes the same
     // allocations and runs the same kernel as two launches -- the same bits (round 6)
-    Tensor a = x;
-    ISHAP_ALLOC(a.p, e, x.numel());
-    float* slices = nullptr;
-    ISHAP_ALLOC(slices, e, (size_t)heads * N * T * C);
-    long long* fl = nullptr;
-    ISHAP_SALLOC(fl, e, (size_t)N * heads * 8);                  // 16 flags of 4 bytes per (image, head), zeroed with the statistics arena
-    y = x;
-    y.pend = SlabSrc{};
-    ISHAP_ALLOC(y.p, e, x.numel());
-    y.sums = nullptr;
+    float* slices = nullptr; ISHAP_ALLOC(slices, e, (size_t)heads * N * T * C);
+    long long* fl = nullptr; ISHAP_SALLOC(fl, e, (size_t)N * heads * 8);   // 16 flags of 4 bytes per (image, head), zeroed with the statistics arena
+    y = Flow{shaped(x)};
+    ISHAP_ALLOC(y.t.p, e, x.numel());
     y.pend.ws = slices; y.pend.nslab = heads; y.pend.zstride = (long long)N * T * C;
     y.pend.bias = L.proj.bias; y.pend.res = x.p; y.pend.ldr = C;
     Attn8Args g;
     g.xn = nrm.p; g.wqkv = L.qkv.w; g.bqkv = L.qkv.bias; g.wproj = L.proj.w; g.qkv = qkv.p; g.aout = a.p; g.lse = lse;
     g.slices = slices; g.flags = reinterpret_cast<unsigned*>(fl);
     g.N = N; g.C = C; g.heads = heads; g.alpha = 1.f / sqrtf((float)d);
-    ISHAP_TRY(e.launch([g, solo = exec_is_solo(e)](hipStream_t s) mutable {
+    return e.launch([g, solo = exec_is_solo(e)](hipStream_t s) mutable {
       g.status = ishap_status_word();        // looked up at the launch: a dry run allocates nothing
       ISHAP_REQUIRE(g.status != nullptr, "device status word");
       return attn8_fused_launch(g, s, solo);
-    }));
-    sv = AttnSaved{x, qkv, a, st, lse};
-    return 0;
+    });
   }
   ISHAP_TRY(conv_op(e, conv_launch(nrm, L.qkv, qkv)));
-  Tensor a = x;
-  ISHAP_ALLOC(a.p, e, x.numel());
   // fused flash-style attention: w = softmax((q*s)^T (k*s)), a = w v   (unet.py:347-353)
   AttnArgs g;
   g.qkv = qkv.p; g.out = a.p; g.lse = lse; g.N = N; g.T = T; g.C = C; g.heads = heads; g.d = d;
   g.alpha = 1.f / sqrtf((float)d);
   g.xcd_map = attn_xcd_setting();
   ISHAP_TRY(e.launch([g](hipStream_t s) { return attn_forward_launch(g, s); }));
-  y = x;
-  y.pend = SlabSrc{};
-  ISHAP_ALLOC(y.p, e, x.numel());
-  y.sums = nullptr;
+  y = Flow{shaped(x)};
+  ISHAP_ALLOC(y.t.p, e, x.numel());
   const bool nosum = small_map(T);
-  if (!nosum) ISHAP_SALLOC(y.sums, e, (size_t)N * C * 2);
-  ConvLaunch kp = conv_launch(a, L.proj, y);
+  if (!nosum) ISHAP_SALLOC(y.t.sums, e, (size_t)N * C * 2);
+  ConvLaunch kp = conv_launch(a, L.proj, y.t);
   kp.res = x.p; kp.ldr = C; kp.pend_out = nosum ? &y.pend : nullptr;
-  ISHAP_TRY(conv_op(e, kp));
-  sv = AttnSaved{x, qkv, a, st, lse};
-  return 0;
+  return conv_op(e, kp);
 }
 
-static int block_forward(Exec& e, BlockL& b, Tensor h, Tensor& out) {
+static int block_forward(Exec& e, BlockL& b, Flow h, Flow& out) {
   ishap_unet* u = e.u;
   for (auto& l : b.layers) {
-    Tensor y;
+    Flow y;
     if (l.kind == 0) {
-      y = Tensor{nullptr, h.N, h.H, h.W, u->stem.cout};
-      ISHAP_ALLOC(y.p, e, y.numel());
-      if (!small_map(h.H * h.W)) ISHAP_SALLOC(y.sums, e, (size_t)h.N * u->stem.cout * 2);
-      ISHAP_TRY(conv_op(e, conv_launch(h, u->stem, y)));
+      Tensor x;
+      ISHAP_TRY(finished(h, "the stem convolution", x));
+      y.t = shaped(x, u->stem.cout);
+      ISHAP_ALLOC(y.t.p, e, y.t.numel());
+      if (!small_map(x.H * x.W)) ISHAP_SALLOC(y.t.sums, e, (size_t)x.N * u->stem.cout * 2);
+      ISHAP_TRY(conv_op(e, conv_launch(x, u->stem, y.t)));
     } else if (l.kind == 1) {
       ISHAP_TRY(res_forward(e, u->res[l.idx], u->kept.res[l.idx], h, y));
     } else {
@@ -488,8 +482,7 @@ static int block_forward(Exec& e, BlockL& b, Tensor h, Tensor& out) {
     h = y;
   }
   out = h;
-  u->kept.out[b.slot] = h;        // what later readers see: by then the next GroupNorm pass has added up a pending output
-  u->kept.out[b.slot].pend = SlabSrc{};
+  u->kept.out[b.slot] = filled_by_next_gn(h);
   return 0;
 }
 
@@ -516,48 +509,48 @@ static void tail_exec(Exec& e, ishap_unet* u) {
 }
 
 // output blocks [i0, i1): skip concatenation + block (gd/unet.py:661-664); records the tap after block `feat_layer`
-static int out_blocks_range(Exec& e, ishap_unet* u, size_t i0, size_t i1, Tensor& h, std::vector<Tensor>& hs, int feat_layer) {
+static int out_blocks_range(Exec& e, ishap_unet* u, size_t i0, size_t i1, Flow& h, std::vector<Tensor>& hs, int feat_layer) {
   for (size_t i = i0; i < i1; ++i) {
     BlockL& b = u->out_blocks[i];
-    Tensor skip = hs.back();
+    const Tensor skip = hs.back();
     hs.pop_back();
-    Tensor cat{nullptr, h.N, h.H, h.W, h.C + skip.C};
-    ISHAP_REQUIRE(skip.H == h.H && cat.C == b.cin, "skip connection shape");
-    ISHAP_ALLOC(cat.p, e, cat.numel());
+    Flow cat{shaped(h.t, h.t.C + skip.C)};
+    Tensor& c = cat.t;
+    ISHAP_REQUIRE(skip.H == c.H && c.C == b.cin, "skip connection shape");
+    ISHAP_ALLOC(c.p, e, c.numel());
     const bool first_is_res = b.layers[0].kind == 1;
-    if (first_is_res && local_gn(h.H * h.W, cat.C)) {
+    if (first_is_res && local_gn(c.H * c.W, c.C)) {
       // no copy pass: the ResBlock's first (group-local) GroupNorm reads both halves -- adding up h if it is still
       // pending -- and writes the concatenation as it goes
-      cat.cat_a = h.p; cat.cat_b = skip.p; cat.cat_ca = h.C; cat.cat_pend = h.pend;
-    } else if (first_is_res && h.sums && skip.sums && h.C % 8 == 0) {
-      cat.cat_a = h.p; cat.cat_b = skip.p; cat.cat_sa = h.sums; cat.cat_sb = skip.sums; cat.cat_ca = h.C;
+      cat.cat = LazyCat{h.t.p, skip.p, nullptr, nullptr, h.t.C};
+      cat.cat_pend = h.take();
     } else {
       ISHAP_TRY(slab_materialize(e, h));
-      cat.sums = (h.sums && skip.sums) ? salloc(e, (size_t)cat.N * cat.C * 2) : nullptr;
-      ISHAP_TRY(e.launch([=](hipStream_t s) { return concat2(h.p, skip.p, cat.p, cat.rows(), h.C, skip.C, s, h.sums, skip.sums, cat.sums, cat.N); }));
+      Tensor a;
+      ISHAP_TRY(finished(h, "the skip concatenation of a large map", a));
+      if (first_is_res && a.sums && skip.sums && a.C % 8 == 0) {
+        cat.cat = LazyCat{a.p, skip.p, a.sums, skip.sums, a.C};     // no copy pass either: the apply kernel reads both halves and their sums
+      } else {
+        c.sums = (a.sums && skip.sums) ? salloc(e, (size_t)c.N * c.C * 2) : nullptr;
+        ISHAP_TRY(e.launch([=](hipStream_t s) { return concat2(a.p, skip.p, c.p, c.rows(), a.C, skip.C, s, a.sums, skip.sums, c.sums, c.N); }));
+      }
     }
-    u->kept.cat[b.slot] = cat;
-    u->kept.cat[b.slot].cat_pend = SlabSrc{};
-    Tensor y;
-    ISHAP_TRY(block_forward(e, b, cat, y));
-    h = y;
-    if ((int)i == feat_layer) {
-      u->kept.tap = h;
-      u->kept.tap.pend = SlabSrc{};
-    }
+    u->kept.cat[b.slot] = filled_by_next_gn(cat);
+    ISHAP_TRY(block_forward(e, b, cat, h));
+    if ((int)i == feat_layer) u->kept.tap = filled_by_next_gn(h);
   }
   return 0;
 }
 
 // ---- head in fp32 (unet.py:667-669): GroupNorm, SiLU, 3x3 conv with fp32 weights.  The fp32 products are
 //      formed on the fp16 MFMA from hi/lo splits of both operands (3 partial products, fp32 accumulate). ----
-static int forward_head(Exec& e, ishap_unet* u, Tensor h, int N, float* out) {
+static int forward_head(Exec& e, ishap_unet* u, Flow h, int N, float* out) {
   const int S = u->cfg.image_size;
   ISHAP_ALLOC(u->kept.head_stats, e, (size_t)N * 64);
-  half_t* hsplit = nullptr; ISHAP_ALLOC(hsplit, e, (size_t)h.numel() * 3);
+  half_t* hsplit = nullptr; ISHAP_ALLOC(hsplit, e, (size_t)h.t.numel() * 3);
   ISHAP_TRY(gn_forward_op(e, h, u->head_norm, hsplit, nullptr, u->kept.head_stats, nullptr, 0, 1, 0, 1));
-  u->kept.h_final = h;
-  ConvLaunch c = conv_launch(Tensor{hsplit, N, S, S, 3 * h.C}, u->head, Tensor{nullptr, N, S, S, 0});
+  ISHAP_TRY(finished(h, "the record of the head's input", u->kept.h_final));
+  ConvLaunch c = conv_launch(Tensor{hsplit, N, S, S, 3 * h.t.C}, u->head, Tensor{nullptr, N, S, S, 0});
   c.out = out; c.out_mode = IG_OUT_NCHW_F32;      // NCHW fp32: no row stride
   return conv_op(e, c);
 }
@@ -653,26 +646,19 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
     }));
   }
   // ---- x: NCHW fp32 -> NHWC fp16 (h = x.type(self.dtype), unet.py:657) ----
-  Tensor h{nullptr, N, S, S, u->in_pad};
-  ISHAP_ALLOC(h.p, e, h.numel());
-  ISHAP_TRY(e.launch([=](hipStream_t s) {
-    return nchw_f32_to_nhwc_f16(x, h.p, N, u->cfg.in_channels, HW, u->in_pad, s, zero_in_convert ? u->stat_base : nullptr,
+  k.x0 = Tensor{nullptr, N, S, S, u->in_pad};
+  ISHAP_ALLOC(k.x0.p, e, k.x0.numel());
+  ISHAP_TRY(e.launch([=, x0 = k.x0.p](hipStream_t s) {
+    return nchw_f32_to_nhwc_f16(x, x0, N, u->cfg.in_channels, HW, u->in_pad, s, zero_in_convert ? u->stat_base : nullptr,
                                 zero_in_convert ? u->stat_cap * sizeof(long long) : 0);
   }));
-  k.x0 = h;
+  Flow h{k.x0};
   std::vector<Tensor> hs;
   for (auto& b : u->in_blocks) {
-    Tensor y;
-    ISHAP_TRY(block_forward(e, b, h, y));
-    h = y;
-    hs.push_back(h);
-    hs.back().pend = SlabSrc{};     // read again only after the next block's first GroupNorm pass has added it up
+    ISHAP_TRY(block_forward(e, b, h, h));
+    hs.push_back(filled_by_next_gn(h));
   }
-  {
-    Tensor y;
-    ISHAP_TRY(block_forward(e, u->mid, h, y));
-    h = y;
-  }
+  ISHAP_TRY(block_forward(e, u->mid, h, h));
   k.tap = Tensor{};
   const size_t n_out = u->out_blocks.size();
   const size_t split = overlap ? (size_t)feat_layer + 1 : n_out;
@@ -681,7 +667,7 @@ int unet_forward_impl(ishap_unet* u, const float* x, const float* ts, int N, int
     // everything after the tap needs only what exists now; whatever the caller enqueues on `s` after this call (loss,
     // backward) needs nothing of what follows: fork
     ISHAP_TRY(slab_materialize(e, h));             // the tap is complete on the caller's stream
-    k.tap = h;
+    ISHAP_TRY(finished(h, "the tap at the fork", k.tap));
     ISHAP_CHECK_HIP(hipEventRecord(u->ev_fork, s));
     // DEFERRED tail (round 5: -2.2 % against a tail enqueued here, at the tap; that form was removed in round 6): the rest is
     // allocated now -- so that the caller's backward gets its scratch above the whole forward -- and its launches are recorded
